@@ -4,13 +4,21 @@ GPU, dropout 0.5, bf16 MFMA operands / fp32 accumulate) on N MI355X.
 
 A "step" is the whole loop body of the reference's sasrec/main.py:143-173 on one batch of 256 sequences per GPU:
 forward (encoder + reconstruction decoder + head classifiers), loss assembly, backward, weight-decay term,
-gradient all-reduce (N > 1), clip_grad_norm_ and Adam -- nothing skipped, dropout on.  `value`: the synthetic ml-1m-shaped id batches
-are resident in HBM before the timed region (a ring of staged batches; per step the host issues one graph launch).  `value_incl_h2d`: the
-same steps fed from HOST int arrays through the trainer's pinned ring (SURVEY 8d counts the id hand-over inside the step): the step's
-first kernel fetches the batch over PCIe.  `ndcg`: a short deterministic training run scored against the reference's recorded NDCG@10 /
-HR@10.  One JSON line on stdout (rank 0).
+gradient all-reduce (N > 1), clip_grad_norm_ and Adam -- nothing skipped, dropout on.  `value` / `ms_per_step`: exactly `--steps` timed
+steps after `--warmup` untimed ones; the synthetic ml-1m-shaped id batches are resident in HBM before the timed region (a ring of staged
+batches; per step the host issues one graph launch).  `--dump-outputs DIR` writes what the last timed step computed (dump_outputs).
+One JSON line on stdout (rank 0).
+
+A plain run measures only that.  `--full` adds the extras, each after the headline steps: `timing`, the median of repeated blocks of
+`--steps` steps; `value_incl_h2d`, the same steps fed from HOST int arrays through the trainer's pinned ring (SURVEY 8d counts the id
+hand-over inside the step: the step's first kernel fetches the batch over PCIe); with N > 1 the other scaling; and on one GPU `ndcg` (a
+short deterministic training run scored against the reference's recorded NDCG@10 / HR@10), `roofline`, `scatter_mode` (the same step
+with the faster, float-atomic table gradients: ADT_ITEM_SORT=0) and `cpu_baseline` (each of the last four can be switched off by its
+--no-* option).
 
     python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full
+    ADT_ITEM_SORT=0 python bench.py ...   # the float-atomic table gradients: faster, but not run-to-run reproducible
     python bench.py --gpus 8 ...          # launches its own 8 ranks (torch.distributed.run, 127.0.0.1) when WORLD_SIZE is unset
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...
     python bench.py --force-dp            # one rank, but through the data-parallel path (1-rank RCCL group, bucketed all-reduce)
@@ -353,20 +361,34 @@ def lce_probe(dev):
         return None
 
 
-def deterministic_leg(args):
-    """The same step with ADT_ITEM_SORT=1 (item / positional table gradients as sorted segmented sums: no float atomics anywhere, two runs of
-    a step give the same bits -- tests/test_hip_model.py::test_step_is_bit_deterministic_with_sorted_item_gradient), in a child process (the
-    library reads the switch once).  Reported beside `value`, never as it."""
+def other_mode_leg(args, sort):
+    """The same step with the other item / positional table gradient (ADT_ITEM_SORT=`sort`; the headline runs the opposite one), in a child
+    process (the library reads the switch once).  Reported beside `value`, never as it."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--precision", args.precision,
-           "--no-cpu-baseline", "--no-ndcg", "--no-roofline"] + (["--no-graph"] if args.no_graph else [])
+           "--full", "--no-cpu-baseline", "--no-ndcg", "--no-roofline"] + (["--no-graph"] if args.no_graph else [])
     try:
-        p = subprocess.run(cmd, env=dict(os.environ, ADT_ITEM_SORT="1"), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+        p = subprocess.run(cmd, env=dict(os.environ, ADT_ITEM_SORT=sort), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
         d = json.loads(p.stdout.strip().splitlines()[-1])
-        return {"env": "ADT_ITEM_SORT=1", "value": d["value"], "ms_per_step": d["ms_per_step"], "value_incl_h2d": d["value_incl_h2d"],
+        return {"env": "ADT_ITEM_SORT=" + sort, "value": d["value"], "ms_per_step": d["ms_per_step"], "value_incl_h2d": d["value_incl_h2d"],
                 "ms_per_step_incl_h2d": d["ms_per_step_incl_h2d"], "blocks": d["timing"]["blocks"]}
     except Exception as e:      # a reported extra: never fails the bench line
-        return {"env": "ADT_ITEM_SORT=1", "error": repr(e)[:200]}
+        return {"env": "ADT_ITEM_SORT=" + sort, "error": repr(e)[:200]}
+
+
+def dump_outputs(path, model, trainer, B, loss):
+    """--dump-outputs: what the last timed step computed, as a caller of the step receives it -- its loss and gradient norm, the updated
+    weights and Adam moments (the flat fp32 buffers: every parameter), and the positive / negative logits of this GPU's B sequences --
+    as path/<name>.npy, float32 (4.8 MB in all).  With the sorted table gradients (main) two runs write the same bits, except
+    the loss scalar, which is summed in float-atomic partial slots and feeds nothing back: it agrees to rounding."""
+    from adt_amd.sasrec.model import WS_POS_LOGITS, WS_NEG_LOGITS
+    os.makedirs(path, exist_ok=True)
+    T = B * CFG["maxlen"]
+    arrays = {"loss": loss.reshape(1), "grad_norm": trainer.grad_norm().reshape(1), "params": model.flat, "adam_m": trainer.m,
+              "adam_v": trainer.v, "pos_logits": model.ws_view(B, WS_POS_LOGITS, 0, T).view(B, CFG["maxlen"]),
+              "neg_logits": model.ws_view(B, WS_NEG_LOGITS, 0, T).view(B, CFG["maxlen"])}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def visible_gpus():
@@ -415,7 +437,11 @@ def main():
                     help="weak: 256 sequences per GPU (global batch 256 N); strong: global batch 256 split over the ranks")
     ap.add_argument("--no-ndcg", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline steps, also measure the extras (module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         have = visible_gpus()                 # from sysfs / the environment: this parent process never touches the HIP runtime
         if have is not None and have < args.gpus and os.environ.get("ADT_DIST_BACKEND", "nccl") == "nccl":
@@ -423,6 +449,11 @@ def main():
         sys.exit(self_launch(args.gpus))
     if args.force_dp:
         os.environ["ADT_FORCE_DP"] = "1"
+    # the timed step is the bit-reproducible one: item / positional table gradients as sorted segmented sums (no float atomics anywhere,
+    # tests/test_hip_model.py::test_step_is_bit_deterministic_with_sorted_item_gradient), so that the same arguments give the same outputs.
+    # With the float-atomic scatters (ADT_ITEM_SORT=0) a few steps turn their rounding noise into lr-sized Adam moves of the weights whose
+    # exact gradient is zero (the key biases), and two runs end up 1e-2 apart.
+    os.environ.setdefault("ADT_ITEM_SORT", "1")
     # stdout carries exactly ONE line, the JSON result: whatever a library prints to fd 1 (RCCL's version banner when the communicator
     # is created) is routed to stderr
     sys.stdout.flush()
@@ -463,17 +494,17 @@ def main():
 
     def blocks(fn, k, min_blocks=5, min_seconds=0.5, max_blocks=200):
         """Blocks of exactly k steps each (every block bracketed like `timed`), at least min_blocks of them and until min_seconds of timed
-        steps have run: returns the per-block seconds.  The figure of the line is the MEDIAN block."""
+        steps have run: returns the per-block seconds.  `timing` (--full) reports the MEDIAN block."""
         fixed = int(os.environ.get("ADT_BENCH_BLOCKS", "0"))      # a fixed block count (tests: the step count must not depend on the clock)
         out = []
         while (len(out) < fixed) if fixed > 0 else (len(out) < min_blocks or (sum(out) < min_seconds and len(out) < max_blocks)):
             out.append(timed(fn, k))
         return out
 
-    def run(scaling):
-        """One complete measurement at `scaling`: every rank draws the same global batches (same seed) and keeps rows [lo, hi); loss
+    def run(scaling, dump=None):
+        """One measurement at `scaling`: every rank draws the same global batches (same seed) and keeps rows [lo, hi); loss
         normalisers are those of the GLOBAL batch, dropout indices are global (b_offset = lo): N ranks compute the step one process would
-        compute on the global batch."""
+        compute on the global batch.  `dump`: the directory the outputs of the last timed step go to (rank 0), before any extra step."""
         GB = CFG["batch"] * (world if scaling == "weak" else 1)      # global batch
         lo, hi = shard_bounds(GB, rank, world)
         B = hi - lo                                                   # this rank's rows of every global batch
@@ -495,13 +526,19 @@ def main():
         torch.cuda.synchronize()
         for i in range(args.warmup):
             tr.step_staged(ring, b_offset=lo)
-        bl = blocks(lambda i: tr.step_staged(ring, b_offset=lo), args.steps)
-        loss = float(tr.loss())
-        # the same steps from HOST int arrays: packed into a slot of the pinned ring, fetched by the step's first kernel / prefetched
-        for i in range(max(3, min(args.warmup, 10))):
-            tr.step(*batches[i % nb], norms=norms[i % nb], b_offset=lo)
-        bl_h = blocks(lambda i: tr.step(*batches[i % nb], norms=norms[i % nb], b_offset=lo), args.steps)
-        return dict(GB=GB, B=B, lo=lo, model=model, tr=tr, batches=batches, bl=bl, bl_h=bl_h, loss=loss)
+        dt = timed(lambda i: tr.step_staged(ring, b_offset=lo), args.steps)
+        loss_t = tr.loss()
+        loss = float(loss_t)
+        if dump and rank == 0:
+            dump_outputs(dump, model, tr, B, loss_t)
+        out = dict(GB=GB, B=B, lo=lo, model=model, tr=tr, batches=batches, dt=dt, loss=loss)
+        if args.full:
+            out["bl"] = blocks(lambda i: tr.step_staged(ring, b_offset=lo), args.steps)
+            # the same steps from HOST int arrays: packed into a slot of the pinned ring, fetched by the step's first kernel / prefetched
+            for i in range(max(3, min(args.warmup, 10))):
+                tr.step(*batches[i % nb], norms=norms[i % nb], b_offset=lo)
+            out["bl_h"] = blocks(lambda i: tr.step(*batches[i % nb], norms=norms[i % nb], b_offset=lo), args.steps)
+        return out
 
     def stats(bl, GB):
         med = sorted(bl)[len(bl) // 2]
@@ -510,43 +547,49 @@ def main():
                 "sequences_per_s": round(GB * args.steps / med, 1)}
 
     main_scaling = args.scaling
-    r = run(main_scaling)
+    r = run(main_scaling, dump=args.dump_outputs)
     other = None
-    if world > 1:      # both scalings in one line: weak (256 sequences per GPU) and strong (the reference's global batch of 256 split over the ranks)
+    if world > 1 and args.full:      # both scalings in one line: weak (256 sequences per GPU) and strong (the reference's global batch of 256 split over the ranks)
         del r["tr"], r["model"]
         torch.cuda.empty_cache()
         other = run("strong" if main_scaling == "weak" else "weak")
     if rank == 0:
-        st, st_h = stats(r["bl"], r["GB"]), stats(r["bl_h"], r["GB"])
-        res = {"metric": "train sequences/sec, SASRec-ADT ml-1m (seq_len=200, d=64, 2 blocks)", "value": st["sequences_per_s"],
+        res = {"metric": "train sequences/sec, SASRec-ADT ml-1m (seq_len=200, d=64, 2 blocks)", "value": round(r["GB"] * args.steps / r["dt"], 1),
                "unit": "sequences/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": st["ms_per_step"], "higher_is_better": True, "scaling": main_scaling, "vs_baseline": None,
+               "ms_per_step": round(r["dt"] / args.steps * 1e3, 4), "higher_is_better": True, "scaling": main_scaling, "vs_baseline": None,
                "dtype": "bf16" if args.precision == "bf16" else "f32", "data": "synthetic",
                "config": {"workload": "SASRec-ADT ml-1m shape, 2 blocks d=64 H=2 seq_len=200, global batch %d (%d sequences on this GPU), dropout 0.5, "
                                       "full train step (fwd+loss+bwd+clip+Adam), ids resident in HBM" % (r["GB"], r["B"]),
                           "global_batch": r["GB"], "seq_len": CFG["maxlen"],
                           "parallelism": "dp%d%s" % (world, ("-rccl" if backend == "nccl" else "-" + backend) if pg is not None else ""),
                           "hip_graph": not args.no_graph and (backend == "nccl" or world == 1),
+                          "table_gradients": "sorted segmented sums, bit-reproducible (ADT_ITEM_SORT=1)" if os.environ["ADT_ITEM_SORT"] != "0"
+                                             else "float-atomic scatters, the library default (ADT_ITEM_SORT=0)",
                           "world_size": dist.get_world_size() if pg is not None else 1,
                           "backend": dist.get_backend() if pg is not None else None},
-               "value_definition": "median of `blocks` blocks of exactly `steps` steps each (barrier + synchronize around every block, MAX over ranks), "
-                                   "id batches resident in HBM; value_incl_h2d = the same from host int arrays through the pinned ring (SURVEY 8d's step)",
-               "timing": st, "loss_last_step": round(r["loss"], 5),
-               "value_incl_h2d": st_h["sequences_per_s"], "ms_per_step_incl_h2d": st_h["ms_per_step"], "timing_incl_h2d": st_h}
+               "value_definition": "exactly `steps` timed steps after `warmup` untimed ones, in one block (barrier + synchronize on both sides, MAX "
+                                   "over ranks), id batches resident in HBM; --full: `timing` = median of `timing.blocks` further blocks of `steps` "
+                                   "steps each, value_incl_h2d = the same from host int arrays through the pinned ring (SURVEY 8d's step)",
+               "loss_last_step": round(r["loss"], 5)}
+        if args.full:
+            st, st_h = stats(r["bl"], r["GB"]), stats(r["bl_h"], r["GB"])
+            res.update({"timing": st, "value_incl_h2d": st_h["sequences_per_s"], "ms_per_step_incl_h2d": st_h["ms_per_step"], "timing_incl_h2d": st_h})
         if other is not None:
             so, so_h = stats(other["bl"], other["GB"]), stats(other["bl_h"], other["GB"])
             res["strong" if main_scaling == "weak" else "weak"] = {
-                "global_batch": other["GB"], "sequences_per_gpu": other["B"], "value": so["sequences_per_s"], "ms_per_step": so["ms_per_step"],
-                "timing": so, "value_incl_h2d": so_h["sequences_per_s"], "ms_per_step_incl_h2d": so_h["ms_per_step"], "loss_last_step": round(other["loss"], 5)}
-        if world == 1 and not args.no_ndcg:
+                "global_batch": other["GB"], "sequences_per_gpu": other["B"], "value": round(other["GB"] * args.steps / other["dt"], 1),
+                "ms_per_step": round(other["dt"] / args.steps * 1e3, 4), "timing": so, "value_incl_h2d": so_h["sequences_per_s"],
+                "ms_per_step_incl_h2d": so_h["ms_per_step"], "loss_last_step": round(other["loss"], 5)}
+        if args.full and world == 1 and not args.no_ndcg:
             res["ndcg"] = ndcg_check(device)
-        if r["B"] == CFG["batch"] and world == 1 and not args.no_roofline:
+        if args.full and r["B"] == CFG["batch"] and world == 1 and not args.no_roofline:
             res["roofline"] = roofline_probe(r["model"], r["tr"], r["B"], st["sequences_per_s"], r["batches"][0])
             res["roofline"]["step"]["incl_h2d"] = {"achieved_GBps": round(st_h["sequences_per_s"] * 2.4e6 / 1e9, 1),
                                                    "frac": round(st_h["sequences_per_s"] * 2.4e6 / 1e9 / HBM_PEAK_GBS, 4)}
-        if world == 1 and not args.no_roofline and not args.force_dp and os.environ.get("ADT_ITEM_SORT", "0") == "0":
-            res["deterministic_mode"] = deterministic_leg(args)
-        if world == 1 and not args.no_cpu_baseline and not args.force_dp:
+        if args.full and world == 1 and not args.no_roofline and not args.force_dp:
+            sort = os.environ["ADT_ITEM_SORT"] != "0"
+            res["scatter_mode" if sort else "deterministic_mode"] = other_mode_leg(args, "0" if sort else "1")
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.force_dp:
             res["cpu_baseline"] = cpu_baseline()
         print(json.dumps(res), file=json_out, flush=True)
     if pg is not None:

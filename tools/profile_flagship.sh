@@ -3,8 +3,9 @@
 # The program sits directly behind `--` (no env / bash -c hop).  Outputs under gpurun_out/r04p/ ; copy the summaries into profiles/.
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && O=gpurun_out/r04p && mkdir -p $O
 SQ="SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU"
-B="python3 bench.py --no-cpu-baseline --no-ndcg"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o p -- $B --steps 50 --warmup 10 > $O/stats_log.txt 2>&1 || exit 1
+export ADT_ITEM_SORT=0       # the profiles/r04_* summaries are of the float-atomic scatter step (bench.py's default is the sorted one)
+B="python3 bench.py --full --no-cpu-baseline --no-ndcg"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o p -- $B --steps 50 --warmup 10 --no-roofline > $O/stats_log.txt 2>&1 || exit 1
 cp $O/stats/p_kernel_stats.csv $O/r04_kernel_stats.csv
 python tools/trace_overlap.py $O/stats/p_kernel_trace.csv -25 > $O/r04_side_stream_timeline.txt
 echo "---- host-fed leg (under the profiler the host is not ahead of the GPU, so the next batch is not published in time for the prefetch and k_step_begin reads the ring over PCIe: 23 us; unprofiled the prefetch hits -- 398 of 400 steps -- and k_step_begin takes 9 us, the two prefetch halves add ~7 us to k_loss_seeds + k_embed_bwd3)" >> $O/r04_side_stream_timeline.txt
