@@ -14,12 +14,22 @@
 // accumulator row in pass B (operands swapped).  The reference's additive -2^32 mask quantises the scores of a fully masked row to
 // multiples of 512 (adt_stosa.cuh: w_score): bit-level agreement of the recomputed scores matters only within one ulp of +-256,
 // +-768, ..., i.e. for squared distances >= 256 sqrt(hd), and the dot product of an MFMA does not depend on which operand is A.
+//
+// MET = WM_KL: the KL-divergence score of adt_klattn.cuh (stosa/modules.py:52-70 with the reference's broadcasts),
+//   x_ij = -(0.5 ((colbias_j - rowbias_i) + X_i . Y_j - hd)) / sqrt(hd),  X_i = [(mq_i - mk_i)^2 | 1/ck_i],  Y_j = [1/ck_j | cq_j],
+//   colbias_j = sum log ck_j, rowbias_i = sum log cq_i:
+// the same one cross term of inner dimension 2 hd, but with two different images.  The resident side holds Y (forward, pass A) or
+// X (pass B) in place of the concatenation and its log-det bias in place of the norm; pass A contracts dW with Y (-> dmq, dmk and the
+// row parts of dck, dcq), pass B with X (-> the column parts of dck, dcq), which the same lane adds to pass A's value in that order.
+// Covered, for both metrics: hd 16 and 32, L <= 128 (MAXKT = 8 tiles of 16 keys); the LDS footprint is wattn_mfma_lds_bytes() for
+// both (about 142 KB in the backward at hd 32 / L 128).
 #pragma once
 #include "adt_stosa.cuh"
 
 namespace adt {
 
 constexpr int WM_NW = 4;
+constexpr int WM_W = 0, WM_KL = 1;      // score of the pair: Wasserstein or KL divergence
 
 template <int HD>
 struct WmShape {
@@ -86,6 +96,81 @@ ADT_DEVICE_INLINE void wm_stage_nat(float* dst, const float* g, int ld, int L, i
   }
 }
 
+// ---- KL images -------------------------------------------------------------------------------------------------------------------
+// sum_d log c[d] of one token in one fixed order: the staged bias of a row and the one a pass computes for a row it owns are one number
+template <int HD>
+ADT_DEVICE_INLINE float wm_kl_logsum(const float* c_row) {
+  float s = 0.f;
+  for (int k = 0; k < HD; ++k) s += logf(c_row[k]);
+  return s;
+}
+
+// the KL row image X (XIMG) = [(qm - km)^2 | 1/kc] or column image Y = [1/kc | qc] of one token, 4 features from 16-byte loads
+template <bool XIMG>
+ADT_DEVICE_INLINE void wm_kl_img4(const float* qm, const float* km, const float* qc, const float* kc, int c4, int HD_, float4& lo, float4& hi) {
+  const float4 k = *reinterpret_cast<const float4*>(kc + c4);
+  const float4 ik = make_float4(1.0f / k.x, 1.0f / k.y, 1.0f / k.z, 1.0f / k.w);
+  if (XIMG) {
+    const float4 q = *reinterpret_cast<const float4*>(qm + c4), m = *reinterpret_cast<const float4*>(km + c4);
+    const float4 d = make_float4(q.x - m.x, q.y - m.y, q.z - m.z, q.w - m.w);
+    lo = make_float4(d.x * d.x, d.y * d.y, d.z * d.z, d.w * d.w);
+    hi = ik;
+  } else {
+    lo = ik;
+    hi = *reinterpret_cast<const float4*>(qc + c4);
+  }
+}
+
+// rows [0, Lp) of the KL image (rows >= L zero) and their log-det biases: X with sum log qc, Y with sum log kc
+template <int HD, bool XIMG>
+ADT_DEVICE_INLINE void wm_kl_stage(float* sImg, float* sBias, const float* qm, int ldqm, const float* km, int ldkm, const float* qc, int ldqc,
+                                   const float* kc, int ldkc, int L, int Lp) {
+  constexpr int RS = WmShape<HD>::RSK, V = HD / 4;
+  for (int i = threadIdx.x; i < Lp * V; i += WM_NW * 64) {
+    const int r = i / V, c4 = (i % V) * 4;
+    float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+    if (r < L) wm_kl_img4<XIMG>(qm + (size_t)r * ldqm, km + (size_t)r * ldkm, qc + (size_t)r * ldqc, kc + (size_t)r * ldkc, c4, HD, lo, hi);
+    *reinterpret_cast<float4*>(sImg + r * RS + c4) = lo;
+    *reinterpret_cast<float4*>(sImg + r * RS + HD + c4) = hi;
+  }
+  for (int r = threadIdx.x; r < Lp; r += WM_NW * 64)
+    sBias[r] = r < L ? wm_kl_logsum<HD>(XIMG ? qc + (size_t)r * ldqc : kc + (size_t)r * ldkc) : 0.f;
+}
+
+// transposed copy dst[k][r] (row stride Lp + 4) of a staged image (call after the barrier that follows wm_kl_stage)
+template <int HD>
+ADT_DEVICE_INLINE void wm_kl_transpose(float* dst, const float* sImg, int Lp) {
+  constexpr int RS = WmShape<HD>::RSK, KC = 2 * HD;
+  const int RST = Lp + 4;
+  for (int i = threadIdx.x; i < Lp * KC; i += WM_NW * 64) {
+    const int k = i / Lp, r = i % Lp;
+    dst[k * RST + r] = sImg[r * RS + k];
+  }
+}
+
+// slots 8g .. 8g+7 of block kb of the KL image of one token straight from global memory (the same arithmetic as wm_kl_stage)
+template <int HD, bool XIMG>
+ADT_DEVICE_INLINE Frag8 wm_kl_frag(const float* qm, const float* km, const float* qc, const float* kc, int kb, int g, bool valid) {
+  Frag8 f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) f.v[j] = 0.f;
+  if (!valid) return f;
+  const int k0 = 32 * kb + 8 * g, c = k0 < HD ? k0 : k0 - HD;
+#pragma unroll
+  for (int h4 = 0; h4 < 2; ++h4) {
+    float4 lo, hi;
+    wm_kl_img4<XIMG>(qm, km, qc, kc, c + 4 * h4, HD, lo, hi);
+    const float4 v = k0 < HD ? lo : hi;
+    f.v[4 * h4 + 0] = v.x; f.v[4 * h4 + 1] = v.y; f.v[4 * h4 + 2] = v.z; f.v[4 * h4 + 3] = v.w;
+  }
+  return f;
+}
+
+// the scaled negative KL divergence from the cross term and the two biases (one expression for the forward and both passes)
+ADT_DEVICE_INLINE float wm_kl_x(float colb, float rowb, float dot, float hd, float rsq_hd) {
+  return -(0.5f * (((colb - rowb) + dot) - hd)) * rsq_hd;
+}
+
 // |m|^2 + sum(S) of one token, by the SAME sequence of fused multiply-adds as wm_stage_cat's LDS loop, so that the norm of a token is the
 // same number whether a pass reads it from the resident side's vector or computes it for the tile it owns
 template <int HD>
@@ -148,14 +233,14 @@ ADT_DEVICE_INLINE float wm_prob(float x, bool masked, bool dead_row, float ref) 
   return __expf(w_score(x, masked, dead_row) - ref);
 }
 
-template <int PREC, int HD, int MAXKT>
+template <int PREC, int HD, int MAXKT, int MET = WM_W>
 __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_fwd(WAttnArgs a) {
   adt_prefetch_kernargs<sizeof(WAttnArgs) <= 512 ? sizeof(WAttnArgs) : 512>();      // every kernarg line in one scalar-cache round trip (adt_common.cuh)
   typedef WmShape<HD> S;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int L = a.L, Lp = (L + 31) / 32 * 32, nt16 = (L + 15) / 16, RST = Lp + 4;
-  float* sK = smem;                          // [Lp][RSK]  [mk | sqrt Sk]
-  float* sNk = sK + Lp * S::RSK;             // [Lp]
+  float* sK = smem;                          // [Lp][RSK]  [mk | sqrt Sk]     (KL: Y = [1/ck | cq])
+  float* sNk = sK + Lp * S::RSK;             // [Lp]                          (KL: column bias sum log ck)
   float* sKv = sNk + Lp;                     // key validity
   float* sDead = sKv + Lp;
   float* sSpare = sDead + Lp;
@@ -167,7 +252,10 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_fwd(WAttnArgs a) {
   for (int i = threadIdx.x; i < Lp; i += WM_NW * 64) sKv[i] = (i < L && a.kid[row_b + i] > 0) ? 1.f : 0.f;
   wm_stage_t<false>(sVmT, a.Vm + row_b * a.ldvm + h * HD, a.ldvm, L, Lp, HD);
   wm_stage_t<false>(sVcT, a.Vc + row_b * a.ldvc + h * HD, a.ldvc, L, Lp, HD);
-  wm_stage_cat<HD>(sK, sNk, a.Km + row_b * a.ldkm + h * HD, a.ldkm, a.Kc + row_b * a.ldkc + h * HD, a.ldkc, L, Lp);
+  if constexpr (MET == WM_KL)
+    wm_kl_stage<HD, false>(sK, sNk, nullptr, 0, nullptr, 0, a.Qc + row_b * a.ldqc + h * HD, a.ldqc, a.Kc + row_b * a.ldkc + h * HD, a.ldkc, L, Lp);
+  else
+    wm_stage_cat<HD>(sK, sNk, a.Km + row_b * a.ldkm + h * HD, a.ldkm, a.Kc + row_b * a.ldkc + h * HD, a.ldkc, L, Lp);
   __syncthreads();
   for (int i = threadIdx.x; i < Lp; i += WM_NW * 64) {
     float cnt = 0.f;
@@ -183,9 +271,18 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_fwd(WAttnArgs a) {
     const float* qm_row = a.Qm + (row_b + (vi ? i : 0)) * a.ldqm + h * HD;
     const float* qc_row = a.Qc + (row_b + (vi ? i : 0)) * a.ldqc + h * HD;
     Frag8 fq[S::KB];
+    float nq;                                  // KL: the row bias sum log cq_i
+    if constexpr (MET == WM_KL) {
+      const float* km_row = a.Km + (row_b + (vi ? i : 0)) * a.ldkm + h * HD;
+      const float* kc_row = a.Kc + (row_b + (vi ? i : 0)) * a.ldkc + h * HD;
 #pragma unroll
-    for (int kb = 0; kb < S::KB; ++kb) fq[kb] = wm_cat_frag<HD>(qm_row, qc_row, kb, g, vi);
-    const float nq = vi ? wm_row_norm<HD>(qm_row, qc_row) : 0.f;
+      for (int kb = 0; kb < S::KB; ++kb) fq[kb] = wm_kl_frag<HD, true>(qm_row, km_row, qc_row, kc_row, kb, g, vi);
+      nq = vi ? wm_kl_logsum<HD>(qc_row) : 0.f;
+    } else {
+#pragma unroll
+      for (int kb = 0; kb < S::KB; ++kb) fq[kb] = wm_cat_frag<HD>(qm_row, qc_row, kb, g, vi);
+      nq = vi ? wm_row_norm<HD>(qm_row, qc_row) : 0.f;
+    }
     const bool dead_i = vi && sDead[i] != 0.f;
     f32x4 s[MAXKT];
     float m = -INFINITY;
@@ -200,7 +297,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_fwd(WAttnArgs a) {
         for (int r = 0; r < 4; ++r) {
           const int j = kt * 16 + 4 * g + r;
           if (j < L) {
-            const float x = -((sNk[j] + nq) - 2.0f * acc[r]) * rsq_hd;
+            const float x = MET == WM_KL ? wm_kl_x(sNk[j], nq, acc[r], (float)HD, rsq_hd) : -((sNk[j] + nq) - 2.0f * acc[r]) * rsq_hd;
             const bool masked = j > i || sKv[j] == 0.f;
             if (!masked || dead_i) {           // masked keys of a live row: exp(x - 2^32 - m) == 0, left at -inf
               s[kt][r] = w_score(x, masked, dead_i);
@@ -271,7 +368,7 @@ ADT_DEVICE_INLINE void wm_pair_bwd(float x, bool masked, bool dead_row, float ls
   dw = -(pr * (dpr - delta)) * rsq_hd;                // d loss / d W_ij
 }
 
-template <int PREC, int HD>
+template <int PREC, int HD, int MET = WM_W>
 __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
   adt_prefetch_kernargs<sizeof(WAttnArgs) <= 512 ? sizeof(WAttnArgs) : 512>();      // every kernarg line in one scalar-cache round trip (adt_common.cuh)
   typedef WmShape<HD> S;
@@ -310,12 +407,18 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
     }
     sDelta[i] = dl;
   }
-  wm_stage_t<false>(sCT, a.Km + row_b * a.ldkm + h * HD, a.ldkm, L, Lp, HD);
-  wm_stage_t<true>(sCT + HD * RST, a.Kc + row_b * a.ldkc + h * HD, a.ldkc, L, Lp, HD);
+  const int co = h * HD;
+  if constexpr (MET == WM_KL) {      // A: Y = [1/ck | cq] rows and column biases; its transpose after the barrier
+    wm_kl_stage<HD, false>(sC, sN, nullptr, 0, nullptr, 0, a.Qc + row_b * a.ldqc + co, a.ldqc, a.Kc + row_b * a.ldkc + co, a.ldkc, L, Lp);
+  } else {
+    wm_stage_t<false>(sCT, a.Km + row_b * a.ldkm + h * HD, a.ldkm, L, Lp, HD);
+    wm_stage_t<true>(sCT + HD * RST, a.Kc + row_b * a.ldkc + h * HD, a.ldkc, L, Lp, HD);
+  }
   wm_stage_nat<HD>(sX0, a.Vm + row_b * a.ldvm + h * HD, a.ldvm, L, Lp);
   wm_stage_nat<HD>(sX1, a.Vc + row_b * a.ldvc + h * HD, a.ldvc, L, Lp);
-  wm_stage_cat<HD>(sC, sN, a.Km + row_b * a.ldkm + h * HD, a.ldkm, a.Kc + row_b * a.ldkc + h * HD, a.ldkc, L, Lp);
+  if constexpr (MET != WM_KL) wm_stage_cat<HD>(sC, sN, a.Km + row_b * a.ldkm + h * HD, a.ldkm, a.Kc + row_b * a.ldkc + h * HD, a.ldkc, L, Lp);
   __syncthreads();
+  if constexpr (MET == WM_KL) wm_kl_transpose<HD>(sCT, sC, Lp);
   for (int i = threadIdx.x; i < Lp; i += WM_NW * 64) {
     float cnt = 0.f;
     for (int j = 0; j <= i && j < L; ++j) cnt += sKv[j];
@@ -329,9 +432,17 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
     const bool vi = i < L;
     const size_t qrow = row_b + (vi ? i : 0);
     Frag8 fq[S::KB], fdm[KBV], fdc[KBV];
+    float nq;
+    if constexpr (MET == WM_KL) {
 #pragma unroll
-    for (int kb = 0; kb < S::KB; ++kb) fq[kb] = wm_cat_frag<HD>(a.Qm + qrow * a.ldqm + h * HD, a.Qc + qrow * a.ldqc + h * HD, kb, g, vi);
-    const float nq = vi ? wm_row_norm<HD>(a.Qm + qrow * a.ldqm + h * HD, a.Qc + qrow * a.ldqc + h * HD) : 0.f;
+      for (int kb = 0; kb < S::KB; ++kb)
+        fq[kb] = wm_kl_frag<HD, true>(a.Qm + qrow * a.ldqm + co, a.Km + qrow * a.ldkm + co, a.Qc + qrow * a.ldqc + co, a.Kc + qrow * a.ldkc + co, kb, g, vi);
+      nq = vi ? wm_kl_logsum<HD>(a.Qc + qrow * a.ldqc + co) : 0.f;
+    } else {
+#pragma unroll
+      for (int kb = 0; kb < S::KB; ++kb) fq[kb] = wm_cat_frag<HD>(a.Qm + qrow * a.ldqm + h * HD, a.Qc + qrow * a.ldqc + h * HD, kb, g, vi);
+      nq = vi ? wm_row_norm<HD>(a.Qm + qrow * a.ldqm + h * HD, a.Qc + qrow * a.ldqc + h * HD) : 0.f;
+    }
 #pragma unroll
     for (int kb = 0; kb < KBV; ++kb) {
       fdm[kb] = frag_contig_hd<HD>(a.dOm + qrow * a.lddom + h * HD, kb, g);
@@ -369,7 +480,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
           for (int r = 0; r < 4; ++r) {
             const int j = kt * 16 + 4 * g + r;
             if (j < L && vi) {
-              const float x = -((sN[j] + nq) - 2.0f * acc[r]) * rsq_hd;
+              const float x = MET == WM_KL ? wm_kl_x(sN[j], nq, acc[r], (float)HD, rsq_hd) : -((sN[j] + nq) - 2.0f * acc[r]) * rsq_hd;
               float dw, pd;
               wm_pair_bwd<HD>(x, j > i || sKv[j] == 0.f, dead_i, lse, ks4[r], gm[r], gc[r], delta, rsq_hd, dw, pd);
               dwt[t][r] = dw;
@@ -383,7 +494,29 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
       for (int ft = 0; ft < S::KC / 16; ++ft) accq[ft] = mma16<PREC>(accq[ft], frag_slotc(sCT + (16 * ft + c) * RST + 32 * kp, g), bdw);
     }
     dwsum = wm_colsum(dwsum);
-    if (vi) {
+    if (MET == WM_KL && vi) {
+      // dmq = (mq - mk) sum_j dW Y1, dmk = -dmq; row parts: dck = -0.5 / ck^2 sum_j dW Y2, dcq = -0.5 / cq sum_j dW
+#pragma unroll
+      for (int ft = 0; ft < S::KC / 16; ++ft) {
+        const int k0 = 16 * ft + 4 * g;
+        const f32x4& acc = accq[ft];
+        if (k0 < HD) {
+          const float4 q = *reinterpret_cast<const float4*>(a.Qm + qrow * a.ldqm + co + k0);
+          const float4 k = *reinterpret_cast<const float4*>(a.Km + qrow * a.ldkm + co + k0);
+          const float4 dq = make_float4((q.x - k.x) * acc[0], (q.y - k.y) * acc[1], (q.z - k.z) * acc[2], (q.w - k.w) * acc[3]);
+          *reinterpret_cast<float4*>(a.dQm + qrow * a.ldd + co + k0) = dq;
+          *reinterpret_cast<float4*>(a.dKm + qrow * a.ldd + co + k0) = make_float4(-dq.x, -dq.y, -dq.z, -dq.w);
+        } else {
+          const int f0 = k0 - HD;
+          const float4 kc = *reinterpret_cast<const float4*>(a.Kc + qrow * a.ldkc + co + f0);
+          const float4 qc = *reinterpret_cast<const float4*>(a.Qc + qrow * a.ldqc + co + f0);
+          *reinterpret_cast<float4*>(a.dKc + qrow * a.ldd + co + f0) =
+              make_float4(-0.5f * acc[0] / (kc.x * kc.x), -0.5f * acc[1] / (kc.y * kc.y), -0.5f * acc[2] / (kc.z * kc.z), -0.5f * acc[3] / (kc.w * kc.w));
+          *reinterpret_cast<float4*>(a.dQc + qrow * a.ldd + co + f0) =
+              make_float4(-0.5f * dwsum / qc.x, -0.5f * dwsum / qc.y, -0.5f * dwsum / qc.z, -0.5f * dwsum / qc.w);
+        }
+      }
+    } else if (vi) {
 #pragma unroll
       for (int ft = 0; ft < S::KC / 16; ++ft) {
         const int k0 = 16 * ft + 4 * g;          // features k0 .. k0+3 of the concatenation
@@ -406,13 +539,22 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
 
   // ---- phase B staging: the query side over the same LDS ------------------------------------------------------------------------------
   __syncthreads();
-  wm_stage_t<false>(sCT, a.Qm + row_b * a.ldqm + h * HD, a.ldqm, L, Lp, HD);
-  wm_stage_t<true>(sCT + HD * RST, a.Qc + row_b * a.ldqc + h * HD, a.ldqc, L, Lp, HD);
+  if constexpr (MET != WM_KL) {
+    wm_stage_t<false>(sCT, a.Qm + row_b * a.ldqm + h * HD, a.ldqm, L, Lp, HD);
+    wm_stage_t<true>(sCT + HD * RST, a.Qc + row_b * a.ldqc + h * HD, a.ldqc, L, Lp, HD);
+  }
   wm_stage_nat<HD>(sX0, a.dOm + row_b * a.lddom + h * HD, a.lddom, L, Lp);
   wm_stage_nat<HD>(sX1, a.dOc + row_b * a.lddoc + h * HD, a.lddoc, L, Lp);
   wm_stage_t<false>(sT0, a.dOm + row_b * a.lddom + h * HD, a.lddom, L, Lp, HD);
   wm_stage_t<false>(sT1, a.dOc + row_b * a.lddoc + h * HD, a.lddoc, L, Lp, HD);
-  wm_stage_cat<HD>(sC, sN, a.Qm + row_b * a.ldqm + h * HD, a.ldqm, a.Qc + row_b * a.ldqc + h * HD, a.ldqc, L, Lp);
+  if constexpr (MET == WM_KL) {      // B: X = [(mq - mk)^2 | 1/ck] rows and row biases; its transpose after the barrier
+    wm_kl_stage<HD, true>(sC, sN, a.Qm + row_b * a.ldqm + co, a.ldqm, a.Km + row_b * a.ldkm + co, a.ldkm, a.Qc + row_b * a.ldqc + co, a.ldqc,
+                          a.Kc + row_b * a.ldkc + co, a.ldkc, L, Lp);
+    __syncthreads();
+    wm_kl_transpose<HD>(sCT, sC, Lp);
+  } else {
+    wm_stage_cat<HD>(sC, sN, a.Qm + row_b * a.ldqm + h * HD, a.ldqm, a.Qc + row_b * a.ldqc + h * HD, a.ldqc, L, Lp);
+  }
   __syncthreads();
 
   // ---- pass B: wave owns key tile kt ; tiles T[query 4g+r][key c] (operands swapped: the QUERY image rows are the A operand) -----------
@@ -421,9 +563,16 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
     const bool vj = j < L;
     const size_t krow = row_b + (vj ? j : 0);
     Frag8 fk[S::KB], fvm[KBV], fvc[KBV];
+    float nk;                                  // KL: the column bias sum log ck_j
+    if constexpr (MET == WM_KL) {
 #pragma unroll
-    for (int kb = 0; kb < S::KB; ++kb) fk[kb] = wm_cat_frag<HD>(a.Km + krow * a.ldkm + h * HD, a.Kc + krow * a.ldkc + h * HD, kb, g, vj);
-    const float nk = vj ? wm_row_norm<HD>(a.Km + krow * a.ldkm + h * HD, a.Kc + krow * a.ldkc + h * HD) : 0.f;
+      for (int kb = 0; kb < S::KB; ++kb) fk[kb] = wm_kl_frag<HD, false>(nullptr, nullptr, a.Qc + krow * a.ldqc + co, a.Kc + krow * a.ldkc + co, kb, g, vj);
+      nk = vj ? wm_kl_logsum<HD>(a.Kc + krow * a.ldkc + co) : 0.f;
+    } else {
+#pragma unroll
+      for (int kb = 0; kb < S::KB; ++kb) fk[kb] = wm_cat_frag<HD>(a.Km + krow * a.ldkm + h * HD, a.Kc + krow * a.ldkc + h * HD, kb, g, vj);
+      nk = vj ? wm_row_norm<HD>(a.Km + krow * a.ldkm + h * HD, a.Kc + krow * a.ldkc + h * HD) : 0.f;
+    }
 #pragma unroll
     for (int kb = 0; kb < KBV; ++kb) {
       fvm[kb] = frag_contig_hd<HD>(a.Vm + krow * a.ldvm + h * HD, kb, g);
@@ -461,7 +610,8 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
           for (int r = 0; r < 4; ++r) {
             const int i = it * 16 + 4 * g + r;
             if (i < L && vj) {
-              const float x = -((nk + sN[i]) - 2.0f * acc[r]) * rsq_hd;      // nk + nq: the same two numbers as in the forward, addition commutes
+              const float x = MET == WM_KL ? wm_kl_x(nk, sN[i], acc[r], (float)HD, rsq_hd)
+                                           : -((nk + sN[i]) - 2.0f * acc[r]) * rsq_hd;      // nk + nq: the same two numbers as in the forward, addition commutes
               const float ks_ = wm_keep_scale(a.drop, key_rng, (idx_bh + (uint32_t)i) * (uint32_t)L + (uint32_t)j);
               float dw, pd;
               wm_pair_bwd<HD>(x, j > i || key_pad, sDead[i] != 0.f, sLse[i], ks_, gm[r], gc[r], sDelta[i], rsq_hd, dw, pd);
@@ -486,7 +636,26 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
       }
     }
     dwsum = wm_colsum(dwsum);
-    if (vj) {
+    if (MET == WM_KL && vj) {
+      // column parts, added to pass A's row parts (same wave, same lane): dck += 0.5 / ck sum_i dW - 0.5 / ck^2 sum_i dW X1,
+      // dcq += 0.5 sum_i dW X2
+#pragma unroll
+      for (int ft = 0; ft < S::KC / 16; ++ft) {
+        const int k0 = 16 * ft + 4 * g;
+        const f32x4& acc = acck[ft];
+        if (k0 < HD) {
+          const float4 kc = *reinterpret_cast<const float4*>(a.Kc + krow * a.ldkc + co + k0);
+          float4* dkc = reinterpret_cast<float4*>(a.dKc + krow * a.ldd + co + k0);
+          const float4 y = make_float4(1.0f / kc.x, 1.0f / kc.y, 1.0f / kc.z, 1.0f / kc.w), o = *dkc;
+          *dkc = make_float4(o.x + (0.5f * dwsum * y.x - 0.5f * acc[0] * y.x * y.x), o.y + (0.5f * dwsum * y.y - 0.5f * acc[1] * y.y * y.y),
+                             o.z + (0.5f * dwsum * y.z - 0.5f * acc[2] * y.z * y.z), o.w + (0.5f * dwsum * y.w - 0.5f * acc[3] * y.w * y.w));
+        } else {
+          float4* dqc = reinterpret_cast<float4*>(a.dQc + krow * a.ldd + co + k0 - HD);
+          const float4 o = *dqc;
+          *dqc = make_float4(o.x + 0.5f * acc[0], o.y + 0.5f * acc[1], o.z + 0.5f * acc[2], o.w + 0.5f * acc[3]);
+        }
+      }
+    } else if (vj) {
 #pragma unroll
       for (int ft = 0; ft < S::KC / 16; ++ft) {
         const int k0 = 16 * ft + 4 * g;
@@ -503,6 +672,8 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
                           dwsum - (s2 > 1.00001e-12f ? acc[2] / s2 : 0.f), dwsum - (s3 > 1.00001e-12f ? acc[3] / s3 : 0.f));
         }
       }
+    }
+    if (vj) {
 #pragma unroll
       for (int nt = 0; nt < S::NT; ++nt) {
         *reinterpret_cast<float4*>(a.dVm + krow * a.ldd + h * HD + 16 * nt + 4 * g) = make_float4(accvm[nt][0], accvm[nt][1], accvm[nt][2], accvm[nt][3]);

@@ -7,6 +7,7 @@
 #include "adt_gemm.cuh"
 #include "adt_dense_rows.cuh"
 #include "adt_stosa.cuh"
+#include "adt_klattn.cuh"
 #include "adt_wattn_mfma.cuh"
 #include "adt_wide.cuh"
 
@@ -380,9 +381,9 @@ static bool wattn_mfma_ok(int L, int hd, const int* lds, int n) {
   return true;
 }
 
-template <int PREC, int HD>
+template <int PREC, int HD, int MET = WM_W>
 static int wattn_mfma_launch(bool bwd, const WAttnArgs& a, hipStream_t s) {
-  const void* fn = bwd ? (const void*)k_wattn_mfma_bwd<PREC, HD> : (const void*)k_wattn_mfma_fwd<PREC, HD, 8>;
+  const void* fn = bwd ? (const void*)k_wattn_mfma_bwd<PREC, HD, MET> : (const void*)k_wattn_mfma_fwd<PREC, HD, 8, MET>;
   const size_t smem = wattn_mfma_lds_bytes(a.L, HD, bwd);
   if (smem > 160 * 1024) return 1;
   static bool done[2] = {false, false};
@@ -399,6 +400,13 @@ static int wattn_mfma_launch(bool bwd, const WAttnArgs& a, hipStream_t s) {
 static int wattn_mfma_dispatch(int prec, bool bwd, const WAttnArgs& a, hipStream_t s) {
   if (prec == ADT_PREC_BF16) return a.hd == 16 ? wattn_mfma_launch<PREC_BF16, 16>(bwd, a, s) : wattn_mfma_launch<PREC_BF16, 32>(bwd, a, s);
   return a.hd == 16 ? wattn_mfma_launch<PREC_F32, 16>(bwd, a, s) : wattn_mfma_launch<PREC_F32, 32>(bwd, a, s);
+}
+
+// the KL-divergence score on the same kernels (adt_wattn_mfma.cuh, MET = WM_KL): the same shapes and LDS
+static int klattn_mfma_dispatch(int prec, bool bwd, const WAttnArgs& a, hipStream_t s) {
+  if (prec == ADT_PREC_BF16)
+    return a.hd == 16 ? wattn_mfma_launch<PREC_BF16, 16, WM_KL>(bwd, a, s) : wattn_mfma_launch<PREC_BF16, 32, WM_KL>(bwd, a, s);
+  return a.hd == 16 ? wattn_mfma_launch<PREC_F32, 16, WM_KL>(bwd, a, s) : wattn_mfma_launch<PREC_F32, 32, WM_KL>(bwd, a, s);
 }
 
 
@@ -581,34 +589,45 @@ int adt_adamw_range(float* P, float* G, float* M, float* V, int64_t n, float wd,
 }
 
 // ---- STOSA-ADT (adt_stosa.cuh) ----------------------------------------------------------------------------------
-int adt_wattn_fwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
-                  const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float p,
-                  const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE,
-                  void* stream) {
-  if (hd != 16 && hd != 32 && hd != 64) return adt_set_error("wattn: head_dim=%d unsupported (16/32/64)", hd);
-  if (L > 256) return adt_set_error("wattn: L=%d > 256 unsupported", L);
+}  // extern "C"
+
+// Both metrics of the vector-ALU STOSA attention share these launchers (adt_stosa.cuh: Wasserstein, adt_klattn.cuh: KL divergence;
+// the same shapes, arguments and LDS footprint)
+template <int MET>
+static int stosa_attn_fwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                          const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float p,
+                          const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE,
+                          void* stream) {
+  const void* fn = MET == WM_KL ? (const void*)k_klattn_fwd : (const void*)k_wattn_fwd;
+  const char* nm = MET == WM_KL ? "klattn" : "wattn";
+  if (hd != 16 && hd != 32 && hd != 64) return adt_set_error("%s: head_dim=%d unsupported (16/32/64)", nm, hd);
+  if (L > 256) return adt_set_error("%s: L=%d > 256 unsupported", nm, L);
   WAttnArgs a{};
   a.Qm = Qm; a.ldqm = ldqm; a.Qc = Qc; a.ldqc = ldqc; a.Km = Km; a.ldkm = ldkm; a.Kc = Kc; a.ldkc = ldkc; a.Vm = Vm; a.ldvm = ldvm;
   a.Vc = Vc; a.ldvc = ldvc; a.kid = key_ids; a.B = B; a.H = H; a.L = L; a.hd = hd; a.scale = 1.0f / sqrtf((float)hd);
   a.drop = adt_make_drop(p, seed, site); a.bh_offset = b_offset * (uint32_t)H; a.Om = Om; a.ldom = ldom; a.Oc = Oc; a.ldoc = ldoc; a.LSE = LSE;
   const size_t smem = wattn_lds_bytes(L, hd, false);
-  if (smem > 160 * 1024) return adt_set_error("wattn_fwd: %zu B of LDS", smem);
+  if (smem > 160 * 1024) return adt_set_error("%s_fwd: %zu B of LDS", nm, smem);
   static bool done = false;
   if (!done) {
-    if (hipFuncSetAttribute((const void*)k_wattn_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return adt_set_error("wattn_fwd: hipFuncSetAttribute");
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return adt_set_error("%s_fwd: hipFuncSetAttribute", nm);
     done = true;
   }
-  hipLaunchKernelGGL(k_wattn_fwd, dim3(B * H), dim3(256), smem, (hipStream_t)stream, a);
-  return check_launch("wattn_fwd");
+  void* kargs[] = {&a};
+  if (hipLaunchKernel(fn, dim3(B * H), dim3(256), kargs, smem, (hipStream_t)stream) != hipSuccess) return adt_set_error("%s_fwd: launch failed", nm);
+  return check_launch(MET == WM_KL ? "klattn_fwd" : "wattn_fwd");
 }
 
-int adt_wattn_bwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
-                  const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc,
-                  int ldoc, const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd, float p,
-                  const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc, float* dKm, float* dKc, float* dVm,
-                  float* dVc, int ldd, void* stream) {
-  if (hd != 16 && hd != 32 && hd != 64) return adt_set_error("wattn: head_dim=%d unsupported (16/32/64)", hd);
-  if (L > 256) return adt_set_error("wattn: L=%d > 256 unsupported", L);
+template <int MET>
+static int stosa_attn_bwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                          const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc,
+                          int ldoc, const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd, float p,
+                          const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc, float* dKm, float* dKc, float* dVm,
+                          float* dVc, int ldd, void* stream) {
+  const void* fn = MET == WM_KL ? (const void*)k_klattn_bwd : (const void*)k_wattn_bwd;
+  const char* nm = MET == WM_KL ? "klattn" : "wattn";
+  if (hd != 16 && hd != 32 && hd != 64) return adt_set_error("%s: head_dim=%d unsupported (16/32/64)", nm, hd);
+  if (L > 256) return adt_set_error("%s: L=%d > 256 unsupported", nm, L);
   WAttnArgs a{};
   a.Qm = Qm; a.ldqm = ldqm; a.Qc = Qc; a.ldqc = ldqc; a.Km = Km; a.ldkm = ldkm; a.Kc = Kc; a.ldkc = ldkc; a.Vm = Vm; a.ldvm = ldvm;
   a.Vc = Vc; a.ldvc = ldvc; a.kid = key_ids; a.B = B; a.H = H; a.L = L; a.hd = hd; a.scale = 1.0f / sqrtf((float)hd);
@@ -617,14 +636,48 @@ int adt_wattn_bwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const fl
   a.dOm = dOm; a.lddom = lddom; a.dOc = dOc; a.lddoc = lddoc;
   a.dQm = dQm; a.dQc = dQc; a.dKm = dKm; a.dKc = dKc; a.dVm = dVm; a.dVc = dVc; a.ldd = ldd;
   const size_t smem = wattn_lds_bytes(L, hd, true);
-  if (smem > 160 * 1024) return adt_set_error("wattn_bwd: %zu B of LDS", smem);
+  if (smem > 160 * 1024) return adt_set_error("%s_bwd: %zu B of LDS", nm, smem);
   static bool done = false;
   if (!done) {
-    if (hipFuncSetAttribute((const void*)k_wattn_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return adt_set_error("wattn_bwd: hipFuncSetAttribute");
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return adt_set_error("%s_bwd: hipFuncSetAttribute", nm);
     done = true;
   }
-  hipLaunchKernelGGL(k_wattn_bwd, dim3(B * H), dim3(256), smem, (hipStream_t)stream, a);
-  return check_launch("wattn_bwd");
+  void* kargs[] = {&a};
+  if (hipLaunchKernel(fn, dim3(B * H), dim3(256), kargs, smem, (hipStream_t)stream) != hipSuccess) return adt_set_error("%s_bwd: launch failed", nm);
+  return check_launch(MET == WM_KL ? "klattn_bwd" : "wattn_bwd");
+}
+
+extern "C" {
+
+int adt_wattn_fwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                  const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float p,
+                  const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE,
+                  void* stream) {
+  return stosa_attn_fwd<WM_W>(Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, B, H, L, hd, p, seed, site, b_offset, Om, ldom, Oc, ldoc, LSE, stream);
+}
+
+int adt_wattn_bwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                  const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc,
+                  int ldoc, const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd, float p,
+                  const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc, float* dKm, float* dKc, float* dVm,
+                  float* dVc, int ldd, void* stream) {
+  return stosa_attn_bwd<WM_W>(Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, Om, ldom, Oc, ldoc, LSE, dOm, lddom, dOc, lddoc, B, H, L, hd, p, seed, site, b_offset, dQm, dQc, dKm, dKc, dVm, dVc, ldd, stream);
+}
+
+// KL-divergence attention (adt_klattn.cuh): the same shapes, arguments and LDS footprint as adt_wattn_fwd / adt_wattn_bwd
+int adt_klattn_fwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                   const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float p,
+                   const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE,
+                   void* stream) {
+  return stosa_attn_fwd<WM_KL>(Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, B, H, L, hd, p, seed, site, b_offset, Om, ldom, Oc, ldoc, LSE, stream);
+}
+
+int adt_klattn_bwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                   const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc,
+                   int ldoc, const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd, float p,
+                   const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc, float* dKm, float* dKc, float* dVm,
+                   float* dVc, int ldd, void* stream) {
+  return stosa_attn_bwd<WM_KL>(Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, Om, ldom, Oc, ldoc, LSE, dOm, lddom, dOc, lddoc, B, H, L, hd, p, seed, site, b_offset, dQm, dQc, dKm, dKc, dVm, dVc, ldd, stream);
 }
 
 // The same attention on the matrix cores; 1 = shape not covered (see wattn_mfma_ok above)
@@ -658,6 +711,37 @@ int adt_wattn_mfma_bwd(int prec, const float* Qm, int ldqm, const float* Qc, int
   return wattn_mfma_dispatch(prec, true, a, (hipStream_t)stream);
 }
 
+// KL-divergence attention on the matrix cores; 1 = shape not covered (see wattn_mfma_ok above)
+int adt_klattn_mfma_fwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                       const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float p,
+                       const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE,
+                       void* stream) {
+  const int lds[8] = {ldqm, ldqc, ldkm, ldkc, ldvm, ldvc, ldom, ldoc};
+  if (!wattn_mfma_ok(L, hd, lds, 8)) return 1;
+  WAttnArgs a{};
+  a.Qm = Qm; a.ldqm = ldqm; a.Qc = Qc; a.ldqc = ldqc; a.Km = Km; a.ldkm = ldkm; a.Kc = Kc; a.ldkc = ldkc; a.Vm = Vm; a.ldvm = ldvm;
+  a.Vc = Vc; a.ldvc = ldvc; a.kid = key_ids; a.B = B; a.H = H; a.L = L; a.hd = hd; a.scale = 1.0f / sqrtf((float)hd);
+  a.drop = adt_make_drop(p, seed, site); a.bh_offset = b_offset * (uint32_t)H; a.Om = Om; a.ldom = ldom; a.Oc = Oc; a.ldoc = ldoc; a.LSE = LSE;
+  return klattn_mfma_dispatch(prec, false, a, (hipStream_t)stream);
+}
+
+int adt_klattn_mfma_bwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                       const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc,
+                       int ldoc, const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd, float p,
+                       const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc, float* dKm, float* dKc, float* dVm,
+                       float* dVc, int ldd, void* stream) {
+  const int lds[11] = {ldqm, ldqc, ldkm, ldkc, ldvm, ldvc, lddom, lddoc, ldd, ldom, ldoc};
+  if (!wattn_mfma_ok(L, hd, lds, 11)) return 1;
+  WAttnArgs a{};
+  a.Qm = Qm; a.ldqm = ldqm; a.Qc = Qc; a.ldqc = ldqc; a.Km = Km; a.ldkm = ldkm; a.Kc = Kc; a.ldkc = ldkc; a.Vm = Vm; a.ldvm = ldvm;
+  a.Vc = Vc; a.ldvc = ldvc; a.kid = key_ids; a.B = B; a.H = H; a.L = L; a.hd = hd; a.scale = 1.0f / sqrtf((float)hd);
+  a.drop = adt_make_drop(p, seed, site); a.bh_offset = b_offset * (uint32_t)H; a.LSE = const_cast<float*>(LSE);
+  a.Om = const_cast<float*>(Om); a.ldom = ldom; a.Oc = const_cast<float*>(Oc); a.ldoc = ldoc;
+  a.dOm = dOm; a.lddom = lddom; a.dOc = dOc; a.lddoc = lddoc;
+  a.dQm = dQm; a.dQc = dQc; a.dKm = dKm; a.dKc = dKc; a.dVm = dVm; a.dVc = dVc; a.ldd = ldd;
+  return klattn_mfma_dispatch(prec, true, a, (hipStream_t)stream);
+}
+
 int adt_wdist_bpr(const float* Sm, const float* Sc, int lds, const float* Em, const float* Ec, const int32_t* pos, const int32_t* neg, int T,
                   int d, float pvn_weight, const float* inv_count, float* dSm, float* dSc, int ldds, float* dEm, float* dEc, float* loss3,
                   void* stream) {
@@ -673,6 +757,24 @@ int adt_wdist_full(const float* Sm, const float* Sc, int lds, const float* Em, c
   WFullArgs a{Sm, Sc, lds, Em, Ec, B, V, d, dist, ldo};
   hipLaunchKernelGGL(k_wdist_full, dim3(grid_for((size_t)B * V, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("wdist_full");
+}
+
+// row-wise KL loss and the chunked full-sort score (adt_klattn.cuh); arguments as adt_wdist_bpr / adt_wdist_full
+int adt_kldist_bpr(const float* Sm, const float* Sc, int lds, const float* Em, const float* Ec, const int32_t* pos, const int32_t* neg, int T,
+                  int d, float pvn_weight, const float* inv_count, float* dSm, float* dSc, int ldds, float* dEm, float* dEc, float* loss3,
+                  void* stream) {
+  if (d % 64) return adt_set_error("kldist_bpr: d=%d must be a multiple of 64", d);
+  WBprArgs a{Sm, Sc, lds, Em, Ec, pos, neg, T, d, pvn_weight, inv_count, dSm, dSc, ldds, dEm, dEc, loss3};
+  hipLaunchKernelGGL(k_kldist_bpr, dim3(grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("kldist_bpr");
+}
+
+int adt_kldist_full(const float* Sm, const float* Sc, int lds, const float* Em, const float* Ec, int B, int V, int d, float* dist, int ldo,
+                   void* stream) {
+  if (B <= 0 || V <= 0) return 0;
+  WFullArgs a{Sm, Sc, lds, Em, Ec, B, V, d, dist, ldo};
+  hipLaunchKernelGGL(k_kldist_full, dim3(grid_for((size_t)B * V, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("kldist_full");
 }
 
 int adt_topk_masked(float* dist, int ld, int B, int N, const int32_t* indptr, const int32_t* indices, int k, int32_t* out_idx,

@@ -415,6 +415,69 @@ def wdist_full(Sm, Sc, Em, Ec, V):
     return dist
 
 
+def klattn_fwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p=0.0, seed=None, site=0, b_offset=0, prec=None):
+    """KL-divergence attention, arguments and outputs as wattn_fwd.  prec: PREC_BF16 / PREC_F32 selects the matrix-core kernels
+    (adt_wattn_mfma.cuh with the KL score) where they cover the shape; None (or an uncovered shape) the exact vector-ALU kernels
+    (adt_klattn.cuh)."""
+    d = Qm.shape[1]
+    hd = d // H
+    Om = torch.empty(B * L, d, device=Qm.device, dtype=torch.float32)
+    Oc = torch.empty_like(Om)
+    LSE = torch.empty(B * H * L, device=Qm.device, dtype=torch.float32)
+    if prec is not None:
+        rc = _lib.load().adt_klattn_mfma_fwd(int(prec), _p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc),
+                                             _p(_f32(Vm)), _ld(Vm), _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), B, H, L, hd, float(p), _p(seed), site,
+                                             b_offset, _p(Om), d, _p(Oc), d, _p(LSE), _stream())
+        if rc != 1:
+            _lib.check(rc, "klattn_mfma_fwd")
+            return Om, Oc, LSE
+    _lib.check(_lib.load().adt_klattn_fwd(_p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc), _p(_f32(Vm)), _ld(Vm),
+                                          _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), B, H, L, hd, float(p), _p(seed), site, b_offset, _p(Om), d, _p(Oc), d,
+                                          _p(LSE), _stream()), "klattn_fwd")
+    return Om, Oc, LSE
+
+
+def klattn_bwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p=0.0, seed=None, site=0, b_offset=0, out=None, prec=None):
+    """As wattn_bwd: out = optional (dQm, dQc, dKm, dKc, dVm, dVc) views sharing one row stride (overwritten); prec as klattn_fwd
+    (use the same value)."""
+    d = Qm.shape[1]
+    hd = d // H
+    outs = [torch.empty(B * L, d, device=Qm.device, dtype=torch.float32) for _ in range(6)] if out is None else list(out)
+    ldd = _ld(outs[0])
+    assert all(_ld(o) == ldd for o in outs)
+    if prec is not None:
+        rc = _lib.load().adt_klattn_mfma_bwd(int(prec), _p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc),
+                                             _p(_f32(Vm)), _ld(Vm), _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), _p(Om), _ld(Om), _p(Oc), _ld(Oc), _p(LSE),
+                                             _p(_f32(dOm)), _ld(dOm), _p(_f32(dOc)), _ld(dOc), B, H, L, hd, float(p), _p(seed), site, b_offset,
+                                             *[_p(o) for o in outs], ldd, _stream())
+        if rc != 1:
+            _lib.check(rc, "klattn_mfma_bwd")
+            return outs
+    _lib.check(_lib.load().adt_klattn_bwd(_p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc), _p(_f32(Vm)), _ld(Vm),
+                                          _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), _p(Om), _ld(Om), _p(Oc), _ld(Oc), _p(LSE), _p(_f32(dOm)), _ld(dOm),
+                                          _p(_f32(dOc)), _ld(dOc), B, H, L, hd, float(p), _p(seed), site, b_offset, *[_p(o) for o in outs], ldd, _stream()),
+               "klattn_bwd")
+    return outs
+
+
+def kldist_bpr(Sm, Sc, Em, Ec, pos, neg, pvn_weight, inv_count, dEm, dEc, loss3):
+    """bpr_optimization on row-wise KL divergences; arguments and outputs as wdist_bpr."""
+    T, d = Sm.shape
+    dSm = torch.empty(T, d, device=Sm.device, dtype=torch.float32)
+    dSc = torch.empty_like(dSm)
+    _lib.check(_lib.load().adt_kldist_bpr(_p(_f32(Sm)), _p(_f32(Sc)), _ld(Sm), _p(Em), _p(Ec), _p(_i32(pos)), _p(_i32(neg)), T, d, float(pvn_weight),
+                                          _p(inv_count), _p(dSm), _p(dSc), d, _p(dEm), _p(dEc), _p(loss3), _stream()), "kldist_bpr")
+    return dSm, dSc
+
+
+def kldist_full(Sm, Sc, Em, Ec, V):
+    """kl_predict_full for one eval batch: the B rows of Sm / Sc ARE the batch (the scores depend on B and on each row's place)."""
+    B, d = Sm.shape
+    dist = torch.empty(B, V, device=Sm.device, dtype=torch.float32)
+    _lib.check(_lib.load().adt_kldist_full(_p(_f32(Sm)), _p(_f32(Sc)), _ld(Sm), _p(Em), _p(Ec), B, V, d, _p(dist), V, _stream()), "kldist_full")
+    return dist
+
+
 def topk_masked(dist, k, indptr=None, indices=None, want_val=False):
     """k smallest entries per row in ascending order after pushing the CSR-listed columns to 1e24; `dist` is consumed."""
     B, N = dist.shape

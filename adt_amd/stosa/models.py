@@ -90,8 +90,13 @@ class DisenDistSAModel(FlatModule):
         d, H = self.hidden_units, self.num_heads
         if d % 64 or (d // H) not in (16, 32, 64):
             raise _lib.AdtError("DisenDistSAModel (adt_amd): hidden_units must be a multiple of 64 with head size 16/32/64, got d=%d H=%d" % (d, H))
-        if getattr(args, "distance_metric", "wasserstein") != "wasserstein":
-            raise _lib.AdtError("DisenDistSAModel (adt_amd): only distance_metric='wasserstein' is built")
+        self.distance_metric = getattr(args, "distance_metric", "wasserstein")
+        if self.distance_metric not in ("wasserstein", "kl"):
+            raise _lib.AdtError("DisenDistSAModel (adt_amd): distance_metric must be 'wasserstein' or 'kl', got %r" % (self.distance_metric,))
+        kl = self.distance_metric == "kl"
+        # attention, BPR loss and full-sort score of the chosen metric (stosa/modules.py:244-248, trainer.py:372-379, :597-600)
+        self._attn_fwd, self._attn_bwd = (ops.klattn_fwd, ops.klattn_bwd) if kl else (ops.wattn_fwd, ops.wattn_bwd)
+        self._dist_bpr, self._dist_full = (ops.kldist_bpr, ops.kldist_full) if kl else (ops.wdist_bpr, ops.wdist_full)
         table, n_trained = param_table(args.item_size, args.maxlen, d, H, args.num_layers, args.num_users, block, dec_layernorm)
         self._build_flat(table, getattr(args, "device", "cuda:0"), REF_ORDER)
         self.n_trained_floats = self._views[table[n_trained][0]][0]     # optimizer prefix (flat floats)
@@ -151,7 +156,7 @@ class DisenDistSAModel(FlatModule):
             Qm, Km, Vm = qm.t, km.t[:, :d], km.t[:, d:]
             Qc, Kc, Vc = qc.t, kc.t[:, :d], kc.t[:, d:]
             holders = ((qm, km), (qc, kc))
-        Om, Oc, LSE = ops.wattn_fwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, pa, self._seed, st["attn"], tp.b_offset, prec=self.prec)
+        Om, Oc, LSE = self._attn_fwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, pa, self._seed, st["attn"], tp.b_offset, prec=self.prec)
         om, oc = Act(Om), Act(Oc)
 
         def bw():
@@ -162,7 +167,7 @@ class DisenDistSAModel(FlatModule):
             goc = oc.g if oc.g is not None else torch.zeros_like(Oc)
             gm = torch.empty(T, 3 * d, device=self.dev, dtype=torch.float32)
             gc = torch.empty(T, 3 * d, device=self.dev, dtype=torch.float32)
-            ops.wattn_bwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, gom, goc, B, H, L, pa, self._seed, st["attn"], tp.b_offset,
+            self._attn_bwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, gom, goc, B, H, L, pa, self._seed, st["attn"], tp.b_offset,
                           out=(gm[:, :d], gc[:, :d], gm[:, d:2 * d], gc[:, d:2 * d], gm[:, 2 * d:], gc[:, 2 * d:]), prec=self.prec)
             for hold, g in ((holders[0], gm), (holders[1], gc)):
                 if len(hold) == 1:
@@ -266,8 +271,8 @@ class DisenDistSAModel(FlatModule):
 
     @torch.no_grad()
     def predict_full(self, input_ids, dec_ids=None):
-        """Full-sort scores (stosa/trainer.py:583-595, dist_predict_full :464-479): Wasserstein distance of the last state to
-        every item, (B, item_size)."""
+        """Full-sort scores (stosa/trainer.py:583-595), (B, item_size): dist_predict_full (:464-479), the Wasserstein distance of the
+        last state to every item, or kl_predict_full (:481-511), whose scores depend on the rows of this call being the eval batch."""
         inp = self.ids(input_ids)
         dec = inp if dec_ids is None else self.ids(dec_ids)
         B, L = inp.shape
@@ -278,7 +283,7 @@ class DisenDistSAModel(FlatModule):
         rows = torch.arange(L - 1, B * L, L, device=self.dev, dtype=torch.int32)
         sm, sc = ops.gather_rows(m.t, rows), ops.gather_rows(c.t, rows)
         self.train(was)
-        return ops.wdist_full(sm, sc, self.P("item_mean_embeddings.weight"), self.P("item_cov_embeddings.weight"), self.item_size)
+        return self._dist_full(sm, sc, self.P("item_mean_embeddings.weight"), self.P("item_cov_embeddings.weight"), self.item_size)
 
     # ------------------------------------------------------------------------------------------------------------------
     def stage(self, input_ids, dec_ids, pos_ids, neg_ids, n_target_global=None):
@@ -295,7 +300,7 @@ class DisenDistSAModel(FlatModule):
         tp = Tape(self, self.prec, self.training, row_offset=b_offset * L, b_offset=b_offset)
         inp, dec = st["inp"].view(-1), st["dec"].view(-1)
         m, c, enc_inputs, enc_recs, dec_outs = self._finetune(tp, inp, dec, B)
-        dsm, dsc = ops.wdist_bpr(m.t, c.t, self.P("item_mean_embeddings.weight"), self.P("item_cov_embeddings.weight"), st["pos"].view(-1),
+        dsm, dsc = self._dist_bpr(m.t, c.t, self.P("item_mean_embeddings.weight"), self.P("item_cov_embeddings.weight"), st["pos"].view(-1),
                                  st["neg"].view(-1), float(self.args.pvn_weight), st["inv_count"], self.G("item_mean_embeddings.weight"),
                                  self.G("item_cov_embeddings.weight"), loss_slots[0:3].view(-1))
         give(m, dsm)

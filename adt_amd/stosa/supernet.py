@@ -16,7 +16,7 @@ lambda2[l] * NLL (mean and covariance), Adam with coupled weight decay, torch's 
 import numpy as np
 import torch
 
-from .. import ops
+from .. import _lib, ops
 from ..supersearch import candidate_features, cand_to_block, get_shared
 from ..wide import Act, Tape
 from .models import SITE_EMB, DisenDistSAModel, dec_sites, enc_sites
@@ -30,6 +30,10 @@ def _cand_sites(sites, k):
 
 class DisenDistSASupernet(DisenDistSAModel):
     def __init__(self, args, rec_choice, ind_choice):
+        if getattr(args, "distance_metric", "wasserstein") != "wasserstein":
+            # the supernet's loss and full-sort paths call the Wasserstein kernels directly: refuse rather than mix the metrics
+            raise _lib.AdtError("DisenDistSASupernet (adt_amd): only distance_metric='wasserstein' is built for the supernet, got %r"
+                                % (args.distance_metric,))
         self.rec_choice, self.ind_choice = np.asarray(rec_choice, np.float64), np.asarray(ind_choice, np.float64)
         self.block = len(self.rec_choice) * len(self.ind_choice)
         super().__init__(args, block=self.block, dec_layernorm=False)     # init_weights is the plain model's (supernet.py:101-111)

@@ -111,8 +111,9 @@ class FusedStosaTrainer:
     @torch.no_grad()
     def full_sort(self, batches, topk=40):
         """Full-sort evaluation (stosa/trainer.py:583-612) over an iterable of (input_ids (B, L), seen, answers (B, A)): rank all
-        items by ascending distance with the seen items pushed to 1e24 and keep `topk`, all on the device (adt_wdist_full +
-        adt_topk_masked); only the (B, topk) ids come back.  `seen` is the users' rows of the train/valid rating matrix as a scipy
+        items by ascending distance with the seen items pushed to 1e24 and keep `topk`, all on the device (model.predict_full: adt_wdist_full,
+        or adt_kldist_full for distance_metric 'kl', whose scores depend on each batch's rows being the eval batch -- pass the reference's
+        eval batches -- then adt_topk_masked); only the (B, topk) ids come back.  `seen` is the users' rows of the train/valid rating matrix as a scipy
         CSR matrix, a dense (B, item_size) 0/1 array, or None.  Returns (pred_list (N, topk), answers (N, A)) for
         get_full_sort_score."""
         preds, answers = [], []

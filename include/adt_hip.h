@@ -275,6 +275,37 @@ int adt_wdist_bpr(const float* Sm, const float* Sc, int lds, const float* Em, co
 /* dist_predict_full (stosa/trainer.py:464-479): dist[b][v] = W2(state b, item v), items 0..V-1 */
 int adt_wdist_full(const float* Sm, const float* Sc, int lds, const float* Em, const float* Ec, int B, int V, int d,
                    float* dist, int ldo, void* stream);
+/* STOSA-ADT with distance_metric='kl' (adt_klattn.cuh).  KL-divergence attention (stosa/modules.py:52-70 kl_distance_matmul with its
+ * broadcasts: the mean term reads key row i, the trace term is transposed; log(prod c) taken as sum(log c)): the same arguments,
+ * shapes (head size 16 / 32 / 64, L <= 256) and outputs as adt_wattn_fwd / adt_wattn_bwd, exact fp32. */
+int adt_klattn_fwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                   const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd,
+                   float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc,
+                   float* LSE, void* stream);
+int adt_klattn_bwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                   const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom,
+                   const float* Oc, int ldoc, const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B,
+                   int H, int L, int hd, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc,
+                   float* dKm, float* dKc, float* dVm, float* dVc, int ldd, void* stream);
+/* The KL attention on the matrix cores (adt_wattn_mfma.cuh with the KL score: the cross term X_i . Y_j as one 16x16x32 MFMA per tile
+ * at head size 16); prec as adt_wattn_mfma_fwd.  Return 1 = shape not covered (head size 16 / 32, L <= 128): use adt_klattn_fwd / _bwd. */
+int adt_klattn_mfma_fwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                        const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd,
+                        float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc,
+                        float* LSE, void* stream);
+int adt_klattn_mfma_bwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                        const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom,
+                        const float* Oc, int ldoc, const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B,
+                        int H, int L, int hd, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc,
+                        float* dKm, float* dKc, float* dVm, float* dVc, int ldd, void* stream);
+/* bpr_optimization on row-wise KL divergences (stosa/trainer.py:358-391, kl_distance modules.py:45-50); arguments as adt_wdist_bpr */
+int adt_kldist_bpr(const float* Sm, const float* Sc, int lds, const float* Em, const float* Ec, const int32_t* pos,
+                   const int32_t* neg, int T, int d, float pvn_weight, const float* inv_count, float* dSm, float* dSc, int ldds,
+                   float* dEm, float* dEc, float* loss3, void* stream);
+/* kl_predict_full (stosa/trainer.py:481-511) for ONE eval batch of B users: the reference's chunking by B items, its broadcasts and its
+ * padding items (zero mean, unit covariance) included, so dist depends on B and on each user's row in the batch; items 0..V-1 */
+int adt_kldist_full(const float* Sm, const float* Sc, int lds, const float* Em, const float* Ec, int B, int V, int d,
+                    float* dist, int ldo, void* stream);
 
 /* Full-sort selection (stosa/trainer.py:598-612: rating_pred[train_matrix[users].toarray() > 0] = 1e+24, np.argpartition(.., 40),
  * np.argsort of the 40): per row b, set dist[b][indices[indptr[b]..indptr[b+1])] = 1e24 (CSR of the seen items; both NULL = no

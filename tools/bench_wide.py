@@ -3,7 +3,7 @@
 one GPU, synthetic ids, HIP graph).  Not the driver's bench (bench.py measures configs[1]); results go to profiles/.
 
     python tools/bench_wide.py bert  [--steps 20] [--batch 256]
-    python tools/bench_wide.py stosa [--steps 20]
+    python tools/bench_wide.py stosa [--steps 20] [--metric wasserstein|kl]
 """
 import argparse
 import json
@@ -71,7 +71,7 @@ def run_stosa(args):
     from adt_amd.stosa.trainer import FusedStosaTrainer
     a = Args()
     a.device, a.item_size, a.maxlen, a.hidden_units, a.num_heads, a.num_layers, a.num_users = "cuda:0", 12103, 100, 64, 4, 1, 22364
-    a.dropout, a.attention_dropout, a.pvn_weight, a.precision, a.distance_metric = 0.3, 0.3, 0.005, "bf16", "wasserstein"
+    a.dropout, a.attention_dropout, a.pvn_weight, a.precision, a.distance_metric = 0.3, 0.3, 0.005, "bf16", args.metric
     torch.manual_seed(42)
     m = DisenDistSAModel(a)
     tr = FusedStosaTrainer(m, [0.1], [0.1], use_graph=not args.no_graph, seed=42)
@@ -99,9 +99,12 @@ def run_stosa(args):
         tr.step_staged(staged[i % 4])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print(json.dumps({"workload": "STOSA-ADT Beauty shape: d=64 H=4 L=100 1+1 layers item_size=12103, batch %d, dropout 0.3, full train step" % B,
+    kl = args.metric == "kl"
+    print(json.dumps({"workload": "STOSA-ADT Beauty shape: d=64 H=4 L=100 1+1 layers item_size=12103, batch %d, dropout 0.3, full train step%s"
+                      % (B, ", distance_metric kl" if kl else ""),
                       "ms_per_step": round(dt / args.steps * 1e3, 3), "sequences_per_s": round(B * args.steps / dt, 1), "loss": round(float(tr.loss()), 4),
-                      "dtype": "bf16 MFMA operands (dense layers and Wasserstein attention), fp32 accumulation, statistics and losses"}))
+                      "steps": args.steps, "warmup": args.warmup,
+                      "dtype": "bf16 MFMA operands (dense layers and %s attention), fp32 accumulation, statistics and losses" % ("KL" if kl else "Wasserstein")}))
 
 
 def run_sasrec256(args):
@@ -142,5 +145,6 @@ if __name__ == "__main__":
     ap.add_argument("--items", type=int, default=26744)
     ap.add_argument("--mcap", type=float, default=0.3)
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl"], help="stosa: distance_metric")
     args = ap.parse_args()
     {"bert": run_bert, "stosa": run_stosa, "sasrec256": run_sasrec256}[args.which](args)

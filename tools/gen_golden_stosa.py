@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/stosa_*.npz by IMPORTING the reference (read-only, /root/reference/stosa) in the build container
+"""Generate tests/golden/stosa_*.npz (and, with --metric kl, stosa_kl_*.npz) by IMPORTING the reference (read-only, /root/reference/stosa) in the build container
 (run through tools/gen_golden_wide.py stosa).  Fixtures are data only: seeded inputs, the seed that regenerates the numpy
 weights, and the tensors the reference produced.
 
 The loss assembly below calls bpr_optimization's arithmetic (stosa/trainer.py:358-391, restated with the reference's own
 wasserstein_distance from stosa/modules.py because the method needs a constructed Trainer with dataloaders) and the loop
-body of DistSAModelTrainer.iteration (:534-559) with the same torch functions in the same order; dropout is 0.
+body of DistSAModelTrainer.iteration (:534-559) with the same torch functions in the same order; dropout is 0.  With
+metric "kl" the distances are the reference's kl_distance / kl_distance_matmul and full_dist is kl_predict_full's arithmetic
+(:481-511) with the fixture batch as the eval batch; those fixtures are compacted (tools/gen_golden_inputs.py:compact) to stay
+small (every float tensor above 2048 entries becomes its norm and 1024 samples), and keep no weights: after one Adam step from
+zero moments they follow from the initial weights and the gradient.
 """
 import os
 import sys
@@ -40,7 +44,19 @@ def stosa_batch(r, B, L, V):
     return inp, dec, pos, neg
 
 
-def gen_stosa(tag, cfg_kw, B, seed, lam1, lam2, lr=1e-3, keep_w3=True, compact=False, steps=3):
+def kl_predict_full(modules, mo, co, Em, Ec):
+    """kl_predict_full (stosa/trainer.py:481-511) with Em / Ec the item tables (Ec already through ELU(.)+1)."""
+    V, E = Em.shape[0], mo.shape[0]
+    pad = E - V % E
+    cm = torch.cat((Em, torch.zeros(pad, Em.shape[1])), 0)
+    cc = torch.cat((Ec, torch.ones(pad, Em.shape[1])), 0)
+    res = torch.zeros(E, cm.shape[0])
+    for s0 in range(0, cm.shape[0], E):
+        res[:, s0:s0 + E] = modules.kl_distance_matmul(mo, co, cm[s0:s0 + E], cc[s0:s0 + E])
+    return res[:, :V]
+
+
+def gen_stosa(tag, cfg_kw, B, seed, lam1, lam2, lr=1e-3, keep_w3=True, compact=False, steps=3, metric="wasserstein", keep_w1=True, thresh=8192):
     from tools.gen_golden_wide import _import_from
     from oracle import stosa_oracle as so
     models = _import_from("/root/reference/stosa", "models")
@@ -54,7 +70,7 @@ def gen_stosa(tag, cfg_kw, B, seed, lam1, lam2, lr=1e-3, keep_w3=True, compact=F
     inp, dec, pos, neg = stosa_batch(r, B, cfg.maxlen, cfg.item_size)
     a = Args()
     a.item_size, a.hidden_units, a.maxlen, a.num_users, a.dropout, a.attention_dropout = cfg.item_size, cfg.hidden_units, cfg.maxlen, cfg.num_users, 0.0, 0.0
-    a.num_heads, a.num_layers, a.hidden_act, a.initializer_range, a.distance_metric, a.kernel_param = cfg.num_heads, cfg.num_layers, "gelu", 0.02, "wasserstein", 1.0
+    a.num_heads, a.num_layers, a.hidden_act, a.initializer_range, a.distance_metric, a.kernel_param = cfg.num_heads, cfg.num_layers, "gelu", 0.02, metric, 1.0
     a.cuda_condition, a.pvn_weight = False, cfg.pvn_weight
     m = models.DisenDistSAModel(a)
     m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in P.items()}, strict=True)
@@ -73,11 +89,15 @@ def gen_stosa(tag, cfg_kw, B, seed, lam1, lam2, lr=1e-3, keep_w3=True, compact=F
             out["dec_out_mean_%d" % i], out["dec_out_cov_%d" % i] = dec_out[i][0].numpy(), dec_out[i][1].numpy()
         # dist_predict_full (trainer.py:464-479) on the last position
         elu = nn.ELU()
-        out["full_dist"] = modules.wasserstein_distance_matmul(mo[:, -1, :], co[:, -1, :], m.item_mean_embeddings.weight,
-                                                               elu(m.item_cov_embeddings.weight) + 1).numpy()
+        if metric == "kl":
+            out["full_dist"] = kl_predict_full(modules, mo[:, -1, :], co[:, -1, :], m.item_mean_embeddings.weight,
+                                               elu(m.item_cov_embeddings.weight) + 1).numpy()
+        else:
+            out["full_dist"] = modules.wasserstein_distance_matmul(mo[:, -1, :], co[:, -1, :], m.item_mean_embeddings.weight,
+                                                                   elu(m.item_cov_embeddings.weight) + 1).numpy()
     m.train()
     opt = torch.optim.Adam(m.parameters(), lr=lr, betas=(0.9, 0.999), weight_decay=0.0)
-    wd = modules.wasserstein_distance
+    wd = modules.kl_distance if metric == "kl" else modules.wasserstein_distance
     for step in range(steps):
         mo, co, att, margins, enc_in, enc_rec, dec_out = m.finetune(t[0], t[1], uid)
         # bpr_optimization (trainer.py:358-391)
@@ -117,18 +137,20 @@ def gen_stosa(tag, cfg_kw, B, seed, lam1, lam2, lr=1e-3, keep_w3=True, compact=F
                     out["grad." + k] = p.grad.numpy().copy()
             out["grad_none"] = np.array(none)
         opt.step()
-        if step == 0 or (step == 2 and keep_w3):
+        if (step == 0 and keep_w1) or (step == 2 and keep_w3):
             for k, p in m.named_parameters():
                 out["w%d." % (step + 1) + k] = p.detach().numpy().copy()
-    path = os.path.join(OUT, "stosa_%s.npz" % tag)
+    path = os.path.join(OUT, ("stosa_kl_%s.npz" if metric == "kl" else "stosa_%s.npz") % tag)
     if compact:
         from tools.gen_golden_inputs import compact as _compact
-        out = _compact(out)
+        out = _compact(out, thresh=thresh)
     np.savez_compressed(path, **out)
     print("wrote", path, "loss", out["loss"], "none-grads", len(out["grad_none"]), "%.1f KB" % (os.path.getsize(path) / 1024))
 
 
-def main():
+def main(metric="wasserstein"):
+    if metric == "kl":
+        return main_kl()
     gen_stosa("small", dict(item_size=42, maxlen=12, hidden_units=64, num_heads=4, num_layers=1, num_users=4, pvn_weight=0.005), B=4, seed=21,
               lam1=[0.3], lam2=[0.2])
     gen_stosa("l2h2", dict(item_size=33, maxlen=20, hidden_units=64, num_heads=2, num_layers=2, num_users=3, pvn_weight=0.1), B=3, seed=22,
@@ -144,6 +166,22 @@ def main_cfg5():
               seed=33, lam1=[0.0021], lam2=[0.0009], keep_w3=False, compact=True, steps=1)
 
 
+def main_kl():
+    """The four shapes of the Wasserstein fixtures with distance_metric='kl' (compacted)."""
+    kw = dict(metric="kl", keep_w3=False, keep_w1=False, compact=True, steps=1, thresh=2048)
+    gen_stosa("small", dict(item_size=42, maxlen=12, hidden_units=64, num_heads=4, num_layers=1, num_users=4, pvn_weight=0.005), B=4, seed=21,
+              lam1=[0.3], lam2=[0.2], **kw)
+    gen_stosa("l2h2", dict(item_size=33, maxlen=20, hidden_units=64, num_heads=2, num_layers=2, num_users=3, pvn_weight=0.1), B=3, seed=22,
+              lam1=[0.25, 0.1], lam2=[0.15, 0.05], **kw)
+    gen_stosa("h1", dict(item_size=28, maxlen=9, hidden_units=64, num_heads=1, num_layers=1, num_users=2, pvn_weight=0.05), B=2, seed=23,
+              lam1=[0.1], lam2=[0.05], **kw)
+    gen_stosa("cfg5_beauty", dict(item_size=12103, maxlen=100, hidden_units=64, num_heads=4, num_layers=1, num_users=22363, pvn_weight=0.005), B=8,
+              seed=33, lam1=[0.0021], lam2=[0.0009], **kw)
+
+
 if __name__ == "__main__":
+    import argparse
     sys.path.insert(0, REPO)
-    main()
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl"])
+    main(ap.parse_args().metric)

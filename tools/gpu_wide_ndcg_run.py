@@ -55,7 +55,7 @@ def run_bert(seed=23, precision="bf16", use_graph=True, data=None):
     return log
 
 
-def run_stosa(seed=42, precision="bf16", use_graph=True, data=None, deterministic=False):
+def run_stosa(seed=42, precision="bf16", use_graph=True, data=None, deterministic=False, metric="wasserstein", epochs=None):
     """deterministic: dropout 0 and the numpy initial weights oracle.stosa_oracle.init_params(cfg, seed) -- exactly what
     tools/ref_train_wide.py stosa_det gave the reference, so the two runs differ by floating-point rounding only."""
     import torch
@@ -63,12 +63,14 @@ def run_stosa(seed=42, precision="bf16", use_graph=True, data=None, deterministi
     from adt_amd.stosa.models import DisenDistSAModel
     from adt_amd.stosa.trainer import FusedStosaTrainer
     cfg = dict(C.STOSA)
+    if epochs is not None:
+        cfg["epochs"] = epochs
     if deterministic:
         cfg["dropout"] = cfg["attention_dropout"] = 0.0
     train, valid, test, vm, tm, max_item, nu = data or C.stosa_data()
     a = _A()
     a.item_size, a.hidden_units, a.maxlen, a.num_users, a.dropout, a.attention_dropout = max_item + 2, cfg["hidden_units"], cfg["maxlen"], nu, cfg["dropout"], cfg["attention_dropout"]
-    a.num_heads, a.num_layers, a.hidden_act, a.initializer_range, a.distance_metric, a.kernel_param = cfg["num_heads"], cfg["num_layers"], "gelu", 0.02, "wasserstein", 1.0
+    a.num_heads, a.num_layers, a.hidden_act, a.initializer_range, a.distance_metric, a.kernel_param = cfg["num_heads"], cfg["num_layers"], "gelu", 0.02, metric, 1.0
     a.cuda_condition, a.pvn_weight, a.device, a.precision = True, cfg["pvn_weight"], "cuda:0", precision
     torch.manual_seed(seed)
     m = DisenDistSAModel(a)

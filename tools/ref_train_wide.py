@@ -7,6 +7,7 @@ batches come from tools/wide_parity_common.py so that the HIP run (tools/gpu_wid
 
     PYTHONDONTWRITEBYTECODE=1 python tools/ref_train_wide.py bert   # -> tests/golden/ref_ndcg_bert_small.json
     PYTHONDONTWRITEBYTECODE=1 python tools/ref_train_wide.py stosa  # -> tests/golden/ref_ndcg_stosa_small.json
+    PYTHONDONTWRITEBYTECODE=1 python tools/ref_train_wide.py stosa_det_kl  # distance_metric kl -> ref_ndcg_stosa_small_kl_det.json
 """
 import json
 import os
@@ -97,10 +98,24 @@ def run_bert(seed=23, suffix=""):
     json.dump(log, open(os.path.join(OUT, "ref_ndcg_bert_small%s.json" % suffix), "w"), indent=1)
 
 
-def run_stosa(seed=42, suffix="", deterministic=False):
+def kl_full_scores(modules, mo, co, Em, Ec):
+    """kl_predict_full (stosa/trainer.py:481-511) on one eval batch: items padded to a multiple of the batch size, scored in chunks."""
+    V, E = Em.shape[0], mo.shape[0]
+    pad = E - V % E
+    cm = torch.cat((Em, torch.zeros(pad, Em.shape[1])), 0)
+    cc = torch.cat((Ec, torch.ones(pad, Em.shape[1])), 0)
+    res = torch.zeros(E, cm.shape[0])
+    for s0 in range(0, cm.shape[0], E):
+        res[:, s0:s0 + E] = modules.kl_distance_matmul(mo, co, cm[s0:s0 + E], cc[s0:s0 + E])
+    return res[:, :V]
+
+
+def run_stosa(seed=42, suffix="", deterministic=False, metric="wasserstein", epochs=None):
     """deterministic: dropout 0 and the numpy initial weights of oracle.stosa_oracle.init_params(cfg, seed) -- the HIP path starts from
     the same weights (tests/test_ndcg_parity_wide.py), so the two training runs differ by floating-point rounding only."""
     cfg = dict(C.STOSA)
+    if epochs is not None:
+        cfg["epochs"] = epochs
     if deterministic:
         cfg["dropout"] = cfg["attention_dropout"] = 0.0
     models = _import_from("/root/reference/stosa", "models")
@@ -108,7 +123,7 @@ def run_stosa(seed=42, suffix="", deterministic=False):
     train, valid, test, vm, tm, max_item, nu = C.stosa_data()
     a = Args()
     a.item_size, a.hidden_units, a.maxlen, a.num_users, a.dropout, a.attention_dropout = max_item + 2, cfg["hidden_units"], cfg["maxlen"], nu, cfg["dropout"], cfg["attention_dropout"]
-    a.num_heads, a.num_layers, a.hidden_act, a.initializer_range, a.distance_metric, a.kernel_param = cfg["num_heads"], cfg["num_layers"], "gelu", 0.02, "wasserstein", 1.0
+    a.num_heads, a.num_layers, a.hidden_act, a.initializer_range, a.distance_metric, a.kernel_param = cfg["num_heads"], cfg["num_layers"], "gelu", 0.02, metric, 1.0
     a.cuda_condition, a.pvn_weight = False, cfg["pvn_weight"]
     torch.manual_seed(seed)
     m = models.DisenDistSAModel(a)
@@ -117,9 +132,9 @@ def run_stosa(seed=42, suffix="", deterministic=False):
         ocfg = so.Cfg(a.item_size, a.maxlen, a.hidden_units, a.num_heads, a.num_layers, num_users=nu, pvn_weight=cfg["pvn_weight"])
         m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in so.init_params(ocfg, seed).items()}, strict=True)
     opt = torch.optim.Adam(m.parameters(), lr=cfg["lr"], betas=(0.9, 0.999), weight_decay=0.0)
-    wd = modules.wasserstein_distance
+    wd = modules.kl_distance if metric == "kl" else modules.wasserstein_distance
     d, L, H = cfg["hidden_units"], cfg["maxlen"], cfg["num_heads"]
-    log = {"seed": seed, "users": nu, "items": max_item, "cfg": {k: v for k, v in cfg.items()}, "evals": [], "loss": []}
+    log = {"seed": seed, "users": nu, "items": max_item, "cfg": {k: v for k, v in cfg.items()}, "evals": [], "loss": [], "distance_metric": metric}
     t0 = time.time()
 
     def full_sort(ds, matrix):
@@ -129,8 +144,9 @@ def run_stosa(seed=42, suffix="", deterministic=False):
             for s in range(0, len(ds), 256):
                 users, inp, dec, pos, neg, ans = ds.batch(np.arange(s, min(s + 256, len(ds))))
                 mo, co, _, _, _, _, _ = m.finetune(torch.from_numpy(inp).long(), torch.from_numpy(dec).long(), torch.from_numpy(users))
-                dist = modules.wasserstein_distance_matmul(mo[:, -1, :], co[:, -1, :], m.item_mean_embeddings.weight,
-                                                           nn.ELU()(m.item_cov_embeddings.weight) + 1).numpy().copy()
+                full = kl_full_scores if metric == "kl" else (lambda _, *t: modules.wasserstein_distance_matmul(*t))
+                dist = full(modules, mo[:, -1, :], co[:, -1, :], m.item_mean_embeddings.weight,
+                            nn.ELU()(m.item_cov_embeddings.weight) + 1).numpy().copy()
                 dist[matrix[users].toarray() > 0] = 1e24
                 ind = np.argpartition(dist, 40)[:, :40]
                 arr = dist[np.arange(len(dist))[:, None], ind]
@@ -180,6 +196,10 @@ if __name__ == "__main__":
     torch.set_num_threads(4)
     if sys.argv[1] == "stosa_det":      # deterministic run: dropout 0, shared numpy init -> ref_ndcg_stosa_small_det.json
         run_stosa(int(sys.argv[2]) if len(sys.argv) > 2 else 42, "_det", deterministic=True)
+        sys.exit(0)
+    if sys.argv[1] == "stosa_det_kl":   # the same with distance_metric kl -> ref_ndcg_stosa_small_kl_det.json
+        # 10 epochs: the reference's KL loss turns NaN at epoch 14 of this run (log(prod(cov)) over 64 covariances)
+        run_stosa(int(sys.argv[2]) if len(sys.argv) > 2 else 42, "_kl_det", deterministic=True, metric="kl", epochs=10)
         sys.exit(0)
     fn = {"bert": run_bert, "stosa": run_stosa}[sys.argv[1]]
     if len(sys.argv) > 2:          # extra model-init seeds (reference seed spread): ... <mode> <seed> -> *_small_s<seed>.json
