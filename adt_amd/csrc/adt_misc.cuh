@@ -681,7 +681,9 @@ struct RingPrefetchArgs {
 ADT_DEVICE_INLINE void ring_prefetch_body(const RingPrefetchArgs& a, int bid, int nblk) {
   typedef int v4i __attribute__((ext_vector_type(4)));
   const uint32_t k = a.state[0];                      // index of the next batch (this step's k_step_begin has counted its own)
-  if (a.state[4] <= k) return;                        // state[4]: the producer's count as k_step_begin of this step saw it -- the same answer in every workgroup
+  // state[4]: the producer's count as k_step_begin of this step saw it -- the same answer in every workgroup.  Wrap-safe, as the host side: the
+  // 32-bit counters roll over (a plain unsigned compare skipped the prefetch at the step whose producer count had wrapped but state[0] had not)
+  if ((int32_t)(a.state[4] - k) <= 0) return;
   const int32_t* slot = a.ring + (size_t)(k % (uint32_t)a.nslots) * a.slot_ints;
   const size_t nall = a.n_ints / 4, np = a.nparts > 1 ? (size_t)a.nparts : 1;
   const size_t lo = nall * (size_t)(a.nparts > 1 ? a.part : 0) / np, n16 = nall * (size_t)((a.nparts > 1 ? a.part : 0) + 1) / np;
@@ -792,6 +794,8 @@ __global__ __launch_bounds__(256) void k_step_begin(StepBeginArgs a) {
   if (blockIdx.x >= nblk) { pack_wimg_block_lds(a.pk, (int)(blockIdx.x - nblk), spk); return; }
   const unsigned nring = a.ring ? (nblk < (unsigned)SB_RING_BLOCKS ? nblk : (unsigned)SB_RING_BLOCKS) : 0u;
   const bool ring_blk = blockIdx.x < nring;
+  // the normaliser block (eb == 65 below) reads state[0], state[2] and the slot's last words as well: it takes a completion ticket too
+  const unsigned ntk = nring + (a.ring && nblk > nring + 65u ? 1u : 0u);
   const int32_t* slot = nullptr;
   constexpr int RU = 8;
   v4i idv[RU];
@@ -861,13 +865,16 @@ __global__ __launch_bounds__(256) void k_step_begin(StepBeginArgs a) {
         if (i < n16) reinterpret_cast<v4i*>(a.ids_dst)[i] = idv[u];
       }
     }
+  }
+  if (ring_blk || (a.ring && eb == 65u)) {
     // every word this block reads has arrived in registers (it was stored): the block is done with the slot.  The ticket only counts
     // completed READS -- nothing another agent reads is published here, so no release fence (a __threadfence() here wrote back the L2 lines
-    // this block's zero-fill had dirtied, ~6 us) -- and it is taken by the nring reading blocks only (256 tickets on one word were a
-    // chain of 256 same-line atomics, ~5 us).
+    // this block's zero-fill had dirtied, ~6 us) -- and it is taken by the nring reading blocks and the normaliser block only (256 tickets
+    // on one word were a chain of 256 same-line atomics, ~5 us).  Without the normaliser block's ticket the last reader could advance
+    // state[0] and release the slot before that block had resolved the slot: the step then took another batch's n_bce / n_mse / n_nll.
     __syncthreads();
     if (threadIdx.x == 0) {
-      if (atomicAdd(a.state + 1, 1u) == nring - 1) {      // the last reader: every reader has read state[0] and its part of the slot
+      if (atomicAdd(a.state + 1, 1u) == ntk - 1) {      // the last reader: every reader has read state[0] and its part of the slot
         a.state[1] = 0u;
         const uint32_t c = a.state[0] + 1u;
         if (slot == a.staging && a.staging) a.state[5] += 1u;      // statistics: batches taken from the staging buffer
