@@ -4,6 +4,7 @@
 #include "adt_host.h"
 
 #include "adt_attn_gen.cuh"
+#include "adt_attn_stream.cuh"
 #include "adt_gemm.cuh"
 #include "adt_dense_rows.cuh"
 #include "adt_stosa.cuh"
@@ -81,10 +82,35 @@ static int dispatch_attn_gen_l(bool bwd, const AttnGenArgs& a, hipStream_t s) {
   return adt_set_error("masked attention: L=%d > 224 unsupported", a.a.L);
 }
 
+// key / query chunks streamed through LDS (adt_attn_stream.cuh), grid (B*H, groups of NW 16-row tiles): hd = 256 (sasrec d = 256,
+// H = 1), and hd = 128 in the exact-fp32 mode where neither the resident forward nor the two-chunk backward fits the LDS
+template <int PREC, int HD>
+static int launch_attn_stream(bool bwd, const AttnGenArgs& a, hipStream_t s) {
+  constexpr int NWF = 4, NWB = 4, KCF = PREC == PREC_BF16 ? 64 : 32, KCB = 32;
+  const size_t smem = bwd ? AttnStreamLds<PREC, HD, KCB>::bwd_bytes : AttnStreamLds<PREC, HD, KCF>::fwd_bytes;
+  if (smem > 160 * 1024) return adt_set_error("masked attention: hd=%d prec=%d needs %zu B of LDS (> 160 KB)", HD, PREC, smem);
+  const void* fn = bwd ? (const void*)k_attn_stream_bwd<PREC, HD, NWB, KCB> : (const void*)k_attn_stream_fwd<PREC, HD, NWF, KCF>;
+  static bool done[2] = {false, false};
+  if (!done[bwd ? 1 : 0]) {
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+      return adt_set_error("masked attention: hipFuncSetAttribute(%zu)", smem);
+    done[bwd ? 1 : 0] = true;
+  }
+  const int nw = bwd ? NWB : NWF, groups = ((a.a.L + 15) / 16 + nw - 1) / nw;
+  AttnGenArgs args = a;
+  void* kargs[] = {&args};
+  if (hipLaunchKernel(fn, dim3(a.a.B * a.a.H, groups), dim3(nw * 64), kargs, smem, s) != hipSuccess) return adt_set_error("masked attention: launch failed");
+  return check_launch(bwd ? "attn_masked_bwd(streamed)" : "attn_masked_fwd(streamed)");
+}
+
 // hd = 128 (sasrec d = 256, H = 2): forward with the whole (b, h) resident, backward staged in NCH chunks
 template <int PREC, int MAXKT, int NCH>
 static int launch_attn_gen_128(bool bwd, const AttnGenArgs& a, hipStream_t s) {
   constexpr int HD = 128;
+  if constexpr (PREC == PREC_F32) {     // exact fp32 at L > 64: 270 KB resident forward, 272 KB two-chunk backward
+    const size_t need = bwd ? AttnChunkLds<PREC, HD, MAXKT, NCH>::bwd_bytes : AttnGenLds<PREC, HD, MAXKT>::fwd_bytes;
+    if (need > 160 * 1024) return launch_attn_stream<PREC, HD>(bwd, a, s);
+  }
   if (!bwd) {     // causal without key padding (the d = 256 SASRec template): skip the key tiles above the diagonal
     const bool csk = a.a.causal && a.kid == nullptr && a.fill <= -1e9f;
     return csk ? launch_attn_gen<PREC, HD, MAXKT, true>(false, a, s) : launch_attn_gen<PREC, HD, MAXKT, false>(false, a, s);
@@ -102,7 +128,11 @@ static int dispatch_attn_gen(bool bwd, int hd, const AttnGenArgs& a, hipStream_t
     if (a.a.L <= 256) return launch_attn_gen_128<PREC, 16, 2>(bwd, a, s);
     return adt_set_error("masked attention: L=%d > 256 unsupported at head_dim 128", a.a.L);
   }
-  return adt_set_error("masked attention: head_dim=%d unsupported (16/32/64/128)", hd);
+  if (hd == 256) {
+    if (a.a.L >= 1 && a.a.L <= 256) return launch_attn_stream<PREC, 256>(bwd, a, s);
+    return adt_set_error("masked attention: L=%d outside 1..256 at head_dim 256", a.a.L);
+  }
+  return adt_set_error("masked attention: head_dim=%d unsupported (16/32/64/128/256)", hd);
 }
 
 template <class K>

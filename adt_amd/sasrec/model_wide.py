@@ -49,8 +49,8 @@ class SASRecADTWide(FlatModule):
         self.args = args
         self.prec = {"f32": ops.PREC_F32, "fp32": ops.PREC_F32, "bf16": ops.PREC_BF16}[getattr(args, "precision", "bf16")]
         d, H = self.hidden_units, self.num_heads
-        if d % 64 or d > 256 or (d // H) not in (16, 32, 64, 128) or self.maxlen > 256:
-            raise _lib.AdtError("SASRecADT (adt_amd, wide path): hidden_units in {64,128,192,256}, head size 16..128, maxlen <= 256; got d=%d H=%d L=%d"
+        if d % 64 or d > 256 or (d // H) not in (16, 32, 64, 128, 256) or self.maxlen > 256:
+            raise _lib.AdtError("SASRecADT (adt_amd, wide path): hidden_units in {64,128,192,256}, head size 16..256, maxlen <= 256; got d=%d H=%d L=%d"
                                 % (d, H, self.maxlen))
         self._build_flat(param_table(item_num, args.maxlen, d, H, args.num_layers), args.device, REF_ORDER)   # item table first: adt_clip_adam's wd term
         g = torch.Generator(device="cpu").manual_seed(torch.initial_seed() % (1 << 31))

@@ -62,8 +62,10 @@ class SuperSASRecModel(FlatModule):
         self.block = len(self.rec_choice) * len(self.ind_choice)
         self.prec = {"f32": ops.PREC_F32, "fp32": ops.PREC_F32, "bf16": ops.PREC_BF16}[getattr(args, "precision", "bf16")]
         d, H = self.hidden_units, self.num_heads
-        if d != 64 or (d // H) not in (16, 32, 64):
-            raise _lib.AdtError("SuperSASRecModel (adt_amd): built for hidden_units=64 with head size 16/32/64, got d=%d H=%d" % (d, H))
+        hd = d // H if H >= 1 and d % H == 0 else 0
+        if d not in (64, 128, 192, 256) or hd not in (16, 32, 64, 128, 256) or not 1 <= args.maxlen <= (224 if hd <= 64 else 256):
+            raise _lib.AdtError("SuperSASRecModel (adt_amd): hidden_units in {64,128,192,256}, head size in {16,32,64,128,256}, maxlen <= 224 "
+                                "(head size <= 64) or <= 256 (128, 256); got d=%d H=%d L=%d" % (d, H, args.maxlen))
         es, ds = _shapes(d, H)
         table = [("item_emb.weight", (itemnum + 1, d)), ("pos_emb.weight", (args.maxlen, d))]
         for i in range(self.num_layers):
@@ -105,9 +107,10 @@ class SuperSASRecModel(FlatModule):
     _DEC_FIELDS = dict(zip(_lib.DecLayerPtrs.NAMES, _DEC[:14]))
 
     def fused_layers(self):
+        """d = 64 only: wider supernets run every candidate layer on the width-generic stage kernels."""
         if getattr(self, "_fused", None) is None:
             import os
-            on = os.environ.get("ADT_SUPER_FUSED", "1") != "0" and self.prec == ops.PREC_BF16
+            on = os.environ.get("ADT_SUPER_FUSED", "1") != "0" and self.prec == ops.PREC_BF16 and self.hidden_units == 64
             self._fused = bool(on and self.lib.adt_seq_layer_supported(self.prec, self.maxlen, self.hidden_units, self.hidden_units // self.num_heads))
             if self._fused:
                 self._wimg = torch.empty(3 * self.flat.numel(), device=self.dev, dtype=torch.float32)      # 6 bf16 per parameter float
@@ -245,14 +248,21 @@ class SuperSASRecModel(FlatModule):
         return x
 
     def _attn(self, tp, q, kv, B, site, qkv=None):
-        """Causal attention on packed projections; q: (T, d) Act, kv: (T, 2d) Act (or qkv: one (T, 3d) Act)."""
+        """Causal attention on packed projections; q: (T, d) Act, kv: (T, 2d) Act (or qkv: one (T, 3d) Act).  d = 64: the
+        per-sequence causal kernels (ops.attn_fwd / attn_bwd); other widths: the general masked attention with the float causal
+        mask of sasrec/modules.py (fill -inf), as SASRecADTWide._attn."""
         d, H, L = self.hidden_units, self.num_heads, self.maxlen
         p = tp.p_eff(self.dropout)
         if qkv is not None:
             Q, K, V = qkv.t[:, :d], qkv.t[:, d:2 * d], qkv.t[:, 2 * d:]
         else:
             Q, K, V = q.t, kv.t[:, :d], kv.t[:, d:]
-        O, LSE = ops.attn_fwd(self.prec, Q, K, V, B, H, L, True, p, self._seed, site, tp.b_offset)
+        general = d != 64
+        fill = float("-inf")
+        if general:
+            O, LSE = ops.attn_masked_fwd(self.prec, Q, K, V, B, H, L, True, None, fill, p, self._seed, site, tp.b_offset)
+        else:
+            O, LSE = ops.attn_fwd(self.prec, Q, K, V, B, H, L, True, p, self._seed, site, tp.b_offset)
         o = Act(O)
 
         def bw():
@@ -264,7 +274,10 @@ class SuperSASRecModel(FlatModule):
             else:
                 q.g, kv.g = torch.empty_like(q.t), torch.empty_like(kv.t)
                 out = (q.g, kv.g[:, :d], kv.g[:, d:])
-            ops.attn_bwd(self.prec, Q, K, V, O, LSE, o.g, B, H, L, True, p, self._seed, site, tp.b_offset, out=out)
+            if general:
+                ops.attn_masked_bwd(self.prec, Q, K, V, O, LSE, o.g, B, H, L, True, None, fill, p, self._seed, site, tp.b_offset, out=out)
+            else:
+                ops.attn_bwd(self.prec, Q, K, V, O, LSE, o.g, B, H, L, True, p, self._seed, site, tp.b_offset, out=out)
         tp.bw.append(bw)
         return o
 

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Stand-alone timing of the masked / general attention kernels (adt_attn_masked_fwd/bwd) at the BERT ml-20m and SASRec d=256 shapes,
-with and without dropout (the backward regenerates the dropout hash in both of its passes)."""
+with and without dropout (the backward regenerates the dropout hash in both of its passes); head size 256 (d = 256, one head: the
+reference's search default, adt_attn_stream.cuh) next to head size 128 at the same L, with achieved TFLOP/s (causal: half the
+score / PV work of the full L x L products is counted)."""
 import os
 import sys
 
@@ -16,7 +18,10 @@ from tools.bench_dense import timeit  # noqa: E402
 def main():
     dev = torch.device("cuda:0")
     seed = torch.tensor([7], device=dev, dtype=torch.int32)
-    for name, B, H, L, hd, causal in (("bert ml-20m", 256, 4, 200, 64, False), ("sasrec d=256", 256, 2, 200, 128, True)):
+    shapes = [("bert ml-20m", 256, 4, 200, 64, False), ("sasrec d=256", 256, 2, 200, 128, True)]
+    for L in (50, 200):
+        shapes += [("hd128 L=%d" % L, 256, 2, L, 128, True), ("hd256 L=%d" % L, 256, 1, L, 256, True)]
+    for name, B, H, L, hd, causal in shapes:
         d = H * hd
         T = B * L
         qkv = torch.randn(T, 3 * d, device=dev)
@@ -28,7 +33,9 @@ def main():
             O, LSE = ops.attn_masked_fwd(ops.PREC_BF16, Q, K, V, B, H, L, causal, kid, -1e9, p, seed, 3, 0)
             t_f = timeit(lambda: ops.attn_masked_fwd(ops.PREC_BF16, Q, K, V, B, H, L, causal, kid, -1e9, p, seed, 3, 0))
             t_b = timeit(lambda: ops.attn_masked_bwd(ops.PREC_BF16, Q, K, V, O, LSE, dO, B, H, L, causal, kid, -1e9, p, seed, 3, 0))
-            print("%-13s p=%.1f  fwd %7.1f us  bwd %7.1f us" % (name, p, t_f, t_b), flush=True)
+            flop = 4.0 * B * H * L * L * hd * (0.5 if causal else 1.0)         # QK^T + PV; the backward does 2.5x that (S, dP, dQ, dK, dV)
+            print("%-13s p=%.1f  fwd %7.1f us %6.1f TFLOP/s  bwd %7.1f us %6.1f TFLOP/s" % (name, p, t_f, flop / t_f * 1e-6, t_b, 2.5 * flop / t_b * 1e-6),
+                  flush=True)
 
 
 if __name__ == "__main__":

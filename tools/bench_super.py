@@ -4,6 +4,7 @@ steps/s (SuperTrainer.step: four candidate layers per depth, mixed) and candidat
 candidate at a time (the reference's check_cand granularity) against the batched evaluation of adt_amd/supersearch.py.
 
     python tools/bench_super.py [--batch 256] [--eval-batch 512] [--cands 32]
+    python tools/bench_super.py --hidden_units 256 --num_heads 1 --num_layers 4 --maxlen 50     # the reference's search defaults
 """
 import argparse
 import json
@@ -33,8 +34,11 @@ def main():
     ap.add_argument("--cands", type=int, default=32)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--precision", default="bf16")
+    C = dict(bench.CFG)
+    for k in ("hidden_units", "num_heads", "num_layers", "maxlen"):       # defaults: the ml-1m flagship shape
+        ap.add_argument("--" + k, type=int, default=C[k])
     a = ap.parse_args()
-    C = bench.CFG
+    C.update({k: getattr(a, k) for k in ("hidden_units", "num_heads", "num_layers", "maxlen")})
     args = Args()
     args.device, args.num_heads, args.maxlen, args.num_layers, args.hidden_units, args.dropout, args.precision = "cuda:0", C["num_heads"], C["maxlen"], C["num_layers"], C["hidden_units"], C["dropout"], a.precision
     rec_choice = [0, 0.0001, 0.0005, 0.001, 0.005, 0.01]
@@ -53,7 +57,8 @@ def main():
         tr.step(*batches[i % 2])
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
-    res = {"supernet_warmup": {"ms_per_step": round(dt * 1e3, 3), "sequences_per_s": round(a.batch / dt, 1), "batch": a.batch, "precision": a.precision}}
+    res = {"shape": {k: C[k] for k in ("hidden_units", "num_heads", "num_layers", "maxlen")}, "parameters": int(m.flat.numel()),
+           "supernet_warmup": {"ms_per_step": round(dt * 1e3, 3), "sequences_per_s": round(a.batch / dt, 1), "batch": a.batch, "precision": a.precision}}
     # candidate evaluation: one validation batch (eval-batch users x 101 candidates items)
     seq = batches[0][0][:a.eval_batch] if a.eval_batch <= a.batch else np.tile(batches[0][0], ((a.eval_batch + a.batch - 1) // a.batch, 1))[:a.eval_batch]
     items = r.randint(1, C["item_num"] + 1, size=(a.eval_batch, 101)).astype(np.int32)
@@ -84,7 +89,8 @@ def main():
     t2 = time.perf_counter()
     res["candidate_evaluation"] = {"candidates": a.cands, "eval_batch": a.eval_batch, "one_at_a_time_ms": round((t1 - t0) * 1e3, 2),
                                    "batched_ms": round((t2 - t1) * 1e3, 2), "speedup": round((t1 - t0) / (t2 - t1), 2), "identical_ranks": same,
-                                   "layer_calls_batched": stats.get("layer_calls"), "layer_calls_one_at_a_time": 4 * C["num_layers"] * a.cands}
+                                   "layer_calls_batched": stats.get("layer_calls"), "layer_calls_one_at_a_time": 4 * C["num_layers"] * a.cands,
+                                   "candidates_per_s_batched": round(a.cands / (t2 - t1), 1)}
     print(json.dumps(res))
 
 

@@ -29,7 +29,9 @@ class Args:
     pass
 
 
-def gen(tag, item_num, L, d, H, nl, rec_choice, ind_choice, B, seed, cand, wd=1e-4, lr=1e-3, clip=5.0):
+def gen(tag, item_num, L, d, H, nl, rec_choice, ind_choice, B, seed, cand, wd=1e-4, lr=1e-3, clip=5.0, wide=False):
+    """wide: the d >= 128 fixtures -- predict under a second block choice and the weights after the second Adam step are recorded too,
+    and the file is compacted (norms + K = 96 strided samples, tools/gen_golden_super_wide.py) to stay under ~1 MB."""
     import supersasrec
     cfg = su.Cfg(item_num, L, d, H, nl, rec_choice, ind_choice)
     P = su.init_params(cfg, seed)
@@ -52,6 +54,14 @@ def gen(tag, item_num, L, d, H, nl, rec_choice, ind_choice, B, seed, cand, wd=1e
         items = np.random.RandomState(seed + 2).randint(1, item_num + 1, size=(B, 7))
         out["items"] = items
         out["predict"] = m.predict(np.zeros(B), seq, items).numpy()
+        if wide:
+            cand2 = [1.0 - c for c in cand]
+            block2 = su.cand_to_block(cfg, cand2)[0]
+            m.set_choice(block2)
+            pl2, nl2 = m(np.zeros(B), seq, dec, pos, neg)[:2]
+            out["cand2"], out["pos_logits2"], out["neg_logits2"] = np.array(cand2), pl2.numpy(), nl2.numpy()
+            out["predict2"] = m.predict(np.zeros(B), seq, items).numpy()
+            m.set_choice(block)
     m.train()
     bce = torch.nn.BCEWithLogitsLoss()
     opt = torch.optim.Adam(m.parameters(), lr=lr, betas=(0.9, 0.999), weight_decay=wd)
@@ -88,11 +98,25 @@ def gen(tag, item_num, L, d, H, nl, rec_choice, ind_choice, B, seed, cand, wd=1e
             used = [k for k, p in m.named_parameters() if p.grad is not None]
             for k in used[:40] + ["item_emb.weight"]:
                 out["w1." + k] = dict(m.named_parameters())[k].detach().numpy().copy()
+        elif wide:
+            for k in used[:40] + ["item_emb.weight"]:
+                out["w2." + k] = dict(m.named_parameters())[k].detach().numpy().copy()
     path = os.path.join(OUT, "super_%s.npz" % tag)
+    if wide:
+        from tools.gen_golden_inputs import compact
+        keep = ("predict", "predict2", "pos_logits", "neg_logits", "pos_logits2", "neg_logits2") + tuple("rec_%d" % i for i in range(nl))
+        out = compact(out, keep=keep, k=96, thresh=600)     # rec rows are permuted in the reference (modules.py:518): kept whole
     np.savez_compressed(path, **out)
     print("wrote", path, "loss", out["loss"], "grad_norm", out["grad_norm"], "none", len(out["grad_none"]), "%.1f KB" % (os.path.getsize(path) / 1024))
 
 
 if __name__ == "__main__":
-    gen("c3", 30, 12, 64, 2, 1, [0, 0.001, 0.01], [0, 0.0005, 0.002], B=3, seed=31, cand=[0.7, 0.2])
-    gen("l2", 25, 10, 64, 2, 2, [0, 0.01], [0, 0.002], B=2, seed=32, cand=[0.3, 0.9, 0.6, 0.4])
+    which = sys.argv[1:] or ["d64"]          # `wide`: the d >= 128 fixtures
+    if "d64" in which:
+        gen("c3", 30, 12, 64, 2, 1, [0, 0.001, 0.01], [0, 0.0005, 0.002], B=3, seed=31, cand=[0.7, 0.2])
+        gen("l2", 25, 10, 64, 2, 2, [0, 0.01], [0, 0.002], B=2, seed=32, cand=[0.3, 0.9, 0.6, 0.4])
+    if "wide" in which:
+        # the reference's default search width and head (head size 256), head size 128 at the ml-1m template length, one 128-wide head
+        gen("d256h1", 40, 50, 256, 1, 2, [0, 0.001, 0.01], [0, 0.0005, 0.002], B=2, seed=33, cand=[0.7, 0.2, 0.4, 0.9], wide=True)
+        gen("d256h2", 40, 200, 256, 2, 1, [0, 0.001, 0.01], [0, 0.0005, 0.002], B=2, seed=34, cand=[0.3, 0.6], wide=True)
+        gen("d128h1", 40, 64, 128, 1, 1, [0, 0.001, 0.01], [0, 0.0005, 0.002], B=3, seed=35, cand=[0.8, 0.1], wide=True)
