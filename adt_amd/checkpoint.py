@@ -52,21 +52,30 @@ def load_trainer_state_dict(tr, sd):
 
 
 def _param_spans(model):
-    base = model.flat.data_ptr()
+    """(parameter, offset) in model.parameters() order.  Offsets are into the flat buffer, or -- for a model that computes on a padded
+    layout (adt_amd/wide.py:padded_layout) -- into its densely packed reference-shaped copy: the moments are then stripped of their
+    pad lanes on export and get them back (as zeros) on import, so the torch side sees the reference's shapes only."""
+    master = model.flat if getattr(model, "ref_flat", None) is None else model.ref_flat
+    base = master.data_ptr()
     for p in model.parameters():
         off = (p.data_ptr() - base) // 4
-        assert 0 <= off and off + p.numel() <= model.flat.numel(), "parameter outside the flat buffer"
+        assert 0 <= off and off + p.numel() <= master.numel(), "parameter outside the flat buffer"
         yield p, off
+
+
+def _padded(model):
+    return getattr(model, "ref_flat", None) is not None
 
 
 def to_torch_adam_state(tr, weight_decay=0.0, skip_untrained=True):
     """torch.optim.Adam(model.parameters(), lr, betas, eps, weight_decay).state_dict() equivalent of the trainer's state."""
     step = _scal_step(tr)
     state, ids = {}, []
+    tm, tv = (tr.model.compact(tr.m), tr.model.compact(tr.v)) if _padded(tr.model) else (tr.m, tr.v)
     for i, (p, off) in enumerate(_param_spans(tr.model)):
         ids.append(i)
-        m = tr.m[off:off + p.numel()].view(p.shape)
-        v = tr.v[off:off + p.numel()].view(p.shape)
+        m = tm[off:off + p.numel()].view(p.shape)
+        v = tv[off:off + p.numel()].view(p.shape)
         if skip_untrained and not bool(v.any()) and not bool(m.any()):
             continue
         state[i] = {"step": torch.tensor(step), "exp_avg": m.detach().clone(), "exp_avg_sq": v.detach().clone()}
@@ -80,13 +89,18 @@ def from_torch_adam_state(tr, osd):
     tr.m.zero_()
     tr.v.zero_()
     step = 0.0
+    pad = _padded(tr.model)
+    tm, tv = (torch.zeros_like(tr.model.ref_flat), torch.zeros_like(tr.model.ref_flat)) if pad else (tr.m, tr.v)
     for i, (p, off) in enumerate(_param_spans(tr.model)):
         st = osd["state"].get(i)
         if st is None:
             continue
-        tr.m[off:off + p.numel()].copy_(st["exp_avg"].reshape(-1))
-        tr.v[off:off + p.numel()].copy_(st["exp_avg_sq"].reshape(-1))
+        tm[off:off + p.numel()].copy_(st["exp_avg"].reshape(-1))
+        tv[off:off + p.numel()].copy_(st["exp_avg_sq"].reshape(-1))
         step = max(step, float(st["step"]))
+    if pad:
+        tr.model.expand_into(tr.m, tm)
+        tr.model.expand_into(tr.v, tv)
     tr.scal[2] = step
     tr.nstep = int(step)
 

@@ -10,6 +10,7 @@
 #include "adt_stosa.cuh"
 #include "adt_klattn.cuh"
 #include "adt_wattn_mfma.cuh"
+#include "adt_lanes.cuh"
 #include "adt_wide.cuh"
 
 using namespace adt;
@@ -489,25 +490,42 @@ static int fill_attn(AttnGenArgs& g, const float* Q, int ldq, const float* K, in
   return 0;
 }
 
+// scale <= 0: the kernels' own 1 / sqrt(hd) (fill_attn); else the caller's score scale (heads padded with zero lanes)
+static int attn_masked_fwd_impl(int prec, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int B, int H, int L, int hd,
+                                float scale, int causal, const int32_t* key_ids, float fill, float p, const uint32_t* seed, uint32_t site,
+                                uint32_t b_offset, float* O, int ldo, float* LSE, void* stream) {
+  AttnGenArgs g{};
+  if (fill_attn(g, Q, ldq, K, ldk, V, ldv, B, H, L, hd, causal, key_ids, fill, p, seed, site, b_offset)) return -1;
+  if (scale > 0.f) g.a.scale = scale;
+  g.a.O = O; g.a.ldo = ldo; g.a.LSE = LSE;
+  return prec == ADT_PREC_F32 ? dispatch_attn_gen<PREC_F32>(false, hd, g, (hipStream_t)stream) : dispatch_attn_gen<PREC_BF16>(false, hd, g, (hipStream_t)stream);
+}
+
+static int attn_masked_bwd_impl(int prec, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, const float* O, int ldo,
+                                const float* LSE, const float* dO, int lddo, int B, int H, int L, int hd, float scale, int causal,
+                                const int32_t* key_ids, float fill, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQ,
+                                int lddq, float* dK, int lddk, float* dV, int lddv, void* stream) {
+  AttnGenArgs g{};
+  if (fill_attn(g, Q, ldq, K, ldk, V, ldv, B, H, L, hd, causal, key_ids, fill, p, seed, site, b_offset)) return -1;
+  if ((ldo % 4) || (lddo % 4) || (lddq % 4) || (lddk % 4) || (lddv % 4)) return adt_set_error("masked attention bwd: ld %% 4");
+  if (scale > 0.f) g.a.scale = scale;
+  g.a.O = const_cast<float*>(O); g.a.ldo = ldo; g.a.LSE = const_cast<float*>(LSE); g.a.dO = dO; g.a.lddo = lddo;
+  g.a.dQ = dQ; g.a.lddq = lddq; g.a.dK = dK; g.a.lddk = lddk; g.a.dV = dV; g.a.lddv = lddv;
+  return prec == ADT_PREC_F32 ? dispatch_attn_gen<PREC_F32>(true, hd, g, (hipStream_t)stream) : dispatch_attn_gen<PREC_BF16>(true, hd, g, (hipStream_t)stream);
+}
+
 int adt_attn_masked_fwd(int prec, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int B, int H, int L, int hd,
                         int causal, const int32_t* key_ids, float fill, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset,
                         float* O, int ldo, float* LSE, void* stream) {
-  AttnGenArgs g{};
-  if (fill_attn(g, Q, ldq, K, ldk, V, ldv, B, H, L, hd, causal, key_ids, fill, p, seed, site, b_offset)) return -1;
-  g.a.O = O; g.a.ldo = ldo; g.a.LSE = LSE;
-  return prec == ADT_PREC_F32 ? dispatch_attn_gen<PREC_F32>(false, hd, g, (hipStream_t)stream) : dispatch_attn_gen<PREC_BF16>(false, hd, g, (hipStream_t)stream);
+  return attn_masked_fwd_impl(prec, Q, ldq, K, ldk, V, ldv, B, H, L, hd, 0.f, causal, key_ids, fill, p, seed, site, b_offset, O, ldo, LSE, stream);
 }
 
 int adt_attn_masked_bwd(int prec, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, const float* O, int ldo,
                         const float* LSE, const float* dO, int lddo, int B, int H, int L, int hd, int causal, const int32_t* key_ids,
                         float fill, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQ, int lddq, float* dK,
                         int lddk, float* dV, int lddv, void* stream) {
-  AttnGenArgs g{};
-  if (fill_attn(g, Q, ldq, K, ldk, V, ldv, B, H, L, hd, causal, key_ids, fill, p, seed, site, b_offset)) return -1;
-  if ((ldo % 4) || (lddo % 4) || (lddq % 4) || (lddk % 4) || (lddv % 4)) return adt_set_error("masked attention bwd: ld %% 4");
-  g.a.O = const_cast<float*>(O); g.a.ldo = ldo; g.a.LSE = const_cast<float*>(LSE); g.a.dO = dO; g.a.lddo = lddo;
-  g.a.dQ = dQ; g.a.lddq = lddq; g.a.dK = dK; g.a.lddk = lddk; g.a.dV = dV; g.a.lddv = lddv;
-  return prec == ADT_PREC_F32 ? dispatch_attn_gen<PREC_F32>(true, hd, g, (hipStream_t)stream) : dispatch_attn_gen<PREC_BF16>(true, hd, g, (hipStream_t)stream);
+  return attn_masked_bwd_impl(prec, Q, ldq, K, ldk, V, ldv, O, ldo, LSE, dO, lddo, B, H, L, hd, 0.f, causal, key_ids, fill, p, seed, site, b_offset,
+                              dQ, lddq, dK, lddk, dV, lddv, stream);
 }
 
 int adt_embed_sum_fwd(const int32_t* ids, const float* E, const float* P, const float* S0, float scale, int T, int L, int d, float* X,
@@ -829,6 +847,94 @@ int adt_dense_gradsrc(const float* dY, int lddy, int T, int N, const int32_t* ma
   a.out = G; a.ldo = ldg; a.t_dev = t_dev;
   hipLaunchKernelGGL(k_gradsrc, dim3(grid_for((size_t)T * (N / 4), 1024, 4096)), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("dense_gradsrc");
+}
+
+}  // extern "C"
+
+// ---- widths that are not multiples of 64: padded lanes, true-width arithmetic (adt_lanes.cuh) -----------------------------------------
+static int make_lanes(Lanes& ln, int H, int hd, int hd_pad, const char* what) {
+  int sh = 0;
+  while ((1 << sh) < hd_pad) ++sh;
+  const int dp = H * hd_pad;
+  if (H < 1 || hd < 1 || hd > hd_pad || (1 << sh) != hd_pad || hd_pad < 16 || hd_pad > 256 || (dp % 64) || dp > 256)
+    return adt_set_error("%s: lanes H=%d hd=%d hd_pad=%d: hd_pad a power of two in 16..256, H * hd_pad in {64,128,192,256}", what, H, hd, hd_pad);
+  ln.H = H; ln.hd = hd; ln.hd_pad = hd_pad; ln.sh = sh;
+  return 0;
+}
+
+template <typename K64, typename K128, typename K192, typename K256>
+static void launch_by_width(int dp, K64 k64, K128 k128, K192 k192, K256 k256, int grid, hipStream_t s, const LnLanesArgs& a) {
+  if (dp == 64) hipLaunchKernelGGL(k64, dim3(grid), dim3(LN_LANES_THREADS), 0, s, a);
+  else if (dp == 128) hipLaunchKernelGGL(k128, dim3(grid), dim3(LN_LANES_THREADS), 0, s, a);
+  else if (dp == 192) hipLaunchKernelGGL(k192, dim3(grid), dim3(LN_LANES_THREADS), 0, s, a);
+  else hipLaunchKernelGGL(k256, dim3(grid), dim3(LN_LANES_THREADS), 0, s, a);
+}
+
+extern "C" {
+
+int adt_layernorm_lanes_fwd(const float* X, int ldx, const float* gamma, const float* beta, float eps, int T, int H, int hd, int hd_pad,
+                            float* Y, int ldy, void* stream) {
+  LnLanesArgs a{};
+  if (make_lanes(a.ln, H, hd, hd_pad, "layernorm_lanes_fwd")) return -1;
+  if (T <= 0) return 0;
+  if ((ldx % 4) || (ldy % 4) || ldx < H * hd_pad || ldy < H * hd_pad || !aligned16(X) || !aligned16(Y) || !aligned16(gamma) || !aligned16(beta))
+    return adt_set_error("layernorm_lanes_fwd: ld %% 4, ld >= d_pad and 16-byte alignment required");
+  a.X = X; a.ldx = ldx; a.gamma = gamma; a.beta = beta; a.eps = eps; a.Y = Y; a.ldy = ldy; a.T = T;
+  launch_by_width(H * hd_pad, k_ln_lanes_fwd<64>, k_ln_lanes_fwd<128>, k_ln_lanes_fwd<192>, k_ln_lanes_fwd<256>, grid_for(T, 16, 2048),
+                  (hipStream_t)stream, a);
+  return check_launch("layernorm_lanes_fwd");
+}
+
+int adt_layernorm_lanes_bwd(const float* dY, int lddy, const float* X, int ldx, const float* gamma, float eps, int T, int H, int hd, int hd_pad,
+                            float* dX, int lddx, int accumulate, float* dgamma, float* dbeta, void* stream) {
+  LnLanesArgs a{};
+  if (make_lanes(a.ln, H, hd, hd_pad, "layernorm_lanes_bwd")) return -1;
+  if (T <= 0) return 0;
+  const int dp = H * hd_pad;
+  if ((ldx % 4) || (lddy % 4) || (lddx % 4) || ldx < dp || lddy < dp || lddx < dp || !aligned16(X) || !aligned16(dY) || !aligned16(dX) || !aligned16(gamma))
+    return adt_set_error("layernorm_lanes_bwd: ld %% 4, ld >= d_pad and 16-byte alignment required");
+  a.X = X; a.ldx = ldx; a.gamma = gamma; a.eps = eps; a.T = T; a.dY = dY; a.lddy = lddy; a.dX = dX; a.lddx = lddx;
+  a.acc = accumulate; a.dgamma = dgamma; a.dbeta = dbeta;
+  launch_by_width(dp, k_ln_lanes_bwd<64>, k_ln_lanes_bwd<128>, k_ln_lanes_bwd<192>, k_ln_lanes_bwd<256>, grid_for(T, 16, 256), (hipStream_t)stream, a);
+  return check_launch("layernorm_lanes_bwd");
+}
+
+int adt_drop_lanes(const float* S, int lds, const float* R, int ldr, const float* R2, int ldr2, const int32_t* mask_ids, int T, int H, int hd,
+                   int hd_pad, float p, const uint32_t* seed, uint32_t site, uint32_t row_offset, float* out, int ldo, void* stream) {
+  DropLanesArgs a{};
+  if (make_lanes(a.ln, H, hd, hd_pad, "drop_lanes")) return -1;
+  if (T <= 0) return 0;
+  const int dp = H * hd_pad;
+  if ((lds % 4) || (ldo % 4) || lds < dp || ldo < dp || !aligned16(S) || !aligned16(out) || (R && ((ldr % 4) || ldr < dp || !aligned16(R))) ||
+      (R2 && ((ldr2 % 4) || ldr2 < dp || !aligned16(R2))))
+    return adt_set_error("drop_lanes: ld %% 4, ld >= d_pad and 16-byte alignment required");
+  a.S = S; a.lds = lds; a.R = R; a.ldr = ldr; a.R2 = R2; a.ldr2 = ldr2; a.ids = mask_ids; a.out = out; a.ldo = ldo; a.T = T;
+  a.drop = adt_make_drop(p, seed, site); a.row_offset = row_offset;
+  hipLaunchKernelGGL(k_drop_lanes, dim3(grid_for((size_t)T * (dp / 4), 1024, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("drop_lanes");
+}
+
+int adt_lane_map(float* padded, float* compact, const int32_t* map, int64_t n, int scatter, void* stream) {
+  if (n <= 0) return 0;
+  LaneMapArgs a{padded, compact, map, (size_t)n, scatter};
+  hipLaunchKernelGGL(k_lane_map, dim3(grid_for((size_t)n, 1024, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("lane_map");
+}
+
+int adt_attn_masked_scaled_fwd(int prec, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int B, int H, int L, int hd,
+                               float scale, int causal, const int32_t* key_ids, float fill, float p, const uint32_t* seed, uint32_t site,
+                               uint32_t b_offset, float* O, int ldo, float* LSE, void* stream) {
+  if (!(scale > 0.f)) return adt_set_error("attn_masked_scaled_fwd: scale %g must be positive", (double)scale);
+  return attn_masked_fwd_impl(prec, Q, ldq, K, ldk, V, ldv, B, H, L, hd, scale, causal, key_ids, fill, p, seed, site, b_offset, O, ldo, LSE, stream);
+}
+
+int adt_attn_masked_scaled_bwd(int prec, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, const float* O, int ldo,
+                               const float* LSE, const float* dO, int lddo, int B, int H, int L, int hd, float scale, int causal,
+                               const int32_t* key_ids, float fill, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQ,
+                               int lddq, float* dK, int lddk, float* dV, int lddv, void* stream) {
+  if (!(scale > 0.f)) return adt_set_error("attn_masked_scaled_bwd: scale %g must be positive", (double)scale);
+  return attn_masked_bwd_impl(prec, Q, ldq, K, ldk, V, ldv, O, ldo, LSE, dO, lddo, B, H, L, hd, scale, causal, key_ids, fill, p, seed, site, b_offset,
+                              dQ, lddq, dK, lddk, dV, lddv, stream);
 }
 
 }  // extern "C"

@@ -257,18 +257,25 @@ def dense_bwd(prec, dY, X, W, dW=None, db=None, dX=None, beta=False, act=ACT_NON
                                          _p(db), _p(t_dev), _stream()), "dense_bwd")
 
 
-def attn_masked_fwd(prec, Q, K, V, B, H, L, causal=False, key_ids=None, fill=-1e9, p=0.0, seed=None, site=0, b_offset=0):
+def attn_masked_fwd(prec, Q, K, V, B, H, L, causal=False, key_ids=None, fill=-1e9, p=0.0, seed=None, site=0, b_offset=0, scale=None):
+    """scale: score scale when it is not 1 / sqrt(hd) (heads padded with zero lanes keep 1 / sqrt(true head size))."""
     d = Q.shape[1]
     hd = d // H
     O = torch.empty(B * L, d, device=Q.device, dtype=torch.float32)
     LSE = torch.empty(B * H * L, device=Q.device, dtype=torch.float32)
+    if scale is not None:
+        _lib.check(_lib.load().adt_attn_masked_scaled_fwd(prec, _p(_f32(Q)), _ld(Q), _p(_f32(K)), _ld(K), _p(_f32(V)), _ld(V), B, H, L, hd, float(scale),
+                                                          int(causal), _p(key_ids), float(fill), float(p), _p(seed), site, b_offset, _p(O), d, _p(LSE),
+                                                          _stream()), "attn_masked_scaled_fwd")
+        return O, LSE
     _lib.check(_lib.load().adt_attn_masked_fwd(prec, _p(_f32(Q)), _ld(Q), _p(_f32(K)), _ld(K), _p(_f32(V)), _ld(V), B, H, L, hd, int(causal),
                                                _p(key_ids), float(fill), float(p), _p(seed), site, b_offset, _p(O), d, _p(LSE), _stream()),
                "attn_masked_fwd")
     return O, LSE
 
 
-def attn_masked_bwd(prec, Q, K, V, O, LSE, dO, B, H, L, causal=False, key_ids=None, fill=-1e9, p=0.0, seed=None, site=0, b_offset=0, out=None):
+def attn_masked_bwd(prec, Q, K, V, O, LSE, dO, B, H, L, causal=False, key_ids=None, fill=-1e9, p=0.0, seed=None, site=0, b_offset=0, out=None,
+                    scale=None):
     d = Q.shape[1]
     hd = d // H
     if out is None:
@@ -277,6 +284,12 @@ def attn_masked_bwd(prec, Q, K, V, O, LSE, dO, B, H, L, causal=False, key_ids=No
         dV = torch.empty_like(dQ)
     else:
         dQ, dK, dV = out
+    if scale is not None:
+        _lib.check(_lib.load().adt_attn_masked_scaled_bwd(prec, _p(_f32(Q)), _ld(Q), _p(_f32(K)), _ld(K), _p(_f32(V)), _ld(V), _p(_f32(O)), _ld(O),
+                                                          _p(LSE), _p(_f32(dO)), _ld(dO), B, H, L, hd, float(scale), int(causal), _p(key_ids),
+                                                          float(fill), float(p), _p(seed), site, b_offset, _p(dQ), _ld(dQ), _p(dK), _ld(dK), _p(dV),
+                                                          _ld(dV), _stream()), "attn_masked_scaled_bwd")
+        return dQ, dK, dV
     _lib.check(_lib.load().adt_attn_masked_bwd(prec, _p(_f32(Q)), _ld(Q), _p(_f32(K)), _ld(K), _p(_f32(V)), _ld(V), _p(_f32(O)), _ld(O), _p(LSE),
                                                _p(_f32(dO)), _ld(dO), B, H, L, hd, int(causal), _p(key_ids), float(fill), float(p), _p(seed), site,
                                                b_offset, _p(dQ), _ld(dQ), _p(dK), _ld(dK), _p(dV), _ld(dV), _stream()), "attn_masked_bwd")
@@ -567,3 +580,41 @@ def posemb_sum(ids_list, dX_list, sites, B, L, p, seed, row_offset, dP):
     s = (ctypes.c_uint32 * 2)(*[int(sites[i]) if i < n else 0 for i in range(2)])
     _lib.check(_lib.load().adt_posemb_sum(_ptr_array([_i32(t) for t in ids_list], 2), _ptr_array(dX_list, 2), s, n, B, L, float(p), _p(seed),
                                           row_offset, _p(_f32(dP)), _stream()), "posemb_sum")
+
+
+# ---- widths that are not multiples of 64: padded lanes, true-width arithmetic (include/adt_hip.h; adt_amd/wide.py:padded_layout) ---------
+def layernorm_lanes_fwd(X, gamma, beta, eps, lanes):
+    """LayerNorm over the live lanes of padded rows; lanes = (H, hd, hd_pad), X is (T, H * hd_pad) with zero pad lanes."""
+    H, hd, hd_pad = lanes
+    T, dp = X.shape
+    assert dp == H * hd_pad, (X.shape, lanes)
+    Y = torch.empty(T, dp, device=X.device, dtype=torch.float32)
+    _lib.check(_lib.load().adt_layernorm_lanes_fwd(_p(_f32(X)), _ld(X), _p(gamma), _p(beta), eps, T, H, hd, hd_pad, _p(Y), dp, _stream()), "ln_lanes_fwd")
+    return Y
+
+
+def layernorm_lanes_bwd(dY, X, gamma, eps, dX, accumulate, dgamma, dbeta, lanes):
+    H, hd, hd_pad = lanes
+    T, dp = X.shape
+    assert dp == H * hd_pad, (X.shape, lanes)
+    _lib.check(_lib.load().adt_layernorm_lanes_bwd(_p(_f32(dY)), _ld(dY), _p(_f32(X)), _ld(X), _p(gamma), eps, T, H, hd, hd_pad, _p(dX), _ld(dX),
+                                                   int(accumulate), _p(dgamma), _p(dbeta), _stream()), "ln_lanes_bwd")
+
+
+def drop_lanes(S, lanes, p=0.0, seed=None, site=0, row_offset=0, R=None, R2=None, mask_ids=None, out=None):
+    """out = rowmask(R + R2 + dropout(S)) on the live lanes (dropout indexed at the true width), exact zeros on the pad lanes.
+    out may be S itself (every element is read and written by the same thread)."""
+    H, hd, hd_pad = lanes
+    T, dp = S.shape
+    assert dp == H * hd_pad, (S.shape, lanes)
+    if out is None:
+        out = torch.empty(T, dp, device=S.device, dtype=torch.float32)
+    _lib.check(_lib.load().adt_drop_lanes(_p(_f32(S)), _ld(S), _p(R), _ld(R), _p(R2), _ld(R2), _p(mask_ids), T, H, hd, hd_pad, float(p), _p(seed), site,
+                                          row_offset, _p(_f32(out)), _ld(out), _stream()), "drop_lanes")
+    return out
+
+
+def lane_map(padded, compact, index, scatter):
+    """compact[i] = padded[index[i]] (scatter False) or padded[index[i]] = compact[i] (scatter True)."""
+    assert padded.dtype == torch.float32 and compact.dtype == torch.float32 and compact.is_contiguous() and compact.numel() == index.numel()
+    _lib.check(_lib.load().adt_lane_map(_p(padded), _p(compact), _p(_i32(index)), index.numel(), int(bool(scatter)), _stream()), "lane_map")

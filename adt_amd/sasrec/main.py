@@ -111,7 +111,7 @@ def main(argv=None):
     val_ds = U.EvalDataset(user_train, user_valid, user_test, usernum, itemnum, args.maxlen, sampler, "val", args.eval_set, args.frozen_eval)
     test_ds = U.EvalDataset(user_train, user_valid, user_test, usernum, itemnum, args.maxlen, sampler, "test", args.eval_set, args.frozen_eval)
 
-    wide = args.hidden_units != 64     # the fused executor is 64-wide; other widths (the d = 256 template) take the general kernels
+    wide = args.hidden_units != 64     # the fused executor is 64-wide; other widths (the d = 256 template, the default 50) take the general kernels
     if wide:
         from .model_wide import SASRecADTWide, WideSasrecTrainer
         model = SASRecADTWide(usernum, itemnum, args)
@@ -123,7 +123,9 @@ def main(argv=None):
         except Exception:
             pass
     if world > 1:
-        torch.distributed.broadcast(model.flat, 0)
+        torch.distributed.broadcast(model.master if wide else model.flat, 0)   # padded widths keep their weights in reference shape between steps
+        if wide:
+            model.push()
     epoch_start = 1
     if args.state_dict_path is not None:          # sasrec/main.py:104-114
         model.load_state_dict(torch.load(args.state_dict_path, map_location=torch.device(args.device)))

@@ -12,7 +12,7 @@ import torch
 
 from .. import _lib, custom_ops, ops
 from ..dp import GradBuckets, reduce_sum, capture
-from ..wide import Act, FlatModule, Tape, give
+from ..wide import Act, FlatModule, Tape, give, padded_layout
 from .model import REF_ORDER, param_table
 
 LN_EPS = 1e-8
@@ -49,24 +49,37 @@ class SASRecADTWide(FlatModule):
         self.args = args
         self.prec = {"f32": ops.PREC_F32, "fp32": ops.PREC_F32, "bf16": ops.PREC_BF16}[getattr(args, "precision", "bf16")]
         d, H = self.hidden_units, self.num_heads
-        if d % 64 or d > 256 or (d // H) not in (16, 32, 64, 128, 256) or self.maxlen > 256:
-            raise _lib.AdtError("SASRecADT (adt_amd, wide path): hidden_units in {64,128,192,256}, head size 16..256, maxlen <= 256; got d=%d H=%d L=%d"
-                                % (d, H, self.maxlen))
-        self._build_flat(param_table(item_num, args.maxlen, d, H, args.num_layers), args.device, REF_ORDER)   # item table first: adt_clip_adam's wd term
+        try:
+            self.hd, self.hd_pad, self.dp = padded_layout(d, H)
+        except _lib.AdtError as e:
+            raise _lib.AdtError("SASRecADT (adt_amd, wide path): %s" % e) from None
+        if self.maxlen > 256:
+            raise _lib.AdtError("SASRecADT (adt_amd, wide path): maxlen <= 256; got d=%d H=%d L=%d" % (d, H, self.maxlen))
+        # dp == d: the kernels tile the width as it is.  Otherwise activations and parameters are padded to dp columns (head h at
+        # [h * hd_pad, h * hd_pad + hd), zero pad lanes) and LayerNorm, the scales and the dropout indices keep the true width.
+        self.lanes = (H, self.hd, self.hd_pad) if self.dp != d else None
+        table = param_table(item_num, args.maxlen, self.dp, H, args.num_layers)      # item table first: adt_clip_adam's wd term
+        if self.lanes is None:
+            self._build_flat(table, args.device, REF_ORDER)
+        else:
+            self._build_flat(table, args.device, REF_ORDER, ref_table=param_table(item_num, args.maxlen, d, H, args.num_layers), width=(d, H))
         g = torch.Generator(device="cpu").manual_seed(torch.initial_seed() % (1 << 31))
-        for name, shape in self.table:
-            v = self.P(name)
+        for name, shape in (self.table if self.lanes is None else [(n, v[2]) for n, v in self._ref_views.items()]):
+            v = self.R(name)         # reference shape: the fan-in is the true one
             if name.endswith("norm.weight"):
                 v.fill_(1.0)
             elif len(shape) >= 2:
                 bound = (1.0 / max(shape[1] * (shape[2] if len(shape) > 2 else 1), 1)) ** 0.5
                 v.copy_((torch.rand(shape, generator=g) * 2 - 1) * bound)
+        self.push()
 
     # ---- layers (sasrec/modules.py:644-677) ------------------------------------------------------------------------------
     def _embed(self, tp, ids, site):
         P, G = self.P, self.G
         L = self.maxlen
         p = tp.p_eff(self.dropout)
+        if self.lanes is not None:
+            return self._embed_lanes(tp, ids, site, p)
         x = Act(ops.embed_fwd(ids, P("item_emb.weight"), P("pos_emb.weight"), L, p, self._seed, site, tp.row_offset))
 
         def bw():
@@ -81,15 +94,36 @@ class SASRecADTWide(FlatModule):
         tp.bw.append(bw)
         return x
 
+    def _embed_lanes(self, tp, ids, site, p):
+        """_embed on a padded width: sqrt(d) with the true d, dropout indexed at the true width (adt_drop_lanes), then the row mask."""
+        P, G = self.P, self.G
+        L, scale = self.maxlen, float(self.hidden_units) ** 0.5
+        X = ops.embed_sum_fwd(ids, P("item_emb.weight"), P("pos_emb.weight"), L, None, scale)
+        x = Act(ops.drop_lanes(X, self.lanes, p, self._seed, site, tp.row_offset, mask_ids=ids, out=X))
+
+        def bw():
+            if x.g is None:
+                return
+            g = ops.drop_lanes(x.g, self.lanes, p, self._seed, site, tp.row_offset, mask_ids=ids)
+            rep = getattr(tp, "item_rep", None)
+            if rep is None:
+                ops.item_scatter(ids, g, None, scale, 0.0, None, 0, 0, G("item_emb.weight"), 1, 0)
+            else:
+                ops.item_scatter(ids, g, None, scale, 0.0, None, 0, 0, rep, self._nrep, self._rep_stride)
+            ops.posemb_bwd(ids, g, L, 0.0, None, 0, 0, G("pos_emb.weight"))
+        tp.bw.append(bw)
+        return x
+
     def _attn(self, tp, q, kv, B, site, qkv=None):
-        d, H, L = self.hidden_units, self.num_heads, self.maxlen
+        d, H, L = self.dp, self.num_heads, self.maxlen
+        scale = None if self.lanes is None else 1.0 / math.sqrt(self.hd)       # padded heads: 1 / sqrt(true head size)
         p = tp.p_eff(self.dropout)
         if qkv is not None:
             Q, K, V = qkv.t[:, :d], qkv.t[:, d:2 * d], qkv.t[:, 2 * d:]
         else:
             Q, K, V = q.t, kv.t[:, :d], kv.t[:, d:]
         fill = float("-inf")     # the float causal mask of sasrec/modules.py:504-507
-        O, LSE = ops.attn_masked_fwd(self.prec, Q, K, V, B, H, L, True, None, fill, p, self._seed, site, tp.b_offset)
+        O, LSE = ops.attn_masked_fwd(self.prec, Q, K, V, B, H, L, True, None, fill, p, self._seed, site, tp.b_offset, scale=scale)
         o = Act(O)
 
         def bw():
@@ -101,12 +135,12 @@ class SASRecADTWide(FlatModule):
             else:
                 q.g, kv.g = torch.empty_like(q.t), torch.empty_like(kv.t)
                 out = (q.g, kv.g[:, :d], kv.g[:, d:])
-            ops.attn_masked_bwd(self.prec, Q, K, V, O, LSE, o.g, B, H, L, True, None, fill, p, self._seed, site, tp.b_offset, out=out)
+            ops.attn_masked_bwd(self.prec, Q, K, V, O, LSE, o.g, B, H, L, True, None, fill, p, self._seed, site, tp.b_offset, out=out, scale=scale)
         tp.bw.append(bw)
         return o
 
     def _conv(self, name, grad=False):
-        d = self.hidden_units
+        d = self.dp
         return (self.G(name) if grad else self.P(name)).view(d, d)
 
     def _ln(self, tp, x, p):
@@ -126,7 +160,7 @@ class SASRecADTWide(FlatModule):
                         site=st["ffn2"], R=x, R2=R2, mask_ids=ids)
 
     def _enc_layer(self, tp, p, x, ids, B, st):
-        d = self.hidden_units
+        d = self.dp
         Q = self._ln(tp, x, p + ".attention_layernorm")
         ip = p + ".attention_layer.in_proj_"
         q = self._lin(tp, Q, ip, slice(0, d))                     # q from LN(x) ...
@@ -138,7 +172,7 @@ class SASRecADTWide(FlatModule):
         return self._ffn(tp, p + ".forward_layer", h2, st, ids), rec
 
     def _dec_layer(self, tp, p, x, enc, ids, B, st):
-        d = self.hidden_units
+        d = self.dp
         D = self._ln(tp, x, p + ".layer_norm")
         qkv = self._lin(tp, D, p + ".slf_attn.in_proj_")
         a1 = self._lin(tp, self._attn(tp, None, None, B, st["slf"], qkv=qkv), p + ".slf_attn.out_proj.")
@@ -172,6 +206,10 @@ class SASRecADTWide(FlatModule):
         the adt_amd::model_forward custom operator, so the reference's loop body (sasrec/main.py:146-173) runs on them unchanged;
         WideSasrecTrainer.step() is the fused, faster way to train."""
         ids = [self.ids(a) for a in (log_seqs, dec_seqs, pos_seqs, neg_seqs)]
+        if self.lanes is not None and custom_ops.wants_grad(self):
+            raise _lib.AdtError("SASRecADT (adt_amd, wide path): autograd through forward() (--loop reference) is not built for padded widths "
+                                "(d=%d H=%d runs as d_pad=%d); train with WideSasrecTrainer (--loop fused) or call forward() under torch.no_grad()"
+                                % (self.hidden_units, self.num_heads, self.dp))
         if custom_ops.wants_grad(self):
             outs = custom_ops.forward_with_grad(self, ids)
         else:
@@ -186,14 +224,21 @@ class SASRecADTWide(FlatModule):
         d, H = self.hidden_units, self.num_heads
         if training:
             self.next_seed()
+        self.push()
         tp = Tape(self, self.prec, training)
         feats, enc_in, recs = self._encode(tp, seq.view(-1), B)
         dec_outs = self._decode(tp, dec.view(-1), feats, B)
         pl, nl = ops.logits_fwd(feats.t, self.P("item_emb.weight"), pos.view(-1), neg.view(-1))
         dec_outs.reverse()
-        outs = [pl.view(B, L), nl.view(B, L)] + [a.t.view(B, L, d) for a in enc_in] + [a.t.view(B, L, d) for a in dec_outs] + \
+        outs = [pl.view(B, L), nl.view(B, L)] + [self._live(a.t, B, L) for a in enc_in] + [self._live(a.t, B, L) for a in dec_outs] + \
                [r.t.view(B, L, H, H) for r in recs]
         return outs, {"tp": tp, "feats": feats, "acts": list(enc_in) + list(dec_outs) + list(recs), "pos": pos, "neg": neg}
+
+    def _live(self, t, B, L):
+        """(B * L, dp) activation as the reference's (B, L, d): the live lanes of a padded width (a copy, outside the training step)."""
+        if self.lanes is None:
+            return t.view(B, L, self.dp)
+        return t.view(B, L, self.num_heads, self.hd_pad)[..., :self.hd].reshape(B, L, self.hidden_units)
 
     def _op_backward(self, st, grads):
         """Reverse of _op_forward for the output gradients autograd hands over; returns one gradient per parameter."""
@@ -214,10 +259,11 @@ class SASRecADTWide(FlatModule):
         B, L = seq.shape
         was = self.training
         self.eval()
+        self.push()
         tp = Tape(self, self.prec, False)
         feats, _, _ = self._encode(tp, seq.view(-1), B)
         self.train(was)
-        d = self.hidden_units
+        d = self.dp
         cand = None if item_indices is None else self.ids(item_indices)
         C = self.item_num + 1 if cand is None else cand.shape[1]
         return ops.score_rank(feats.t[L - 1:], L * d, self.P("item_emb.weight"), cand, B, C, want_rank)
@@ -302,10 +348,12 @@ class WideSasrecTrainer:
         self.loss_slots.zero_()
         m.flat_grad.zero_()
         m.dp_hook = self._buckets.tail_ready if self._buckets.active else None
+        m.push()        # padded widths: the reference-shaped parameters are the truth between steps (no-op otherwise)
         m.loss_forward_backward((st["seq"], st["dec"], st["pos"], st["neg"]), self.lambdas1, self.lambdas2, st["norms"], self.loss_slots, b_offset)
         self._buckets.finish()
-        ops.clip_adam(m.flat, m.flat_grad, self.m, self.v, (m.item_num + 1) * m.hidden_units, self.wd, self.clip, self.lr, self.betas[0],
-                      self.betas[1], self.eps, self.scal)
+        ops.clip_adam(m.flat, m.flat_grad, self.m, self.v, (m.item_num + 1) * m.dp, self.wd, self.clip, self.lr, self.betas[0],
+                      self.betas[1], self.eps, self.scal)     # the weight-decay span is the item table as laid out: padded rows
+        m.pull()
 
     def step(self, seq, dec, pos, neg, norms=None, b_offset=0):
         self.model.train()

@@ -46,13 +46,64 @@ def ref_sorted(names, order):
     return sorted(names, key=key)
 
 
+HEAD_PADS = (16, 32, 64, 128, 256)
+WIDTH_PADS = (64, 128, 192, 256)
+
+
+def padded_layout(d, H):
+    """(hd, hd_pad, d_pad) of hidden width d with H heads on the stage kernels: hd = d / H, hd_pad the smallest of 16, 32, 64, 128, 256
+    that holds hd, d_pad = H * hd_pad, which must be 64, 128, 192 or 256.  Head h occupies columns [h * hd_pad, h * hd_pad + hd) of a
+    padded row; the other lanes are zero.  Pure arithmetic (no GPU, no library); raises AdtError for a shape the kernels do not tile."""
+    d, H = int(d), int(H)
+    rule = "hd = d / H, hd_pad = smallest of %s >= hd, d_pad = H * hd_pad must be one of %s" % (list(HEAD_PADS), list(WIDTH_PADS))
+    if d < 1 or H < 1 or d % H:
+        raise _lib.AdtError("hidden_units d=%d is not a positive multiple of num_heads H=%d (%s)" % (d, H, rule))
+    hd = d // H
+    pads = [p for p in HEAD_PADS if p >= hd]
+    if not pads:
+        raise _lib.AdtError("d=%d H=%d: head size hd=%d exceeds hd_pad=%d (%s)" % (d, H, hd, HEAD_PADS[-1], rule))
+    hd_pad = pads[0]
+    d_pad = H * hd_pad
+    if d_pad not in WIDTH_PADS:
+        raise _lib.AdtError("d=%d H=%d: hd=%d pads to hd_pad=%d, d_pad=%d is not supported (%s)" % (d, H, hd, hd_pad, d_pad, rule))
+    return hd, hd_pad, d_pad
+
+
+def lane_index(ref_table, pad_table, pad_offsets, d, H):
+    """For every element of the reference-shaped parameters (ref_table order, packed densely) its position in the padded flat buffer.
+    A dimension of size d (or 3d, or hd) that the padded table widens to d_pad (3 d_pad, hd_pad) maps channel h * hd + j to
+    h * hd_pad + j; equal dimensions map to themselves."""
+    hd, hd_pad, d_pad = padded_layout(d, H)
+    chan = (np.arange(d) // hd) * hd_pad + np.arange(d) % hd
+    maps = {(d, d_pad): chan, (3 * d, 3 * d_pad): np.concatenate([chan + k * d_pad for k in range(3)]), (hd, hd_pad): np.arange(hd)}
+    pad_shapes = dict(pad_table)
+    out = []
+    for name, shape in ref_table:
+        pshape = pad_shapes[name]
+        assert len(pshape) == len(shape), (name, shape, pshape)
+        idx = np.zeros((), dtype=np.int64)
+        stride = 1
+        for r, q in zip(shape[::-1], pshape[::-1]):
+            m = np.arange(r) if r == q else maps[(r, q)]
+            idx = m.reshape((-1,) + (1,) * idx.ndim) * stride + idx
+            stride *= q
+        out.append((idx + pad_offsets[name]).reshape(-1))
+    idx = np.concatenate(out)
+    assert idx.max() < (1 << 31) and np.unique(idx).size == idx.size
+    return idx.astype(np.int32)
+
+
 class FlatModule(torch.nn.Module):
     """nn.Module whose parameters are views into ONE flat fp32 GPU buffer (`flat`), with an identically laid-out
     gradient buffer (`flat_grad`): the optimizer and the gradient all-reduce see one array.  Tensors start on 16-byte
     boundaries; tensors listed consecutively with sizes that are multiples of 4 floats are contiguous, which is what
     lets q/k/v projections run as one GEMM over a (3d, d) view."""
 
-    def _build_flat(self, table, device, ref_order=None):
+    def _build_flat(self, table, device, ref_order=None, ref_table=None, width=None):
+        """ref_table / width=(d, H): `table` is the PADDED layout of a width the kernels do not tile (padded_layout); the registered
+        parameters then have the reference's shapes and live in a second, densely packed buffer `ref_flat`, copied to and from the
+        live lanes of `flat` by push() / pull() (one kernel each).  Between steps ref_flat is the truth; the pad lanes of `flat`
+        are zero and nothing ever writes them."""
         self.lib = _lib.load()   # raises when the HIP library is missing: no fallback
         self.dev = torch.device(device)
         if self.dev.type != "cuda":
@@ -70,9 +121,22 @@ class FlatModule(torch.nn.Module):
         # The flat layout follows `table` (what the kernels want: q/k/v consecutive, never-trained tensors last); the nn.Module
         # registration follows the reference's constructor order so that parameters() lines up with the reference's optimizer.
         names = [n for n, _ in self.table]
+        self.ref_flat, self.lane_idx, self._ref_views = None, None, None
+        if ref_table is not None:
+            ref_table = [(n, tuple(s)) for n, s in ref_table]
+            assert [n for n, _ in ref_table] == names
+            index = lane_index(ref_table, self.table, {n: v[0] for n, v in self._views.items()}, *width)
+            self.lane_idx = torch.from_numpy(index).to(self.dev)
+            self.ref_flat = torch.zeros(index.size, device=self.dev, dtype=torch.float32)
+            self._ref_views, o = {}, 0
+            for name, shape in ref_table:
+                n = int(np.prod(shape))
+                self._ref_views[name] = (o, n, shape)
+                o += n
         for name in (ref_sorted(names, ref_order) if ref_order else names):
-            o, n, shape = self._views[name]
-            _set_nested(self, name, torch.nn.Parameter(self.flat[o:o + n].view(shape), requires_grad=True))
+            o, n, shape = (self._ref_views or self._views)[name]
+            src = self.flat if self.ref_flat is None else self.ref_flat
+            _set_nested(self, name, torch.nn.Parameter(src[o:o + n].view(shape), requires_grad=True))
         self._seed = torch.zeros(1, device=self.dev, dtype=torch.int32)   # uint32 bits of the dropout seed, device resident
         self._step_seed = 0
         self.dp_hook = None       # see Tape.mark_decoder_start
@@ -95,6 +159,47 @@ class FlatModule(torch.nn.Module):
     def G(self, name):
         o, n, shape = self._views[name]
         return self.flat_grad[o:o + n].view(shape)
+
+    def R(self, name):
+        """The parameter in the reference's shape (a view of ref_flat for a padded layout, of flat otherwise)."""
+        o, n, shape = (self._ref_views or self._views)[name]
+        return (self.flat if self.ref_flat is None else self.ref_flat)[o:o + n].view(shape)
+
+    def GR(self, name):
+        """The gradient in the reference's shape (for a padded layout a compacted copy of flat_grad, not a view)."""
+        if self.ref_flat is None:
+            return self.G(name)
+        o, n, shape = self._ref_views[name]
+        return self.compact(self.flat_grad)[o:o + n].view(shape)
+
+    @property
+    def master(self):
+        """The buffer that holds the weights between steps (what a data-parallel run broadcasts from rank 0)."""
+        return self.flat if self.ref_flat is None else self.ref_flat
+
+    def push(self):
+        """Reference-shaped parameters -> live lanes of the padded flat buffer (no-op without padding)."""
+        if self.ref_flat is not None:
+            ops.lane_map(self.flat, self.ref_flat, self.lane_idx, True)
+
+    def pull(self):
+        """Live lanes of the padded flat buffer -> reference-shaped parameters (no-op without padding)."""
+        if self.ref_flat is not None:
+            ops.lane_map(self.flat, self.ref_flat, self.lane_idx, False)
+
+    def compact(self, padded):
+        """The live lanes of a buffer laid out like `flat` (an Adam moment), packed like ref_flat."""
+        out = torch.empty_like(self.ref_flat)
+        ops.lane_map(padded, out, self.lane_idx, False)
+        return out
+
+    def expand_into(self, padded, compact):
+        ops.lane_map(padded, compact.to(device=self.dev, dtype=torch.float32).contiguous(), self.lane_idx, True)
+
+    def load_state_dict(self, *a, **kw):
+        r = super().load_state_dict(*a, **kw)
+        self.push()
+        return r
 
     def span(self, first, last, shape, grad=False):
         """One view over the consecutive tensors first..last (e.g. query/key/value weights as (3d, d))."""
@@ -119,7 +224,8 @@ class FlatModule(torch.nn.Module):
 
     def load_numpy(self, P):
         for k, v in P.items():
-            self.P(k).copy_(torch.from_numpy(np.ascontiguousarray(v)))
+            self.R(k).copy_(torch.from_numpy(np.ascontiguousarray(v)))
+        self.push()
 
 
 class Act:
@@ -154,6 +260,7 @@ class Tape:
         self.row_offset, self.b_offset = row_offset, b_offset
         self.bw = []
         self.marks = {}
+        self.lanes = getattr(model, "lanes", None)      # (H, hd, hd_pad) of a padded width (padded_layout), else None
 
     def p_eff(self, p):
         return float(p) if self.training else 0.0
@@ -179,6 +286,9 @@ class Tape:
     def dense(self, x, W, b, gW, gb, act=ops.ACT_NONE, p=0.0, site=0, R=None, t_dev=None, ldy=None, R2=None, mask_ids=None):
         """y = mask(R + R2 + dropout(act(x W^T + b))).  With a row mask the residuals receive the masked gradient."""
         p = self.p_eff(p)
+        if self.lanes is not None and p > 0.0:
+            assert t_dev is None and ldy is None, "padded widths: a device row count / output stride is not carried through the dropout pass"
+            return self._dense_lanes(x, W, b, gW, gb, act, p, site, R, R2, mask_ids)
         Y, U = ops.dense_fwd(self.prec, x.t, W, b, act, act != ops.ACT_NONE, p, self.seed, site, self.row_offset, None if R is None else R.t,
                              mask_ids, None, t_dev, ldy, None if R2 is None else R2.t)
         y = Act(Y)
@@ -203,6 +313,35 @@ class Tape:
                     continue
                 if mask_ids is None and R2 is None:
                     give(res, y.g)          # y.g is not used again: hand the buffer over
+                else:
+                    g = torch.empty_like(y.g)
+                    ops.axpy(g, y.g, 1.0, False, mask_ids, y.g.shape[1])
+                    give(res, g)
+        self.bw.append(bw)
+        return y
+
+    def _dense_lanes(self, x, W, b, gW, gb, act, p, site, R, R2, mask_ids):
+        """dense() on a padded width with dropout on.  The GEMM epilogues index the dropout RNG by row * N + column with the PADDED N;
+        the oracle's index runs over the true width.  So the layer runs without its dropout, residuals and row mask, and one
+        elementwise pass (adt_drop_lanes) applies them with true-width indices; the backward pulls the gradient through the same pass
+        first.  relu(dropout(u)) == dropout(relu(u)) (the scale is positive), so the activation stays in the GEMM."""
+        Y, U = ops.dense_fwd(self.prec, x.t, W, b, act, act != ops.ACT_NONE)
+        ops.drop_lanes(Y, self.lanes, p, self.seed, site, self.row_offset, None if R is None else R.t, None if R2 is None else R2.t, mask_ids, out=Y)
+        y = Act(Y)
+
+        def bw():
+            if y.g is None:
+                return
+            beta = x.g is not None
+            if not beta:
+                x.g = torch.empty_like(x.t)
+            G = ops.drop_lanes(y.g, self.lanes, p, self.seed, site, self.row_offset, mask_ids=mask_ids)
+            ops.dense_bwd(self.prec, G, x.t, W, gW, gb, x.g, beta, act, U)
+            for res in (R, R2):
+                if res is None:
+                    continue
+                if mask_ids is None and R2 is None:
+                    give(res, y.g)
                 else:
                     g = torch.empty_like(y.g)
                     ops.axpy(g, y.g, 1.0, False, mask_ids, y.g.shape[1])
@@ -243,6 +382,8 @@ class Tape:
         return y
 
     def layernorm(self, x, w, b, gw, gb, eps):
+        if self.lanes is not None:
+            return self._layernorm_lanes(x, w, b, gw, gb, eps)
         y = Act(ops.layernorm_fwd(x.t, w, b, eps))
 
         def bw():
@@ -252,6 +393,19 @@ class Tape:
             if not acc:
                 x.g = torch.empty_like(x.t)
             ops.layernorm_bwd(y.g, x.t, w, eps, x.g, acc, gw, gb)
+        self.bw.append(bw)
+        return y
+
+    def _layernorm_lanes(self, x, w, b, gw, gb, eps):
+        y = Act(ops.layernorm_lanes_fwd(x.t, w, b, eps, self.lanes))
+
+        def bw():
+            if y.g is None:
+                return
+            acc = x.g is not None
+            if not acc:
+                x.g = torch.empty_like(x.t)
+            ops.layernorm_lanes_bwd(y.g, x.t, w, eps, x.g, acc, gw, gb, self.lanes)
         self.bw.append(bw)
         return y
 

@@ -493,6 +493,34 @@ int adt_sasrec_fold_grads(const adt_sasrec_cfg* cfg, float* ws, int B, float* pa
 int adt_sasrec_predict(const adt_sasrec_cfg* cfg, const float* params, float* ws, const int32_t* seq,
                        const int32_t* cand, int B, int C, float* logits, int32_t* rank, void* stream);
 
+/* ---- widths that are not multiples of 64 (SASRec-ADT at hidden_units 50, 100, ...) ----
+ * Rows keep a padded layout: H heads of hd live lanes, head h at columns [h * hd_pad, h * hd_pad + hd) of d_pad = H * hd_pad floats
+ * (hd_pad a power of two in 16..256, d_pad in {64,128,192,256}); pad lanes are exact zeros on input and on output.
+ * LayerNorm over the d = H * hd live lanes; the backward leaves the pad entries of dgamma / dbeta untouched. */
+int adt_layernorm_lanes_fwd(const float* X, int ldx, const float* gamma, const float* beta, float eps, int T, int H, int hd,
+                            int hd_pad, float* Y, int ldy, void* stream);
+int adt_layernorm_lanes_bwd(const float* dY, int lddy, const float* X, int ldx, const float* gamma, float eps, int T, int H, int hd,
+                            int hd_pad, float* dX, int lddx, int accumulate, float* dgamma, float* dbeta, void* stream);
+/* out = rowmask(R + R2 + dropout(S)) on the live lanes, 0 on the pad lanes; the dropout index of (row t, live lane c) is the
+ * TRUE-width one, (t + row_offset) * d + true column.  R, R2, mask_ids may be NULL.  With S = dY and no residuals it is the
+ * gradient pulled back through the same site. */
+int adt_drop_lanes(const float* S, int lds, const float* R, int ldr, const float* R2, int ldr2, const int32_t* mask_ids, int T,
+                   int H, int hd, int hd_pad, float p, const uint32_t* seed, uint32_t site, uint32_t row_offset, float* out,
+                   int ldo, void* stream);
+/* compact[i] = padded[map[i]] (scatter == 0) or padded[map[i]] = compact[i] (scatter != 0; map injective): reference-shaped
+ * parameters / optimizer moments against the padded flat buffer. */
+int adt_lane_map(float* padded, float* compact, const int32_t* map, int64_t n, int scatter, void* stream);
+/* adt_attn_masked_fwd / _bwd with the score scale given by the caller (1 / sqrt(true head size) when the heads are padded
+ * to hd with zero lanes) instead of 1 / sqrt(hd). */
+int adt_attn_masked_scaled_fwd(int prec, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int B, int H,
+                               int L, int hd, float scale, int causal, const int32_t* key_ids, float fill, float p,
+                               const uint32_t* seed, uint32_t site, uint32_t b_offset, float* O, int ldo, float* LSE,
+                               void* stream);
+int adt_attn_masked_scaled_bwd(int prec, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, const float* O,
+                               int ldo, const float* LSE, const float* dO, int lddo, int B, int H, int L, int hd, float scale,
+                               int causal, const int32_t* key_ids, float fill, float p, const uint32_t* seed, uint32_t site,
+                               uint32_t b_offset, float* dQ, int lddq, float* dK, int lddk, float* dV, int lddv, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

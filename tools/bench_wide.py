@@ -113,7 +113,8 @@ def run_sasrec256(args):
     import bench
     from adt_amd.sasrec.model_wide import SASRecADTWide, WideSasrecTrainer
     a = Args()
-    a.device, a.num_heads, a.maxlen, a.num_layers, a.hidden_units, a.dropout, a.precision = "cuda:0", 2, 200, 2, 256, 0.5, "bf16"
+    d, H, L, nl = args.hidden_units, args.num_heads, args.maxlen, args.num_layers        # defaults: the template shape
+    a.device, a.num_heads, a.maxlen, a.num_layers, a.hidden_units, a.dropout, a.precision = "cuda:0", H, L, nl, d, 0.5, "bf16"
     torch.manual_seed(23)
     m = SASRecADTWide(6040, 3416, a)
     for _, p in m.named_parameters():
@@ -121,8 +122,9 @@ def run_sasrec256(args):
             torch.nn.init.xavier_normal_(p.data)
         except Exception:
             pass
-    tr = WideSasrecTrainer(m, bench.CFG["lambdas1"], bench.CFG["lambdas2"], weight_decay=1e-3, use_graph=not args.no_graph, seed=23)
-    batches = bench.synth_batches(4, args.batch, 200, 3416, seed=100)
+    lam1, lam2 = ([lam[i % len(lam)] for i in range(nl)] for lam in (bench.CFG["lambdas1"], bench.CFG["lambdas2"]))   # one pair per layer
+    tr = WideSasrecTrainer(m, lam1, lam2, weight_decay=1e-3, use_graph=not args.no_graph, seed=23)
+    batches = bench.synth_batches(4, args.batch, L, 3416, seed=100)
     for i in range(args.warmup):
         tr.step(*batches[i % 4])
     torch.cuda.synchronize()
@@ -131,7 +133,9 @@ def run_sasrec256(args):
         tr.step(*batches[i % 4])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print(json.dumps({"workload": "SASRec-ADT ml-1m TEMPLATE width: d=256 H=2 (head size 128) L=200 2+2 layers V=3416, batch %d, dropout 0.5, full train step (H2D of ids included)" % args.batch,
+    what = "ml-1m TEMPLATE width: d=256 H=2 (head size 128) L=200 2+2 layers" if (d, H, L, nl) == (256, 2, 200, 2) else \
+        "wide path: d=%d H=%d (head size %d, computed as d_pad=%d) L=%d %d+%d layers" % (d, H, d // H, m.dp, L, nl, nl)
+    print(json.dumps({"workload": "SASRec-ADT %s V=3416, batch %d, dropout 0.5, full train step (H2D of ids included)" % (what, args.batch),
                       "ms_per_step": round(dt / args.steps * 1e3, 3), "sequences_per_s": round(args.batch * args.steps / dt, 1), "loss": round(float(tr.loss()), 4),
                       "dtype": "bf16"}))
 
@@ -146,5 +150,9 @@ if __name__ == "__main__":
     ap.add_argument("--mcap", type=float, default=0.3)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl"], help="stosa: distance_metric")
+    ap.add_argument("--hidden_units", type=int, default=256, help="sasrec256: width (default: the template's)")
+    ap.add_argument("--num_heads", type=int, default=2)
+    ap.add_argument("--maxlen", type=int, default=200)
+    ap.add_argument("--num_layers", type=int, default=2)
     args = ap.parse_args()
     {"bert": run_bert, "stosa": run_stosa, "sasrec256": run_sasrec256}[args.which](args)

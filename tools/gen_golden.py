@@ -307,6 +307,12 @@ if __name__ == "__main__":
         # one 256-wide head (the reference search default's width and head count) on the wide path
         case_sampled("sasrec_d256_h1", V=50, L=24, d=256, H=1, nl=1, B=3, seed=37, lam1=[0.104292], lam2=[0.100833])
         sys.exit(0)
+    if sys.argv[1:] == ["oddwidth"]:
+        # widths that are not multiples of 64 (the CLI default hidden_units 50 among them): one head; head size 25 (padded to 32 on the
+        # HIP path); head size 50 (padded to 64, 128 padded columns).  Two layers with distinct lambda pairs: the stale-index lambda2.
+        for nm, d, H, seed in (("sasrec_w50_h1", 50, 1, 41), ("sasrec_w50_h2", 50, 2, 43), ("sasrec_w100_h2", 100, 2, 47)):
+            case_sampled(nm, V=50, L=24, d=d, H=H, nl=2, B=3, seed=seed, lam1=[0.104292, 0.065892], lam2=[0.100833, 0.000607])
+        sys.exit(0)
     case_small("sasrec_small", B=4, L=16, d=32, H=2, nl=2, V=50, seed=11,
                lam1=[0.104292, 0.065892], lam2=[0.100833, 0.000607], wd=1e-3)
     case_small("sasrec_small_h1", B=3, L=12, d=16, H=1, nl=1, V=30, seed=13, lam1=[0.05], lam2=[0.02], wd=1e-4)
