@@ -23,10 +23,33 @@ int adt_set_error(const char* fmt, ...) {
   return -1;
 }
 
-static int check_launch(const char* what) {
+int adt_check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return adt_set_error("%s: %s", what, hipGetErrorString(e));
   return 0;
+}
+
+int adt_launch_lds(const void* fn, dim3 grid, dim3 block, size_t smem, void** kargs, hipStream_t stream, const char* what, AdtLdsOptIn& slot,
+                   size_t optin) {
+  if (smem > ADT_LDS_MAX) return adt_set_error("%s: %zu B of LDS (> 160 KB)", what, smem);
+  const int want = (int)(optin > smem ? optin : smem);
+  if (want > slot.bytes) {
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, want);
+    if (e != hipSuccess) return adt_set_error("%s: hipFuncSetAttribute(%d): %s", what, want, hipGetErrorString(e));
+    slot.bytes = want;
+  }
+  if (hipLaunchKernel(fn, grid, block, kargs, smem, stream) != hipSuccess) return adt_set_error("%s: launch failed", what);
+  return adt_check_launch(what);
+}
+
+int adt_env_on(const char* name) {
+  const char* e = getenv(name);
+  return (e && atoi(e) == 0) ? 0 : 1;
+}
+
+int adt_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
 }
 
 DropCfg adt_make_drop(float p, const uint32_t* seed, uint32_t site) {
@@ -44,11 +67,9 @@ DropCfg adt_make_drop(float p, const uint32_t* seed, uint32_t site) {
   return d;
 }
 
-static int grid_for(size_t work_items, int per_block, int cap) {
-  size_t g = (work_items + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  if (g > (size_t)cap) g = cap;
-  return (int)g;
+static int env_grid_cap(const char* name, int dflt) {      // ADT_FWD_GRID / ADT_LINBWD_GRID: a value below 1 means the default
+  const int v = adt_env_int(name, dflt);
+  return v < 1 ? dflt : v;
 }
 
 template <int PREC>
@@ -61,13 +82,7 @@ static void launch_linear_bwd(const LinBwdArgs& a, int nch, int grid, hipStream_
 // ---- attention dispatch --------------------------------------------------------------------------
 static int attn_waves(bool bwd) {
   // waves per workgroup: tunable for experiments (ADT_ATTN_FWD_NW / ADT_ATTN_BWD_NW = 4 or 8)
-  static int nw[2] = {0, 0};
-  if (!nw[0]) {
-    const char* f = getenv("ADT_ATTN_FWD_NW");
-    const char* b = getenv("ADT_ATTN_BWD_NW");
-    nw[0] = (f && atoi(f) == 4) ? 4 : 8;
-    nw[1] = (b && atoi(b) == 4) ? 4 : 8;
-  }
+  static const int nw[2] = {adt_env_int("ADT_ATTN_FWD_NW", 8) == 4 ? 4 : 8, adt_env_int("ADT_ATTN_BWD_NW", 8) == 4 ? 4 : 8};
   return nw[bwd ? 1 : 0];
 }
 
@@ -75,43 +90,22 @@ static int attn_waves(bool bwd) {
 template <int HD, int MAXKT, int NW>
 static int launch_attn_bf16(bool bwd, const AttnArgs& a, hipStream_t s) {
   const size_t smem = bwd ? AttnBf16Lds<HD, MAXKT>::bwd_bytes : AttnBf16Lds<HD, MAXKT>::fwd_bytes;
-  if (smem > 160 * 1024) return adt_set_error("attention(bf16): L/hd too large for LDS-resident form (%zu B)", smem);
-  static bool attr_done[2] = {false, false};
-  if (!attr_done[bwd ? 1 : 0]) {
-    hipError_t e = bwd ? hipFuncSetAttribute((const void*)k_attn_bwd_bf16<HD, MAXKT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)
-                       : hipFuncSetAttribute((const void*)k_attn_fwd_bf16<HD, MAXKT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return adt_set_error("attention(bf16): hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_done[bwd ? 1 : 0] = true;
-  }
-  const int grid = a.B * a.H;
-  if (bwd) hipLaunchKernelGGL((k_attn_bwd_bf16<HD, MAXKT, NW>), dim3(grid), dim3(NW * 64), smem, s, a);
-  else hipLaunchKernelGGL((k_attn_fwd_bf16<HD, MAXKT, NW>), dim3(grid), dim3(NW * 64), smem, s, a);
-  return check_launch(bwd ? "attn_bwd_bf16" : "attn_fwd_bf16");
+  const void* fn = bwd ? (const void*)k_attn_bwd_bf16<HD, MAXKT, NW> : (const void*)k_attn_fwd_bf16<HD, MAXKT, NW>;
+  static AdtLdsOptIn slot[2];
+  return adt_launch_lds1(fn, dim3(a.B * a.H), dim3(NW * 64), smem, a, s, bwd ? "attn_bwd_bf16" : "attn_fwd_bf16", slot[bwd ? 1 : 0]);
 }
 
 template <int PREC, int HD, int MAXKT, int NW>
 static int launch_attn_nw(bool bwd, const AttnArgs& a, hipStream_t s) {
   if constexpr (PREC == PREC_BF16) {
-    static int use_img = -1;
-    if (use_img < 0) { const char* e = getenv("ADT_ATTN_BF16_IMG"); use_img = (e && atoi(e) == 0) ? 0 : 1; }
+    static const int use_img = adt_env_on("ADT_ATTN_BF16_IMG");
     if (use_img) return launch_attn_bf16<HD, MAXKT, NW>(bwd, a, s);
   }
   constexpr int RS = HD + 4, LP = MAXKT * 16;
   const size_t smem = bwd ? (size_t)(4 * LP * RS + 2 * LP) * sizeof(float) : (size_t)(2 * LP * RS) * sizeof(float);
-  if (smem > 160 * 1024) return adt_set_error("attention: L/hd too large for LDS-resident form (%zu B)", smem);
-  static bool attr_done[2] = {false, false};
-  if (!attr_done[bwd ? 1 : 0]) {
-    hipError_t e = bwd ? hipFuncSetAttribute((const void*)k_attn_bwd<PREC, HD, MAXKT, NW>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)
-                       : hipFuncSetAttribute((const void*)k_attn_fwd<PREC, HD, MAXKT, NW>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return adt_set_error("attention: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_done[bwd ? 1 : 0] = true;
-  }
-  const int grid = a.B * a.H;
-  if (bwd) hipLaunchKernelGGL((k_attn_bwd<PREC, HD, MAXKT, NW>), dim3(grid), dim3(NW * 64), smem, s, a);
-  else hipLaunchKernelGGL((k_attn_fwd<PREC, HD, MAXKT, NW>), dim3(grid), dim3(NW * 64), smem, s, a);
-  return check_launch(bwd ? "attn_bwd" : "attn_fwd");
+  const void* fn = bwd ? (const void*)k_attn_bwd<PREC, HD, MAXKT, NW> : (const void*)k_attn_fwd<PREC, HD, MAXKT, NW>;
+  static AdtLdsOptIn slot[2];
+  return adt_launch_lds1(fn, dim3(a.B * a.H), dim3(NW * 64), smem, a, s, bwd ? "attn_bwd" : "attn_fwd", slot[bwd ? 1 : 0]);
 }
 
 template <int PREC, int HD, int MAXKT>
@@ -166,28 +160,18 @@ static int launch_bwdchain_t(int which, const BwdChainArgs& a, hipStream_t s) {
     case 5: fn = (const void*)k_kv_bwd<PREC, NW>; smem = BwdLds<PREC, NW, 2>::bytes; break;
     default: return adt_set_error("bwdchain: bad kernel id %d", which);
   }
-  if (smem > 160 * 1024) return adt_set_error("bwdchain %d: %zu B of LDS", which, smem);
-  static bool done[8] = {false, false, false, false, false, false, false, false};
-  if (!done[which]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-      return adt_set_error("bwdchain: hipFuncSetAttribute");
-    done[which] = true;
-  }
+  static AdtLdsOptIn slot[8];
   BwdChainArgs args = a;
-  static int ablate = -1;
-  if (ablate < 0) { const char* e = getenv("ADT_BWD_ABLATE"); ablate = e ? atoi(e) : 0; }
+  static const int ablate = adt_env_int("ADT_BWD_ABLATE", 0);
   args.ablate = ablate;
-  void* kargs[] = {&args};
-  if (hipLaunchKernel(fn, dim3(grid), dim3(NW * 64), kargs, smem, s) != hipSuccess) return adt_set_error("bwdchain %d: launch failed", which);
-  return check_launch("bwdchain");
+  return adt_launch_lds1(fn, dim3(grid), dim3(NW * 64), smem, args, s, "bwdchain", slot[which]);
 }
 
 template <int PREC, int NW>
 static int launch_fwdchain_t(int which, const FwdChainArgs& a, hipStream_t s) {
   const int ntiles = (a.T + 15) / 16;
   int grid = (ntiles + NW - 1) / NW;
-  static int cap = 0;
-  if (!cap) { const char* e = getenv("ADT_FWD_GRID"); cap = e ? atoi(e) : 512; if (cap < 1) cap = 512; }
+  static const int cap = env_grid_cap("ADT_FWD_GRID", 512);
   if (grid > cap) grid = cap;
   const void* fn = nullptr;
   size_t smem = 0;
@@ -203,16 +187,8 @@ static int launch_fwdchain_t(int which, const FwdChainArgs& a, hipStream_t s) {
     case 5: fn = (const void*)k_final_fwd<PREC, NW>; smem = FwdLds<PREC, NW, 4>::bytes; break;
     default: return adt_set_error("fwdchain: bad kernel id %d", which);
   }
-  static bool done[9] = {false, false, false, false, false, false, false, false, false};
-  if (!done[which]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-      return adt_set_error("fwdchain: hipFuncSetAttribute");
-    done[which] = true;
-  }
-  FwdChainArgs args = a;
-  void* kargs[] = {&args};
-  if (hipLaunchKernel(fn, dim3(grid), dim3(NW * 64), kargs, smem, s) != hipSuccess) return adt_set_error("fwdchain %d: launch failed", which);
-  return check_launch("fwdchain");
+  static AdtLdsOptIn slot[9];
+  return adt_launch_lds1(fn, dim3(grid), dim3(NW * 64), smem, a, s, "fwdchain", slot[which]);
 }
 
 int adt_launch_fwdchain(int prec, int which, const FwdChainArgs& a, void* stream) {
@@ -244,8 +220,8 @@ int adt_embed_fwd(const int32_t* ids, const float* E, const float* P, int T, int
   EmbedArgs a{};
   a.ids = ids; a.E = E; a.P = P; a.T = T; a.L = L; a.d = d; a.scale = sqrtf((float)d);
   a.drop = adt_make_drop(p, seed, site); a.row_offset = row_offset; a.X = X;
-  hipLaunchKernelGGL(k_embed_fwd, dim3(grid_for((size_t)T * d / 4, 256, 2048)), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("embed_fwd");
+  hipLaunchKernelGGL(k_embed_fwd, dim3(adt_grid_for((size_t)T * d / 4, 256, 2048)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("embed_fwd");
 }
 
 int adt_embed_bwd(const int32_t* ids, const float* dX, int T, int L, int d, float p, const uint32_t* seed,
@@ -261,8 +237,8 @@ int adt_embed_bwd(const int32_t* ids, const float* dX, int T, int L, int d, floa
   ScatterArgs sc{};
   sc.ids = ids; sc.G = dX; sc.ldg = d; sc.rowscale = nullptr; sc.T = T; sc.d = d; sc.scale = a.scale; sc.drop = a.drop;
   sc.row_offset = row_offset; sc.dE = dE;
-  hipLaunchKernelGGL(k_item_scatter, dim3(grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, sc);
-  return check_launch("embed_bwd");
+  hipLaunchKernelGGL(k_item_scatter, dim3(adt_grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, sc);
+  return adt_check_launch("embed_bwd");
 }
 
 int adt_item_scatter(const int32_t* ids, const float* G, int ldg, const float* rowscale, int T, int d, float scale, float p,
@@ -271,16 +247,16 @@ int adt_item_scatter(const int32_t* ids, const float* G, int ldg, const float* r
   ScatterArgs sc{};
   sc.ids = ids; sc.G = G; sc.ldg = ldg; sc.rowscale = rowscale; sc.T = T; sc.d = d; sc.scale = scale;
   sc.drop = adt_make_drop(p, seed, site); sc.row_offset = row_offset; sc.dE = rep; sc.nrep = nrep; sc.rep_stride = (size_t)rep_stride;
-  hipLaunchKernelGGL(k_item_scatter, dim3(grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, sc);
-  return check_launch("item_scatter");
+  hipLaunchKernelGGL(k_item_scatter, dim3(adt_grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, sc);
+  return adt_check_launch("item_scatter");
 }
 
 // fused forms used by the executor (adt_host.h)
 int adt_logits_bwd_scatter(const float* F, int ldf, const float* E, const int32_t* pos, const int32_t* neg, const float* dpos, const float* dneg,
                            int T, int d, float* dF, int lddf, float* rep, int nrep, int64_t rep_stride, void* stream) {
   LogitsScatterArgs a{F, ldf, E, pos, neg, dpos, dneg, T, d, dF, lddf, rep, nrep, (size_t)rep_stride};
-  hipLaunchKernelGGL(k_logits_bwd_scatter, dim3(grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("logits_bwd_scatter");
+  hipLaunchKernelGGL(k_logits_bwd_scatter, dim3(adt_grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("logits_bwd_scatter");
 }
 
 int adt_logits_bce_scatter(const float* F, const float* E, const int32_t* pos, const int32_t* neg, const float* norms, int T, float* pos_logits,
@@ -292,8 +268,8 @@ int adt_logits_bce_scatter_ex(const float* F, const float* E, const int32_t* pos
                               float* neg_logits, float* dpos, float* dneg, float* loss_bce, float* dF, float* rep, int nrep, int64_t rep_stride,
                               int neg_only, void* stream) {
   LogitsBceArgs a{F, E, pos, neg, norms, T, pos_logits, neg_logits, dpos, dneg, loss_bce, dF, rep, nrep, (size_t)rep_stride, neg_only};
-  hipLaunchKernelGGL(k_logits_bce_scatter, dim3(grid_for(T, 4 * 16, 1024)), dim3(256), 0, (hipStream_t)stream, a);      // ~16 rows per wave
-  return check_launch("logits_bce_scatter");
+  hipLaunchKernelGGL(k_logits_bce_scatter, dim3(adt_grid_for(T, 4 * 16, 1024)), dim3(256), 0, (hipStream_t)stream, a);      // ~16 rows per wave
+  return adt_check_launch("logits_bce_scatter");
 }
 
 // adt_loss_seeds_split_prefetch(): the NEXT adt_loss_seeds_prefetch of this host thread copies only the first half of the ring slot and leaves the
@@ -318,7 +294,7 @@ int adt_embed_bwd3(const int32_t* seq, const int32_t* dec, const int32_t* pos, c
   } else {
     hipLaunchKernelGGL(k_embed_bwd3, dim3((L * ns + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
   }
-  return check_launch("embed_bwd3");
+  return adt_check_launch("embed_bwd3");
 }
 
 int adt_embed_bwd_rep(const int32_t* ids, const float* dX, int T, int L, int d, float p, const uint32_t* seed, uint32_t site, uint32_t row_offset,
@@ -330,7 +306,7 @@ int adt_embed_bwd_rep(const int32_t* ids, const float* dX, int T, int L, int d, 
   const int B = T / L, ns = B < 32 ? B : 32;
   EmbedBwdArgs a{ids, dX, T, L, sqrtf((float)d), adt_make_drop(p, seed, site), row_offset, dP, rep, nrep, (size_t)rep_stride, ns};
   hipLaunchKernelGGL(k_embed_bwd64, dim3((L * ns + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("embed_bwd_rep");
+  return adt_check_launch("embed_bwd_rep");
 }
 
 int adt_replica_reduce2(float* d0, const float* r0, int64_t n0, int nrep0, int64_t s0, float* d1, const float* r1, int64_t n1, int nrep1, int64_t s1,
@@ -339,17 +315,17 @@ int adt_replica_reduce2(float* d0, const float* r0, int64_t n0, int nrep0, int64
   if (n0 <= 0) return adt_replica_reduce(d1, r1, n1, nrep1, s1, stream);
   if (n1 <= 0) return adt_replica_reduce(d0, r0, n0, nrep0, s0, stream);
   RepReduce2Args a{{d0, d1}, {r0, r1}, {(size_t)n0, (size_t)n1}, {nrep0, nrep1}, {(size_t)s0, (size_t)s1}, 0};
-  const int g0 = grid_for((size_t)n0 / 4, 256, 1024), g1 = grid_for((size_t)n1 / 4, 256, 1024);
+  const int g0 = adt_grid_for((size_t)n0 / 4, 256, 1024), g1 = adt_grid_for((size_t)n1 / 4, 256, 1024);
   a.g0 = g0;
   hipLaunchKernelGGL(k_replica_reduce2, dim3(g0 + g1), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("replica_reduce2");
+  return adt_check_launch("replica_reduce2");
 }
 
 int adt_replica_reduce(float* dE, const float* rep, int64_t n, int nrep, int64_t rep_stride, void* stream) {
   if (n % 4 || rep_stride % 4) return adt_set_error("replica_reduce: n, stride %% 4");
-  hipLaunchKernelGGL(k_replica_reduce, dim3(grid_for((size_t)n / 4, 256, 1024)), dim3(256), 0, (hipStream_t)stream, dE, rep, (size_t)n, nrep,
+  hipLaunchKernelGGL(k_replica_reduce, dim3(adt_grid_for((size_t)n / 4, 256, 1024)), dim3(256), 0, (hipStream_t)stream, dE, rep, (size_t)n, nrep,
                      (size_t)rep_stride);
-  return check_launch("replica_reduce");
+  return adt_check_launch("replica_reduce");
 }
 
 int adt_posemb_bwd(const int32_t* ids, const float* dX, int T, int L, int d, float p, const uint32_t* seed,
@@ -360,27 +336,27 @@ int adt_posemb_bwd(const int32_t* ids, const float* dX, int T, int L, int d, flo
   a.drop = adt_make_drop(p, seed, site); a.row_offset = row_offset; a.dX = dX; a.dP = dP;
   const int B = T / L;
   hipLaunchKernelGGL(k_posemb_bwd, dim3((L * d / 4 + 255) / 256, B < 32 ? B : 32), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("posemb_bwd");
+  return adt_check_launch("posemb_bwd");
 }
 
 int adt_logits_bwd_df(const float* E, const int32_t* pos, const int32_t* neg, const float* dpos, const float* dneg, int T,
                       int d, float* dF, int lddf, void* stream) {
   LogitsArgs a{};
   a.E = E; a.pos = pos; a.neg = neg; a.T = T; a.d = d; a.dpos = dpos; a.dneg = dneg; a.dF = dF; a.lddf = lddf;
-  hipLaunchKernelGGL(k_logits_bwd, dim3(grid_for(T, 16, 2048)), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("logits_bwd_df");
+  hipLaunchKernelGGL(k_logits_bwd, dim3(adt_grid_for(T, 16, 2048)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("logits_bwd_df");
 }
 
 int adt_layernorm_fwd(const float* X, int ldx, const float* gamma, const float* beta, float eps, int T, int d,
                       float* Y, int ldy, void* stream) {
   LnArgs a{};
   a.X = X; a.ldx = ldx; a.gamma = gamma; a.beta = beta; a.eps = eps; a.Y = Y; a.ldy = ldy; a.T = T;
-  const int grid = grid_for(T, 16, 2048);
+  const int grid = adt_grid_for(T, 16, 2048);
   if (d == 64) hipLaunchKernelGGL(k_ln_fwd<64>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   else if (d == 128) hipLaunchKernelGGL(k_ln_fwd<128>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   else if (d == 256) hipLaunchKernelGGL(k_ln_fwd<256>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   else return adt_set_error("layernorm_fwd: d=%d unsupported (64/128/256)", d);
-  return check_launch("layernorm_fwd");
+  return adt_check_launch("layernorm_fwd");
 }
 
 int adt_layernorm_bwd(const float* dY, int lddy, const float* X, int ldx, const float* gamma, float eps, int T,
@@ -396,12 +372,12 @@ int adt_layernorm_bwd_rep(const float* dY, int lddy, const float* X, int ldx, co
   LnArgs a{};
   a.X = X; a.ldx = ldx; a.gamma = gamma; a.eps = eps; a.T = T; a.dY = dY; a.lddy = lddy; a.dX = dX; a.lddx = lddx;
   a.acc = accumulate; a.dgamma = dgamma; a.dbeta = dbeta; a.nrep = nrep; a.rep_stride = (size_t)rep_stride;
-  const int grid = grid_for(T, 16, nrep > 1 ? 1024 : 256);
+  const int grid = adt_grid_for(T, 16, nrep > 1 ? 1024 : 256);
   if (d == 64) hipLaunchKernelGGL(k_ln_bwd<64>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   else if (d == 128) hipLaunchKernelGGL(k_ln_bwd<128>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   else if (d == 256) hipLaunchKernelGGL(k_ln_bwd<256>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   else return adt_set_error("layernorm_bwd: d=%d unsupported (64/128/256)", d);
-  return check_launch("layernorm_bwd");
+  return adt_check_launch("layernorm_bwd");
 }
 
 /* adt_layernorm_bwd_rep with PRIVATE per-block sums: block b stores dgamma / dbeta sums at part + b * 2 * d (dgamma | dbeta); returns the number of
@@ -411,12 +387,12 @@ int adt_layernorm_bwd_parts(const float* dY, int lddy, const float* X, int ldx, 
   LnArgs a{};
   a.X = X; a.ldx = ldx; a.gamma = gamma; a.eps = eps; a.T = T; a.dY = dY; a.lddy = lddy; a.dX = dX; a.lddx = lddx;
   a.acc = accumulate; a.dgamma = part; a.dbeta = part + d; a.nrep = 1; a.rep_stride = (size_t)(2 * d); a.plain = 1;
-  const int grid = grid_for(T, 16, max_blocks);
+  const int grid = adt_grid_for(T, 16, max_blocks);
   if (d == 64) hipLaunchKernelGGL(k_ln_bwd<64>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   else if (d == 128) hipLaunchKernelGGL(k_ln_bwd<128>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   else if (d == 256) hipLaunchKernelGGL(k_ln_bwd<256>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   else return adt_set_error("layernorm_bwd_parts: d=%d unsupported (64/128/256)", d);
-  const int rc = check_launch("layernorm_bwd_parts");
+  const int rc = adt_check_launch("layernorm_bwd_parts");
   return rc < 0 ? rc : grid;
 }
 
@@ -431,10 +407,10 @@ int adt_linear_fwd(int prec, const float* X, int ldx, const float* W, const floa
   a.X = X; a.ldx = ldx; a.W = W; a.b = b; a.N = N; a.Y = Y; a.ldy = ldy; a.T = T;
   a.drop = adt_make_drop(p, seed, site); a.row_offset = row_offset; a.relu = relu;
   a.R1 = R1; a.ldr1 = ldr1; a.R2 = R2; a.ldr2 = ldr2; a.ids = mask_ids;
-  const int grid = grid_for(T, BM, 768);
+  const int grid = adt_grid_for(T, BM, 768);
   if (prec == ADT_PREC_F32) hipLaunchKernelGGL((k_linear_fwd<PREC_F32, 64>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL((k_linear_fwd<PREC_BF16, 64>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("linear_fwd");
+  return adt_check_launch("linear_fwd");
 }
 
 int adt_linear_bwd(int prec, const float* dY, int lddy, const float* X, int ldx, const float* W, int T, int K,
@@ -451,12 +427,11 @@ int adt_linear_bwd(int prec, const float* dY, int lddy, const float* X, int ldx,
   a.dX = dX; a.lddx = lddx; a.beta = beta; a.Radd = Radd; a.ldradd = ldradd; a.radd_ids = radd_ids;
   a.dW = dW; a.db = db;
   const int nch = (N + 63) / 64;
-  static int cap = 0;
-  if (!cap) { const char* e = getenv("ADT_LINBWD_GRID"); cap = e ? atoi(e) : 256; if (cap < 1) cap = 256; }
-  const int grid = grid_for(T, BM, cap);
+  static const int cap = env_grid_cap("ADT_LINBWD_GRID", 256);
+  const int grid = adt_grid_for(T, BM, cap);
   if (prec == ADT_PREC_F32) launch_linear_bwd<PREC_F32>(a, nch, grid, (hipStream_t)stream);
   else launch_linear_bwd<PREC_BF16>(a, nch, grid, (hipStream_t)stream);
-  return check_launch("linear_bwd");
+  return adt_check_launch("linear_bwd");
 }
 
 int adt_attn_fwd(int prec, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int B,
@@ -514,8 +489,8 @@ int adt_headcls_fwd(const float* O, int ldo, const float* Ws, const float* bs, i
   if (H > MAXH || hd % 4) return adt_set_error("headcls: H=%d (max %d) hd=%d", H, MAXH, hd);
   HeadClsArgs a{};
   a.O = O; a.ldo = ldo; a.Ws = Ws; a.bs = bs; a.B = B; a.L = L; a.H = H; a.hd = hd; a.rec = rec;
-  hipLaunchKernelGGL(k_headcls_fwd, dim3(grid_for((size_t)B * L * H, 256, 1024)), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("headcls_fwd");
+  hipLaunchKernelGGL(k_headcls_fwd, dim3(adt_grid_for((size_t)B * L * H, 256, 1024)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("headcls_fwd");
 }
 
 int adt_headcls_bwd(const float* O, int ldo, const float* Ws, const float* rec, const float* drec, int B, int L,
@@ -525,8 +500,8 @@ int adt_headcls_bwd(const float* O, int ldo, const float* Ws, const float* rec, 
   a.O = O; a.ldo = ldo; a.Ws = Ws; a.B = B; a.L = L; a.H = H; a.hd = hd; a.rec = const_cast<float*>(rec);
   a.drec = drec; a.dO = dO; a.lddo = lddo; a.dWs = dWs; a.dbs = dbs;
   const size_t smem = (size_t)(H * hd + H) * sizeof(float);
-  hipLaunchKernelGGL(k_headcls_bwd, dim3(grid_for((size_t)B * L, 16, 1024)), dim3(256), smem, (hipStream_t)stream, a);
-  return check_launch("headcls_bwd");
+  hipLaunchKernelGGL(k_headcls_bwd, dim3(adt_grid_for((size_t)B * L, 16, 1024)), dim3(256), smem, (hipStream_t)stream, a);
+  return adt_check_launch("headcls_bwd");
 }
 
 int adt_logits_fwd(const float* F, int ldf, const float* E, const int32_t* pos, const int32_t* neg, int T, int d,
@@ -534,8 +509,8 @@ int adt_logits_fwd(const float* F, int ldf, const float* E, const int32_t* pos, 
   LogitsArgs a{};
   a.F = F; a.ldf = ldf; a.E = E; a.pos = pos; a.neg = neg; a.T = T; a.d = d; a.pos_logits = pos_logits;
   a.neg_logits = neg_logits;
-  hipLaunchKernelGGL(k_logits_fwd, dim3(grid_for(T, 16, 2048)), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("logits_fwd");
+  hipLaunchKernelGGL(k_logits_fwd, dim3(adt_grid_for(T, 16, 2048)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("logits_fwd");
 }
 
 int adt_logits_bwd(const float* F, int ldf, const float* E, const int32_t* pos, const int32_t* neg,
@@ -544,36 +519,36 @@ int adt_logits_bwd(const float* F, int ldf, const float* E, const int32_t* pos, 
   LogitsArgs a{};
   a.F = F; a.ldf = ldf; a.E = E; a.pos = pos; a.neg = neg; a.T = T; a.d = d; a.dpos = dpos; a.dneg = dneg;
   a.dF = dF; a.lddf = lddf; a.dE = dE;
-  hipLaunchKernelGGL(k_logits_bwd, dim3(grid_for(T, 16, 2048)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_logits_bwd, dim3(adt_grid_for(T, 16, 2048)), dim3(256), 0, (hipStream_t)stream, a);
   ScatterArgs sc{};
   sc.G = F; sc.ldg = ldf; sc.T = T; sc.d = d; sc.scale = 1.0f; sc.drop = adt_make_drop(0.f, nullptr, 0); sc.dE = dE;
   sc.ids = pos; sc.rowscale = dpos;
-  hipLaunchKernelGGL(k_item_scatter, dim3(grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, sc);
+  hipLaunchKernelGGL(k_item_scatter, dim3(adt_grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, sc);
   sc.ids = neg; sc.rowscale = dneg;
-  hipLaunchKernelGGL(k_item_scatter, dim3(grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, sc);
-  return check_launch("logits_bwd");
+  hipLaunchKernelGGL(k_item_scatter, dim3(adt_grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, sc);
+  return adt_check_launch("logits_bwd");
 }
 
 int adt_bce_seed(const float* pos_logits, const float* neg_logits, const int32_t* pos, int T, const float* norms,
                  float* dpos, float* dneg, float* loss2, void* stream) {
   BceArgs a{pos_logits, neg_logits, pos, T, norms, dpos, dneg, loss2};
-  hipLaunchKernelGGL(k_bce, dim3(grid_for(T, 256, 256)), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("bce_seed");
+  hipLaunchKernelGGL(k_bce, dim3(adt_grid_for(T, 256, 256)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("bce_seed");
 }
 
 int adt_mse_seed(const float* A, const float* Bm, int64_t n, float lambda, const float* norms, float* GA,
                  int accumulate_a, float* GB, float* loss1, void* stream) {
   if (n % 4) return adt_set_error("mse_seed: n %% 4");
   MseArgs a{A, Bm, (size_t)n, lambda, norms, GA, accumulate_a, GB, loss1};
-  hipLaunchKernelGGL(k_mse_seed, dim3(grid_for((size_t)n / 4, 256, 512)), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("mse_seed");
+  hipLaunchKernelGGL(k_mse_seed, dim3(adt_grid_for((size_t)n / 4, 256, 512)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("mse_seed");
 }
 
 int adt_nll_seed(const float* rec, int n_rows, int H, float lambda2, const float* norms, float* drec,
                  float* loss1, void* stream) {
   NllArgs a{rec, n_rows, H, lambda2, norms, drec, loss1};
-  hipLaunchKernelGGL(k_nll_seed, dim3(grid_for((size_t)n_rows * H * H, 256, 512)), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("nll_seed");
+  hipLaunchKernelGGL(k_nll_seed, dim3(adt_grid_for((size_t)n_rows * H * H, 256, 512)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("nll_seed");
 }
 
 // the executor's loss assembly in one launch (adt_host.h); nmse, nnll <= 4
@@ -615,12 +590,12 @@ int adt_loss_seeds_prefetch(const float* pos_logits, const float* neg_logits, co
     a.mse[i] = MseArgs{A[i], Bm[i], (size_t)n, lambdas[i], norms, GA[i], accumulate_a, GB[i], loss_mse[i], (!GA[i] || !GB[i]) ? const_cast<float*>(norms) + 8 + i : nullptr};
   for (int i = 0; i < nnll; ++i) a.nll[i] = NllArgs{rec[i], n_rows, H, lambda2, norms, drec[i], loss_nll[i]};
   a.nmse = nmse; a.nnll = nnll;
-  if (g_lb_set) { a.lb = g_lb_job; a.gl = grid_for(a.lb.T, 4 * 16, 1024); g_lb_set = false; }
-  a.gb = pos_logits ? grid_for(T, 256, 256) : 0;      // no logits: the BCE seed is formed elsewhere (adt_logits_bce_scatter)
-  a.gm = nmse ? grid_for((size_t)n / 4, 256, 512) : 1;
-  a.gn = nnll ? grid_for((size_t)n_rows * H * H, 256, 512) : 1;
+  if (g_lb_set) { a.lb = g_lb_job; a.gl = adt_grid_for(a.lb.T, 4 * 16, 1024); g_lb_set = false; }
+  a.gb = pos_logits ? adt_grid_for(T, 256, 256) : 0;      // no logits: the BCE seed is formed elsewhere (adt_logits_bce_scatter)
+  a.gm = nmse ? adt_grid_for((size_t)n / 4, 256, 512) : 1;
+  a.gn = nnll ? adt_grid_for((size_t)n_rows * H * H, 256, 512) : 1;
   hipLaunchKernelGGL(k_loss_seeds, dim3(a.gl + a.gb + nmse * a.gm + nnll * a.gn + a.gp), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("loss_seeds");
+  return adt_check_launch("loss_seeds");
 }
 
 // ---- deterministic item-table / positional-table gradient (adt_itemgrad.cuh) -----------------------------------------------------------
@@ -671,7 +646,7 @@ int adt_item_sort(const int32_t* const* ids, int nsrc, int T, int V1, const floa
   hipLaunchKernelGGL(k_isort_hist, dim3(IS_NCH), dim3(64), lds, s, a);
   hipLaunchKernelGGL(k_isort_scan_chunks, dim3((V1 + 63) / 64), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_isort_place, dim3(IS_NCH), dim3(64), lds + 256 * sizeof(int), s, a);
-  return check_launch("item_sort");
+  return adt_check_launch("item_sort");
 }
 
 /* dE[item] (accumulate ? += : =) sum over the sorted entries of `item` that belong to the sources in src_mask (rows of items without entries are not touched). */
@@ -707,7 +682,7 @@ int adt_item_segsum(const int32_t* work, int nsrc, int T, int V1, uint32_t src_m
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_item_segsum, dim3(a.nblk), dim3(IG_WAVES * 64), 0, s, a);
   hipLaunchKernelGGL(k_item_carry, dim3(a.nblk), dim3(64), 0, s, a);
-  return check_launch("item_segsum");
+  return adt_check_launch("item_segsum");
 }
 
 /* dP[l] += sum_b [ids != 0] keep / (1 - p) dX[b, l] for nsrc (1 or 2) embedding layers, b ascending */
@@ -716,7 +691,7 @@ int adt_posemb_sum(const int32_t* const* ids, const float* const* dX, const uint
   PosSumArgs a{};
   if (pos_sum_args(a, ids, dX, site, nsrc, B, L, p, seed, row_offset, dP)) return 1;
   hipLaunchKernelGGL(k_posemb_sum, dim3(L), dim3(PS_WAVES * 64), 0, (hipStream_t)stream, a);
-  return check_launch("posemb_sum");
+  return adt_check_launch("posemb_sum");
 }
 
 /* adt_item_segsum + adt_posemb_sum (same p / seed) in one launch + the carry launch */
@@ -730,7 +705,7 @@ int adt_item_segsum_posemb(const int32_t* work, int nsrc, int T, int V1, uint32_
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_item_segsum_posemb, dim3(a.nblk + L), dim3(IG_WAVES * 64), 0, s, a, ps);
   hipLaunchKernelGGL(k_item_carry, dim3(a.nblk), dim3(64), 0, s, a);
-  return check_launch("item_segsum_posemb");
+  return adt_check_launch("item_segsum_posemb");
 }
 
 int adt_clip_adam(float* P, float* G, float* M, float* V, int64_t n, int64_t nE, float wd, float clip, float lr,
@@ -740,10 +715,10 @@ int adt_clip_adam(float* P, float* G, float* M, float* V, int64_t n, int64_t nE,
   a.b1 = b1; a.b2 = b2; a.eps = eps; a.scal = scal; a.grad_scale = grad_scale;
   hipStream_t s = (hipStream_t)stream;
   if (adt::zero_f32_async(scal + 64, 128, s)) return adt_set_error("clip_adam: zero");
-  if (wd != 0.f && nE > 0) hipLaunchKernelGGL(k_sumsq, dim3(grid_for((size_t)nE, 256, 256)), dim3(256), 0, s, (const float*)P, (size_t)nE, scal + 64);
-  hipLaunchKernelGGL(k_wd_gradnorm, dim3(grid_for((size_t)n, 256, 512)), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_adam, dim3(grid_for((size_t)n, 256, 1024)), dim3(256), 0, s, a);
-  return check_launch("clip_adam");
+  if (wd != 0.f && nE > 0) hipLaunchKernelGGL(k_sumsq, dim3(adt_grid_for((size_t)nE, 256, 256)), dim3(256), 0, s, (const float*)P, (size_t)nE, scal + 64);
+  hipLaunchKernelGGL(k_wd_gradnorm, dim3(adt_grid_for((size_t)n, 256, 512)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_adam, dim3(adt_grid_for((size_t)n, 256, 1024)), dim3(256), 0, s, a);
+  return adt_check_launch("clip_adam");
 }
 
 /* adt_clip_adam for a step opened by adt_sasrec_step_begin: scal[64..128) already holds the partial sums of ||E||^2 and scal[128..192) is zero */
@@ -753,9 +728,9 @@ int adt_clip_adam_pre(float* P, float* G, float* M, float* V, int64_t n, int64_t
   a.P = P; a.G = G; a.M = M; a.Vv = V; a.n = (size_t)n; a.nE = (size_t)nE; a.wd = wd; a.clip = clip; a.lr = lr;
   a.b1 = b1; a.b2 = b2; a.eps = eps; a.scal = scal; a.grad_scale = grad_scale;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_wd_gradnorm, dim3(grid_for((size_t)n, 256, 512)), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_adam, dim3(grid_for((size_t)n, 256, 1024)), dim3(256), 0, s, a);
-  return check_launch("clip_adam_pre");
+  hipLaunchKernelGGL(k_wd_gradnorm, dim3(adt_grid_for((size_t)n, 256, 512)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_adam, dim3(adt_grid_for((size_t)n, 256, 1024)), dim3(256), 0, s, a);
+  return adt_check_launch("clip_adam_pre");
 }
 
 /* fold (d0 += replicas r0, d1 += replicas r1) + weight decay on job 0 + ||g||^2 partials, then Adam: adt_replica_reduce2 + adt_clip_adam_pre in two launches.
@@ -768,12 +743,12 @@ int adt_fold_clip_adam(float* P, float* G, float* M, float* V, int64_t n, float*
   a.P = P; a.G = G; a.M = M; a.Vv = V; a.n = (size_t)n; a.nE = (size_t)n0; a.wd = wd; a.clip = clip; a.lr = lr;
   a.b1 = b1; a.b2 = b2; a.eps = eps; a.scal = scal; a.grad_scale = 1.0f;
   RepReduce2Args r{{d0, d1}, {r0, r1}, {(size_t)n0, (size_t)n1}, {nrep0, nrep1}, {(size_t)s0, (size_t)s1}, 0};
-  const int g0 = grid_for((size_t)n0 / 4, 256, 1024), g1 = grid_for((size_t)n1 / 4, 256, 1024);
+  const int g0 = adt_grid_for((size_t)n0 / 4, 256, 1024), g1 = adt_grid_for((size_t)n1 / 4, 256, 1024);
   r.g0 = g0;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_fold_wd_gradnorm, dim3(g0 + g1), dim3(256), 0, s, r, a);
-  hipLaunchKernelGGL(k_adam, dim3(grid_for((size_t)n, 256, 1024)), dim3(256), 0, s, a);
-  return check_launch("fold_clip_adam");
+  hipLaunchKernelGGL(k_adam, dim3(adt_grid_for((size_t)n, 256, 1024)), dim3(256), 0, s, a);
+  return adt_check_launch("fold_clip_adam");
 }
 
 /* adt_fold_clip_adam that also sums the per-sequence partials of the 64 x 64 weight gradients (nslots blocks: slot index inside a workgroup's
@@ -788,7 +763,7 @@ static int fold_parts_impl(bool adam, float* P, float* G, float* M, float* V, in
   a.P = P; a.G = G; a.M = M; a.Vv = V; a.n = (size_t)n; a.nE = (size_t)n0; a.wd = wd; a.clip = clip; a.lr = lr;
   a.b1 = b1; a.b2 = b2; a.eps = eps; a.scal = scal; a.grad_scale = 1.0f; a.fold_only = adam ? 0 : 1;
   RepReduce2Args r{{d0, d1}, {r0, r1}, {(size_t)n0, (size_t)n1}, {nrep0, nrep1}, {(size_t)s0, (size_t)s1}, 0};
-  const int g0 = grid_for((size_t)n0 / 4, 256, 1024), g1 = grid_for((size_t)n1 / 4, 256, 1024);
+  const int g0 = adt_grid_for((size_t)n0 / 4, 256, 1024), g1 = adt_grid_for((size_t)n1 / 4, 256, 1024);
   r.g0 = g0;
   PartFoldArgs pf{};
   pf.part = part; pf.stride = (size_t)part_stride; pf.nslots = nslots; pf.mask_base = d1 - G;
@@ -811,8 +786,8 @@ static int fold_parts_impl(bool adam, float* P, float* G, float* M, float* V, in
   if (gn_part) { a.gn_part = gn_part; a.gn_n = g0 + g1 + g2 + g3; }
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_fold_parts_gradnorm, dim3(g0 + g1 + g2 + g3), dim3(256), 0, s, r, a, pf, vf, g1, g2);
-  if (adam) hipLaunchKernelGGL(k_adam, dim3(grid_for((size_t)n, 256, 1024)), dim3(256), 0, s, a);
-  return check_launch("fold_parts_clip_adam");
+  if (adam) hipLaunchKernelGGL(k_adam, dim3(adt_grid_for((size_t)n, 256, 1024)), dim3(256), 0, s, a);
+  return adt_check_launch("fold_parts_clip_adam");
 }
 
 int adt_fold_parts_clip_adam(float* P, float* G, float* M, float* V, int64_t n, float* d0, const float* r0, int64_t n0, int nrep0, int64_t s0, float* d1,
@@ -845,7 +820,7 @@ int adt_step_begin_launch(uint32_t* seed, uint32_t inc, float* norms_dst, const 
   StepBeginArgs a{seed, inc, norms_dst, norms_src, loss, nloss, scal, G, (size_t)n, E, (size_t)nE, nullptr, 0, 0, nullptr, 0, nullptr, nullptr};
   step_begin_extras(a, Z, nz, pack_base, pack_img, pack_offs, npack);
   hipLaunchKernelGGL(k_step_begin, dim3(256 + a.pk.n), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("step_begin");
+  return adt_check_launch("step_begin");
 }
 
 int adt_step_begin_ring_launch(uint32_t* seed, uint32_t inc, float* norms_dst, float* loss, int nloss, float* scal, float* G, int64_t n, const float* E,
@@ -859,7 +834,7 @@ int adt_step_begin_ring_launch(uint32_t* seed, uint32_t inc, float* norms_dst, f
                   staging, produced};
   step_begin_extras(a, Z, nz, pack_base, pack_img, pack_offs, npack);
   hipLaunchKernelGGL(k_step_begin, dim3(256 + a.pk.n), dim3(256), 0, (hipStream_t)stream, a);
-  return check_launch("step_begin_ring");
+  return adt_check_launch("step_begin_ring");
 }
 
 int adt_clip_adam_l2(float* P, float* G, float* M, float* V, int64_t n, float l2, float clip, float lr, float b1, float b2,
@@ -869,27 +844,27 @@ int adt_clip_adam_l2(float* P, float* G, float* M, float* V, int64_t n, float l2
   a.b1 = b1; a.b2 = b2; a.eps = eps; a.scal = scal; a.grad_scale = grad_scale; a.l2 = l2;
   hipStream_t s = (hipStream_t)stream;
   if (adt::zero_f32_async(scal + 64, 128, s)) return adt_set_error("clip_adam_l2: zero");
-  hipLaunchKernelGGL(k_wd_gradnorm, dim3(grid_for((size_t)n, 256, 512)), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_adam, dim3(grid_for((size_t)n, 256, 1024)), dim3(256), 0, s, a);
-  return check_launch("clip_adam_l2");
+  hipLaunchKernelGGL(k_wd_gradnorm, dim3(adt_grid_for((size_t)n, 256, 512)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_adam, dim3(adt_grid_for((size_t)n, 256, 1024)), dim3(256), 0, s, a);
+  return adt_check_launch("clip_adam_l2");
 }
 
 int adt_score_rank_bias(const float* F, int ldf, const float* E, const float* bias, const int32_t* cand, int B, int C, int d,
                         float* logits, int32_t* rank, void* stream) {
   ScoreArgs a{F, ldf, E, cand, B, C, d, logits, rank, bias};
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_score, dim3(grid_for((size_t)B * C, 16, 4096)), dim3(256), 0, s, a);
-  if (rank) hipLaunchKernelGGL(k_rank, dim3(grid_for(B, 4, 1024)), dim3(256), 0, s, a);
-  return check_launch("score_rank_bias");
+  hipLaunchKernelGGL(k_score, dim3(adt_grid_for((size_t)B * C, 16, 4096)), dim3(256), 0, s, a);
+  if (rank) hipLaunchKernelGGL(k_rank, dim3(adt_grid_for(B, 4, 1024)), dim3(256), 0, s, a);
+  return adt_check_launch("score_rank_bias");
 }
 
 int adt_score_rank(const float* F, int ldf, const float* E, const int32_t* cand, int B, int C, int d,
                    float* logits, int32_t* rank, void* stream) {
   ScoreArgs a{F, ldf, E, cand, B, C, d, logits, rank, nullptr};
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_score, dim3(grid_for((size_t)B * C, 16, 4096)), dim3(256), 0, s, a);
-  if (rank) hipLaunchKernelGGL(k_rank, dim3(grid_for(B, 4, 1024)), dim3(256), 0, s, a);
-  return check_launch("score_rank");
+  hipLaunchKernelGGL(k_score, dim3(adt_grid_for((size_t)B * C, 16, 4096)), dim3(256), 0, s, a);
+  if (rank) hipLaunchKernelGGL(k_rank, dim3(adt_grid_for(B, 4, 1024)), dim3(256), 0, s, a);
+  return adt_check_launch("score_rank");
 }
 
 }  // extern "C"

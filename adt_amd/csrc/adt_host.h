@@ -12,6 +12,39 @@
 int adt_set_error(const char* fmt, ...);
 DropCfg adt_make_drop(float p, const uint32_t* seed, uint32_t site);
 
+// ---- launching; the out-of-line parts are defined next to adt_set_error in adt_capi.hip ----------------------------------------------
+#define ADT_HIDDEN __attribute__((visibility("hidden")))      // shared by the translation units, not exported from libadt_hip.so
+ADT_HIDDEN int adt_check_launch(const char* what);      // hipGetLastError() -> 0, or adt_set_error("<what>: <hip error>")
+
+static inline int adt_grid_for(size_t work_items, int per_block, int cap) {
+  size_t g = (work_items + per_block - 1) / per_block;
+  if (g < 1) g = 1;
+  if (g > (size_t)cap) g = cap;
+  return (int)g;
+}
+
+static inline bool adt_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+
+// Dynamic LDS a kernel has been allowed so far (hipFuncAttributeMaxDynamicSharedMemorySize): one slot per kernel instantiation, kept as a
+// function-local static (or an array of them) by its launcher.  A high-water mark, so a later launch that needs more opts in again.
+struct AdtLdsOptIn { int bytes = 0; };
+constexpr size_t ADT_LDS_MAX = 160 * 1024;      // per workgroup on gfx950
+
+// Launch fn with smem bytes of dynamic LDS: error when smem > ADT_LDS_MAX, opt in when max(smem, optin) is above what slot recorded,
+// hipLaunchKernel, adt_check_launch(what).  optin: a launcher whose smem varies per call passes the most it will ever ask for.
+ADT_HIDDEN int adt_launch_lds(const void* fn, dim3 grid, dim3 block, size_t smem, void** kargs, hipStream_t stream, const char* what, AdtLdsOptIn& slot,
+                              size_t optin = 0);
+template <class Args>      // the usual case: one argument struct
+static inline int adt_launch_lds1(const void* fn, dim3 grid, dim3 block, size_t smem, const Args& a, hipStream_t stream, const char* what,
+                                  AdtLdsOptIn& slot, size_t optin = 0) {
+  void* kargs[] = {const_cast<Args*>(&a)};
+  return adt_launch_lds(fn, grid, block, smem, kargs, stream, what, slot, optin);
+}
+
+// ---- ADT_* switches: read through `static const int on = adt_env_on("ADT_X");`, so once per process and site ---------------------------
+ADT_HIDDEN int adt_env_on(const char* name);                 // on unless the value parses to 0
+ADT_HIDDEN int adt_env_int(const char* name, int dflt);      // atoi of the value; dflt when unset
+
 // dropout sites (identical to oracle/sasrec_oracle.py)
 enum { SITE_EMB_SEQ = 1, SITE_EMB_DEC = 2 };
 static inline uint32_t enc_site(int layer, int which) { return 16u + 8u * (uint32_t)layer + (uint32_t)which; }   // 0 attn 1 ffn1 2 ffn2

@@ -6,12 +6,6 @@
 
 using namespace adt;
 
-static int lce_check(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return adt_set_error("%s: %s", what, hipGetErrorString(e));
-  return 0;
-}
-
 static int g_lce_slots = 0;
 static int lce_slots() {
   if (!g_lce_slots) {
@@ -49,28 +43,16 @@ static LceLayout lce_layout(int mcap, int V, int K, int slots) {
 
 template <int KD, int MODE>
 static int lce_launch(const LceArgs& a, hipStream_t s, const char* what) {
-  static bool done = false;
-  const void* fn = (const void*)k_lce<KD, MODE>;
-  if (!done) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LceGeo<KD>::LDS) != hipSuccess) return adt_set_error("%s: hipFuncSetAttribute", what);
-    done = true;
-  }
-  hipLaunchKernelGGL((k_lce<KD, MODE>), dim3(a.slots), dim3(LCE_NTH), LceGeo<KD>::LDS, s, a);
-  return lce_check(what);
+  static AdtLdsOptIn optin;
+  return adt_launch_lds1((const void*)k_lce<KD, MODE>, dim3(a.slots), dim3(LCE_NTH), LceGeo<KD>::LDS, a, s, what, optin);
 }
 
 template <int KD>
 static int lce_reduce(const LceReduceArgs& a, int nx_cap, hipStream_t s, const char* what) {
-  static bool done = false;
+  static AdtLdsOptIn optin;
   const size_t smem = 32 * (KD + 4) * sizeof(float);
-  const void* fn = (const void*)k_lce_reduce<KD>;
-  if (!done) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return adt_set_error("%s: hipFuncSetAttribute", what);
-    done = true;
-  }
   const int nb = (nx_cap + 31) / 32;
-  hipLaunchKernelGGL((k_lce_reduce<KD>), dim3(nb < 2048 ? nb : 2048), dim3(256), smem, s, a);
-  return lce_check(what);
+  return adt_launch_lds1((const void*)k_lce_reduce<KD>, dim3(nb < 2048 ? nb : 2048), dim3(256), smem, a, s, what, optin);
 }
 
 template <int KD>
@@ -91,14 +73,14 @@ static int lce_run(const float* h, int ldh, const int32_t* rows, const int32_t* 
     hipLaunchKernelGGL(k_lce_pack, dim3(2048), dim3(256), 0, s, p);
     LcePackArgs q{h, ldh, rows, m_dev, mcap, LCE_XR_FWD, KD, Hb, nullptr, nullptr};
     hipLaunchKernelGGL(k_lce_pack, dim3(1024), dim3(256), 0, s, q);
-    if (int rc = lce_check("lce: pack")) return rc;
+    if (int rc = adt_check_launch("lce: pack")) return rc;
   }
   {
     LceArgs a{Hb, Eb, nullptr, biasp, m_dev, nullptr, mcap, V, part_m, part_s, nullptr, nullptr, slots};
     if (int rc = lce_launch<KD, LCE_FWD>(a, s, "lce: forward")) return rc;
     LceCombineArgs c{part_m, part_s, Hb, Eb, bias, labels, m_dev, mcap, V, KD, slots, inv_count, loss64, nlse, lse_out, dE, lddE, dbias};
     hipLaunchKernelGGL(k_lce_combine<KD>, dim3(std::min(4096, (L.Mpad + 15) / 16)), dim3(256), 0, s, c);
-    if (int rc = lce_check("lce: combine")) return rc;
+    if (int rc = adt_check_launch("lce: combine")) return rc;
   }
   if (!dh) return 0;                                       // loss only
   {

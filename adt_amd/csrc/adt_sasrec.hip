@@ -37,8 +37,7 @@ int64_t up64(int64_t x) { return (x + 63) / 64 * 64; }
 // workgroups per sequence of the per-sequence kernels: the largest power of two that keeps B * S within the CUs (ADT_SEQ_SPLIT overrides;
 // 1 at B >= 129).  Small batches -- a data-parallel rank's share of a global batch -- otherwise leave most CUs without a workgroup.
 int seq_split(int B) {
-  static int forced = -1;
-  if (forced < 0) { const char* e = getenv("ADT_SEQ_SPLIT"); forced = e ? atoi(e) : 0; }
+  static const int forced = adt_env_int("ADT_SEQ_SPLIT", 0);
   if (forced > 0) return forced;
   int s = 1;
   while (s < 8 && B * s * 2 <= 256) s *= 2;
@@ -150,8 +149,7 @@ struct SideStream {
 // ADT_SIDE_STREAM: bit 0 the logits' item rows, bit 1 the decoder's embedding gradient + partial sums, bit 2 the encoder's partial sums
 // (default 7, 0 = everything on the caller's stream)
 int side_sites() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("ADT_SIDE_STREAM"); on = e ? (atoi(e) & 7) : 7; }
+  static const int on = adt_env_int("ADT_SIDE_STREAM", 7) & 7;
   return on;
 }
 SideStream* side_stream(hipStream_t main) {
@@ -203,15 +201,13 @@ int side_join(SideStream* sd, int k, void* main) {
 // The item-table and positional-table gradients as sorted segmented sums (adt_itemgrad.cuh) instead of float-atomic scatters into replicas:
 // deterministic, and no atomics-bound kernels beside the chain kernels.  ADT_ITEM_SORT=1 switches it on (default: the scatters).
 bool item_det(const WS& w) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("ADT_ITEM_SORT"); on = (e && atoi(e) != 0) ? 1 : 0; }      // opt-in: +12 us per flagship step (0.637 against 0.625 ms: DESIGN.md "item-table gradient")
+  static const int on = adt_env_int("ADT_ITEM_SORT", 0) != 0;      // opt-in: +12 us per flagship step (0.637 against 0.625 ms: DESIGN.md "item-table gradient")
   return on && w.isort_n > 0;
 }
 
 // ADT_LNL_FUSED=0: the model's last LayerNorm is reversed by its own kernel (k_ln_bwd) instead of inside k_seqtt_post_bwd<ENC>
 bool lnl_fuse_on() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("ADT_LNL_FUSED"); on = (e && atoi(e) == 0) ? 0 : 1; }
+  static const int on = adt_env_on("ADT_LNL_FUSED");
   return on != 0;
 }
 
@@ -272,8 +268,7 @@ int partial_slots(const adt_sasrec_cfg* c, const Layout& lo, bool enc, bool dec,
 // workgroups that write partial slot `slot` of a step with B sequences: the token-chain kernels run S workgroups per sequence
 // k_seqtt_attn_pre_bwd: one workgroup per sequence, two at small batches (ADT_ATTN_SPLIT=0: always one)
 int attn_split(int B) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("ADT_ATTN_SPLIT"); on = (e && atoi(e) == 0) ? 0 : 1; }
+  static const int on = adt_env_on("ADT_ATTN_SPLIT");
   return on && seq_split(B) >= 2 ? 2 : 1;
 }
 // workgroups that wrote partial `slot`
@@ -313,8 +308,7 @@ int partial_slots(const adt_sasrec_cfg* c, const Layout& lo, bool enc, bool dec,
 }
 // single-GPU step: the partials are summed by the optimizer's first kernel (adt_fold_parts_clip_adam), not by k_dwpart_reduce launches
 bool fold_sums_partials(const adt_sasrec_cfg* c, const WS& w) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("ADT_FOLD_PARTS"); on = (e && atoi(e) == 0) ? 0 : 1; }
+  static const int on = adt_env_on("ADT_FOLD_PARTS");
   return on && w.part_stride > 0 && c->num_layers <= 2 && adt_seq_partials(c->prec, c->maxlen, c->hidden, c->hidden / c->num_heads) != 0;
 }
 
@@ -465,22 +459,19 @@ int dec_layer_seq_fwd(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, co
 // and the pos / neg logits + BCE seed are formed by the backward's first side kernel, which gathers E[pos], E[neg] and log_feats anyway
 // (adt_logits_bce_scatter; adt_sasrec_backward with phase bit 4).  Returns 1 when the shape is not covered (nothing launched).
 bool bce_deferred(const adt_sasrec_cfg* c) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("ADT_FWD_FUSED"); on = (e && atoi(e) == 0) ? 0 : 1; }
+  static const int on = adt_env_on("ADT_FWD_FUSED");
   const int d = c->hidden, hd = d / c->num_heads;
   return on && d == 64 && c->num_layers <= 4 && adt_seq_lean(c->prec, c->maxlen, d, hd) != 0;
 }
 // ADT_EMBED3=0: the two embedding gradients and the positive-logit rows keep their own scatters (default: one pass, adt_embed_bwd3 -- deferred
 // path only, without the sorted form)
 bool embed3_on(const WS& w) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("ADT_EMBED3"); on = (e && atoi(e) == 0) ? 0 : 1; }
+  static const int on = adt_env_on("ADT_EMBED3");
   return on != 0 && !item_det(w) && w.d == 64;
 }
 // ADT_BCE_MERGED=0: the forward's logits / BCE kernel (training bit 2) goes to the side stream instead of into the loss launch
 bool bce_merged() {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("ADT_BCE_MERGED"); on = (e && atoi(e) == 0) ? 0 : 1; }
+  static const int on = adt_env_on("ADT_BCE_MERGED");
   return on != 0;
 }
 struct RingRef { const int32_t* ring; int64_t slot_ints; int nslots; uint32_t* state; uint32_t* consumed; int32_t* staging; };
@@ -839,8 +830,7 @@ int adt_sasrec_backward(const adt_sasrec_cfg* c, const float* P, float* G, float
   SideStream* const sd_sort = det ? side_stream((hipStream_t)st) : nullptr;      // the id sort runs beside the decoder's chain kernels, also in the two-phase form
   // (one-phase backward by default: the two-phase form belongs to the data-parallel step, whose capture already carries the collectives'
   // stream; there the side stream measured 0.692 against 0.699 ms on a 1-rank RCCL group and is opt-in: ADT_SIDE_STREAM_DP=1)
-  static int dp_on = -1;
-  if (dp_on < 0) { const char* e = getenv("ADT_SIDE_STREAM_DP"); dp_on = (e && atoi(e) != 0) ? 1 : 0; }
+  static const int dp_on = adt_env_int("ADT_SIDE_STREAM_DP", 0) != 0;
   SideStream* const sd = (phase == 0 || dp_on) ? side_stream((hipStream_t)st) : nullptr;
   int dec_side = 0;      // the decoder's embedding gradient + partial sums on the side stream: 1 marked, 2 enqueued
   bool dec_parts_done = false;

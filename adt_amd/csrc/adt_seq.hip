@@ -1,6 +1,6 @@
 // Launchers of the per-sequence fused layer kernels (adt_seqfwd.cuh, adt_seqbwd.cuh): one workgroup per user sequence.
 #include "adt_host.h"
-#include <stdlib.h>
+#include <limits.h>
 #include "adt_seqfwd.cuh"
 #include "adt_seqfwd_tt.cuh"
 #include "adt_seqattn.cuh"
@@ -9,21 +9,9 @@
 
 using namespace adt;
 
-static int seq_check(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return adt_set_error("%s: %s", what, hipGetErrorString(e));
-  return 0;
-}
-
-static int seq_launch(const void* fn, size_t smem, bool& attr_done, int grid, const void* args_ptr, hipStream_t s, const char* what, int nwaves = SQ_NW) {
-  if (!attr_done) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-      return adt_set_error("%s: hipFuncSetAttribute(%zu)", what, smem);
-    attr_done = true;
-  }
-  void* kargs[] = {const_cast<void*>(args_ptr)};
-  if (hipLaunchKernel(fn, dim3(grid), dim3(nwaves * 64), kargs, smem, s) != hipSuccess) return adt_set_error("%s: launch failed", what);
-  return seq_check(what);
+template <class Args>
+static int seq_launch(const void* fn, size_t smem, AdtLdsOptIn& slot, int grid, const Args* args, hipStream_t s, const char* what, int nwaves = SQ_NW) {
+  return adt_launch_lds1(fn, dim3(grid), dim3(nwaves * 64), smem, *args, s, what, slot);
 }
 
 // ---- pre-packed weight images (adt_wave.cuh: WPack) -----------------------------------------------------------------------------
@@ -35,24 +23,21 @@ extern "C" int adt_pack_wimg(const float* base, void* img, const int* offs, int 
   a.base = base; a.img = reinterpret_cast<__bf16*>(img); a.n = n;
   for (int i = 0; i < n; ++i) a.off[i] = offs[i];
   hipLaunchKernelGGL(k_pack_wimg, dim3(n), dim3(256), 0, (hipStream_t)stream, a);
-  return seq_check("pack_wimg");
+  return adt_check_launch("pack_wimg");
 }
 
 int adt_seq_supported(int prec, int L, int d, int hd) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("ADT_SEQ"); on = (e && atoi(e) == 0) ? 0 : 1; }
+  static const int on = adt_env_on("ADT_SEQ");
   return on && prec == ADT_PREC_BF16 && d == 64 && L <= SQ_LP && (hd == 16 || hd == 32 || hd == 64);
 }
-
-static int env_on(const char* name) { const char* e = getenv(name); return (e && atoi(e) == 0) ? 0 : 1; }
 
 // Lean saved tensors: the transposed-chain forward writes o, h, u, a1, q2, kv2, o2 as bf16 rows and does not write LN(x) / qkv at all (the fused
 // block backward recomputes them from x).  Only when every kernel of the backward that reads them is the per-sequence / flag-aware one:
 // the caller must then treat a "not covered" (1) from adt_launch_seq_attn_pre_bwd / adt_launch_seq_attn_bwd as an error.  ADT_SEQ_LEAN=0: off.
 int adt_seq_lean(int prec, int L, int d, int hd) {
-  static int on = -1;
-  if (on < 0) on = env_on("ADT_SEQ_LEAN") && env_on("ADT_SEQ_TT") && env_on("ADT_SEQ_BWD") && env_on("ADT_SEQ_ATTN_BWD") && !getenv("ADT_SEQ_ABLATE");
-  return on && adt_seq_supported(prec, L, d, hd) && (L & 3) == 0 && L <= SB_R && L <= 224 && sab_lds_bytes(L, 64 / hd) <= 160 * 1024;
+  static const int on = adt_env_on("ADT_SEQ_LEAN") && adt_env_on("ADT_SEQ_TT") && adt_env_on("ADT_SEQ_BWD") && adt_env_on("ADT_SEQ_ATTN_BWD") &&
+                        adt_env_int("ADT_SEQ_ABLATE", INT_MIN) == INT_MIN;      // ADT_SEQ_ABLATE set at all, to 0 included: off
+  return on && adt_seq_supported(prec, L, d, hd) && (L & 3) == 0 && L <= SB_R && L <= 224 && sab_lds_bytes(L, 64 / hd) <= ADT_LDS_MAX;
 }
 
 static unsigned long long* g_stamps = nullptr;
@@ -63,99 +48,87 @@ extern "C" int adt_seq_stamps_read(unsigned long long* out, int n) {      // deb
   return hipMemcpy(out, g_stamps, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
 }
 
-static unsigned long long* seq_stamp_buffer(bool for_attention) {      // ADT_SEQ_STAMPS=1: forward kernels; =2: the attention backward
-  static int st = -1;
-  if (st < 0) {
-    const char* e = getenv("ADT_SEQ_STAMPS");
-    st = e ? atoi(e) : 0;
-    if (st && hipMalloc(&g_stamps, 16 * 16 * sizeof(unsigned long long)) != hipSuccess) st = 0;
-  }
-  return (st == (for_attention ? 2 : 1)) ? g_stamps : nullptr;
+static int seq_stamps_mode() {      // ADT_SEQ_STAMPS=1: forward kernels; =2: the attention backward; =3: the encoder post chain backward
+  static const int st = [] {
+    const int v = adt_env_int("ADT_SEQ_STAMPS", 0);
+    return (v && hipMalloc(&g_stamps, 16 * 16 * sizeof(unsigned long long)) != hipSuccess) ? 0 : v;
+  }();
+  return st;
 }
-static unsigned long long* seq_stamp_buffer_post() { seq_stamp_buffer(false); const char* e = getenv("ADT_SEQ_STAMPS"); return (e && atoi(e) == 3) ? g_stamps : nullptr; }
+static unsigned long long* seq_stamp_buffer(bool for_attention) { return seq_stamps_mode() == (for_attention ? 2 : 1) ? g_stamps : nullptr; }
+static unsigned long long* seq_stamp_buffer_post() { return seq_stamps_mode() == 3 ? g_stamps : nullptr; }
 
 static void seq_ablate(SeqFwdArgs& a) {
   a.stamps = seq_stamp_buffer(false);
-  static int ab = -1;
-  if (ab < 0) { const char* e = getenv("ADT_SEQ_ABLATE"); ab = e ? atoi(e) : 0; }
+  static const int ab = adt_env_int("ADT_SEQ_ABLATE", 0);
   a.ablate = ab;
   if (ab & 1) { a.qkv = nullptr; a.o = nullptr; a.h = nullptr; a.u = nullptr; a.a1 = nullptr; a.q2 = nullptr; a.kv2 = nullptr; a.o2 = nullptr; a.mask = nullptr; a.mask2 = nullptr; }
 }
 
 static bool seq_use_tt(const SeqFwdArgs& a) {     // register-resident transposed chains (adt_seqfwd_tt.cuh); ADT_SEQ_TT=0: the row-major fused form
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("ADT_SEQ_TT"); on = (e && atoi(e) == 0) ? 0 : 1; }
+  static const int on = adt_env_on("ADT_SEQ_TT");
   return on && a.wp_img != nullptr && (a.L & 3) == 0;      // L % 4 == 0: a quad of attention keys shares one dropout hash word
 }
 
 int adt_launch_seq_enc_fwd(int hd, const SeqFwdArgs& a, void* stream) {
-  static bool done[3] = {false, false, false};
-  static bool done_tt[3] = {false, false, false};
+  static AdtLdsOptIn optin[3], optin_tt[3];
   SeqFwdArgs args = a;
   seq_ablate(args);
   hipStream_t s = (hipStream_t)stream;
   if (seq_use_tt(args)) {
     const int nsp = args.nsplit > 1 ? args.nsplit : 1;
     const size_t smem_tt = SeqTtLds<6>::bytes;
-    if (hd == 64) return seq_launch((const void*)k_seqtt_enc_fwd<64>, smem_tt, done_tt[0], a.B * nsp, &args, s, "seqtt_enc_fwd<64>", TQ_FWD_NW);
-    if (hd == 32) return seq_launch((const void*)k_seqtt_enc_fwd<32>, smem_tt, done_tt[1], a.B * nsp, &args, s, "seqtt_enc_fwd<32>", TQ_FWD_NW);
-    if (hd == 16) return seq_launch((const void*)k_seqtt_enc_fwd<16>, smem_tt, done_tt[2], a.B * nsp, &args, s, "seqtt_enc_fwd<16>", TQ_FWD_NW);
+    if (hd == 64) return seq_launch((const void*)k_seqtt_enc_fwd<64>, smem_tt, optin_tt[0], a.B * nsp, &args, s, "seqtt_enc_fwd<64>", TQ_FWD_NW);
+    if (hd == 32) return seq_launch((const void*)k_seqtt_enc_fwd<32>, smem_tt, optin_tt[1], a.B * nsp, &args, s, "seqtt_enc_fwd<32>", TQ_FWD_NW);
+    if (hd == 16) return seq_launch((const void*)k_seqtt_enc_fwd<16>, smem_tt, optin_tt[2], a.B * nsp, &args, s, "seqtt_enc_fwd<16>", TQ_FWD_NW);
   }
   args.nsplit = 0;
   const size_t smem = SeqFwdLds<6>::bytes;
-  if (hd == 64) return seq_launch((const void*)k_seq_enc_fwd<64, 2>, smem, done[0], a.B, &args, s, "seq_enc_fwd<64>");
-  if (hd == 32) return seq_launch((const void*)k_seq_enc_fwd<32, 2>, smem, done[1], a.B, &args, s, "seq_enc_fwd<32>");
-  if (hd == 16) return seq_launch((const void*)k_seq_enc_fwd<16, 4>, smem, done[2], a.B, &args, s, "seq_enc_fwd<16>");
+  if (hd == 64) return seq_launch((const void*)k_seq_enc_fwd<64, 2>, smem, optin[0], a.B, &args, s, "seq_enc_fwd<64>");
+  if (hd == 32) return seq_launch((const void*)k_seq_enc_fwd<32, 2>, smem, optin[1], a.B, &args, s, "seq_enc_fwd<32>");
+  if (hd == 16) return seq_launch((const void*)k_seq_enc_fwd<16, 4>, smem, optin[2], a.B, &args, s, "seq_enc_fwd<16>");
   return adt_set_error("seq_enc_fwd: head size %d", hd);
 }
 
 int adt_launch_seq_dec_fwd(int hd, const SeqFwdArgs& a, void* stream) {
-  static bool done[3] = {false, false, false};
-  static bool done_tt[3] = {false, false, false};
+  static AdtLdsOptIn optin[3], optin_tt[3];
   SeqFwdArgs args = a;
   seq_ablate(args);
   hipStream_t s = (hipStream_t)stream;
   if (seq_use_tt(args)) {
     const int nsp = args.nsplit > 1 ? args.nsplit : 1;
     const size_t smem_tt = SeqTtLds<5>::bytes;
-    if (hd == 64) return seq_launch((const void*)k_seqtt_dec_fwd<64>, smem_tt, done_tt[0], a.B * nsp, &args, s, "seqtt_dec_fwd<64>", TQ_FWD_NW);
-    if (hd == 32) return seq_launch((const void*)k_seqtt_dec_fwd<32>, smem_tt, done_tt[1], a.B * nsp, &args, s, "seqtt_dec_fwd<32>", TQ_FWD_NW);
-    if (hd == 16) return seq_launch((const void*)k_seqtt_dec_fwd<16>, smem_tt, done_tt[2], a.B * nsp, &args, s, "seqtt_dec_fwd<16>", TQ_FWD_NW);
+    if (hd == 64) return seq_launch((const void*)k_seqtt_dec_fwd<64>, smem_tt, optin_tt[0], a.B * nsp, &args, s, "seqtt_dec_fwd<64>", TQ_FWD_NW);
+    if (hd == 32) return seq_launch((const void*)k_seqtt_dec_fwd<32>, smem_tt, optin_tt[1], a.B * nsp, &args, s, "seqtt_dec_fwd<32>", TQ_FWD_NW);
+    if (hd == 16) return seq_launch((const void*)k_seqtt_dec_fwd<16>, smem_tt, optin_tt[2], a.B * nsp, &args, s, "seqtt_dec_fwd<16>", TQ_FWD_NW);
   }
   args.nsplit = 0;
   const size_t smem = SeqFwdLds<5>::bytes;
-  if (hd == 64) return seq_launch((const void*)k_seq_dec_fwd<64>, smem, done[0], a.B, &args, s, "seq_dec_fwd<64>");
-  if (hd == 32) return seq_launch((const void*)k_seq_dec_fwd<32>, smem, done[1], a.B, &args, s, "seq_dec_fwd<32>");
-  if (hd == 16) return seq_launch((const void*)k_seq_dec_fwd<16>, smem, done[2], a.B, &args, s, "seq_dec_fwd<16>");
+  if (hd == 64) return seq_launch((const void*)k_seq_dec_fwd<64>, smem, optin[0], a.B, &args, s, "seq_dec_fwd<64>");
+  if (hd == 32) return seq_launch((const void*)k_seq_dec_fwd<32>, smem, optin[1], a.B, &args, s, "seq_dec_fwd<32>");
+  if (hd == 16) return seq_launch((const void*)k_seq_dec_fwd<16>, smem, optin[2], a.B, &args, s, "seq_dec_fwd<16>");
   return adt_set_error("seq_dec_fwd: head size %d", hd);
 }
 
 // causal attention backward, one workgroup per sequence (adt_seqattn.cuh); returns 1 when the shape is not covered (caller falls back)
 int adt_launch_seq_attn_bwd(int hd, const AttnArgs& a, void* stream) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("ADT_SEQ_ATTN_BWD"); on = (e && atoi(e) == 0) ? 0 : 1; }
+  static const int on = adt_env_on("ADT_SEQ_ATTN_BWD");
   if (!on || !a.causal || a.H * hd != 64 || a.L > 224) return 1;
   if ((a.ldq % 4) || (a.ldk % 4) || (a.ldv % 4) || (a.ldo % 4)) return 1;
   if (a.in_bf16 && ((a.ldq % 8) || (a.ldk % 8) || (a.ldv % 8) || (a.ldo % 8))) return 1;
   const size_t smem = sab_lds_bytes(a.L, a.H);
-  if (smem > 160 * 1024) return 1;
+  if (smem > ADT_LDS_MAX) return 1;
   const int mode = a.drop.thr == 0 ? 0 : (a.mask != nullptr ? 1 : 2);
-  static bool done[9] = {false, false, false, false, false, false, false, false, false};
+  static AdtLdsOptIn optin[9];
   const void* fns[9] = {(const void*)k_seq_attn_bwd<64, 0>, (const void*)k_seq_attn_bwd<64, 1>, (const void*)k_seq_attn_bwd<64, 2>,
                         (const void*)k_seq_attn_bwd<32, 0>, (const void*)k_seq_attn_bwd<32, 1>, (const void*)k_seq_attn_bwd<32, 2>,
                         (const void*)k_seq_attn_bwd<16, 0>, (const void*)k_seq_attn_bwd<16, 1>, (const void*)k_seq_attn_bwd<16, 2>};
   if (hd != 64 && hd != 32 && hd != 16) return 1;
   const int slot = (hd == 64 ? 0 : hd == 32 ? 3 : 6) + mode;
-  const void* fn = fns[slot];
-  if (!done[slot]) {      // the attribute is the maximum this kernel may ask for, not this launch's size
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return adt_set_error("seq_attn_bwd: hipFuncSetAttribute");
-    done[slot] = true;
-  }
   AttnArgs args = a;
   args.stamps = seq_stamp_buffer(true);
-  void* kargs[] = {&args};
-  if (hipLaunchKernel(fn, dim3(a.B), dim3(SAB_NW * 64), kargs, smem, (hipStream_t)stream) != hipSuccess) return adt_set_error("seq_attn_bwd: launch failed");
-  return seq_check("seq_attn_bwd");
+  // smem varies with L: opt in once to the most this kernel may ask for
+  return adt_launch_lds1(fns[slot], dim3(a.B), dim3(SAB_NW * 64), smem, args, (hipStream_t)stream, "seq_attn_bwd", optin[slot], ADT_LDS_MAX);
 }
 
 // fused backward of one attention block (adt_seqbwd_tt.cuh); dec = 0: encoder block, 1: decoder self-attention block.
@@ -164,19 +137,18 @@ template <int HD, bool DEC>
 static int seq_attn_pre_bwd_t(int mode, const SeqBwdArgs& a, hipStream_t s) {
   constexpr int H = 64 / HD;
   const size_t smem = SeqBwdLds<H>::bytes;
-  static bool done[3] = {false, false, false};
+  static AdtLdsOptIn optin[3];
   const void* fns[3] = {(const void*)k_seqtt_attn_pre_bwd<HD, 0, DEC>, (const void*)k_seqtt_attn_pre_bwd<HD, 1, DEC>,
                         (const void*)k_seqtt_attn_pre_bwd<HD, 2, DEC>};
   SeqBwdArgs args = a;
   args.stamps = seq_stamp_buffer(true);
   if (a.nsplit == 2 && !a.part) return adt_set_error("seqtt_attn_pre_bwd: two workgroups per sequence need the weight-gradient partials");
   if (a.nsplit != 2) args.nsplit = 1;
-  return seq_launch(fns[mode], smem, done[mode], a.B * args.nsplit, &args, s, "seqtt_attn_pre_bwd");
+  return seq_launch(fns[mode], smem, optin[mode], a.B * args.nsplit, &args, s, "seqtt_attn_pre_bwd");
 }
 
 int adt_launch_seq_attn_pre_bwd(int hd, int dec, const SeqBwdArgs& a, void* stream) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("ADT_SEQ_BWD"); on = (e && atoi(e) == 0) ? 0 : 1; }
+  static const int on = adt_env_on("ADT_SEQ_BWD");
   if (!on || a.wp_img == nullptr || a.L > SB_R || (a.L & 3) || a.H * hd != 64) return 1;
   const int mode = a.drop.thr == 0 ? 0 : (a.mask != nullptr ? 1 : 2);
   hipStream_t s = (hipStream_t)stream;
@@ -188,27 +160,26 @@ int adt_launch_seq_attn_pre_bwd(int hd, int dec, const SeqBwdArgs& a, void* stre
 
 // per-sequence backward of the token-wise chains (adt_seqpost_tt.cuh); 0 launched, 1 not covered (the caller runs the row-major chain kernels)
 static bool seq_post_ok(const BwdChainArgs& a, int hd) {
-  static int on = -1;
-  if (on < 0) on = env_on("ADT_SEQ_POST_BWD");
+  static const int on = adt_env_on("ADT_SEQ_POST_BWD");
   return on && a.wp_img != nullptr && a.L <= SB_R && a.T == a.B * a.L && (hd == 16 || hd == 32 || hd == 64);
 }
 
 int adt_launch_seq_post_bwd(int hd, int enc, const BwdChainArgs& a, void* stream) {
   if (!seq_post_ok(a, hd)) return 1;
   if (enc && a.drec != nullptr && a.H * hd != 64) return 1;
-  static bool done[6] = {false, false, false, false, false, false};
+  static AdtLdsOptIn optin[6];
   const void* fns[6] = {(const void*)k_seqtt_post_bwd<64, false>, (const void*)k_seqtt_post_bwd<64, true>, (const void*)k_seqtt_post_bwd<32, false>,
                         (const void*)k_seqtt_post_bwd<32, true>, (const void*)k_seqtt_post_bwd<16, false>, (const void*)k_seqtt_post_bwd<16, true>};
   const int slot = (hd == 64 ? 0 : hd == 32 ? 2 : 4) + (enc ? 1 : 0);
   BwdChainArgs args = a;
   args.stamps = enc ? seq_stamp_buffer_post() : nullptr;
-  return seq_launch(fns[slot], SeqPostLds<3>::bytes, done[slot], a.B * (a.nsplit > 1 ? a.nsplit : 1), &args, (hipStream_t)stream, "seqtt_post_bwd", SP_NW);
+  return seq_launch(fns[slot], SeqPostLds<3>::bytes, optin[slot], a.B * (a.nsplit > 1 ? a.nsplit : 1), &args, (hipStream_t)stream, "seqtt_post_bwd", SP_NW);
 }
 
 int adt_launch_seq_mid_bwd(int hd, const BwdChainArgs& a, void* stream) {
   if (!seq_post_ok(a, hd)) return 1;
-  static bool done = false;
-  return seq_launch((const void*)k_seqtt_mid_bwd, SeqPostLds<4>::bytes, done, a.B * (a.nsplit > 1 ? a.nsplit : 1), &a, (hipStream_t)stream, "seqtt_mid_bwd", SP_MID_NW);
+  static AdtLdsOptIn optin;
+  return seq_launch((const void*)k_seqtt_mid_bwd, SeqPostLds<4>::bytes, optin, a.B * (a.nsplit > 1 ? a.nsplit : 1), &a, (hipStream_t)stream, "seqtt_mid_bwd", SP_MID_NW);
 }
 
 // ---- sum of the per-workgroup weight-gradient partials (adt_seqbwd_tt.cuh: sb_dw_tiles) --------------------------------------------
@@ -274,12 +245,11 @@ int adt_dwpart_reduce_n(float* G, const float* part, size_t stride, int nwg, con
   a.G = G; a.part = part; a.stride = stride; a.nwg = nwg; a.nslots = nslots;
   for (int i = 0; i < nslots; ++i) { a.slot[i] = slots[i]; a.off[i] = offs[i]; a.nwg_slot[i] = nwg_slot ? nwg_slot[i] : nwg; }
   hipLaunchKernelGGL(k_dwpart_reduce, dim3(nslots, PR_SPLIT), dim3(256), 0, (hipStream_t)stream, a);
-  return seq_check("dwpart_reduce");
+  return adt_check_launch("dwpart_reduce");
 }
 
 // every block-weight gradient of the backward can go through private partials: all five per-sequence backward kernels cover the shape
 int adt_seq_partials(int prec, int L, int d, int hd) {
-  static int on = -1;
-  if (on < 0) on = env_on("ADT_SEQ_PARTIALS") && env_on("ADT_SEQ_POST_BWD");
+  static const int on = adt_env_on("ADT_SEQ_PARTIALS") && adt_env_on("ADT_SEQ_POST_BWD");
   return on && adt_seq_lean(prec, L, d, hd);
 }

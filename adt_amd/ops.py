@@ -263,14 +263,12 @@ def attn_masked_fwd(prec, Q, K, V, B, H, L, causal=False, key_ids=None, fill=-1e
     hd = d // H
     O = torch.empty(B * L, d, device=Q.device, dtype=torch.float32)
     LSE = torch.empty(B * H * L, device=Q.device, dtype=torch.float32)
-    if scale is not None:
-        _lib.check(_lib.load().adt_attn_masked_scaled_fwd(prec, _p(_f32(Q)), _ld(Q), _p(_f32(K)), _ld(K), _p(_f32(V)), _ld(V), B, H, L, hd, float(scale),
-                                                          int(causal), _p(key_ids), float(fill), float(p), _p(seed), site, b_offset, _p(O), d, _p(LSE),
-                                                          _stream()), "attn_masked_scaled_fwd")
-        return O, LSE
-    _lib.check(_lib.load().adt_attn_masked_fwd(prec, _p(_f32(Q)), _ld(Q), _p(_f32(K)), _ld(K), _p(_f32(V)), _ld(V), B, H, L, hd, int(causal),
-                                               _p(key_ids), float(fill), float(p), _p(seed), site, b_offset, _p(O), d, _p(LSE), _stream()),
-               "attn_masked_fwd")
+    args = [prec, _p(_f32(Q)), _ld(Q), _p(_f32(K)), _ld(K), _p(_f32(V)), _ld(V), B, H, L, hd, int(causal), _p(key_ids), float(fill), float(p),
+            _p(seed), site, b_offset, _p(O), d, _p(LSE), _stream()]
+    if scale is None:
+        _lib.check(_lib.load().adt_attn_masked_fwd(*args), "attn_masked_fwd")
+    else:      # the scaled entry point takes the scale after hd
+        _lib.check(_lib.load().adt_attn_masked_scaled_fwd(*args[:11], float(scale), *args[11:]), "attn_masked_scaled_fwd")
     return O, LSE
 
 
@@ -284,15 +282,12 @@ def attn_masked_bwd(prec, Q, K, V, O, LSE, dO, B, H, L, causal=False, key_ids=No
         dV = torch.empty_like(dQ)
     else:
         dQ, dK, dV = out
-    if scale is not None:
-        _lib.check(_lib.load().adt_attn_masked_scaled_bwd(prec, _p(_f32(Q)), _ld(Q), _p(_f32(K)), _ld(K), _p(_f32(V)), _ld(V), _p(_f32(O)), _ld(O),
-                                                          _p(LSE), _p(_f32(dO)), _ld(dO), B, H, L, hd, float(scale), int(causal), _p(key_ids),
-                                                          float(fill), float(p), _p(seed), site, b_offset, _p(dQ), _ld(dQ), _p(dK), _ld(dK), _p(dV),
-                                                          _ld(dV), _stream()), "attn_masked_scaled_bwd")
-        return dQ, dK, dV
-    _lib.check(_lib.load().adt_attn_masked_bwd(prec, _p(_f32(Q)), _ld(Q), _p(_f32(K)), _ld(K), _p(_f32(V)), _ld(V), _p(_f32(O)), _ld(O), _p(LSE),
-                                               _p(_f32(dO)), _ld(dO), B, H, L, hd, int(causal), _p(key_ids), float(fill), float(p), _p(seed), site,
-                                               b_offset, _p(dQ), _ld(dQ), _p(dK), _ld(dK), _p(dV), _ld(dV), _stream()), "attn_masked_bwd")
+    args = [prec, _p(_f32(Q)), _ld(Q), _p(_f32(K)), _ld(K), _p(_f32(V)), _ld(V), _p(_f32(O)), _ld(O), _p(LSE), _p(_f32(dO)), _ld(dO), B, H, L, hd,
+            int(causal), _p(key_ids), float(fill), float(p), _p(seed), site, b_offset, _p(dQ), _ld(dQ), _p(dK), _ld(dK), _p(dV), _ld(dV), _stream()]
+    if scale is None:
+        _lib.check(_lib.load().adt_attn_masked_bwd(*args), "attn_masked_bwd")
+    else:
+        _lib.check(_lib.load().adt_attn_masked_scaled_bwd(*args[:16], float(scale), *args[16:]), "attn_masked_scaled_bwd")
     return dQ, dK, dV
 
 
@@ -369,47 +364,50 @@ def score_rank_bias(F, ldf, E, bias, cand, B, C, want_rank=True):
     return logits, rank
 
 
-def wattn_fwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p=0.0, seed=None, site=0, b_offset=0, prec=None):
-    """prec: PREC_BF16 / PREC_F32 selects the matrix-core kernels (adt_wattn_mfma.cuh) where they cover the shape; None (or an
-    uncovered shape) the exact vector-ALU kernels."""
+def _stosa_attn_call(mfma, valu, args, prec):
+    """adt_<mfma> (matrix cores) when prec is given and that entry point covers the shape (rc != 1), else adt_<valu> (vector ALU, exact)."""
+    lib = _lib.load()
+    if prec is not None:
+        rc = getattr(lib, "adt_" + mfma)(int(prec), *args)
+        if rc != 1:
+            return _lib.check(rc, mfma)
+    _lib.check(getattr(lib, "adt_" + valu)(*args), valu)
+
+
+def _stosa_attn_fwd(mfma, valu, Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, site, b_offset, prec):
     d = Qm.shape[1]
     hd = d // H
     Om = torch.empty(B * L, d, device=Qm.device, dtype=torch.float32)
     Oc = torch.empty_like(Om)
     LSE = torch.empty(B * H * L, device=Qm.device, dtype=torch.float32)
-    if prec is not None:
-        rc = _lib.load().adt_wattn_mfma_fwd(int(prec), _p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc),
-                                            _p(_f32(Vm)), _ld(Vm), _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), B, H, L, hd, float(p), _p(seed), site,
-                                            b_offset, _p(Om), d, _p(Oc), d, _p(LSE), _stream())
-        if rc != 1:
-            _lib.check(rc, "wattn_mfma_fwd")
-            return Om, Oc, LSE
-    _lib.check(_lib.load().adt_wattn_fwd(_p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc), _p(_f32(Vm)), _ld(Vm),
-                                         _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), B, H, L, hd, float(p), _p(seed), site, b_offset, _p(Om), d, _p(Oc), d,
-                                         _p(LSE), _stream()), "wattn_fwd")
+    args = [_p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc), _p(_f32(Vm)), _ld(Vm), _p(_f32(Vc)), _ld(Vc),
+            _p(_i32(key_ids)), B, H, L, hd, float(p), _p(seed), site, b_offset, _p(Om), d, _p(Oc), d, _p(LSE), _stream()]
+    _stosa_attn_call(mfma, valu, args, prec)
     return Om, Oc, LSE
 
 
-def wattn_bwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p=0.0, seed=None, site=0, b_offset=0, out=None, prec=None):
-    """out: optional (dQm, dQc, dKm, dKc, dVm, dVc) views sharing one row stride.  prec: as wattn_fwd (use the same value)."""
+def _stosa_attn_bwd(mfma, valu, Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site, b_offset, out, prec):
     d = Qm.shape[1]
     hd = d // H
     outs = [torch.empty(B * L, d, device=Qm.device, dtype=torch.float32) for _ in range(6)] if out is None else list(out)
     ldd = _ld(outs[0])
     assert all(_ld(o) == ldd for o in outs)
-    if prec is not None:
-        rc = _lib.load().adt_wattn_mfma_bwd(int(prec), _p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc),
-                                            _p(_f32(Vm)), _ld(Vm), _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), _p(Om), _ld(Om), _p(Oc), _ld(Oc), _p(LSE),
-                                            _p(_f32(dOm)), _ld(dOm), _p(_f32(dOc)), _ld(dOc), B, H, L, hd, float(p), _p(seed), site, b_offset,
-                                            *[_p(o) for o in outs], ldd, _stream())
-        if rc != 1:
-            _lib.check(rc, "wattn_mfma_bwd")
-            return outs
-    _lib.check(_lib.load().adt_wattn_bwd(_p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc), _p(_f32(Vm)), _ld(Vm),
-                                         _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), _p(Om), _ld(Om), _p(Oc), _ld(Oc), _p(LSE), _p(_f32(dOm)), _ld(dOm),
-                                         _p(_f32(dOc)), _ld(dOc), B, H, L, hd, float(p), _p(seed), site, b_offset, *[_p(o) for o in outs], ldd, _stream()),
-               "wattn_bwd")
+    args = [_p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc), _p(_f32(Vm)), _ld(Vm), _p(_f32(Vc)), _ld(Vc),
+            _p(_i32(key_ids)), _p(Om), _ld(Om), _p(Oc), _ld(Oc), _p(LSE), _p(_f32(dOm)), _ld(dOm), _p(_f32(dOc)), _ld(dOc), B, H, L, hd, float(p),
+            _p(seed), site, b_offset, *[_p(o) for o in outs], ldd, _stream()]
+    _stosa_attn_call(mfma, valu, args, prec)
     return outs
+
+
+def wattn_fwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p=0.0, seed=None, site=0, b_offset=0, prec=None):
+    """prec: PREC_BF16 / PREC_F32 selects the matrix-core kernels (adt_wattn_mfma.cuh) where they cover the shape; None (or an
+    uncovered shape) the exact vector-ALU kernels."""
+    return _stosa_attn_fwd("wattn_mfma_fwd", "wattn_fwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, site, b_offset, prec)
+
+
+def wattn_bwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p=0.0, seed=None, site=0, b_offset=0, out=None, prec=None):
+    """out: optional (dQm, dQc, dKm, dKc, dVm, dVc) views sharing one row stride.  prec: as wattn_fwd (use the same value)."""
+    return _stosa_attn_bwd("wattn_mfma_bwd", "wattn_bwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site, b_offset, out, prec)
 
 
 def wdist_bpr(Sm, Sc, Em, Ec, pos, neg, pvn_weight, inv_count, dEm, dEc, loss3):
@@ -432,45 +430,13 @@ def klattn_fwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p=0.0, seed=None, site=
     """KL-divergence attention, arguments and outputs as wattn_fwd.  prec: PREC_BF16 / PREC_F32 selects the matrix-core kernels
     (adt_wattn_mfma.cuh with the KL score) where they cover the shape; None (or an uncovered shape) the exact vector-ALU kernels
     (adt_klattn.cuh)."""
-    d = Qm.shape[1]
-    hd = d // H
-    Om = torch.empty(B * L, d, device=Qm.device, dtype=torch.float32)
-    Oc = torch.empty_like(Om)
-    LSE = torch.empty(B * H * L, device=Qm.device, dtype=torch.float32)
-    if prec is not None:
-        rc = _lib.load().adt_klattn_mfma_fwd(int(prec), _p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc),
-                                             _p(_f32(Vm)), _ld(Vm), _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), B, H, L, hd, float(p), _p(seed), site,
-                                             b_offset, _p(Om), d, _p(Oc), d, _p(LSE), _stream())
-        if rc != 1:
-            _lib.check(rc, "klattn_mfma_fwd")
-            return Om, Oc, LSE
-    _lib.check(_lib.load().adt_klattn_fwd(_p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc), _p(_f32(Vm)), _ld(Vm),
-                                          _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), B, H, L, hd, float(p), _p(seed), site, b_offset, _p(Om), d, _p(Oc), d,
-                                          _p(LSE), _stream()), "klattn_fwd")
-    return Om, Oc, LSE
+    return _stosa_attn_fwd("klattn_mfma_fwd", "klattn_fwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, site, b_offset, prec)
 
 
 def klattn_bwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p=0.0, seed=None, site=0, b_offset=0, out=None, prec=None):
     """As wattn_bwd: out = optional (dQm, dQc, dKm, dKc, dVm, dVc) views sharing one row stride (overwritten); prec as klattn_fwd
     (use the same value)."""
-    d = Qm.shape[1]
-    hd = d // H
-    outs = [torch.empty(B * L, d, device=Qm.device, dtype=torch.float32) for _ in range(6)] if out is None else list(out)
-    ldd = _ld(outs[0])
-    assert all(_ld(o) == ldd for o in outs)
-    if prec is not None:
-        rc = _lib.load().adt_klattn_mfma_bwd(int(prec), _p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc),
-                                             _p(_f32(Vm)), _ld(Vm), _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), _p(Om), _ld(Om), _p(Oc), _ld(Oc), _p(LSE),
-                                             _p(_f32(dOm)), _ld(dOm), _p(_f32(dOc)), _ld(dOc), B, H, L, hd, float(p), _p(seed), site, b_offset,
-                                             *[_p(o) for o in outs], ldd, _stream())
-        if rc != 1:
-            _lib.check(rc, "klattn_mfma_bwd")
-            return outs
-    _lib.check(_lib.load().adt_klattn_bwd(_p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc), _p(_f32(Vm)), _ld(Vm),
-                                          _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), _p(Om), _ld(Om), _p(Oc), _ld(Oc), _p(LSE), _p(_f32(dOm)), _ld(dOm),
-                                          _p(_f32(dOc)), _ld(dOc), B, H, L, hd, float(p), _p(seed), site, b_offset, *[_p(o) for o in outs], ldd, _stream()),
-               "klattn_bwd")
-    return outs
+    return _stosa_attn_bwd("klattn_mfma_bwd", "klattn_bwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site, b_offset, out, prec)
 
 
 def kldist_bpr(Sm, Sc, Em, Ec, pos, neg, pvn_weight, inv_count, dEm, dEc, loss3):
