@@ -117,6 +117,8 @@ SIGNATURES = {
     "adt_dense_workspace": (_I, [_P, _L]),
     "adt_dense_gradsrc": (_I, [_P, _I, _I, _I, _P, _F, _P, _U, _U, _I, _P, _I, _P, _I, _P, _P]),
     "adt_topk_masked": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "adt_full_rank_ws_bytes": (_L, [_I, _I, _I, _I]),
+    "adt_full_rank": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P]),
     "adt_item_sort_supported": (_I, [_I]),
     "adt_item_sort_work_ints": (_L, [_I, _I, _I]),
     "adt_item_sort": (_I, [_P, _I, _I, _I, _P, _P, _P, _U, _P, _P]),

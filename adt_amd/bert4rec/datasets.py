@@ -137,8 +137,12 @@ class BertEvalDataset:
         """dataset.py:201-215."""
         answer = [(self.user_val if self.mode == "val" else self.user_test)[user][0]]
         cand = answer + self.sampler.get_negative_samples(user, mode=self.mode)
+        return self.sequence(user), cand
+
+    def sequence(self, user):
+        """The left-padded history with the [MASK] token appended, as fed to the model."""
         seq = (list(self.user_train[user]) + [self.mask_token])[-self.maxlen:]
-        return [0] * (self.maxlen - len(seq)) + seq, cand
+        return [0] * (self.maxlen - len(seq)) + seq
 
     def __len__(self):
         return len(self.users)

@@ -52,6 +52,8 @@ def parse_args(argv=None):
     p.add_argument("--override", default=None, help="JSON applied after the template")
     p.add_argument("--precision", default="bf16", choices=["bf16", "f32"])
     p.add_argument("--use_graph", type=lambda s: str(s).lower() in ("1", "true", "yes"), default=True)
+    p.add_argument("--eval_full", type=lambda s: str(s).lower() in ("1", "true", "yes"), default=False,
+                   help="also rank the held-out item against the whole catalogue at every evaluation")
     return p.parse_args(argv)
 
 
@@ -116,6 +118,13 @@ def main(argv=None):
             for k in (5, 10) if rank == 0 else ():
                 print("epoch: %d, time: %f, valid (NDCG@%d: %.4f, HR@%d: %.4f, AUC: %s), test (NDCG@%d: %.4f, HR@%d: %.4f, AUC: %s)"
                       % (epoch + 1, T, k, t_valid[0][k], k, t_valid[1][k], auc_valid, k, t_test[0][k], k, t_test[1][k], auc_test))
+            if args.eval_full:     # the held-out item against ALL unseen items (adt_full_rank), beside the sampled-negative metrics
+                from ..sasrec.utils import evaluate_full
+                f_test, _ = evaluate_full(model, test_ds, "test", (5, 10), args.eval_batch_size, process_group=pg)
+                f_valid, _ = evaluate_full(model, val_ds, "val", (5, 10), args.eval_batch_size, process_group=pg)
+                for k in (5, 10) if rank == 0 else ():
+                    print("epoch: %d, full catalogue: valid (NDCG@%d: %.4f, HR@%d: %.4f), test (NDCG@%d: %.4f, HR@%d: %.4f)"
+                          % (epoch + 1, k, f_valid[0][k], k, f_valid[1][k], k, f_test[0][k], k, f_test[1][k]))
             loss = float(trainer.loss())      # a collective under data parallelism: every rank calls it
             if rank == 0:
                 print(json.dumps({"epoch": epoch + 1, "train_seconds": T, "sequences_per_sec": nseq / max(T, 1e-9), "loss": loss,

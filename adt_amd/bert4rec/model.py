@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from .. import _lib, custom_ops, ops
+from ..fullrank import FullRankMixin
 from ..wide import Act, FlatModule, Tape, give
 
 LN_EPS = 1e-5
@@ -76,7 +77,7 @@ def param_table(item_num, maxlen, d, H, nl, inner, type_vocab, vocab=None, block
     return t
 
 
-class BertModel(FlatModule):
+class BertModel(FullRankMixin, FlatModule):
     def __init__(self, usernum, itemnum, args, vocab=None, inner_units=None, block=0):
         super().__init__()
         self.usernum, self.itemnum = usernum, itemnum
@@ -280,6 +281,17 @@ class BertModel(FlatModule):
         logits, rank = ops.score_rank_bias(h.t, self.hidden_units, self.P("item_emb.word_emb.weight"), self.P("mask_bias"), cand, B, cand.shape[1],
                                            want_rank)
         return (logits, rank) if want_rank else logits
+
+    @torch.no_grad()
+    def _full_rank_operands(self, seqs):
+        """rank_full / recommend (adt_amd/fullrank.py) at the last position (the appended [MASK] token): the catalogue is items
+        1..itemnum; the [MASK] row and the other rows of the 100-row vocabulary tail are never scored."""
+        src = self.ids(seqs)
+        B, L = src.shape
+        tp = Tape(self, self.prec, False)
+        enc, _, _ = self._encode(tp, src.view(-1), B)
+        h = self._head(tp, Act(ops.gather_rows(enc.t, torch.arange(L - 1, B * L, L, device=self.dev, dtype=torch.int32))))
+        return h.t, self.P("item_emb.word_emb.weight"), self.itemnum, self.P("mask_bias")
 
     # ------------------------------------------------------------------------------------------------------------------
     def stage(self, src, dec, labels, n_valid_global=None):

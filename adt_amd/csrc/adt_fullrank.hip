@@ -1,0 +1,69 @@
+// C ABI (include/adt_hip.h, "full-catalogue ranking"): launch wrappers of adt_fullrank.cuh.  Host code only enqueues work on the
+// caller's stream.
+#include "adt_host.h"
+
+#include "adt_fullrank.cuh"
+
+using namespace adt;
+
+// The split count and the items per split, from the shape alone.  Automatic: about two workgroups per CU (512) over the tiles of 16
+// users, every split at least two chunks long, at most 64 splits.  The range per split is a whole number of chunks, and splits that
+// would be empty are dropped, so S <= the request.
+static int fr_plan(int B, int n_items, int splits, int* S_out, int* per_out) {
+  const int tiles = (B + 15) / 16, total = n_items + 1;
+  int S = splits;
+  if (S <= 0) {
+    S = (512 + tiles - 1) / tiles;
+    const int most = total / (2 * FR_CH);
+    if (S > most) S = most;
+    if (S > 64) S = 64;
+    if (S < 1) S = 1;
+  }
+  int per = ((total + S - 1) / S + FR_CH - 1) / FR_CH * FR_CH;
+  S = (total + per - 1) / per;
+  *S_out = S;
+  *per_out = per;
+  return 0;
+}
+
+static int64_t fr_ws_bytes(int B, int S, int K) { return (int64_t)B * S * (8 + 8 * (int64_t)K); }
+
+extern "C" {
+
+int64_t adt_full_rank_ws_bytes(int B, int n_items, int K, int splits) {
+  if (B < 1 || n_items < 1 || K < 0 || K > FR_KMAX || splits < 0 || splits > 1024) return 0;
+  int S, per;
+  fr_plan(B, n_items, splits, &S, &per);
+  return fr_ws_bytes(B, S, K);
+}
+
+int adt_full_rank(const float* F, int ldf, const float* E, int lde, const float* bias, int B, int d, int n_items, const int32_t* target,
+                  const int32_t* indptr, const int32_t* indices, int K, int splits, void* ws, int64_t ws_bytes, int32_t* rank,
+                  int32_t* n_elig, int32_t* top_idx, float* top_val, void* stream) {
+  if (K < 0 || K > FR_KMAX) return adt_set_error("full_rank: K=%d outside 0..%d", K, FR_KMAX);
+  if (d < 4 || (d % 4)) return adt_set_error("full_rank: d=%d must be a positive multiple of 4", d);
+  if (lde < d || ldf < d) return adt_set_error("full_rank: lde=%d, ldf=%d must be >= d=%d", lde, ldf, d);
+  if (n_items < 1) return adt_set_error("full_rank: n_items=%d < 1", n_items);
+  if ((lde % 4) || (ldf % 4) || !adt_aligned16(F) || !adt_aligned16(E)) return adt_set_error("full_rank: F and E must be 16-byte aligned with ld %% 4 == 0");
+  if ((indptr == nullptr) != (indices == nullptr)) return adt_set_error("full_rank: indptr and indices go together");
+  if (splits < 0 || splits > 1024) return adt_set_error("full_rank: splits=%d outside 0..1024", splits);
+  if (B <= 0) return 0;
+  if (!rank || !n_elig || (K > 0 && (!top_idx || !top_val))) return adt_set_error("full_rank: missing output");
+  const size_t smem = full_rank_lds_bytes(d);
+  if (smem > ADT_LDS_MAX) return adt_set_error("full_rank: d=%d needs %zu B of LDS (> 160 KB)", d, smem);
+  FullRankArgs a{};
+  fr_plan(B, n_items, splits, &a.S, &a.per);
+  if (!ws || ws_bytes < fr_ws_bytes(B, a.S, K)) return adt_set_error("full_rank: workspace of %lld B, need %lld (adt_full_rank_ws_bytes)", (long long)ws_bytes, (long long)fr_ws_bytes(B, a.S, K));
+  a.F = F; a.ldf = ldf; a.E = E; a.lde = lde; a.bias = bias; a.B = B; a.d = d; a.n_items = n_items;
+  a.target = target; a.indptr = indptr; a.indices = indices; a.K = K;
+  a.ws_cnt = static_cast<int32_t*>(ws);
+  a.ws_val = reinterpret_cast<float*>(a.ws_cnt + (size_t)B * a.S * 2);
+  a.ws_idx = reinterpret_cast<int32_t*>(a.ws_val + (size_t)B * a.S * K);
+  a.rank = rank; a.n_elig = n_elig; a.top_idx = top_idx; a.top_val = top_val;
+  static AdtLdsOptIn optin;      // smem follows d: the high-water mark in optin follows it
+  if (adt_launch_lds1((const void*)k_full_rank, dim3((B + 15) / 16, a.S), dim3(FR_NTH), smem, a, (hipStream_t)stream, "full_rank", optin)) return -1;
+  hipLaunchKernelGGL(k_full_rank_merge, dim3((B + FR_NW - 1) / FR_NW), dim3(FR_NTH), 0, (hipStream_t)stream, a);
+  return adt_check_launch("full_rank(merge)");
+}
+
+}  // extern "C"

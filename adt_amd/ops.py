@@ -584,3 +584,67 @@ def lane_map(padded, compact, index, scatter):
     """compact[i] = padded[index[i]] (scatter False) or padded[index[i]] = compact[i] (scatter True)."""
     assert padded.dtype == torch.float32 and compact.dtype == torch.float32 and compact.is_contiguous() and compact.numel() == index.numel()
     _lib.check(_lib.load().adt_lane_map(_p(padded), _p(compact), _p(_i32(index)), index.numel(), int(bool(scatter)), _stream()), "lane_map")
+
+
+# ---- full-catalogue ranking (include/adt_hip.h: adt_full_rank; adt_amd/csrc/adt_fullrank.cuh) ---------------------------------------------
+def seen_csr_host(seen, rows):
+    """The seen items of `rows` users as int32 CSR (indptr (rows + 1,), indices) numpy arrays.  `seen`: a scipy sparse matrix (its stored
+    entries are the seen items), a dense (rows, n) 0/1 array, an (indptr, indices) pair, or None -> (None, None); also (None, None) when nothing is stored."""
+    import numpy as np
+    if seen is None:
+        return None, None
+    if isinstance(seen, tuple):
+        ip, ix = seen
+    elif hasattr(seen, "tocsr"):
+        csr = seen.tocsr()
+        ip, ix = csr.indptr, csr.indices
+    else:
+        r, cols = np.nonzero(np.asarray(seen))
+        ip = np.zeros(rows + 1, np.int64)
+        np.cumsum(np.bincount(r, minlength=rows), out=ip[1:])
+        ix = cols
+    if len(ip) < rows + 1:
+        raise ValueError("seen has %d rows, the batch %d" % (len(ip) - 1, rows))
+    if len(ix) == 0:
+        return None, None
+    return np.ascontiguousarray(ip, dtype=np.int32), np.ascontiguousarray(ix, dtype=np.int32)
+
+
+def seen_csr(seen, rows, device):
+    """seen_csr_host on the device: (indptr, indices) int32 tensors, or (None, None)."""
+    ip, ix = seen_csr_host(seen, rows)
+    if ip is None:
+        return None, None
+    return torch.from_numpy(ip).to(device), torch.from_numpy(ix).to(device)
+
+
+def full_rank(F, ldf, E, n_items, target=None, bias=None, indptr=None, indices=None, k=0, splits=0):
+    """Exact fp32 scores F[b] . E[j] (+ bias[j]) of every eligible item 1 <= j <= n_items not in the user's CSR seen list, never
+    materialised: returns (rank (B,) int32 of target[b] among the eligible items, -1 without a target; n_elig (B,) int32 eligible items
+    other than the target; top_idx (B, k) int32 and top_val (B, k) of the k best, score descending, ties to the smaller id, -1 / -inf
+    tail; both None when k = 0).  F: B rows of width E.shape[1] at row stride ldf (any view whose first element is row 0)."""
+    # F is either the (B, d) view itself or a longer buffer whose rows sit ldf apart: then the targets / the CSR give the batch
+    if F.dim() == 2 and F.stride(0) == ldf:
+        B = F.shape[0]
+    elif target is not None:
+        B = target.numel()
+    elif indptr is not None:
+        B = indptr.numel() - 1
+    else:
+        raise _lib.AdtError("full_rank: the batch size is unknown: pass F as the (B, d) view with row stride ldf, or a target / indptr")
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous() or bias.numel() < n_items + 1):
+        raise _lib.AdtError("full_rank: bias must be contiguous fp32 with at least n_items + 1 = %d entries" % (n_items + 1))
+    if E.shape[0] < n_items + 1:
+        raise _lib.AdtError("full_rank: the item table has %d rows, n_items + 1 = %d are read" % (E.shape[0], n_items + 1))
+    d, lde = E.shape[1], E.stride(0)
+    dev = E.device
+    lib = _lib.load()
+    ws = torch.empty(max(int(lib.adt_full_rank_ws_bytes(B, int(n_items), int(k), int(splits))), 16), device=dev, dtype=torch.uint8)
+    rank = torch.empty(B, device=dev, dtype=torch.int32)
+    n_elig = torch.empty(B, device=dev, dtype=torch.int32)
+    top_idx = torch.empty(B, k, device=dev, dtype=torch.int32) if k > 0 else None
+    top_val = torch.empty(B, k, device=dev, dtype=torch.float32) if k > 0 else None
+    _lib.check(lib.adt_full_rank(_p(_f32(F)), int(ldf), _p(_f32(E)), lde, _p(bias), B, d, int(n_items), _p(None if target is None else _i32(target)),
+                                 _p(None if indptr is None else _i32(indptr)), _p(None if indices is None else _i32(indices)), int(k), int(splits),
+                                 _p(ws), ws.numel(), _p(rank), _p(n_elig), _p(top_idx), _p(top_val), _stream()), "full_rank")
+    return rank, n_elig, top_idx, top_val

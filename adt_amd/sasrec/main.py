@@ -62,6 +62,7 @@ def parse_args(argv=None):
     p.add_argument("--override", default=None, help="JSON dict applied AFTER the template (e.g. '{\"hidden_units\": 64}')")
     p.add_argument("--frozen_eval", default=True, type=str2bool, help="draw evaluation negatives once (seed 23)")
     p.add_argument("--use_graph", default=True, type=str2bool)
+    p.add_argument("--eval_full", default=False, type=str2bool, help="also rank the held-out item against the whole catalogue at every evaluation")
     args = p.parse_args(argv)
     if not args.no_template:
         args = U.set_template(args)          # sasrec/main.py:50: the template silently overrides the CLI
@@ -195,6 +196,12 @@ def main(argv=None):
             model.eval()
             t_test, auc_test = U.evaluate_loader(model, test_ds.batches(args.eval_batch_size), args, "test", ks, process_group=pg)
             t_valid, auc_valid = U.evaluate_loader(model, val_ds.batches(args.eval_batch_size), args, "val", ks, process_group=pg)
+            if args.eval_full:     # the held-out item against ALL unseen items (adt_full_rank), beside the sampled-negative metrics
+                f_test, _ = U.evaluate_full(model, test_ds, "test", ks, args.eval_batch_size, process_group=pg)
+                f_valid, _ = U.evaluate_full(model, val_ds, "val", ks, args.eval_batch_size, process_group=pg)
+                for k in ks if rank == 0 else ():
+                    print("epoch: %d, full catalogue: valid (NDCG@%d: %.4f, HR@%d: %.4f), test (NDCG@%d: %.4f, HR@%d: %.4f)"
+                          % (epoch + 1, k, f_valid[0][k], k, f_valid[1][k], k, f_test[0][k], k, f_test[1][k]))
             model.train()
             # trainer.loss() sum-reduces the per-rank loss slots when world > 1: EVERY rank calls it (a collective issued by rank 0
             # alone would pair with the other ranks' next gradient all-reduce)

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..fullrank import FullRankMixin
 
 # slot order of adt_sasrec_param_layout (include/adt_hip.h)
 _ENC_SLOTS = ["attention_layernorm.weight", "attention_layernorm.bias", "attention_layer.in_proj_weight",
@@ -71,7 +72,7 @@ def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
-class SASRecADT(torch.nn.Module):
+class SASRecADT(FullRankMixin, torch.nn.Module):
     def __init__(self, user_num, item_num, args):
         super().__init__()
         self.lib = _lib.load()   # raises when the HIP library is missing: no fallback
@@ -274,6 +275,20 @@ class SASRecADT(torch.nn.Module):
         _lib.check(self.lib.adt_sasrec_predict(ctypes.byref(self.cfg), _ptr(self.flat), _ptr(self.workspace(B)), _ptr(seq), _ptr(cand),
                                                B, C, _ptr(logits), _ptr(rank), self._stream()), "sasrec_predict")
         return logits, rank
+
+    @torch.no_grad()
+    def _full_rank_operands(self, log_seqs):
+        """rank_full / recommend (adt_amd/fullrank.py).  The executor has no encoder-only entry point: adt_sasrec_predict runs the
+        encoder and leaves the fp32 log_feats (B, L, d) at adt_sasrec_ws_offset(ADT_WS_F) -- the slot the C ABI names for them and the
+        rows adt_sasrec_predict itself scores from -- so the encoder runs through it with ONE throw-away candidate column (a B-element
+        score kernel) and the last position's rows are read from that slot."""
+        seq = self._ids(log_seqs)
+        B, L = seq.shape
+        d = self.hidden_units
+        self.predict_rank(seq, torch.zeros(B, 1, device=self.dev, dtype=torch.int32), want_rank=False)
+        F = self.ws_view(B, WS_F, 0, B * L * d).view(B, L * d)[:, (L - 1) * d:]
+        off, n, shape = self._views["item_emb.weight"]
+        return F, self.flat[off:off + n].view(shape), self.item_num, None
 
 
 class _SasrecFn(torch.autograd.Function):

@@ -12,6 +12,7 @@ import torch
 
 from .. import _lib, custom_ops, ops
 from ..dp import GradBuckets, reduce_sum, capture
+from ..fullrank import FullRankMixin
 from ..wide import Act, FlatModule, Tape, give, padded_layout
 from .model import REF_ORDER, param_table
 
@@ -40,7 +41,7 @@ def n_replicas(table_floats):
     return int(max(1, min(NREP_MAX, REP_BUDGET // (4 * int(table_floats)))))
 
 
-class SASRecADTWide(FlatModule):
+class SASRecADTWide(FullRankMixin, FlatModule):
     def __init__(self, user_num, item_num, args):
         super().__init__()
         self.user_num, self.item_num = user_num, item_num
@@ -254,15 +255,31 @@ class SASRecADTWide(FlatModule):
         return custom_ops.param_grads(self, lambda n: "pos_ffn_layernorm" in n or (H == 1 and ".sparse." in n))
 
     @torch.no_grad()
-    def predict_rank(self, log_seqs, item_indices, want_rank=True):
-        seq = self.ids(log_seqs)
-        B, L = seq.shape
+    def _final_feats(self, seq):
+        """Encoder in eval mode: the (B * L, dp) feature rows."""
+        B = seq.shape[0]
         was = self.training
         self.eval()
         self.push()
         tp = Tape(self, self.prec, False)
         feats, _, _ = self._encode(tp, seq.view(-1), B)
         self.train(was)
+        return feats
+
+    @torch.no_grad()
+    def _full_rank_operands(self, log_seqs):
+        """rank_full / recommend (adt_amd/fullrank.py): padded widths score over the dp columns as laid out (zero pad lanes)."""
+        seq = self.ids(log_seqs)
+        B, L = seq.shape
+        d = self.dp
+        F = self._final_feats(seq).t.view(B, L * d)[:, (L - 1) * d:]
+        return F, self.P("item_emb.weight"), self.item_num, None
+
+    @torch.no_grad()
+    def predict_rank(self, log_seqs, item_indices, want_rank=True):
+        seq = self.ids(log_seqs)
+        B, L = seq.shape
+        feats = self._final_feats(seq)
         d = self.dp
         cand = None if item_indices is None else self.ids(item_indices)
         C = self.item_num + 1 if cand is None else cand.shape[1]

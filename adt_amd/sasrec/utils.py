@@ -256,7 +256,8 @@ class EvalDataset:
         first = self.user_val[user][0] if self.mode == "val" else self.user_test[user][0]
         return np.array([first] + self.negative_sampler.get_negative_samples(user, mode=self.mode, rng=rng), np.int32)
 
-    def sample_data(self, user, rng=np.random):
+    def sequence(self, user):
+        """The right-aligned history fed to the model: the training items, plus the validation item in test mode."""
         L = self.maxlen
         seq = np.zeros(L, np.int32)
         hist = list(self.user_train[user])
@@ -264,6 +265,10 @@ class EvalDataset:
             hist = hist + [self.user_val[user][0]]
         n = min(len(hist), L)
         seq[L - n:] = hist[-n:]
+        return seq
+
+    def sample_data(self, user, rng=np.random):
+        seq = self.sequence(user)
         item_idx = self._frozen[user] if self._frozen is not None else self._candidates(user, rng)
         label = np.zeros(len(item_idx), np.int64)
         label[0] = 1
@@ -348,3 +353,59 @@ def evaluate_loader(model, loader, args=None, mode="val", ks=(5, 10), process_gr
     if W == 1:
         return metrics_from_ranks(ranks, ncand, ks)
     return metrics_from_stats(reduce_rank_stats(rank_stats(ranks, ncand, ks), process_group), ks)
+
+
+# ---- full-catalogue evaluation (adt_full_rank: the rank of the held-out item among ALL unseen items) ----------------------------------
+def full_rank_stats(ranks, n_elig, ks=(5, 10)):
+    """rank_stats for full-catalogue ranks: [N, sum((n_elig - rank) / n_elig), then per k: hits, sum 1/log2(rank+2)] as float64, where
+    n_elig[u] is the number of items user u's target competes with (its AUC term is the share of them it beats or ties).  Additive, so
+    reduce_rank_stats / metrics_from_stats apply unchanged."""
+    ranks, n_elig = np.asarray(ranks, np.int64), np.asarray(n_elig, np.int64)
+    out = [float(len(ranks)), float(((n_elig - ranks) / np.maximum(n_elig, 1)).sum())]
+    for k in ks:
+        hit = ranks < k
+        out += [float(hit.sum()), float((1.0 / np.log2(ranks[hit] + 2.0)).sum())]
+    return np.array(out, np.float64)
+
+
+def eval_target(dataset, user):
+    return int((dataset.user_val if dataset.mode == "val" else dataset.user_test)[user][0])
+
+
+def eval_seen_csr(dataset, users):
+    """The seen items of `users` as int32 CSR (indptr, indices): the training items, plus the validation item in test mode."""
+    rows = []
+    for u in users:
+        items = list(dataset.user_train.get(u, []))
+        if dataset.mode == "test":
+            items = items + list(dataset.user_val.get(u, []))
+        rows.append(items)
+    indptr = np.zeros(len(rows) + 1, np.int32)
+    np.cumsum([len(r) for r in rows], out=indptr[1:])
+    indices = np.asarray([i for r in rows for i in r], np.int32)
+    return indptr, indices
+
+
+def evaluate_full(model, dataset, mode=None, ks=(5, 10), batch_size=512, process_group=None):
+    """((NDCG, HT), AUC) over the WHOLE catalogue: every evaluation user's held-out item (dataset.mode: "val" or "test"; `mode`, when
+    given, must agree) is ranked against all items the user has not seen, on the device (model.rank_full).  The sequences are the ones
+    dataset.sample_data feeds today (dataset.sequence).  With a process group, rank r scores batches r, r + W, ... and the additive
+    statistics are sum-reduced, as evaluate_loader does."""
+    if mode is not None and mode != dataset.mode:
+        raise ValueError("evaluate_full: mode %r, but the dataset was built for %r" % (mode, dataset.mode))
+    r, W = 0, 1
+    if process_group is not None:
+        import torch.distributed as dist
+        r, W = dist.get_rank(process_group), dist.get_world_size(process_group)
+    ranks, nel = [], []
+    for i, s in enumerate(range(0, len(dataset.users), batch_size)):
+        if i % W != r:
+            continue
+        users = dataset.users[s:s + batch_size]
+        seqs = np.stack([np.asarray(dataset.sequence(u), np.int32) for u in users])
+        rank, n_elig, _, _ = model.rank_full(seqs, [eval_target(dataset, u) for u in users], eval_seen_csr(dataset, users))
+        ranks.append(rank.cpu().numpy())
+        nel.append(n_elig.cpu().numpy())
+    ranks = np.concatenate(ranks) if ranks else np.zeros(0, np.int64)
+    nel = np.concatenate(nel) if nel else np.zeros(0, np.int64)
+    return metrics_from_stats(reduce_rank_stats(full_rank_stats(ranks, nel, ks), process_group), ks)

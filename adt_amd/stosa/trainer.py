@@ -114,26 +114,13 @@ class FusedStosaTrainer:
         items by ascending distance with the seen items pushed to 1e24 and keep `topk`, all on the device (model.predict_full: adt_wdist_full,
         or adt_kldist_full for distance_metric 'kl', whose scores depend on each batch's rows being the eval batch -- pass the reference's
         eval batches -- then adt_topk_masked); only the (B, topk) ids come back.  `seen` is the users' rows of the train/valid rating matrix as a scipy
-        CSR matrix, a dense (B, item_size) 0/1 array, or None.  Returns (pred_list (N, topk), answers (N, A)) for
+        CSR matrix, a dense (B, item_size) 0/1 array, an int32 (indptr, indices) pair, or None (ops.seen_csr).  Returns (pred_list (N, topk), answers (N, A)) for
         get_full_sort_score."""
         preds, answers = [], []
         dev = self.model.dev
         for input_ids, seen, ans in batches:
             dist = self.model.predict_full(input_ids)
-            indptr = indices = None
-            if seen is not None:
-                if hasattr(seen, "tocsr"):
-                    csr = seen.tocsr()
-                    ip, ix = csr.indptr, csr.indices
-                else:
-                    rows, cols = np.nonzero(np.asarray(seen))
-                    ip = np.zeros(dist.shape[0] + 1, np.int64)
-                    np.cumsum(np.bincount(rows, minlength=dist.shape[0]), out=ip[1:])
-                    ix = cols
-                indptr = torch.from_numpy(np.ascontiguousarray(ip, dtype=np.int32)).to(dev)
-                indices = torch.from_numpy(np.ascontiguousarray(ix, dtype=np.int32)).to(dev)
-                if indices.numel() == 0:
-                    indptr = indices = None
+            indptr, indices = ops.seen_csr(seen, dist.shape[0], dev)
             preds.append(ops.topk_masked(dist, topk, indptr, indices).cpu().numpy().astype(np.int64))
             answers.append(np.asarray(ans))
         return np.concatenate(preds), np.concatenate(answers)

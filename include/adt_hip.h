@@ -314,6 +314,24 @@ int adt_kldist_full(const float* Sm, const float* Sc, int lds, const float* Em, 
 int adt_topk_masked(float* dist, int ld, int B, int N, const int32_t* indptr, const int32_t* indices, int k, int32_t* out_idx,
                     float* out_val, void* stream);
 
+/* ---- full-catalogue ranking for the dot-product backbones (adt_fullrank.cuh; sasrec/model.py:83-97 predict(full=True) without the
+ * (B, V) logit matrix).  s[b][j] = F[b] . E[j] (+ bias[j]) in exact fp32 (v_mfma_f32_16x16x4_f32) over the d columns (a multiple of 4;
+ * zero pad lanes of a padded table change nothing).  Item j is ELIGIBLE for user b when 1 <= j <= n_items and j is not in the user's
+ * seen list indices[indptr[b] .. indptr[b + 1]) (CSR, both NULL = nothing seen; ids outside 1..n_items and duplicates are ignored);
+ * target[b] stays eligible even when listed.  E has at least n_items + 1 rows (row stride lde >= d; rows above n_items are never
+ * scored), bias (or NULL) at least n_items + 1 entries.
+ *   rank[b]    = #{eligible j != target[b] : s[b][j] > s[b][target[b]]} (strict, as adt_score_rank); -1 when target is NULL or
+ *                target[b] is not in 1..n_items.  The target's score comes from the same tile code as every other score.
+ *   n_elig[b]  = #{eligible j != target[b]}
+ *   top_idx / top_val (B, K): the K best eligible items (the target included), score descending, ties to the smaller id; -1 / -inf
+ *                where fewer than K are eligible.  K = 0 .. 128; 0 skips the selection (top_idx / top_val may be NULL).
+ * splits: item ranges the catalogue is cut into (one workgroup per 16 users and range), 0 = chosen from B and n_items; no output
+ * depends on it.  ws: adt_full_rank_ws_bytes(B, n_items, K, splits) bytes of scratch (0 for arguments adt_full_rank rejects). */
+int64_t adt_full_rank_ws_bytes(int B, int n_items, int K, int splits);
+int adt_full_rank(const float* F, int ldf, const float* E, int lde, const float* bias, int B, int d, int n_items,
+                  const int32_t* target, const int32_t* indptr, const int32_t* indices, int K, int splits, void* ws,
+                  int64_t ws_bytes, int32_t* rank, int32_t* n_elig, int32_t* top_idx, float* top_val, void* stream);
+
 /* ==== model-level executor: SASRecADT (sasrec/model.py:8-97) + loop body (sasrec/main.py:146-173) ====== */
 typedef struct adt_sasrec_cfg {
   int32_t item_num;     /* V; item table has V+1 rows                      */
