@@ -20,8 +20,8 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..supersearch import candidate_features, cand_to_block, get_shared
-from ..wide import Act, Tape
+from ..supersearch import SupernetTrainer, candidate_features, get_shared
+from ..wide import Act, Tape, loss_norms
 from .model import SITE_EMB_DEC, SITE_EMB_SEQ, BertModel, dec_sites, enc_sites
 
 CAND_SITE = 4096
@@ -138,53 +138,24 @@ class SuperBertModel(BertModel):
         return rank.view(P, B)
 
 
-class SuperBertTrainer:
-    """One warm-up optimisation step of the supernet (bert4rec/evolution.py:266-296) with torch.optim.AdamW's per-parameter bookkeeping."""
+class SuperBertTrainer(SupernetTrainer):
+    """SearcherEvolution._train_warmup's optimiser step (bert4rec/evolution.py:266-296) with torch.optim.AdamW's bookkeeping (decoupled decay)."""
+
+    _adam_range = staticmethod(ops.adamw_range)
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, clip=5.0, seed=2022):
-        self.model = model
-        self.lr, self.betas, self.eps, self.wd, self.clip = lr, betas, eps, weight_decay, clip
-        dev = model.dev
-        self.m, self.v = torch.zeros_like(model.flat), torch.zeros_like(model.flat)
-        self.gn2 = torch.zeros(64, device=dev, dtype=torch.float32)
-        self.loss_slots = torch.zeros(1 + 2 * model.num_layers, 64, device=dev, dtype=torch.float32)
-        self.steps = {}       # (lo, hi) -> AdamW step count of that range
-        self.rec_weights = [0.0] * model.num_layers
-        self.ind_weights = [0.0] * model.num_layers
-        model.set_seed(seed * 1000003 + 12345)
+        super().__init__(model, 1 + 2 * model.num_layers, lr, betas, eps, weight_decay, clip, seed)
 
-    def set_choice(self, cand):
-        """SearcherEvolution._set_choice (bert4rec/evolution.py:119-133)."""
+    def _stage(self, src, dec, labels):
         m = self.model
-        block, rw, iw = cand_to_block(m.rec_choice, m.ind_choice, cand)
-        self.rec_weights[:], self.ind_weights[:] = rw, iw
-        m.set_choice(block)
-
-    def step(self, src, dec, labels):
-        m = self.model
-        m.train()
         st = m.stage(src, dec, labels)
-        T = st["B"] * m.maxlen
-        norms = torch.tensor([0.0, float(T * m.hidden_units), float(T * m.num_heads)], device=m.dev, dtype=torch.float32)
-        m._seed.add_(-1640531535)
-        self.loss_slots.zero_()
-        m.flat_grad.zero_()
-        nl = m.num_layers
-        lam2 = [self.ind_weights[nl - 1]] * nl        # `ind_weights[i]` with the reconstruction loop's stale i (evolution.py:291)
-        m.loss_forward_backward(st, self.rec_weights, lam2, norms, self.loss_slots)
-        ops.grad_sumsq(m.flat_grad, self.gn2)
-        for lo, hi in m.shared_ranges():
-            t = self.steps.get((lo, hi), 0) + 1
-            self.steps[(lo, hi)] = t
-            ops.adamw_range(m.flat[lo:hi], m.flat_grad[lo:hi], self.m[lo:hi], self.v[lo:hi], self.wd, self.clip, self.lr, self.betas[0],
-                            self.betas[1], self.eps, t, self.gn2)
+        return st, loss_norms(m, st["B"] * m.maxlen)
 
-    def loss(self):
+    def _ind_lambdas(self):
+        nl = self.model.num_layers
+        return [self.ind_weights[nl - 1]] * nl        # `ind_weights[i]` with the reconstruction loop's stale i (evolution.py:291)
+
+    def _loss_w(self):
         m = self.model
         nl = m.num_layers
-        s = self.loss_slots.sum(1)
-        w = [1.0] + list(self.rec_weights) + [self.ind_weights[nl - 1] if m.num_heads > 1 else 0.0] * nl
-        return (s * torch.tensor(w, device=m.dev, dtype=torch.float32)).sum()
-
-    def grad_norm(self):
-        return self.gn2.sum().sqrt()
+        return [1.0] + list(self.rec_weights) + [self.ind_weights[nl - 1] if m.num_heads > 1 else 0.0] * nl

@@ -11,9 +11,8 @@ import numpy as np
 import torch
 
 from .. import _lib, custom_ops, ops
-from ..dp import GradBuckets, reduce_sum, capture
 from ..fullrank import FullRankMixin
-from ..wide import Act, FlatModule, Tape, give, padded_layout
+from ..wide import Act, FlatModule, Tape, TapeTrainer, give, loss_norms, padded_layout
 from .model import REF_ORDER, param_table
 
 LN_EPS = 1e-8
@@ -39,6 +38,25 @@ def n_replicas(table_floats):
     the gradient, no replica traffic at all) from 32 MB up -- Amazon-Beauty's 54,542 x 256 table is 56 MB, and its ids are spread
     over 16x more rows, so the same-address atomic chains the replicas exist to break are short anyway."""
     return int(max(1, min(NREP_MAX, REP_BUDGET // (4 * int(table_floats)))))
+
+
+def seed_mse_nll(enc_in, dec_outs, recs, lambdas1, lambdas2, H, norms, loss_slots):
+    """Loss seeds of the reconstruction and independence terms, shared with the supernet's warm-up loss (sasrec/main.py:155-169,
+    sasrec/evolution.py:300-313): lambdas1[i] * MSE between encoder layer i's input and the decoder output that mirrors it, into loss slot
+    2 + i, and with more than one head lambdas2[stale i] * NLL of every layer's head classifier, into slot 2 + nl + l."""
+    nl = len(enc_in)
+    i = 0
+    for i in range(nl):
+        a, bq = enc_in[i], dec_outs[nl - 1 - i]
+        if a.g is None:
+            a.g = torch.zeros_like(a.t)
+        g_b = torch.empty_like(bq.t)
+        ops.mse_seed(a.t, bq.t, lambdas1[i], norms, a.g, True, g_b, loss_slots[2 + i])
+        give(bq, g_b)
+    if H > 1:
+        for l in range(nl):
+            recs[l].g = torch.empty_like(recs[l].t)
+            ops.nll_seed(recs[l].t, H, lambdas2[i], norms, recs[l].g, loss_slots[2 + nl + l])     # stale index (main.py:169, evolution.py:313)
 
 
 class SASRecADTWide(FullRankMixin, FlatModule):
@@ -294,7 +312,6 @@ class SASRecADTWide(FullRankMixin, FlatModule):
         flat_grad; the wd * ||E||_F term is added by adt_clip_adam.  ids: device int32 (seq, dec, pos, neg) (B, L)."""
         seq, dec, pos, neg = ids
         B, L = seq.shape
-        nl, H = self.num_layers, self.num_heads
         tp = Tape(self, self.prec, self.training, row_offset=b_offset * L, b_offset=b_offset)
         feats, enc_in, recs = self._encode(tp, seq.view(-1), B)
         dec_outs = self._decode(tp, dec.view(-1), feats, B)
@@ -313,58 +330,33 @@ class SASRecADTWide(FullRankMixin, FlatModule):
         give(feats, ops.logits_bwd_df(E, pos.view(-1), neg.view(-1), dpos, dneg))
         ops.item_scatter(pos.view(-1), feats.t, dpos, 1.0, 0.0, None, 0, 0, self._rep, self._nrep, self._rep_stride)
         ops.item_scatter(neg.view(-1), feats.t, dneg, 1.0, 0.0, None, 0, 0, self._rep, self._nrep, self._rep_stride)
-        i = 0
-        for i in range(nl):
-            a, bq = enc_in[i], dec_outs[nl - 1 - i]
-            if a.g is None:
-                a.g = torch.zeros_like(a.t)
-            g_b = torch.empty_like(bq.t)
-            ops.mse_seed(a.t, bq.t, lambdas1[i], norms, a.g, True, g_b, loss_slots[2 + i])
-            give(bq, g_b)
-        if H > 1:
-            for l in range(nl):
-                recs[l].g = torch.empty_like(recs[l].t)
-                ops.nll_seed(recs[l].t, H, lambdas2[i], norms, recs[l].g, loss_slots[2 + nl + l])     # stale index (main.py:169)
+        seed_mse_nll(enc_in, dec_outs, recs, lambdas1, lambdas2, self.num_heads, norms, loss_slots)
         tp.backward()
         if self._nrep > 1:
             ops.replica_reduce(gE, self._rep, self._nrep, self._rep_stride)
 
 
-class WideSasrecTrainer:
+class WideSasrecTrainer(TapeTrainer):
     def __init__(self, model, lambdas1, lambdas2, lr=1e-3, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.0, clip=5.0, process_group=None,
                  use_graph=False, seed=23):
-        self.model = model
         self.lambdas1, self.lambdas2 = [float(x) for x in lambdas1], [float(x) for x in lambdas2]
-        self.lr, self.betas, self.eps, self.wd, self.clip = lr, betas, eps, weight_decay, clip
-        self.pg = process_group
-        self.world = 1 if process_group is None else torch.distributed.get_world_size(process_group)
-        self.use_graph = use_graph       # data-parallel steps are captured too (RCCL collectives are graph nodes)
-        dev = model.dev
-        self._buckets = GradBuckets(model.flat_grad, model.offset_of("decoder.decoder_layers.0.layer_norm.weight"), process_group)
-        self.m, self.v = torch.zeros_like(model.flat), torch.zeros_like(model.flat)
-        self.scal = torch.zeros(192, device=dev, dtype=torch.float32)
         nl = model.num_layers
-        self.loss_slots = torch.zeros(2 + 2 * nl, 64, device=dev, dtype=torch.float32)
         w = [1.0, 1.0] + self.lambdas1 + [self.lambdas2[nl - 1] if model.num_heads > 1 else 0.0] * nl
-        self._loss_w = torch.tensor(w, device=dev, dtype=torch.float32)
-        model.set_seed(seed * 1000003 + 12345)
-        self._graph, self._st = None, None
-        self.nstep = 0
+        super().__init__(model, w, "decoder.decoder_layers.0.layer_norm.weight", lr, betas, eps, weight_decay, clip, process_group, use_graph)
+        model.seed_trainer(seed)
 
     def stage(self, seq, dec, pos, neg, norms=None):
         m = self.model
         ids = tuple(m.ids(a) for a in (seq, dec, pos, neg))
         B, L = ids[0].shape
         if norms is None:
-            norms = (float(np.count_nonzero(np.asarray(pos))), float(self.world * B * L * m.hidden_units), float(self.world * B * L * m.num_heads))
-        return {"B": B, "seq": ids[0], "dec": ids[1], "pos": ids[2], "neg": ids[3], "norms": torch.tensor(norms, device=m.dev, dtype=torch.float32)}
+            norms = loss_norms(m, B * L, np.count_nonzero(np.asarray(pos)), self.world)
+        else:
+            norms = torch.tensor(norms, device=m.dev, dtype=torch.float32)
+        return {"B": B, "seq": ids[0], "dec": ids[1], "pos": ids[2], "neg": ids[3], "norms": norms}
 
-    def _launch(self, b_offset):
-        m, st = self.model, self._st
-        m._seed.add_(-1640531535)
-        self.loss_slots.zero_()
-        m.flat_grad.zero_()
-        m.dp_hook = self._buckets.tail_ready if self._buckets.active else None
+    def _body(self, st, b_offset):
+        m = self.model
         m.push()        # padded widths: the reference-shaped parameters are the truth between steps (no-op otherwise)
         m.loss_forward_backward((st["seq"], st["dec"], st["pos"], st["neg"]), self.lambdas1, self.lambdas2, st["norms"], self.loss_slots, b_offset)
         self._buckets.finish()
@@ -373,32 +365,7 @@ class WideSasrecTrainer:
         m.pull()
 
     def step(self, seq, dec, pos, neg, norms=None, b_offset=0):
-        self.model.train()
-        self.nstep += 1
-        st = self.stage(seq, dec, pos, neg, norms)
-        if self._st is None or self._st["B"] != st["B"]:
-            self._st = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in st.items()}
-            self._graph = None
-        else:
-            for k, v in st.items():
-                if isinstance(v, torch.Tensor):
-                    self._st[k].copy_(v, non_blocking=True)
-        if not self.use_graph:
-            return self._launch(b_offset)
-        if self._graph is None:
-            self._launch(b_offset)
-            torch.cuda.synchronize()
-            self._graph = torch.cuda.CUDAGraph()
-            with capture(self._graph):
-                self._launch(b_offset)
-            return
-        self._graph.replay()
+        self.step_staged(self.stage(seq, dec, pos, neg, norms), b_offset)
 
     def loss(self):
-        slots = self.loss_slots.sum(1)
-        if self.world > 1:
-            slots = reduce_sum(slots, self.pg)
-        return (slots * self._loss_w).sum() + self.scal[3]
-
-    def grad_norm(self):
-        return self.scal[1].sqrt()
+        return super().loss() + self.scal[3]

@@ -19,9 +19,10 @@ import numpy as np
 import torch
 
 from .. import _lib, custom_ops, ops
-from ..supersearch import candidate_features, cand_to_block, get_position, get_shared, get_weight  # noqa: F401
-from ..wide import Act, FlatModule, Tape, give
+from ..supersearch import SupernetTrainer, candidate_features, cand_to_block, get_position, get_shared, get_weight  # noqa: F401
+from ..wide import Act, FlatModule, Tape, give, loss_norms
 from .model import REF_ORDER
+from .model_wide import seed_mse_nll
 
 LN_EPS = 1e-8
 SITE_EMB_SEQ, SITE_EMB_DEC = 1, 2
@@ -473,7 +474,6 @@ class SuperSASRecModel(FlatModule):
         pos, neg) (B, L); norms: device {n_bce, n_mse, n_nll}; loss_slots: (2 + 2*num_layers) x 64 {bce_pos, bce_neg, mse.., nll..}."""
         seq, dec, pos, neg = ids
         B, L = seq.shape
-        nl, H = self.num_layers, self.num_heads
         tp = Tape(self, self.prec, self.training, row_offset=b_offset * L, b_offset=b_offset)
         feats, enc_in, recs = self._encode(tp, seq.view(-1), B)
         dec_outs = self._decode(tp, dec.view(-1), feats, B)
@@ -481,76 +481,36 @@ class SuperSASRecModel(FlatModule):
         pl, nlg = ops.logits_fwd(feats.t, E, pos.view(-1), neg.view(-1))
         dpos, dneg = ops.bce_seed(pl, nlg, pos.view(-1), norms, loss_slots[0:2].view(-1))
         give(feats, ops.logits_bwd(feats.t, E, pos.view(-1), neg.view(-1), dpos, dneg, gE))
-        i = 0
-        for i in range(nl):
-            a, bq = enc_in[i], dec_outs[nl - 1 - i]
-            if a.g is None:
-                a.g = torch.zeros_like(a.t)
-            g_b = torch.empty_like(bq.t)
-            ops.mse_seed(a.t, bq.t, rec_w[i], norms, a.g, True, g_b, loss_slots[2 + i])
-            give(bq, g_b)
-        if H > 1:
-            for l in range(nl):
-                recs[l].g = torch.empty_like(recs[l].t)
-                ops.nll_seed(recs[l].t, H, ind_w[i], norms, recs[l].g, loss_slots[2 + nl + l])    # stale index i (evolution.py:313)
+        seed_mse_nll(enc_in, dec_outs, recs, rec_w, ind_w, self.num_heads, norms, loss_slots)
         tp.backward()
 
 
-class SuperTrainer:
-    """One warm-up optimisation step of the supernet with torch.optim.Adam's per-parameter bookkeeping: only the embeddings
-    and the candidate layers that were mixed in are clipped (global norm), decayed and stepped, each with its own step count."""
+class SuperTrainer(SupernetTrainer):
+    """SearcherEvolution._train_warmup's optimiser step (sasrec/evolution.py:286-316) with torch.optim.Adam's bookkeeping (coupled weight
+    decay): the embeddings and the candidate layers that were mixed in."""
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip=5.0, seed=2022):
-        self.model = model
-        self.lr, self.betas, self.eps, self.wd, self.clip = lr, betas, eps, weight_decay, clip
-        dev = model.dev
-        self.m, self.v = torch.zeros_like(model.flat), torch.zeros_like(model.flat)
-        self.gn2 = torch.zeros(64, device=dev, dtype=torch.float32)
-        self.loss_slots = torch.zeros(2 + 2 * model.num_layers, 64, device=dev, dtype=torch.float32)
-        self.steps = {}       # (lo, hi) -> Adam step count of that range
-        self._emb_range = (0, model._views["encoder.encoder_layers.0.0." + _ENC[0]][0])
-        self.rec_weights = [0.0] * model.num_layers
-        self.ind_weights = [0.0] * model.num_layers
-        model.set_seed(seed * 1000003 + 12345)
-
+    _adam_range = staticmethod(ops.adam_range)
     get_weight = staticmethod(get_weight)
 
-    def set_choice(self, cand):
-        """SearcherEvolution._set_choice (evolution.py:139-153): probabilities -> loss weights + the model's block choice."""
-        m = self.model
-        block, rw, iw = cand_to_block(m.rec_choice, m.ind_choice, cand)
-        self.rec_weights[:], self.ind_weights[:] = rw, iw
-        m.set_choice(block)
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip=5.0, seed=2022):
+        super().__init__(model, 2 + 2 * model.num_layers, lr, betas, eps, weight_decay, clip, seed)
+        self._emb_range = (0, model._views["encoder.encoder_layers.0.0." + _ENC[0]][0])
 
-    def step(self, seq, dec, pos, neg):
+    def _stage(self, seq, dec, pos, neg):
         m = self.model
-        m.train()
         ids = tuple(m.ids(a) for a in (seq, dec, pos, neg))
         B, L = ids[0].shape
-        T = B * L
-        n_bce = float(np.count_nonzero(np.asarray(pos)))
-        norms = torch.tensor([n_bce, float(T * m.hidden_units), float(T * m.num_heads)], device=m.dev, dtype=torch.float32)
-        m._seed.add_(-1640531535)
-        self.loss_slots.zero_()
-        m.flat_grad.zero_()
-        m.loss_forward_backward(ids, self.rec_weights, self.ind_weights, norms, self.loss_slots)
-        ops.grad_sumsq(m.flat_grad, self.gn2)
+        return ids, loss_norms(m, B * L, np.count_nonzero(np.asarray(pos)))
+
+    def _ranges(self):
+        m = self.model
         ranges = [self._emb_range]
         for depth, (idxs, _) in enumerate(m.shared):
             for idx in sorted(set(idxs)):
                 ranges += [m.layer_range("encoder", depth, idx), m.layer_range("decoder", depth, idx)]
-        for lo, hi in ranges:
-            t = self.steps.get((lo, hi), 0) + 1
-            self.steps[(lo, hi)] = t
-            ops.adam_range(m.flat[lo:hi], m.flat_grad[lo:hi], self.m[lo:hi], self.v[lo:hi], self.wd, self.clip, self.lr, self.betas[0],
-                           self.betas[1], self.eps, t, self.gn2)
+        return ranges
 
-    def loss(self):
+    def _loss_w(self):
         m = self.model
         nl = m.num_layers
-        s = self.loss_slots.sum(1)
-        w = [1.0, 1.0] + list(self.rec_weights) + [self.ind_weights[nl - 1] if m.num_heads > 1 else 0.0] * nl
-        return (s * torch.tensor(w, device=m.dev, dtype=torch.float32)).sum()
-
-    def grad_norm(self):
-        return self.gn2.sum().sqrt()
+        return [1.0, 1.0] + list(self.rec_weights) + [self.ind_weights[nl - 1] if m.num_heads > 1 else 0.0] * nl

@@ -17,8 +17,8 @@ import numpy as np
 import torch
 
 from .. import _lib, ops
-from ..supersearch import candidate_features, cand_to_block, get_shared
-from ..wide import Act, Tape
+from ..supersearch import SupernetTrainer, candidate_features, get_shared
+from ..wide import Act, Tape, loss_norms
 from .models import SITE_EMB, DisenDistSAModel, dec_sites, enc_sites
 
 CAND_SITE = 4096
@@ -111,55 +111,24 @@ class DisenDistSASupernet(DisenDistSAModel):
                               self.P("item_cov_embeddings.weight"), self.item_size)
 
 
-class SuperStosaTrainer:
-    """One warm-up optimisation step of the supernet (stosa/super_trainer.py:205-235) with torch.optim.Adam's per-parameter bookkeeping:
-    no gradient clipping, coupled weight decay, candidates that were not selected keep their moments and step counts."""
+class SuperStosaTrainer(SupernetTrainer):
+    """SuperDistSAModelTrainer.iteration's optimiser step (stosa/super_trainer.py:205-235) with torch.optim.Adam's bookkeeping (coupled
+    weight decay); the reference does not clip the gradient: clip = inf."""
+
+    _adam_range = staticmethod(ops.adam_range)
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, seed=42):
-        self.model = model
-        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
-        dev = model.dev
-        self.m, self.v = torch.zeros_like(model.flat), torch.zeros_like(model.flat)
-        self.gn2 = torch.zeros(64, device=dev, dtype=torch.float32)
-        nl = model.num_layers
-        self.loss_slots = torch.zeros(3 + 4 * nl, 64, device=dev, dtype=torch.float32)
-        self.steps = {}
-        self.rec_weights, self.ind_weights = [0.0] * nl, [0.0] * nl
-        model.set_seed(seed * 1000003 + 12345)
+        super().__init__(model, 3 + 4 * model.num_layers, lr, betas, eps, weight_decay, 1e30, seed)
 
-    def set_choice(self, cand):
-        """SearcherEvolution._set_choice (stosa/searcher.py:88-102)."""
+    def _stage(self, input_ids, dec_ids, pos_ids, neg_ids):
         m = self.model
-        block, rw, iw = cand_to_block(m.rec_choice, m.ind_choice, cand)
-        self.rec_weights[:], self.ind_weights[:] = rw, iw
-        m.set_choice(block)
-
-    def step(self, input_ids, dec_ids, pos_ids, neg_ids):
-        m = self.model
-        m.train()
         st = m.stage(input_ids, dec_ids, pos_ids, neg_ids)
-        T = st["B"] * m.maxlen
-        norms = torch.tensor([0.0, float(T * m.hidden_units), float(T * m.num_heads)], device=m.dev, dtype=torch.float32)
-        m._seed.add_(-1640531535)
-        self.loss_slots.zero_()
-        m.flat_grad.zero_()
-        m.loss_forward_backward(st, self.rec_weights, self.ind_weights, norms, self.loss_slots)
-        ops.grad_sumsq(m.flat_grad, self.gn2)
-        for lo, hi in m.shared_ranges():
-            t = self.steps.get((lo, hi), 0) + 1
-            self.steps[(lo, hi)] = t
-            ops.adam_range(m.flat[lo:hi], m.flat_grad[lo:hi], self.m[lo:hi], self.v[lo:hi], self.wd, 1e30, self.lr, self.betas[0], self.betas[1],
-                           self.eps, t, self.gn2)
+        return st, loss_norms(m, st["B"] * m.maxlen)
 
-    def loss(self):
-        nl = self.model.num_layers
-        s = self.loss_slots.sum(1)
+    def _loss_w(self):
         w = [1.0, 1.0, 0.0]
-        for l in range(nl):
+        for l in range(self.model.num_layers):
             w += [self.rec_weights[l]] * 2
-        for l in range(nl):
+        for l in range(self.model.num_layers):
             w += [self.ind_weights[l]] * 2
-        return (s * torch.tensor(w, device=self.model.dev, dtype=torch.float32)).sum()
-
-    def grad_norm(self):
-        return self.gn2.sum().sqrt()
+        return w

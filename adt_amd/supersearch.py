@@ -71,6 +71,60 @@ def cand_to_block(rec_choice, ind_choice, cand):
     return np.array(block), rec_w, ind_w
 
 
+class SupernetTrainer:
+    """One warm-up optimisation step of a supernet (SearcherEvolution._train_warmup) with torch.optim's per-parameter bookkeeping: only
+    the flat ranges that received a gradient -- the tensors outside the candidate layers and the candidates that were mixed in -- are
+    clipped (global norm), decayed and stepped, each with its own step count; the others keep their moments.  A subclass supplies
+    `_stage(*batch)` -> (what its model's loss_forward_backward takes, norms), `_ranges()`, `_adam_range` (ops.adam_range or
+    ops.adamw_range) and `_loss_w()`."""
+
+    def __init__(self, model, n_slots, lr, betas, eps, weight_decay, clip, seed):
+        self.model = model
+        self.lr, self.betas, self.eps, self.wd, self.clip = lr, betas, eps, weight_decay, clip
+        dev = model.dev
+        self.m, self.v = torch.zeros_like(model.flat), torch.zeros_like(model.flat)
+        self.gn2 = torch.zeros(64, device=dev, dtype=torch.float32)
+        self.loss_slots = torch.zeros(n_slots, 64, device=dev, dtype=torch.float32)
+        self.steps = {}       # (lo, hi) -> optimiser step count of that range
+        self.rec_weights = [0.0] * model.num_layers
+        self.ind_weights = [0.0] * model.num_layers
+        model.seed_trainer(seed)
+
+    def set_choice(self, cand):
+        """SearcherEvolution._set_choice: probabilities -> loss weights + the model's block choice."""
+        m = self.model
+        block, rw, iw = cand_to_block(m.rec_choice, m.ind_choice, cand)
+        self.rec_weights[:], self.ind_weights[:] = rw, iw
+        m.set_choice(block)
+
+    def _ranges(self):
+        return self.model.shared_ranges()
+
+    def _ind_lambdas(self):
+        return self.ind_weights
+
+    def step(self, *batch):
+        m = self.model
+        m.train()
+        staged, norms = self._stage(*batch)
+        m.advance_seed()
+        self.loss_slots.zero_()
+        m.flat_grad.zero_()
+        m.loss_forward_backward(staged, self.rec_weights, self._ind_lambdas(), norms, self.loss_slots)
+        ops.grad_sumsq(m.flat_grad, self.gn2)
+        for lo, hi in self._ranges():
+            t = self.steps.get((lo, hi), 0) + 1
+            self.steps[(lo, hi)] = t
+            self._adam_range(m.flat[lo:hi], m.flat_grad[lo:hi], self.m[lo:hi], self.v[lo:hi], self.wd, self.clip, self.lr, self.betas[0],
+                             self.betas[1], self.eps, t, self.gn2)
+
+    def loss(self):
+        return (self.loss_slots.sum(1) * torch.tensor(self._loss_w(), device=self.model.dev, dtype=torch.float32)).sum()
+
+    def grad_norm(self):
+        return self.gn2.sum().sqrt()
+
+
 # ---- batched candidate evaluation ---------------------------------------------------------------------------------------------
 def _stack(parts):
     """parts: list of tuples of (rows, d) tensors -> one tuple of stacked tensors."""

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .dp import GradBuckets, capture, reduce_sum
 
 
 class _Holder(torch.nn.Module):
@@ -217,6 +218,13 @@ class FlatModule(torch.nn.Module):
         self._step_seed += 1
         self.set_seed(self._step_seed * 2654435761 + 12345)
 
+    def seed_trainer(self, seed):
+        """The dropout stream a trainer constructed with `seed` starts from."""
+        self.set_seed(seed * 1000003 + 12345)
+
+    def advance_seed(self):
+        self._seed.add_(-1640531535)    # += 0x9E3779B1 (mod 2^32): a fresh dropout stream every step, on the device
+
     def ids(self, a):
         if isinstance(a, torch.Tensor):
             return a.to(device=self.dev, dtype=torch.int32).contiguous()
@@ -226,6 +234,13 @@ class FlatModule(torch.nn.Module):
         for k, v in P.items():
             self.R(k).copy_(torch.from_numpy(np.ascontiguousarray(v)))
         self.push()
+
+
+def loss_norms(model, T, n_bce=0.0, scale=1):
+    """Device normalisers {n_bce, n_mse, n_nll} of the loss seeds for T = B * L token rows: the BCE count (0 where the loss has no BCE
+    term), T * d and T * H.  `scale`: the factor from a data-parallel shard's rows to the GLOBAL batch (adt_amd/dp.py, rule 1)."""
+    return torch.tensor([float(n_bce), float(scale * T * model.hidden_units), float(scale * T * model.num_heads)], device=model.dev,
+                        dtype=torch.float32)
 
 
 class Act:
@@ -439,3 +454,76 @@ class Tape:
             ops.headcls_bwd(o.t, Ws, rec.t, rec.g, 1, T, o.g, gWs, gbs)
         self.bw.append(bw)
         return rec
+
+
+class TapeTrainer:
+    """What the fused trainers of the tape models share (sasrec/model_wide.py, bert4rec/trainer.py, stosa/trainer.py): the flat Adam
+    moments and device scalars, the data-parallel gradient buckets, the staged-batch buffers a HIP graph replays from, and the step
+    protocol around one launch sequence.  A subclass supplies `stage(...)` (one batch -> dict of device tensors + "B"), `_body(st, b_offset)`
+    (forward, loss, backward, `_buckets.finish()`, optimiser) and a `step(...)` with its own batch signature."""
+
+    def __init__(self, model, loss_w, boundary, lr, betas, eps, weight_decay, clip, process_group, use_graph, n=None):
+        """loss_w: the weight of every loss slot row in loss(); boundary: the first parameter of the gradient's tail bucket (the decoder, whose
+        backward runs first); n: the trained prefix of the flat buffer when it is not all of it."""
+        self.model = model
+        self.lr, self.betas, self.eps, self.wd, self.clip = lr, betas, eps, weight_decay, clip
+        self.pg = process_group
+        self.world = 1 if process_group is None else torch.distributed.get_world_size(process_group)
+        self.rank = 0 if process_group is None else torch.distributed.get_rank(process_group)
+        self.use_graph = use_graph       # data-parallel steps are captured too (RCCL collectives are graph nodes)
+        self._buckets = GradBuckets(model.flat_grad, model.offset_of(boundary), process_group, n=n)
+        dev = model.dev
+        self.m, self.v = torch.zeros_like(model.flat), torch.zeros_like(model.flat)
+        self.scal = torch.zeros(192, device=dev, dtype=torch.float32)
+        self.loss_slots = torch.zeros(len(loss_w), 64, device=dev, dtype=torch.float32)
+        self._loss_w = torch.tensor(loss_w, device=dev, dtype=torch.float32)
+        self.nstep = 0
+        self._graph, self._st = None, None
+
+    def _launch(self, b_offset):
+        m = self.model
+        m.advance_seed()
+        self.loss_slots.zero_()
+        m.flat_grad.zero_()
+        m.dp_hook = self._buckets.tail_ready if self._buckets.active else None
+        self._body(self._st, b_offset)
+
+    def _copy_stage(self, st):
+        """Graph replays read fixed buffers: copy the new batch into the captured ones."""
+        if self._st is None or self._st["B"] != st["B"]:
+            self._st = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in st.items()}
+            self._graph = None
+            return
+        for k, v in st.items():
+            if isinstance(v, torch.Tensor):
+                self._st[k].copy_(v, non_blocking=True)
+            else:
+                self._st[k] = v
+
+    def step_staged(self, st, b_offset=0):
+        self.model.train()
+        self._copy_stage(st)
+        self.nstep += 1
+        if not self.use_graph:
+            self._launch(b_offset)
+            return
+        if self._graph is None:
+            self._launch(b_offset)          # warm up eagerly (hipFuncSetAttribute is not capturable), then capture
+            torch.cuda.synchronize()
+            self._graph = torch.cuda.CUDAGraph()
+            with capture(self._graph):
+                self._launch(b_offset)
+            return
+        self._graph.replay()
+
+    def loss_parts(self):
+        """The loss slots of the last step, one sum per row (summed over the ranks: each holds its shard's partial sums)."""
+        slots = self.loss_slots.sum(1)
+        return reduce_sum(slots, self.pg) if self.world > 1 else slots
+
+    def loss(self):
+        """Device scalar: the loss of the last step as the reference's training loop reports it."""
+        return (self.loss_parts() * self._loss_w).sum()
+
+    def grad_norm(self):
+        return self.scal[1].sqrt()
