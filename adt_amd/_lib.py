@@ -119,6 +119,8 @@ SIGNATURES = {
     "adt_topk_masked": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
     "adt_full_rank_ws_bytes": (_L, [_I, _I, _I, _I]),
     "adt_full_rank": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P]),
+    "adt_full_rank_from": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P]),
+    "adt_wdist_pack": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _F, _P]),
     "adt_item_sort_supported": (_I, [_I]),
     "adt_item_sort_work_ints": (_L, [_I, _I, _I]),
     "adt_item_sort": (_I, [_P, _I, _I, _I, _P, _P, _P, _U, _P, _P]),

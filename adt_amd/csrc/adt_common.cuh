@@ -165,6 +165,11 @@ __device__ __forceinline__ float wave_max(float v) {
 
 #define ADT_DEVICE_INLINE __device__ __forceinline__
 
+// The two covariance transforms of STOSA-ADT, shared by adt_stosa.cuh and adt_wdist_pack.cuh (two translation units) so that a packed
+// item image holds exactly the operands the elementwise kernels multiply: sqrt of the covariance clamped at 1e-24, and ELU(x) + 1.
+ADT_DEVICE_INLINE float w_sqrt_cov(float c) { return sqrtf(fmaxf(c, 1e-24f)); }
+ADT_DEVICE_INLINE float w_elu1(float x) { return (x > 0.f ? x : expf(x) - 1.0f) + 1.0f; }
+
 // wave sum that stays in the vector ALU: four DPP steps inside each row of 16 lanes, then v_permlane16_swap / v_permlane32_swap across the
 // rows (gfx950).  wave_sum above goes through ds_bpermute_b32 six times: a dependent chain of LDS-crossbar round trips.
 __device__ __forceinline__ float wave_sum_valu(float v) {

@@ -1,5 +1,5 @@
 // Full-catalogue ranking and top-K selection for the dot-product backbones (SASRec-ADT, BERT4Rec-ADT): exact fp32 scores
-// s[b][j] = F[b] . E[j] (+ bias[j]) of every eligible item, the rank of one target item per user and the K best items, without a
+// s[b][j] = F[b] . E[j] (+ bias[j]) of every eligible item (ids first_id .. n_items, first_id = 1 or 0), the rank of one target item per user and the K best items, without a
 // (B, V) logit matrix in HBM.  DESIGN.md section 12.
 //
 //   k_full_rank        grid (tiles of 16 user rows, S item splits), 4 waves.  The workgroup keeps its 16 feature rows in LDS and streams
@@ -32,6 +32,7 @@ constexpr int FR_LD4 = FR_CH * FR_KC / 4 / FR_NTH;      // float4 loads per thre
 struct FullRankArgs {
   const float* F; int ldf; const float* E; int lde; const float* bias;
   int B, d, n_items;
+  int first_id;                        // the smallest id that competes: 1, or 0 where the padding row is a candidate (STOSA-ADT's full sort)
   const int32_t* target; const int32_t* indptr; const int32_t* indices;
   int K, S, per;                      // per: items per split, a multiple of FR_CH
   int32_t* ws_cnt; float* ws_val; int32_t* ws_idx;      // (B, S, 2) {rank count, eligible count}, (B, S, K), (B, S, K)
@@ -155,13 +156,13 @@ ADT_DEVICE_INLINE void fr_run(const FullRankArgs& a, const FrCtx& x, int lo, int
           constexpr int rr = decltype(R)::value;
           const int row = 4 * x.w + rr;
           const bool live = x.b0 + row < a.B;
-          const int t = x.tgt[row];
+          const int t = x.tgt[row] ? x.tgt[row] : -1;      // no target: no id is set aside (id 0 competes when first_id = 0)
           const float ts = x.tsc[row];
 #pragma unroll
           for (int half = 0; half < 2; ++half) {
             const int slot = x.lane + 64 * half, id = base + slot;
             const float v = x.Sc[row * FR_SRS + slot];
-            bool elig = live && id >= 1 && id < hi;
+            bool elig = live && id >= a.first_id && id < hi;
             if (elig) elig = ((x.bm[row * FR_BMW + ((id - sc_lo) >> 5)] >> ((id - sc_lo) & 31)) & 1u) == 0u;
             const bool other = elig && id != t;
             ne[rr] += __popcll(__ballot(other));
@@ -220,10 +221,10 @@ __global__ __launch_bounds__(FR_NTH) void k_full_rank(FullRankArgs a) {
       for (int row = x.w; row < 16; row += FR_NW) {
         const int b = x.b0 + row;
         if (b >= a.B) break;
-        const int t = x.tgt[row], j1 = a.indptr[b + 1];
+        const int t = x.tgt[row] ? x.tgt[row] : -1, j1 = a.indptr[b + 1];
         for (int j = a.indptr[b] + x.lane; j < j1; j += 64) {
           const int id = a.indices[j];
-          if (id >= 1 && id >= sc_lo && id < sc_hi && id != t) atomicOr(&x.bm[row * FR_BMW + ((id - sc_lo) >> 5)], 1u << ((id - sc_lo) & 31));
+          if (id >= a.first_id && id >= sc_lo && id < sc_hi && id != t) atomicOr(&x.bm[row * FR_BMW + ((id - sc_lo) >> 5)], 1u << ((id - sc_lo) & 31));
         }
       }
       __syncthreads();

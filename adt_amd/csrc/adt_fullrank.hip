@@ -3,6 +3,7 @@
 #include "adt_host.h"
 
 #include "adt_fullrank.cuh"
+#include "adt_wdist_pack.cuh"
 
 using namespace adt;
 
@@ -37,9 +38,10 @@ int64_t adt_full_rank_ws_bytes(int B, int n_items, int K, int splits) {
   return fr_ws_bytes(B, S, K);
 }
 
-int adt_full_rank(const float* F, int ldf, const float* E, int lde, const float* bias, int B, int d, int n_items, const int32_t* target,
-                  const int32_t* indptr, const int32_t* indices, int K, int splits, void* ws, int64_t ws_bytes, int32_t* rank,
-                  int32_t* n_elig, int32_t* top_idx, float* top_val, void* stream) {
+int adt_full_rank_from(const float* F, int ldf, const float* E, int lde, const float* bias, int B, int d, int n_items, int first_id,
+                       const int32_t* target, const int32_t* indptr, const int32_t* indices, int K, int splits, void* ws, int64_t ws_bytes,
+                       int32_t* rank, int32_t* n_elig, int32_t* top_idx, float* top_val, void* stream) {
+  if (first_id != 0 && first_id != 1) return adt_set_error("full_rank: first_id=%d must be 0 or 1", first_id);
   if (K < 0 || K > FR_KMAX) return adt_set_error("full_rank: K=%d outside 0..%d", K, FR_KMAX);
   if (d < 4 || (d % 4)) return adt_set_error("full_rank: d=%d must be a positive multiple of 4", d);
   if (lde < d || ldf < d) return adt_set_error("full_rank: lde=%d, ldf=%d must be >= d=%d", lde, ldf, d);
@@ -54,7 +56,7 @@ int adt_full_rank(const float* F, int ldf, const float* E, int lde, const float*
   FullRankArgs a{};
   fr_plan(B, n_items, splits, &a.S, &a.per);
   if (!ws || ws_bytes < fr_ws_bytes(B, a.S, K)) return adt_set_error("full_rank: workspace of %lld B, need %lld (adt_full_rank_ws_bytes)", (long long)ws_bytes, (long long)fr_ws_bytes(B, a.S, K));
-  a.F = F; a.ldf = ldf; a.E = E; a.lde = lde; a.bias = bias; a.B = B; a.d = d; a.n_items = n_items;
+  a.F = F; a.ldf = ldf; a.E = E; a.lde = lde; a.bias = bias; a.B = B; a.d = d; a.n_items = n_items; a.first_id = first_id;
   a.target = target; a.indptr = indptr; a.indices = indices; a.K = K;
   a.ws_cnt = static_cast<int32_t*>(ws);
   a.ws_val = reinterpret_cast<float*>(a.ws_cnt + (size_t)B * a.S * 2);
@@ -64,6 +66,26 @@ int adt_full_rank(const float* F, int ldf, const float* E, int lde, const float*
   if (adt_launch_lds1((const void*)k_full_rank, dim3((B + 15) / 16, a.S), dim3(FR_NTH), smem, a, (hipStream_t)stream, "full_rank", optin)) return -1;
   hipLaunchKernelGGL(k_full_rank_merge, dim3((B + FR_NW - 1) / FR_NW), dim3(FR_NTH), 0, (hipStream_t)stream, a);
   return adt_check_launch("full_rank(merge)");
+}
+
+int adt_full_rank(const float* F, int ldf, const float* E, int lde, const float* bias, int B, int d, int n_items, const int32_t* target,
+                  const int32_t* indptr, const int32_t* indices, int K, int splits, void* ws, int64_t ws_bytes, int32_t* rank,
+                  int32_t* n_elig, int32_t* top_idx, float* top_val, void* stream) {
+  return adt_full_rank_from(F, ldf, E, lde, bias, B, d, n_items, 1, target, indptr, indices, K, splits, ws, ws_bytes, rank, n_elig, top_idx,
+                            top_val, stream);
+}
+
+int adt_wdist_pack(const float* M, const float* C, int ld, int rows, int d, int elu, float* img, int ldi, float* nrm, float nrm_scale,
+                   void* stream) {
+  if (d < 4 || (d % 4)) return adt_set_error("wdist_pack: d=%d must be a positive multiple of 4", d);
+  if (ld < d || ldi < 2 * d) return adt_set_error("wdist_pack: ld=%d must be >= d=%d and ldi=%d >= 2d", ld, d, ldi);
+  if ((ld % 4) || (ldi % 4) || !adt_aligned16(M) || !adt_aligned16(C) || !adt_aligned16(img))
+    return adt_set_error("wdist_pack: M, C and img must be 16-byte aligned with ld %% 4 == 0 and ldi %% 4 == 0");
+  if (rows <= 0) return 0;
+  if (!M || !C || !img || !nrm) return adt_set_error("wdist_pack: missing operand");
+  WPackArgs a{M, C, ld, rows, d, elu != 0, img, ldi, nrm, nrm_scale};
+  hipLaunchKernelGGL(k_wdist_pack, dim3(adt_grid_for((size_t)rows, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("wdist_pack");
 }
 
 }  // extern "C"

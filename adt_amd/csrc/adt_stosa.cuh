@@ -41,8 +41,6 @@ static inline size_t wattn_lds_bytes(int L, int hd, bool bwd) {
   return f * sizeof(float);
 }
 
-ADT_DEVICE_INLINE float w_sqrt_cov(float c) { return sqrtf(fmaxf(c, 1e-24f)); }
-
 // stage a head slice (L x hd) into LDS rows of stride hd+1, optionally through sqrt(clamp(.)); also return via `norm`
 // (if non-null) the per-row sums |m|^2 (SQUARE) or sum(c) (plain) ACCUMULATED into norm[r]
 template <bool SQRT, bool SQUARE_NORM>
@@ -377,7 +375,6 @@ struct WBprArgs {
   float* loss3;                                  // 3 x 64 slots: bpr, pvn (weighted), auc
 };
 
-ADT_DEVICE_INLINE float w_elu1(float x) { return (x > 0.f ? x : expf(x) - 1.0f) + 1.0f; }
 ADT_DEVICE_INLINE float w_elu_grad(float x) { return x > 0.f ? 1.f : expf(x); }
 
 __global__ __launch_bounds__(256) void k_wdist_bpr(WBprArgs a) {

@@ -1,10 +1,22 @@
 """Full-catalogue ranking and top-K recommendation for the dot-product backbones (SASRecADT, SASRecADTWide, BertModel): one
 adt_full_rank call on the final feature rows and the item table (include/adt_hip.h; adt_amd/csrc/adt_fullrank.cuh).  No (B, V) logit
-matrix exists at any point; only B ranks, B counts and the (B, k) best items come back."""
+matrix exists at any point; only B ranks, B counts and the (B, k) best items come back.
+
+STOSA-ADT (DistRankMixin) ranks by ascending Wasserstein distance through the same kernel: adt_wdist_pack turns the two item tables and
+the users' last states into 2d-wide row images with dist[b][j] = na[b] - 2 (A[b] . W[j] + bias[j]) ("STOSA")."""
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
+
+
+def _targets(targets, B, device):
+    if targets is None:
+        return None
+    tgt = targets.to(device=device, dtype=torch.int32).contiguous() if isinstance(targets, torch.Tensor) else \
+        torch.from_numpy(np.ascontiguousarray(np.asarray(targets), dtype=np.int32)).to(device)
+    assert tgt.numel() == B, (tgt.shape, B)
+    return tgt
 
 
 class FullRankMixin:
@@ -19,16 +31,81 @@ class FullRankMixin:
         than the target, top_idx (B, topk), top_val (B, topk)); the last two are None when topk = 0."""
         F, E, n_items, bias = self._full_rank_operands(log_seqs)
         B = F.shape[0]
-        tgt = None
-        if targets is not None:
-            tgt = targets.to(device=E.device, dtype=torch.int32).contiguous() if isinstance(targets, torch.Tensor) else \
-                torch.from_numpy(np.ascontiguousarray(np.asarray(targets), dtype=np.int32)).to(E.device)
-            assert tgt.numel() == B, (tgt.shape, B)
         indptr, indices = ops.seen_csr(seen, B, E.device)
-        return ops.full_rank(F, F.stride(0), E, n_items, tgt, bias, indptr, indices, topk)
+        return ops.full_rank(F, F.stride(0), E, n_items, _targets(targets, B, E.device), bias, indptr, indices, topk)
 
     def recommend(self, log_seqs, k, seen=None):
         """The k best unseen items of every user: (ids (B, k) int32, scores (B, k)), best first, ties to the smaller id; -1 / -inf where
         fewer than k items are left."""
         _, _, idx, val = self.rank_full(log_seqs, None, seen, k)
         return idx, val
+
+
+# ---- STOSA-ADT: Wasserstein distance ---------------------------------------------------------------------------------------------------
+def _seen(seen, B, device):
+    """ops.seen_csr, or an (indptr, indices) pair that is on the device already."""
+    if isinstance(seen, tuple) and all(x is None or isinstance(x, torch.Tensor) for x in seen):
+        return seen
+    return ops.seen_csr(seen, B, device)
+
+
+def dist_from_scores(na, top_idx, top_val):
+    """Scores of adt_full_rank on packed images back to distances: top_dist = na[:, None] - 2 * top_val (ascending, as top_val
+    descends); +inf where top_idx is -1 (fewer than k eligible items)."""
+    dist = na[:, None] - 2.0 * top_val
+    return torch.where(top_idx < 0, torch.full_like(dist, float("inf")), dist)
+
+
+def fused_ids_or_two_pass(top_idx, two_pass):
+    """The fused top-k ids of one evaluation batch as an int64 array -- unless some row came back with a -1 (fewer than k unseen
+    items: the reference's sort then continues into the seen items, pushed to 1e24): then the whole batch is two_pass(), the form that
+    reproduces it.  Returns (ids, fell_back)."""
+    ids = top_idx.cpu().numpy().astype(np.int64)
+    if (ids < 0).any():
+        return two_pass(), True
+    return ids, False
+
+
+class DistRankMixin:
+    """A model supplies _dist_tables() -> (Em, Ec, n_items): the item mean / raw covariance tables (n_items + 1 rows are ranked) and
+    _last_state(input_ids) -> (sm, sc): the (B, d) mean / covariance of the last position.  Wasserstein distance only."""
+
+    def _check_wasserstein(self):
+        if getattr(self, "distance_metric", "wasserstein") != "wasserstein":
+            raise _lib.AdtError("fused full-catalogue ranking is built for distance_metric='wasserstein' only: the %r scores depend on the eval "
+                                "batch's size and row order, not on (user, item) alone; use predict_full + topk_masked" % (self.distance_metric,))
+
+    @torch.no_grad()
+    def item_image(self):
+        """(W (n_items + 1, 2d), bias (n_items + 1,)) of the two item tables.  Packed on every call -- no cache: it is stale after any
+        weight update -- so a caller that ranks many batches under the same weights holds on to it and passes it as `image`."""
+        self._check_wasserstein()
+        Em, Ec, _ = self._dist_tables()
+        return ops.wdist_pack(Em, Ec, True, -0.5)
+
+    @torch.no_grad()
+    def _rank_states(self, sm, sc, targets, seen, topk, image, first_id):
+        W, bias = self.item_image() if image is None else image
+        n_items = self._dist_tables()[2]
+        A, na = ops.wdist_pack(sm, sc, False, 1.0)
+        B = A.shape[0]
+        indptr, indices = _seen(seen, B, A.device)
+        rank, n_elig, top_idx, top_val = ops.full_rank(A, A.stride(0), W, n_items, _targets(targets, B, A.device), bias, indptr, indices, topk,
+                                                       first_id=first_id)
+        return rank, n_elig, top_idx, (None if top_idx is None else dist_from_scores(na, top_idx, top_val))
+
+    @torch.no_grad()
+    def rank_full(self, input_ids, targets, seen=None, topk=0, image=None, first_id=1):
+        """As FullRankMixin.rank_full with `smaller distance` for `higher score`: (rank (B,) -- eligible items strictly closer than the
+        target, -1 without one --, n_elig (B,), top_idx (B, topk), top_dist (B, topk) ascending, ties to the smaller id, -1 / +inf
+        tail).  image: item_image() of the current weights; first_id = 0 lets the padding item 0 compete, as the reference's full sort
+        does (targets stay 1..n_items)."""
+        self._check_wasserstein()
+        sm, sc = self._last_state(input_ids)
+        return self._rank_states(sm, sc, targets, seen, topk, image, first_id)
+
+    def recommend(self, input_ids, k, seen=None, image=None):
+        """The k closest unseen items of every user: (ids (B, k) int32, distances (B, k)), closest first; -1 / +inf where fewer than k
+        items are left.  The padding item 0 is never recommended."""
+        _, _, idx, dist = self.rank_full(input_ids, None, seen, k, image, 1)
+        return idx, dist

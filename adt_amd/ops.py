@@ -618,11 +618,12 @@ def seen_csr(seen, rows, device):
     return torch.from_numpy(ip).to(device), torch.from_numpy(ix).to(device)
 
 
-def full_rank(F, ldf, E, n_items, target=None, bias=None, indptr=None, indices=None, k=0, splits=0):
+def full_rank(F, ldf, E, n_items, target=None, bias=None, indptr=None, indices=None, k=0, splits=0, first_id=1):
     """Exact fp32 scores F[b] . E[j] (+ bias[j]) of every eligible item 1 <= j <= n_items not in the user's CSR seen list, never
     materialised: returns (rank (B,) int32 of target[b] among the eligible items, -1 without a target; n_elig (B,) int32 eligible items
     other than the target; top_idx (B, k) int32 and top_val (B, k) of the k best, score descending, ties to the smaller id, -1 / -inf
-    tail; both None when k = 0).  F: B rows of width E.shape[1] at row stride ldf (any view whose first element is row 0)."""
+    tail; both None when k = 0).  F: B rows of width E.shape[1] at row stride ldf (any view whose first element is row 0).
+    first_id = 0 (adt_full_rank_from) lets item 0 compete as well: ranked, counted, selected, excluded where the seen list names it."""
     # F is either the (B, d) view itself or a longer buffer whose rows sit ldf apart: then the targets / the CSR give the batch
     if F.dim() == 2 and F.stride(0) == ldf:
         B = F.shape[0]
@@ -644,7 +645,21 @@ def full_rank(F, ldf, E, n_items, target=None, bias=None, indptr=None, indices=N
     n_elig = torch.empty(B, device=dev, dtype=torch.int32)
     top_idx = torch.empty(B, k, device=dev, dtype=torch.int32) if k > 0 else None
     top_val = torch.empty(B, k, device=dev, dtype=torch.float32) if k > 0 else None
-    _lib.check(lib.adt_full_rank(_p(_f32(F)), int(ldf), _p(_f32(E)), lde, _p(bias), B, d, int(n_items), _p(None if target is None else _i32(target)),
-                                 _p(None if indptr is None else _i32(indptr)), _p(None if indices is None else _i32(indices)), int(k), int(splits),
-                                 _p(ws), ws.numel(), _p(rank), _p(n_elig), _p(top_idx), _p(top_val), _stream()), "full_rank")
+    _lib.check(lib.adt_full_rank_from(_p(_f32(F)), int(ldf), _p(_f32(E)), lde, _p(bias), B, d, int(n_items), int(first_id),
+                                      _p(None if target is None else _i32(target)), _p(None if indptr is None else _i32(indptr)),
+                                      _p(None if indices is None else _i32(indices)), int(k), int(splits), _p(ws), ws.numel(), _p(rank),
+                                      _p(n_elig), _p(top_idx), _p(top_val), _stream()), "full_rank")
     return rank, n_elig, top_idx, top_val
+
+
+def wdist_pack(M, C, elu, nrm_scale):
+    """Row images for Wasserstein full-catalogue ranking (adt_wdist_pack): img (rows, 2d) = [M | sqrt(max(c, 1e-24))] and
+    nrm (rows,) = nrm_scale * (sum M^2 + sum c), c = ELU(C) + 1 when elu else C.  Items: (True, -0.5) -> (W, bias) of full_rank; user
+    states: (False, 1.0) -> (A, na), with dist[b][j] = na[b] - 2 * (A[b] . W[j] + bias[j])."""
+    assert M.dim() == 2 and M.shape == C.shape and M.stride(0) == C.stride(0), (M.shape, C.shape, M.stride(), C.stride())
+    rows, d = M.shape
+    img = torch.empty(rows, 2 * d, device=M.device, dtype=torch.float32)
+    nrm = torch.empty(rows, device=M.device, dtype=torch.float32)
+    _lib.check(_lib.load().adt_wdist_pack(_p(_f32(M)), _p(_f32(C)), M.stride(0), rows, d, int(bool(elu)), _p(img), 2 * d, _p(nrm), float(nrm_scale),
+                                          _stream()), "wdist_pack")
+    return img, nrm

@@ -53,6 +53,8 @@ def parse_args(argv=None):
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--precision", default="bf16", choices=["bf16", "f32"])
     p.add_argument("--out_dir", default="res")
+    p.add_argument("--fused_eval", action="store_true",
+                   help="score candidates without the (group * B, item_size) distance matrix: packed item image + adt_full_rank_from")
     return p.parse_args(argv)
 
 

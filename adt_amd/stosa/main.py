@@ -51,6 +51,8 @@ def parse_args(argv=None):
     p.add_argument("--precision", default="bf16", choices=["bf16", "f32"])
     p.add_argument("--use_graph", type=lambda s: str(s).lower() in ("1", "true", "yes"), default=True)
     p.add_argument("--override", default=None)
+    p.add_argument("--fused_eval", action="store_true",
+                   help="full-sort evaluation without the (B, item_size) distance matrix: packed item image + adt_full_rank_from (Wasserstein only)")
     return p.parse_args(argv)
 
 
@@ -67,14 +69,14 @@ def _write_synthetic(path, users=22363, items=12101, seed=42):
             f.write("%d %s\n" % (u, " ".join(str(int(x)) for x in seq)))
 
 
-def _evaluate(trainer, ds, matrix, batch_size):
+def _evaluate(trainer, ds, matrix, batch_size, fused=False):
     """Full-sort scores of the whole user set on every rank: under data parallelism rank r sorts batches r, r+W, ... on its GPU
     and the (N, 40) id lists are gathered (a few hundred KB)."""
     def gen():
         for i, (users, inp, dec, pos, neg, ans) in enumerate(ds.epoch_batches(batch_size, shuffle=False)):
             if i % trainer.world == trainer.rank:
                 yield inp, matrix[users], ans
-    pred, answers = trainer.full_sort(gen())
+    pred, answers = trainer.full_sort(gen(), fused=fused)
     if trainer.world > 1:
         parts = [None] * trainer.world
         torch.distributed.all_gather_object(parts, (pred, answers), group=trainer.pg)
@@ -130,7 +132,7 @@ def main(argv=None):
             nseq += len(users)
         torch.cuda.synchronize()
         T += time.time() - t0
-        scores = _evaluate(trainer, valid_ds, valid_matrix, args.eval_batch_size)
+        scores = _evaluate(trainer, valid_ds, valid_matrix, args.eval_batch_size, args.fused_eval)
         parts = trainer.loss_parts().cpu().numpy()      # a collective under data parallelism: every rank calls it
         if rank == 0:
             print(json.dumps({"epoch": epoch, "train_seconds": T, "sequences_per_sec": nseq / max(T, 1e-9), "n_gpus": world,
@@ -147,8 +149,8 @@ def main(argv=None):
     if world > 1:
         torch.distributed.barrier()
     model.load_state_dict(torch.load(ckpt))
-    valid_scores = _evaluate(trainer, valid_ds, valid_matrix, args.eval_batch_size)
-    scores = _evaluate(trainer, test_ds, test_matrix, args.eval_batch_size)
+    valid_scores = _evaluate(trainer, valid_ds, valid_matrix, args.eval_batch_size, args.fused_eval)
+    scores = _evaluate(trainer, test_ds, test_matrix, args.eval_batch_size, args.fused_eval)
     if rank == 0:
         print("(%s, %s, %s, %s, %s, %s, %s, %s)" % (valid_scores[0], valid_scores[2], valid_scores[3], valid_scores[-1], scores[0], scores[2], scores[3], scores[-1]))
     if pg is not None:

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from .. import _lib, custom_ops, ops
+from ..fullrank import DistRankMixin
 from ..wide import Act, FlatModule, Tape, give
 
 LN_EPS = 1e-12
@@ -79,7 +80,7 @@ def param_table(item_size, maxlen, d, H, nl, num_users, block=0, dec_layernorm=T
     return t, n_trained
 
 
-class DisenDistSAModel(FlatModule):
+class DisenDistSAModel(DistRankMixin, FlatModule):
     def __init__(self, args, block=0, dec_layernorm=True):
         super().__init__()
         self.args = args
@@ -270,9 +271,8 @@ class DisenDistSAModel(FlatModule):
         return custom_ops.param_grads(self, lambda n: self._views[n][0] >= base)     # the reference leaves these at grad None
 
     @torch.no_grad()
-    def predict_full(self, input_ids, dec_ids=None):
-        """Full-sort scores (stosa/trainer.py:583-595), (B, item_size): dist_predict_full (:464-479), the Wasserstein distance of the
-        last state to every item, or kl_predict_full (:481-511), whose scores depend on the rows of this call being the eval batch."""
+    def _last_state(self, input_ids, dec_ids=None):
+        """(mean, covariance) (B, d) of the last position in eval mode: what every full-sort score is taken from (stosa/trainer.py:590-595)."""
         inp = self.ids(input_ids)
         dec = inp if dec_ids is None else self.ids(dec_ids)
         B, L = inp.shape
@@ -283,6 +283,18 @@ class DisenDistSAModel(FlatModule):
         rows = torch.arange(L - 1, B * L, L, device=self.dev, dtype=torch.int32)
         sm, sc = ops.gather_rows(m.t, rows), ops.gather_rows(c.t, rows)
         self.train(was)
+        return sm, sc
+
+    def _dist_tables(self):
+        """The item tables for DistRankMixin.  Every row 0..item_size - 1 of the tables takes part in the reference's full sort (the
+        padding row 0 only with first_id = 0), so n_items = item_size - 1."""
+        return self.P("item_mean_embeddings.weight"), self.P("item_cov_embeddings.weight"), self.item_size - 1
+
+    @torch.no_grad()
+    def predict_full(self, input_ids, dec_ids=None):
+        """Full-sort scores (stosa/trainer.py:583-595), (B, item_size): dist_predict_full (:464-479), the Wasserstein distance of the
+        last state to every item, or kl_predict_full (:481-511), whose scores depend on the rows of this call being the eval batch."""
+        sm, sc = self._last_state(input_ids, dec_ids)
         return self._dist_full(sm, sc, self.P("item_mean_embeddings.weight"), self.P("item_cov_embeddings.weight"), self.item_size)
 
     # ------------------------------------------------------------------------------------------------------------------

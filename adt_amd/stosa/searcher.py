@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..fullrank import fused_ids_or_two_pass
 from ..supersearch import EvolutionSearch, cand_to_block, get_shared, result_name
 from .datasets import DisenDataset, get_user_seqs
 from .supernet import DisenDistSASupernet, SuperStosaTrainer
@@ -33,13 +34,16 @@ class SearcherEvolution:
         self.model = DisenDistSASupernet(args, self.rec_choice, self.ind_choice)
         self.trainer = SuperStosaTrainer(self.model, lr=args.lr, betas=(args.adam_beta1, args.adam_beta2), weight_decay=args.weight_decay,
                                          seed=args.seed)
-        self.search_state = EvolutionSearch(args.num_layers, self.evaluate_candidates, "MRR", args.select_num, args.population_num, args.m_prob,
+        self.search_state = EvolutionSearch(args.num_layers, self._evaluate_for_search, "MRR", args.select_num, args.population_num, args.m_prob,
                                             args.crossover_num, args.mutation_num, args.scale_factor)
         self.eval_stats = {}
 
     @property
     def vis_dict(self):
         return self.search_state.vis_dict
+
+    def _evaluate_for_search(self, cands):
+        return self.evaluate_candidates(cands, fused=bool(getattr(self.args, "fused_eval", False)))
 
     def _seen_csr(self, matrix, users, copies):
         """CSR of the users' seen items, repeated for `copies` stacked candidates, on the device."""
@@ -54,9 +58,13 @@ class SearcherEvolution:
         return (torch.from_numpy(np.ascontiguousarray(ip_all, dtype=np.int32)).to(dev),
                 torch.from_numpy(np.ascontiguousarray(np.tile(ix, copies), dtype=np.int32)).to(dev))
 
-    def evaluate_candidates(self, cands, dataset=None, matrix=None, group=8, prefix="V"):
+    def evaluate_candidates(self, cands, dataset=None, matrix=None, group=8, prefix="V", fused=False):
         """Full-sort scores (Trainer.get_full_sort_score, stosa/trainer.py:62-86) of the supernet under every candidate of `cands`:
-        every validation batch is ranked for `group` candidates per pass (distances, seen-item masking and top-40 on the device)."""
+        every validation batch is ranked for `group` candidates per pass (distances, seen-item masking and top-40 on the device).
+        fused (the search passes args.fused_eval; default off): the item image is packed once per call -- the candidates share the item tables --
+        and each pass is one adt_full_rank_from call (first_id = 0) on the stacked rows instead of a (group * B, item_size) distance
+        matrix; a pass with a user who has fewer than 40 unseen items falls back to the two-pass form."""
+        image = self.model.item_image() if fused else None
         ds = self.valid_ds if dataset is None else dataset
         matrix = self.valid_matrix if matrix is None else matrix
         shared = [get_shared(self.rec_choice, self.ind_choice, cand_to_block(self.rec_choice, self.ind_choice, c)[0]) for c in cands]
@@ -67,9 +75,16 @@ class SearcherEvolution:
             B = len(users)
             for g0 in range(0, len(cands), group):
                 sl = shared[g0:g0 + group]
-                dist = self.model.predict_full_candidates(inp, sl, stats=self.eval_stats)
                 indptr, indices = self._seen_csr(matrix, users, len(sl))
-                top = ops.topk_masked(dist, 40, indptr, indices).cpu().numpy().astype(np.int64)
+
+                def two_pass():
+                    dist = self.model.predict_full_candidates(inp, sl, stats=self.eval_stats)
+                    return ops.topk_masked(dist, 40, indptr, indices).cpu().numpy().astype(np.int64)
+                if fused:
+                    top_idx = self.model.rank_full_candidates(inp, sl, None, (indptr, indices), 40, image, self.eval_stats, first_id=0)[2]
+                    top, _ = fused_ids_or_two_pass(top_idx, two_pass)
+                else:
+                    top = two_pass()
                 for k in range(len(sl)):
                     preds[g0 + k].append(top[k * B:(k + 1) * B])
         answers = np.concatenate(answers)

@@ -85,10 +85,10 @@ class DisenDistSASupernet(DisenDistSAModel):
         return m, c, enc_inputs, enc_recs, dec_outs
 
     @torch.no_grad()
-    def predict_full_candidates(self, input_ids, shared_list, stats=None):
-        """Full-sort Wasserstein distances of the last state to every item under EVERY block choice of `shared_list`: (P * B, item_size),
-        candidate-major.  One pass: chain prefixes of depth 0 are shared between candidates, deeper links run once per distinct layer on
-        the stacked inputs (supersearch.candidate_features, chain=True)."""
+    def _last_state_candidates(self, input_ids, shared_list, stats=None):
+        """(mean, covariance) (P * B, d) of the last position under EVERY block choice of `shared_list`, candidate-major.  One pass: chain
+        prefixes of depth 0 are shared between candidates, deeper links run once per distinct layer on the stacked inputs
+        (supersearch.candidate_features, chain=True)."""
         inp = self.ids(input_ids)
         B, L = inp.shape
         was = self.training
@@ -107,8 +107,27 @@ class DisenDistSASupernet(DisenDistSAModel):
         M = feats[0][0] if P == 1 else torch.cat([f[0] for f in feats], 0)
         C = feats[0][1] if P == 1 else torch.cat([f[1] for f in feats], 0)
         rows = torch.arange(L - 1, P * B * L, L, device=self.dev, dtype=torch.int32)
-        return ops.wdist_full(ops.gather_rows(M, rows), ops.gather_rows(C, rows), self.P("item_mean_embeddings.weight"),
-                              self.P("item_cov_embeddings.weight"), self.item_size)
+        return ops.gather_rows(M, rows), ops.gather_rows(C, rows)
+
+    @torch.no_grad()
+    def predict_full_candidates(self, input_ids, shared_list, stats=None):
+        """Full-sort Wasserstein distances of the last state to every item under EVERY block choice of `shared_list`: (P * B, item_size),
+        candidate-major (the feature pass of _last_state_candidates, then adt_wdist_full)."""
+        sm, sc = self._last_state_candidates(input_ids, shared_list, stats)
+        return ops.wdist_full(sm, sc, self.P("item_mean_embeddings.weight"), self.P("item_cov_embeddings.weight"), self.item_size)
+
+    @torch.no_grad()
+    def rank_full_candidates(self, input_ids, shared_list, targets=None, seen=None, topk=0, image=None, stats=None, first_id=1):
+        """DistRankMixin.rank_full under every block choice of `shared_list` with ONE fused call on the stacked P * B last states:
+        (rank, n_elig, top_idx, top_dist) with P * B rows, candidate-major.  targets: (B,) (repeated per candidate), (P * B,) or None;
+        seen: the CSR of the P * B stacked rows (any form ops.seen_csr takes, or a device (indptr, indices) pair); image: item_image()."""
+        sm, sc = self._last_state_candidates(input_ids, shared_list, stats)
+        PB = sm.shape[0]
+        if targets is not None:
+            targets = torch.as_tensor(np.asarray(targets.cpu() if isinstance(targets, torch.Tensor) else targets)).reshape(-1)
+            if targets.numel() != PB:
+                targets = targets.repeat(len(shared_list))
+        return self._rank_states(sm, sc, targets, seen, topk, image, first_id)
 
 
 class SuperStosaTrainer(SupernetTrainer):

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..fullrank import fused_ids_or_two_pass
 from ..wide import TapeTrainer, loss_norms
 
 
@@ -49,19 +50,35 @@ class FusedStosaTrainer(TapeTrainer):
 
     # ------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def full_sort(self, batches, topk=40):
+    def full_sort(self, batches, topk=40, fused=False):
         """Full-sort evaluation (stosa/trainer.py:583-612) over an iterable of (input_ids (B, L), seen, answers (B, A)): rank all
         items by ascending distance with the seen items pushed to 1e24 and keep `topk`, all on the device (model.predict_full: adt_wdist_full,
         or adt_kldist_full for distance_metric 'kl', whose scores depend on each batch's rows being the eval batch -- pass the reference's
         eval batches -- then adt_topk_masked); only the (B, topk) ids come back.  `seen` is the users' rows of the train/valid rating matrix as a scipy
         CSR matrix, a dense (B, item_size) 0/1 array, an int32 (indptr, indices) pair, or None (ops.seen_csr).  Returns (pred_list (N, topk), answers (N, A)) for
-        get_full_sort_score."""
+        get_full_sort_score.
+
+        fused=True (Wasserstein only; 'kl' raises): no (B, item_size) distance matrix -- the item image is packed once for all batches
+        (adt_wdist_pack) and every batch is one adt_full_rank_from call with first_id = 0 (the padding item competes, as in the
+        reference).  A batch in which some user has fewer than `topk` unseen items is recomputed by the two-pass form, whose list
+        continues into the seen items the way the reference's does."""
         preds, answers = [], []
-        dev = self.model.dev
+        m = self.model
+        dev = m.dev
+        image = m.item_image() if fused else None
+        self.fused_fallbacks = 0
+
+        def two_pass(input_ids, indptr, indices):
+            return ops.topk_masked(m.predict_full(input_ids), topk, indptr, indices).cpu().numpy().astype(np.int64)
         for input_ids, seen, ans in batches:
-            dist = self.model.predict_full(input_ids)
-            indptr, indices = ops.seen_csr(seen, dist.shape[0], dev)
-            preds.append(ops.topk_masked(dist, topk, indptr, indices).cpu().numpy().astype(np.int64))
+            indptr, indices = ops.seen_csr(seen, len(input_ids), dev)
+            if fused:
+                _, _, top_idx, _ = m.rank_full(input_ids, None, (indptr, indices), topk, image, first_id=0)
+                ids, fell_back = fused_ids_or_two_pass(top_idx, lambda: two_pass(input_ids, indptr, indices))
+                self.fused_fallbacks += int(fell_back)
+                preds.append(ids)
+            else:
+                preds.append(two_pass(input_ids, indptr, indices))
             answers.append(np.asarray(ans))
         return np.concatenate(preds), np.concatenate(answers)
 

@@ -331,6 +331,19 @@ int64_t adt_full_rank_ws_bytes(int B, int n_items, int K, int splits);
 int adt_full_rank(const float* F, int ldf, const float* E, int lde, const float* bias, int B, int d, int n_items,
                   const int32_t* target, const int32_t* indptr, const int32_t* indices, int K, int splits, void* ws,
                   int64_t ws_bytes, int32_t* rank, int32_t* n_elig, int32_t* top_idx, float* top_val, void* stream);
+/* adt_full_rank with the smallest competing id as an argument: first_id = 1 is adt_full_rank, bit for bit; first_id = 0 lets item 0 (the
+ * padding row) compete like any other item -- ranked, counted in rank / n_elig, selected, excluded where the seen list names it --
+ * which is what the reference's STOSA full sort does.  Targets stay 1..n_items (0 = no target).  Any other first_id is an error. */
+int adt_full_rank_from(const float* F, int ldf, const float* E, int lde, const float* bias, int B, int d, int n_items, int first_id,
+                       const int32_t* target, const int32_t* indptr, const int32_t* indices, int K, int splits, void* ws,
+                       int64_t ws_bytes, int32_t* rank, int32_t* n_elig, int32_t* top_idx, float* top_val, void* stream);
+/* Row images for Wasserstein full-catalogue ranking (adt_wdist_pack.cuh): dist[b][j] = na[b] + nb[j] - 2 A[b] . W[j] with the 2d-wide
+ * rows A[b] = [sm | sqrt sc], W[j] = [em | sqrt ec], so ascending distance is descending A[b] . W[j] - nb[j] / 2 = adt_full_rank's score.
+ * Per row r: img[r][0..d) = M[r], img[r][d..2d) = sqrt(max(c, 1e-24)), nrm[r] = nrm_scale * (sum M[r]^2 + sum c), with
+ * c = elu ? ELU(C[r]) + 1 : C[r].  Items: elu = 1, nrm_scale = -0.5 (nrm is the bias); user states: elu = 0, nrm_scale = 1 (nrm is na).
+ * d % 4 == 0, ld >= d, ldi >= 2d, both multiples of 4, M / C / img 16-byte aligned.  Bit-reproducible (fixed reduction order). */
+int adt_wdist_pack(const float* M, const float* C, int ld, int rows, int d, int elu, float* img, int ldi, float* nrm, float nrm_scale,
+                   void* stream);
 
 /* ==== model-level executor: SASRecADT (sasrec/model.py:8-97) + loop body (sasrec/main.py:146-173) ====== */
 typedef struct adt_sasrec_cfg {

@@ -4,7 +4,14 @@ kernel (adt_score_rank without candidates: a (B, V + 1) fp32 matrix in HBM), neg
   python tools/bench_fullrank.py [--out profiles/r07_fullrank_bench.jsonl]
 
 HIP-event timing: 3 warm-up calls, then 5 timed repetitions per form; the median and the spread (min .. max) are reported, one JSON
-line per shape (ml-1m: V 3,416, d 64; ml-20m: V 26,744, d 256; B 512, K 10, 100 seen items per user; the fused call also with 1,000 and with none)."""
+line per shape (ml-1m: V 3,416, d 64; ml-20m: V 26,744, d 256; B 512, K 10, 100 seen items per user; the fused call also with 1,000 and with none).
+
+  python tools/bench_fullrank.py --stosa [--out profiles/r08_stosa_fullrank.jsonl]
+
+STOSA-ADT (Wasserstein) at the Beauty shape: item_size 12,103, d 64 (image width 128), B 512 (stosa/main.py's eval_batch_size; the
+template does not override it), K 40, 100 seen items per user, item 0 competing (first_id = 0, as full_sort(fused=True) runs it).
+Same timing scheme; one JSON line for one model (P = 1) and one for P = 8 stacked candidates: (a) two_pass = adt_wdist_full +
+adt_topk_masked, (b) fused = the user-state pack + adt_full_rank_from with a pre-packed item image, (c) pack = the item pack alone."""
 import argparse
 import json
 import os
@@ -35,13 +42,52 @@ def timed(fn):
     return {"median_ms": float(np.median(ms)), "min_ms": float(min(ms)), "max_ms": float(max(ms))}
 
 
+def stosa_lines(dev):
+    V, d, K = 12103, 64, 40
+    lines = []
+    for P in (1, 8):
+        rows = P * B
+        g = torch.Generator(device="cpu").manual_seed(V + P)
+        Em, Ec = (0.5 * torch.randn(V, d, generator=g)).to(dev), torch.randn(V, d, generator=g).to(dev)
+        sm, sc = torch.randn(rows, d, generator=g).to(dev), (0.05 + 2.0 * torch.rand(rows, d, generator=g)).to(dev)
+        r = np.random.RandomState(V + P)
+        indptr = torch.arange(0, (rows + 1) * SEEN, SEEN, dtype=torch.int32, device=dev)
+        indices = torch.from_numpy(r.randint(0, V, rows * SEEN).astype(np.int32)).to(dev)
+        image = ops.wdist_pack(Em, Ec, True, -0.5)
+
+        def fused():
+            A, na = ops.wdist_pack(sm, sc, False, 1.0)
+            return ops.full_rank(A, 2 * d, image[0], V - 1, None, image[1], indptr, indices, K, first_id=0)
+
+        def two_pass():
+            return ops.topk_masked(ops.wdist_full(sm, sc, Em, Ec, V), K, indptr, indices, want_val=True)
+
+        ti = fused()[2].cpu().numpy()
+        tp = two_pass()[0].cpu().numpy()
+        same = float(np.mean([len(set(ti[b]) & set(tp[b])) for b in range(rows)])) / K
+        tables, dist = 2 * V * d * 4, rows * V * 4
+        rec = {"shape": "stosa-beauty", "V": V, "d": d, "B": B, "candidates": P, "K": K, "seen_per_user": SEEN, "first_id": 0,
+               "two_pass": timed(two_pass), "fused": timed(fused), "pack": timed(lambda: ops.wdist_pack(Em, Ec, True, -0.5)),
+               "topk_overlap": same,
+               "hbm_bytes_fused": V * (2 * d + 1) * 4 + 3 * rows * 2 * d * 4,     # the image and bias; the states read, their image written and read
+               "hbm_bytes_pack": tables + V * (2 * d + 1) * 4,
+               "hbm_bytes_two_pass": tables + rows * 2 * d * 4 + 2 * dist}      # + the distance matrix written, then read by the selection
+        rec["fused_over_two_pass"] = rec["fused"]["median_ms"] / rec["two_pass"]["median_ms"]
+        print(json.dumps(rec), flush=True)
+        lines.append(json.dumps(rec))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "r07_fullrank_bench.jsonl"))
+    ap.add_argument("--stosa", action="store_true", help="the STOSA-ADT (Wasserstein) Beauty shape instead of the dot-product shapes")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join("profiles", "r08_stosa_fullrank.jsonl" if args.stosa else "r07_fullrank_bench.jsonl")
     dev = "cuda:0"
-    lines = []
-    for name, V, d in SHAPES:
+    lines = stosa_lines(dev) if args.stosa else []
+    for name, V, d in (() if args.stosa else SHAPES):
         g = torch.Generator(device="cpu").manual_seed(V)
         F = torch.randn(B, d, generator=g).to(dev)
         E = torch.randn(V + 1, d, generator=g).to(dev)
