@@ -36,6 +36,10 @@ class DecLayerPtrs(ctypes.Structure):
 
 _EP, _DP = ctypes.POINTER(EncLayerPtrs), ctypes.POINTER(DecLayerPtrs)
 
+# the `training` word of adt_sasrec_forward* and the `phase` word of adt_sasrec_backward* (include/adt_hip.h: ADT_TRAIN_*, ADT_PHASE_*)
+TRAIN_DROPOUT, TRAIN_PACKED, TRAIN_BCE_SIDE = 1, 2, 4
+PHASE_MASK, PHASE_PREZEROED, PHASE_DEFER_FOLD, PHASE_BCE_HERE, PHASE_BCE_FWD, PHASE_SEEDS_VIRTUAL = 3, 4, 8, 16, 32, 64
+
 # name -> (restype, argtypes); the single source of truth for symbol coverage (tests/test_capi_symbols.py)
 SIGNATURES = {
     "adt_version": (_I, []),
@@ -150,6 +154,7 @@ SIGNATURES = {
     "adt_sasrec_step_begin": (_I, [_CP, _P, _I, _P, _U, _P, _P, _P, _L, _P, _P]),
     "adt_sasrec_step_begin_ring": (_I, [_CP, _P, _I, _P, _U, _P, _L, _I, _P, _P, _P, _P, _P, _L, _P, _P]),
     "adt_sasrec_backward": (_I, [_CP, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _U, _I, _P]),
+    "adt_sasrec_backward_prefetch": (_I, [_CP, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _U, _I, _P, _L, _I, _P, _P, _P, _P]),
     "adt_sasrec_predict": (_I, [_CP, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
 }
 

@@ -272,25 +272,23 @@ int adt_logits_bce_scatter_ex(const float* F, const float* E, const int32_t* pos
   return adt_check_launch("logits_bce_scatter");
 }
 
-// adt_loss_seeds_split_prefetch(): the NEXT adt_loss_seeds_prefetch of this host thread copies only the first half of the ring slot and leaves the
-// second half (+ the staged mark) to the next adt_embed_bwd3 launch of this thread (same step, later in the stream).
-static thread_local RingPrefetchArgs g_pf_job;
-static thread_local bool g_pf_set = false, g_pf_split = false;
-void adt_loss_seeds_split_prefetch() { g_pf_split = true; g_pf_set = false; }
-
 /* The encoder embedding gradient, the decoder embedding gradient and the positive-logit rows into the item-table replicas in one pass (d = 64,
  * T a multiple of L): one atomic row-add per token where the three ids are the shifts of one item list that the reference's sampler produces
  * (seq[b, l] == dec[b, l + 1] == pos[b, l - 1]); any other ids are added on their own.  dP += the positional sums of both embeddings. */
 int adt_embed_bwd3(const int32_t* seq, const int32_t* dec, const int32_t* pos, const float* dXs, const float* dXd, const float* F, const float* dpos,
                    int T, int L, float p, const uint32_t* seed, uint32_t site_seq, uint32_t site_dec, uint32_t row_offset, float* dP, float* rep,
                    int nrep, int64_t rep_stride, void* stream) {
+  return adt_embed_bwd3_prefetch(seq, dec, pos, dXs, dXd, F, dpos, T, L, p, seed, site_seq, site_dec, row_offset, dP, rep, nrep, rep_stride, nullptr, stream);
+}
+int adt_embed_bwd3_prefetch(const int32_t* seq, const int32_t* dec, const int32_t* pos, const float* dXs, const float* dXd, const float* F,
+                            const float* dpos, int T, int L, float p, const uint32_t* seed, uint32_t site_seq, uint32_t site_dec, uint32_t row_offset,
+                            float* dP, float* rep, int nrep, int64_t rep_stride, const RingPrefetchArgs* pf, void* stream) {
   if (L < 1 || T % L) return adt_set_error("embed_bwd3: T %d is not a multiple of L %d", T, L);
   const int B = T / L, ns = B < 32 ? B : 32;
   EmbedBwd3Args a{seq, dec, pos, dXs, dXd, F, dpos, T, L, 8.0f, adt_make_drop(p, seed, site_seq), adt_make_drop(p, seed, site_dec), row_offset, dP, rep, nrep,
                   (size_t)rep_stride, ns};
-  if (g_pf_set) {      // the second half of this step's ring prefetch (adt_loss_seeds_split_prefetch)
-    g_pf_set = false;
-    hipLaunchKernelGGL(k_embed_bwd3_prefetch, dim3((L * ns + 3) / 4 + 16), dim3(256), 0, (hipStream_t)stream, a, g_pf_job, 16);
+  if (pf) {      // the second half of this step's ring prefetch (AdtLossSeedsJob::split)
+    hipLaunchKernelGGL(k_embed_bwd3_prefetch, dim3((L * ns + 3) / 4 + 16), dim3(256), 0, (hipStream_t)stream, a, *pf, 16);
   } else {
     hipLaunchKernelGGL(k_embed_bwd3, dim3((L * ns + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
   }
@@ -556,45 +554,29 @@ int adt_loss_seeds(const float* pos_logits, const float* neg_logits, const int32
                    float* loss_bce, int nmse, const float* const* A, const float* const* Bm, int64_t n, const float* lambdas, float* const* GA,
                    int accumulate_a, float* const* GB, float* const* loss_mse, int nnll, const float* const* rec, int n_rows, int H, float lambda2,
                    float* const* drec, float* const* loss_nll, void* stream) {
-  return adt_loss_seeds_prefetch(pos_logits, neg_logits, pos, T, norms, dpos, dneg, loss_bce, nmse, A, Bm, n, lambdas, GA, accumulate_a, GB, loss_mse, nnll,
-                                 rec, n_rows, H, lambda2, drec, loss_nll, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, stream);
-}
-// The logits / BCE / item-row pass of the deferred path (adt_logits_bce_scatter) as the first workgroups of the NEXT adt_loss_seeds_prefetch launch of
-// this host thread (one launch, no second stream: adt_sasrec.hip, forward_loss_lean).
-static thread_local LogitsBceArgs g_lb_job;
-static thread_local bool g_lb_set = false;
-void adt_loss_seeds_attach_logits(const float* F, const float* E, const int32_t* pos, const int32_t* neg, const float* norms, int T, float* pos_logits,
-                                  float* neg_logits, float* dpos, float* dneg, float* loss_bce, float* dF, float* rep, int nrep, int64_t rep_stride,
-                                  int neg_only) {
-  g_lb_job = LogitsBceArgs{F, E, pos, neg, norms, T, pos_logits, neg_logits, dpos, dneg, loss_bce, dF, rep, nrep, (size_t)rep_stride, neg_only};
-  g_lb_set = true;
+  return adt_loss_seeds_prefetch(AdtLossSeedsJob{pos_logits, neg_logits, pos, T, norms, dpos, dneg, loss_bce, nmse, A, Bm, n, lambdas, GA, accumulate_a, GB,
+                                                 loss_mse, nnll, rec, n_rows, H, lambda2, drec, loss_nll, nullptr, nullptr, false}, stream);
 }
 
-int adt_loss_seeds_prefetch(const float* pos_logits, const float* neg_logits, const int32_t* pos, int T, const float* norms, float* dpos, float* dneg,
-                            float* loss_bce, int nmse, const float* const* A, const float* const* Bm, int64_t n, const float* lambdas, float* const* GA,
-                            int accumulate_a, float* const* GB, float* const* loss_mse, int nnll, const float* const* rec, int n_rows, int H, float lambda2,
-                            float* const* drec, float* const* loss_nll, const int32_t* ring, int64_t slot_ints, int nslots, int64_t n_ints,
-                            uint32_t* state, uint32_t* consumed, int32_t* staging, void* stream) {
-  if (nmse > 4 || nnll > 4 || n % 4) return adt_set_error("loss_seeds: at most 4 + 4 terms, n %% 4");
+int adt_loss_seeds_prefetch(const AdtLossSeedsJob& j, void* stream) {
+  if (j.nmse > 4 || j.nnll > 4 || j.n % 4) return adt_set_error("loss_seeds: at most 4 + 4 terms, n %% 4");
   LossSeedsArgs a{};
-  if (ring && staging && state) {
-    a.pf = RingPrefetchArgs{ring, (size_t)slot_ints, nslots, (size_t)n_ints, state, consumed, staging, 0, g_pf_split ? 2 : 0};
+  if (j.ring && j.ring->ring && j.ring->staging && j.ring->state) {
+    a.pf = *j.ring; a.pf.part = 0; a.pf.nparts = j.split ? 2 : 0;
     a.gp = 32;      // one round of 8 x 16-byte loads per thread covers the flagship batch (819 KB): a PCIe read wants everything in flight at once
-    if (g_pf_split) {      // ... its second half rides on the next adt_embed_bwd3 launch of this host thread
-      g_pf_job = a.pf; g_pf_job.part = 1; g_pf_set = true; g_pf_split = false;
-    }
   }
-  a.bce = BceArgs{pos_logits, neg_logits, pos, T, norms, dpos, dneg, loss_bce};
+  a.bce = BceArgs{j.pos_logits, j.neg_logits, j.pos, j.T, j.norms, j.dpos, j.dneg, j.loss_bce};
   // (a seed that is not materialised -- GA[i] or GB[i] == nullptr -- leaves its coefficient at norms[8 + i] for its consumer)
-  for (int i = 0; i < nmse; ++i)
-    a.mse[i] = MseArgs{A[i], Bm[i], (size_t)n, lambdas[i], norms, GA[i], accumulate_a, GB[i], loss_mse[i], (!GA[i] || !GB[i]) ? const_cast<float*>(norms) + 8 + i : nullptr};
-  for (int i = 0; i < nnll; ++i) a.nll[i] = NllArgs{rec[i], n_rows, H, lambda2, norms, drec[i], loss_nll[i]};
-  a.nmse = nmse; a.nnll = nnll;
-  if (g_lb_set) { a.lb = g_lb_job; a.gl = adt_grid_for(a.lb.T, 4 * 16, 1024); g_lb_set = false; }
-  a.gb = pos_logits ? adt_grid_for(T, 256, 256) : 0;      // no logits: the BCE seed is formed elsewhere (adt_logits_bce_scatter)
-  a.gm = nmse ? adt_grid_for((size_t)n / 4, 256, 512) : 1;
-  a.gn = nnll ? adt_grid_for((size_t)n_rows * H * H, 256, 512) : 1;
-  hipLaunchKernelGGL(k_loss_seeds, dim3(a.gl + a.gb + nmse * a.gm + nnll * a.gn + a.gp), dim3(256), 0, (hipStream_t)stream, a);
+  for (int i = 0; i < j.nmse; ++i)
+    a.mse[i] = MseArgs{j.A[i], j.Bm[i], (size_t)j.n, j.lambdas[i], j.norms, j.GA[i], j.accumulate_a, j.GB[i], j.loss_mse[i],
+                       (!j.GA[i] || !j.GB[i]) ? const_cast<float*>(j.norms) + 8 + i : nullptr};
+  for (int i = 0; i < j.nnll; ++i) a.nll[i] = NllArgs{j.rec[i], j.n_rows, j.H, j.lambda2, j.norms, j.drec[i], j.loss_nll[i]};
+  a.nmse = j.nmse; a.nnll = j.nnll;
+  if (j.logits) { a.lb = *j.logits; a.gl = adt_grid_for(a.lb.T, 4 * 16, 1024); }
+  a.gb = j.pos_logits ? adt_grid_for(j.T, 256, 256) : 0;      // no logits: the BCE seed is formed elsewhere (adt_logits_bce_scatter)
+  a.gm = j.nmse ? adt_grid_for((size_t)j.n / 4, 256, 512) : 1;
+  a.gn = j.nnll ? adt_grid_for((size_t)j.n_rows * j.H * j.H, 256, 512) : 1;
+  hipLaunchKernelGGL(k_loss_seeds, dim3(a.gl + a.gb + j.nmse * a.gm + j.nnll * a.gn + a.gp), dim3(256), 0, (hipStream_t)stream, a);
   return adt_check_launch("loss_seeds");
 }
 

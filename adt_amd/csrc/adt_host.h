@@ -8,6 +8,7 @@
 
 #include "../../include/adt_hip.h"
 #include "adt_common.cuh"
+#include "adt_lossring_args.h"
 
 int adt_set_error(const char* fmt, ...);
 DropCfg adt_make_drop(float p, const uint32_t* seed, uint32_t site);
@@ -103,19 +104,9 @@ int adt_step_begin_ring_launch(uint32_t* seed, uint32_t inc, float* norms_dst, f
                                int64_t nE, const int32_t* ring, int64_t slot_ints, int nslots, int32_t* ids_dst, int64_t n_ints, uint32_t* state,
                                uint32_t* consumed, const int32_t* staging, const uint32_t* produced, float* Z, int64_t nz, const float* pack_base,
                                void* pack_img, const int* pack_offs, int npack, void* stream);
-// adt_loss_seeds + the prefetch of the next step's id batch into `staging` as extra workgroups of the same launch (adt_misc.cuh: ring_prefetch_body)
-void adt_loss_seeds_split_prefetch();
-void adt_loss_seeds_attach_logits(const float* F, const float* E, const int32_t* pos, const int32_t* neg, const float* norms, int T, float* pos_logits,
-                                  float* neg_logits, float* dpos, float* dneg, float* loss_bce, float* dF, float* rep, int nrep, int64_t rep_stride,
-                                  int neg_only);
 int adt_logits_bce_scatter_ex(const float* F, const float* E, const int32_t* pos, const int32_t* neg, const float* norms, int T, float* pos_logits,
                               float* neg_logits, float* dpos, float* dneg, float* loss_bce, float* dF, float* rep, int nrep, int64_t rep_stride,
                               int neg_only, void* stream);
-int adt_loss_seeds_prefetch(const float* pos_logits, const float* neg_logits, const int32_t* pos, int T, const float* norms, float* dpos, float* dneg,
-                            float* loss_bce, int nmse, const float* const* A, const float* const* Bm, int64_t n, const float* lambdas, float* const* GA,
-                            int accumulate_a, float* const* GB, float* const* loss_mse, int nnll, const float* const* rec, int n_rows, int H, float lambda2,
-                            float* const* drec, float* const* loss_nll, const int32_t* ring, int64_t slot_ints, int nslots, int64_t n_ints,
-                            uint32_t* state, uint32_t* consumed, int32_t* staging, void* stream);
 int adt_loss_seeds(const float* pos_logits, const float* neg_logits, const int32_t* pos, int T, const float* norms, float* dpos, float* dneg,
                    float* loss_bce, int nmse, const float* const* A, const float* const* Bm, int64_t n, const float* lambdas, float* const* GA,
                    int accumulate_a, float* const* GB, float* const* loss_mse, int nnll, const float* const* rec, int n_rows, int H, float lambda2,
@@ -136,4 +127,24 @@ int adt_fold_parts(float* P, float* G, int64_t n, float* d0, const float* r0, in
                    void* stream);
 int adt_layernorm_bwd_parts(const float* dY, int lddy, const float* X, int ldx, const float* gamma, float eps, int T, int d, float* dX, int lddx,
                             int accumulate, float* part, int max_blocks, void* stream);
+}
+
+// One loss-assembly launch (adt_misc.cuh: k_loss_seeds) with everything that can ride on it.  nmse, nnll <= 4; pos_logits == nullptr: no BCE
+// block (the seed is formed by the logits pass).  logits: that pass as the first workgroups of this launch.  ring (its part / nparts are set
+// here): the next step's id batch is copied into ring->staging by extra workgroups -- with `split` only its first half, the second half and the
+// staged mark being left to adt_embed_bwd3_prefetch of the same step, later in the stream.
+struct AdtLossSeedsJob {
+  const float* pos_logits; const float* neg_logits; const int32_t* pos; int T; const float* norms; float* dpos; float* dneg; float* loss_bce;
+  int nmse; const float* const* A; const float* const* Bm; int64_t n; const float* lambdas; float* const* GA; int accumulate_a; float* const* GB;
+  float* const* loss_mse;
+  int nnll; const float* const* rec; int n_rows; int H; float lambda2; float* const* drec; float* const* loss_nll;
+  const adt::LogitsBceArgs* logits; const adt::RingPrefetchArgs* ring; bool split;
+};
+extern "C" {
+ADT_HIDDEN int adt_loss_seeds_prefetch(const AdtLossSeedsJob& job, void* stream);
+// adt_embed_bwd3 (include/adt_hip.h) with the second half of a split ring prefetch as extra workgroups of its launch ; pf == nullptr: adt_embed_bwd3
+ADT_HIDDEN int adt_embed_bwd3_prefetch(const int32_t* seq, const int32_t* dec, const int32_t* pos, const float* dXs, const float* dXd, const float* F,
+                                       const float* dpos, int T, int L, float p, const uint32_t* seed, uint32_t site_seq, uint32_t site_dec,
+                                       uint32_t row_offset, float* dP, float* rep, int nrep, int64_t rep_stride, const adt::RingPrefetchArgs* pf,
+                                       void* stream);
 }

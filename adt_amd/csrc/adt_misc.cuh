@@ -2,6 +2,7 @@
 // clip + Adam.  HBM-bound integer/elementwise work: coalesced float4 accesses, no MFMA.
 #pragma once
 #include "adt_common.cuh"
+#include "adt_lossring_args.h"
 #include "adt_wave.cuh"
 
 namespace adt {
@@ -336,12 +337,7 @@ __global__ __launch_bounds__(256) void k_logits_bwd_scatter(LogitsScatterArgs a)
 // over the positions with pos != 0 and its derivatives (sasrec/main.py:151-153; bce_body above), then dF and the item rows as in
 // k_logits_bwd_scatter.  The rows E[pos], E[neg] and f are gathered by this kernel anyway, so the forward needs no logits kernel and the
 // loss assembly no BCE pass.  One wave per token row, lane = feature; the two dot products are wave sums.
-struct LogitsBceArgs {
-  const float* F; const float* E; const int* pos; const int* neg; const float* norms; int T;
-  float* pos_logits; float* neg_logits; float* dpos; float* dneg; float* loss;      // loss: 2 x 64 sub-slots (pos term, neg term)
-  float* dF; float* rep; int nrep; size_t rep_stride;
-  int neg_only;              // the item rows of the NEGATIVE ids only: the positive ones are added by k_embed_bwd3 with the embedding rows they share
-};
+// (LogitsBceArgs: adt_lossring_args.h)
 ADT_DEVICE_INLINE void logits_bce_body(const LogitsBceArgs& a, const int bid, const int nblk) {
   const int lane = threadIdx.x & 63;
   const int wave = bid * 4 + (threadIdx.x >> 6), nwaves = nblk * 4;
@@ -672,12 +668,7 @@ __global__ __launch_bounds__(256) void k_nll_seed(NllArgs a) {
 // k_step_begin of the next step then copies the batch HBM -> HBM.  Not published yet: nothing happens, the next step reads the ring itself.
 // state: [0] batches fetched, [1] k_step_begin's ticket, [2] staged batch + 1, [3] the prefetch ticket, [4] *produced as k_step_begin saw it,
 // [5] statistics: batches k_step_begin took from the staging buffer.
-struct RingPrefetchArgs {
-  const int32_t* ring; size_t slot_ints; int nslots; size_t n_ints; uint32_t* state; uint32_t* consumed; int32_t* staging;
-  int part, nparts;      // this launch copies 16-byte words [part, part + 1) * n / nparts of the slot; the LAST part marks the batch staged and releases the
-                         // slot (the parts run in stream order).  0, 0 = the whole slot.  819 KB over PCIe took 34-39 us inside the 24 us loss launch:
-                         // half there, half inside the 20 us embedding scatter is hidden in both.
-};
+// (RingPrefetchArgs: adt_lossring_args.h)
 ADT_DEVICE_INLINE void ring_prefetch_body(const RingPrefetchArgs& a, int bid, int nblk) {
   typedef int v4i __attribute__((ext_vector_type(4)));
   const uint32_t k = a.state[0];                      // index of the next batch (this step's k_step_begin has counted its own)

@@ -6,6 +6,7 @@
 #include "adt_host.h"
 #include <string.h>
 #include <mutex>
+#include "adt_bwd_plan.h"
 #include "adt_bwdchain_args.h"
 #include "adt_fwdchain_args.h"
 #include "adt_seq_args.h"
@@ -218,6 +219,13 @@ int check_cfg(const adt_sasrec_cfg* c) {
   if (hd != 16 && hd != 32 && hd != 64) return adt_set_error("sasrec: head_dim=%d unsupported (16/32/64)", hd);
   if (c->maxlen > 224) return adt_set_error("sasrec: maxlen=%d > 224 unsupported", c->maxlen);
   if (c->num_layers < 1 || c->num_layers > 16) return adt_set_error("sasrec: num_layers");
+  return 0;
+}
+// what every entry point starts with: the configuration checked, the parameter layout and the workspace carve-up for B sequences
+int layout_ws(const adt_sasrec_cfg* c, int B, Layout* lo, WS* w) {
+  CK(check_cfg(c));
+  make_layout(c, lo);
+  make_ws(c, B, w);
   return 0;
 }
 
@@ -469,62 +477,537 @@ bool embed3_on(const WS& w) {
   static const int on = adt_env_on("ADT_EMBED3");
   return on != 0 && !item_det(w) && w.d == 64;
 }
-// ADT_BCE_MERGED=0: the forward's logits / BCE kernel (training bit 2) goes to the side stream instead of into the loss launch
+// ADT_BCE_MERGED=0: the forward's logits / BCE kernel (ADT_TRAIN_BCE_SIDE) goes to the side stream instead of into the loss launch
 bool bce_merged() {
   static const int on = adt_env_on("ADT_BCE_MERGED");
   return on != 0;
 }
-struct RingRef { const int32_t* ring; int64_t slot_ints; int nslots; uint32_t* state; uint32_t* consumed; int32_t* staging; };
-// bce_side (training bit 2 of adt_sasrec_forward_loss*): the logits + BCE + item-row scatter kernel of the deferred path is launched HERE, on
-// the library's side stream beside the streaming loss pass (both are memory passes; under the backward's first chain kernels it stretched the
-// latency-bound cross-attention backward by about its own duration), and joined by adt_sasrec_backward(phase bit 5) in front of the first
-// kernel that reads d log_feats.  The item-table replicas are zero: adt_sasrec_step_begin* of this step.
+// the stream the forward's logits kernel runs on when it is not merged into the loss launch (nullptr: the caller's), and whose join_ev[0] the backward waits for
+SideStream* fwd_logits_stream(void* st) { return ((side_sites() & 1) && !bce_merged()) ? side_stream((hipStream_t)st) : nullptr; }
+// same step, same ring arguments: the forward's loss launch copies the first half of the next batch's ring slot exactly when the backward's
+// embedding scatter copies the second (and then marks the batch staged) -- 819 KB over PCIe do not fit behind either launch alone
+bool ring_prefetch_split(const adt::RingPrefetchArgs& rr, bool bce_by_forward, const WS& w) {
+  return rr.ring && rr.staging && rr.state && bce_by_forward && embed3_on(w);
+}
+
+// Pointer arrays of the loss launch (AdtLossSeedsJob) and its reconstruction / independence terms: pair i = (enc_in[i], dec_out_rev[i] = DEC_X[nl - i])
+// (sasrec/main.py:155-158), independence term i = encoder layer i with the stale loop index lambdas2[nl - 1] (sasrec/main.py:169).
+// all_seeds = false: only the reconstruction seed the backward's FIRST kernels read as a plain input (d / d decoder output) is written.  The others
+// were written to be added to the input gradient of a block that re-reads that very input: k_seqtt_attn_pre_bwd forms them from its own x
+// rows and the other stack's rows (SeqBwdArgs::seed_other) -- 39 MB of stores here and as many loads there less per step.
+struct LossPtrs { const float *A[4], *Bm[4], *rc[4]; float *GA[4], *GB[4], *lm[4], *dr[4], *ln[4]; };
+AdtLossSeedsJob loss_terms(const WS& w, float* ws, const float* lambdas1, const float* lambdas2, bool all_seeds, LossPtrs* q) {
+  const int nl = (int)w.nl, H = (int)w.H;
+  const int64_t Td = up64(w.T * w.d), rec = up64(w.T * w.H * w.H);
+  float* loss = ws + w.loss;
+  for (int i = 0; i < nl; ++i) {
+    q->A[i] = ws + w.enc_x + i * Td; q->Bm[i] = ws + w.dec_x + (nl - i) * Td;
+    q->GA[i] = all_seeds ? ws + w.g_enc_x + i * Td : nullptr;
+    q->GB[i] = (all_seeds || i == 0) ? ws + w.g_dec_x + (nl - i) * Td : nullptr;      // (i >= 1: not even read -- the encoder block's backward adds the loss term)
+    q->lm[i] = loss + 64 * (2 + i);
+    q->rc[i] = ws + i * w.e_stride + w.e_rec; q->dr[i] = ws + w.g_rec + i * rec; q->ln[i] = loss + 64 * (2 + nl + i);
+  }
+  AdtLossSeedsJob j{};
+  j.T = (int)w.T; j.norms = ws + w.norms; j.loss_bce = loss;
+  j.nmse = nl; j.A = q->A; j.Bm = q->Bm; j.n = w.T * w.d; j.lambdas = lambdas1; j.GA = q->GA; j.GB = q->GB; j.loss_mse = q->lm;
+  j.nnll = H > 1 ? nl : 0; j.rec = q->rc; j.n_rows = (int)w.T; j.H = H; j.lambda2 = lambdas2[nl - 1]; j.drec = q->dr; j.loss_nll = q->ln;
+  return j;
+}
+
+// bce_side (ADT_TRAIN_BCE_SIDE of adt_sasrec_forward_loss*): the logits + BCE + item-row scatter kernel of the deferred path is launched HERE, as the
+// first workgroups of the loss launch or (ADT_BCE_MERGED=0) on the library's side stream beside it (both are memory passes; under the backward's
+// first chain kernels it stretched the latency-bound cross-attention backward by about its own duration), and joined by
+// adt_sasrec_backward(ADT_PHASE_BCE_FWD) in front of the first kernel that reads d log_feats.  The item-table replicas are zero:
+// adt_sasrec_step_begin* of this step.
 int forward_loss_lean(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, const float* P, float* ws, const int32_t* seq, const int32_t* dec,
                       const int32_t* pos, const int32_t* neg, bool bce_side, float p, const uint32_t* seed, uint32_t b_offset, const float* lambdas1,
-                      const float* lambdas2, const RingRef& rr, void* st) {
-  const int d = (int)w.d, H = (int)w.H, hd = d / H, nl = c->num_layers, T = (int)w.T;
+                      const float* lambdas2, const adt::RingPrefetchArgs& rr, void* st) {
+  const int hd = (int)(w.d / w.H), nl = c->num_layers;
   if (!bce_deferred(c)) return 1;
-  const int64_t Td = up64(w.T * w.d), rec = up64(w.T * w.H * w.H);
   for (int i = 0; i < nl; ++i) {
     adt::SeqFwdArgs a = enc_layer_seq_args(c, lo, w, P, ws, seq, p, seed, b_offset, i, true, true);
     if (i == nl - 1) { a.lnl_gamma = P + lo.lnl_w(); a.lnl_beta = P + lo.lnl_b(); a.f_out = ws + w.f; }
     CK(adt_launch_seq_enc_fwd(hd, a, st));
   }
   for (int j = 0; j < nl; ++j) CK(dec_layer_seq_fwd(c, lo, w, P, ws, dec, p, seed, b_offset, j, st));
-  // reconstruction + independence seeds in one launch (the BCE block is the backward's: no logits yet)
-  float* loss = ws + w.loss;
-  const float *A[4], *Bm[4], *rc[4];
-  float *GA[4], *GB[4], *lm[4], *dr[4], *ln[4];
-  // Reconstruction seeds: only the one the backward's FIRST kernels read as a plain input (d / d decoder output) is written here.  The others
-  // were written to be added to the input gradient of a block that re-reads that very input: k_seqtt_attn_pre_bwd forms them from its own x
-  // rows and the other stack's rows (SeqBwdArgs::seed_other) -- 39 MB of stores here and as many loads there less per step.
-  for (int i = 0; i < nl; ++i) {
-    A[i] = ws + w.enc_x + i * Td; Bm[i] = ws + w.dec_x + (nl - i) * Td;
-    GA[i] = nullptr; GB[i] = i == 0 ? ws + w.g_dec_x + (nl - i) * Td : nullptr;      // (i >= 1: not even read here -- the encoder block's backward adds the loss term)
-    lm[i] = loss + 64 * (2 + i);
-    rc[i] = ws + i * w.e_stride + w.e_rec; dr[i] = ws + w.g_rec + i * rec; ln[i] = loss + 64 * (2 + nl + i);
-  }
-  // host-fed step: the next batch's ring slot is copied to the staging buffer in two halves, one inside this launch, one inside the embedding
-  // scatter at the end of the backward (which then marks it staged) -- 819 KB over PCIe do not fit behind either launch alone
-  if (rr.ring && rr.staging && rr.state && bce_side && embed3_on(w)) adt_loss_seeds_split_prefetch();
-  const bool merged = bce_side && bce_merged();
-  if (merged)      // ... as the first workgroups of the loss launch itself: no second stream, no fork / join
-    adt_loss_seeds_attach_logits(ws + w.f, P + lo.item(), pos, neg, ws + w.norms, T, ws + w.posl, ws + w.negl, ws + w.g_pos, ws + w.g_neg, ws + w.loss,
-                                 ws + w.g_f, item_det(w) ? nullptr : ws + w.rep, NREP, w.rep_stride, embed3_on(w) ? 1 : 0);
-  SideStream* const sd = (bce_side && !merged && (side_sites() & 1)) ? side_stream((hipStream_t)st) : nullptr;
-  if (bce_side && !merged) CK(side_mark(sd, 0, st));
+  // reconstruction + independence seeds in one launch (no BCE block: no logits yet)
+  LossPtrs q;
+  AdtLossSeedsJob job = loss_terms(w, ws, lambdas1, lambdas2, false, &q);
   // (+ the next step's id batch, if its producer has published it: the PCIe read runs under this streaming pass)
-  CK(adt_loss_seeds_prefetch(nullptr, nullptr, nullptr, 0, ws + w.norms, nullptr, nullptr, loss, nl, A, Bm, w.T * w.d, lambdas1, GA, 0, GB, lm,
-                             H > 1 ? nl : 0, rc, T, H, lambdas2[nl - 1], dr, ln, rr.ring, rr.slot_ints, rr.nslots, 4 * (int64_t)w.T + 4, rr.state,
-                             rr.consumed, rr.staging, st));
+  job.ring = &rr; job.split = ring_prefetch_split(rr, bce_side, w);
+  const adt::LogitsBceArgs lb{ws + w.f, P + lo.item(), pos, neg, ws + w.norms, (int)w.T, ws + w.posl, ws + w.negl, ws + w.g_pos, ws + w.g_neg, ws + w.loss,
+                              ws + w.g_f, item_det(w) ? nullptr : ws + w.rep, NREP, (size_t)w.rep_stride, embed3_on(w) ? 1 : 0};
+  const bool merged = bce_side && bce_merged();
+  if (merged) job.logits = &lb;      // ... as the first workgroups of the loss launch itself: no second stream, no fork / join
+  SideStream* const sd = (bce_side && !merged) ? fwd_logits_stream(st) : nullptr;
+  if (bce_side && !merged) CK(side_mark(sd, 0, st));
+  CK(adt_loss_seeds_prefetch(job, st));
   if (bce_side && !merged) {
     void* s2 = nullptr;
     CK(side_enter(sd, 0, st, &s2));
-    CK(adt_logits_bce_scatter_ex(ws + w.f, P + lo.item(), pos, neg, ws + w.norms, T, ws + w.posl, ws + w.negl, ws + w.g_pos, ws + w.g_neg, ws + w.loss,
-                                 ws + w.g_f, item_det(w) ? nullptr : ws + w.rep, NREP, w.rep_stride, embed3_on(w) ? 1 : 0, s2));
+    CK(adt_logits_bce_scatter_ex(lb.F, lb.E, pos, neg, lb.norms, lb.T, lb.pos_logits, lb.neg_logits, lb.dpos, lb.dneg, lb.loss, lb.dF, lb.rep, lb.nrep,
+                                 w.rep_stride, lb.neg_only, s2));
     if (sd && hipEventRecord(sd->join_ev[0], sd->s) != hipSuccess) return adt_set_error("forward_loss: logits event");
   }
   return 0;
+}
+
+// ---- the reverse pass ----------------------------------------------------------------------------------------------------------------
+// Measurement hook (bench.py's roofline probe; not part of include/adt_hip.h): HIP events recorded on the launch stream right before and right
+// after ONE launch inside adt_sasrec_backward -- which = 1: the fused attention-block backward (k_seqtt_attn_pre_bwd) of encoder layer `layer`;
+// which = 2: the same kernel's decoder instantiation for decoder layer `layer`; 3: see time_mark; 0 switches the hook off.
+int g_time_which = 0, g_time_layer = 0;
+hipEvent_t g_time_ev0 = nullptr, g_time_ev1 = nullptr;
+// which = 3: calibration -- BOTH events in front of the launch of which = 1 (nothing between them): what an event pair itself adds to an interval
+inline void time_mark(int which, int layer, bool start, void* st) {
+  if (!g_time_ev0 || !g_time_ev1 || g_time_layer != layer) return;
+  if (g_time_which == 3 && which == 1 && start) {
+    (void)hipEventRecord(g_time_ev0, (hipStream_t)st);
+    (void)hipEventRecord(g_time_ev1, (hipStream_t)st);
+  } else if (g_time_which == which) {
+    (void)hipEventRecord(start ? g_time_ev0 : g_time_ev1, (hipStream_t)st);
+  }
+}
+
+const char* const NO_FALLBACK = "backward: shape L=%d hd=%d left the per-sequence kernels although the partial-gradient path was chosen";
+
+// What one adt_sasrec_backward* call works on: built once (bwd_init), read by the functions of the blocks below.
+struct Bwd {
+  const adt_sasrec_cfg* c; Layout lo; WS w;
+  const float* P; float* G; float* ws;
+  const int32_t *seq, *dec, *pos, *neg;
+  float p; const uint32_t* seed; uint32_t b_offset, ro;      // ro: b_offset in token rows
+  void* st;                      // the caller's stream
+  BwdPlan plan;
+  adt::RingPrefetchArgs ring;      // the step's id ring as adt_sasrec_forward_loss_prefetch got it (ring == nullptr: none)
+  int T, d, H, hd, L, prec, nl;
+  int64_t Td, recsz;
+  bool use_seq;                  // the per-sequence kernels cover the shape
+  int lean;                      // what the forward of this step saved (same predicate, same process)
+  bool parts;                    // weight gradients through private per-sequence partials + one ordered sum instead of float atomics (adt_seqbwd_tt.cuh: sb_dw_tiles)
+  bool late_parts;               // adt_sasrec_fold_clip_adam sums those partials, and the bias / LayerNorm / classifier sums the chain kernels then STORE per workgroup
+  bool det;                      // item / positional table gradients by sorted segmented sums (no replicas, no float atomics)
+  bool embed3;                   // encoder / decoder embedding gradients and the positive-logit rows share ONE scatter at the end (adt_embed_bwd3)
+  bool lnl_fused;                // the last LayerNorm is reversed inside the last encoder block's first kernel (k_seqtt_post_bwd<ENC>: BwdChainArgs::lnl_x)
+  // the backward chains flush their weight / bias / LayerNorm gradients into NREPP zeroed replicas of the non-item parameters
+  // (Gq + lo.xxx() addresses replica 0); each phase folds its range into G at its end
+  float* Gq;
+  float *s1, *s3, *s4, *s5, *gf;      // scratch ; d log_feats
+  const float* f;                     // log_feats
+  SideStream *sd, *sd_sort;           // side stream of the scatter / fold kernels ; of the id sort (nullptr: the caller's stream)
+
+  adt::BwdChainArgs BA(const int32_t* ids, float pp, const uint32_t* sdp) const {
+    adt::BwdChainArgs a = bwd_args(T, L, (int)w.B, ids, pp, sdp, ro);
+    a.nrep = NREPP; a.rep_stride = (size_t)w.prep_stride;
+    a.wp_base = P + lo.posw(); a.wp_img = prec == ADT_PREC_BF16 ? (const void*)(ws + w.wpack) : nullptr;   // packed by the forward of this step
+    a.nsplit = seq_split((int)w.B);
+    return a;
+  }
+  float* PART(int layer, int slot) const { return parts ? ws + w.part + (int64_t)(16 * layer + slot) * 4096 : nullptr; }
+  float* VPART(int layer, int k) const { return late_parts ? ws + w.vpart + (int64_t)(5 * layer + k) * w.vcall : nullptr; }
+  // d log_feats + item rows of pos / neg (+ logits and BCE seed on the deferred path)   (sasrec/model.py:72-76)
+  int logits_scatter(void* s) const {
+    if (plan.bce_here)
+      return adt_logits_bce_scatter_ex(f, P + lo.item(), pos, neg, ws + w.norms, T, ws + w.posl, ws + w.negl, ws + w.g_pos, ws + w.g_neg, ws + w.loss,
+                                       gf, det ? nullptr : ws + w.rep, NREP, w.rep_stride, embed3 ? 1 : 0, s);
+    if (det) return adt_logits_bwd_df(P + lo.item(), pos, neg, ws + w.g_pos, ws + w.g_neg, T, d, gf, d, s);
+    return adt_logits_bwd_scatter(f, d, P + lo.item(), pos, neg, ws + w.g_pos, ws + w.g_neg, T, d, gf, d, ws + w.rep, NREP, w.rep_stride, s);
+  }
+  // a replica area that adt_sasrec_step_begin* did not zero for this step
+  int zero_unless_prezeroed(int64_t at, size_t n, void* s) const {
+    return (!plan.prep_zeroed && adt::zero_f32_async(ws + at, n, (hipStream_t)s)) ? adt_set_error("replica zero") : 0;
+  }
+};
+
+int bwd_init(Bwd& x, const adt_sasrec_cfg* c, const float* P, float* G, float* ws, const int32_t* seq, const int32_t* dec, const int32_t* pos,
+             const int32_t* neg, int B, int training, const uint32_t* seed, uint32_t b_offset, int phase, const adt::RingPrefetchArgs& ring, void* st) {
+  CK(layout_ws(c, B, &x.lo, &x.w));
+  if (const char* err = adt_bwd_plan(phase, bce_deferred(c), &x.plan)) return adt_set_error("%s", err);
+  const WS& w = x.w;
+  x.c = c; x.P = P; x.G = G; x.ws = ws; x.seq = seq; x.dec = dec; x.pos = pos; x.neg = neg; x.seed = seed; x.b_offset = b_offset; x.st = st; x.ring = ring;
+  x.T = (int)w.T; x.d = (int)w.d; x.H = (int)w.H; x.hd = x.d / x.H; x.L = (int)w.L; x.prec = c->prec; x.nl = c->num_layers;
+  x.Td = up64(w.T * w.d); x.recsz = up64(w.T * w.H * w.H);
+  x.p = training ? c->dropout : 0.f;
+  x.ro = b_offset * (uint32_t)x.L;
+  x.s1 = ws + w.s1; x.s3 = ws + w.s3; x.s4 = ws + w.s4; x.s5 = ws + w.s5; x.gf = ws + w.g_f; x.f = ws + w.f;
+  x.Gq = ws + w.prep - x.lo.posw();
+  x.use_seq = adt_seq_supported(x.prec, x.L, x.d, x.hd) != 0;
+  x.lean = adt_seq_lean(x.prec, x.L, x.d, x.hd);
+  x.parts = w.part_stride > 0 && adt_seq_partials(x.prec, x.L, x.d, x.hd) != 0;
+  x.late_parts = x.plan.defer_fold && fold_sums_partials(c, w);
+  x.det = item_det(w);
+  x.embed3 = x.plan.seeds_virtual && embed3_on(w);
+  x.lnl_fused = x.parts && x.use_seq && lnl_fuse_on();      // (without the stored sums: float atomics into the replicas, like its other vectors)
+  x.sd_sort = x.det ? side_stream((hipStream_t)st) : nullptr;      // the id sort runs beside the decoder's chain kernels, also in the two-phase form
+  // (one-phase backward by default: the two-phase form belongs to the data-parallel step, whose capture already carries the collectives'
+  // stream; there the side stream measured 0.692 against 0.699 ms on a 1-rank RCCL group and is opt-in: ADT_SIDE_STREAM_DP=1)
+  static const int dp_on = adt_env_int("ADT_SIDE_STREAM_DP", 0) != 0;
+  x.sd = (x.plan.phase == 0 || dp_on) ? side_stream((hipStream_t)st) : nullptr;
+  return 0;
+}
+
+// Where the logits kernel (Bwd::logits_scatter) goes.  Its item-table rows and d log_feats (first read by the reverse of the cross-attention
+// projections) run on the side stream under the first two decoder kernels, which only need the parameter replicas zeroed.
+struct LogitsSide {
+  enum { DONE, MARKED, ENQUEUED, BY_FORWARD } at = DONE;      // MARKED: forked, to be enqueued behind the first chain kernel
+
+  // in front of the decoder stack (item-table replicas and parameter replicas are adjacent in the workspace: one fill)
+  int begin(const Bwd& x) {
+    const WS& w = x.w;
+    if (x.plan.bce_fwd) {      // nothing to launch: the forward put the kernel on the side stream (or, without one, on this stream); joined below
+      at = BY_FORWARD;
+    } else if (x.det) {
+      CK(x.zero_unless_prezeroed(w.prep, (size_t)NREPP * w.prep_stride, x.st));
+      CK(x.logits_scatter(x.st));      // no atomics left in it: a short streaming pass on the caller's stream
+    } else if (x.sd && (side_sites() & 1)) {
+      CK(side_mark(x.sd, 0, x.st));
+      CK(x.zero_unless_prezeroed(w.prep, (size_t)NREPP * w.prep_stride, x.st));
+      at = MARKED;
+    } else {
+      CK(x.zero_unless_prezeroed(w.rep, (size_t)NREP * w.rep_stride + (size_t)NREPP * w.prep_stride, x.st));
+      CK(x.logits_scatter(x.st));
+    }
+    return 0;
+  }
+  int after_first_chain_kernel(const Bwd& x) {
+    if (at != MARKED) return 0;
+    void* s2 = nullptr;
+    CK(side_enter(x.sd, 0, x.st, &s2));
+    CK(x.zero_unless_prezeroed(x.w.rep, (size_t)NREP * x.w.rep_stride, s2));
+    CK(x.logits_scatter(s2));
+    at = ENQUEUED;
+    return 0;
+  }
+  // in front of the first kernel that reads d log_feats: complete from here on
+  int join(const Bwd& x) {
+    if (at == ENQUEUED) CK(side_join(x.sd, 0, x.st));
+    if (at == BY_FORWARD) {
+      SideStream* const sl = fwd_logits_stream(x.st);
+      if (sl && hipStreamWaitEvent((hipStream_t)x.st, sl->join_ev[0], 0) != hipSuccess) return adt_set_error("backward: logits join");
+    }
+    at = DONE;
+    return 0;
+  }
+};
+
+// ---- one decoder block, last kernel first ------------------------------------------------------------------------------------------
+// FFN + mask + enc_attn.out_proj reverse -> dO2 (s1)
+int dec_post_bwd(const Bwd& x, int i) {
+  const WS& w = x.w; const Layout& lo = x.lo; const float* P = x.P; float* const Gq = x.Gq;
+  float* base = x.ws + i * w.d_stride;
+  adt::BwdChainArgs a = x.BA(x.dec, x.p, x.seed);
+  a.site1 = dec_site(i, 2); a.site2 = dec_site(i, 3);
+  a.gy = x.ws + w.g_dec_x + (i + 1) * x.Td; a.u = base + w.d_u; a.xin = base + w.d_a2; a.o = base + w.d_o2; a.saved_bf16 = x.lean;
+  a.W0 = P + lo.dec(i, D_C2W); a.W1 = P + lo.dec(i, D_C1W); a.W2 = P + lo.dec(i, D_EOW);
+  a.dW0 = Gq + lo.dec(i, D_C2W); a.dW1 = Gq + lo.dec(i, D_C1W); a.dW2 = Gq + lo.dec(i, D_EOW);
+  a.db0 = Gq + lo.dec(i, D_C2B); a.db1 = Gq + lo.dec(i, D_C1B); a.db2 = Gq + lo.dec(i, D_EOB);
+  a.out0 = x.s1;
+  a.part[0] = x.PART(i, PS_D_C2); a.part[1] = x.PART(i, PS_D_C1); a.part[2] = x.PART(i, PS_D_EO); a.part_stride = (size_t)w.part_stride;
+  a.vpart = x.VPART(i, 0);
+  const int rc = x.use_seq ? adt_launch_seq_post_bwd(x.hd, 0, a, x.st) : 1;
+  if (rc < 0) return rc;
+  if (rc && x.parts) return adt_set_error(NO_FALLBACK, x.L, x.hd);
+  return rc ? adt_launch_bwdchain(x.prec, 1, a, x.st) : 0;
+}
+
+// cross attention core: dq2 -> s5, dkv2 -> s4
+int dec_cross_attn_bwd(const Bwd& x, int i) {
+  const WS& w = x.w; const int d = x.d, B = (int)w.B;
+  float* base = x.ws + i * w.d_stride;
+  float *q2 = base + w.d_q2, *kv2 = base + w.d_kv2, *o2 = base + w.d_o2, *lse2 = base + w.d_lse2, *s4 = x.s4;
+  const uint32_t* mask2 = reinterpret_cast<const uint32_t*>(base + w.d_mask2);
+  if (!x.lean)
+    return adt_attn_bwd(x.prec, q2, d, kv2, 2 * d, kv2 + d, 2 * d, o2, d, lse2, x.s1, d, B, x.H, x.L, x.hd, 1, x.p, x.seed, dec_site(i, 1), x.b_offset,
+                        x.s5, d, s4, 2 * d, s4 + d, 2 * d, mask2, x.st);
+  const uint16_t* kvb = reinterpret_cast<const uint16_t*>(kv2);      // rows of 128 bf16: k2 | v2
+  // dq2 / dk2 / dv2 go to k_seqtt_mid_bwd only (with `parts` a "not covered" from it is an error), which builds bf16 MFMA operands from
+  // them: written as bf16 rows (the same rounding, half the bytes); s4 + d / 2 floats = 64 bf16 elements into the (k | v) row
+  return adt_attn_bwd_saved_bf16(q2, d, kvb, 2 * d, kvb + d, 2 * d, o2, d, lse2, x.s1, d, B, x.H, x.L, x.hd, x.p, x.seed, dec_site(i, 1), x.b_offset,
+                                 x.s5, d, s4, 2 * d, x.parts ? s4 + d / 2 : s4 + d, 2 * d, mask2, x.parts ? 1 : 0, x.st);
+}
+
+// enc_attn q / k / v projections and slf_attn.out_proj reverse -> dO1 (s1), g_f +=
+int dec_mid_bwd(const Bwd& x, int i) {
+  const WS& w = x.w; const Layout& lo = x.lo; const float* P = x.P; float* const Gq = x.Gq;
+  const int d = x.d, dd = d * d;
+  float* base = x.ws + i * w.d_stride;
+  float *o1 = base + w.d_o1, *a1 = base + w.d_a1;
+  const float* einw = P + lo.dec(i, D_EINW);
+  float* geinw = Gq + lo.dec(i, D_EINW);
+  float* geinb = Gq + lo.dec(i, D_EINB);
+  if (x.use_seq) {   // both projections' reverse in one launch per sequence (adt_seqpost_tt.cuh)
+    adt::BwdChainArgs a = x.BA(x.dec, 0.f, nullptr);
+    a.dqkv = x.s5; a.lddqkv = d; a.xin = a1; a.o = o1; a.saved_bf16 = x.lean; a.dkv2 = x.s4; a.f = x.f; a.grad_bf16 = (x.lean && x.parts) ? 1 : 0;
+    a.W0 = einw; a.W1 = P + lo.dec(i, D_SOW); a.W2 = einw + dd; a.W3 = einw + 2 * dd;
+    a.dW0 = geinw; a.dW1 = Gq + lo.dec(i, D_SOW); a.dW2 = geinw + dd; a.dW3 = geinw + 2 * dd;
+    a.db0 = geinb; a.db1 = Gq + lo.dec(i, D_SOB); a.db2 = geinb + d; a.db3 = geinb + 2 * d;
+    a.out0 = x.s1; a.out1 = x.gf; a.acc1 = 1;
+    a.part[0] = x.PART(i, PS_D_EIN); a.part[1] = x.PART(i, PS_D_SO); a.part[2] = x.PART(i, PS_D_EIN + 1); a.part[3] = x.PART(i, PS_D_EIN + 2);
+    a.part_stride = (size_t)w.part_stride;
+    a.vpart = x.VPART(i, 1);
+    const int rc = adt_launch_seq_mid_bwd(x.hd, a, x.st);
+    if (rc <= 0) return rc;
+    if (x.parts) return adt_set_error(NO_FALLBACK, x.L, x.hd);
+  }
+  {  // q2 = a1 Wq^T, a1 = o1 Wo1^T  -> dO1 (s1)
+    adt::BwdChainArgs a = x.BA(x.dec, 0.f, nullptr);
+    a.dqkv = x.s5; a.lddqkv = d; a.xin = a1; a.o = o1; a.saved_bf16 = x.lean;
+    a.W0 = einw; a.W1 = P + lo.dec(i, D_SOW);
+    a.dW0 = geinw; a.dW1 = Gq + lo.dec(i, D_SOW); a.db0 = geinb; a.db1 = Gq + lo.dec(i, D_SOB);
+    a.out0 = x.s1;
+    CK(adt_launch_bwdchain(x.prec, 4, a, x.st));
+  }
+  // [k2, v2] = f Wkv^T  -> g_f +=
+  adt::BwdChainArgs a = x.BA(x.dec, 0.f, nullptr);
+  a.dkv2 = x.s4; a.f = x.f;
+  a.W0 = einw + dd; a.W1 = einw + 2 * dd;
+  a.dW0 = geinw + dd; a.dW1 = geinw + 2 * dd; a.db0 = geinb + d; a.db1 = geinb + 2 * d;
+  a.out0 = x.gf; a.acc0 = 1;
+  return adt_launch_bwdchain(x.prec, 5, a, x.st);
+}
+
+// (self-)attention backward + LayerNorm / in-projection backward of one block, decoder (dec) or encoder:
+// gx (+)= LN'(dqkv Win + gy * mask)      |      gx += LN'(dq Wq + dh) + dk Wk + dv Wv
+int attn_block_bwd(const Bwd& x, int i, bool dec) {
+  const WS& w = x.w; const Layout& lo = x.lo; const float* P = x.P; float* const Gq = x.Gq; float* const ws = x.ws;
+  const int d = x.d, dd = d * d, nl = x.nl;
+  const int32_t* ids = dec ? x.dec : x.seq;
+  float* gy = ws + (dec ? w.g_dec_x : w.g_enc_x) + (i + 1) * x.Td;      // d loss / d (output of layer i), complete (the encoder's went into dh = s5)
+  float* gx = ws + (dec ? w.g_dec_x : w.g_enc_x) + i * x.Td;            // accumulates d / d (input of layer i) ; encoder: already holds the reconstruction seed
+  const float* xi = ws + (dec ? w.dec_x : w.enc_x) + i * x.Td;
+  float* base = ws + i * (dec ? w.d_stride : w.e_stride);
+  float *qkv = base + (dec ? w.d_qkv : w.e_qkv), *o = base + (dec ? w.d_o1 : w.e_o), *lse = base + (dec ? w.d_lse1 : w.e_lse);
+  const uint32_t* mask = reinterpret_cast<const uint32_t*>(base + (dec ? w.d_mask1 : w.e_mask));
+  const int64_t lnw = dec ? lo.dec(i, D_LNW) : lo.enc(i, E_LN1W), lnb = dec ? lo.dec(i, D_LNB) : lo.enc(i, E_LN1B);
+  const int64_t inw = dec ? lo.dec(i, D_SINW) : lo.enc(i, E_INW), inb = dec ? lo.dec(i, D_SINB) : lo.enc(i, E_INB);
+  const uint32_t site = dec ? dec_site(i, 0) : enc_site(i, 0);
+  const int acc = dec ? (i > 0 ? 1 : 0) : 1;
+  if (x.use_seq) {   // ... in one launch per sequence (adt_seqbwd_tt.cuh)
+    adt::SeqBwdArgs a = seq_bwd_args(x.L, (int)w.B, x.H, ids, x.p, x.seed, site, x.b_offset, x.hd);
+    a.x = xi; a.gamma = P + lnw; a.beta = P + lnb; a.Win = P + inw; a.bin = P + inb;
+    a.dO = x.s1; a.o = o; a.lse = lse; a.mask = mask; a.dres = dec ? gy : x.s5;
+    a.gx = gx; a.acc = acc; a.dWin = Gq + inw; a.dbin = Gq + inb; a.dgamma = Gq + lnw; a.dbeta = Gq + lnb;
+    if (x.plan.seeds_virtual && dec && i > 0) {      // reconstruction pair (enc_in[nl - i], dec_x[i]): d / d dec_x[i] = -2 lambda (a - b) / n = coef * (x - a)
+      a.acc = 0; a.seed_other = ws + w.enc_x + (nl - i) * x.Td; a.seed_coef = ws + w.norms + 8 + (nl - i);
+    }
+    if (x.plan.seeds_virtual && !dec) {               // reconstruction pair (enc_in[i], dec_x[nl - i]): d / d enc_in[i] = coef * (x - b)
+      a.acc = 0; a.seed_other = ws + w.dec_x + (nl - i) * x.Td; a.seed_coef = ws + w.norms + 8 + i;
+      if (i > 0) { a.seed_loss = ws + w.loss + 64 * (2 + i); a.seed_norms = ws + w.norms; }      // pair i >= 1 is not touched by the loss pass at all
+    }
+    a.nrep = NREPP; a.rep_stride = (size_t)w.prep_stride; a.wp_base = P + lo.posw(); a.wp_img = ws + w.wpack; a.saved_bf16 = x.lean;
+    a.part = x.PART(i, dec ? PS_D_SIN : PS_E_IN); a.part_stride = (size_t)w.part_stride;
+    a.vpart = x.VPART(i, dec ? 2 : 4);
+    a.nsplit = a.part ? attn_split((int)w.B) : 1;
+    time_mark(dec ? 2 : 1, i, true, x.st);
+    const int rc = adt_launch_seq_attn_pre_bwd(x.hd, dec ? 1 : 0, a, x.st);
+    time_mark(dec ? 2 : 1, i, false, x.st);
+    if (rc <= 0) return rc;
+    if (x.lean) return adt_set_error("backward: the lean forward needs the fused attention-block backward (L=%d hd=%d)", x.L, x.hd);
+  }
+  CK(adt_attn_bwd(x.prec, qkv, 3 * d, qkv + d, 3 * d, qkv + 2 * d, 3 * d, o, d, lse, x.s1, d, (int)w.B, x.H, x.L, x.hd, 1, x.p, x.seed, site, x.b_offset,
+                  x.s3, 3 * d, x.s3 + d, 3 * d, x.s3 + 2 * d, 3 * d, mask, x.st));
+  adt::BwdChainArgs a = x.BA(ids, 0.f, nullptr);
+  a.dqkv = x.s3; a.lddqkv = 3 * d; a.xin = xi;
+  if (dec) a.gy = gy; else a.dh = x.s5;
+  a.W0 = P + inw; a.W1 = P + inw + dd; a.W2 = P + inw + 2 * dd; a.gamma = P + lnw; a.beta = P + lnb;
+  a.dW0 = Gq + inw; a.dW1 = Gq + inw + dd; a.dW2 = Gq + inw + 2 * dd; a.db0 = Gq + inb; a.db1 = Gq + inb + d; a.db2 = Gq + inb + 2 * d;
+  a.dgamma = Gq + lnw; a.dbeta = Gq + lnb;
+  a.out0 = gx; a.acc0 = acc;
+  return adt_launch_bwdchain(x.prec, dec ? 3 : 2, a, x.st);
+}
+
+int dec_block_backward(const Bwd& x, int i, LogitsSide& logits) {
+  CK(dec_post_bwd(x, i));
+  CK(logits.after_first_chain_kernel(x));
+  CK(dec_cross_attn_bwd(x, i));
+  CK(logits.join(x));
+  CK(dec_mid_bwd(x, i));
+  return attn_block_bwd(x, i, true);
+}
+
+// The decoder's input embedding gradient (sasrec/model.py:53-59) and the sum of the decoder blocks' partials need nothing from the encoder
+// chain: in a one-phase backward they run on the side stream under it (joined in front of the last fold); in the two-phase form the sum runs
+// beside the embedding gradient.  k_dwpart_reduce adds with atomics and k_replica_reduce2 read-modify-writes the same range of G: the fold
+// always comes behind the join.
+struct DecSide {
+  enum { NONE, MARKED, ENQUEUED } at = NONE;
+  bool parts_done = false;      // the decoder blocks' partials were summed here (not left to the encoder's sum)
+
+  int embed(const Bwd& x, void* s) const {
+    const WS& w = x.w;
+    return adt_embed_bwd_rep(x.dec, x.ws + w.g_dec_x, x.T, x.L, x.d, x.p, x.seed, SITE_EMB_DEC, x.ro, x.G + x.lo.posw(), x.ws + w.rep, NREP, w.rep_stride, s);
+  }
+  // behind the decoder stack (phase 0 or 1)
+  int begin(const Bwd& x) {
+    const WS& w = x.w; const Layout& lo = x.lo;
+    const int64_t dec_begin = lo.dec(0, 0);
+    // (embed3: the decoder embedding's rows go out with the encoder's at the very end -- with the sums left to the optimizer's fold there is then
+    // nothing for the side stream here, and no fork)
+    if (x.plan.phase == 0 && x.sd && (side_sites() & 2) && !(x.embed3 && (x.late_parts || !x.parts))) {
+      CK(side_mark(x.sd, 1, x.st));
+      at = MARKED;                      // enqueued behind the first kernel of the encoder phase
+    } else if (x.plan.phase == 0) {
+      if (!x.det && !x.embed3) CK(embed(x, x.st));
+    } else if (x.det) {      // two-phase form: the decoder blocks' partial sums and the fold of the decoder range (nothing of the tables yet)
+      if (x.parts) CK(reduce_partials(x.c, lo, w, x.G, x.ws, false, true, x.st));
+      CK(adt_replica_reduce(x.G + dec_begin, x.Gq + dec_begin, lo.total - dec_begin, NREPP, w.prep_stride, x.st));
+    } else {
+      void* s2 = nullptr;
+      CK(side_mark(x.sd, 1, x.st));
+      if (!x.embed3) CK(embed(x, x.st));
+      CK(side_enter(x.sd, 1, x.st, &s2));
+      if (x.parts) CK(reduce_partials(x.c, lo, w, x.G, x.ws, false, true, s2));
+      CK(side_join(x.sd, 1, x.st));
+      CK(adt_replica_reduce2(x.G + lo.item(), x.ws + w.rep, (int64_t)(x.c->item_num + 1) * x.d, NREP, w.rep_stride, x.G + dec_begin, x.Gq + dec_begin,
+                             lo.total - dec_begin, NREPP, w.prep_stride, x.st));
+    }
+    return 0;
+  }
+  // behind the first kernel of the encoder phase (which keeps the caller's queue)
+  int enter(const Bwd& x) {
+    if (at != MARKED) return 0;
+    void* s2 = nullptr;
+    CK(side_enter(x.sd, 1, x.st, &s2));
+    if (!x.det && !x.embed3) CK(embed(x, s2));
+    if (x.parts && !x.late_parts) { CK(reduce_partials(x.c, x.lo, x.w, x.G, x.ws, false, true, s2)); parts_done = true; }
+    at = ENQUEUED;
+    return 0;
+  }
+  // in front of the table gradients, unless a later join of the (in-order) side stream covers it
+  int join(const Bwd& x, bool covered) {
+    if (at == ENQUEUED && !covered) CK(side_join(x.sd, 1, x.st));
+    at = NONE;
+    return 0;
+  }
+};
+
+// last_layernorm: g_enc_x[nl] = LN'(g_f), unless the last encoder block's first kernel does it (Bwd::lnl_fused)
+int last_layernorm_bwd(const Bwd& x) {
+  const WS& w = x.w; const Layout& lo = x.lo; float* const ws = x.ws;
+  const int d = x.d;
+  if (x.lnl_fused) return 0;      // (nothing to launch: BwdChainArgs::lnl_x of the first encoder kernel)
+  if (x.late_parts) {
+    const int nb = adt_layernorm_bwd_parts(x.gf, d, ws + w.enc_x + x.nl * x.Td, d, x.P + lo.lnl_w(), LN_EPS, x.T, d, ws + w.g_enc_x + x.nl * x.Td, d, 0,
+                                           ws + w.lnpart, LN_PART_BLOCKS, x.st);
+    return nb < 0 ? nb : 0;
+  }
+  return adt_layernorm_bwd_rep(x.gf, d, ws + w.enc_x + x.nl * x.Td, d, x.P + lo.lnl_w(), LN_EPS, x.T, d, ws + w.g_enc_x + x.nl * x.Td, d, 0,
+                               x.Gq + lo.lnl_w(), x.Gq + lo.lnl_b(), NREPP, w.prep_stride, x.st);
+}
+
+// ---- one encoder block ---------------------------------------------------------------------------------------------------------------
+// FFN + mask + forward_layernorm + out_proj reverse -> dh (s5), dO (s1)  [+ the last LayerNorm in front, + the head classifier]
+int enc_post_bwd(const Bwd& x, int i) {
+  const WS& w = x.w; const Layout& lo = x.lo; const float* P = x.P; float* const Gq = x.Gq; float* const ws = x.ws;
+  const int H = x.H, nl = x.nl;
+  float* base = ws + i * w.e_stride;
+  adt::BwdChainArgs a = x.BA(x.seq, x.p, x.seed);
+  a.site1 = enc_site(i, 1); a.site2 = enc_site(i, 2);
+  a.gy = ws + w.g_enc_x + (i + 1) * x.Td; a.u = base + w.e_u; a.xin = base + w.e_h; a.o = base + w.e_o; a.saved_bf16 = x.lean;
+  a.W0 = P + lo.enc(i, E_C2W); a.W1 = P + lo.enc(i, E_C1W); a.W2 = P + lo.enc(i, E_OW);
+  a.gamma = P + lo.enc(i, E_LN2W); a.beta = P + lo.enc(i, E_LN2B);
+  a.dW0 = Gq + lo.enc(i, E_C2W); a.dW1 = Gq + lo.enc(i, E_C1W); a.dW2 = Gq + lo.enc(i, E_OW);
+  a.db0 = Gq + lo.enc(i, E_C2B); a.db1 = Gq + lo.enc(i, E_C1B); a.db2 = Gq + lo.enc(i, E_OB);
+  a.dgamma = Gq + lo.enc(i, E_LN2W); a.dbeta = Gq + lo.enc(i, E_LN2B);
+  a.out0 = x.s5; a.out1 = x.s1;
+  int which = 0;
+  if (H > 1 && H <= 4) {   // independence-head classifier reverse, fused (sasrec/modules.py:648-649; main.py:160-169)
+    which = H <= 2 ? 6 : 7;
+    a.rec = base + w.e_rec; a.drec = ws + w.g_rec + i * x.recsz; a.Ws = P + lo.enc(i, E_SW); a.dWs = Gq + lo.enc(i, E_SW);
+    a.dbs = Gq + lo.enc(i, E_SB); a.H = H;
+  }
+  a.part[0] = x.PART(i, PS_E_C2); a.part[1] = x.PART(i, PS_E_C1); a.part[2] = x.PART(i, PS_E_O); a.part_stride = (size_t)w.part_stride;
+  a.vpart = x.VPART(i, 3);
+  if (x.lnl_fused && i == nl - 1) {
+    a.gy = x.gf; a.lnl_x = ws + w.enc_x + nl * x.Td; a.lnl_gamma = P + lo.lnl_w(); a.lnl_eps = LN_EPS;
+    a.vpart2 = x.late_parts ? ws + w.vpart + (int64_t)(5 * nl) * w.vcall : nullptr;
+    a.lnl_dgamma = Gq + lo.lnl_w(); a.lnl_dbeta = Gq + lo.lnl_b();
+  }
+  const int rc = x.use_seq ? adt_launch_seq_post_bwd(x.hd, 1, a, x.st) : 1;
+  if (rc < 0) return rc;
+  if (rc && x.parts) return adt_set_error(NO_FALLBACK, x.L, x.hd);
+  return rc ? adt_launch_bwdchain(x.prec, which, a, x.st) : 0;
+}
+
+int enc_block_backward(const Bwd& x, int i, DecSide& dec_side) {
+  const WS& w = x.w; const Layout& lo = x.lo;
+  CK(enc_post_bwd(x, i));
+  if (x.lnl_fused && i == x.nl - 1) CK(dec_side.enter(x));      // the first kernel of the encoder phase
+  if (x.H > 4) {   // wider classifiers: separate kernel
+    float* base = x.ws + i * w.e_stride;
+    CK(adt_headcls_bwd(base + w.e_o, x.d, x.P + lo.enc(i, E_SW), base + w.e_rec, x.ws + w.g_rec + i * x.recsz, (int)w.B, x.L, x.H, x.hd, x.s1, x.d,
+                       x.G + lo.enc(i, E_SW), x.G + lo.enc(i, E_SB), x.st));
+  }
+  return attn_block_bwd(x, i, false);
+}
+
+// The table gradients (sasrec/model.py:34-41, :53-59, :72-76 reversed) in their three forms, the sum of the encoder blocks' partials beside
+// them, and the last fold.  The side stream is in order: the join behind that sum also covers the decoder's work queued on it earlier -- a
+// join of its own in front of the embedding gradient was one more cross-queue wait (5-9 us) on the caller's stream.
+int table_gradients(const Bwd& x, DecSide& dec_side) {
+  const WS& w = x.w; const Layout& lo = x.lo; float* const ws = x.ws; float* const G = x.G;
+  const int phase = x.plan.phase;
+  if (phase == 2 && !x.det && adt::zero_f32_async(ws + w.rep, (size_t)NREP * w.rep_stride, (hipStream_t)x.st)) return adt_set_error("replica zero");
+  // (nothing to put beside the embedding gradient when the optimizer's fold sums the partials: no empty fork / join pair then)
+  SideStream* const sd2 = ((side_sites() & 4) && x.parts && !x.late_parts) ? x.sd : nullptr;
+  CK(dec_side.join(x, sd2 != nullptr));
+  void* s2 = nullptr;
+  CK(side_mark(sd2, 2, x.st));
+  if (x.det) {
+    // item table: every item's rows (encoder ids, decoder ids, positive / negative items of the logits) summed by one owner in sorted
+    // order ; positional table: one owner per position
+    if (x.sd_sort && hipStreamWaitEvent((hipStream_t)x.st, x.sd_sort->join_ev[3], 0) != hipSuccess) return adt_set_error("backward: sort join");
+    const uint32_t site4[4] = {SITE_EMB_SEQ, SITE_EMB_DEC, 0u, 0u};
+    const int32_t* const ids2[2] = {x.seq, x.dec};
+    const float* const dx2[2] = {ws + w.g_enc_x, ws + w.g_dec_x};
+    CK(adt_item_segsum_posemb(reinterpret_cast<int32_t*>(ws + w.isort), 4, x.T, x.c->item_num + 1, 0xFu, site4, x.p, x.seed, sqrtf((float)x.d), G + lo.item(),
+                              x.plan.prep_zeroed ? 0 : 1, ids2, dx2, site4, 2, (int)w.B, x.L, x.ro, G + lo.posw(), x.st));
+  } else if (x.embed3) {      // encoder + decoder embedding rows + the positive-logit rows: one atomic row-add per token where their ids line up
+    const bool by_forward = phase == 2 ? x.plan.seeds_virtual : x.plan.bce_fwd;      // (phase 2: the caller passes the ring only behind such a forward)
+    CK(adt_embed_bwd3_prefetch(x.seq, x.dec, x.pos, ws + w.g_enc_x, ws + w.g_dec_x, x.f, ws + w.g_pos, x.T, x.L, x.p, x.seed, SITE_EMB_SEQ, SITE_EMB_DEC, x.ro,
+                               G + lo.posw(), ws + w.rep, NREP, w.rep_stride, ring_prefetch_split(x.ring, by_forward, w) ? &x.ring : nullptr, x.st));
+  } else {
+    CK(adt_embed_bwd_rep(x.seq, ws + w.g_enc_x, x.T, x.L, x.d, x.p, x.seed, SITE_EMB_SEQ, x.ro, G + lo.posw(), ws + w.rep, NREP, w.rep_stride, x.st));
+  }
+  CK(side_enter(sd2, 2, x.st, &s2));
+  if (x.parts && !x.late_parts) CK(reduce_partials(x.c, lo, w, G, ws, true, phase == 0 && !dec_side.parts_done, s2));
+  CK(side_join(sd2, 2, x.st));
+  if (x.plan.defer_fold) return 0;
+  return adt_replica_reduce2(G + lo.item(), ws + w.rep, (int64_t)(x.c->item_num + 1) * x.d, x.det ? 0 : NREP, w.rep_stride, G + lo.posw(), x.Gq + lo.posw(),
+                             (phase == 0 ? lo.total : lo.dec(0, 0)) - lo.posw(), NREPP, w.prep_stride, x.st);
+}
+
+// sort of the step's ids + gather plan of the sorted table gradients (a function of the ids and of fixed workspace addresses only), beside the
+// decoder's chain kernels; joined in front of the sums (table_gradients)
+int item_sort_begin(const Bwd& x) {
+  const WS& w = x.w; float* const ws = x.ws;
+  const int32_t* const ids4[4] = {x.seq, x.dec, x.pos, x.neg};
+  const float* const rows4[4] = {ws + w.g_enc_x, ws + w.g_dec_x, x.f, x.f};
+  const float* const coef4[4] = {nullptr, nullptr, ws + w.g_pos, ws + w.g_neg};
+  const int kind4[4] = {0, 0, 1, 1};
+  void* s2 = x.st;
+  if (x.sd_sort) { CK(side_mark(x.sd_sort, 3, x.st)); CK(side_enter(x.sd_sort, 3, x.st, &s2)); }
+  CK(adt_item_sort(ids4, 4, x.T, x.c->item_num + 1, rows4, coef4, kind4, x.ro, reinterpret_cast<int32_t*>(ws + w.isort), s2));
+  if (x.sd_sort && hipEventRecord(x.sd_sort->join_ev[3], x.sd_sort->s) != hipSuccess) return adt_set_error("backward: sort event");
+  return 0;
+}
+
+// phase 0 / 1: logits, decoder stack, the decoder-side table work
+int decoder_phase(const Bwd& x, DecSide& dec_side) {
+  if (x.w.prep != x.w.rep + NREP * x.w.rep_stride) return adt_set_error("workspace layout: replica areas not adjacent");
+  if (x.det) CK(item_sort_begin(x));
+  LogitsSide logits;
+  CK(logits.begin(x));
+  for (int i = x.nl - 1; i >= 0; --i) CK(dec_block_backward(x, i, logits));
+  return dec_side.begin(x);
+}
+
+// phase 0 / 2: last LayerNorm, encoder stack, table gradients, fold
+int encoder_phase(const Bwd& x, DecSide& dec_side) {
+  CK(last_layernorm_bwd(x));
+  if (!x.lnl_fused) CK(dec_side.enter(x));
+  for (int i = x.nl - 1; i >= 0; --i) CK(enc_block_backward(x, i, dec_side));
+  return table_gradients(x, dec_side);
 }
 
 }  // namespace
@@ -571,15 +1054,13 @@ int64_t adt_sasrec_ws_offset(const adt_sasrec_cfg* cfg, int B, int what, int lay
 int adt_sasrec_forward(const adt_sasrec_cfg* c, const float* P, float* ws, const int32_t* seq, const int32_t* dec,
                        const int32_t* pos, const int32_t* neg, int B, int training, const uint32_t* seed,
                        uint32_t b_offset, void* st) {
-  CK(check_cfg(c));
   Layout lo;
-  make_layout(c, &lo);
   WS w;
-  make_ws(c, B, &w);
+  CK(layout_ws(c, B, &lo, &w));
   const int T = (int)w.T, d = (int)w.d, H = (int)w.H, hd = d / H, L = (int)w.L, prec = c->prec;
   const int64_t Td = up64(w.T * w.d);
-  const bool packed = (training & 2) != 0;       // bit 1: the weight images were packed by adt_sasrec_step_begin* of this step
-  training &= 1;
+  const bool packed = (training & ADT_TRAIN_PACKED) != 0;       // the weight images were packed by adt_sasrec_step_begin* of this step
+  training &= ADT_TRAIN_DROPOUT;
   const float p = training ? c->dropout : 0.f;
   const uint32_t ro = b_offset * (uint32_t)L;
   CK(encoder_forward(c, lo, w, P, ws, seq, pos, neg, p, seed, b_offset, true, st, packed));
@@ -633,7 +1114,7 @@ int adt_sasrec_forward(const adt_sasrec_cfg* c, const float* P, float* ws, const
 }
 
 // adt_sasrec_forward (training) + adt_sasrec_loss_seed_nz in one call; on the lean per-sequence path (adt_sasrec_bce_deferred) without the
-// k_final_fwd launch and without the BCE block of the loss assembly: the caller must then run adt_sasrec_backward with phase bit 4 (+ 16).
+// k_final_fwd launch and without the BCE block of the loss assembly: the caller must then run adt_sasrec_backward with ADT_PHASE_BCE_HERE.
 // The loss slots must have been zeroed (adt_sasrec_step_begin*).
 int adt_sasrec_bce_deferred(const adt_sasrec_cfg* c) { return check_cfg(c) == 0 && bce_deferred(c) ? 1 : 0; }
 int adt_sasrec_forward_loss(const adt_sasrec_cfg* c, const float* P, float* ws, const int32_t* seq, const int32_t* dec, const int32_t* pos,
@@ -647,14 +1128,12 @@ int adt_sasrec_forward_loss_prefetch(const adt_sasrec_cfg* c, const float* P, fl
                                      const int32_t* neg, int B, int training, const uint32_t* seed, uint32_t b_offset, const float* lambdas1,
                                      const float* lambdas2, const int32_t* ring, int64_t slot_ints, int nslots, uint32_t* state, uint32_t* consumed,
                                      int32_t* staging, void* st) {
-  CK(check_cfg(c));
-  if ((training & 1) && (training & 2)) {      // training forward on weight images packed by this step's adt_sasrec_step_begin*
-    Layout lo;
-    make_layout(c, &lo);
-    WS w;
-    make_ws(c, B, &w);
-    const RingRef rr{ring, slot_ints, nslots, state, consumed, staging};
-    const int rc = forward_loss_lean(c, lo, w, P, ws, seq, dec, pos, neg, (training & 4) != 0, c->dropout, seed, b_offset, lambdas1, lambdas2, rr, st);
+  Layout lo;
+  WS w;
+  CK(layout_ws(c, B, &lo, &w));
+  if ((training & ADT_TRAIN_DROPOUT) && (training & ADT_TRAIN_PACKED)) {      // training forward on weight images packed by this step's adt_sasrec_step_begin*
+    const adt::RingPrefetchArgs rr{ring, (size_t)slot_ints, nslots, (size_t)(4 * w.T + 4), state, consumed, staging, 0, 0};
+    const int rc = forward_loss_lean(c, lo, w, P, ws, seq, dec, pos, neg, (training & ADT_TRAIN_BCE_SIDE) != 0, c->dropout, seed, b_offset, lambdas1, lambdas2, rr, st);
     if (rc <= 0) return rc;
   }
   CK(adt_sasrec_forward(c, P, ws, seq, dec, pos, neg, B, training, seed, b_offset, st));
@@ -665,11 +1144,9 @@ int adt_sasrec_forward_loss_prefetch(const adt_sasrec_cfg* c, const float* P, fl
 // adt_sasrec_forward of the same batch (its inputs -- log_feats, the layer input, the packed weight images -- are read from there).
 int adt_sasrec_probe_dec_layer_fwd(const adt_sasrec_cfg* c, const float* P, float* ws, const int32_t* dec, int B, int training,
                                    const uint32_t* seed, uint32_t b_offset, int layer, void* st) {
-  CK(check_cfg(c));
   Layout lo;
-  make_layout(c, &lo);
   WS w;
-  make_ws(c, B, &w);
+  CK(layout_ws(c, B, &lo, &w));
   const int d = (int)w.d, hd = d / (int)w.H;
   if (layer < 0 || layer >= c->num_layers) return adt_set_error("probe: layer %d", layer);
   if (!adt_seq_supported(c->prec, (int)w.L, d, hd)) return adt_set_error("probe: the fused decoder layer does not cover this configuration");
@@ -678,11 +1155,9 @@ int adt_sasrec_probe_dec_layer_fwd(const adt_sasrec_cfg* c, const float* P, floa
 
 int adt_sasrec_step_begin(const adt_sasrec_cfg* c, float* ws, int B, uint32_t* seed, uint32_t seed_inc, const float* norms_src, const float* P,
                           float* G, int64_t n, float* scal, void* st) {
-  CK(check_cfg(c));
   Layout lo;
-  make_layout(c, &lo);
   WS w;
-  make_ws(c, B, &w);
+  CK(layout_ws(c, B, &lo, &w));
   int offs[256];
   const int npack = pack_offsets(c, lo, offs);
   return adt_step_begin_launch(seed, seed_inc, ws + w.norms, norms_src, ws + w.loss, 64 * (2 + 2 * c->num_layers), scal, G, n, P + lo.item(),
@@ -699,11 +1174,9 @@ int adt_sasrec_step_begin_ring(const adt_sasrec_cfg* c, float* ws, int B, uint32
 int adt_sasrec_step_begin_ring_staged(const adt_sasrec_cfg* c, float* ws, int B, uint32_t* seed, uint32_t seed_inc, const int32_t* ring,
                                       int64_t slot_ints, int nslots, int32_t* ids_dst, uint32_t* state, uint32_t* consumed, const int32_t* staging,
                                       const uint32_t* produced, const float* P, float* G, int64_t n, float* scal, void* st) {
-  CK(check_cfg(c));
   Layout lo;
-  make_layout(c, &lo);
   WS w;
-  make_ws(c, B, &w);
+  CK(layout_ws(c, B, &lo, &w));
   int offs[256];
   const int npack = pack_offsets(c, lo, offs);
   return adt_step_begin_ring_launch(seed, seed_inc, ws + w.norms, ws + w.loss, 64 * (2 + 2 * c->num_layers), scal, G, n, P + lo.item(),
@@ -732,15 +1205,10 @@ static int loss_seed_impl(const adt_sasrec_cfg* c, float* ws, const int32_t* pos
   const float* norms = ws + w.norms;
   if (zero_loss && adt::zero_f32_async(loss, (size_t)64 * (2 + 2 * nl), (hipStream_t)st)) return adt_set_error("loss zero");
   if (nl <= 4) {   // one launch for all of them (adt_misc.cuh: k_loss_seeds)
-    const float *A[4], *Bm[4], *rc[4];
-    float *GA[4], *GB[4], *lm[4], *dr[4], *ln[4];
-    for (int i = 0; i < nl; ++i) {
-      A[i] = ws + w.enc_x + i * Td; Bm[i] = ws + w.dec_x + (nl - i) * Td; GA[i] = ws + w.g_enc_x + i * Td; GB[i] = ws + w.g_dec_x + (nl - i) * Td;
-      lm[i] = loss + 64 * (2 + i);
-      rc[i] = ws + i * w.e_stride + w.e_rec; dr[i] = ws + w.g_rec + i * rec; ln[i] = loss + 64 * (2 + nl + i);
-    }
-    return adt_loss_seeds(ws + w.posl, ws + w.negl, pos, T, norms, ws + w.g_pos, ws + w.g_neg, loss, nl, A, Bm, w.T * w.d, lambdas1, GA, 0, GB, lm,
-                          H > 1 ? nl : 0, rc, T, H, lambdas2[nl - 1], dr, ln, st);
+    LossPtrs q;
+    AdtLossSeedsJob job = loss_terms(w, ws, lambdas1, lambdas2, true, &q);
+    job.pos_logits = ws + w.posl; job.neg_logits = ws + w.negl; job.pos = pos; job.dpos = ws + w.g_pos; job.dneg = ws + w.g_neg;
+    return adt_loss_seeds_prefetch(job, st);
   }
   CK(adt_bce_seed(ws + w.posl, ws + w.negl, pos, T, norms, ws + w.g_pos, ws + w.g_neg, loss, st));
   for (int i = 0; i < nl; ++i)   // enc_in[i] pairs with dec_out_rev[i] = DEC_X[nl - i]      (sasrec/main.py:155-158)
@@ -752,414 +1220,35 @@ static int loss_seed_impl(const adt_sasrec_cfg* c, float* ws, const int32_t* pos
   return 0;
 }
 
-// Measurement hook (bench.py's roofline probe; not part of include/adt_hip.h): HIP events recorded on the launch stream right before and right
-// after ONE launch inside adt_sasrec_backward -- which = 1: the fused attention-block backward (k_seqtt_attn_pre_bwd) of encoder layer `layer`;
-// which = 2: the same kernel's decoder instantiation for decoder layer `layer`; 3: see time_mark; 0 switches the hook off.
-static int g_time_which = 0, g_time_layer = 0;
-static hipEvent_t g_time_ev0 = nullptr, g_time_ev1 = nullptr;
-extern "C" int adt_debug_time_launch(int which, int layer, void* ev_start, void* ev_stop) {
+// the measurement hook of time_mark above
+int adt_debug_time_launch(int which, int layer, void* ev_start, void* ev_stop) {
   g_time_which = which; g_time_layer = layer; g_time_ev0 = (hipEvent_t)ev_start; g_time_ev1 = (hipEvent_t)ev_stop;
   return 0;
-}
-// which = 3: calibration -- BOTH events in front of the launch of which = 1 (nothing between them): what an event pair itself adds to an interval
-static inline void time_mark(int which, int layer, bool start, void* st) {
-  if (!g_time_ev0 || !g_time_ev1 || g_time_layer != layer) return;
-  if (g_time_which == 3 && which == 1 && start) {
-    (void)hipEventRecord(g_time_ev0, (hipStream_t)st);
-    (void)hipEventRecord(g_time_ev1, (hipStream_t)st);
-  } else if (g_time_which == which) {
-    (void)hipEventRecord(start ? g_time_ev0 : g_time_ev1, (hipStream_t)st);
-  }
 }
 
 int adt_sasrec_backward(const adt_sasrec_cfg* c, const float* P, float* G, float* ws, const int32_t* seq,
                         const int32_t* dec, const int32_t* pos, const int32_t* neg, int B, int training,
                         const uint32_t* seed, uint32_t b_offset, int phase, void* st) {
-  CK(check_cfg(c));
-  Layout lo;
-  make_layout(c, &lo);
-  WS w;
-  make_ws(c, B, &w);
-  const int T = (int)w.T, d = (int)w.d, H = (int)w.H, hd = d / H, L = (int)w.L, prec = c->prec, nl = c->num_layers;
-  const int64_t Td = up64(w.T * w.d), recsz = up64(w.T * w.H * w.H);
-  const float p = training ? c->dropout : 0.f;
-  const uint32_t ro = b_offset * (uint32_t)L;
-  float *s1 = ws + w.s1, *s3 = ws + w.s3, *s4 = ws + w.s4, *s5 = ws + w.s5;
-  float* gf = ws + w.g_f;
-  // the backward chains flush their weight / bias / LayerNorm gradients into NREPP zeroed replicas of the non-item parameters
-  // (Gq + lo.xxx() addresses replica 0); each phase folds its range into G at its end
-  float* const Gq = ws + w.prep - lo.posw();
-  auto BA = [&](const int32_t* ids, float pp, const uint32_t* sd) {
-    adt::BwdChainArgs a = bwd_args(T, L, (int)w.B, ids, pp, sd, ro);
-    a.nrep = NREPP; a.rep_stride = (size_t)w.prep_stride;
-    a.wp_base = P + lo.posw(); a.wp_img = prec == ADT_PREC_BF16 ? (const void*)(ws + w.wpack) : nullptr;   // packed by the forward of this step
-    a.nsplit = seq_split((int)w.B);
-    return a;
-  };
-  const int64_t dec_begin = lo.dec(0, 0);
-  const float* f = ws + w.f;
-  const bool use_seq = adt_seq_supported(prec, L, d, hd) != 0;
-  const int lean = adt_seq_lean(prec, L, d, hd);      // what the forward of this step saved (same predicate, same process)
-  // weight gradients through private per-sequence partials + one ordered sum instead of float atomics (adt_seqbwd_tt.cuh: sb_dw_tiles)
-  const bool parts = w.part_stride > 0 && adt_seq_partials(prec, L, d, hd) != 0;
-  auto PART = [&](int layer, int slot) { return parts ? ws + w.part + (int64_t)(16 * layer + slot) * 4096 : nullptr; };
-  const char* const no_fallback = "backward: shape L=%d hd=%d left the per-sequence kernels although the partial-gradient path was chosen";
-  const bool prep_zeroed = (phase & 4) != 0;      // bit 2: adt_sasrec_step_begin* of this step zeroed the item-table and parameter-gradient replicas
-  const bool defer_fold = (phase & 8) != 0 && (phase & 3) == 0;      // bit 3 (one-phase only): adt_sasrec_fold_clip_adam does the last fold
-  const bool late_parts = defer_fold && fold_sums_partials(c, w);      // adt_sasrec_fold_clip_adam sums the weight-gradient partials too
-  // ... and the bias / LayerNorm / classifier gradient sums, which the chain kernels then STORE per workgroup (no float atomics, no replicas)
-  auto VPART = [&](int layer, int k) { return late_parts ? ws + w.vpart + (int64_t)(5 * layer + k) * w.vcall : nullptr; };
-  const bool bce_here = (phase & 16) != 0;        // bit 4: the forward was adt_sasrec_forward_loss on the deferred path: logits + BCE seed are formed here
-  const bool bce_fwd = (phase & 32) != 0;         // bit 5: ... and launched that kernel itself (training bit 2): only its join is left
-  if ((bce_here || bce_fwd) && !bce_deferred(c)) return adt_set_error("backward: phase bit 4 / 5 without the deferred-BCE forward (adt_sasrec_bce_deferred)");
-  if (bce_fwd && (bce_here || (phase & 4) == 0 || (phase & 3) == 2)) return adt_set_error("backward: phase bit 5 goes with bit 2, without bit 4, in phase 0 or 1");
-  // the forward of the deferred path (forward_loss_lean) does not materialise the reconstruction seeds that k_seqtt_attn_pre_bwd can form itself
-  const bool seeds_virtual = bce_here || bce_fwd || (phase & 64) != 0;      // (bit 6: phase 2 of a two-phase backward behind such a forward)
-  // ... and on that path the encoder / decoder embedding gradients and the positive-logit rows share ONE scatter at the end (adt_embed_bwd3)
-  const bool embed3 = seeds_virtual && embed3_on(w);
-  phase &= 3;
-  const bool det = item_det(w);                   // item / positional table gradients by sorted segmented sums (no replicas, no float atomics)
-  auto logits_scatter = [&](void* s) {      // d log_feats + item rows of pos / neg (+ logits and BCE seed on the deferred path)   (sasrec/model.py:72-76)
-    if (bce_here)
-      return adt_logits_bce_scatter_ex(f, P + lo.item(), pos, neg, ws + w.norms, T, ws + w.posl, ws + w.negl, ws + w.g_pos, ws + w.g_neg, ws + w.loss,
-                                       gf, det ? nullptr : ws + w.rep, NREP, w.rep_stride, embed3 ? 1 : 0, s);
-    if (det) return adt_logits_bwd_df(P + lo.item(), pos, neg, ws + w.g_pos, ws + w.g_neg, T, d, gf, d, s);
-    return adt_logits_bwd_scatter(f, d, P + lo.item(), pos, neg, ws + w.g_pos, ws + w.g_neg, T, d, gf, d, ws + w.rep, NREP, w.rep_stride, s);
-  };
-  int32_t* const iwork = reinterpret_cast<int32_t*>(ws + w.isort);
-  SideStream* const sd_sort = det ? side_stream((hipStream_t)st) : nullptr;      // the id sort runs beside the decoder's chain kernels, also in the two-phase form
-  // (one-phase backward by default: the two-phase form belongs to the data-parallel step, whose capture already carries the collectives'
-  // stream; there the side stream measured 0.692 against 0.699 ms on a 1-rank RCCL group and is opt-in: ADT_SIDE_STREAM_DP=1)
-  static const int dp_on = adt_env_int("ADT_SIDE_STREAM_DP", 0) != 0;
-  SideStream* const sd = (phase == 0 || dp_on) ? side_stream((hipStream_t)st) : nullptr;
-  int dec_side = 0;      // the decoder's embedding gradient + partial sums on the side stream: 1 marked, 2 enqueued
-  bool dec_parts_done = false;
-  if (phase == 0 || phase == 1) {
-    // d log_feats (overwrites g_f) and item-table rows of pos/neg      (sasrec/model.py:72-76)
-    // item-table replicas and parameter replicas are adjacent in the workspace: one fill
-    if (w.prep != w.rep + NREP * w.rep_stride) return adt_set_error("workspace layout: replica areas not adjacent");
-    // The item-table rows of the logits (and d log_feats, first read by the reverse of the cross-attention projections) go to the side
-    // stream: they run under the first two decoder kernels, which only need the parameter replicas zeroed.
-    int logits_side = 0;      // 1: marked, to be enqueued behind the first chain kernel ; 2: enqueued, to be joined ; 3: enqueued by the forward
-    if (bce_fwd) logits_side = 3;
-    if (det) {
-      // sort of the step's ids + gather plan (a function of the ids and of fixed workspace addresses only); joined in front of the sums
-      const int32_t* const ids4[4] = {seq, dec, pos, neg};
-      const float* const rows4[4] = {ws + w.g_enc_x, ws + w.g_dec_x, f, f};
-      const float* const coef4[4] = {nullptr, nullptr, ws + w.g_pos, ws + w.g_neg};
-      const int kind4[4] = {0, 0, 1, 1};
-      void* s2 = st;
-      if (sd_sort) { CK(side_mark(sd_sort, 3, st)); CK(side_enter(sd_sort, 3, st, &s2)); }
-      CK(adt_item_sort(ids4, 4, T, c->item_num + 1, rows4, coef4, kind4, ro, iwork, s2));
-      if (sd_sort && hipEventRecord(sd_sort->join_ev[3], sd_sort->s) != hipSuccess) return adt_set_error("backward: sort event");
-    }
-    if (bce_fwd) {
-      // nothing to launch: the forward put the kernel on the side stream (or, without one, on this stream); joined below
-    } else if (det) {
-      if (!prep_zeroed && adt::zero_f32_async(ws + w.prep, (size_t)NREPP * w.prep_stride, (hipStream_t)st)) return adt_set_error("replica zero");
-      CK(logits_scatter(st));      // no atomics left in it: a short streaming pass on the caller's stream
-    } else if (sd && (side_sites() & 1)) {
-      CK(side_mark(sd, 0, st));
-      if (!prep_zeroed && adt::zero_f32_async(ws + w.prep, (size_t)NREPP * w.prep_stride, (hipStream_t)st)) return adt_set_error("replica zero");
-      logits_side = 1;
-    } else {
-      if (!prep_zeroed && adt::zero_f32_async(ws + w.rep, (size_t)NREP * w.rep_stride + (size_t)NREPP * w.prep_stride, (hipStream_t)st)) return adt_set_error("replica zero");
-      CK(logits_scatter(st));
-    }
-    for (int i = nl - 1; i >= 0; --i) {
-      float* gy = ws + w.g_dec_x + (i + 1) * Td;      // d loss / d (output of decoder layer i), complete
-      float* gx = ws + w.g_dec_x + i * Td;            // accumulates d / d (input of layer i)
-      const float* x = ws + w.dec_x + i * Td;
-      float* base = ws + i * w.d_stride;
-      float *qkv = base + w.d_qkv, *o1 = base + w.d_o1, *lse1 = base + w.d_lse1, *a1 = base + w.d_a1,
-            *q2 = base + w.d_q2, *kv2 = base + w.d_kv2, *o2 = base + w.d_o2, *lse2 = base + w.d_lse2, *a2 = base + w.d_a2,
-            *u = base + w.d_u;
-      const float* einw = P + lo.dec(i, D_EINW);
-      float* geinw = Gq + lo.dec(i, D_EINW);
-      float* geinb = Gq + lo.dec(i, D_EINB);
-      const float* sinw = P + lo.dec(i, D_SINW);
-      float* gsinw = Gq + lo.dec(i, D_SINW);
-      float* gsinb = Gq + lo.dec(i, D_SINB);
-      const int dd = d * d;
-      {  // FFN + mask + enc_attn.out_proj reverse -> dO2 (s1)
-        adt::BwdChainArgs a = BA(dec, p, seed);
-        a.site1 = dec_site(i, 2); a.site2 = dec_site(i, 3);
-        a.gy = gy; a.u = u; a.xin = a2; a.o = o2; a.saved_bf16 = lean;
-        a.W0 = P + lo.dec(i, D_C2W); a.W1 = P + lo.dec(i, D_C1W); a.W2 = P + lo.dec(i, D_EOW);
-        a.dW0 = Gq + lo.dec(i, D_C2W); a.dW1 = Gq + lo.dec(i, D_C1W); a.dW2 = Gq + lo.dec(i, D_EOW);
-        a.db0 = Gq + lo.dec(i, D_C2B); a.db1 = Gq + lo.dec(i, D_C1B); a.db2 = Gq + lo.dec(i, D_EOB);
-        a.out0 = s1;
-        a.part[0] = PART(i, PS_D_C2); a.part[1] = PART(i, PS_D_C1); a.part[2] = PART(i, PS_D_EO); a.part_stride = (size_t)w.part_stride;
-        a.vpart = VPART(i, 0);
-        const int rc = use_seq ? adt_launch_seq_post_bwd(hd, 0, a, st) : 1;
-        if (rc < 0) return rc;
-        if (rc && parts) return adt_set_error(no_fallback, L, hd);
-        if (rc) CK(adt_launch_bwdchain(prec, 1, a, st));
-      }
-      if (logits_side == 1) {
-        void* s2 = nullptr;
-        CK(side_enter(sd, 0, st, &s2));
-        if (!prep_zeroed && adt::zero_f32_async(ws + w.rep, (size_t)NREP * w.rep_stride, (hipStream_t)s2)) return adt_set_error("replica zero");
-        CK(logits_scatter(s2));
-        logits_side = 2;
-      }
-      // cross attention core: dq2 -> s5, dkv2 -> s4
-      if (lean) {
-        const uint16_t* kvb = reinterpret_cast<const uint16_t*>(kv2);      // rows of 128 bf16: k2 | v2
-        // dq2 / dk2 / dv2 go to k_seqtt_mid_bwd only (with `parts` a "not covered" from it is an error), which builds bf16 MFMA operands from
-        // them: written as bf16 rows (the same rounding, half the bytes); s4 + d / 2 floats = 64 bf16 elements into the (k | v) row
-        CK(adt_attn_bwd_saved_bf16(q2, d, kvb, 2 * d, kvb + d, 2 * d, o2, d, lse2, s1, d, B, H, L, hd, p, seed, dec_site(i, 1), b_offset,
-                                   s5, d, s4, 2 * d, parts ? s4 + d / 2 : s4 + d, 2 * d, reinterpret_cast<const uint32_t*>(base + w.d_mask2), parts ? 1 : 0, st));
-      } else {
-        CK(adt_attn_bwd(prec, q2, d, kv2, 2 * d, kv2 + d, 2 * d, o2, d, lse2, s1, d, B, H, L, hd, 1, p, seed, dec_site(i, 1), b_offset,
-                        s5, d, s4, 2 * d, s4 + d, 2 * d, reinterpret_cast<const uint32_t*>(base + w.d_mask2), st));
-      }
-      if (logits_side == 2) { CK(side_join(sd, 0, st)); logits_side = 0; }      // d log_feats is complete from here on
-      if (logits_side == 3) {
-        SideStream* const sl = ((side_sites() & 1) && !bce_merged()) ? side_stream((hipStream_t)st) : nullptr;
-        if (sl && hipStreamWaitEvent((hipStream_t)st, sl->join_ev[0], 0) != hipSuccess) return adt_set_error("backward: logits join");
-        logits_side = 0;
-      }
-      int mid_rc = 1;
-      if (use_seq) {   // both projections' reverse in one launch per sequence (adt_seqpost_tt.cuh)
-        adt::BwdChainArgs a = BA(dec, 0.f, nullptr);
-        a.dqkv = s5; a.lddqkv = d; a.xin = a1; a.o = o1; a.saved_bf16 = lean; a.dkv2 = s4; a.f = f; a.grad_bf16 = (lean && parts) ? 1 : 0;
-        a.W0 = einw; a.W1 = P + lo.dec(i, D_SOW); a.W2 = einw + dd; a.W3 = einw + 2 * dd;
-        a.dW0 = geinw; a.dW1 = Gq + lo.dec(i, D_SOW); a.dW2 = geinw + dd; a.dW3 = geinw + 2 * dd;
-        a.db0 = geinb; a.db1 = Gq + lo.dec(i, D_SOB); a.db2 = geinb + d; a.db3 = geinb + 2 * d;
-        a.out0 = s1; a.out1 = gf; a.acc1 = 1;
-        a.part[0] = PART(i, PS_D_EIN); a.part[1] = PART(i, PS_D_SO); a.part[2] = PART(i, PS_D_EIN + 1); a.part[3] = PART(i, PS_D_EIN + 2);
-        a.part_stride = (size_t)w.part_stride;
-        a.vpart = VPART(i, 1);
-        mid_rc = adt_launch_seq_mid_bwd(hd, a, st);
-        if (mid_rc < 0) return mid_rc;
-        if (mid_rc && parts) return adt_set_error(no_fallback, L, hd);
-      }
-      if (mid_rc) {
-        {  // q2 = a1 Wq^T, a1 = o1 Wo1^T  -> dO1 (s1)
-          adt::BwdChainArgs a = BA(dec, 0.f, nullptr);
-          a.dqkv = s5; a.lddqkv = d; a.xin = a1; a.o = o1; a.saved_bf16 = lean;
-          a.W0 = einw; a.W1 = P + lo.dec(i, D_SOW);
-          a.dW0 = geinw; a.dW1 = Gq + lo.dec(i, D_SOW); a.db0 = geinb; a.db1 = Gq + lo.dec(i, D_SOB);
-          a.out0 = s1;
-          CK(adt_launch_bwdchain(prec, 4, a, st));
-        }
-        {  // [k2, v2] = f Wkv^T  -> g_f +=
-          adt::BwdChainArgs a = BA(dec, 0.f, nullptr);
-          a.dkv2 = s4; a.f = f;
-          a.W0 = einw + dd; a.W1 = einw + 2 * dd;
-          a.dW0 = geinw + dd; a.dW1 = geinw + 2 * dd; a.db0 = geinb + d; a.db1 = geinb + 2 * d;
-          a.out0 = gf; a.acc0 = 1;
-          CK(adt_launch_bwdchain(prec, 5, a, st));
-        }
-      }
-      bool fused_blk = false;
-      if (adt_seq_supported(prec, L, d, hd)) {   // self-attention backward + layer_norm / in-projection backward in one launch per sequence
-        adt::SeqBwdArgs a = seq_bwd_args(L, (int)w.B, H, dec, p, seed, dec_site(i, 0), b_offset, hd);
-        a.x = x; a.gamma = P + lo.dec(i, D_LNW); a.beta = P + lo.dec(i, D_LNB); a.Win = sinw; a.bin = P + lo.dec(i, D_SINB);
-        a.dO = s1; a.o = o1; a.lse = lse1; a.mask = reinterpret_cast<const uint32_t*>(base + w.d_mask1); a.dres = gy;
-        a.gx = gx; a.acc = i > 0 ? 1 : 0; a.dWin = gsinw; a.dbin = gsinb; a.dgamma = Gq + lo.dec(i, D_LNW); a.dbeta = Gq + lo.dec(i, D_LNB);
-        if (seeds_virtual && i > 0) {      // reconstruction pair (enc_in[nl - i], dec_x[i]): d / d dec_x[i] = -2 lambda (a - b) / n = coef * (x - a)
-          a.acc = 0; a.seed_other = ws + w.enc_x + (nl - i) * Td; a.seed_coef = ws + w.norms + 8 + (nl - i);
-        }
-        a.nrep = NREPP; a.rep_stride = (size_t)w.prep_stride; a.wp_base = P + lo.posw(); a.wp_img = ws + w.wpack; a.saved_bf16 = lean;
-        a.part = PART(i, PS_D_SIN); a.part_stride = (size_t)w.part_stride;
-        a.vpart = VPART(i, 2);
-        a.nsplit = a.part ? attn_split((int)w.B) : 1;
-        time_mark(2, i, true, st);
-        const int rc = adt_launch_seq_attn_pre_bwd(hd, 1, a, st);
-        time_mark(2, i, false, st);
-        if (rc < 0) return rc;
-        if (rc != 0 && lean) return adt_set_error("backward: the lean forward needs the fused attention-block backward (L=%d hd=%d)", L, hd);
-        fused_blk = rc == 0;
-      }
-      if (!fused_blk) {
-        CK(adt_attn_bwd(prec, qkv, 3 * d, qkv + d, 3 * d, qkv + 2 * d, 3 * d, o1, d, lse1, s1, d, B, H, L, hd, 1, p, seed,
-                        dec_site(i, 0), b_offset, s3, 3 * d, s3 + d, 3 * d, s3 + 2 * d, 3 * d,
-                        reinterpret_cast<const uint32_t*>(base + w.d_mask1), st));
-        {  // layer_norm + packed in_proj reverse: gx (+)= LN'(dqkv Win + gy*mask)
-          adt::BwdChainArgs a = BA(dec, 0.f, nullptr);
-          a.dqkv = s3; a.lddqkv = 3 * d; a.gy = gy; a.xin = x;
-          a.W0 = sinw; a.W1 = sinw + dd; a.W2 = sinw + 2 * dd; a.gamma = P + lo.dec(i, D_LNW); a.beta = P + lo.dec(i, D_LNB);
-          a.dW0 = gsinw; a.dW1 = gsinw + dd; a.dW2 = gsinw + 2 * dd; a.db0 = gsinb; a.db1 = gsinb + d; a.db2 = gsinb + 2 * d;
-          a.dgamma = Gq + lo.dec(i, D_LNW); a.dbeta = Gq + lo.dec(i, D_LNB);
-          a.out0 = gx; a.acc0 = i > 0 ? 1 : 0;
-          CK(adt_launch_bwdchain(prec, 3, a, st));
-        }
-      }
-    }
-    // decoder input embedding (sasrec/model.py:53-59)
-    // The decoder's input embedding gradient and the sum of the decoder blocks' partials need nothing from the encoder chain: in a
-    // one-phase backward they run on the side stream under it (joined in front of the last fold); in the two-phase form the sum runs
-    // beside the embedding gradient.  k_dwpart_reduce adds with atomics and k_replica_reduce2 read-modify-writes the same range of G:
-    // the fold always comes behind the join.
-    // (embed3: the decoder embedding's rows go out with the encoder's at the very end -- with the sums left to the optimizer's fold there is then
-    // nothing for the side stream here, and no fork)
-    if (phase == 0 && sd && (side_sites() & 2) && !(embed3 && (late_parts || !parts))) {
-      CK(side_mark(sd, 1, st));
-      dec_side = 1;                      // enqueued behind the first kernel of the encoder phase
-    } else if (phase == 0) {
-      if (!det && !embed3) CK(adt_embed_bwd_rep(dec, ws + w.g_dec_x, T, L, d, p, seed, SITE_EMB_DEC, ro, G + lo.posw(), ws + w.rep, NREP, w.rep_stride, st));
-    } else if (det) {      // two-phase form: the decoder blocks' partial sums and the fold of the decoder range (nothing of the tables yet)
-      if (parts) CK(reduce_partials(c, lo, w, G, ws, false, true, st));
-      CK(adt_replica_reduce(G + dec_begin, Gq + dec_begin, lo.total - dec_begin, NREPP, w.prep_stride, st));
-    } else {
-      void* s2 = nullptr;
-      CK(side_mark(sd, 1, st));
-      if (!embed3) CK(adt_embed_bwd_rep(dec, ws + w.g_dec_x, T, L, d, p, seed, SITE_EMB_DEC, ro, G + lo.posw(), ws + w.rep, NREP, w.rep_stride, st));
-      CK(side_enter(sd, 1, st, &s2));
-      if (parts) CK(reduce_partials(c, lo, w, G, ws, false, true, s2));
-      CK(side_join(sd, 1, st));
-      CK(adt_replica_reduce2(G + lo.item(), ws + w.rep, (int64_t)(c->item_num + 1) * d, NREP, w.rep_stride, G + dec_begin, Gq + dec_begin,
-                             lo.total - dec_begin, NREPP, w.prep_stride, st));
-    }
-  }
-  if (phase == 0 || phase == 2) {
-    // last_layernorm: g_enc_x[nl] = LN'(g_f) -- inside the last encoder block's first backward kernel when that is the per-sequence kernel
-    // with stored vector sums (k_seqtt_post_bwd<ENC>: BwdChainArgs::lnl_x)
-    const bool lnl_fused = parts && use_seq && lnl_fuse_on();      // (without the stored sums: float atomics into the replicas, like its other vectors)
-    if (lnl_fused) {
-      // (nothing to launch: BwdChainArgs::lnl_x of the first encoder kernel below)
-    } else if (late_parts) {
-      const int nb = adt_layernorm_bwd_parts(gf, d, ws + w.enc_x + nl * Td, d, P + lo.lnl_w(), LN_EPS, T, d, ws + w.g_enc_x + nl * Td, d, 0,
-                                             ws + w.lnpart, LN_PART_BLOCKS, st);
-      if (nb < 0) return nb;
-    } else
-    CK(adt_layernorm_bwd_rep(gf, d, ws + w.enc_x + nl * Td, d, P + lo.lnl_w(), LN_EPS, T, d, ws + w.g_enc_x + nl * Td, d, 0,
-                             Gq + lo.lnl_w(), Gq + lo.lnl_b(), NREPP, w.prep_stride, st));
-    auto dec_side_enter = [&]() -> int {      // behind the first kernel of the encoder phase (which keeps the caller's queue)
-      if (dec_side != 1) return 0;
-      void* s2 = nullptr;
-      CK(side_enter(sd, 1, st, &s2));
-      if (!det && !embed3) CK(adt_embed_bwd_rep(dec, ws + w.g_dec_x, T, L, d, p, seed, SITE_EMB_DEC, ro, G + lo.posw(), ws + w.rep, NREP, w.rep_stride, s2));
-      if (parts && !late_parts) { CK(reduce_partials(c, lo, w, G, ws, false, true, s2)); dec_parts_done = true; }
-      dec_side = 2;
-      return 0;
-    };
-    if (!lnl_fused) CK(dec_side_enter());
-    for (int i = nl - 1; i >= 0; --i) {
-      float* gy = ws + w.g_enc_x + (i + 1) * Td;
-      float* gx = ws + w.g_enc_x + i * Td;     // already holds the reconstruction seed for enc_in[i]
-      const float* x = ws + w.enc_x + i * Td;
-      float* base = ws + i * w.e_stride;
-      float *qkv = base + w.e_qkv, *o = base + w.e_o, *lse = base + w.e_lse, *h = base + w.e_h, *u = base + w.e_u,
-            *rec = base + w.e_rec;
-      const float* inw = P + lo.enc(i, E_INW);
-      float* ginw = Gq + lo.enc(i, E_INW);
-      float* ginb = Gq + lo.enc(i, E_INB);
-      const int dd = d * d;
-      {  // FFN + mask + forward_layernorm + out_proj reverse -> dh (s5), dO (s1)
-        adt::BwdChainArgs a = BA(seq, p, seed);
-        a.site1 = enc_site(i, 1); a.site2 = enc_site(i, 2);
-        a.gy = gy; a.u = u; a.xin = h; a.o = o; a.saved_bf16 = lean;
-        a.W0 = P + lo.enc(i, E_C2W); a.W1 = P + lo.enc(i, E_C1W); a.W2 = P + lo.enc(i, E_OW);
-        a.gamma = P + lo.enc(i, E_LN2W); a.beta = P + lo.enc(i, E_LN2B);
-        a.dW0 = Gq + lo.enc(i, E_C2W); a.dW1 = Gq + lo.enc(i, E_C1W); a.dW2 = Gq + lo.enc(i, E_OW);
-        a.db0 = Gq + lo.enc(i, E_C2B); a.db1 = Gq + lo.enc(i, E_C1B); a.db2 = Gq + lo.enc(i, E_OB);
-        a.dgamma = Gq + lo.enc(i, E_LN2W); a.dbeta = Gq + lo.enc(i, E_LN2B);
-        a.out0 = s5; a.out1 = s1;
-        int which = 0;
-        if (H > 1 && H <= 4) {   // independence-head classifier reverse, fused (sasrec/modules.py:648-649; main.py:160-169)
-          which = H <= 2 ? 6 : 7;
-          a.rec = rec; a.drec = ws + w.g_rec + i * recsz; a.Ws = P + lo.enc(i, E_SW); a.dWs = Gq + lo.enc(i, E_SW);
-          a.dbs = Gq + lo.enc(i, E_SB); a.H = H;
-        }
-        a.part[0] = PART(i, PS_E_C2); a.part[1] = PART(i, PS_E_C1); a.part[2] = PART(i, PS_E_O); a.part_stride = (size_t)w.part_stride;
-        a.vpart = VPART(i, 3);
-        if (lnl_fused && i == nl - 1) {
-          a.gy = gf; a.lnl_x = ws + w.enc_x + nl * Td; a.lnl_gamma = P + lo.lnl_w(); a.lnl_eps = LN_EPS;
-          a.vpart2 = late_parts ? ws + w.vpart + (int64_t)(5 * nl) * w.vcall : nullptr;
-          a.lnl_dgamma = Gq + lo.lnl_w(); a.lnl_dbeta = Gq + lo.lnl_b();
-        }
-        const int rc = use_seq ? adt_launch_seq_post_bwd(hd, 1, a, st) : 1;
-        if (rc < 0) return rc;
-        if (rc && parts) return adt_set_error(no_fallback, L, hd);
-        if (lnl_fused && i == nl - 1) CK(dec_side_enter());
-        if (rc) CK(adt_launch_bwdchain(prec, which, a, st));
-      }
-      if (H > 4)   // wider classifiers: separate kernel
-        CK(adt_headcls_bwd(o, d, P + lo.enc(i, E_SW), rec, ws + w.g_rec + i * recsz, (int)w.B, L, H, hd, s1, d, G + lo.enc(i, E_SW),
-                           G + lo.enc(i, E_SB), st));
-      bool fused_blk = false;
-      if (use_seq) {   // attention backward + LayerNorm / in-projection backward in one launch per sequence (adt_seqbwd_tt.cuh)
-        adt::SeqBwdArgs a = seq_bwd_args(L, (int)w.B, H, seq, p, seed, enc_site(i, 0), b_offset, hd);
-        a.x = x; a.gamma = P + lo.enc(i, E_LN1W); a.beta = P + lo.enc(i, E_LN1B); a.Win = inw; a.bin = P + lo.enc(i, E_INB);
-        a.dO = s1; a.o = o; a.lse = lse; a.mask = reinterpret_cast<const uint32_t*>(base + w.e_mask); a.dres = s5;
-        a.gx = gx; a.acc = 1; a.dWin = ginw; a.dbin = ginb; a.dgamma = Gq + lo.enc(i, E_LN1W); a.dbeta = Gq + lo.enc(i, E_LN1B);
-        if (seeds_virtual) {               // reconstruction pair (enc_in[i], dec_x[nl - i]): d / d enc_in[i] = coef * (x - b)
-          a.acc = 0; a.seed_other = ws + w.dec_x + (nl - i) * Td; a.seed_coef = ws + w.norms + 8 + i;
-          if (i > 0) { a.seed_loss = ws + w.loss + 64 * (2 + i); a.seed_norms = ws + w.norms; }      // pair i >= 1 is not touched by the loss pass at all
-        }
-        a.nrep = NREPP; a.rep_stride = (size_t)w.prep_stride; a.wp_base = P + lo.posw(); a.wp_img = ws + w.wpack; a.saved_bf16 = lean;
-        a.part = PART(i, PS_E_IN); a.part_stride = (size_t)w.part_stride;
-        a.vpart = VPART(i, 4);
-        a.nsplit = a.part ? attn_split((int)w.B) : 1;
-        time_mark(1, i, true, st);
-        const int rc = adt_launch_seq_attn_pre_bwd(hd, 0, a, st);
-        time_mark(1, i, false, st);
-        if (rc < 0) return rc;
-        if (rc != 0 && lean) return adt_set_error("backward: the lean forward needs the fused attention-block backward (L=%d hd=%d)", L, hd);
-        fused_blk = rc == 0;
-      }
-      if (!fused_blk) {
-        CK(adt_attn_bwd(prec, qkv, 3 * d, qkv + d, 3 * d, qkv + 2 * d, 3 * d, o, d, lse, s1, d, (int)w.B, H, L, hd, 1, p, seed,
-                        enc_site(i, 0), b_offset, s3, 3 * d, s3 + d, 3 * d, s3 + 2 * d, 3 * d,
-                        reinterpret_cast<const uint32_t*>(base + w.e_mask), st));
-        {  // attention_layernorm + in_proj reverse: gx += LN'(dq Wq + dh) + dk Wk + dv Wv
-          adt::BwdChainArgs a = BA(seq, 0.f, nullptr);
-          a.dqkv = s3; a.lddqkv = 3 * d; a.dh = s5; a.xin = x;
-          a.W0 = inw; a.W1 = inw + dd; a.W2 = inw + 2 * dd; a.gamma = P + lo.enc(i, E_LN1W); a.beta = P + lo.enc(i, E_LN1B);
-          a.dW0 = ginw; a.dW1 = ginw + dd; a.dW2 = ginw + 2 * dd; a.db0 = ginb; a.db1 = ginb + d; a.db2 = ginb + 2 * d;
-          a.dgamma = Gq + lo.enc(i, E_LN1W); a.dbeta = Gq + lo.enc(i, E_LN1B);
-          a.out0 = gx; a.acc0 = 1;
-          CK(adt_launch_bwdchain(prec, 2, a, st));
-        }
-      }
-    }
-    if (phase == 2 && !det && adt::zero_f32_async(ws + w.rep, (size_t)NREP * w.rep_stride, (hipStream_t)st)) return adt_set_error("replica zero");
-    // the sum of the encoder blocks' partials runs beside the embedding gradient ; the fold (read-modify-write of the same range) behind both.
-    // The side stream is in order: the join behind that sum also covers the decoder's work queued on it earlier -- a join of its own in front
-    // of the embedding gradient was one more cross-queue wait (5-9 us) on the caller's stream.
-    {
-      // (nothing to put beside the embedding gradient when the optimizer's fold sums the partials: no empty fork / join pair then)
-      SideStream* const sd2 = ((side_sites() & 4) && parts && !late_parts) ? sd : nullptr;
-      if (dec_side == 2 && !sd2) CK(side_join(sd, 1, st));
-      dec_side = 0;
-      void* s2 = nullptr;
-      CK(side_mark(sd2, 2, st));
-      if (det) {
-        // item table: every item's rows (encoder ids, decoder ids, positive / negative items of the logits) summed by one owner in sorted
-        // order ; positional table: one owner per position.  (sasrec/model.py:34-41, :53-59, :72-76 reversed)
-        if (sd_sort && hipStreamWaitEvent((hipStream_t)st, sd_sort->join_ev[3], 0) != hipSuccess) return adt_set_error("backward: sort join");
-        const uint32_t site4[4] = {SITE_EMB_SEQ, SITE_EMB_DEC, 0u, 0u};
-        const int32_t* const ids2[2] = {seq, dec};
-        const float* const dx2[2] = {ws + w.g_enc_x, ws + w.g_dec_x};
-        CK(adt_item_segsum_posemb(iwork, 4, T, c->item_num + 1, 0xFu, site4, p, seed, sqrtf((float)d), G + lo.item(), prep_zeroed ? 0 : 1,
-                                  ids2, dx2, site4, 2, (int)w.B, L, ro, G + lo.posw(), st));
-      } else if (embed3) {      // encoder + decoder embedding rows + the positive-logit rows: one atomic row-add per token where their ids line up
-        CK(adt_embed_bwd3(seq, dec, pos, ws + w.g_enc_x, ws + w.g_dec_x, f, ws + w.g_pos, T, L, p, seed, SITE_EMB_SEQ, SITE_EMB_DEC, ro, G + lo.posw(),
-                          ws + w.rep, NREP, w.rep_stride, st));
-      } else {
-        CK(adt_embed_bwd_rep(seq, ws + w.g_enc_x, T, L, d, p, seed, SITE_EMB_SEQ, ro, G + lo.posw(), ws + w.rep, NREP, w.rep_stride, st));
-      }
-      CK(side_enter(sd2, 2, st, &s2));
-      if (parts && !late_parts) CK(reduce_partials(c, lo, w, G, ws, true, phase == 0 && !dec_parts_done, s2));
-      CK(side_join(sd2, 2, st));
-    }
-    if (!defer_fold)
-      CK(adt_replica_reduce2(G + lo.item(), ws + w.rep, (int64_t)(c->item_num + 1) * d, det ? 0 : NREP, w.rep_stride, G + lo.posw(), Gq + lo.posw(),
-                             (phase == 0 ? lo.total : dec_begin) - lo.posw(), NREPP, w.prep_stride, st));
-  }
+  return adt_sasrec_backward_prefetch(c, P, G, ws, seq, dec, pos, neg, B, training, seed, b_offset, phase, nullptr, 0, 0, nullptr, nullptr, nullptr, st);
+}
+
+int adt_sasrec_backward_prefetch(const adt_sasrec_cfg* c, const float* P, float* G, float* ws, const int32_t* seq, const int32_t* dec,
+                                 const int32_t* pos, const int32_t* neg, int B, int training, const uint32_t* seed, uint32_t b_offset, int phase,
+                                 const int32_t* ring, int64_t slot_ints, int nslots, uint32_t* state, uint32_t* consumed, int32_t* staging, void* st) {
+  Bwd x;
+  const adt::RingPrefetchArgs rr{ring, (size_t)slot_ints, nslots, (size_t)(4 * (int64_t)B * c->maxlen + 4), state, consumed, staging, 1, 2};
+  CK(bwd_init(x, c, P, G, ws, seq, dec, pos, neg, B, training, seed, b_offset, phase, rr, st));
+  DecSide dec_side;
+  if (x.plan.phase == 0 || x.plan.phase == 1) CK(decoder_phase(x, dec_side));
+  if (x.plan.phase == 0 || x.plan.phase == 2) CK(encoder_phase(x, dec_side));
   return 0;
 }
 
 static int fold_impl(bool adam, const adt_sasrec_cfg* c, float* ws, int B, float* P, float* G, float* M, float* V, float wd, float clip, float lr,
                      float b1, float b2, float eps, float* scal, void* st) {
-  CK(check_cfg(c));
   Layout lo;
-  make_layout(c, &lo);
   WS w;
-  make_ws(c, B, &w);
+  CK(layout_ws(c, B, &lo, &w));
   float* const Gq = ws + w.prep - lo.posw();
   if (fold_sums_partials(c, w)) {
     int slots[256], offs[256];
@@ -1220,11 +1309,9 @@ int adt_sasrec_fold_grads(const adt_sasrec_cfg* c, float* ws, int B, float* P, f
 
 int adt_sasrec_predict(const adt_sasrec_cfg* c, const float* P, float* ws, const int32_t* seq, const int32_t* cand,
                        int B, int C, float* logits, int32_t* rank, void* st) {
-  CK(check_cfg(c));
   Layout lo;
-  make_layout(c, &lo);
   WS w;
-  make_ws(c, B, &w);
+  CK(layout_ws(c, B, &lo, &w));
   const int T = (int)w.T, d = (int)w.d, L = (int)w.L;
   CK(encoder_forward(c, lo, w, P, ws, seq, nullptr, nullptr, 0.f, nullptr, 0, false, st));
   // final_feat = log_feats[:, -1, :]  (sasrec/model.py:89): row b*L + L-1, i.e. ld = L*d starting at (L-1)*d

@@ -158,10 +158,11 @@ class SASRecADT(FullRankMixin, torch.nn.Module):
 
     # raw launches (no autograd); ids are device int32 tensors
     def run_forward(self, seq, dec, pos, neg, B, training, b_offset=0, packed=False):
-        """packed: run_step_begin / run_step_begin_ring of THIS step already wrote the bf16 weight images (bit 1 of `training`)."""
+        """packed: run_step_begin / run_step_begin_ring of THIS step already wrote the bf16 weight images (TRAIN_PACKED)."""
         ws = self.workspace(B)
         _lib.check(self.lib.adt_sasrec_forward(ctypes.byref(self.cfg), _ptr(self.flat), _ptr(ws), _ptr(seq), _ptr(dec), _ptr(pos),
-                                               _ptr(neg), B, int(bool(training)) | (2 if packed else 0), _ptr(self._seed), b_offset, self._stream()),
+                                               _ptr(neg), B, (_lib.TRAIN_DROPOUT if training else 0) | (_lib.TRAIN_PACKED if packed else 0), _ptr(self._seed), b_offset,
+                                               self._stream()),
                    "sasrec_forward")
 
     def probe_dec_layer_forward(self, dec, B, layer, training=True, b_offset=0):
@@ -206,10 +207,10 @@ class SASRecADT(FullRankMixin, torch.nn.Module):
         ring, slot_ints, nslots, state, consumed, staging = prefetch if prefetch is not None else (None, 0, 0, None, None, None)
         deferred = bool(training) and packed and self.bce_deferred()
         side = bool(bce_side) and deferred
+        flags = (_lib.TRAIN_DROPOUT if training else 0) | (_lib.TRAIN_PACKED if packed else 0) | (_lib.TRAIN_BCE_SIDE if side else 0)
         _lib.check(self.lib.adt_sasrec_forward_loss_prefetch(ctypes.byref(self.cfg), _ptr(self.flat), _ptr(self.workspace(B)), _ptr(seq), _ptr(dec),
-                                                             _ptr(pos), _ptr(neg), B, int(bool(training)) | (2 if packed else 0) | (4 if side else 0), _ptr(self._seed),
-                                                             b_offset, l1, l2, _ptr(ring), slot_ints, nslots, _ptr(state), _ptr(consumed),
-                                                             _ptr(staging), self._stream()), "sasrec_forward_loss")
+                                                             _ptr(pos), _ptr(neg), B, flags, _ptr(self._seed), b_offset, l1, l2, _ptr(ring), slot_ints,
+                                                             nslots, _ptr(state), _ptr(consumed), _ptr(staging), self._stream()), "sasrec_forward_loss")
         return "fwd" if side else deferred
 
     def run_loss_seed(self, pos, B, lambdas1, lambdas2, zero_loss=True):
@@ -219,16 +220,23 @@ class SASRecADT(FullRankMixin, torch.nn.Module):
         fn = self.lib.adt_sasrec_loss_seed if zero_loss else self.lib.adt_sasrec_loss_seed_nz
         _lib.check(fn(ctypes.byref(self.cfg), _ptr(self.workspace(B)), _ptr(pos), B, l1, l2, self._stream()), "sasrec_loss_seed")
 
-    def run_backward(self, seq, dec, pos, neg, B, training, b_offset=0, phase=0, prezeroed=False, defer_fold=False, bce=False):
-        """prezeroed: run_step_begin / run_step_begin_ring of THIS step already zeroed the parameter-gradient replicas (bit 2 of `phase`).
-        defer_fold (phase 0 only): the last replica fold is left to run_fold_clip_adam, which must follow (bit 3).
-        bce: what run_forward_loss of this step returned (pass it to EVERY phase: bits 4 / 5 in phases 0 and 1, bit 6 in phase 2 -- that forward
-        leaves the reconstruction seeds of the block inputs to the backward kernels)."""
-        _lib.check(self.lib.adt_sasrec_backward(ctypes.byref(self.cfg), _ptr(self.flat), _ptr(self.flat_grad), _ptr(self.workspace(B)),
-                                                _ptr(seq), _ptr(dec), _ptr(pos), _ptr(neg), B, int(training), _ptr(self._seed),
-                                                b_offset, phase | (4 if prezeroed else 0) | (8 if defer_fold and phase == 0 else 0) |
-                                                ((32 if bce == "fwd" else 16) if bce and phase in (0, 1) else 0) | (64 if bce and phase == 2 else 0),
-                                                self._stream()),
+    def run_backward(self, seq, dec, pos, neg, B, training, b_offset=0, phase=0, prezeroed=False, defer_fold=False, bce=False, prefetch=None):
+        """prezeroed: run_step_begin / run_step_begin_ring of THIS step already zeroed the parameter-gradient replicas (PHASE_PREZEROED).
+        defer_fold (phase 0 only): the last replica fold is left to run_fold_clip_adam, which must follow (PHASE_DEFER_FOLD).
+        bce: what run_forward_loss of this step returned (pass it to EVERY phase: PHASE_BCE_HERE / PHASE_BCE_FWD in phases 0 and 1,
+        PHASE_SEEDS_VIRTUAL in phase 2 -- that forward leaves the reconstruction seeds of the block inputs to the backward kernels).
+        prefetch: the tuple run_forward_loss of this step got (pass it to phase 0 or 2): where that call copied half of the next batch into the
+        staging buffer, the embedding scatter here copies the other half and marks it staged."""
+        flags = phase | (_lib.PHASE_PREZEROED if prezeroed else 0) | (_lib.PHASE_DEFER_FOLD if defer_fold and phase == 0 else 0)
+        if bce and phase in (0, 1):
+            flags |= _lib.PHASE_BCE_FWD if bce == "fwd" else _lib.PHASE_BCE_HERE
+        elif bce and phase == 2:
+            flags |= _lib.PHASE_SEEDS_VIRTUAL
+        # (only a forward that launched the logits kernel itself splits the prefetch: nothing of the ring is handed on behind any other)
+        ring, slot_ints, nslots, state, consumed, staging = prefetch if prefetch is not None and bce == "fwd" else (None, 0, 0, None, None, None)
+        _lib.check(self.lib.adt_sasrec_backward_prefetch(ctypes.byref(self.cfg), _ptr(self.flat), _ptr(self.flat_grad), _ptr(self.workspace(B)),
+                                                         _ptr(seq), _ptr(dec), _ptr(pos), _ptr(neg), B, int(training), _ptr(self._seed), b_offset, flags,
+                                                         _ptr(ring), slot_ints, nslots, _ptr(state), _ptr(consumed), _ptr(staging), self._stream()),
                    "sasrec_backward")
 
     def run_fold_clip_adam(self, B, m, v, wd, clip, lr, b1, b2, eps, scal):

@@ -110,7 +110,7 @@ class FusedTrainer:
         bce = m.run_forward_loss(seq, dec, pos, neg, B, self.lambdas1, self.lambdas2, b_offset, prefetch=prefetch, bce_side=self._bce_side)
         if not self._buckets.active:
             # ... and zeroed the parameter-gradient replicas ; the last fold of the replicas happens inside the optimizer's first kernel
-            m.run_backward(seq, dec, pos, neg, B, True, b_offset, phase=0, prezeroed=True, defer_fold=True, bce=bce)
+            m.run_backward(seq, dec, pos, neg, B, True, b_offset, phase=0, prezeroed=True, defer_fold=True, bce=bce, prefetch=prefetch)
             m.run_fold_clip_adam(B, self.m, self.v, self.wd, self.clip, self.lr, self.betas[0], self.betas[1], self.eps, self.scal)
             return
         elif self._dp_phases == 1:
@@ -118,7 +118,7 @@ class FusedTrainer:
             # gradient, one all-reduce of its 1.46 MB, then weight-decay term + clip + Adam on every rank.  The two-bucket form below hides
             # the decoder's 0.3 MB behind the encoder backward but runs the atomics-and-replicas backward on one stream: 0.663 against
             # 0.63 ms per step on one rank (ADT_DP_PHASES=2 selects it).
-            m.run_backward(seq, dec, pos, neg, B, True, b_offset, phase=0, prezeroed=True, defer_fold=True, bce=bce)
+            m.run_backward(seq, dec, pos, neg, B, True, b_offset, phase=0, prezeroed=True, defer_fold=True, bce=bce, prefetch=prefetch)
             m.run_fold_grads(B, self.scal)
             self._buckets.whole(m.flat_grad)
         else:
@@ -127,7 +127,7 @@ class FusedTrainer:
             # (item/pos tables at flat offset 0) -- that bucket is reduced after phase 2, so nothing is lost.
             m.run_backward(seq, dec, pos, neg, B, True, b_offset, phase=1, prezeroed=True, bce=bce)
             self._buckets.tail_ready()
-            m.run_backward(seq, dec, pos, neg, B, True, b_offset, phase=2, prezeroed=True, bce=bce)      # the gradient buffer's table rows are still zero
+            m.run_backward(seq, dec, pos, neg, B, True, b_offset, phase=2, prezeroed=True, bce=bce, prefetch=prefetch)      # the gradient buffer's table rows are still zero
             self._buckets.finish()
         ops.clip_adam_pre(m.flat, m.flat_grad, self.m, self.v, (m.item_num + 1) * m.hidden_units, self.wd, self.clip, self.lr,
                           self.betas[0], self.betas[1], self.eps, self.scal)

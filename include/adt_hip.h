@@ -380,8 +380,11 @@ int64_t adt_sasrec_workspace_floats(const adt_sasrec_cfg* cfg, int B);
 #define ADT_WS_SCAL 13      /* 192 floats for adt_clip_adam                                                    */
 int64_t adt_sasrec_ws_offset(const adt_sasrec_cfg* cfg, int B, int what, int layer);
 
-/* SASRecADT.forward (sasrec/model.py:67-81).  ids are device int32 (B*L).  training bit 0 enables dropout; bit 1 (value 2): the bf16
- * weight images of this step were already packed by adt_sasrec_step_begin / _ring (the forward then skips its own packing launch). */
+/* The `training` word of adt_sasrec_forward / adt_sasrec_forward_loss*: a sum of */
+#define ADT_TRAIN_DROPOUT 1      /* dropout on */
+#define ADT_TRAIN_PACKED 2       /* the bf16 weight images of this step were already packed by adt_sasrec_step_begin* (no packing launch here) */
+#define ADT_TRAIN_BCE_SIDE 4     /* adt_sasrec_forward_loss* on the deferred path only, with the two above: see there */
+/* SASRecADT.forward (sasrec/model.py:67-81).  ids are device int32 (B*L).  training: ADT_TRAIN_DROPOUT | ADT_TRAIN_PACKED. */
 int adt_sasrec_forward(const adt_sasrec_cfg* cfg, const float* params, float* ws, const int32_t* seq,
                        const int32_t* dec, const int32_t* pos, const int32_t* neg, int B, int training,
                        const uint32_t* seed, uint32_t b_offset, void* stream);
@@ -429,7 +432,7 @@ int adt_sasrec_loss_seed(const adt_sasrec_cfg* cfg, float* ws, const int32_t* po
  * slots = 0, NORMS = norms_src[0..4), *seed += seed_inc (the per-step dropout stream), scal[128..192) = 0 and scal[64..128) = partial sums of
  * ||item table||^2 (the weight-decay term of adt_clip_adam_pre; the parameters do not change in between).  The same launch zeroes the
  * parameter-gradient replicas the backward chains flush into and, in bf16 mode, packs the step's weight images (adt_pack_wimg's work):
- * tell the forward (training | 2) and the backward (phase | 4) of the same step.  Pair it with adt_sasrec_loss_seed_nz
+ * tell the forward (ADT_TRAIN_PACKED) and the backward (ADT_PHASE_PREZEROED) of the same step.  Pair it with adt_sasrec_loss_seed_nz
  * (adt_sasrec_loss_seed without its loss-slot fill) and adt_clip_adam_pre. */
 int adt_sasrec_step_begin(const adt_sasrec_cfg* cfg, float* ws, int B, uint32_t* seed, uint32_t seed_inc, const float* norms_src,
                           const float* params, float* grads, int64_t n, float* scal, void* stream);
@@ -482,40 +485,56 @@ int adt_item_segsum_posemb(const int32_t* work, int nsrc, int T, int V1, uint32_
 /* adt_sasrec_forward + adt_sasrec_loss_seed_nz of one training step (sasrec/model.py:67-81 + sasrec/main.py:151-169) in one call.  When
  * adt_sasrec_bce_deferred(cfg) is 1 (bf16, d = 64, the lean per-sequence kernels cover the shape, <= 4 blocks) and training == 3 (dropout on,
  * weight images packed by adt_sasrec_step_begin* of this step), log_feats is written by the last encoder layer's own kernel and the pos / neg
- * logits + BCE seed + BCE loss terms are NOT formed here: adt_sasrec_backward of the same step must be called with phase bit 4 (+ 16) and
+ * logits + BCE seed + BCE loss terms are NOT formed here: adt_sasrec_backward of the same step must be called with ADT_PHASE_BCE_HERE and
  * forms them in its first side kernel, which gathers the same rows.  Otherwise the two calls in sequence.  ADT_FWD_FUSED=0: never deferred. */
-/* training bit 2 (value 4, with bits 0 and 1, deferred path only): the logits / BCE / item-row kernel is launched by THIS call on the library's
- * side stream beside the loss pass (adt_sasrec_step_begin* of the step zeroed the item-table replicas); adt_sasrec_backward of the step takes
- * phase bit 5 (+ 32) instead of bit 4 and joins it. */
+/* ADT_TRAIN_BCE_SIDE (with the other two training flags, deferred path only): the logits / BCE / item-row kernel is launched by THIS call, inside
+ * the loss launch or on the library's side stream beside it (adt_sasrec_step_begin* of the step zeroed the item-table replicas);
+ * adt_sasrec_backward of the step takes ADT_PHASE_BCE_FWD instead of ADT_PHASE_BCE_HERE and joins it. */
 int adt_sasrec_bce_deferred(const adt_sasrec_cfg* cfg);
 int adt_sasrec_forward_loss(const adt_sasrec_cfg* cfg, const float* params, float* ws, const int32_t* seq, const int32_t* dec,
                             const int32_t* pos, const int32_t* neg, int B, int training, const uint32_t* seed, uint32_t b_offset,
                             const float* lambdas1, const float* lambdas2, void* stream);
-/* adt_sasrec_forward_loss + the prefetch half of adt_sasrec_step_begin_ring_staged (ring == NULL: plain adt_sasrec_forward_loss) */
+/* adt_sasrec_forward_loss + the prefetch half of adt_sasrec_step_begin_ring_staged (ring == NULL: plain adt_sasrec_forward_loss).  With
+ * ADT_TRAIN_BCE_SIDE and the one-pass embedding scatter (ADT_EMBED3) this call copies only the first half of the slot: the second half and the
+ * staged mark belong to adt_sasrec_backward_prefetch of the same step, which must be given the same ring arguments. */
 int adt_sasrec_forward_loss_prefetch(const adt_sasrec_cfg* cfg, const float* params, float* ws, const int32_t* seq, const int32_t* dec,
                                      const int32_t* pos, const int32_t* neg, int B, int training, const uint32_t* seed, uint32_t b_offset,
                                      const float* lambdas1, const float* lambdas2, const int32_t* ring, int64_t slot_ints, int nslots,
                                      uint32_t* state, uint32_t* consumed, int32_t* staging, void* stream);
-/* reverse pass: consumes the G_* buffers (destroyed), accumulates into `grads` (same layout as params).
- * phase: 0 = everything; 1 = logits + decoder stack only; 2 = last LN + encoder stack + embeddings (lets the
- * host overlap the gradient all-reduce of the decoder bucket with phase 2).  + 4: the item-table and parameter-gradient replicas were already
- * zeroed by adt_sasrec_step_begin / _ring of this step (phase 2 zeroes the item-table replicas again for its own scatter).  With phase 0 the scatter / fold kernels run on a side stream of the library under the
- * chain kernels (joined before the call returns its last launch; ADT_SIDE_STREAM=0 keeps everything on `stream`).  + 8 (with phase 0 only):
- * the last fold of the gradient replicas into `grads` is left to adt_sasrec_fold_clip_adam, which must follow.  + 16: the step's forward was
- * adt_sasrec_forward_loss on the deferred path (adt_sasrec_bce_deferred): logits, BCE seed and BCE loss terms are formed here.  + 32 (instead
- * of + 16, with + 4, phase 0 or 1): that forward was called with training bit 2 and launched the kernel itself: only its join is left.
- * + 64 (phase 2 of a two-phase backward behind such a forward; implied by + 16 / + 32): the reconstruction seeds of the block inputs were not
- * materialised by the forward -- the attention-block backward forms each from its own input rows and the other stack's. */
+/* The `phase` word of adt_sasrec_backward*: the phase proper in its low two bits plus a sum of flags. */
+#define ADT_PHASE_MASK 3            /* 0 = everything; 1 = logits + decoder stack only; 2 = last LN + encoder stack + embeddings (lets the host
+                                     * overlap the gradient all-reduce of the decoder bucket with phase 2); 3 is an error */
+#define ADT_PHASE_PREZEROED 4       /* the item-table and parameter-gradient replicas were already zeroed by adt_sasrec_step_begin* of this step
+                                     * (phase 2 zeroes the item-table replicas again for its own scatter) */
+#define ADT_PHASE_DEFER_FOLD 8      /* phase 0 only: the last fold of the gradient replicas into `grads` is left to adt_sasrec_fold_clip_adam /
+                                     * adt_sasrec_fold_grads, which must follow */
+#define ADT_PHASE_BCE_HERE 16       /* the step's forward was adt_sasrec_forward_loss on the deferred path (adt_sasrec_bce_deferred): logits, BCE
+                                     * seed and BCE loss terms are formed here */
+#define ADT_PHASE_BCE_FWD 32        /* instead of ADT_PHASE_BCE_HERE, with ADT_PHASE_PREZEROED, phase 0 or 1: that forward was called with
+                                     * ADT_TRAIN_BCE_SIDE and launched the kernel itself: only its join is left */
+#define ADT_PHASE_SEEDS_VIRTUAL 64  /* phase 2 of a two-phase backward behind such a forward (implied by the two above): the reconstruction seeds of
+                                     * the block inputs were not materialised by the forward -- the attention-block backward forms each from its
+                                     * own input rows and the other stack's */
+/* reverse pass: consumes the G_* buffers (destroyed), accumulates into `grads` (same layout as params).  With phase 0 the scatter / fold kernels
+ * run on a side stream of the library under the chain kernels (joined before the call returns its last launch; ADT_SIDE_STREAM=0 keeps
+ * everything on `stream`). */
 int adt_sasrec_backward(const adt_sasrec_cfg* cfg, const float* params, float* grads, float* ws,
                         const int32_t* seq, const int32_t* dec, const int32_t* pos, const int32_t* neg, int B,
                         int training, const uint32_t* seed, uint32_t b_offset, int phase, void* stream);
-/* The optimizer step of a single-GPU training step whose backward ran with phase 0 + 8 (and whose scal was prepared by
+/* adt_sasrec_backward behind adt_sasrec_forward_loss_prefetch(..., ring, ...) of the same step, with the same ring arguments: where that call
+ * copied only the first half of the next batch's slot, the embedding scatter at the end of this one copies the second half and marks the batch
+ * staged.  ring == NULL: plain adt_sasrec_backward. */
+int adt_sasrec_backward_prefetch(const adt_sasrec_cfg* cfg, const float* params, float* grads, float* ws,
+                                 const int32_t* seq, const int32_t* dec, const int32_t* pos, const int32_t* neg, int B,
+                                 int training, const uint32_t* seed, uint32_t b_offset, int phase, const int32_t* ring, int64_t slot_ints,
+                                 int nslots, uint32_t* state, uint32_t* consumed, int32_t* staging, void* stream);
+/* The optimizer step of a single-GPU training step whose backward ran with phase 0 + ADT_PHASE_DEFER_FOLD (and whose scal was prepared by
  * adt_sasrec_step_begin): the last fold of the gradient replicas, grad += wd * E / ||E||_F on the item table and the partial sums of
  * ||g||^2 in ONE pass over the gradient, then clip_grad_norm_(clip) + Adam (sasrec/main.py:170-173) -- adt_clip_adam_pre's result in two
  * launches instead of three.  m, v: Adam moments laid out like params. */
 int adt_sasrec_fold_clip_adam(const adt_sasrec_cfg* cfg, float* ws, int B, float* params, float* grads, float* m, float* v, float wd,
                               float clip, float lr, float b1, float b2, float eps, float* scal, void* stream);
-/* The fold half of adt_sasrec_fold_clip_adam alone: completes `grads` behind adt_sasrec_backward(phase | 8) -- no weight-decay term, no
+/* The fold half of adt_sasrec_fold_clip_adam alone: completes `grads` behind adt_sasrec_backward(phase | ADT_PHASE_DEFER_FOLD) -- no weight-decay term, no
  * norm, no optimizer step.  The data-parallel step runs it in front of the gradient all-reduce (sasrec/main.py:170 on every rank, then one
  * sum over the ranks) and adt_clip_adam_pre behind it. */
 int adt_sasrec_fold_grads(const adt_sasrec_cfg* cfg, float* ws, int B, float* params, float* grads, float* scal, void* stream);

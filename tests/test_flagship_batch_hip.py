@@ -372,3 +372,66 @@ def test_pinned_ring_prefetch_is_taken_and_exact(arm):
     p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     print(p.stdout)
     assert p.returncode == 0 and "ring-ok" in p.stdout, p.stdout[-2000:] + p.stderr[-3000:]
+
+
+def _forward_without_backward_arm():
+    """The smallest lean shape (bf16, d 64, H 2, one block, L 16, B 4, V 40).  Batches k and k + 1 are published, step k runs its first kernel and
+    its forward + loss launch with the ring arguments (which copies the FIRST half of batch k + 1 into the staging buffer) -- and then no backward.
+    Everything the forward saw (model, trainer, ring, staging) stays alive to the end."""
+    from adt_amd import ops
+    from adt_amd.sasrec.model import SASRecADT
+    from adt_amd.sasrec.trainer import FusedTrainer
+    from tests.test_hip_kernels import check, embed_bwd3_case, run_embed_bwd3
+
+    class Args:
+        device, maxlen, num_heads, num_layers, precision, hidden_units, dropout = "cuda:0", 16, 2, 1, "bf16", 64, 0.2
+    B, Ls, Vs = 4, 16, 40
+    torch.manual_seed(23)
+    m = SASRecADT(1, Vs, Args())
+    assert m.bce_deferred()
+    tr = FusedTrainer(m, [0.1], [0.05], weight_decay=1e-3, seed=3)
+    st = tr._bind(B)
+    r = np.random.RandomState(7)
+    for k in range(2):
+        seq = r.randint(1, Vs + 1, size=(B, Ls))
+        seq[:, :3] = 0
+        dec = np.roll(seq, 1, 1)
+        dec[:, 0] = 0
+        pos, neg = (r.randint(1, Vs + 1, size=(B, Ls)) * (seq > 0) for _ in range(2))
+        views, _ = tr.slot(B, k)
+        for v, a in zip(views, (seq, dec, pos, neg)):
+            v[...] = a
+        tr.publish(B, k, (float(np.count_nonzero(pos)), float(B * Ls * 64), float(B * Ls * 2)))
+    prefetch = (st["ring"], st["n_int"], tr.NSLOTS, st["state"], st["consumed"], st["staging"])
+    m.run_step_begin_ring_staged(B, st["ring"], st["n_int"], tr.NSLOTS, tr._devbuf, st["state"], st["consumed"], st["staging"], st["produced"], tr.scal)
+    bce = m.run_forward_loss(*tr._ids, B, tr.lambdas1, tr.lambdas2, prefetch=prefetch, bce_side=True)
+    assert bce == "fwd"
+    torch.cuda.synchronize()
+    before = st["state"].cpu().numpy().view(np.uint32).copy()
+    assert int(before[0]) == 1 and int(before[4]) == 2 and int(before[2]) == 0, before.tolist()      # batch 0 fetched, batch 1 seen published, nothing staged
+    # an unrelated caller of the public entry point on this thread
+    case, dE, dP = embed_bwd3_case("sampler", 0.25)
+    dE_t, dP_t = run_embed_bwd3(ops, case, 0.25)
+    torch.cuda.synchronize()
+    after = st["state"].cpu().numpy().view(np.uint32).copy()
+    assert int(after[2]) == int(before[2]), "a half-copied staging buffer was marked staged by an unrelated adt_embed_bwd3: state %s -> %s" % (
+        before.tolist(), after.tolist())
+    assert np.array_equal(after, before), (before.tolist(), after.tolist())
+    check(dE_t, dE, 2e-5, "embed_bwd3 dE")
+    check(dP_t, dP, 2e-5, "embed_bwd3 dP")
+    del tr, m
+    return True
+
+
+def test_forward_without_backward_hands_nothing_to_embed_bwd3():
+    """A forward + loss launch that was given the id ring and is not followed by its backward (an error, another trainer, a test) must leave
+    nothing behind for the next adt_embed_bwd3 of the host thread: the second half of the split ring prefetch is an argument of
+    adt_sasrec_backward_prefetch, not thread state.  (With the hand-over in thread-local variables the public adt_embed_bwd3 launched the
+    prefetch variant of its kernel with the earlier step's ring pointers and marked the half-copied staging buffer staged: state[2] 0 -> 2.)
+    The result of that adt_embed_bwd3 is the one tests/test_hip_kernels.py expects.  Own process: the switches are read once per process."""
+    env = dict(os.environ, ADT_ITEM_SORT="0", ADT_EMBED3="1")
+    code = ("import sys; sys.path.insert(0, %r); from tests.test_flagship_batch_hip import _forward_without_backward_arm; "
+            "assert _forward_without_backward_arm(); print('handoff-ok')" % REPO)
+    p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    print(p.stdout)
+    assert p.returncode == 0 and "handoff-ok" in p.stdout, p.stdout[-2000:] + p.stderr[-3000:]

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What the device sees from three steps of one trainer: the evidence that a change to the trainers' HOST code left the launches alone.
 
-    python tools/trainer_launch_sequence.py NAME            # NAME: wide bert stosa super superbert superstosa
+    python tools/trainer_launch_sequence.py NAME            # NAME: wide bert stosa super superbert superstosa flagship flagship-ring
     rocprofv3 --kernel-trace --output-format csv -d out -o NAME -- python3 tools/trainer_launch_sequence.py NAME
     python tools/trainer_launch_sequence.py --digest out/NAME_kernel_trace.csv
 
@@ -11,6 +11,14 @@ trainers run twice in the process, eagerly and with use_graph=True (eager warm-u
 have no graph mode and change their block choice between the steps.  Only public constructors and step() are used, so the same file
 runs on an older checkout.  --digest prints the length and the SHA-256 of the trace's ordered kernel list, by name alone and with grid
 and workgroup sizes; two checkouts launched the same work when the digests agree.  One trainer per process.
+
+flagship / flagship-ring: the fused SASRec-ADT step (FusedTrainer, width 64) on ids resident in HBM (stage_ring / step_staged), and through the
+pinned id ring (slot / publish / commit) with every batch published one ahead, so each step prefetches its successor and the next takes it
+from the staging buffer.  After each step they also print a SHA-256 of the gradient behind the two tables (float atomics order the table
+rows' sums by arrival; the learning rate is 0 there, so that order does not reach the weights) -- under ADT_ITEM_SORT=1, where the whole step
+is deterministic and Adam runs, of the whole gradient and of the weights instead.
+A step that launches kernels on two streams has no fixed dispatch order across them: --digest therefore prints a second, order-independent
+pair of hashes, taken over the sorted lines.
 """
 import csv
 import hashlib
@@ -23,7 +31,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 V, L, B, STEPS = 40, 16, 4, 3
-NAMES = ("wide", "bert", "stosa", "super", "superbert", "superstosa")
+NAMES = ("wide", "bert", "stosa", "super", "superbert", "superstosa", "flagship", "flagship-ring")
 CHOICE = [0.0, 0.5, 1.0]
 CANDS = [[0.2, 0.7], [0.9, 0.1], [0.2, 0.7]]         # steps 1 and 3 share a block choice, step 2 selects other candidate layers
 
@@ -75,6 +83,14 @@ def make(name, use_graph=False, dropout=0.2):
         from adt_amd.sasrec.model_wide import SASRecADTWide, WideSasrecTrainer
         m = SASRecADTWide(1, V, _args(dropout, hidden_units=50))
         return WideSasrecTrainer(m, [0.1], [0.05], weight_decay=1e-3, use_graph=use_graph, seed=3)
+    if name.startswith("flagship"):
+        from adt_amd.sasrec.model import SASRecADT
+        from adt_amd.sasrec.trainer import FusedTrainer
+        m = SASRecADT(1, V, _args(dropout, hidden_units=64))
+        # (the table rows are summed by float atomics in arrival order: with a learning rate they would carry that order into the weights and
+        # so into every later gradient; the sorted form is deterministic and keeps Adam on)
+        lr = 1e-3 if os.environ.get("ADT_ITEM_SORT", "0") != "0" else 0.0
+        return FusedTrainer(m, [0.1], [0.05], lr=lr, weight_decay=1e-3, use_graph=use_graph, seed=3)
     if name == "bert":
         from adt_amd.bert4rec.model import BertModel
         from adt_amd.bert4rec.trainer import FusedBertTrainer
@@ -114,6 +130,41 @@ def run(name):
             print("%s %s step %d loss %.9g %s" % (name, mode, i + 1, loss, loss.hex()), flush=True)
 
 
+def run_flagship(name):
+    import torch
+    sort = os.environ.get("ADT_ITEM_SORT", "0") != "0"
+    sha = lambda t: hashlib.sha256(t.detach().cpu().numpy().tobytes()).hexdigest()
+    for mode in ("eager", "graph"):
+        tr = make(name, mode == "graph")
+        m, bs = tr.model, batches(name)
+        if name == "flagship":
+            ring = tr.stage_ring(bs)
+
+        def produce(i):
+            views, _ = tr.slot(B, i)
+            for v, a in zip(views, bs[i]):
+                v[...] = a
+            tr.publish(B, i, (float(np.count_nonzero(bs[i][2])), float(B * L * m.hidden_units), float(B * L * m.num_heads)))
+        if name == "flagship-ring":
+            produce(0)
+        for i in range(STEPS):
+            if name == "flagship":
+                tr.step_staged(ring)
+            else:
+                if i + 1 < STEPS:
+                    produce(i + 1)      # published before this step is committed: the step prefetches it
+                tr.commit(B)
+            torch.cuda.synchronize()
+            loss = float(tr.loss())
+            print("%s %s step %d loss %.9g %s" % (name, mode, i + 1, loss, loss.hex()), flush=True)
+            if sort:
+                print("%s %s step %d grad sha256 %s weights sha256 %s" % (name, mode, i + 1, sha(m.flat_grad), sha(m.flat)), flush=True)
+            else:
+                print("%s %s step %d non-table grad sha256 %s" % (name, mode, i + 1, sha(m.flat_grad[m.offsets[2]:])), flush=True)
+        if name == "flagship-ring":
+            print("%s %s batches taken from staging %d" % (name, mode, int(tr._st["state"][5])), flush=True)
+
+
 def digest(path):
     rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Dispatch_Id"]))
     names = [r["Kernel_Name"] for r in rows]
@@ -121,12 +172,13 @@ def digest(path):
              for r in rows]
     sha = lambda lines: hashlib.sha256("\n".join(lines).encode()).hexdigest()
     print("%s: %d kernels, names sha256 %s, names+grid+workgroup sha256 %s" % (os.path.basename(path), len(rows), sha(names), sha(sized)))
+    print("%s: order-independent: names sha256 %s, names+grid+workgroup sha256 %s" % (os.path.basename(path), sha(sorted(names)), sha(sorted(sized))))
 
 
 if __name__ == "__main__":
     if len(sys.argv) == 3 and sys.argv[1] == "--digest":
         digest(sys.argv[2])
     elif len(sys.argv) == 2:
-        run(sys.argv[1])
+        (run_flagship if sys.argv[1].startswith("flagship") else run)(sys.argv[1])
     else:
         raise SystemExit(__doc__)
