@@ -229,8 +229,9 @@ __global__ __launch_bounds__(256) void k_logsoftmax_rows(LsmArgs a) {
       for (int j = 0; j < a.H; ++j) { v[j] = a.X[r * a.H + j]; m = fmaxf(m, v[j]); }
       float s = 0.f;
       for (int j = 0; j < a.H; ++j) s += expf(v[j] - m);
-      const float lz = m + logf(s);
-      for (int j = 0; j < a.H; ++j) a.Y[r * a.H + j] = v[j] - lz;
+      // (x - m) - log(s), not x - (m + log(s)): the latter rounds at the magnitude of m (4e-6 on a row of values near 80)
+      const float ls = logf(s);
+      for (int j = 0; j < a.H; ++j) a.Y[r * a.H + j] = (v[j] - m) - ls;
     } else {
       float sd = 0.f;
       for (int j = 0; j < a.H; ++j) { v[j] = a.dY[r * a.H + j]; sd += v[j]; }

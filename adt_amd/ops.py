@@ -472,14 +472,18 @@ def axpy(dst, src, alpha=1.0, accumulate=True, mask_ids=None, d=0):
     return dst
 
 
+def _lsm_rows(t, H):
+    return t.numel() // H if H > 0 else 0      # H < 1 is the library's to reject (AdtError), not a ZeroDivisionError here
+
+
 def log_softmax_fwd(X, H):
     Y = torch.empty_like(X)
-    _lib.check(_lib.load().adt_log_softmax_fwd(_p(_f32(X)), X.numel() // H, H, _p(Y), _stream()), "log_softmax_fwd")
+    _lib.check(_lib.load().adt_log_softmax_fwd(_p(_f32(X)), _lsm_rows(X, H), H, _p(Y), _stream()), "log_softmax_fwd")
     return Y
 
 
 def log_softmax_bwd(Y, dY, H, dX, accumulate):
-    _lib.check(_lib.load().adt_log_softmax_bwd(_p(Y), _p(_f32(dY)), Y.numel() // H, H, _p(dX), int(accumulate), _stream()), "log_softmax_bwd")
+    _lib.check(_lib.load().adt_log_softmax_bwd(_p(Y), _p(_f32(dY)), _lsm_rows(Y, H), H, _p(dX), int(accumulate), _stream()), "log_softmax_bwd")
 
 
 def grad_sumsq(G, out64):

@@ -1,4 +1,7 @@
-"""GPU parity tests of every C-ABI stage kernel against the numpy oracle on the same seeded inputs.
+"""GPU parity tests of the SASRec-ADT C-ABI stage kernels against the numpy oracle on the same seeded inputs.  The rest live in
+test_wide_kernels.py (BERT4Rec / STOSA stages), test_direct_kernels_hip.py (supernet optimiser, clip_adam_pre, axpy, log_softmax,
+padded lanes, replica scatter, posemb_bwd, logits_bwd_df), test_itemgrad_hip.py, test_lce_hip.py, test_fullrank_hip.py and
+test_stosa*_hip.py; test_ops_coverage_cpu.py requires every kernel wrapper of adt_amd/ops.py to be called by one of them.
 Tolerances (stated per precision): PREC_F32 (exact-fp32 MFMA) 2e-5 of the tensor's max magnitude;
 PREC_BF16 (bf16 operands, fp32 accumulate) 2e-2 of it."""
 import math
