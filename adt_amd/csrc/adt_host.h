@@ -66,13 +66,23 @@ int adt_seq_lean(int prec, int L, int d, int hd);           // the forward may s
 int adt_launch_seq_enc_fwd(int hd, const adt::SeqFwdArgs& a, void* stream);
 int adt_launch_seq_dec_fwd(int hd, const adt::SeqFwdArgs& a, void* stream);
 // adt_pack_wimg (pre-packed bf16 weight images) is part of the C ABI now: include/adt_hip.h; defined in adt_seq.hip
-namespace adt { struct AttnArgs; }
+#include "adt_attn_args.h"
 int adt_launch_seq_attn_bwd(int hd, const adt::AttnArgs& a, void* stream);     // 0 launched, 1 shape not covered, < 0 error
+// the argument block adt_attn_bwd_saved_bf16 launches with (for a caller that hands it to adt_launch_seq_xattn_mid_bwd instead)
+adt::AttnArgs adt_attn_bwd_saved_bf16_args(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* O, int ldo, const float* LSE,
+                                           const float* dO, int lddo, int B, int H, int L, int hd, float p, const uint32_t* seed, uint32_t site,
+                                           uint32_t b_offset, float* dQ, int lddq, float* dK, int lddk, float* dV, int lddv, const uint32_t* mask,
+                                           int out_bf16);
 // adt_attn_bwd with Q, K, V, O saved as bf16 rows (ld* of those four count bf16 elements); per-sequence kernel only: anything it does not
 // cover is an error.  Defined in adt_capi.hip.
 int adt_attn_bwd_saved_bf16(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* O, int ldo, const float* LSE,
                             const float* dO, int lddo, int B, int H, int L, int hd, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset,
                             float* dQ, int lddq, float* dK, int lddk, float* dV, int lddv, const uint32_t* mask, int out_bf16, void* stream);
+// The decoder's cross-attention backward and the mid chain behind it in one launch per sequence (adt_seqxattn_tt.cuh): `a` and `mid` are the
+// argument blocks of adt_launch_seq_attn_bwd and adt_launch_seq_mid_bwd; dq2 / dk2 / dv2 stay in registers, a.dQ / dK / dV are not written.
+// Bit-equal to the two launches.  0 launched, 1 not covered (run the two launches), < 0 error.  ADT_XATTN_FUSED=0: never covered.
+int adt_seq_xattn_mid_covered(int hd, const adt::AttnArgs& a, const adt::BwdChainArgs& mid);      // 1 covered, 0 not
+int adt_launch_seq_xattn_mid_bwd(int hd, const adt::AttnArgs& a, const adt::BwdChainArgs& mid, void* stream);
 // per-sequence backward of the token-wise chains (adt_seqpost_tt.cuh); enc: 1 encoder post chain, 0 decoder post chain; 0 launched, 1 not covered
 int adt_launch_seq_post_bwd(int hd, int enc, const adt::BwdChainArgs& a, void* stream);
 int adt_launch_seq_mid_bwd(int hd, const adt::BwdChainArgs& a, void* stream);      // dec_mid + kv chains in one launch

@@ -726,6 +726,37 @@ int dec_cross_attn_bwd(const Bwd& x, int i) {
                                  x.s5, d, s4, 2 * d, x.parts ? s4 + d / 2 : s4 + d, 2 * d, mask2, x.parts ? 1 : 0, x.st);
 }
 
+// the per-sequence mid chain's argument block (adt_seqpost_tt.cuh: both projections' reverse in one launch)
+adt::BwdChainArgs dec_mid_seq_args(const Bwd& x, int i) {
+  const WS& w = x.w; const Layout& lo = x.lo; const float* P = x.P; float* const Gq = x.Gq;
+  const int d = x.d, dd = d * d;
+  float* base = x.ws + i * w.d_stride;
+  const float* einw = P + lo.dec(i, D_EINW);
+  float* geinw = Gq + lo.dec(i, D_EINW);
+  float* geinb = Gq + lo.dec(i, D_EINB);
+  adt::BwdChainArgs a = x.BA(x.dec, 0.f, nullptr);
+  a.dqkv = x.s5; a.lddqkv = d; a.xin = base + w.d_a1; a.o = base + w.d_o1; a.saved_bf16 = x.lean; a.dkv2 = x.s4; a.f = x.f;
+  a.grad_bf16 = (x.lean && x.parts) ? 1 : 0;
+  a.W0 = einw; a.W1 = P + lo.dec(i, D_SOW); a.W2 = einw + dd; a.W3 = einw + 2 * dd;
+  a.dW0 = geinw; a.dW1 = Gq + lo.dec(i, D_SOW); a.dW2 = geinw + dd; a.dW3 = geinw + 2 * dd;
+  a.db0 = geinb; a.db1 = Gq + lo.dec(i, D_SOB); a.db2 = geinb + d; a.db3 = geinb + 2 * d;
+  a.out0 = x.s1; a.out1 = x.gf; a.acc1 = 1;
+  a.part[0] = x.PART(i, PS_D_EIN); a.part[1] = x.PART(i, PS_D_SO); a.part[2] = x.PART(i, PS_D_EIN + 1); a.part[3] = x.PART(i, PS_D_EIN + 2);
+  a.part_stride = (size_t)w.part_stride;
+  a.vpart = x.VPART(i, 1);
+  return a;
+}
+
+// the argument block of dec_cross_attn_bwd's launch on the lean path with partials (dq2 / dk2 / dv2 as bf16 rows)
+adt::AttnArgs dec_cross_attn_lean_args(const Bwd& x, int i) {
+  const WS& w = x.w; const int d = x.d;
+  float* base = x.ws + i * w.d_stride;
+  const uint16_t* kvb = reinterpret_cast<const uint16_t*>(base + w.d_kv2);      // rows of 128 bf16: k2 | v2
+  return adt_attn_bwd_saved_bf16_args(base + w.d_q2, d, kvb, 2 * d, kvb + d, 2 * d, base + w.d_o2, d, base + w.d_lse2, x.s1, d, (int)w.B, x.H, x.L, x.hd, x.p,
+                                      x.seed, dec_site(i, 1), x.b_offset, x.s5, d, x.s4, 2 * d, x.s4 + d / 2, 2 * d,
+                                      reinterpret_cast<const uint32_t*>(base + w.d_mask2), 1);
+}
+
 // enc_attn q / k / v projections and slf_attn.out_proj reverse -> dO1 (s1), g_f +=
 int dec_mid_bwd(const Bwd& x, int i) {
   const WS& w = x.w; const Layout& lo = x.lo; const float* P = x.P; float* const Gq = x.Gq;
@@ -736,16 +767,7 @@ int dec_mid_bwd(const Bwd& x, int i) {
   float* geinw = Gq + lo.dec(i, D_EINW);
   float* geinb = Gq + lo.dec(i, D_EINB);
   if (x.use_seq) {   // both projections' reverse in one launch per sequence (adt_seqpost_tt.cuh)
-    adt::BwdChainArgs a = x.BA(x.dec, 0.f, nullptr);
-    a.dqkv = x.s5; a.lddqkv = d; a.xin = a1; a.o = o1; a.saved_bf16 = x.lean; a.dkv2 = x.s4; a.f = x.f; a.grad_bf16 = (x.lean && x.parts) ? 1 : 0;
-    a.W0 = einw; a.W1 = P + lo.dec(i, D_SOW); a.W2 = einw + dd; a.W3 = einw + 2 * dd;
-    a.dW0 = geinw; a.dW1 = Gq + lo.dec(i, D_SOW); a.dW2 = geinw + dd; a.dW3 = geinw + 2 * dd;
-    a.db0 = geinb; a.db1 = Gq + lo.dec(i, D_SOB); a.db2 = geinb + d; a.db3 = geinb + 2 * d;
-    a.out0 = x.s1; a.out1 = x.gf; a.acc1 = 1;
-    a.part[0] = x.PART(i, PS_D_EIN); a.part[1] = x.PART(i, PS_D_SO); a.part[2] = x.PART(i, PS_D_EIN + 1); a.part[3] = x.PART(i, PS_D_EIN + 2);
-    a.part_stride = (size_t)w.part_stride;
-    a.vpart = x.VPART(i, 1);
-    const int rc = adt_launch_seq_mid_bwd(x.hd, a, x.st);
+    const int rc = adt_launch_seq_mid_bwd(x.hd, dec_mid_seq_args(x, i), x.st);
     if (rc <= 0) return rc;
     if (x.parts) return adt_set_error(NO_FALLBACK, x.L, x.hd);
   }
@@ -819,6 +841,16 @@ int attn_block_bwd(const Bwd& x, int i, bool dec) {
 int dec_block_backward(const Bwd& x, int i, LogitsSide& logits) {
   CK(dec_post_bwd(x, i));
   CK(logits.after_first_chain_kernel(x));
+  if (x.use_seq && x.lean && x.parts) {      // dec_cross_attn_bwd + dec_mid_bwd in one launch per sequence where covered (adt_seqxattn_tt.cuh)
+    const adt::AttnArgs at = dec_cross_attn_lean_args(x, i);
+    const adt::BwdChainArgs mid = dec_mid_seq_args(x, i);
+    if (adt_seq_xattn_mid_covered(x.hd, at, mid)) {
+      CK(logits.join(x));      // the launch adds into d log_feats: the logits side joins in front of it
+      const int rc = adt_launch_seq_xattn_mid_bwd(x.hd, at, mid, x.st);
+      if (rc) return rc < 0 ? rc : adt_set_error("backward: the fused cross-attention + mid launch refused a shape it covers (L=%d hd=%d)", x.L, x.hd);
+      return attn_block_bwd(x, i, true);
+    }
+  }
   CK(dec_cross_attn_bwd(x, i));
   CK(logits.join(x));
   CK(dec_mid_bwd(x, i));

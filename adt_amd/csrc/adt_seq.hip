@@ -1,17 +1,20 @@
 // Launchers of the per-sequence fused layer kernels (adt_seqfwd.cuh, adt_seqbwd.cuh): one workgroup per user sequence.
 #include "adt_host.h"
 #include <limits.h>
+#include <atomic>
 #include "adt_seqfwd.cuh"
 #include "adt_seqfwd_tt.cuh"
 #include "adt_seqattn.cuh"
 #include "adt_seqbwd_tt.cuh"
 #include "adt_seqpost_tt.cuh"
+#include "adt_seqxattn_tt.cuh"
 
 using namespace adt;
 
 template <class Args>
-static int seq_launch(const void* fn, size_t smem, AdtLdsOptIn& slot, int grid, const Args* args, hipStream_t s, const char* what, int nwaves = SQ_NW) {
-  return adt_launch_lds1(fn, dim3(grid), dim3(nwaves * 64), smem, *args, s, what, slot);
+static int seq_launch(const void* fn, size_t smem, AdtLdsOptIn& slot, int grid, const Args* args, hipStream_t s, const char* what, int nwaves = SQ_NW,
+                      size_t optin = 0) {
+  return adt_launch_lds1(fn, dim3(grid), dim3(nwaves * 64), smem, *args, s, what, slot, optin);
 }
 
 // ---- pre-packed weight images (adt_wave.cuh: WPack) -----------------------------------------------------------------------------
@@ -48,7 +51,9 @@ extern "C" int adt_seq_stamps_read(unsigned long long* out, int n) {      // deb
   return hipMemcpy(out, g_stamps, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
 }
 
-static int seq_stamps_mode() {      // ADT_SEQ_STAMPS=1: forward kernels; =2: the attention backward; =3: the encoder post chain backward
+// ADT_SEQ_STAMPS=1: forward kernels; =2: the attention backward; =3: the encoder post chain backward; =4: the decoder cross-attention backward
+// alone (k_seq_attn_bwd); =5: the decoder mid chain (k_seqtt_mid_bwd); =6: the two in one launch (k_seqtt_xattn_mid_bwd)
+static int seq_stamps_mode() {
   static const int st = [] {
     const int v = adt_env_int("ADT_SEQ_STAMPS", 0);
     return (v && hipMalloc(&g_stamps, 16 * 16 * sizeof(unsigned long long)) != hipSuccess) ? 0 : v;
@@ -57,6 +62,7 @@ static int seq_stamps_mode() {      // ADT_SEQ_STAMPS=1: forward kernels; =2: th
 }
 static unsigned long long* seq_stamp_buffer(bool for_attention) { return seq_stamps_mode() == (for_attention ? 2 : 1) ? g_stamps : nullptr; }
 static unsigned long long* seq_stamp_buffer_post() { return seq_stamps_mode() == 3 ? g_stamps : nullptr; }
+static unsigned long long* seq_stamp_buffer_mode(int mode) { return seq_stamps_mode() == mode ? g_stamps : nullptr; }
 
 static void seq_ablate(SeqFwdArgs& a) {
   a.stamps = seq_stamp_buffer(false);
@@ -127,6 +133,7 @@ int adt_launch_seq_attn_bwd(int hd, const AttnArgs& a, void* stream) {
   const int slot = (hd == 64 ? 0 : hd == 32 ? 3 : 6) + mode;
   AttnArgs args = a;
   args.stamps = seq_stamp_buffer(true);
+  if (!args.stamps) args.stamps = seq_stamp_buffer_mode(4);
   // smem varies with L: opt in once to the most this kernel may ask for
   return adt_launch_lds1(fns[slot], dim3(a.B), dim3(SAB_NW * 64), smem, args, (hipStream_t)stream, "seq_attn_bwd", optin[slot], ADT_LDS_MAX);
 }
@@ -179,7 +186,59 @@ int adt_launch_seq_post_bwd(int hd, int enc, const BwdChainArgs& a, void* stream
 int adt_launch_seq_mid_bwd(int hd, const BwdChainArgs& a, void* stream) {
   if (!seq_post_ok(a, hd)) return 1;
   static AdtLdsOptIn optin;
-  return seq_launch((const void*)k_seqtt_mid_bwd, SeqPostLds<4>::bytes, optin, a.B * (a.nsplit > 1 ? a.nsplit : 1), &a, (hipStream_t)stream, "seqtt_mid_bwd", SP_MID_NW);
+  BwdChainArgs args = a;
+  args.stamps = seq_stamp_buffer_mode(5);
+  return seq_launch((const void*)k_seqtt_mid_bwd, SeqPostLds<4>::bytes, optin, a.B * (a.nsplit > 1 ? a.nsplit : 1), &args, (hipStream_t)stream, "seqtt_mid_bwd", SP_MID_NW);
+}
+
+// ---- decoder cross-attention backward + mid chain in one launch per sequence (adt_seqxattn_tt.cuh) ----------------------------------------
+// `at` and `ch` are the argument blocks of the two launches it stands for (adt_launch_seq_attn_bwd, adt_launch_seq_mid_bwd); the hand-over
+// buffers at.dQ / dK / dV == ch.dqkv / dkv2 are neither written nor read.  Covered: the lean bf16 path with private weight-gradient partials,
+// one workgroup per sequence, causal, H * hd = 64, L % 4 = 0, L <= 224, saved keep bits (or no dropout), LDS within the limit.
+// ADT_XATTN_FUSED=0: never covered.
+// Launches ISSUED by this process (eager steps, warm-up and the one capture of a graph), not replays of a captured graph: a debugging aid of
+// the tests, not part of include/adt_hip.h.  Atomic: data-parallel trainers may step from several host threads.
+static std::atomic<unsigned long long> g_xattn_fused_launches{0};
+extern "C" unsigned long long adt_seq_xattn_fused_launches() { return g_xattn_fused_launches.load(); }
+
+int adt_seq_xattn_mid_covered(int hd, const AttnArgs& at, const BwdChainArgs& ch) {
+  static const int on = adt_env_on("ADT_XATTN_FUSED");
+  if (!on || !seq_post_ok(ch, hd)) return 0;
+  if (!at.in_bf16 || !at.out_bf16 || !ch.saved_bf16 || !ch.grad_bf16 || !ch.part[0] || !ch.part[1] || !ch.part[2] || !ch.part[3]) return 0;
+  if (ch.nsplit > 1 || ch.ablate) return 0;
+  if (!at.causal || at.H * hd != 64 || (at.L & 3) || at.L > 224 || at.L != ch.L || at.B != ch.B) return 0;
+  if (at.drop.thr != 0 && at.mask == nullptr) return 0;
+  if ((at.ldq % 8) || (at.ldk % 8) || (at.ldv % 8) || (at.ldo % 8) || (at.lddo % 4)) return 0;
+  // one hand-over: what the attention would write is what the mid chain would read (bf16 rows: dq2 of 64, dk2 | dv2 of 128 elements)
+  if (ch.dqkv != at.dQ || ch.lddqkv != at.lddq || at.lddq != 64 || ch.dkv2 != at.dK || at.lddk != 128 || at.lddv != 128 ||
+      reinterpret_cast<const __bf16*>(at.dV) != reinterpret_cast<const __bf16*>(at.dK) + 64)
+    return 0;
+  return xm_lds_bytes(at.L, at.H) <= ADT_LDS_MAX;
+}
+
+int adt_launch_seq_xattn_mid_bwd(int hd, const AttnArgs& at, const BwdChainArgs& ch, void* stream) {
+  if (!adt_seq_xattn_mid_covered(hd, at, ch)) return 1;
+  XattnMidArgs a{};
+  a.Q = reinterpret_cast<const __bf16*>(at.Q); a.K = reinterpret_cast<const __bf16*>(at.K); a.V = reinterpret_cast<const __bf16*>(at.V);
+  a.O = reinterpret_cast<const __bf16*>(at.O); a.ldq = at.ldq; a.ldk = at.ldk; a.ldv = at.ldv; a.ldo = at.ldo;
+  a.LSE = at.LSE; a.dO = at.dO; a.lddo = at.lddo; a.L = at.L; a.mask = at.mask; a.scale = at.scale; a.drop = at.drop;
+  a.xin = ch.xin; a.o = ch.o; a.f = ch.f; a.wp_base = ch.wp_base; a.wp_img = ch.wp_img;
+  a.W0 = ch.W0; a.W1 = ch.W1; a.W2 = ch.W2; a.W3 = ch.W3;
+  a.out0 = ch.out0; a.out1 = ch.out1; a.acc1 = ch.acc1; a.nrep = ch.nrep; a.rep_stride = ch.rep_stride;
+  a.db0 = ch.db0; a.db1 = ch.db1; a.db2 = ch.db2; a.db3 = ch.db3; a.vpart = ch.vpart;
+  for (int k = 0; k < 4; ++k) a.part[k] = ch.part[k];
+  a.part_stride = ch.part_stride;
+  a.stamps = seq_stamp_buffer_mode(6);
+  const int mode = at.drop.thr == 0 ? 0 : 1;
+  static AdtLdsOptIn optin[6];
+  const void* fns[6] = {(const void*)k_seqtt_xattn_mid_bwd<64, 0>, (const void*)k_seqtt_xattn_mid_bwd<64, 1>, (const void*)k_seqtt_xattn_mid_bwd<32, 0>,
+                        (const void*)k_seqtt_xattn_mid_bwd<32, 1>, (const void*)k_seqtt_xattn_mid_bwd<16, 0>, (const void*)k_seqtt_xattn_mid_bwd<16, 1>};
+  const int slot = (hd == 64 ? 0 : hd == 32 ? 2 : 4) + mode;
+  // smem takes one of two values with L: opt in once (during warm-up, not under capture) to the larger one this head count admits
+  const size_t most = xm_lds_bytes(224, at.H) <= ADT_LDS_MAX ? xm_lds_bytes(224, at.H) : xm_lds_bytes(128, at.H);
+  const int rc = seq_launch(fns[slot], xm_lds_bytes(at.L, at.H), optin[slot], at.B, &a, (hipStream_t)stream, "seqtt_xattn_mid_bwd", XM_NW, most);
+  if (rc == 0) ++g_xattn_fused_launches;
+  return rc;
 }
 
 // ---- sum of the per-workgroup weight-gradient partials (adt_seqbwd_tt.cuh: sb_dw_tiles) --------------------------------------------

@@ -339,6 +339,7 @@ __global__ __launch_bounds__(SP_MID_NW * 64) void k_seqtt_mid_bwd(BwdChainArgs a
   const int L = a.L, ntiles = (L + 15) / 16, npair = (L + 31) / 32;
   auto tileof = [&](int s) { const int t = tq_tile(s, w, ntiles, NW); return (t >= 0 && t % nsp == part) ? t : -1; };      // this workgroup's tiles only
   sp_replica(a);
+  SB_STAMP(0);
   const float* const ws4[4] = {a.W0, a.W1, a.W2, a.W3};
   sp_wdma<4, NW>(a, ws4, wimg);
   TT dqa[NS];
@@ -352,10 +353,13 @@ __global__ __launch_bounds__(SP_MID_NW * 64) void k_seqtt_mid_bwd(BwdChainArgs a
     a1req[s] = tt_saved_request(a.xin, row, valid, g, a.saved_bf16);
     oreq[s] = tt_saved_request(a.o, row, valid, g, a.saved_bf16);
   }
+  SB_STAMP(1);
   sp_zero_images<NW>(img0);
   if (threadIdx.x < 256) sRed[threadIdx.x] = 0.f;
   adt_wait_vm0();
+  SB_STAMP(2);
   __syncthreads();
+  SB_STAMP(3);
   // ---- A: cross-attention query projection: da1 = dq2 Wq ; dWq = dq2^T a1 ----------------------------------------------------------
   TT da1[NS];
 #pragma unroll
@@ -371,6 +375,7 @@ __global__ __launch_bounds__(SP_MID_NW * 64) void k_seqtt_mid_bwd(BwdChainArgs a
   __syncthreads();
   sb_dw_product16<NW>(img0, img1, npair, a.dW0, a.part[0] ? a.part[0] + (size_t)blockIdx.x * a.part_stride : nullptr, sRed, w, c, g);
   __syncthreads();
+  SB_STAMP(4);
   // ---- B: self-attention out_proj: dO1 = da1 Wo1 ; dWo1 = da1^T o1 --------------------------------------------------------------------
   TT dk[NS], fx[NS];
 #pragma unroll
@@ -388,6 +393,7 @@ __global__ __launch_bounds__(SP_MID_NW * 64) void k_seqtt_mid_bwd(BwdChainArgs a
   __syncthreads();
   sb_dw_product16<NW>(img0, img1, npair, a.dW1, a.part[1] ? a.part[1] + (size_t)blockIdx.x * a.part_stride : nullptr, sRed + 64, w, c, g);
   __syncthreads();
+  SB_STAMP(5);
   // ---- C: cross-attention keys: df = dk2 Wk ; dWk = dk2^T f -----------------------------------------------------------------------------
   TT df[NS], dv[NS], acc1v[NS];
 #pragma unroll
@@ -405,6 +411,7 @@ __global__ __launch_bounds__(SP_MID_NW * 64) void k_seqtt_mid_bwd(BwdChainArgs a
   __syncthreads();
   sb_dw_product16<NW>(img0, img1, npair, a.dW2, a.part[2] ? a.part[2] + (size_t)blockIdx.x * a.part_stride : nullptr, sRed + 128, w, c, g);
   __syncthreads();
+  SB_STAMP(6);
   // ---- D: cross-attention values (the X image still holds f) --------------------------------------------------------------------------
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
@@ -421,6 +428,7 @@ __global__ __launch_bounds__(SP_MID_NW * 64) void k_seqtt_mid_bwd(BwdChainArgs a
   __syncthreads();
   sb_dw_product16<NW>(img0, img1, npair, a.dW3, a.part[3] ? a.part[3] + (size_t)blockIdx.x * a.part_stride : nullptr, sRed + 192, w, c, g);
   __syncthreads();          // the last product's bias sums
+  SB_STAMP(7);
   {
     const int t = threadIdx.x;
     float* const dst[4] = {a.db0, a.db1, a.db2, a.db3};
@@ -429,6 +437,7 @@ __global__ __launch_bounds__(SP_MID_NW * 64) void k_seqtt_mid_bwd(BwdChainArgs a
       else atomicAdd(dst[t >> 6] + (t & 63), sRed[t]);
     }
   }
+  SB_STAMP(8);
 }
 
 }  // namespace adt
