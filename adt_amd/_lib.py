@@ -119,6 +119,7 @@ SIGNATURES = {
                                  _P, _U, _U, _P, _P, _P, _P, _P, _P, _I, _P]),
     "adt_dense_rows_enable": (_I, [_I]),
     "adt_dense_workspace": (_I, [_P, _L]),
+    "adt_dense_bwd_ws_bytes": (_L, [_I, _I, _I, _I]),
     "adt_dense_gradsrc": (_I, [_P, _I, _I, _I, _P, _F, _P, _U, _U, _I, _P, _I, _P, _I, _P, _P]),
     "adt_topk_masked": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
     "adt_full_rank_ws_bytes": (_L, [_I, _I, _I, _I]),

@@ -18,8 +18,7 @@
 
 namespace adt {
 
-constexpr int ROWS_NW = 8;                  // waves per workgroup
-constexpr int ROWS_PC = 256;                // output columns per weight panel
+// ROWS_NW waves per workgroup, ROWS_PC output columns per weight panel, rows_lds_bytes, DW_*: adt_wide_plan.h
 
 // position of contraction index k (0..31 inside its 32-block) in the permuted panel row: lane g reads 8 consecutive elements
 ADT_DEVICE_INLINE int rows_slot_pos(int k32) { return k32 < 16 ? ((k32 >> 2) * 8 + (k32 & 3)) : (((k32 - 16) >> 2) * 8 + 4 + (k32 & 3)); }
@@ -32,8 +31,6 @@ ADT_DEVICE_INLINE bf16x8 rows_pack(const float4& lo, const float4& hi) {
   o[4] = (__bf16)hi.x; o[5] = (__bf16)hi.y; o[6] = (__bf16)hi.z; o[7] = (__bf16)hi.w;
   return o;
 }
-
-static inline size_t rows_lds_bytes(int contraction, int pc) { return (size_t)pc * (contraction + 8) * sizeof(__bf16) + (size_t)pc * sizeof(float); }
 
 // ---- forward: Y = mask(R + R2 + dropout(act(X W^T + b))) ------------------------------------------------------------------
 // panel: rows n0..n0+pc of W (N x K) -> sW[pc][K + 8], k permuted; rows >= N are zero
@@ -328,8 +325,6 @@ __global__ __launch_bounds__(ROWS_NW * 64) void k_dense_dx_rows(DenseBwdArgs a, 
 // ds_read_b128 per operand fragment and no transposition anywhere: the staging thread that owns (octet, 4 columns) loads its
 // 8 rows x 16 bytes with coalesced 16-byte loads and writes four packed 16-byte words (the X side: 4 rows, 8-byte words).
 // acc[r] = dW[n0 + 16 nt + 4g + r][k0 + 16 kt + c].
-constexpr int DW_BN = 256, DW_BK = 128, DW_TS = 64, DW_NTH = 512;
-constexpr size_t DW_LDS_BYTES = 2 * (size_t)(8 * DW_BN * 8 + 8 * DW_BK * 8) * sizeof(__bf16);     // 96 KB
 
 struct DwStage { float4 g[8]; float4 x[4]; };
 

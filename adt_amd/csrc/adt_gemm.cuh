@@ -12,6 +12,7 @@
 // the loop.  Exact mode: fp32 tiles (stride 36) and v_mfma_f32_16x16x4_f32 through mma16<PREC_F32>.
 #pragma once
 #include "adt_common.cuh"
+#include "adt_wide_plan.h"      // tile constants (GBM, GBK, GTH, DW64_*, DWP_*) and xcd_grid
 
 namespace adt {
 
@@ -36,7 +37,6 @@ ADT_DEVICE_INLINE float act_grad(int act, float u) {
   }
 }
 
-constexpr int GBM = 128, GBK = 32, GTH = 256;   // BK = 64 measured slower at d = 256 (fewer waves per SIMD), faster only at d = 64
 constexpr int GPR = GBK / 4;   // float4 per tile row
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 gbf16x4 __attribute__((ext_vector_type(4)));
@@ -327,7 +327,6 @@ ADT_DEVICE_INLINE void xcd_tile(int n_outer, int n_inner, int& outer, int& inner
   outer = (local / n_inner) * 8 + xcd;
   inner = local % n_inner;
 }
-static inline int xcd_grid(int n_outer, int n_inner) { return n_outer < 16 ? n_outer * n_inner : (n_outer + 7) / 8 * 8 * n_inner; }
 
 // ---- forward: Y = mask(R + R2 + dropout(act(X W^T + b))) -----------------------------------------------------
 struct DenseFwdArgs {
@@ -455,7 +454,7 @@ __global__ __launch_bounds__(GTH) void k_dense_bwd_dx(DenseBwdArgs a) {
 // applied by GradSrc::at) and X go to two natural-order bf16 images, wave w computes output rows 16 w .. 16 w + 15 (four 16 x 16 tiles,
 // the G fragment shared) with both operands read through ds_read_b64_tr_b16, and the chunk count is chosen so that ~200 workgroups flush.
 // Layers of up to four 64 x 64 blocks (64 <-> 256 feed-forward layers) run one block per blockIdx.y.
-constexpr int DW64_ROWS = 128, DW64_RS = 72, DW64_NTH = 256;
+constexpr int DW64_RS = 72;
 typedef short dw64_s4 __attribute__((ext_vector_type(4)));
 typedef __bf16 dw64_b4 __attribute__((ext_vector_type(4)));
 ADT_DEVICE_INLINE bf16x8 dw64_trfrag(const __bf16* img, int row0, int col0, int c, int g) {     // feature col0 + c on the lane, 8 rows in slot order
@@ -468,7 +467,6 @@ ADT_DEVICE_INLINE bf16x8 dw64_trfrag(const __bf16* img, int row0, int col0, int 
 // part != nullptr: the workgroup's 64 x 64 product (+ its 64 bias sums) is STORED at part + (blockIdx.y * gridDim.x + blockIdx.x) * 4160 in
 // register order and k_dense_dw64_reduce adds the partials up: with ~200 workgroups flushing 4,096 float atomics each onto the same 4,096
 // addresses the flush was most of the kernel's 27.5 us at 25,600 tokens (STOSA-ADT runs it twenty times per step).
-constexpr int DW64_PART = 4096 + 64;
 __global__ __launch_bounds__(DW64_NTH) void k_dense_dw64(DenseBwdArgs a, float* part) {
   __shared__ __attribute__((aligned(16))) __bf16 sG[DW64_ROWS * DW64_RS];
   __shared__ __attribute__((aligned(16))) __bf16 sX[DW64_ROWS * DW64_RS];
@@ -587,7 +585,6 @@ __global__ __launch_bounds__(1024) void k_dense_dw64_reduce(const float* part, i
 // current one is multiplied.  The partial goes to the workspace in register order with plain 16-byte stores; k_dense_dw256_reduce folds the
 // partials into dW (32 per block, then one atomic per element: an 8-deep chain instead of a 256-deep one).  Layers of up to four 256 x 256
 // blocks (the 256 <-> 1024 feed-forward layers) run one block per blockIdx.y with the workgroups divided among the blocks.
-constexpr int DWP_TS = 32, DWP_NTH = 512, DWP_IMG = 32 * 256 * 2;
 ADT_DEVICE_INLINE int dwp_off(int row, int ch) {          // byte offset of 16-byte chunk ch of row `row` (adt_lce.cuh: lce_off<256>)
   return 4096 * (row >> 3) + 512 * (ch >> 2) + 64 * (row & 7) + 16 * ((ch & 3) ^ ((row >> 2) & 3));
 }

@@ -9,6 +9,7 @@
 #include "../../include/adt_hip.h"
 #include "adt_common.cuh"
 #include "adt_lossring_args.h"
+#include "adt_wide_plan.h"      // ADT_LDS_MAX
 
 int adt_set_error(const char* fmt, ...);
 DropCfg adt_make_drop(float p, const uint32_t* seed, uint32_t site);
@@ -29,7 +30,6 @@ static inline bool adt_aligned16(const void* p) { return (((uintptr_t)p) & 15u) 
 // Dynamic LDS a kernel has been allowed so far (hipFuncAttributeMaxDynamicSharedMemorySize): one slot per kernel instantiation, kept as a
 // function-local static (or an array of them) by its launcher.  A high-water mark, so a later launch that needs more opts in again.
 struct AdtLdsOptIn { int bytes = 0; };
-constexpr size_t ADT_LDS_MAX = 160 * 1024;      // per workgroup on gfx950
 
 // Launch fn with smem bytes of dynamic LDS: error when smem > ADT_LDS_MAX, opt in when max(smem, optin) is above what slot recorded,
 // hipLaunchKernel, adt_check_launch(what).  optin: a launcher whose smem varies per call passes the most it will ever ask for.

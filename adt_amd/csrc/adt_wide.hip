@@ -15,333 +15,104 @@
 
 using namespace adt;
 
-// ---- masked attention dispatch ---------------------------------------------------------------------------------
+static_assert(PREC_F32 == ADT_PREC_F32 && PREC_BF16 == ADT_PREC_BF16, "adt_wide_plan.h speaks of the ABI's prec values");
+
+// ---- masked attention: adt_attn_masked_plan (adt_wide_plan.h) chooses; these name the instantiation and pass its numbers -------------------
 template <int PREC, int HD, int MAXKT, bool CSK = false>
-static int launch_attn_gen(bool bwd, const AttnGenArgs& a, hipStream_t s) {
-  // bf16 operands: the forward (<= 106 VGPRs at every head size) and the backward at head size <= 64 (<= 124) fit the 128-register budget of
-  // 16 waves = 4 per SIMD: one query / key tile per wave at L = 200 instead of two, and twice the waves to cover each other's LDS and MFMA latency
-  constexpr int NWF = PREC == PREC_BF16 ? 16 : 8, NWB = (PREC == PREC_BF16 && HD <= 64) ? 16 : 8;
-  const size_t smem = bwd ? AttnGenLds<PREC, HD, MAXKT>::bwd_bytes : AttnGenLds<PREC, HD, MAXKT>::fwd_bytes;
-  if (smem > ADT_LDS_MAX) return adt_set_error("masked attention: L=%d hd=%d prec=%d needs %zu B of LDS (> 160 KB)", a.a.L, HD, PREC, smem);
+static int launch_attn_gen(const AttnPlan& p, bool bwd, const AttnGenArgs& a, hipStream_t s) {
+  constexpr int NWF = attn_resident_waves(PREC, HD, false), NWB = attn_resident_waves(PREC, HD, true);
+  static_assert(attn_resident_lds(PREC, HD, MAXKT, false) == AttnGenLds<PREC, HD, MAXKT>::fwd_bytes, "plan and kernel disagree on the LDS footprint");
+  static_assert(attn_resident_lds(PREC, HD, MAXKT, true) == AttnGenLds<PREC, HD, MAXKT>::bwd_bytes, "plan and kernel disagree on the LDS footprint");
   const void* fn = bwd ? (const void*)k_attn_gen_bwd<PREC, HD, MAXKT, NWB> : (const void*)k_attn_gen_fwd<PREC, HD, MAXKT, NWF, CSK>;
   static AdtLdsOptIn optin[2];
-  return adt_launch_lds1(fn, dim3(a.a.B * a.a.H), dim3((bwd ? NWB : NWF) * 64), smem, a, s, bwd ? "attn_masked_bwd" : "attn_masked_fwd", optin[bwd ? 1 : 0]);
+  return adt_launch_lds1(fn, dim3(a.a.B * a.a.H), dim3(p.waves * 64), p.lds_bytes, a, s, bwd ? "attn_masked_bwd" : "attn_masked_fwd", optin[bwd ? 1 : 0]);
 }
 
-// backward staged in NCH chunks of the sequence (k_attn_gen_bwd_chunked): hd = 128 always, and hd = 64 in the exact-fp32 mode at
-// L > 128, whose whole-(b, h) images (fp32: 248 KB at L = 200) do not fit the 160 KB of LDS
+// backward staged in NCH chunks of the sequence (k_attn_gen_bwd_chunked)
 template <int PREC, int HD, int MAXKT, int NCH>
-static int launch_attn_gen_bwd_chunked(const AttnGenArgs& a, hipStream_t s) {
-  constexpr int NW = 8;
-  const size_t smem = AttnChunkLds<PREC, HD, MAXKT, NCH>::bwd_bytes;
-  if (smem > ADT_LDS_MAX) return adt_set_error("masked attention bwd: L=%d hd=%d prec=%d needs %zu B of LDS (> 160 KB)", a.a.L, HD, PREC, smem);
+static int launch_attn_gen_bwd_chunked(const AttnPlan& p, const AttnGenArgs& a, hipStream_t s) {
+  static_assert(attn_chunked_lds(PREC, HD, MAXKT, NCH) == AttnChunkLds<PREC, HD, MAXKT, NCH>::bwd_bytes, "plan and kernel disagree on the LDS footprint");
+  // <PREC_F32, 128, 16, 2> (272 KB) is in the code object only: the plan streams that shape, and the host keeps no handle for what cannot be launched
+  if (attn_chunked_lds(PREC, HD, MAXKT, NCH) > ADT_LDS_MAX) return adt_set_error("masked attention bwd: the chunked backward of this shape does not fit the LDS");
   static AdtLdsOptIn optin;
-  return adt_launch_lds1((const void*)k_attn_gen_bwd_chunked<PREC, HD, MAXKT, NCH, NW>, dim3(a.a.B * a.a.H), dim3(NW * 64), smem, a, s,
+  return adt_launch_lds1((const void*)k_attn_gen_bwd_chunked<PREC, HD, MAXKT, NCH, ATTN_CHUNKED_NW>, dim3(a.a.B * a.a.H), dim3(p.waves * 64), p.lds_bytes, a, s,
                          "attn_masked_bwd(chunked)", optin);
 }
 
+// hd 16 / 32 / 64 by MAXKT; the chunked backward exists for exact fp32 at hd = 64 only
 template <int PREC, int HD>
-static int dispatch_attn_gen_l(bool bwd, const AttnGenArgs& a, hipStream_t s) {
-  if (a.a.L <= 64) return launch_attn_gen<PREC, HD, 4>(bwd, a, s);
-  if (a.a.L <= 128) return launch_attn_gen<PREC, HD, 8>(bwd, a, s);
-  if (a.a.L <= 224) {
-    if constexpr (PREC == PREC_F32 && HD == 64) {
-      if (bwd) return launch_attn_gen_bwd_chunked<PREC, HD, 16, 2>(a, s);
-    }
-    return launch_attn_gen<PREC, HD, 14>(bwd, a, s);
+static int launch_attn_gen_l(const AttnPlan& p, bool bwd, const AttnGenArgs& a, hipStream_t s) {
+  if (p.maxkt == 4) return launch_attn_gen<PREC, HD, 4>(p, bwd, a, s);
+  if (p.maxkt == 8) return launch_attn_gen<PREC, HD, 8>(p, bwd, a, s);
+  if constexpr (PREC == PREC_F32 && HD == 64) {
+    if (p.family == ATTN_CHUNKED) return launch_attn_gen_bwd_chunked<PREC, HD, 16, 2>(p, a, s);
   }
-  return adt_set_error("masked attention: L=%d > 224 unsupported", a.a.L);
+  return launch_attn_gen<PREC, HD, 14>(p, bwd, a, s);
 }
 
-// key / query chunks streamed through LDS (adt_attn_stream.cuh), grid (B*H, groups of NW 16-row tiles): hd = 256 (sasrec d = 256,
-// H = 1), and hd = 128 in the exact-fp32 mode where neither the resident forward nor the two-chunk backward fits the LDS
+// key / query chunks streamed through LDS (adt_attn_stream.cuh), grid (B*H, groups of NW 16-row tiles)
 template <int PREC, int HD>
-static int launch_attn_stream(bool bwd, const AttnGenArgs& a, hipStream_t s) {
-  constexpr int NWF = 4, NWB = 4, KCF = PREC == PREC_BF16 ? 64 : 32, KCB = 32;
-  const size_t smem = bwd ? AttnStreamLds<PREC, HD, KCB>::bwd_bytes : AttnStreamLds<PREC, HD, KCF>::fwd_bytes;
-  if (smem > ADT_LDS_MAX) return adt_set_error("masked attention: hd=%d prec=%d needs %zu B of LDS (> 160 KB)", HD, PREC, smem);
-  const void* fn = bwd ? (const void*)k_attn_stream_bwd<PREC, HD, NWB, KCB> : (const void*)k_attn_stream_fwd<PREC, HD, NWF, KCF>;
+static int launch_attn_stream(const AttnPlan& p, bool bwd, const AttnGenArgs& a, hipStream_t s) {
+  constexpr int NW = ATTN_STREAMED_NW, KCF = attn_streamed_kc(PREC, false), KCB = attn_streamed_kc(PREC, true);
+  static_assert(attn_streamed_lds(PREC, HD, KCF, false) == AttnStreamLds<PREC, HD, KCF>::fwd_bytes, "plan and kernel disagree on the LDS footprint");
+  static_assert(attn_streamed_lds(PREC, HD, KCB, true) == AttnStreamLds<PREC, HD, KCB>::bwd_bytes, "plan and kernel disagree on the LDS footprint");
+  const void* fn = bwd ? (const void*)k_attn_stream_bwd<PREC, HD, NW, KCB> : (const void*)k_attn_stream_fwd<PREC, HD, NW, KCF>;
   static AdtLdsOptIn optin[2];
-  const int nw = bwd ? NWB : NWF, groups = ((a.a.L + 15) / 16 + nw - 1) / nw;
-  return adt_launch_lds1(fn, dim3(a.a.B * a.a.H, groups), dim3(nw * 64), smem, a, s, bwd ? "attn_masked_bwd(streamed)" : "attn_masked_fwd(streamed)",
+  return adt_launch_lds1(fn, dim3(a.a.B * a.a.H, p.grid_y), dim3(p.waves * 64), p.lds_bytes, a, s, bwd ? "attn_masked_bwd(streamed)" : "attn_masked_fwd(streamed)",
                          optin[bwd ? 1 : 0]);
 }
 
-// hd = 128 (sasrec d = 256, H = 2): forward with the whole (b, h) resident, backward staged in NCH chunks
+// hd = 128: streamed (exact fp32 only), resident forward with or without the causal tile skip, chunked backward
 template <int PREC, int MAXKT, int NCH>
-static int launch_attn_gen_128(bool bwd, const AttnGenArgs& a, hipStream_t s) {
+static int launch_attn_gen_128(const AttnPlan& p, bool bwd, const AttnGenArgs& a, hipStream_t s) {
   constexpr int HD = 128;
-  if constexpr (PREC == PREC_F32) {     // exact fp32 at L > 64: 270 KB resident forward, 272 KB two-chunk backward
-    const size_t need = bwd ? AttnChunkLds<PREC, HD, MAXKT, NCH>::bwd_bytes : AttnGenLds<PREC, HD, MAXKT>::fwd_bytes;
-    if (need > ADT_LDS_MAX) return launch_attn_stream<PREC, HD>(bwd, a, s);
+  if constexpr (PREC == PREC_F32) {
+    if (p.family == ATTN_STREAMED) return launch_attn_stream<PREC, HD>(p, bwd, a, s);
   }
-  if (!bwd) {     // causal without key padding (the d = 256 SASRec template): skip the key tiles above the diagonal
-    const bool csk = a.a.causal && a.kid == nullptr && a.fill <= -1e9f;
-    return csk ? launch_attn_gen<PREC, HD, MAXKT, true>(false, a, s) : launch_attn_gen<PREC, HD, MAXKT, false>(false, a, s);
-  }
-  return launch_attn_gen_bwd_chunked<PREC, HD, MAXKT, NCH>(a, s);
+  if (p.family == ATTN_RESIDENT) return p.csk ? launch_attn_gen<PREC, HD, MAXKT, true>(p, false, a, s) : launch_attn_gen<PREC, HD, MAXKT, false>(p, false, a, s);
+  return launch_attn_gen_bwd_chunked<PREC, HD, MAXKT, NCH>(p, a, s);
 }
 
 template <int PREC>
-static int dispatch_attn_gen(bool bwd, int hd, const AttnGenArgs& a, hipStream_t s) {
-  if (hd == 16) return dispatch_attn_gen_l<PREC, 16>(bwd, a, s);
-  if (hd == 32) return dispatch_attn_gen_l<PREC, 32>(bwd, a, s);
-  if (hd == 64) return dispatch_attn_gen_l<PREC, 64>(bwd, a, s);
-  if (hd == 128) {
-    if (a.a.L <= 64) return launch_attn_gen_128<PREC, 4, 1>(bwd, a, s);
-    if (a.a.L <= 256) return launch_attn_gen_128<PREC, 16, 2>(bwd, a, s);
-    return adt_set_error("masked attention: L=%d > 256 unsupported at head_dim 128", a.a.L);
-  }
-  if (hd == 256) {
-    if (a.a.L >= 1 && a.a.L <= 256) return launch_attn_stream<PREC, 256>(bwd, a, s);
-    return adt_set_error("masked attention: L=%d outside 1..256 at head_dim 256", a.a.L);
-  }
-  return adt_set_error("masked attention: head_dim=%d unsupported (16/32/64/128/256)", hd);
+static int launch_attn(const AttnPlan& p, bool bwd, int hd, const AttnGenArgs& a, hipStream_t s) {
+  if (hd == 16) return launch_attn_gen_l<PREC, 16>(p, bwd, a, s);
+  if (hd == 32) return launch_attn_gen_l<PREC, 32>(p, bwd, a, s);
+  if (hd == 64) return launch_attn_gen_l<PREC, 64>(p, bwd, a, s);
+  if (hd == 128) return p.maxkt == 4 ? launch_attn_gen_128<PREC, 4, 1>(p, bwd, a, s) : launch_attn_gen_128<PREC, 16, 2>(p, bwd, a, s);
+  return launch_attn_stream<PREC, 256>(p, bwd, a, s);
 }
-
-template <class K, class Args>
-static int gemm_launch(K kernel, size_t smem, int grid, hipStream_t s, const Args& a, const char* what, AdtLdsOptIn& optin) {
-  return adt_launch_lds1((const void*)kernel, dim3(grid), dim3(GTH), smem, a, s, what, optin);
-}
-
 
 // ---- row-streaming kernels (adt_dense_rows.cuh): bf16 operands, contraction 64 / 128 / 256 ---------------------------------------
-static float* g_dense_ws = nullptr;      // scratch registered by the host (adt_dense_workspace): private partials of the 256 x 256 weight gradients
-static int64_t g_dense_ws_bytes = 0;
-static int g_rows_enabled = 1;
-// ADT_STAGE256=0 in the environment keeps the 256-wide forward / input-gradient stage kernels (k_dense_fwd256, k_dense_dx256) off: A/B runs
-static bool stage_kernels_on() {
-  static const int on = adt_env_on("ADT_STAGE256");
-  return on != 0;
-}      // adt_dense_rows_enable(0) routes everything to the tiled kernels (A/B measurements, tests)
-
-template <class KFn, class Args>
-static int rows_launch(KFn kernel, const Args& a, int n_panels, int pc, int contraction, int T, hipStream_t s, const char* what, AdtLdsOptIn& optin) {
-  const size_t smem = rows_lds_bytes(contraction, pc);      // grows with the run-time panel width: the high-water mark in optin follows it
-  // one workgroup per CU and panel group; never more row groups than 16-row tiles / waves
-  const int ntiles = (T + 15) / 16;
-  int nrg = 256 / n_panels;
-  if (smem <= 64 * 1024) nrg *= 2;
-  const int need = (ntiles + ROWS_NW - 1) / ROWS_NW;
-  if (nrg > need) nrg = need;
-  if (nrg < 1) nrg = 1;
-  Args args = a;
-  int np = n_panels, pcv = pc;
-  void* kargs[] = {&args, &np, &pcv};
-  return adt_launch_lds((const void*)kernel, dim3(nrg * n_panels), dim3(ROWS_NW * 64), smem, kargs, s, what, optin);
+template <class Args>
+static int rows_launch(const void* kernel, const Args& a, int n_panels, int pc, int row_groups, size_t smem, hipStream_t s, const char* what, AdtLdsOptIn& optin) {
+  void* kargs[] = {const_cast<Args*>(&a), &n_panels, &pc};      // smem grows with the run-time panel width: the high-water mark in optin follows it
+  return adt_launch_lds(kernel, dim3(row_groups * n_panels), dim3(ROWS_NW * 64), smem, kargs, s, what, optin);
 }
 
-static bool rows_fwd_ok(const DenseFwdArgs& a) {
-  if (!g_rows_enabled) return false;
-  if (!(a.K == 64 || a.K == 128 || a.K == 256) || (a.N % 4) || (a.ldy % 4) || !adt_aligned16(a.Y)) return false;
-  if (a.b && !adt_aligned16(a.b)) return false;
-  if (a.U && ((a.ldu % 4) || !adt_aligned16(a.U))) return false;
-  if (a.R && ((a.ldr % 4) || !adt_aligned16(a.R))) return false;
-  if (a.R2 && ((a.ldr2 % 4) || !adt_aligned16(a.R2))) return false;
-  return true;
-}
-
-static int launch_dense_fwd_rows(const DenseFwdArgs& a, hipStream_t s) {
-  const int pc = a.N >= ROWS_PC ? ROWS_PC : (a.N + 15) / 16 * 16;
-  const int n_panels = (a.N + pc - 1) / pc;
+static int launch_dense_fwd_rows(const DenseFwdPlan& p, const DenseFwdArgs& a, hipStream_t s) {
+  static const void* const fns[6] = {(const void*)k_dense_fwd_rows<2, 4>, (const void*)k_dense_fwd_rows<4, 4>, (const void*)k_dense_fwd_rows<8, 4>,
+                                     (const void*)k_dense_fwd_rows<2, 8>, (const void*)k_dense_fwd_rows<4, 8>, (const void*)k_dense_fwd_rows<8, 8>};
   static AdtLdsOptIn optin[6];
-  const char* what = "dense_fwd(rows)";
-  // residual loads run one chunk of CH column tiles ahead (double buffered in registers): 8 tiles, or 4 when there are two residuals
-  if (a.R2) {
-    if (a.K == 64) return rows_launch(k_dense_fwd_rows<2, 4>, a, n_panels, pc, 64, a.T, s, what, optin[3]);
-    if (a.K == 128) return rows_launch(k_dense_fwd_rows<4, 4>, a, n_panels, pc, 128, a.T, s, what, optin[4]);
-    return rows_launch(k_dense_fwd_rows<8, 4>, a, n_panels, pc, 256, a.T, s, what, optin[5]);
-  }
-  if (a.K == 64) return rows_launch(k_dense_fwd_rows<2, 8>, a, n_panels, pc, 64, a.T, s, what, optin[0]);
-  if (a.K == 128) return rows_launch(k_dense_fwd_rows<4, 8>, a, n_panels, pc, 128, a.T, s, what, optin[1]);
-  return rows_launch(k_dense_fwd_rows<8, 8>, a, n_panels, pc, 256, a.T, s, what, optin[2]);
+  const int i = (p.ch == 4 ? 0 : 3) + (p.kb == 2 ? 0 : (p.kb == 4 ? 1 : 2));      // k_dense_fwd_rows<KB, CH>
+  return rows_launch(fns[i], a, p.n_panels, p.pc, p.row_groups, p.lds_bytes, s, "dense_fwd(rows)", optin[i]);
 }
 
-static bool rows_dx_ok(const DenseBwdArgs& a) {
-  if (!g_rows_enabled || !a.dX) return false;
-  const int N = a.G.N;
-  if ((N % 64) || N > 1024 || (a.K % 4) || (a.lddx % 4) || !adt_aligned16(a.dX) || (a.G.lddy % 4) || !adt_aligned16(a.G.dY)) return false;
-  if (a.G.act != ACT_NONE && ((a.G.ldu % 4) || !adt_aligned16(a.G.U))) return false;
-  return true;
-}
-
-// contraction chunks of <= 256 columns of G / rows of W; every chunk after the first accumulates
-static int launch_dense_dx_rows(const DenseBwdArgs& a0, hipStream_t s) {
-  const int N = a0.G.N;
+// one launch per contraction piece: its columns of G and U, its rows of W, the layer's own dropout indices; dX only
+static int launch_dense_dx_rows(const DenseBwdPlan& p, const DenseBwdArgs& a0, hipStream_t s) {
+  static const void* const fns[5] = {(const void*)k_dense_dx_rows<2, true>, (const void*)k_dense_dx_rows<4, true>, (const void*)k_dense_dx_rows<2, false>,
+                                     (const void*)k_dense_dx_rows<4, false>, (const void*)k_dense_dx_rows<8, false>};
   static AdtLdsOptIn optin[5];
-  const char* what = "dense_bwd_dx(rows)";
-  const bool has_u = a0.G.act != ACT_NONE;
-  for (int n0 = 0; n0 < N;) {
-    // with an activation the saved pre-activation rides along in registers: contraction chunks of 128 instead of 256
-    int chunk = (N - n0 >= 256 && !has_u) ? 256 : (N - n0 >= 128 ? 128 : 64);
+  for (int i = 0; i < p.n_pieces; ++i) {
+    const DxPiece& pc = p.piece[i];
     DenseBwdArgs a = a0;
-    a.G.dY = a0.G.dY + n0; a.G.U = a0.G.U ? a0.G.U + n0 : nullptr; a.G.N = chunk; a.G.idx_off = a0.G.idx_off + n0;
-    a.W = a0.W + (size_t)n0 * a0.ldw;
-    a.beta = (n0 > 0) ? 1 : a0.beta;
+    a.G.dY = a0.G.dY + pc.n0; a.G.U = a0.G.U ? a0.G.U + pc.n0 : nullptr; a.G.N = pc.chunk; a.G.idx_off = a0.G.idx_off + pc.n0;
+    a.W = a0.W + (size_t)pc.n0 * a0.ldw;
+    a.beta = i ? pc.beta : a0.beta;      // the first piece keeps the caller's word
     a.dW = nullptr; a.db = nullptr;
-    const int pc = a.K >= ROWS_PC ? ROWS_PC : (a.K + 15) / 16 * 16;
-    const int n_panels = (a.K + pc - 1) / pc;
-    int rc;
-    if (has_u) {
-      if (chunk == 64) rc = rows_launch(k_dense_dx_rows<2, true>, a, n_panels, pc, 64, a.G.T, s, what, optin[3]);
-      else rc = rows_launch(k_dense_dx_rows<4, true>, a, n_panels, pc, 128, a.G.T, s, what, optin[4]);
-    } else if (chunk == 64) rc = rows_launch(k_dense_dx_rows<2, false>, a, n_panels, pc, 64, a.G.T, s, what, optin[0]);
-    else if (chunk == 128) rc = rows_launch(k_dense_dx_rows<4, false>, a, n_panels, pc, 128, a.G.T, s, what, optin[1]);
-    else rc = rows_launch(k_dense_dx_rows<8, false>, a, n_panels, pc, 256, a.G.T, s, what, optin[2]);
-    if (rc) return rc;
-    n0 += chunk;
+    const int k = p.has_u ? (pc.kb == 2 ? 0 : 1) : (pc.kb == 2 ? 2 : (pc.kb == 4 ? 3 : 4));      // k_dense_dx_rows<KB, has_u>
+    if (rows_launch(fns[k], a, p.n_panels, p.pc, pc.row_groups, pc.lds_bytes, s, "dense_bwd_dx(rows)", optin[k])) return -1;
   }
   return 0;
-}
-
-template <int PREC>
-static int launch_dense_fwd(const DenseFwdArgs& a0, hipStream_t s) {
-  if (PREC == PREC_BF16 && g_rows_enabled && a0.K == 256 && (a0.N % 256) == 0 && a0.N <= 1024 &&
-      (a0.ldx % 4) == 0 && adt_aligned16(a0.X) && (a0.ldw % 4) == 0 && adt_aligned16(a0.W) && (a0.ldy % 4) == 0 && adt_aligned16(a0.Y) &&
-      (!a0.U || ((a0.ldu % 4) == 0 && adt_aligned16(a0.U))) && (!a0.R || ((a0.ldr % 4) == 0 && adt_aligned16(a0.R))) && (!a0.R2 || ((a0.ldr2 % 4) == 0 && adt_aligned16(a0.R2))) &&
-      stage_kernels_on()) {
-    // K = 256, N = 256 .. 1024: weight rows in registers, activations through LDS, compile-time epilogue on rows (adt_gemm.cuh: k_dense_fwd256)
-    const int T = a0.T;
-    int nwg = (T + DWP_TS - 1) / DWP_TS;
-    const int cap = a0.N > 256 ? 512 / (a0.N / 256) : 256;
-    if (nwg > cap) nwg = cap;
-    const int chunk = ((T + nwg - 1) / nwg + DWP_TS - 1) / DWP_TS * DWP_TS;
-    const dim3 grid((T + chunk - 1) / chunk, a0.N / 256);
-    const int epi = ((a0.R || a0.R2 || a0.ids) ? 1 : 0) | (a0.drop.thr ? 2 : 0) | ((a0.act != ACT_NONE || a0.U) ? 4 : 0);
-    switch (epi) {
-      case 0: hipLaunchKernelGGL(k_dense_fwd256<0>, grid, dim3(DWP_NTH), 0, s, a0, chunk); break;
-      case 1: hipLaunchKernelGGL(k_dense_fwd256<1>, grid, dim3(DWP_NTH), 0, s, a0, chunk); break;
-      case 2: hipLaunchKernelGGL(k_dense_fwd256<2>, grid, dim3(DWP_NTH), 0, s, a0, chunk); break;
-      case 3: hipLaunchKernelGGL(k_dense_fwd256<3>, grid, dim3(DWP_NTH), 0, s, a0, chunk); break;
-      case 4: hipLaunchKernelGGL(k_dense_fwd256<4>, grid, dim3(DWP_NTH), 0, s, a0, chunk); break;
-      case 5: hipLaunchKernelGGL(k_dense_fwd256<5>, grid, dim3(DWP_NTH), 0, s, a0, chunk); break;
-      case 6: hipLaunchKernelGGL(k_dense_fwd256<6>, grid, dim3(DWP_NTH), 0, s, a0, chunk); break;
-      default: hipLaunchKernelGGL(k_dense_fwd256<7>, grid, dim3(DWP_NTH), 0, s, a0, chunk); break;
-    }
-    return 0;
-  }
-  if (PREC == PREC_BF16 && rows_fwd_ok(a0)) return launch_dense_fwd_rows(a0, s);
-  DenseFwdArgs a = a0;
-  a.nt_n = a.N > 64 ? (a.N + 127) / 128 : 1;
-  a.nt_m = (a.T + GBM - 1) / GBM;
-  const int grid = xcd_grid(a.nt_m, a.nt_n);      // XCD-aware 1-D launch (xcd_tile)
-  static AdtLdsOptIn optin[2];
-  if (a.N > 64) return gemm_launch(k_dense_fwd<PREC, 128>, gemm_lds_bytes<PREC, 128>(), grid, s, a, "dense_fwd", optin[0]);
-  return gemm_launch(k_dense_fwd<PREC, 64>, gemm_lds_bytes<PREC, 64>(), grid, s, a, "dense_fwd", optin[1]);
-}
-
-template <int PREC>
-static int launch_dense_bwd(const DenseBwdArgs& a0, hipStream_t s) {
-  DenseBwdArgs a = a0;
-  const int T = a.G.T, N = a.G.N, K = a.K;
-  if (PREC == PREC_BF16 && g_rows_enabled && a.dX && (N % 256) == 0 && N <= 768 && K == 256 && (a.ldw % 4) == 0 && adt_aligned16(a.W) &&
-      (a.G.lddy % 4) == 0 && adt_aligned16(a.G.dY) && (a.G.act == ACT_NONE || ((a.G.ldu % 4) == 0 && adt_aligned16(a.G.U))) && stage_kernels_on()) {
-    // contraction 256 / 512 / 768 into 256 columns: weight in registers, gradient tiles through LDS, transposed output (adt_gemm.cuh:
-    // k_dense_dx256; wider outputs -- K = 1024 as four column blocks -- measured neutral against the row-streaming kernel and stay there)
-    const int NB = N / 256, kblocks = K / 256;
-    int nwg = (T + DWP_TS - 1) / DWP_TS;
-    const int cap = 256 / (kblocks > 2 ? 2 : 1);
-    if (nwg > cap) nwg = cap;
-    const int chunk = ((T + nwg - 1) / nwg + DWP_TS - 1) / DWP_TS * DWP_TS;
-    DenseBwdArgs d = a;
-    d.t_chunk = chunk;
-    const dim3 grid((T + chunk - 1) / chunk, kblocks);
-    const size_t smem = (size_t)DWP_IMG * NB;
-    if (NB == 1) hipLaunchKernelGGL(k_dense_dx256<1>, grid, dim3(DWP_NTH), smem, s, d);
-    else if (NB == 2) hipLaunchKernelGGL(k_dense_dx256<2>, grid, dim3(DWP_NTH), smem, s, d);
-    else hipLaunchKernelGGL(k_dense_dx256<3>, grid, dim3(DWP_NTH), smem, s, d);
-    a.dX = nullptr;
-  }
-  if (PREC == PREC_BF16 && rows_dx_ok(a)) {
-    if (launch_dense_dx_rows(a, s)) return -1;
-    a.dX = nullptr;
-  }
-  if (a.dX) {
-    const int gx = K > 64 ? (K + 127) / 128 : 1, gy = (T + GBM - 1) / GBM;
-    // long contractions over few output tiles (the all-item logits: N = V + 100) are split over blockIdx.z
-    int splits = 1;
-    if (N >= 4096 && gx * gy < 1024) {
-      splits = (2048 + gx * gy - 1) / (gx * gy);
-      if (splits > 32) splits = 32;
-      a.n_chunk = ((N + splits - 1) / splits + GBK - 1) / GBK * GBK;
-      splits = (N + a.n_chunk - 1) / a.n_chunk;
-      if (splits > 1 && !a.beta && adt::zero_rows_f32_async(a.dX, (size_t)a.lddx, K, (size_t)T, s)) return adt_set_error("dense_bwd: zero");
-    }
-    a.nt_a = gx; a.nt_b = gy; a.nt_z = splits;
-    const int grid = xcd_grid(gy, gx * splits);
-    static AdtLdsOptIn optin[2];
-    if (K > 64) { if (gemm_launch(k_dense_bwd_dx<PREC, 128>, gemm_lds_bytes<PREC, 128>(), grid, s, a, "dense_bwd_dx", optin[0])) return -1; }
-    else if (gemm_launch(k_dense_bwd_dx<PREC, 64>, gemm_lds_bytes<PREC, 64>(), grid, s, a, "dense_bwd_dx", optin[1])) return -1;
-  }
-  if (a.dW && PREC == PREC_BF16 && g_rows_enabled && (N % 256) == 0 && (K % 256) == 0 && (N / 256) * (K / 256) <= 4 && g_dense_ws && (a.ldx % 4) == 0 &&
-      adt_aligned16(a.X) && (a.G.lddy % 4) == 0 && adt_aligned16(a.G.dY)) {
-    // the whole 256 x 256 product (of each 256 x 256 block) per workgroup, private partials in the registered workspace + a reduce
-    // (adt_gemm.cuh: k_dense_dw256); 256 workgroups in all
-    const int blocks = (N / 256) * (K / 256), kblocks = K / 256;
-    int nwg = (T + DWP_TS - 1) / DWP_TS;
-    if (nwg > 256 / blocks) nwg = 256 / blocks;
-    if ((int64_t)nwg * blocks * 262144 <= g_dense_ws_bytes) {
-      const int chunk = ((T + nwg - 1) / nwg + DWP_TS - 1) / DWP_TS * DWP_TS;
-      nwg = (T + chunk - 1) / chunk;
-      a.t_chunk = chunk;
-      hipLaunchKernelGGL(k_dense_dw256, dim3(nwg, blocks), dim3(DWP_NTH), 0, s, a, g_dense_ws);
-      const int per = nwg >= 128 ? 32 : 16;
-      hipLaunchKernelGGL(k_dense_dw256_reduce, dim3(64, (nwg + per - 1) / per, blocks), dim3(256), 0, s, (const float*)g_dense_ws, nwg, per, a.dW, a.lddw, kblocks);
-      a.dW = nullptr;
-    }
-  }
-  // the 256 x 128-block kernel pays off from four output blocks on (N = 768: 127 us vs 225 us tiled); at two blocks (256 x 256)
-  // its 32 K atomics per workgroup cost what the deeper stages save (84 us vs 77 us)
-  if (a.dW && PREC == PREC_BF16 && g_rows_enabled && ((N + DW_BN - 1) / DW_BN) * ((K + DW_BK - 1) / DW_BK) >= 4 && (N % 4) == 0 && (K % 4) == 0 && (a.ldx % 4) == 0 &&
-      adt_aligned16(a.X) && (a.G.lddy % 4) == 0 && adt_aligned16(a.G.dY) && (a.G.act == ACT_NONE || ((a.G.ldu % 4) == 0 && adt_aligned16(a.G.U)))) {
-    const int n_blocks = (N + DW_BN - 1) / DW_BN, k_blocks = (K + DW_BK - 1) / DW_BK, tiles = n_blocks * k_blocks;
-    // one workgroup per CU (96 KB of LDS): 256 workgroups when the T chunks stay >= 4 stages, chunks are multiples of 64 rows
-    int splits = tiles >= 256 ? 1 : 256 / tiles;
-    int chunk = ((T + splits - 1) / splits + DW_TS - 1) / DW_TS * DW_TS;
-    if (chunk < DW_TS) chunk = DW_TS;
-    splits = (T + chunk - 1) / chunk;
-    a.t_chunk = chunk;
-    static AdtLdsOptIn optin;
-    DenseBwdArgs args = a;
-    args.nt_z = splits;
-    int nb = n_blocks, kb = k_blocks;
-    void* kargs[] = {&args, &nb, &kb};
-    if (adt_launch_lds((const void*)k_dense_dw_rows, dim3(xcd_grid(splits, tiles)), dim3(DW_NTH), DW_LDS_BYTES, kargs, s, "dense_bwd_dw(rows)", optin)) return -1;
-    a.dW = nullptr;
-  }
-  if (a.dW && PREC == PREC_BF16 && g_rows_enabled && (N % 64) == 0 && (K % 64) == 0 && (N / 64) * (K / 64) <= 4 && (a.ldx % 4) == 0 && adt_aligned16(a.X) && (a.G.lddy % 4) == 0 && adt_aligned16(a.G.dY)) {
-    // 64 x 64 layers: 128-row stages, ~200 workgroups (adt_gemm.cuh: k_dense_dw64)
-    int chunk = ((T + 255) / 256 + DW64_ROWS - 1) / DW64_ROWS * DW64_ROWS;
-    if (chunk < DW64_ROWS) chunk = DW64_ROWS;
-    a.t_chunk = chunk;
-    const int nwg = (T + chunk - 1) / chunk, blocks = (N / 64) * (K / 64);
-    // private partials in the registered workspace + an ordered sum (no float atomics) when there is one
-    float* const part = (g_dense_ws && (int64_t)nwg * blocks * DW64_PART * 4 <= g_dense_ws_bytes) ? g_dense_ws : nullptr;
-    hipLaunchKernelGGL(k_dense_dw64, dim3(nwg, blocks), dim3(DW64_NTH), 0, s, a, part);
-    if (part)
-      hipLaunchKernelGGL(k_dense_dw64_reduce, dim3(17, blocks), dim3(1024), 0, s, (const float*)part, nwg, a.t_dev, T, chunk, a.dW, a.lddw, K / 64, a.db);
-    a.dW = nullptr;
-  }
-  if (a.dW) {
-    const int bn = K > 64 ? 128 : 64;
-    const int gx = (K + bn - 1) / bn, gy = (N + GBM - 1) / GBM;
-    // split T so that enough workgroups are in flight while each still amortises the 16 K atomics of its flush over >= 10
-    // k-steps; the targets are measured (tools/bench_dense.py at T = 51,200: 4 tiles 78 us @512 vs 98 @1024; 12 tiles 223 @2048
-    // vs 247 @1024; 16 tiles 565 @1024 vs 602 @2048)
-    const int tiles = gx * gy;
-    const int target_wgs = tiles <= 4 ? 512 : (tiles <= 12 ? 2048 : 1024);
-    int splits = (target_wgs + tiles - 1) / tiles;
-    int chunk = ((T + splits - 1) / splits + GBK - 1) / GBK * GBK;
-    if (chunk < GBK) chunk = GBK;
-    splits = (T + chunk - 1) / chunk;
-    a.t_chunk = chunk;
-    a.nt_a = gx; a.nt_b = gy; a.nt_z = splits;
-    const int grid = xcd_grid(splits, gx * gy);
-    static AdtLdsOptIn optin[2];
-    if (bn == 128) { if (gemm_launch(k_dense_bwd_dw<PREC, 128>, gemm_lds_bytes<PREC, 128>(), grid, s, a, "dense_bwd_dw", optin[0])) return -1; }
-    else if (gemm_launch(k_dense_bwd_dw<PREC, 64>, gemm_lds_bytes<PREC, 64>(), grid, s, a, "dense_bwd_dw", optin[1])) return -1;
-  }
-  return adt_check_launch("dense_bwd");
 }
 
 // ---- STOSA-ADT attention (adt_stosa.cuh, adt_klattn.cuh, adt_wattn_mfma.cuh) ------------------------------------------------------------
@@ -481,6 +252,71 @@ int adt_klattn_mfma_bwd(int prec, const float* Qm, int ldqm, const float* Qc, in
                                                                     B, H, L, hd, p, seed, site, b_offset, dQm, dQc, dKm, dKc, dVm, dVc, ldd), (hipStream_t)stream);
 }
 
+}  // extern "C"
+
+// ---- dense layers: adt_dense_fwd_plan / adt_dense_bwd_plan (adt_wide_plan.h) choose the kernel and its numbers; the launchers pass them -----
+// Below the STOSA entry points, each entry point behind its launchers, for the same reason: the order of first use.
+static float* g_dense_ws = nullptr;      // scratch registered by the host (adt_dense_workspace): private partials of the 256 x 256 weight gradients
+static int64_t g_dense_ws_bytes = 0;
+static int g_rows_enabled = 1;      // adt_dense_rows_enable(0) routes everything to the tiled kernels (A/B measurements, tests)
+// ADT_STAGE256=0 in the environment keeps the 256-wide forward / input-gradient stage kernels (k_dense_fwd256, k_dense_dx256) off: A/B runs
+static bool stage_kernels_on() {
+  static const int on = adt_env_on("ADT_STAGE256");
+  return on != 0;
+}
+
+// what the vectorised kernels ask of an operand: a 16-byte aligned base and a row stride that is a multiple of 4 floats
+static bool operand_ok(const void* p, int ld) { return (ld % 4) == 0 && adt_aligned16(p); }
+
+static DenseFacts dense_facts(int prec, int T, int K, int N) {
+  DenseFacts f{};
+  f.prec = prec; f.T = T; f.K = K; f.N = N;
+  f.rows_on = g_rows_enabled != 0; f.stage256_on = stage_kernels_on(); f.ws_bytes = g_dense_ws ? g_dense_ws_bytes : 0;
+  return f;
+}
+
+static DenseFacts dense_fwd_facts(int prec, const DenseFwdArgs& a) {
+  DenseFacts f = dense_facts(prec, a.T, a.K, a.N);
+  f.has_bias = a.b != nullptr; f.has_u = a.U != nullptr; f.has_r = a.R != nullptr; f.has_r2 = a.R2 != nullptr; f.has_mask = a.ids != nullptr;
+  f.has_drop = a.drop.thr != 0; f.has_act = a.act != ACT_NONE;
+  f.x_ok = operand_ok(a.X, a.ldx); f.w_ok = operand_ok(a.W, a.ldw); f.g_ok = operand_ok(a.Y, a.ldy); f.bias_ok = adt_aligned16(a.b);
+  f.u_ok = operand_ok(a.U, a.ldu); f.r_ok = operand_ok(a.R, a.ldr); f.r2_ok = operand_ok(a.R2, a.ldr2);
+  return f;
+}
+
+static DenseFacts dense_bwd_facts(int prec, const DenseBwdArgs& a) {
+  DenseFacts f = dense_facts(prec, a.G.T, a.K, a.G.N);
+  f.has_u = a.G.U != nullptr; f.has_mask = a.G.ids != nullptr; f.has_drop = a.G.drop.thr != 0; f.has_act = a.G.act != ACT_NONE;
+  f.has_dx = a.dX != nullptr; f.has_dw = a.dW != nullptr; f.beta = a.beta != 0;
+  f.x_ok = operand_ok(a.X, a.ldx); f.w_ok = operand_ok(a.W, a.ldw); f.g_ok = operand_ok(a.G.dY, a.G.lddy); f.u_ok = operand_ok(a.G.U, a.G.ldu);
+  f.dx_ok = operand_ok(a.dX, a.lddx);
+  return f;
+}
+
+static int launch_dense_fwd256(const DenseFwdPlan& p, const DenseFwdArgs& a, hipStream_t s) {
+  static const void* const fns[8] = {(const void*)k_dense_fwd256<0>, (const void*)k_dense_fwd256<1>, (const void*)k_dense_fwd256<2>, (const void*)k_dense_fwd256<3>,
+                                     (const void*)k_dense_fwd256<4>, (const void*)k_dense_fwd256<5>, (const void*)k_dense_fwd256<6>, (const void*)k_dense_fwd256<7>};
+  static AdtLdsOptIn none;      // static LDS only
+  int chunk = p.chunk;
+  void* kargs[] = {const_cast<DenseFwdArgs*>(&a), &chunk};
+  return adt_launch_lds(fns[p.epi], dim3(p.grid_x, p.grid_y), dim3(p.block), 0, kargs, s, "dense_fwd(256)", none);
+}
+
+template <int PREC>
+static int launch_dense_fwd(const DenseFwdPlan& p, const DenseFwdArgs& a0, hipStream_t s) {
+  static_assert(gemm_tile_lds_bytes(PREC == PREC_BF16, 128) == gemm_lds_bytes<PREC, 128>() && gemm_tile_lds_bytes(PREC == PREC_BF16, 64) == gemm_lds_bytes<PREC, 64>(),
+                "plan and kernel disagree on the LDS footprint");
+  if (p.arm == F256) return launch_dense_fwd256(p, a0, s);
+  if (p.arm == FROWS) return launch_dense_fwd_rows(p, a0, s);
+  DenseFwdArgs a = a0;
+  a.nt_n = p.nt_n; a.nt_m = p.nt_m;
+  static AdtLdsOptIn optin[2];
+  if (p.bn == 128) return adt_launch_lds1((const void*)k_dense_fwd<PREC, 128>, dim3(p.grid_x), dim3(p.block), p.lds_bytes, a, s, "dense_fwd", optin[0]);
+  return adt_launch_lds1((const void*)k_dense_fwd<PREC, 64>, dim3(p.grid_x), dim3(p.block), p.lds_bytes, a, s, "dense_fwd", optin[1]);
+}
+
+extern "C" {
+
 int adt_dense_workspace(void* ws, int64_t bytes) {
   g_dense_ws = static_cast<float*>(ws);
   g_dense_ws_bytes = ws ? bytes : 0;
@@ -493,6 +329,8 @@ int adt_dense_rows_enable(int on) {
   return was;
 }
 
+int64_t adt_dense_bwd_ws_bytes(int prec, int T, int K, int N) { return adt_dense_bwd_ws_need(prec, T, K, N); }
+
 int adt_dense_fwd(int prec, const float* X, int ldx, const float* W, int ldw, const float* b, int T, int K, int N, int act, float* U,
                   int ldu, float p, const uint32_t* seed, uint32_t site, uint32_t row_offset, const float* R, int ldr,
                   const float* R2, int ldr2, const int32_t* mask_ids, float* Y, int ldy, const int32_t* t_dev, void* stream) {
@@ -502,8 +340,91 @@ int adt_dense_fwd(int prec, const float* X, int ldx, const float* W, int ldw, co
   DenseFwdArgs a{};
   a.X = X; a.ldx = ldx; a.W = W; a.ldw = ldw; a.b = b; a.T = T; a.K = K; a.N = N; a.Y = Y; a.ldy = ldy; a.U = U; a.ldu = ldu; a.act = act;
   a.drop = adt_make_drop(p, seed, site); a.row_offset = row_offset; a.R = R; a.ldr = ldr; a.R2 = R2; a.ldr2 = ldr2; a.ids = mask_ids; a.t_dev = t_dev;
-  return prec == ADT_PREC_F32 ? launch_dense_fwd<PREC_F32>(a, (hipStream_t)stream) : launch_dense_fwd<PREC_BF16>(a, (hipStream_t)stream);
+  const DenseFwdPlan plan = adt_dense_fwd_plan(dense_fwd_facts(prec, a));
+  return prec == ADT_PREC_F32 ? launch_dense_fwd<PREC_F32>(plan, a, (hipStream_t)stream) : launch_dense_fwd<PREC_BF16>(plan, a, (hipStream_t)stream);
 }
+
+}  // extern "C"
+
+static void launch_dense_dx256(const DenseBwdPlan& p, const DenseBwdArgs& a0, hipStream_t s) {
+  DenseBwdArgs a = a0;
+  a.t_chunk = p.dx_chunk;
+  const dim3 grid(p.dx_grid_x, p.dx_grid_y), block(p.dx_block);
+  if (p.nb == 1) hipLaunchKernelGGL(k_dense_dx256<1>, grid, block, p.dx_lds_bytes, s, a);
+  else if (p.nb == 2) hipLaunchKernelGGL(k_dense_dx256<2>, grid, block, p.dx_lds_bytes, s, a);
+  else hipLaunchKernelGGL(k_dense_dx256<3>, grid, block, p.dx_lds_bytes, s, a);
+}
+
+// the tiled dX kernel's block: its tile counts and the split of N
+static DenseBwdArgs dense_dx_tiled_args(const DenseBwdPlan& p, const DenseBwdArgs& a0) {
+  DenseBwdArgs a = a0;
+  a.n_chunk = p.n_chunk; a.nt_a = p.gx; a.nt_b = p.gy; a.nt_z = p.dx_splits;
+  return a;
+}
+
+template <int PREC>
+static int launch_dense_dx_tiled(const DenseBwdPlan& p, const DenseBwdArgs& a, hipStream_t s) {
+  if (p.dx_zero_fill && adt::zero_rows_f32_async(a.dX, (size_t)a.lddx, a.K, (size_t)a.G.T, s)) return adt_set_error("dense_bwd: zero");
+  static AdtLdsOptIn optin[2];
+  if (p.dx_bn == 128) return adt_launch_lds1((const void*)k_dense_bwd_dx<PREC, 128>, dim3(p.dx_grid_x), dim3(p.dx_block), p.dx_lds_bytes, a, s, "dense_bwd_dx", optin[0]);
+  return adt_launch_lds1((const void*)k_dense_bwd_dx<PREC, 64>, dim3(p.dx_grid_x), dim3(p.dx_block), p.dx_lds_bytes, a, s, "dense_bwd_dx", optin[1]);
+}
+
+static void launch_dense_dw256(const DenseBwdPlan& p, const DenseBwdArgs& a0, hipStream_t s) {
+  DenseBwdArgs a = a0;
+  a.t_chunk = p.dw_chunk;
+  hipLaunchKernelGGL(k_dense_dw256, dim3(p.dw_grid_x, p.dw_grid_y), dim3(p.dw_block), 0, s, a, g_dense_ws);
+  hipLaunchKernelGGL(k_dense_dw256_reduce, dim3(64, p.reduce_groups, p.blocks), dim3(256), 0, s, (const float*)g_dense_ws, p.nwg, p.per, a.dW, a.lddw, p.kblocks);
+}
+
+static int launch_dense_dw_rows(const DenseBwdPlan& p, const DenseBwdArgs& a0, hipStream_t s) {
+  DenseBwdArgs a = a0;
+  a.t_chunk = p.dw_chunk; a.nt_z = p.dw_splits;
+  int nb = p.n_blocks, kb = p.k_blocks;
+  void* kargs[] = {&a, &nb, &kb};
+  static AdtLdsOptIn optin;
+  return adt_launch_lds((const void*)k_dense_dw_rows, dim3(p.dw_grid_x), dim3(p.dw_block), p.dw_lds_bytes, kargs, s, "dense_bwd_dw(rows)", optin);
+}
+
+static void launch_dense_dw64(const DenseBwdPlan& p, const DenseBwdArgs& a0, hipStream_t s) {
+  DenseBwdArgs a = a0;
+  a.t_chunk = p.dw_chunk;
+  float* const part = p.partials ? g_dense_ws : nullptr;
+  hipLaunchKernelGGL(k_dense_dw64, dim3(p.dw_grid_x, p.dw_grid_y), dim3(p.dw_block), 0, s, a, part);
+  if (part)
+    hipLaunchKernelGGL(k_dense_dw64_reduce, dim3(17, p.blocks), dim3(1024), 0, s, (const float*)part, p.nwg, a.t_dev, a.G.T, p.dw_chunk, a.dW, a.lddw, p.kblocks, a.db);
+}
+
+template <int PREC>
+static int launch_dense_dw_tiled(const DenseBwdPlan& p, const DenseBwdArgs& a0, hipStream_t s) {
+  DenseBwdArgs a = a0;
+  a.t_chunk = p.dw_chunk; a.nt_a = p.dw_gx; a.nt_b = p.dw_gy; a.nt_z = p.dw_splits;
+  static AdtLdsOptIn optin[2];
+  if (p.dw_bn == 128) return adt_launch_lds1((const void*)k_dense_bwd_dw<PREC, 128>, dim3(p.dw_grid_x), dim3(p.dw_block), p.dw_lds_bytes, a, s, "dense_bwd_dw", optin[0]);
+  return adt_launch_lds1((const void*)k_dense_bwd_dw<PREC, 64>, dim3(p.dw_grid_x), dim3(p.dw_block), p.dw_lds_bytes, a, s, "dense_bwd_dw", optin[1]);
+}
+
+template <int PREC>
+static int launch_dense_bwd(const DenseBwdPlan& p, const DenseBwdArgs& a0, hipStream_t s) {
+  // The dW kernels' block.  They read neither dX nor the dX kernel's tile counts; both stay in it as those kernels have always received them.
+  DenseBwdArgs w = a0;
+  switch (p.dx) {
+    case DX256: launch_dense_dx256(p, a0, s); w.dX = nullptr; break;
+    case DXROWS: if (launch_dense_dx_rows(p, a0, s)) return -1; w.dX = nullptr; break;
+    case DXTILED: w = dense_dx_tiled_args(p, a0); if (launch_dense_dx_tiled<PREC>(p, w, s)) return -1; break;
+    case DXNONE: break;
+  }
+  switch (p.dw) {
+    case DW256: launch_dense_dw256(p, w, s); break;
+    case DWROWS: if (launch_dense_dw_rows(p, w, s)) return -1; break;
+    case DW64: launch_dense_dw64(p, w, s); break;
+    case DWTILED: if (launch_dense_dw_tiled<PREC>(p, w, s)) return -1; break;
+    case DWNONE: break;
+  }
+  return adt_check_launch("dense_bwd");
+}
+
+extern "C" {
 
 int adt_dense_bwd(int prec, const float* dY, int lddy, int T, int K, int N, const int32_t* mask_ids, float p, const uint32_t* seed,
                   uint32_t site, uint32_t row_offset, int act, const float* U, int ldu, const float* X, int ldx, const float* W, int ldw,
@@ -516,7 +437,8 @@ int adt_dense_bwd(int prec, const float* dY, int lddy, int T, int K, int N, cons
   a.G.dY = dY; a.G.lddy = lddy; a.G.T = T; a.G.N = N; a.G.U = U; a.G.ldu = ldu; a.G.act = act;
   a.G.drop = adt_make_drop(p, seed, site); a.G.row_offset = row_offset; a.G.ids = mask_ids; a.G.idx_ld = N; a.G.idx_off = 0;
   a.X = X; a.ldx = ldx; a.W = W; a.ldw = ldw; a.K = K; a.dX = dX; a.lddx = lddx; a.beta = beta; a.dW = dW; a.lddw = lddw; a.db = db; a.t_dev = t_dev;
-  return prec == ADT_PREC_F32 ? launch_dense_bwd<PREC_F32>(a, (hipStream_t)stream) : launch_dense_bwd<PREC_BF16>(a, (hipStream_t)stream);
+  const DenseBwdPlan plan = adt_dense_bwd_plan(dense_bwd_facts(prec, a));
+  return prec == ADT_PREC_F32 ? launch_dense_bwd<PREC_F32>(plan, a, (hipStream_t)stream) : launch_dense_bwd<PREC_BF16>(plan, a, (hipStream_t)stream);
 }
 
 static int fill_attn(AttnGenArgs& g, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int B, int H, int L, int hd,
@@ -528,6 +450,13 @@ static int fill_attn(AttnGenArgs& g, const float* Q, int ldq, const float* K, in
   return 0;
 }
 
+// adt_attn_masked_plan (adt_wide_plan.h) chooses, launch_attn names the instantiation
+static int attn_masked_launch(int prec, bool bwd, int hd, const AttnGenArgs& g, void* stream) {
+  const AttnPlan p = adt_attn_masked_plan(prec, hd, g.a.L, bwd, g.a.causal != 0, g.kid != nullptr, g.fill);
+  if (p.error[0]) return adt_set_error("%s", p.error);
+  return prec == ADT_PREC_F32 ? launch_attn<PREC_F32>(p, bwd, hd, g, (hipStream_t)stream) : launch_attn<PREC_BF16>(p, bwd, hd, g, (hipStream_t)stream);
+}
+
 // scale <= 0: the kernels' own 1 / sqrt(hd) (fill_attn); else the caller's score scale (heads padded with zero lanes)
 static int attn_masked_fwd_impl(int prec, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int B, int H, int L, int hd,
                                 float scale, int causal, const int32_t* key_ids, float fill, float p, const uint32_t* seed, uint32_t site,
@@ -536,7 +465,7 @@ static int attn_masked_fwd_impl(int prec, const float* Q, int ldq, const float* 
   if (fill_attn(g, Q, ldq, K, ldk, V, ldv, B, H, L, hd, causal, key_ids, fill, p, seed, site, b_offset)) return -1;
   if (scale > 0.f) g.a.scale = scale;
   g.a.O = O; g.a.ldo = ldo; g.a.LSE = LSE;
-  return prec == ADT_PREC_F32 ? dispatch_attn_gen<PREC_F32>(false, hd, g, (hipStream_t)stream) : dispatch_attn_gen<PREC_BF16>(false, hd, g, (hipStream_t)stream);
+  return attn_masked_launch(prec, false, hd, g, stream);
 }
 
 static int attn_masked_bwd_impl(int prec, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, const float* O, int ldo,
@@ -549,7 +478,7 @@ static int attn_masked_bwd_impl(int prec, const float* Q, int ldq, const float* 
   if (scale > 0.f) g.a.scale = scale;
   g.a.O = const_cast<float*>(O); g.a.ldo = ldo; g.a.LSE = const_cast<float*>(LSE); g.a.dO = dO; g.a.lddo = lddo;
   g.a.dQ = dQ; g.a.lddq = lddq; g.a.dK = dK; g.a.lddk = lddk; g.a.dV = dV; g.a.lddv = lddv;
-  return prec == ADT_PREC_F32 ? dispatch_attn_gen<PREC_F32>(true, hd, g, (hipStream_t)stream) : dispatch_attn_gen<PREC_BF16>(true, hd, g, (hipStream_t)stream);
+  return attn_masked_launch(prec, true, hd, g, stream);
 }
 
 int adt_attn_masked_fwd(int prec, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int B, int H, int L, int hd,

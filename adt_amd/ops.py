@@ -250,7 +250,7 @@ def dense_bwd(prec, dY, X, W, dW=None, db=None, dX=None, beta=False, act=ACT_NON
     """G = dY * mask * dropmask * act'(U); dX (+)= G W; dW += G^T X; db += colsum(G)."""
     T, N = dY.shape
     K = W.shape[1]
-    if dW is not None and prec == PREC_BF16 and ((N % 256 == 0 and K % 256 == 0) or (N % 64 == 0 and K % 64 == 0 and (N // 64) * (K // 64) <= 4)):
+    if dW is not None and _lib.load().adt_dense_bwd_ws_bytes(prec, T, K, N) > 0:
         _ensure_dense_ws(dY.device)      # 256-wide layers and 64 x 64 blocks: private partials + an ordered sum instead of an atomic flush
     _lib.check(_lib.load().adt_dense_bwd(prec, _p(_f32(dY)), _ld(dY), T, K, N, _p(mask_ids), float(p), _p(seed), site, row_offset, act, _p(U),
                                          _ld(U), _p(X), _ld(X), _p(_f32(W)), _ld(W), _p(dX), _ld(dX), int(beta), _p(dW), _ld(dW) if dW is not None else 0,

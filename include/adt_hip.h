@@ -176,6 +176,9 @@ int adt_dense_rows_enable(int on);
  * layer in bf16 mode runs through private per-workgroup partials + a reduce instead of a 128-256 KiB atomic flush per workgroup.  The
  * library keeps the pointer (it allocates nothing itself); ws = NULL unregisters.  Results agree with the atomic path to summation order. */
 int adt_dense_workspace(void* ws, int64_t bytes);
+/* Host only, launches nothing: the bytes of that scratch the weight gradient of a (T, K, N) layer would write, 0 when no workspace kernel
+ * takes the shape (aligned operands and the row-streaming kernels assumed).  A host registers the scratch when the answer is positive. */
+int64_t adt_dense_bwd_ws_bytes(int prec, int T, int K, int N);
 /* torch.nn.Linear with its surrounding elementwise ops, any K / N (bert4rec/model/modules.py:59-75,128-139,
  * bert.py:48-51,80-90; stosa/modules.py:199-212,477-487): Y = mask(R + dropout(act(X W^T + b))); W is N x K with row
  * stride ldw; U (optional) receives the pre-activation X W^T + b for the backward.  t_dev (optional, DEVICE int): only

@@ -364,8 +364,11 @@ def test_dense_rows_kernels_match_tiled(T, K, N, act):
     """The row-streaming bf16 kernels (adt_dense_rows.cuh) against the tiled ones on the same inputs: same bf16 operands and fp32
     accumulation, different summation order => 2e-5 of the output magnitude (forward, incl. bias / activation / dropout /
     residuals / row mask / device row count / saved pre-activation) and 2e-5 on dX through the full prologue (mask, dropout,
-    act') with the contraction chunked (N = 768, 1024) and accumulated into an existing dX (beta)."""
-    from adt_amd import ops
+    act') with the contraction chunked (N = 768, 1024) and accumulated into an existing dX (beta).  Which shapes' weight gradients go through the
+    registered workspace (k_dense_dw256 at 256-wide blocks, the partials of k_dense_dw64) is asked of the library, not assumed."""
+    from adt_amd import _lib, ops
+    ws_shape = _lib.load().adt_dense_bwd_ws_bytes(ops.PREC_BF16, T, K, N) > 0
+    assert ws_shape == ((T, K, N) in {(1000, 256, 256), (333, 256, 768), (4100, 64, 64), (48, 64, 256), (700, 1024, 256)})
     r = np.random.RandomState(T + K + N)
     X = T_(r.standard_normal((T, K)).astype(np.float32))
     W = T_((r.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32))

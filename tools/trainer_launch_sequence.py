@@ -10,7 +10,8 @@ fixed random ids, printing the loss after every step as decimal and as float.hex
 trainers run twice in the process, eagerly and with use_graph=True (eager warm-up, capture, replay, replay); the supernet trainers
 have no graph mode and change their block choice between the steps.  Only public constructors and step() are used, so the same file
 runs on an older checkout.  --digest prints the length and the SHA-256 of the trace's ordered kernel list, by name alone and with grid
-and workgroup sizes; two checkouts launched the same work when the digests agree.  One trainer per process.
+and workgroup sizes (and the LDS bytes of each dispatch, where the trace has the column); two checkouts launched the same work when the
+digests agree.  One trainer per process.
 
 flagship / flagship-ring: the fused SASRec-ADT step (FusedTrainer, width 64) on ids resident in HBM (stage_ring / step_staged), and through the
 pinned id ring (slot / publish / commit) with every batch published one ahead, so each step prefetches its successor and the next takes it
@@ -170,9 +171,13 @@ def digest(path):
     names = [r["Kernel_Name"] for r in rows]
     sized = ["%s grid %s,%s,%s workgroup %s,%s,%s" % ((r["Kernel_Name"],) + tuple(r[k + a] for k in ("Grid_Size_", "Workgroup_Size_") for a in "XYZ"))
              for r in rows]
+    lds = next((k for k in ("LDS_Block_Size", "Group_Segment_Size") if rows and k in rows[0]), None)      # static + dynamic LDS of the dispatch, where the trace has it
+    if lds:
+        sized = ["%s lds %s" % (line, r[lds]) for line, r in zip(sized, rows)]
     sha = lambda lines: hashlib.sha256("\n".join(lines).encode()).hexdigest()
-    print("%s: %d kernels, names sha256 %s, names+grid+workgroup sha256 %s" % (os.path.basename(path), len(rows), sha(names), sha(sized)))
-    print("%s: order-independent: names sha256 %s, names+grid+workgroup sha256 %s" % (os.path.basename(path), sha(sorted(names)), sha(sorted(sized))))
+    what = "names+grid+workgroup+lds" if lds else "names+grid+workgroup"
+    print("%s: %d kernels, names sha256 %s, %s sha256 %s" % (os.path.basename(path), len(rows), sha(names), what, sha(sized)))
+    print("%s: order-independent: names sha256 %s, %s sha256 %s" % (os.path.basename(path), sha(sorted(names)), what, sha(sorted(sized))))
 
 
 if __name__ == "__main__":
