@@ -1,0 +1,41 @@
+// C ABI (include/adt_hip.h, "STOSA-ADT batches built on the device"): launch wrapper of adt_seqbatch.cuh and the host-side draw.  Host
+// code only enqueues work on the caller's stream.
+#include "adt_host.h"
+
+#include "adt_seqbatch.cuh"
+
+using namespace adt;
+
+extern "C" {
+
+int adt_seqbatch_draw(uint32_t seed, uint32_t step, int row, int t, int attempt, int item_size) {
+  if (item_size < 2 || row < 0 || t < 0 || attempt < 0) return 0;
+  return adt_seqbatch_draw_id(seed, step, (uint32_t)row, (uint32_t)t, (uint32_t)attempt, (uint32_t)item_size);
+}
+
+int adt_seqbatch_build(const int64_t* seq_off, const int32_t* seq_items, const int64_t* set_off, const int32_t* set_items, const int32_t* users,
+                       int n_users, int row0, int n_rows, int L, int cut, int item_size, uint32_t seed, uint32_t step, int32_t* inp, int32_t* dec,
+                       int32_t* pos, int32_t* neg, float* inv_count, void* stream) {
+  if (cut < 1 || cut > 3) return adt_set_error("seqbatch_build: cut=%d outside 1..3", cut);
+  if (L < 1) return adt_set_error("seqbatch_build: L=%d < 1", L);
+  if (item_size < 2) return adt_set_error("seqbatch_build: item_size=%d < 2", item_size);
+  if (n_users < 0 || row0 < 0 || n_rows < 0 || (int64_t)row0 + n_rows > n_users)
+    return adt_set_error("seqbatch_build: rows %d..%d+%d outside the batch of %d users", row0, row0, n_rows, n_users);
+  if (!seq_off || !seq_items || !set_off || !set_items || !users) return adt_set_error("seqbatch_build: NULL input");
+  const size_t work = (size_t)n_rows * (size_t)L;
+  if (work > ((size_t)1 << 31)) return adt_set_error("seqbatch_build: %d rows x L=%d is more than 2^31 positions", n_rows, L);
+  if (n_rows > 0 && !inp) return adt_set_error("seqbatch_build: inp is NULL");
+  SeqBatchArgs a{seq_off, seq_items, set_off, set_items, users, n_users, row0, n_rows, L, cut, (uint32_t)item_size, seed, step, inp, dec, pos, neg,
+                 inv_count};
+  if (n_rows > 0) {
+    hipLaunchKernelGGL(k_seqbatch_build, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    if (adt_check_launch("seqbatch_build")) return -1;
+  }
+  if (inv_count) {
+    hipLaunchKernelGGL(k_seqbatch_count, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
+    return adt_check_launch("seqbatch_build(count)");
+  }
+  return 0;
+}
+
+}  // extern "C"

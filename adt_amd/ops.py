@@ -667,3 +667,33 @@ def wdist_pack(M, C, elu, nrm_scale):
     _lib.check(_lib.load().adt_wdist_pack(_p(_f32(M)), _p(_f32(C)), M.stride(0), rows, d, int(bool(elu)), _p(img), 2 * d, _p(nrm), float(nrm_scale),
                                           _stream()), "wdist_pack")
     return img, nrm
+
+
+# ---- STOSA-ADT batches built on the device (include/adt_hip.h: adt_seqbatch_build; adt_amd/csrc/adt_seqbatch.cuh) -----------------------
+def seqbatch_build(seq_off, seq_items, set_off, set_items, users, L, cut, item_size, seed=0, step=0, rows=None, want_neg=True,
+                   want_inv_count=True, views=True):
+    """Rows rows=(lo, hi) (default: all) of the batch `users` (device int32, the GLOBAL batch, ids inside the CSRs) as (hi - lo, L) int32
+    device tensors (inp, dec, pos, neg, inv_count): the train (cut 3) / valid (2) / test (1) view of every sequence, negatives outside
+    the user's set drawn from (seed, step, global row, position), inv_count = 1 / max(non-zero pos entries of ALL users, 1).  neg /
+    inv_count are None when not wanted; views=False also leaves dec and pos out (evaluation reads inp alone)."""
+    for off, items in ((seq_off, seq_items), (set_off, set_items)):
+        assert off.dtype == torch.int64 and off.is_contiguous() and off.numel() >= 2, (off.dtype, off.shape)
+        _i32(items)
+    n_users = users.numel()
+    lo, hi = (0, n_users) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= lo <= hi <= n_users:
+        raise _lib.AdtError("seqbatch_build: rows (%d, %d) outside the batch of %d users" % (lo, hi, n_users))
+    dev = users.device
+    inp, dec, pos, neg = (torch.empty(hi - lo, int(L), device=dev, dtype=torch.int32) if want else None
+                          for want in (True, views, views, want_neg))
+    inv_count = torch.empty(1, device=dev, dtype=torch.float32) if want_inv_count else None
+    _lib.check(_lib.load().adt_seqbatch_build(_p(seq_off), _p(seq_items), _p(set_off), _p(set_items), _p(_i32(users)), n_users, lo, hi - lo,
+                                              int(L), int(cut), int(item_size), int(seed) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF, _p(inp), _p(dec),
+                                              _p(pos), _p(neg), _p(inv_count), _stream()), "seqbatch_build")
+    return inp, dec, pos, neg, inv_count
+
+
+def seqbatch_draw(seed, step, row, t, attempt, item_size):
+    """The id in [1, item_size - 1] that attempt `attempt` proposes as the negative of position t of GLOBAL batch row `row` (host only:
+    the inline function adt_seqbatch_build's kernel calls)."""
+    return int(_lib.load().adt_seqbatch_draw(int(seed) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF, int(row), int(t), int(attempt), int(item_size)))

@@ -74,3 +74,66 @@ class DisenDataset:
         order = self.rng.permutation(self.n) if shuffle else np.arange(self.n)
         for s in range(0, self.n, batch_size):
             yield self.batch(order[s:s + batch_size])
+
+
+class DeviceDisenData:
+    """DisenDataset's batches built on the GPU (adt_seqbatch_build).  Resident on the device as int32 CSR, uploaded
+    once: the user sequences, every user's sorted item set (the whole sequence, as DisenDataset.sets) and the valid / test rating
+    matrices; every indptr is kept on the host as well, so a contiguous user range is sliced without a device read.  No call below
+    copies ids, CSR rows or normalisers from the host."""
+    CUT = {"train": 3, "valid": 2, "test": 1}
+
+    def __init__(self, user_seq, item_size, maxlen, device, valid_matrix, test_matrix):
+        import torch
+        self.item_size, self.max_len, self.dev, self.n = int(item_size), int(maxlen), torch.device(device), len(user_seq)
+        sets = [sorted(set(s)) for s in user_seq]
+        assert all(len(s) > 0 and q[0] >= 1 and q[-1] < self.item_size for s, q in zip(user_seq, sets)), "item ids must lie in [1, item_size - 1]"
+
+        def csr(rows):
+            off = np.zeros(len(rows) + 1, np.int64)
+            np.cumsum([len(r) for r in rows], out=off[1:])
+            items = np.fromiter((x for r in rows for x in r), np.int32, count=int(off[-1]))
+            return torch.from_numpy(off).to(self.dev), torch.from_numpy(items).to(self.dev)
+        self.seq_off, self.seq_items = csr(user_seq)
+        self.set_off, self.set_items = csr(sets)
+        self.seen, self.answers = {}, {}
+        for split, matrix in (("valid", valid_matrix), ("test", test_matrix)):
+            m = matrix.tocsr()
+            assert m.shape[0] == self.n, (m.shape, self.n)
+            ip = np.ascontiguousarray(m.indptr, dtype=np.int32)
+            self.seen[split] = (ip, torch.from_numpy(ip).to(self.dev), torch.from_numpy(np.ascontiguousarray(m.indices, dtype=np.int32)).to(self.dev))
+            c = self.CUT[split]      # the held-out item; 0 for a sequence too short to have one (DisenDataset raises IndexError there)
+            self.answers[split] = np.array([[s[-c] if len(s) >= c else 0] for s in user_seq], np.int64)
+        self._all_users = torch.arange(self.n, device=self.dev, dtype=torch.int32)
+        self.order = None
+
+    def __len__(self):
+        return self.n
+
+    def set_order(self, order):
+        """Upload one epoch's user permutation (the only host -> device copy of an epoch)."""
+        import torch
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        assert order.ndim == 1 and (order.size == 0 or (order.min() >= 0 and order.max() < self.n)), "order holds a user outside 0..n-1"
+        self.order = torch.from_numpy(order).to(self.dev)
+
+    def train_stage(self, start, B, seed, step, rows=None):
+        """The `stage` dict of TapeTrainer.step_staged for users order[start:start + B] -- under data parallelism rows (lo, hi) of that
+        global batch, with the global inv_count and the negatives the whole batch would get."""
+        from .. import ops
+        assert self.order is not None and 0 <= start and start + B <= self.order.numel(), "set_order first; the batch must lie inside it"
+        lo, hi = (0, B) if rows is None else rows
+        inp, dec, pos, neg, inv_count = ops.seqbatch_build(self.seq_off, self.seq_items, self.set_off, self.set_items, self.order[start:start + B],
+                                                           self.max_len, self.CUT["train"], self.item_size, seed, step, (lo, hi))
+        return {"B": hi - lo, "B_global": B, "inp": inp, "dec": dec, "pos": pos, "neg": neg, "inv_count": inv_count}
+
+    def eval_batch(self, split, start, B):
+        """(inp device (B, L), (indptr, indices) device int32, answers numpy (B, 1)) of the contiguous users start .. start + B - 1: what
+        FusedStosaTrainer.full_sort takes for (DisenDataset.batch's input_ids, matrix[users], answers)."""
+        from .. import ops
+        assert split in self.seen and 0 <= start and start + B <= self.n, (split, start, B, self.n)
+        inp = ops.seqbatch_build(self.seq_off, self.seq_items, self.set_off, self.set_items, self._all_users[start:start + B], self.max_len,
+                                 self.CUT[split], self.item_size, want_neg=False, want_inv_count=False, views=False)[0]
+        ip, ip_dev, ix_dev = self.seen[split]
+        indptr = ip_dev[start:start + B + 1] - int(ip[start])
+        return inp, (indptr, ix_dev[int(ip[start]):int(ip[start + B])]), self.answers[split][start:start + B]

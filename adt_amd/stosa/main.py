@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import utils as U
-from .datasets import DisenDataset, get_user_seqs
+from .datasets import DeviceDisenData, DisenDataset, get_user_seqs
 from .models import DisenDistSAModel
 from .trainer import FusedStosaTrainer, get_full_sort_score
 
@@ -53,6 +53,8 @@ def parse_args(argv=None):
     p.add_argument("--override", default=None)
     p.add_argument("--fused_eval", action="store_true",
                    help="full-sort evaluation without the (B, item_size) distance matrix: packed item image + adt_full_rank_from (Wasserstein only)")
+    p.add_argument("--device_batches", action="store_true",
+                   help="build the training and evaluation batches on the GPU from resident sequences (adt_seqbatch_build) instead of on the host")
     return p.parse_args(argv)
 
 
@@ -69,10 +71,16 @@ def _write_synthetic(path, users=22363, items=12101, seed=42):
             f.write("%d %s\n" % (u, " ".join(str(int(x)) for x in seq)))
 
 
-def _evaluate(trainer, ds, matrix, batch_size, fused=False):
+def _evaluate(trainer, ds, matrix, batch_size, fused=False, dev_data=None):
     """Full-sort scores of the whole user set on every rank: under data parallelism rank r sorts batches r, r+W, ... on its GPU
-    and the (N, 40) id lists are gathered (a few hundred KB)."""
+    and the (N, 40) id lists are gathered (a few hundred KB).  dev_data (--device_batches): the same batches of the same users, cut on
+    the GPU by DeviceDisenData.eval_batch."""
     def gen():
+        if dev_data is not None:
+            for i, s in enumerate(range(0, len(ds), batch_size)):
+                if i % trainer.world == trainer.rank:
+                    yield dev_data.eval_batch(ds.data_type, s, min(batch_size, len(ds) - s))
+            return
         for i, (users, inp, dec, pos, neg, ans) in enumerate(ds.epoch_batches(batch_size, shuffle=False)):
             if i % trainer.world == trainer.rank:
                 yield inp, matrix[users], ans
@@ -82,6 +90,22 @@ def _evaluate(trainer, ds, matrix, batch_size, fused=False):
         torch.distributed.all_gather_object(parts, (pred, answers), group=trainer.pg)
         pred, answers = np.concatenate([p for p, _ in parts]), np.concatenate([a for _, a in parts])
     return get_full_sort_score(answers, pred)
+
+
+def _device_epoch(trainer, dev_data, train_ds, args, nstep):
+    """One training epoch on batches built on the GPU (--device_batches): the same rng.permutation call as epoch_batches, full batches
+    only (one captured graph shape).  Under data parallelism every rank builds its own rows lo:hi of the same global batch; the draws
+    are indexed by global row, the normaliser counts the global batch.  `nstep`: the steps the run has taken so far (step nstep + i draws with `step` = nstep + i).  Returns the steps taken."""
+    from ..dp import shard_bounds, skip_batch
+    B = args.batch_size
+    dev_data.set_order(train_ds.rng.permutation(len(train_ds)))
+    if skip_batch(B, trainer.world):
+        return 0
+    lo, hi = shard_bounds(B, trainer.rank, trainer.world)
+    starts = range(0, len(train_ds) - B + 1, B)
+    for i, s in enumerate(starts):
+        trainer.step_device(dev_data.train_stage(s, B, args.seed, nstep + i, rows=(lo, hi)), b_offset=lo)
+    return len(starts)
 
 
 def main(argv=None):
@@ -117,22 +141,28 @@ def main(argv=None):
     trainer = FusedStosaTrainer(model, lambda1, lambda2, lr=args.lr, betas=(args.adam_beta1, args.adam_beta2), weight_decay=args.weight_decay,
                                 process_group=pg, use_graph=args.use_graph, seed=args.seed)
     ckpt = os.path.join(args.output_dir, "adt-%s-%d-%d-%d.pt" % (args.dataset, args.hidden_units, args.num_layers, args.num_heads))
-    best, wait, T, nseq = None, 0, 0.0, 0
+    dev_data = DeviceDisenData(user_seq, args.item_size, args.maxlen, model.dev, valid_matrix, test_matrix) if args.device_batches else None
+    best, wait, T, nseq, nstep = None, 0, 0.0, 0, 0
     for epoch in range(args.epochs):
         t0 = time.time()
-        for users, inp, dec, pos, neg, _ in train_ds.epoch_batches(args.batch_size):
-            if len(users) != args.batch_size or skip_batch(len(users), world):
-                continue          # one captured graph shape
-            if pg is None:
-                trainer.step(inp, dec, pos, neg)
-            else:                 # same global batch on every rank (same seed); each trains on its rows with the GLOBAL normalisers
-                lo, hi = shard_bounds(len(users), rank, world)
-                trainer.step(inp[lo:hi], dec[lo:hi], pos[lo:hi], neg[lo:hi], n_target_global=int((np.asarray(pos) > 0).sum()), b_offset=lo,
-                             norms_scale=len(users) / float(hi - lo))
-            nseq += len(users)
+        if dev_data is not None:
+            done = _device_epoch(trainer, dev_data, train_ds, args, nstep)
+            nstep += done
+            nseq += done * args.batch_size
+        else:
+            for users, inp, dec, pos, neg, _ in train_ds.epoch_batches(args.batch_size):
+                if len(users) != args.batch_size or skip_batch(len(users), world):
+                    continue          # one captured graph shape
+                if pg is None:
+                    trainer.step(inp, dec, pos, neg)
+                else:                 # same global batch on every rank (same seed); each trains on its rows with the GLOBAL normalisers
+                    lo, hi = shard_bounds(len(users), rank, world)
+                    trainer.step(inp[lo:hi], dec[lo:hi], pos[lo:hi], neg[lo:hi], n_target_global=int((np.asarray(pos) > 0).sum()), b_offset=lo,
+                                 norms_scale=len(users) / float(hi - lo))
+                nseq += len(users)
         torch.cuda.synchronize()
         T += time.time() - t0
-        scores = _evaluate(trainer, valid_ds, valid_matrix, args.eval_batch_size, args.fused_eval)
+        scores = _evaluate(trainer, valid_ds, valid_matrix, args.eval_batch_size, args.fused_eval, dev_data)
         parts = trainer.loss_parts().cpu().numpy()      # a collective under data parallelism: every rank calls it
         if rank == 0:
             print(json.dumps({"epoch": epoch, "train_seconds": T, "sequences_per_sec": nseq / max(T, 1e-9), "n_gpus": world,
@@ -149,8 +179,8 @@ def main(argv=None):
     if world > 1:
         torch.distributed.barrier()
     model.load_state_dict(torch.load(ckpt))
-    valid_scores = _evaluate(trainer, valid_ds, valid_matrix, args.eval_batch_size, args.fused_eval)
-    scores = _evaluate(trainer, test_ds, test_matrix, args.eval_batch_size, args.fused_eval)
+    valid_scores = _evaluate(trainer, valid_ds, valid_matrix, args.eval_batch_size, args.fused_eval, dev_data)
+    scores = _evaluate(trainer, test_ds, test_matrix, args.eval_batch_size, args.fused_eval, dev_data)
     if rank == 0:
         print("(%s, %s, %s, %s, %s, %s, %s, %s)" % (valid_scores[0], valid_scores[2], valid_scores[3], valid_scores[-1], scores[0], scores[2], scores[3], scores[-1]))
     if pg is not None:

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..fullrank import fused_ids_or_two_pass
+from ..fullrank import _seen, fused_ids_or_two_pass
 from ..wide import TapeTrainer, loss_norms
 
 
@@ -31,6 +31,7 @@ class FusedStosaTrainer(TapeTrainer):
         super().__init__(model, w, "item_decoder.layer.0.enc_attention.mean_query.weight", lr, betas, eps, weight_decay, 1e30, process_group,
                          use_graph, n=model.n_trained_floats)
         model.seed_trainer(seed)
+        self._device_norms = {}          # step_device: (rows, global rows) -> device normalisers
 
     def stage(self, input_ids, dec_ids, pos_ids, neg_ids, n_target_global=None, norms_scale=1):
         m = self.model
@@ -48,6 +49,15 @@ class FusedStosaTrainer(TapeTrainer):
     def step(self, input_ids, dec_ids, pos_ids, neg_ids, n_target_global=None, b_offset=0, norms_scale=1):
         self.step_staged(self.stage(input_ids, dec_ids, pos_ids, neg_ids, n_target_global, norms_scale), b_offset)
 
+    def step_device(self, st, b_offset=0):
+        """One step on a batch that is on the device already (DeviceDisenData.train_stage): adds the normalisers -- kept per
+        (rows, global rows), so a step uploads nothing -- and runs step_staged.  Under data parallelism st holds this rank's rows of a
+        batch of st["B_global"] sequences and b_offset is the first of them."""
+        key = (st["B"], st.get("B_global", st["B"]))
+        if key not in self._device_norms:
+            self._device_norms[key] = loss_norms(self.model, key[0] * self.model.maxlen, scale=key[1] / float(key[0]))
+        self.step_staged(dict(st, norms=self._device_norms[key]), b_offset)
+
     # ------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def full_sort(self, batches, topk=40, fused=False):
@@ -55,8 +65,9 @@ class FusedStosaTrainer(TapeTrainer):
         items by ascending distance with the seen items pushed to 1e24 and keep `topk`, all on the device (model.predict_full: adt_wdist_full,
         or adt_kldist_full for distance_metric 'kl', whose scores depend on each batch's rows being the eval batch -- pass the reference's
         eval batches -- then adt_topk_masked); only the (B, topk) ids come back.  `seen` is the users' rows of the train/valid rating matrix as a scipy
-        CSR matrix, a dense (B, item_size) 0/1 array, an int32 (indptr, indices) pair, or None (ops.seen_csr).  Returns (pred_list (N, topk), answers (N, A)) for
-        get_full_sort_score.
+        CSR matrix, a dense (B, item_size) 0/1 array, an int32 (indptr, indices) pair, or None (ops.seen_csr).  input_ids may be a device int32
+        tensor and `seen` a pair of device int32 tensors (DeviceDisenData.eval_batch): both are used where they are, nothing is copied from the
+        host.  Returns (pred_list (N, topk), answers (N, A)) for get_full_sort_score.
 
         fused=True (Wasserstein only; 'kl' raises): no (B, item_size) distance matrix -- the item image is packed once for all batches
         (adt_wdist_pack) and every batch is one adt_full_rank_from call with first_id = 0 (the padding item competes, as in the
@@ -71,7 +82,9 @@ class FusedStosaTrainer(TapeTrainer):
         def two_pass(input_ids, indptr, indices):
             return ops.topk_masked(m.predict_full(input_ids), topk, indptr, indices).cpu().numpy().astype(np.int64)
         for input_ids, seen, ans in batches:
-            indptr, indices = ops.seen_csr(seen, len(input_ids), dev)
+            indptr, indices = _seen(seen, len(input_ids), dev)
+            if indices is not None and indices.numel() == 0:      # a device pair that lists nothing: as the host forms, no seen list
+                indptr, indices = None, None
             if fused:
                 _, _, top_idx, _ = m.rank_full(input_ids, None, (indptr, indices), topk, image, first_id=0)
                 ids, fell_back = fused_ids_or_two_pass(top_idx, lambda: two_pass(input_ids, indptr, indices))

@@ -348,6 +348,32 @@ int adt_full_rank_from(const float* F, int ldf, const float* E, int lde, const f
 int adt_wdist_pack(const float* M, const float* C, int ld, int rows, int d, int elu, float* img, int ldi, float* nrm, float nrm_scale,
                    void* stream);
 
+/* ---- STOSA-ADT batches built on the device (adt_seqbatch.cuh; stosa/datasets.py:202-300, utils.py:32-36 neg_sample) -----------------
+ * Resident inputs: the user sequences as CSR (seq_off int64 (U + 1), seq_items int32, ids >= 1) and every user's sorted, de-duplicated
+ * item set as a second CSR (set_off, set_items; the whole sequence, held-out items included).  users: the device int32 list of the
+ * whole (GLOBAL) batch, n_users entries, each in 0..U-1 (the caller's to guarantee: the library does not know U).  The call writes rows
+ * row0 .. row0 + n_rows - 1 of that batch into (n_rows, L) int32 arrays, left-padded with 0.  For a sequence s of length n, with Python
+ * slicing (an empty slice is all padding) and each array keeping its last L entries:
+ *   cut 3 (train): inp = s[:-3], pos = s[1:-2], dec = s[:-4]
+ *   cut 2 (valid): inp = s[:-2], pos = s[1:-1], dec = s[:-3]
+ *   cut 1 (test):  inp = s[:-1], pos = s[1:],   dec = s[:-2]
+ * neg (NULL: not wanted, as in evaluation; dec and pos may be NULL likewise) is 0 where pos is 0; elsewhere it is uniform over
+ * [1, item_size - 1] minus the user's set, by rejection: attempt a of position t of GLOBAL row r proposes
+ * adt_seqbatch_draw(seed, step, r, t, a, item_size), and the first proposal outside the set wins, so a shard draws what the whole
+ * batch would.  Termination: at most 32 proposals (attempts 0..31) are rejected; after that the first id outside the set is taken,
+ * walking upward from the last proposal, cyclically in [1, item_size - 1] (at most item_size - 1 steps); 0 when the set covers every id.
+ * inv_count (NULL: not wanted) receives 1 / max(number of non-zero pos entries over ALL n_users users, 1) as a device float: an
+ * integer sum (no float atomics), the quotient rounded once from double.
+ * Errors: cut outside 1..3, L < 1, item_size < 2, row0 + n_rows > n_users. */
+int adt_seqbatch_build(const int64_t* seq_off, const int32_t* seq_items, const int64_t* set_off, const int32_t* set_items,
+                       const int32_t* users, int n_users, int row0, int n_rows, int L, int cut, int item_size, uint32_t seed,
+                       uint32_t step, int32_t* inp, int32_t* dec, int32_t* pos, int32_t* neg, float* inv_count, void* stream);
+/* Host only (like adt_rng_keep): the id in [1, item_size - 1] that attempt `attempt` proposes for position t of global row `row`; the
+ * same inline function the kernel calls.  A chain of adt_hash32 over (seed, step, row, t, attempt), mapped onto the range by a
+ * multiply-high, 1 + ((uint64_t)h * (item_size - 1) >> 32): bias at most (item_size - 1) / 2^32.  0 for item_size < 2 or a negative
+ * index. */
+int adt_seqbatch_draw(uint32_t seed, uint32_t step, int row, int t, int attempt, int item_size);
+
 /* ==== model-level executor: SASRecADT (sasrec/model.py:8-97) + loop body (sasrec/main.py:146-173) ====== */
 typedef struct adt_sasrec_cfg {
   int32_t item_num;     /* V; item table has V+1 rows                      */
