@@ -1,7 +1,8 @@
-// C ABI (include/adt_hip.h, "STOSA-ADT batches built on the device"): launch wrapper of adt_seqbatch.cuh and the host-side draw.  Host
-// code only enqueues work on the caller's stream.
+// C ABI (include/adt_hip.h, "STOSA-ADT batches built on the device" and "full-sort scores on the device"): launch wrappers of
+// adt_seqbatch.cuh and adt_hithist.cuh, and the host-side draw.  Host code only enqueues work on the caller's stream.
 #include "adt_host.h"
 
+#include "adt_hithist.cuh"
 #include "adt_seqbatch.cuh"
 
 using namespace adt;
@@ -36,6 +37,25 @@ int adt_seqbatch_build(const int64_t* seq_off, const int32_t* seq_items, const i
     return adt_check_launch("seqbatch_build(count)");
   }
   return 0;
+}
+
+int adt_hit_hist(const int32_t* top_idx, int ld, int n_rows, int K, const int32_t* answers, int rows_per_group, int64_t* hist,
+                 int32_t* hit_pos, void* stream) {
+  if (K < 1 || K > ADT_HITHIST_MAX_K) return adt_set_error("hit_hist: K=%d outside 1..%d", K, ADT_HITHIST_MAX_K);
+  if (ld < K) return adt_set_error("hit_hist: ld=%d < K=%d", ld, K);
+  if (rows_per_group < 1) return adt_set_error("hit_hist: rows_per_group=%d < 1", rows_per_group);
+  if (n_rows < 0 || n_rows % rows_per_group != 0)
+    return adt_set_error("hit_hist: n_rows=%d is not a multiple of rows_per_group=%d", n_rows, rows_per_group);
+  if (n_rows == 0) return 0;      // nothing to count: the pointers are not looked at (an empty tensor has none)
+  if (!top_idx || !answers || !hist) return adt_set_error("hit_hist: NULL top_idx, answers or hist");
+  // 16 rows of a group per block (4 per wave) up to 256 blocks per group; beyond that the waves stride over the group's rows
+  const int groups = n_rows / rows_per_group;
+  int chunks = (rows_per_group + 4 * ADT_HITHIST_WAVES - 1) / (4 * ADT_HITHIST_WAVES);
+  chunks = chunks > 256 ? 256 : chunks;
+  const int64_t blocks = (int64_t)groups * chunks;      // <= n_rows
+  HitHistArgs a{top_idx, ld, K, rows_per_group, chunks, answers, (unsigned long long*)hist, hit_pos};
+  hipLaunchKernelGGL(k_hit_hist, dim3((unsigned)blocks), dim3(64 * ADT_HITHIST_WAVES), 0, (hipStream_t)stream, a);
+  return adt_check_launch("hit_hist");
 }
 
 }  // extern "C"

@@ -697,3 +697,30 @@ def seqbatch_draw(seed, step, row, t, attempt, item_size):
     """The id in [1, item_size - 1] that attempt `attempt` proposes as the negative of position t of GLOBAL batch row `row` (host only:
     the inline function adt_seqbatch_build's kernel calls)."""
     return int(_lib.load().adt_seqbatch_draw(int(seed) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF, int(row), int(t), int(attempt), int(item_size)))
+
+
+# ---- STOSA-ADT full-sort scores on the device (include/adt_hip.h: adt_hit_hist; adt_amd/csrc/adt_hithist.cuh) ---------------------------
+def hit_hist(top_idx, answers, rows_per_group=None, hist=None, want_pos=False):
+    """Histogram of where each held-out item stands in its top-K list: top_idx (N, K) device int32 at any row stride (adt_full_rank_from /
+    adt_topk_masked output, -1 tails included), group-major -- row r belongs to group r // rows_per_group and its answer is
+    answers[r % rows_per_group]; answers a device int32 (rows_per_group,) or (rows_per_group, 1) (rows_per_group defaults to its
+    length).  Position = the first j with top_idx[r][j] == answer, K when there is none.  Returns hist (groups, K + 1) int64: new zeros
+    when `hist` is None, otherwise `hist` itself, accumulated into; with want_pos also the (N,) int32 positions."""
+    if top_idx.dim() != 2 or top_idx.dtype != torch.int32 or (top_idx.shape[1] > 1 and top_idx.stride(1) != 1):
+        raise _lib.AdtError("hit_hist: top_idx must be (N, K) int32 with unit column stride")
+    N, K = top_idx.shape
+    ans = answers.reshape(-1)
+    if ans.dtype != torch.int32 or not ans.is_contiguous():
+        raise _lib.AdtError("hit_hist: answers must be a contiguous int32 (rows_per_group,) or (rows_per_group, 1) tensor")
+    rpg = ans.numel() if rows_per_group is None else int(rows_per_group)
+    if rpg < 1 or ans.numel() != rpg or N % rpg != 0:
+        raise _lib.AdtError("hit_hist: %d list rows, %d answers, rows_per_group=%d" % (N, ans.numel(), rpg))
+    groups = N // rpg
+    if hist is None:
+        hist = torch.zeros(groups, K + 1, device=top_idx.device, dtype=torch.int64)
+    elif hist.dtype != torch.int64 or not hist.is_contiguous() or (N > 0 and hist.numel() != groups * (K + 1)):
+        raise _lib.AdtError("hit_hist: hist must be contiguous int64 with %d x %d entries" % (groups, K + 1))
+    pos = torch.empty(N, device=top_idx.device, dtype=torch.int32) if want_pos else None
+    ld = top_idx.stride(0) if N > 1 else max(top_idx.stride(0), K)
+    _lib.check(_lib.load().adt_hit_hist(_p(top_idx), int(ld), N, K, _p(ans), rpg, _p(hist), _p(pos), _stream()), "hit_hist")
+    return (hist, pos) if want_pos else hist

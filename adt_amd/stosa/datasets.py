@@ -78,9 +78,9 @@ class DisenDataset:
 
 class DeviceDisenData:
     """DisenDataset's batches built on the GPU (adt_seqbatch_build).  Resident on the device as int32 CSR, uploaded
-    once: the user sequences, every user's sorted item set (the whole sequence, as DisenDataset.sets) and the valid / test rating
-    matrices; every indptr is kept on the host as well, so a contiguous user range is sliced without a device read.  No call below
-    copies ids, CSR rows or normalisers from the host."""
+    once: the user sequences, every user's sorted item set (the whole sequence, as DisenDataset.sets), the valid / test rating
+    matrices and the held-out ids of both splits; every indptr is kept on the host as well, so a contiguous user range is sliced without
+    a device read.  No call below copies ids, CSR rows or normalisers from the host."""
     CUT = {"train": 3, "valid": 2, "test": 1}
 
     def __init__(self, user_seq, item_size, maxlen, device, valid_matrix, test_matrix):
@@ -96,7 +96,7 @@ class DeviceDisenData:
             return torch.from_numpy(off).to(self.dev), torch.from_numpy(items).to(self.dev)
         self.seq_off, self.seq_items = csr(user_seq)
         self.set_off, self.set_items = csr(sets)
-        self.seen, self.answers = {}, {}
+        self.seen, self.answers, self.answers_dev = {}, {}, {}
         for split, matrix in (("valid", valid_matrix), ("test", test_matrix)):
             m = matrix.tocsr()
             assert m.shape[0] == self.n, (m.shape, self.n)
@@ -104,6 +104,7 @@ class DeviceDisenData:
             self.seen[split] = (ip, torch.from_numpy(ip).to(self.dev), torch.from_numpy(np.ascontiguousarray(m.indices, dtype=np.int32)).to(self.dev))
             c = self.CUT[split]      # the held-out item; 0 for a sequence too short to have one (DisenDataset raises IndexError there)
             self.answers[split] = np.array([[s[-c] if len(s) >= c else 0] for s in user_seq], np.int64)
+            self.answers_dev[split] = torch.from_numpy(self.answers[split][:, 0].astype(np.int32)).to(self.dev)
         self._all_users = torch.arange(self.n, device=self.dev, dtype=torch.int32)
         self.order = None
 
@@ -137,3 +138,14 @@ class DeviceDisenData:
         ip, ip_dev, ix_dev = self.seen[split]
         indptr = ip_dev[start:start + B + 1] - int(ip[start])
         return inp, (indptr, ix_dev[int(ip[start]):int(ip[start + B])]), self.answers[split][start:start + B]
+
+    def eval_stage(self, split, start, B):
+        """eval_batch as a dict for FusedStosaTrainer.full_sort_scores and the search: inp, indptr, indices (eval_batch's), answers (the
+        resident held-out ids, device int32 (B,)), answers_host (eval_batch's numpy (B, 1)) and min_unseen -- the smallest number of items
+        a user of the batch has not seen, item_size - max(stored entries per row), a host int from the host indptr: a fused ranking
+        (first_id = 0) returns topk ids for every row exactly when min_unseen >= topk."""
+        inp, (indptr, indices), ans = self.eval_batch(split, start, B)
+        ip = self.seen[split][0]
+        most = int(np.diff(ip[start:start + B + 1]).max()) if B > 0 else 0
+        return {"inp": inp, "indptr": indptr, "indices": indices, "answers": self.answers_dev[split][start:start + B], "answers_host": ans,
+                "min_unseen": self.item_size - most}

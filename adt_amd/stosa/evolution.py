@@ -55,6 +55,11 @@ def parse_args(argv=None):
     p.add_argument("--out_dir", default="res")
     p.add_argument("--fused_eval", action="store_true",
                    help="score candidates without the (group * B, item_size) distance matrix: packed item image + adt_full_rank_from")
+    p.add_argument("--device_batches", action="store_true",
+                   help="cut the candidates' validation batches on the GPU from resident sequences (DeviceDisenData.eval_stage); the warm-up "
+                        "stays on host batches")
+    p.add_argument("--device_scores", action="store_true",
+                   help="score candidates on the GPU: one histogram of hit positions per candidate (adt_hit_hist) instead of id lists on the host")
     return p.parse_args(argv)
 
 

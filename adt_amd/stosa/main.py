@@ -17,7 +17,7 @@ import torch
 from . import utils as U
 from .datasets import DeviceDisenData, DisenDataset, get_user_seqs
 from .models import DisenDistSAModel
-from .trainer import FusedStosaTrainer, get_full_sort_score
+from .trainer import FusedStosaTrainer, get_full_sort_score, scores_from_hist
 
 
 def parse_args(argv=None):
@@ -55,6 +55,8 @@ def parse_args(argv=None):
                    help="full-sort evaluation without the (B, item_size) distance matrix: packed item image + adt_full_rank_from (Wasserstein only)")
     p.add_argument("--device_batches", action="store_true",
                    help="build the training and evaluation batches on the GPU from resident sequences (adt_seqbatch_build) instead of on the host")
+    p.add_argument("--device_scores", action="store_true",
+                   help="score the full sort on the GPU: a histogram of hit positions (adt_hit_hist) instead of the (N, 40) id lists on the host")
     return p.parse_args(argv)
 
 
@@ -71,19 +73,27 @@ def _write_synthetic(path, users=22363, items=12101, seed=42):
             f.write("%d %s\n" % (u, " ".join(str(int(x)) for x in seq)))
 
 
-def _evaluate(trainer, ds, matrix, batch_size, fused=False, dev_data=None):
+def _evaluate(trainer, ds, matrix, batch_size, fused=False, dev_data=None, device_scores=False):
     """Full-sort scores of the whole user set on every rank: under data parallelism rank r sorts batches r, r+W, ... on its GPU
     and the (N, 40) id lists are gathered (a few hundred KB).  dev_data (--device_batches): the same batches of the same users, cut on
-    the GPU by DeviceDisenData.eval_batch."""
+    the GPU by DeviceDisenData.eval_batch.  device_scores (--device_scores): the id lists stay on the GPU; every rank keeps the
+    41-entry histogram of hit positions (FusedStosaTrainer.full_sort_hist), the ranks sum theirs with one all-reduce, and the 13
+    numbers come from scores_from_hist."""
     def gen():
         if dev_data is not None:
+            cut = dev_data.eval_stage if device_scores else dev_data.eval_batch
             for i, s in enumerate(range(0, len(ds), batch_size)):
                 if i % trainer.world == trainer.rank:
-                    yield dev_data.eval_batch(ds.data_type, s, min(batch_size, len(ds) - s))
+                    yield cut(ds.data_type, s, min(batch_size, len(ds) - s))
             return
         for i, (users, inp, dec, pos, neg, ans) in enumerate(ds.epoch_batches(batch_size, shuffle=False)):
             if i % trainer.world == trainer.rank:
                 yield inp, matrix[users], ans
+    if device_scores:
+        hist = trainer.full_sort_hist(gen(), fused=fused)
+        if trainer.world > 1:
+            torch.distributed.all_reduce(hist, op=torch.distributed.ReduceOp.SUM, group=trainer.pg)
+        return scores_from_hist(hist.cpu().numpy())
     pred, answers = trainer.full_sort(gen(), fused=fused)
     if trainer.world > 1:
         parts = [None] * trainer.world
@@ -162,7 +172,7 @@ def main(argv=None):
                 nseq += len(users)
         torch.cuda.synchronize()
         T += time.time() - t0
-        scores = _evaluate(trainer, valid_ds, valid_matrix, args.eval_batch_size, args.fused_eval, dev_data)
+        scores = _evaluate(trainer, valid_ds, valid_matrix, args.eval_batch_size, args.fused_eval, dev_data, args.device_scores)
         parts = trainer.loss_parts().cpu().numpy()      # a collective under data parallelism: every rank calls it
         if rank == 0:
             print(json.dumps({"epoch": epoch, "train_seconds": T, "sequences_per_sec": nseq / max(T, 1e-9), "n_gpus": world,
@@ -179,8 +189,8 @@ def main(argv=None):
     if world > 1:
         torch.distributed.barrier()
     model.load_state_dict(torch.load(ckpt))
-    valid_scores = _evaluate(trainer, valid_ds, valid_matrix, args.eval_batch_size, args.fused_eval, dev_data)
-    scores = _evaluate(trainer, test_ds, test_matrix, args.eval_batch_size, args.fused_eval, dev_data)
+    valid_scores = _evaluate(trainer, valid_ds, valid_matrix, args.eval_batch_size, args.fused_eval, dev_data, args.device_scores)
+    scores = _evaluate(trainer, test_ds, test_matrix, args.eval_batch_size, args.fused_eval, dev_data, args.device_scores)
     if rank == 0:
         print("(%s, %s, %s, %s, %s, %s, %s, %s)" % (valid_scores[0], valid_scores[2], valid_scores[3], valid_scores[-1], scores[0], scores[2], scores[3], scores[-1]))
     if pg is not None:

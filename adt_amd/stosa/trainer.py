@@ -11,7 +11,7 @@ leaves at grad=None are outside it).
 import numpy as np
 import torch
 
-from .. import ops
+from .. import _lib, ops
 from ..fullrank import _seen, fused_ids_or_two_pass
 from ..wide import TapeTrainer, loss_norms
 
@@ -95,6 +95,62 @@ class FusedStosaTrainer(TapeTrainer):
             answers.append(np.asarray(ans))
         return np.concatenate(preds), np.concatenate(answers)
 
+    @torch.no_grad()
+    def full_sort_scores(self, batches, topk=40, fused=False):
+        """full_sort + get_full_sort_score without the id lists leaving the GPU: the same loop over the same
+        batches, both distance metrics ('kl' two-pass only: fused=True raises as in full_sort), but every batch's (B, topk) device ids go
+        straight into ops.hit_hist with the batch's held-out ids (one per user; uploaded as int32 when they arrive as numpy, used where
+        they are when they are a device tensor).  Nothing is copied from the device until the one copy of the histogram after the last
+        batch.  Returns (scores -- the 13 numbers of get_full_sort_score, by scores_from_hist --, hist (topk + 1,) numpy int64).
+
+        A batch is (input_ids, seen, answers), (input_ids, seen, answers, min_unseen) or the dict of DeviceDisenData.eval_stage.
+        fused=True recomputes a batch two-pass when some row could come back short, decided from host data: a row has
+        item_size - (its seen count) candidates (first_id = 0: all item_size ids compete), so the batch falls back when the smallest such
+        count is below topk.  The count comes from the host indptr of a host `seen` (a repeated stored id only makes it larger: more
+        fallbacks, never fewer, and the two-pass form is the reference's own); for a device (indptr, indices) pair the caller passes it as
+        min_unseen.  Sets self.fused_fallbacks as full_sort does."""
+        hist = self.full_sort_hist(batches, topk, fused).cpu().numpy()
+        return scores_from_hist(hist), hist
+
+    @torch.no_grad()
+    def full_sort_hist(self, batches, topk=40, fused=False):
+        """The loop of full_sort_scores; returns the (topk + 1,) int64 histogram still on the device (data-parallel callers all-reduce it
+        before the copy)."""
+        m = self.model
+        dev = m.dev
+        image = m.item_image() if fused else None
+        self.fused_fallbacks = 0
+        hist = torch.zeros(1, topk + 1, device=dev, dtype=torch.int64)
+        for batch in batches:
+            if isinstance(batch, dict):
+                input_ids, seen, ans, min_unseen = batch["inp"], (batch["indptr"], batch["indices"]), batch["answers"], batch["min_unseen"]
+            else:
+                input_ids, seen, ans = batch[:3]
+                min_unseen = batch[3] if len(batch) > 3 else None
+            B = len(input_ids)
+            if isinstance(seen, tuple) and all(x is None or isinstance(x, torch.Tensor) for x in seen):
+                indptr, indices = seen
+                if fused and min_unseen is None and indices is not None and indices.numel() > 0:
+                    raise _lib.AdtError("full_sort_scores(fused=True): a device seen list needs the batch's smallest unseen count (min_unseen; "
+                                        "DeviceDisenData.eval_stage gives it): it is not read back from the device")
+            else:
+                ip, ix = ops.seen_csr_host(seen, B)
+                min_unseen = m.item_size if ip is None else m.item_size - int(np.diff(ip[:B + 1]).max())
+                indptr, indices = (None, None) if ip is None else (torch.from_numpy(ip).to(dev), torch.from_numpy(ix).to(dev))
+            if indices is not None and indices.numel() == 0:      # as full_sort: a pair that lists nothing is no seen list
+                indptr, indices, min_unseen = None, None, m.item_size
+            if not isinstance(ans, torch.Tensor):
+                ans = np.asarray(ans)
+                assert ans.ndim == 1 or ans.shape[1] == 1, "scores_from_hist needs one held-out item per user"
+                ans = torch.from_numpy(np.ascontiguousarray(ans.reshape(-1), dtype=np.int32)).to(dev)
+            if fused and min_unseen >= topk:
+                top_idx = m.rank_full(input_ids, None, (indptr, indices), topk, image, first_id=0)[2]
+            else:
+                self.fused_fallbacks += int(bool(fused))
+                top_idx = ops.topk_masked(m.predict_full(input_ids), topk, indptr, indices)
+            ops.hit_hist(top_idx, ans, hist=hist)
+        return hist[0]
+
 
 def recall_at_k(actual, predicted, topk):
     """stosa/utils.py:228-242: mean over the users that have answers of |top-k hits| / |answers|."""
@@ -134,3 +190,32 @@ def get_full_sort_score(answers, pred_list):
     for k in (1, 5, 10, 15, 20, 40):
         out += [recall_at_k(answers, pred_list, k), ndcg_k(answers, pred_list, k)]
     return out + [cal_mrr(answers, pred_list)]
+
+
+_SCORE_KS = (1, 5, 10, 15, 20, 40)
+
+
+def scores_from_hist(hist_row):
+    """get_full_sort_score from the histogram of hit positions (ops.hit_hist), on the host in float64.  hist_row: one
+    (K + 1,) integer row h, h[j] = the users whose held-out item stands at position j of their top-K list, h[K] = those whose list does
+    not hold it; N = sum(h).  HIT@k = sum(h[:k]) / N, NDCG@k = sum_{j<k} h[j] / log2(j + 2) / N, MRR = sum_{j<K} h[j] / (j + 1) / N.
+
+    Precondition: every user has exactly ONE held-out item (DisenDataset._views and DeviceDisenData.answers produce nothing else).  Then
+    the ideal DCG is 1, recall is hit / 1 and the first hit is the only one, so the three metrics depend on the hit position alone.
+    K >= 40, the largest k reported; otherwise AdtError."""
+    h = np.asarray(hist_row)
+    if h.ndim != 1 or not np.issubdtype(h.dtype, np.integer):
+        raise _lib.AdtError("scores_from_hist: one (K + 1,) integer row, got %s %s" % (h.dtype, h.shape))
+    K = h.size - 1
+    if K < _SCORE_KS[-1]:
+        raise _lib.AdtError("scores_from_hist: K=%d < %d, the largest k reported" % (K, _SCORE_KS[-1]))
+    n = float(h.sum())
+    if n <= 0:
+        raise _lib.AdtError("scores_from_hist: an empty histogram")
+    hf = h[:K].astype(np.float64)
+    j = np.arange(K, dtype=np.float64)
+    gain = hf / np.log2(j + 2.0)
+    out = []
+    for k in _SCORE_KS:
+        out += [float(hf[:k].sum() / n), float(gain[:k].sum() / n)]
+    return out + [float((hf / (j + 1.0)).sum() / n)]

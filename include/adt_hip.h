@@ -374,6 +374,18 @@ int adt_seqbatch_build(const int64_t* seq_off, const int32_t* seq_items, const i
  * index. */
 int adt_seqbatch_draw(uint32_t seed, uint32_t step, int row, int t, int attempt, int item_size);
 
+/* ---- STOSA-ADT full-sort scores on the device (adt_hithist.cuh; stosa/trainer.py:62-86 get_full_sort_score) ---------------------------
+ * Where each held-out item stands in its top-K list, as an integer histogram.  top_idx: n_rows rows of K ids at row stride ld >= K, the
+ * output of adt_full_rank_from or adt_topk_masked, -1 tails included.  The rows are group-major: row r belongs to group
+ * r / rows_per_group and its answer is answers[r % rows_per_group]; n_rows is a multiple of rows_per_group (one group:
+ * rows_per_group = n_rows).  hit_pos[r] (hit_pos may be NULL) = the smallest j with top_idx[r][j] == answer, or K when there is none;
+ * ids compare as plain integers (answer 0 hits where item 0 is listed) and a -1 never matches.  hist[g][hit_pos[r]] += 1, with hist
+ * (n_rows / rows_per_group, K + 1) contiguous int64: the call ACCUMULATES, the caller supplies the zeros.  Integer atomics only, so
+ * the result does not depend on the order of execution.  n_rows = 0 is a no-op that looks at no pointer.
+ * Errors: K outside 1..128, ld < K, rows_per_group < 1, n_rows % rows_per_group != 0, a NULL top_idx, answers or hist. */
+int adt_hit_hist(const int32_t* top_idx, int ld, int n_rows, int K, const int32_t* answers, int rows_per_group, int64_t* hist,
+                 int32_t* hit_pos, void* stream);
+
 /* ==== model-level executor: SASRecADT (sasrec/model.py:8-97) + loop body (sasrec/main.py:146-173) ====== */
 typedef struct adt_sasrec_cfg {
   int32_t item_num;     /* V; item table has V+1 rows                      */
