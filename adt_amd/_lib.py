@@ -128,6 +128,9 @@ SIGNATURES = {
     "adt_wdist_pack": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _F, _P]),
     "adt_seqbatch_build": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U, _U, _P, _P, _P, _P, _P, _P]),
     "adt_seqbatch_draw": (_I, [_U, _U, _I, _I, _I, _I]),
+    "adt_bertbatch_build": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _U, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "adt_bertbatch_eval": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "adt_bertbatch_token": (_I, [_U, _U, _I, _I, _U, _I, _I, _P]),
     "adt_hit_hist": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P]),
     "adt_item_sort_supported": (_I, [_I]),
     "adt_item_sort_work_ints": (_L, [_I, _I, _I]),

@@ -125,6 +125,98 @@ class BertTrainDataset:
             yield self.src[idx], self.dec[idx], self.labels[idx]
 
 
+class DeviceBertData:
+    """BertTrainDataset's examples and BertEvalDataset's rows built on the GPU (adt_bertbatch_build / adt_bertbatch_eval; DESIGN.md section
+    16).  Resident on the device, uploaded once: the training sequences as CSR over the U users with a non-empty sequence, in user order,
+    and the table of the W sliding windows BertTrainDataset cuts (offset into the items, length).  Examples are numbered, not stored:
+    with D = dupe_factor, example e < W * D is random copy e % D of window e // D and example W * D + u is the mask-last example of the
+    u-th user, so len(self) == len(BertTrainDataset(...)).  The masks are a function of (seed, salt, example, position): one salt keeps
+    one mask per example for a whole run (the reference's dupe_factor copies), salt = epoch draws a fresh set every epoch."""
+
+    def __init__(self, user_train, usernum, itemnum, maxlen, mask_prob, device, dupe_factor=10, prop_sliding_window=0.5):
+        import torch
+        from .. import ops
+        self.itemnum, self.maxlen, self.dupe_factor, self.dev = int(itemnum), int(maxlen), int(dupe_factor), torch.device(device)
+        assert self.dupe_factor >= 1 and self.maxlen >= 1 and self.itemnum >= 1, (dupe_factor, maxlen, itemnum)
+        self.thr_mask = ops.bertbatch_threshold(mask_prob)
+        L = self.maxlen
+        step = int(prop_sliding_window * L) if prop_sliding_window != -1 else L
+        self.user_index, lens, items, win_start, win_len = {}, [], [], [], []
+        at = 0
+        for user in range(1, usernum + 1):
+            seqs = user_train.get(user, [])
+            n = len(seqs)
+            if n < 1:
+                continue
+            self.user_index[user] = len(lens)
+            lens.append(n)
+            items.append(np.asarray(seqs, np.int32))
+            if n <= L:
+                win_start.append(at), win_len.append(n)
+            else:       # BertTrainDataset.__init__: windows of maxlen items, the last one flush with the end
+                for b in (list(range(n - L, 0, -step)) + [0])[::-1]:
+                    win_start.append(at + b), win_len.append(L)
+            at += n
+        self.U, self.W = len(lens), len(win_start)
+        seq_off = np.zeros(self.U + 1, np.int64)
+        np.cumsum(lens, out=seq_off[1:])
+        seq_items = np.concatenate(items) if items else np.zeros(0, np.int32)
+        assert seq_items.size == 0 or (seq_items.min() >= 1 and seq_items.max() <= self.itemnum), "item ids must lie in [1, itemnum]"
+        assert self.W * self.dupe_factor + self.U < 2 ** 31, "more than 2^31 examples"
+        self.seq_off, self.seq_items = torch.from_numpy(seq_off).to(self.dev), torch.from_numpy(seq_items).to(self.dev)
+        self.win_start = torch.from_numpy(np.asarray(win_start, np.int64)).to(self.dev)
+        self.win_len = torch.from_numpy(np.asarray(win_len, np.int32)).to(self.dev)
+        self.order = None
+        self._eval = {}
+
+    def __len__(self):
+        return self.W * self.dupe_factor + self.U
+
+    def set_order(self, order):
+        """Upload one epoch's permutation of example ids (the only host -> device copy of an epoch)."""
+        import torch
+        from .._lib import AdtError
+        order = np.ascontiguousarray(order, dtype=np.int64)
+        if order.ndim != 1 or (order.size and (order.min() < 0 or order.max() >= len(self))):
+            raise AdtError("DeviceBertData.set_order: an example id outside 0..%d" % (len(self) - 1))
+        self.order = torch.from_numpy(order.astype(np.int32)).to(self.dev)
+
+    def train_stage(self, start, B, seed, salt, rows=None):
+        """The dict of BertModel.stage for examples order[start:start + B], built on the device (no M_host: the count is not read back) --
+        under data parallelism rows (lo, hi) of that global batch, with local `rows` indices, the global inv_count and the masks the whole
+        batch would get."""
+        from .. import ops
+        assert self.order is not None and 0 <= start and start + B <= self.order.numel(), "set_order first; the batch must lie inside it"
+        lo, hi = (0, B) if rows is None else rows
+        src, dec, _, rows_c, labels_c, M, inv_count = ops.bertbatch_build(
+            self.seq_off, self.seq_items, self.win_start, self.win_len, self.order[start:start + B], self.maxlen, self.dupe_factor, self.itemnum,
+            self.thr_mask, seed, salt, (lo, hi), want_labels=False)
+        return {"B": hi - lo, "B_global": B, "src": src, "dec": dec, "rows": rows_c, "labels": labels_c, "M": M, "inv_count": inv_count}
+
+    def add_eval(self, eval_ds):
+        """Keep a BertEvalDataset's user list and its (N, 1 + C) candidate matrix (the positive, then the sampler's negatives, which it
+        freezes per (user, mode)) resident, under eval_ds.mode."""
+        import torch
+        users = np.array([self.user_index[u] for u in eval_ds.users], np.int32)
+        cand = np.array([eval_ds.sample_data(u)[1] for u in eval_ds.users], np.int32).reshape(len(users), -1)
+        self._eval[eval_ds.mode] = (torch.from_numpy(users).to(self.dev), torch.from_numpy(cand).to(self.dev))
+
+    def eval_len(self, mode):
+        return self._eval[mode][0].numel()
+
+    def eval_batch(self, mode, start, B):
+        """(seq (B, L), candidates (B, 1 + C)), both device int32, of users start .. start + B - 1 of the mode's list: what
+        BertEvalDataset.batches yields, for FusedBertTrainer.evaluate."""
+        from .. import ops
+        users, cand = self._eval[mode]
+        assert 0 <= start and start + B <= users.numel(), (mode, start, B, users.numel())
+        return ops.bertbatch_eval(self.seq_off, self.seq_items, users[start:start + B], self.maxlen, self.itemnum), cand[start:start + B]
+
+    def eval_batches(self, mode, batch_size):
+        n = self.eval_len(mode)
+        return (self.eval_batch(mode, s, min(batch_size, n - s)) for s in range(0, n, batch_size))
+
+
 class BertEvalDataset:
     def __init__(self, user_train, user_val, user_test, usernum, itemnum, maxlen, negative_sampler, mode="val", eval_set=-1):
         self.user_train, self.user_val, self.user_test = user_train, user_val, user_test

@@ -54,7 +54,31 @@ def parse_args(argv=None):
     p.add_argument("--use_graph", type=lambda s: str(s).lower() in ("1", "true", "yes"), default=True)
     p.add_argument("--eval_full", type=lambda s: str(s).lower() in ("1", "true", "yes"), default=False,
                    help="also rank the held-out item against the whole catalogue at every evaluation")
-    return p.parse_args(argv)
+    p.add_argument("--device_batches", action="store_true",
+                   help="mask and build the training batches, and build the evaluation rows, on the GPU from resident sequences "
+                        "(adt_bertbatch_build) instead of on the host; the masks come from a different random stream, so such a run is "
+                        "not the host run's trajectory")
+    p.add_argument("--remask_every_epoch", action="store_true",
+                   help="with --device_batches: draw a fresh set of masks every epoch instead of one per example for the whole run")
+    args = p.parse_args(argv)
+    if args.remask_every_epoch and not args.device_batches:
+        p.error("--remask_every_epoch needs --device_batches")
+    return args
+
+
+def _device_epoch(trainer, data, args, rng, salt, rank=0, world=1):
+    """One epoch of --device_batches: the same rng.permutation(len(data)) call as BertTrainDataset.epoch_batches, uploaded once; full
+    batches only; every rank builds its rows lo:hi of the global batch.  Returns the number of steps."""
+    from ..dp import shard_bounds, skip_batch
+    B = args.batch_size
+    data.set_order(rng.permutation(len(data)))
+    if skip_batch(B, world):
+        return 0
+    lo, hi = shard_bounds(B, rank, world)
+    steps = len(data) // B
+    for i in range(steps):
+        trainer.step_device(data.train_stage(i * B, B, args.dataset_random_seed, salt, rows=(lo, hi) if world > 1 else None), b_offset=lo)
+    return steps
 
 
 def main(argv=None):
@@ -84,11 +108,17 @@ def main(argv=None):
     user_train, user_valid, user_test, usernum, itemnum = D.data_partition(args.dataset, args.data_dir)
     for u in user_train:          # the training sequences include the validation item (bert4rec/trainer.py:165-167)
         user_train[u] = list(user_train[u]) + list(user_valid.get(u, []))
-    train_ds = D.BertTrainDataset(user_train, usernum, itemnum, args.maxlen, args.mask_prob, args.dataset_random_seed, args.dupe_factor,
-                                  args.prop_sliding_window)
+    if args.device_batches:
+        train_ds = D.DeviceBertData(user_train, usernum, itemnum, args.maxlen, args.mask_prob, args.device, args.dupe_factor,
+                                    args.prop_sliding_window)
+    else:
+        train_ds = D.BertTrainDataset(user_train, usernum, itemnum, args.maxlen, args.mask_prob, args.dataset_random_seed, args.dupe_factor,
+                                      args.prop_sliding_window)
     sampler = D.PopularSampler(user_train, user_valid, user_test, usernum, itemnum, args.eval_negative_sample_size)
     val_ds = D.BertEvalDataset(user_train, user_valid, user_test, usernum, itemnum, args.maxlen, sampler, "val", args.eval_set_size)
     test_ds = D.BertEvalDataset(user_train, user_valid, user_test, usernum, itemnum, args.maxlen, sampler, "test", args.eval_set_size)
+    if args.device_batches:
+        train_ds.add_eval(val_ds), train_ds.add_eval(test_ds)
     torch.manual_seed(23)
     model = BertModel(usernum, itemnum, args)
     if world > 1:
@@ -96,25 +126,31 @@ def main(argv=None):
     trainer = FusedBertTrainer(model, lambda1, lambda2, lr=args.lr, betas=(0.9, 0.999), weight_decay=args.weight_decay, clip=args.clip,
                                process_group=pg, use_graph=args.use_graph, seed=23)
     rng = np.random.RandomState(23)
+
+    def eval_batches(ds):
+        return train_ds.eval_batches(ds.mode, args.eval_batch_size) if args.device_batches else ds.batches(args.eval_batch_size)
     best = dict(score=0.0, epoch=0, valid=None, test=None, auc_valid=0.0, auc_test=0.0)
     T, nseq = 0.0, 0
     for epoch in range(args.num_epochs):
         t0 = time.time()
-        for src, dec, lab in train_ds.epoch_batches(args.batch_size, rng):
-            if len(src) != args.batch_size or skip_batch(len(src), world):
-                continue      # keep one captured graph shape (the reference's last partial batch is < 0.5 % of an epoch)
-            if pg is None:
-                trainer.step(src, dec, lab)
-            else:             # every rank draws the same global batch (same seed) and trains on its contiguous rows, with the
-                lo, hi = shard_bounds(len(src), rank, world)     # GLOBAL normalisers: label count, B*L*d, B*L*H of the whole batch
-                trainer.step(src[lo:hi], dec[lo:hi], lab[lo:hi], n_valid_global=int(np.count_nonzero(lab)), b_offset=lo,
-                             norms_scale=len(src) / float(hi - lo))
-            nseq += len(src)
+        if args.device_batches:
+            nseq += args.batch_size * _device_epoch(trainer, train_ds, args, rng, epoch if args.remask_every_epoch else 0, rank, world)
+        else:
+            for src, dec, lab in train_ds.epoch_batches(args.batch_size, rng):
+                if len(src) != args.batch_size or skip_batch(len(src), world):
+                    continue      # keep one captured graph shape (the reference's last partial batch is < 0.5 % of an epoch)
+                if pg is None:
+                    trainer.step(src, dec, lab)
+                else:             # every rank draws the same global batch (same seed) and trains on its contiguous rows, with the
+                    lo, hi = shard_bounds(len(src), rank, world)     # GLOBAL normalisers: label count, B*L*d, B*L*H of the whole batch
+                    trainer.step(src[lo:hi], dec[lo:hi], lab[lo:hi], n_valid_global=int(np.count_nonzero(lab)), b_offset=lo,
+                                 norms_scale=len(src) / float(hi - lo))
+                nseq += len(src)
         torch.cuda.synchronize()
         T += time.time() - t0
         if (epoch + 1) % args.eval_interval == 0 or epoch + 1 == args.num_epochs:
-            t_test, auc_test = trainer.evaluate(test_ds.batches(args.eval_batch_size))
-            t_valid, auc_valid = trainer.evaluate(val_ds.batches(args.eval_batch_size))
+            t_test, auc_test = trainer.evaluate(eval_batches(test_ds))
+            t_valid, auc_valid = trainer.evaluate(eval_batches(val_ds))
             for k in (5, 10) if rank == 0 else ():
                 print("epoch: %d, time: %f, valid (NDCG@%d: %.4f, HR@%d: %.4f, AUC: %s), test (NDCG@%d: %.4f, HR@%d: %.4f, AUC: %s)"
                       % (epoch + 1, T, k, t_valid[0][k], k, t_valid[1][k], auc_valid, k, t_test[0][k], k, t_test[1][k], auc_test))

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from .._lib import AdtError
 from ..dp import reduce_sum
 from ..wide import TapeTrainer, loss_norms
 
@@ -26,6 +27,7 @@ class FusedBertTrainer(TapeTrainer):
                          lr, betas, eps, weight_decay, clip, process_group, use_graph)
         self.norms = torch.zeros(3, device=model.dev, dtype=torch.float32)
         self.mcap_frac = float(mcap_frac)   # the masked-row GEMMs are launched for at most this fraction of B*L rows
+        self._device_norms = {}             # step_device: (rows, global rows) -> device normalisers
         model.seed_trainer(seed)
 
     # ------------------------------------------------------------------------------------------------------------------
@@ -55,12 +57,24 @@ class FusedBertTrainer(TapeTrainer):
     def step(self, src, dec, labels, n_valid_global=None, b_offset=0, norms_scale=1):
         self.step_staged(self.stage(src, dec, labels, n_valid_global, norms_scale), b_offset)
 
+    def step_device(self, st, b_offset=0):
+        """One step on a batch that is on the device already (DeviceBertData.train_stage): adds the normalisers -- kept per
+        (rows, global rows), so a step uploads nothing -- and runs step_staged.  Under data parallelism st holds this rank's rows of a
+        batch of st["B_global"] examples and b_offset is the first of them.  The masked-row count stays on the device, so the capacity
+        check of stage() cannot be made: only mcap_frac = 1.0 is accepted, where the capacity is B * L and cannot be exceeded."""
+        if self.mcap_frac != 1.0:
+            raise AdtError("step_device: mcap_frac = %g needs the masked-row count on the host (stage / step); use mcap_frac = 1.0" % self.mcap_frac)
+        key = (st["B"], st.get("B_global", st["B"]))
+        if key not in self._device_norms:
+            self._device_norms[key] = loss_norms(self.model, key[0] * self.model.maxlen, scale=key[1] / float(key[0]))
+        self.step_staged(dict(st, norms=self._device_norms[key]), b_offset)
+
     # ------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def evaluate(self, batches, ks=(5, 10)):
-        """BertTrainer.evaluate (trainer.py:49-86) over an iterable of (seq (B, L), candidates (B, C)) with the positive in
-        column 0: rank = number of candidates scored above it, HR@k, NDCG@k, and the AUC with the reference's
-        candidates_size = 1 + C."""
+        """BertTrainer.evaluate (trainer.py:49-86) over an iterable of (seq (B, L), candidates (B, C)) -- host arrays or device int32
+        tensors (DeviceBertData.eval_batch), which are used where they are -- with the positive in column 0: rank = number of
+        candidates scored above it, HR@k, NDCG@k, and the AUC with the reference's candidates_size = 1 + C."""
         self.model.eval()
         ks = tuple(ks)
         # additive statistics [n, sum of AUC terms, per k: hits, sum 1/log2(rank+2)]: under data parallelism rank r scores batches
@@ -71,7 +85,7 @@ class FusedBertTrainer(TapeTrainer):
                 continue
             _, rank = self.model.predict(None, seq, None, None, cand, want_rank=True)
             r = rank.cpu().numpy().astype(np.int64)
-            size = 1 + np.asarray(cand).shape[1]
+            size = 1 + (cand if isinstance(cand, torch.Tensor) else np.asarray(cand)).shape[1]
             stats[0] += len(r)
             stats[1] += float(((size - (r + 1)) / (size - 1)).sum())
             for j, k in enumerate(ks):

@@ -1,7 +1,9 @@
-// C ABI (include/adt_hip.h, "STOSA-ADT batches built on the device" and "full-sort scores on the device"): launch wrappers of
-// adt_seqbatch.cuh and adt_hithist.cuh, and the host-side draw.  Host code only enqueues work on the caller's stream.
+// C ABI (include/adt_hip.h, "STOSA-ADT batches built on the device", "full-sort scores on the device" and "BERT4Rec-ADT batches masked and
+// built on the device"): launch wrappers of adt_seqbatch.cuh, adt_hithist.cuh and adt_bertbatch.cuh, and the host-side draws.  Host code
+// only enqueues work on the caller's stream.
 #include "adt_host.h"
 
+#include "adt_bertbatch.cuh"
 #include "adt_hithist.cuh"
 #include "adt_seqbatch.cuh"
 
@@ -56,6 +58,59 @@ int adt_hit_hist(const int32_t* top_idx, int ld, int n_rows, int K, const int32_
   HitHistArgs a{top_idx, ld, K, rows_per_group, chunks, answers, (unsigned long long*)hist, hit_pos};
   hipLaunchKernelGGL(k_hit_hist, dim3((unsigned)blocks), dim3(64 * ADT_HITHIST_WAVES), 0, (hipStream_t)stream, a);
   return adt_check_launch("hit_hist");
+}
+
+int adt_bertbatch_token(uint32_t seed, uint32_t salt, int example, int pos, uint32_t thr_mask, int itemnum, int item, int* masked) {
+  bool m = false;
+  int tok = item;
+  if (itemnum >= 1 && example >= 0 && pos >= 0)
+    tok = adt_bertbatch_rule(seed, salt, (uint32_t)example, (uint32_t)pos, thr_mask, (uint32_t)itemnum, item, &m);
+  if (masked) *masked = m ? 1 : 0;
+  return tok;
+}
+
+int adt_bertbatch_build(const int64_t* seq_off, const int32_t* seq_items, const int64_t* win_start, const int32_t* win_len,
+                        const int32_t* examples, int n_examples, int row0, int n_rows, int L, int n_windows, int dupe, int n_users, int itemnum,
+                        uint32_t seed, uint32_t salt, uint32_t thr_mask, int32_t* src, int32_t* dec, int32_t* labels, int32_t* rows,
+                        int32_t* labels_c, int32_t* M, float* inv_count, int32_t* work, void* stream) {
+  if (L < 1) return adt_set_error("bertbatch_build: L=%d < 1", L);
+  if (itemnum < 1) return adt_set_error("bertbatch_build: itemnum=%d < 1", itemnum);
+  if (dupe < 1 || n_windows < 0 || n_users < 0 || (int64_t)n_windows * dupe + n_users > (int64_t)INT32_MAX)
+    return adt_set_error("bertbatch_build: %d windows x %d copies + %d users is not a count of examples below 2^31", n_windows, dupe, n_users);
+  if (n_examples < 0 || row0 < 0 || n_rows < 0 || (int64_t)row0 + n_rows > n_examples)
+    return adt_set_error("bertbatch_build: rows %d..%d+%d outside the batch of %d examples", row0, row0, n_rows, n_examples);
+  if ((size_t)n_examples * (size_t)L >= ((size_t)1 << 31))
+    return adt_set_error("bertbatch_build: %d examples x L=%d is 2^31 positions or more", n_examples, L);
+  if (!seq_off || !seq_items || !win_start || !win_len || (n_examples > 0 && !examples)) return adt_set_error("bertbatch_build: NULL input");
+  if (!M || !work) return adt_set_error("bertbatch_build: M or work is NULL");
+  if (n_rows > 0 && (!src || !dec || !rows || !labels_c)) return adt_set_error("bertbatch_build: src, dec, rows or labels_c is NULL");
+  BertBatchArgs a{seq_off, seq_items, win_start, win_len, examples, n_examples, row0, n_rows, L, n_windows, dupe, n_users, (uint32_t)itemnum,
+                  seed, salt, thr_mask, src, dec, labels, rows, labels_c, M, inv_count, (uint32_t*)work};
+  if (n_examples > 0) {
+    hipLaunchKernelGGL(k_bertbatch_count, dim3((unsigned)((n_examples + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+    if (adt_check_launch("bertbatch_build(count)")) return -1;
+  }
+  hipLaunchKernelGGL(k_bertbatch_scan, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+  if (adt_check_launch("bertbatch_build(scan)")) return -1;
+  if (n_rows > 0) {
+    hipLaunchKernelGGL(k_bertbatch_rows, dim3((unsigned)n_rows), dim3(256), 0, (hipStream_t)stream, a);
+    return adt_check_launch("bertbatch_build(rows)");
+  }
+  return 0;
+}
+
+int adt_bertbatch_eval(const int64_t* seq_off, const int32_t* seq_items, const int32_t* users, int n_rows, int n_users, int L, int itemnum,
+                       int32_t* seq, void* stream) {
+  if (L < 1) return adt_set_error("bertbatch_eval: L=%d < 1", L);
+  if (itemnum < 1) return adt_set_error("bertbatch_eval: itemnum=%d < 1", itemnum);
+  if (n_rows < 0 || n_users < 0) return adt_set_error("bertbatch_eval: n_rows=%d, n_users=%d", n_rows, n_users);
+  if (n_rows == 0) return 0;
+  if (!seq_off || !seq_items || !users || !seq) return adt_set_error("bertbatch_eval: NULL pointer");
+  const size_t work = (size_t)n_rows * (size_t)L;
+  if (work > ((size_t)1 << 31)) return adt_set_error("bertbatch_eval: %d rows x L=%d is more than 2^31 positions", n_rows, L);
+  BertEvalArgs a{seq_off, seq_items, users, n_rows, n_users, L, (uint32_t)itemnum, seq};
+  hipLaunchKernelGGL(k_bertbatch_eval, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("bertbatch_eval");
 }
 
 }  // extern "C"

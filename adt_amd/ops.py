@@ -699,6 +699,63 @@ def seqbatch_draw(seed, step, row, t, attempt, item_size):
     return int(_lib.load().adt_seqbatch_draw(int(seed) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF, int(row), int(t), int(attempt), int(item_size)))
 
 
+# ---- BERT4Rec-ADT batches masked and built on the device (include/adt_hip.h: adt_bertbatch_*; adt_amd/csrc/adt_bertbatch.cuh) -----------
+def bertbatch_threshold(mask_prob):
+    """thr_mask of adt_bertbatch_build: a position is masked iff a 32-bit hash is below min(floor(mask_prob * 2^32), 2^32 - 1)."""
+    p = float(mask_prob)
+    if not 0.0 <= p < 1.0:
+        raise _lib.AdtError("bertbatch: mask_prob = %r, need 0 <= mask_prob < 1" % (mask_prob,))
+    return min(int(p * 4294967296.0), 0xFFFFFFFF)
+
+
+def bertbatch_build(seq_off, seq_items, win_start, win_len, examples, L, dupe, itemnum, thr_mask, seed=0, salt=0, rows=None, want_labels=True):
+    """Rows rows=(lo, hi) (default: all) of the batch `examples` (device int32, the GLOBAL batch of example ids: e < W * dupe is random copy
+    e % dupe of window e // dupe, W * dupe + u the mask-last example of user u) as device tensors (src, dec, labels, rows, labels_c, M,
+    inv_count): src / dec / labels (hi - lo, L) int32 (labels None when not wanted), rows / labels_c ((hi - lo) * L,) the ascending flat
+    indices of the non-zero labels and those labels, zero beyond M (int32 (1,)), inv_count (1,) = 1 / max(labels of ALL examples, 1).  The
+    masks are a function of (seed, salt, example id, window position) alone.  Example ids are the caller's to check (an id outside the
+    table gives an all-padding row)."""
+    assert seq_off.dtype == torch.int64 and seq_off.is_contiguous() and seq_off.numel() >= 1, (seq_off.dtype, seq_off.shape)
+    assert win_start.dtype == torch.int64 and win_start.is_contiguous() and win_start.numel() == win_len.numel(), (win_start.dtype, win_start.shape)
+    _i32(seq_items), _i32(win_len)
+    n = examples.numel()
+    lo, hi = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= lo <= hi <= n:
+        raise _lib.AdtError("bertbatch_build: rows (%d, %d) outside the batch of %d examples" % (lo, hi, n))
+    dev, L = examples.device, int(L)
+    src, dec, labels = (torch.empty(hi - lo, max(L, 0), device=dev, dtype=torch.int32) if want else None for want in (True, True, want_labels))
+    rows_c, labels_c = (torch.empty((hi - lo) * max(L, 0), device=dev, dtype=torch.int32) for _ in range(2))
+    M = torch.empty(1, device=dev, dtype=torch.int32)
+    inv_count = torch.empty(1, device=dev, dtype=torch.float32)
+    work = torch.empty(n + 1, device=dev, dtype=torch.int32)
+    _lib.check(_lib.load().adt_bertbatch_build(_p(seq_off), _p(seq_items), _p(win_start), _p(win_len), _p(_i32(examples)), n, lo, hi - lo, L,
+                                               win_start.numel(), int(dupe), seq_off.numel() - 1, int(itemnum), int(seed) & 0xFFFFFFFF,
+                                               int(salt) & 0xFFFFFFFF, int(thr_mask) & 0xFFFFFFFF, _p(src), _p(dec), _p(labels), _p(rows_c),
+                                               _p(labels_c), _p(M), _p(inv_count), _p(work), _stream()), "bertbatch_build")
+    return src, dec, labels, rows_c, labels_c, M, inv_count
+
+
+def bertbatch_eval(seq_off, seq_items, users, L, itemnum):
+    """(len(users), L) int32: the last L - 1 training items of every user (device int32 indices into the CSR) followed by [MASK] =
+    itemnum + 1, left-padded (BertEvalDataset.sequence)."""
+    assert seq_off.dtype == torch.int64 and seq_off.is_contiguous() and seq_off.numel() >= 1, (seq_off.dtype, seq_off.shape)
+    _i32(seq_items)
+    n, L = users.numel(), int(L)
+    seq = torch.empty(n, max(L, 0), device=users.device, dtype=torch.int32)
+    _lib.check(_lib.load().adt_bertbatch_eval(_p(seq_off), _p(seq_items), _p(_i32(users)), n, seq_off.numel() - 1, L, int(itemnum), _p(seq),
+                                              _stream()), "bertbatch_eval")
+    return seq
+
+
+def bertbatch_token(seed, salt, example, pos, thr_mask, itemnum, item):
+    """(token, masked) at window position `pos` of random example `example` whose item is `item` (host only: the inline function
+    adt_bertbatch_build's kernel calls)."""
+    masked = ctypes.c_int(0)
+    tok = _lib.load().adt_bertbatch_token(int(seed) & 0xFFFFFFFF, int(salt) & 0xFFFFFFFF, int(example), int(pos), int(thr_mask) & 0xFFFFFFFF,
+                                          int(itemnum), int(item), ctypes.byref(masked))
+    return int(tok), bool(masked.value)
+
+
 # ---- STOSA-ADT full-sort scores on the device (include/adt_hip.h: adt_hit_hist; adt_amd/csrc/adt_hithist.cuh) ---------------------------
 def hit_hist(top_idx, answers, rows_per_group=None, hist=None, want_pos=False):
     """Histogram of where each held-out item stands in its top-K list: top_idx (N, K) device int32 at any row stride (adt_full_rank_from /

@@ -374,6 +374,41 @@ int adt_seqbatch_build(const int64_t* seq_off, const int32_t* seq_items, const i
  * index. */
 int adt_seqbatch_draw(uint32_t seed, uint32_t step, int row, int t, int attempt, int item_size);
 
+/* ---- BERT4Rec-ADT batches masked and built on the device (adt_bertbatch.cuh; bert4rec/datasets/dataset.py:49-156, 176-222) ------------
+ * Resident inputs: the training sequences as CSR over the U = n_users users with a non-empty sequence (seq_off int64 (U + 1), seq_items
+ * int32, ids in 1..itemnum) and the table of the W = n_windows sliding windows (win_start int64: offset into seq_items; win_len int32:
+ * 1..L; every window lies inside seq_items -- the caller's to guarantee).  Examples are numbered, not stored: with D = dupe, example
+ * e < W * D is random copy e % D of window e / D, and example W * D + u is the mask-last example of user u over its last min(n, L)
+ * items.  examples: the device int32 list of the whole (GLOBAL) batch, n_examples ids; an id outside 0 .. W * D + U - 1 gives an
+ * all-padding row (check ids on the host: nothing is read back).  The call writes rows row0 .. row0 + n_rows - 1 of that batch:
+ *   src, dec, labels (labels may be NULL): (n_rows, L) int32, left-padded with 0.  At window position j of random example e:
+ *     key = hash chain over (seed ^ 0x9E3779B9, salt, e, j) as in adt_seqbatch_draw; h_k = adt_hash32(key ^ k) for k = 0, 1, 2;
+ *     masked iff h_0 < thr_mask (the caller's min(floor(mask_prob * 2^32), 2^32 - 1)); a masked position becomes [MASK] = itemnum + 1
+ *     when h_1 < floor(0.8 * 2^32), the item 1 + ((uint64_t)h_2 * itemnum >> 32) when h_1 < floor(0.9 * 2^32), and stays the item
+ *     otherwise; its label is the item.  An unmasked position keeps the item, label 0.  dec equals src except that its last position is
+ *     always [MASK].  A mask-last example draws nothing: src = dec = the items with the last replaced by [MASK]; the only label is the
+ *     last item.  The decision depends on neither the row nor the step, so a shard draws what the whole batch would.
+ *   rows, labels_c: capacity n_rows * L int32; the local flat indices r * L + t with a non-zero label in ASCENDING order and their
+ *     labels, zero beyond M; M (device int32) = their number for this call's rows.
+ *   inv_count (NULL: not wanted) = (float)(1.0 / (double)max(labels over ALL n_examples rows, 1)).
+ * work: n_examples + 1 int32 of scratch (row counts, then their exclusive prefix sums).  Integer counts and prefix sums only, no
+ * atomics: the output does not depend on the order of execution.
+ * Errors: L < 1, itemnum < 1, dupe < 1, W * D + U >= 2^31, row0 + n_rows > n_examples, n_examples * L >= 2^31, a NULL input, M or work,
+ * a NULL src / dec / rows / labels_c with n_rows > 0. */
+int adt_bertbatch_build(const int64_t* seq_off, const int32_t* seq_items, const int64_t* win_start, const int32_t* win_len,
+                        const int32_t* examples, int n_examples, int row0, int n_rows, int L, int n_windows, int dupe, int n_users,
+                        int itemnum, uint32_t seed, uint32_t salt, uint32_t thr_mask, int32_t* src, int32_t* dec, int32_t* labels,
+                        int32_t* rows, int32_t* labels_c, int32_t* M, float* inv_count, int32_t* work, void* stream);
+/* Evaluation rows (BertEvalDataset.sequence): seq (n_rows, L) int32 = the last L - 1 training items of users[r] (device int32, index into
+ * the CSR; an index outside 0..n_users-1 has no history) followed by [MASK] = itemnum + 1, left-padded with 0.
+ * Errors: L < 1, itemnum < 1, a negative count, a NULL pointer with n_rows > 0, more than 2^31 positions. */
+int adt_bertbatch_eval(const int64_t* seq_off, const int32_t* seq_items, const int32_t* users, int n_rows, int n_users, int L,
+                       int itemnum, int32_t* seq, void* stream);
+/* Host only (like adt_seqbatch_draw): the token the rule above puts at window position `pos` of random example `example` whose item is
+ * `item`, and in *masked (may be NULL) whether the position carries a label; the same inline function the kernel calls.  For
+ * itemnum < 1 or a negative index: the item itself, not masked. */
+int adt_bertbatch_token(uint32_t seed, uint32_t salt, int example, int pos, uint32_t thr_mask, int itemnum, int item, int* masked);
+
 /* ---- STOSA-ADT full-sort scores on the device (adt_hithist.cuh; stosa/trainer.py:62-86 get_full_sort_score) ---------------------------
  * Where each held-out item stands in its top-K list, as an integer histogram.  top_idx: n_rows rows of K ids at row stride ld >= K, the
  * output of adt_full_rank_from or adt_topk_masked, -1 tails included.  The rows are group-major: row r belongs to group
