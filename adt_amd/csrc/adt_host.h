@@ -10,6 +10,7 @@
 #include "adt_common.cuh"
 #include "adt_lossring_args.h"
 #include "adt_wide_plan.h"      // ADT_LDS_MAX
+#include "adt_step_plan.h"      // SeqSwitches, StepPlan
 
 int adt_set_error(const char* fmt, ...);
 DropCfg adt_make_drop(float p, const uint32_t* seed, uint32_t site);
@@ -42,9 +43,13 @@ static inline int adt_launch_lds1(const void* fn, dim3 grid, dim3 block, size_t 
   return adt_launch_lds(fn, grid, block, smem, kargs, stream, what, slot, optin);
 }
 
-// ---- ADT_* switches: read through `static const int on = adt_env_on("ADT_X");`, so once per process and site ---------------------------
+// ---- ADT_* switches --------------------------------------------------------------------------------------------------------------------
+// The flagship step's (adt_sasrec.hip, adt_seq.hip) are read together, once per process, by adt_seq_switches() into the SeqSwitches of
+// adt_step_plan.h; the staged and wide kernels' through `static const int on = adt_env_on("ADT_X");`, so once per process and site.
 ADT_HIDDEN int adt_env_on(const char* name);                 // on unless the value parses to 0
 ADT_HIDDEN int adt_env_int(const char* name, int dflt);      // atoi of the value; dflt when unset
+ADT_HIDDEN const SeqSwitches& adt_seq_switches();            // defined in adt_seq.hip
+ADT_HIDDEN size_t adt_seq_attn_bwd_lds(int L, int H);        // dynamic LDS of k_seq_attn_bwd (adt_seqattn.cuh: sab_lds_bytes), for StepFacts ; adt_seq.hip
 
 // dropout sites (identical to oracle/sasrec_oracle.py)
 enum { SITE_EMB_SEQ = 1, SITE_EMB_DEC = 2 };
@@ -61,8 +66,6 @@ int adt_launch_fwdchain(int prec, int which, const adt::FwdChainArgs& a, void* s
 
 // per-sequence fused layer kernels (adt_seqfwd.cuh); defined in adt_seq.hip
 namespace adt { struct SeqFwdArgs; }
-int adt_seq_supported(int prec, int L, int d, int hd);      // bf16 mode, d = 64, L <= 224; ADT_SEQ=0 in the environment turns them off
-int adt_seq_lean(int prec, int L, int d, int hd);           // the forward may save bf16 tensors and skip LN(x) / qkv (see adt_seq.hip)
 int adt_launch_seq_enc_fwd(int hd, const adt::SeqFwdArgs& a, void* stream);
 int adt_launch_seq_dec_fwd(int hd, const adt::SeqFwdArgs& a, void* stream);
 // adt_pack_wimg (pre-packed bf16 weight images) is part of the C ABI now: include/adt_hip.h; defined in adt_seq.hip
@@ -87,7 +90,6 @@ int adt_launch_seq_xattn_mid_bwd(int hd, const adt::AttnArgs& a, const adt::BwdC
 int adt_launch_seq_post_bwd(int hd, int enc, const adt::BwdChainArgs& a, void* stream);
 int adt_launch_seq_mid_bwd(int hd, const adt::BwdChainArgs& a, void* stream);      // dec_mid + kv chains in one launch
 // private per-workgroup partials of the 64 x 64 weight gradients instead of atomics (adt_seqbwd_tt.cuh: sb_dw_tiles) and their sum
-int adt_seq_partials(int prec, int L, int d, int hd);
 int adt_dwpart_reduce(float* G, const float* part, size_t stride, int nwg, const int* slots, const int* offs, int nslots, void* stream);
 // the same with a workgroup count per slot (nwg_slot[i] workgroups wrote slot i ; null: nwg everywhere)
 int adt_dwpart_reduce_n(float* G, const float* part, size_t stride, int nwg, const int* nwg_slot, const int* slots, const int* offs, int nslots, void* stream);

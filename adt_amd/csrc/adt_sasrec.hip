@@ -6,7 +6,6 @@
 #include "adt_host.h"
 #include <string.h>
 #include <mutex>
-#include "adt_bwd_plan.h"
 #include "adt_bwdchain_args.h"
 #include "adt_fwdchain_args.h"
 #include "adt_seq_args.h"
@@ -35,16 +34,12 @@ enum { D_LNW, D_LNB, D_SINW, D_SINB, D_SOW, D_SOB, D_EINW, D_EINB, D_EOW, D_EOB,
 
 int64_t up64(int64_t x) { return (x + 63) / 64 * 64; }
 
-// workgroups per sequence of the per-sequence kernels: the largest power of two that keeps B * S within the CUs (ADT_SEQ_SPLIT overrides;
-// 1 at B >= 129).  Small batches -- a data-parallel rank's share of a global batch -- otherwise leave most CUs without a workgroup.
-int seq_split(int B) {
-  static const int forced = adt_env_int("ADT_SEQ_SPLIT", 0);
-  if (forced > 0) return forced;
-  int s = 1;
-  while (s < 8 && B * s * 2 <= 256) s *= 2;
-  return s;
+// what a step with this configuration and B sequences launches (adt_step_plan.h)
+StepPlan step_plan(const adt_sasrec_cfg* c, int B) {
+  const StepFacts f{c->prec, c->maxlen, c->hidden, c->num_heads, c->num_layers, B, c->item_num + 1, adt_item_sort_supported(c->item_num + 1) != 0,
+                    c->num_heads > 0 ? adt_seq_attn_bwd_lds(c->maxlen, c->num_heads) : 0};
+  return adt_step_plan(f, adt_seq_switches());
 }
-
 
 bool make_layout(const adt_sasrec_cfg* c, Layout* lo) {
   if (c->num_layers < 1 || c->num_layers > 16) return false;
@@ -87,7 +82,7 @@ struct WS {
   int64_t total;
 };
 
-void make_ws(const adt_sasrec_cfg* c, int B, WS* w) {
+void make_ws(const adt_sasrec_cfg* c, int B, const StepPlan& pl, WS* w) {
   w->B = B; w->d = c->hidden; w->H = c->num_heads; w->L = c->maxlen; w->nl = c->num_layers;
   w->T = (int64_t)B * w->L;
   const int64_t Td = up64(w->T * w->d), T1 = up64(w->T), lse = up64((int64_t)B * w->H * w->L);
@@ -124,11 +119,11 @@ void make_ws(const adt_sasrec_cfg* c, int B, WS* w) {
     w->prep = take(NREPP * w->prep_stride);
     w->wpack = take(3 * w->prep_stride);
   }
-  w->part_stride = (c->prec == ADT_PREC_BF16 && c->hidden == 64) ? (int64_t)w->nl * 16 * 4096 : 0;
-  w->part = take((int64_t)B * seq_split(B) * w->part_stride);      // one partial area per WORKGROUP (several per sequence at small batches)
-  w->isort_n = (c->hidden == 64 && adt_item_sort_supported(c->item_num + 1)) ? adt_item_sort_work_ints(4, (int)w->T, c->item_num + 1) : 0;
+  w->part_stride = pl.parts_area ? (int64_t)w->nl * 16 * 4096 : 0;
+  w->part = take((int64_t)B * pl.seq_split * w->part_stride);      // one partial area per WORKGROUP (several per sequence at small batches)
+  w->isort_n = pl.sort_area ? adt_item_sort_work_ints(4, (int)w->T, c->item_num + 1) : 0;
   w->isort = take(up64(w->isort_n));
-  w->vcall = (int64_t)B * seq_split(B) * 512;
+  w->vcall = (int64_t)B * pl.seq_split * 512;
   w->vpart = take(w->part_stride > 0 ? (5 * w->nl + 1) * w->vcall : 0);      // (+ 1: the last LayerNorm's sums from the first encoder kernel of the backward)
   w->lnpart = take(LN_PART_BLOCKS * 128);
   w->gnpart = take(4096);
@@ -147,16 +142,12 @@ struct SideStream {
   hipStream_t s = nullptr;
   hipEvent_t fork_ev[4] = {nullptr, nullptr, nullptr, nullptr}, join_ev[4] = {nullptr, nullptr, nullptr, nullptr};      // [3]: the id sort
 };
-// ADT_SIDE_STREAM: bit 0 the logits' item rows, bit 1 the decoder's embedding gradient + partial sums, bit 2 the encoder's partial sums
-// (default 7, 0 = everything on the caller's stream)
-int side_sites() {
-  static const int on = adt_env_int("ADT_SIDE_STREAM", 7) & 7;
-  return on;
-}
-SideStream* side_stream(hipStream_t main) {
+// StepPlan::side_sites (ADT_SIDE_STREAM): bit 0 the logits' item rows, bit 1 the decoder's embedding gradient + partial sums, bit 2 the
+// encoder's partial sums (default 7, 0 = everything on the caller's stream)
+SideStream* side_stream(const StepPlan& pl, hipStream_t main) {
   static SideStream g[16];
   static std::mutex mu;                          // first use from two host threads at once (one trainer per thread)
-  if (!side_sites()) return nullptr;
+  if (!pl.side_sites) return nullptr;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
   SideStream* sd = &g[dev];
@@ -199,36 +190,14 @@ int side_join(SideStream* sd, int k, void* main) {
   return 0;
 }
 
-// The item-table and positional-table gradients as sorted segmented sums (adt_itemgrad.cuh) instead of float-atomic scatters into replicas:
-// deterministic, and no atomics-bound kernels beside the chain kernels.  ADT_ITEM_SORT=1 switches it on (default: the scatters).
-bool item_det(const WS& w) {
-  static const int on = adt_env_int("ADT_ITEM_SORT", 0) != 0;      // opt-in: +12 us per flagship step (0.637 against 0.625 ms: DESIGN.md "item-table gradient")
-  return on && w.isort_n > 0;
-}
-
-// ADT_LNL_FUSED=0: the model's last LayerNorm is reversed by its own kernel (k_ln_bwd) instead of inside k_seqtt_post_bwd<ENC>
-bool lnl_fuse_on() {
-  static const int on = adt_env_on("ADT_LNL_FUSED");
-  return on != 0;
-}
-
-int check_cfg(const adt_sasrec_cfg* c) {
-  if (c->hidden != 64) return adt_set_error("sasrec: hidden=%d unsupported in this build (64)", c->hidden);
-  if (c->num_heads < 1 || c->hidden % c->num_heads) return adt_set_error("sasrec: bad num_heads");
-  const int hd = c->hidden / c->num_heads;
-  if (hd != 16 && hd != 32 && hd != 64) return adt_set_error("sasrec: head_dim=%d unsupported (16/32/64)", hd);
-  if (c->maxlen > 224) return adt_set_error("sasrec: maxlen=%d > 224 unsupported", c->maxlen);
-  if (c->num_layers < 1 || c->num_layers > 16) return adt_set_error("sasrec: num_layers");
-  return 0;
-}
-// what every entry point starts with: the configuration checked, the parameter layout and the workspace carve-up for B sequences
-int layout_ws(const adt_sasrec_cfg* c, int B, Layout* lo, WS* w) {
-  CK(check_cfg(c));
+// what every entry point starts with: the configuration checked, the step's plan, the parameter layout and the workspace carve-up for B sequences
+int layout_ws(const adt_sasrec_cfg* c, int B, Layout* lo, WS* w, StepPlan* pl) {
+  *pl = step_plan(c, B);
+  if (pl->cfg_error[0]) return adt_set_error("%s", pl->cfg_error);
   make_layout(c, lo);
-  make_ws(c, B, w);
+  make_ws(c, B, *pl, w);
   return 0;
 }
-
 
 adt::FwdChainArgs fwd_args(int T, int L, int B, int H, const int32_t* ids, float p, const uint32_t* seed, uint32_t row_offset) {
   adt::FwdChainArgs a;
@@ -273,24 +242,19 @@ enum { PS_E_IN = 0, PS_E_O = 3, PS_E_C1 = 4, PS_E_C2 = 5, PS_D_SIN = 6, PS_D_EIN
 
 // the partial slots of the encoder (enc = true) and / or decoder (dec = true) blocks of every layer and their offsets in G
 int partial_slots(const adt_sasrec_cfg* c, const Layout& lo, bool enc, bool dec, int* slots, int* offs);
-// workgroups that write partial slot `slot` of a step with B sequences: the token-chain kernels run S workgroups per sequence
-// k_seqtt_attn_pre_bwd: one workgroup per sequence, two at small batches (ADT_ATTN_SPLIT=0: always one)
-int attn_split(int B) {
-  static const int on = adt_env_on("ADT_ATTN_SPLIT");
-  return on && seq_split(B) >= 2 ? 2 : 1;
-}
-// workgroups that wrote partial `slot`
-int partial_nwg(int slot, int B) {
+// workgroups that wrote partial `slot` of a step with B sequences: the token-chain kernels run StepPlan::seq_split workgroups per sequence,
+// k_seqtt_attn_pre_bwd one, two at small batches (StepPlan::attn_split)
+int partial_nwg(const StepPlan& pl, int slot, int B) {
   const int k = slot % 16;
   const bool attn_block = (k >= PS_E_IN && k < PS_E_IN + 3) || (k >= PS_D_SIN && k < PS_D_SIN + 3);
-  return attn_block ? B * attn_split(B) : B * seq_split(B);
+  return attn_block ? B * pl.attn_split : B * pl.seq_split;
 }
 // sums the partials of the encoder (enc = true) and / or decoder (dec = true) blocks of every layer into G
-int reduce_partials(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, float* G, float* ws, bool enc, bool dec, void* st) {
+int reduce_partials(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, const StepPlan& pl, float* G, float* ws, bool enc, bool dec, void* st) {
   int slots[256], offs[256];
   const int n = partial_slots(c, lo, enc, dec, slots, offs);
   int nwg[256];
-  for (int i = 0; i < n; ++i) nwg[i] = partial_nwg(slots[i], (int)w.B);
+  for (int i = 0; i < n; ++i) nwg[i] = partial_nwg(pl, slots[i], (int)w.B);
   return adt_dwpart_reduce_n(G, ws + w.part, (size_t)w.part_stride, (int)w.B, nwg, slots, offs, n, st);
 }
 int partial_slots(const adt_sasrec_cfg* c, const Layout& lo, bool enc, bool dec, int* slots, int* offs) {
@@ -314,11 +278,6 @@ int partial_slots(const adt_sasrec_cfg* c, const Layout& lo, bool enc, bool dec,
   }
   return n;
 }
-// single-GPU step: the partials are summed by the optimizer's first kernel (adt_fold_parts_clip_adam), not by k_dwpart_reduce launches
-bool fold_sums_partials(const adt_sasrec_cfg* c, const WS& w) {
-  static const int on = adt_env_on("ADT_FOLD_PARTS");
-  return on && w.part_stride > 0 && c->num_layers <= 2 && adt_seq_partials(c->prec, c->maxlen, c->hidden, c->hidden / c->num_heads) != 0;
-}
 
 adt::SeqBwdArgs seq_bwd_args(int L, int B, int H, const int32_t* ids, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, int hd) {
   adt::SeqBwdArgs a;
@@ -328,24 +287,24 @@ adt::SeqBwdArgs seq_bwd_args(int L, int B, int H, const int32_t* ids, float p, c
   return a;
 }
 
-adt::SeqFwdArgs seq_args(int L, int B, int H, const int32_t* ids, float p, const uint32_t* seed, uint32_t b_offset, int hd) {
+adt::SeqFwdArgs seq_args(int nsplit, int L, int B, int H, const int32_t* ids, float p, const uint32_t* seed, uint32_t b_offset, int hd) {
   adt::SeqFwdArgs a;
   memset(&a, 0, sizeof(a));
-  a.nsplit = seq_split(B);
+  a.nsplit = nsplit;
   a.L = L; a.B = B; a.H = H; a.ids = ids; a.drop = adt_make_drop(p, seed, 0); a.b_offset = b_offset; a.ln_eps = LN_EPS;
   a.scale = 1.0f / sqrtf((float)hd);
   return a;
 }
 
 // argument block of one encoder layer's fused forward (adt_seqfwd_tt.cuh / adt_seqfwd.cuh)
-adt::SeqFwdArgs enc_layer_seq_args(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, const float* P, float* ws, const int32_t* seq, float p,
-                                   const uint32_t* seed, uint32_t b_offset, int i, bool training_outputs, bool lean) {
+adt::SeqFwdArgs enc_layer_seq_args(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, const StepPlan& pl, const float* P, float* ws, const int32_t* seq,
+                                   float p, const uint32_t* seed, uint32_t b_offset, int i, bool training_outputs, bool lean) {
   const int d = (int)w.d, H = (int)w.H, hd = d / H, L = (int)w.L, B = (int)w.B, prec = c->prec;
   const int64_t Td = up64(w.T * w.d);
   float* x = ws + w.enc_x + i * Td;
   float* y = ws + w.enc_x + (i + 1) * Td;
   float* base = ws + i * w.e_stride;
-  adt::SeqFwdArgs a = seq_args(L, B, H, seq, p, seed, b_offset, hd);
+  adt::SeqFwdArgs a = seq_args(pl.seq_split, L, B, H, seq, p, seed, b_offset, hd);
   a.x = i == 0 ? nullptr : x; a.E = P + lo.item(); a.P = P + lo.posw(); a.emb_scale = sqrtf((float)d); a.site_emb = SITE_EMB_SEQ;
   a.site_attn = enc_site(i, 0); a.site1 = enc_site(i, 1); a.site2 = enc_site(i, 2);
   a.gamma = P + lo.enc(i, E_LN1W); a.beta = P + lo.enc(i, E_LN1B); a.Win = P + lo.enc(i, E_INW); a.bin = P + lo.enc(i, E_INB);
@@ -361,15 +320,15 @@ adt::SeqFwdArgs enc_layer_seq_args(const adt_sasrec_cfg* c, const Layout& lo, co
 
 // encoder stack forward (gathers the input embedding inside the first chain) + last LayerNorm (+ logits and the
 // cross-attention k/v projections of every decoder layer when training_outputs)
-int encoder_forward(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, const float* P, float* ws,
+int encoder_forward(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, const StepPlan& pl, const float* P, float* ws,
                     const int32_t* seq, const int32_t* pos, const int32_t* neg, float p, const uint32_t* seed,
                     uint32_t b_offset, bool training_outputs, void* st, bool packed = false) {
   const int T = (int)w.T, d = (int)w.d, H = (int)w.H, hd = d / H, L = (int)w.L, B = (int)w.B, prec = c->prec, nl = c->num_layers;
   const int64_t Td = up64(w.T * w.d);
   const uint32_t ro = b_offset * (uint32_t)L;
   const int dd = d * d;
-  const bool use_seq = adt_seq_supported(prec, L, d, hd) != 0;
-  const bool lean = training_outputs && adt_seq_lean(prec, L, d, hd) != 0;   // bf16 saved tensors, no LN(x) / qkv (the fused backward recomputes them)
+  const bool use_seq = pl.use_seq;
+  const bool lean = training_outputs && pl.lean;   // bf16 saved tensors, no LN(x) / qkv (the fused backward recomputes them)
   if (!packed) CK(pack_weights(c, lo, w, P, ws, st));      // packed: adt_sasrec_step_begin* of this step wrote the images
   const float* wp_base = P + lo.posw();
   const void* wp_img = prec == ADT_PREC_BF16 ? (const void*)(ws + w.wpack) : nullptr;
@@ -382,7 +341,7 @@ int encoder_forward(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, cons
     const float* inw = P + lo.enc(i, E_INW);
     const float* inb = P + lo.enc(i, E_INB);
     if (use_seq) {   // the whole layer in one launch, one workgroup per sequence (adt_seqfwd.cuh)
-      const adt::SeqFwdArgs a = enc_layer_seq_args(c, lo, w, P, ws, seq, p, seed, b_offset, i, training_outputs, lean);
+      const adt::SeqFwdArgs a = enc_layer_seq_args(c, lo, w, pl, P, ws, seq, p, seed, b_offset, i, training_outputs, lean);
       CK(adt_launch_seq_enc_fwd(hd, a, st));
       continue;
     }
@@ -434,16 +393,16 @@ int encoder_forward(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, cons
 }
 
 // one decoder layer, fused forward: one launch, one workgroup per sequence (adt_seqfwd_tt.cuh / adt_seqfwd.cuh)
-adt::SeqFwdArgs dec_layer_seq_args(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, const float* P, float* ws, const int32_t* dec, float p,
+adt::SeqFwdArgs dec_layer_seq_args(const Layout& lo, const WS& w, const StepPlan& pl, const float* P, float* ws, const int32_t* dec, float p,
                                    const uint32_t* seed, uint32_t b_offset, int i) {
-  const int d = (int)w.d, H = (int)w.H, hd = d / H, L = (int)w.L, B_ = (int)w.B, prec = c->prec;
+  const int d = (int)w.d, H = (int)w.H, hd = d / H, L = (int)w.L, B_ = (int)w.B;
   const int64_t Td = up64(w.T * w.d);
   float* x = ws + w.dec_x + i * Td;
   float* y = ws + w.dec_x + (i + 1) * Td;
   float* base = ws + i * w.d_stride;   // d_* offsets are absolute for layer 0
   float *dn = base + w.d_dn, *qkv = base + w.d_qkv, *o1 = base + w.d_o1, *lse1 = base + w.d_lse1, *a1 = base + w.d_a1,
         *q2 = base + w.d_q2, *kv2 = base + w.d_kv2, *o2 = base + w.d_o2, *lse2 = base + w.d_lse2, *a2 = base + w.d_a2, *u = base + w.d_u;
-  adt::SeqFwdArgs a = seq_args(L, B_, H, dec, p, seed, b_offset, hd);
+  adt::SeqFwdArgs a = seq_args(pl.seq_split, L, B_, H, dec, p, seed, b_offset, hd);
   a.x = i == 0 ? nullptr : x; a.E = P + lo.item(); a.P = P + lo.posw(); a.emb_scale = sqrtf((float)d); a.site_emb = SITE_EMB_DEC;
   a.site_attn = dec_site(i, 0); a.site_attn2 = dec_site(i, 1); a.site1 = dec_site(i, 2); a.site2 = dec_site(i, 3);
   a.gamma = P + lo.dec(i, D_LNW); a.beta = P + lo.dec(i, D_LNB); a.Win = P + lo.dec(i, D_SINW); a.bin = P + lo.dec(i, D_SINB);
@@ -454,40 +413,24 @@ adt::SeqFwdArgs dec_layer_seq_args(const adt_sasrec_cfg* c, const Layout& lo, co
   a.a1 = a1; a.q2 = q2; a.kv2 = kv2; a.o2 = o2; a.lse2 = lse2; a.mask2 = reinterpret_cast<uint32_t*>(base + w.d_mask2);
   a.h = a2; a.u = u; a.y = y;
   a.wp_base = P + lo.posw(); a.wp_img = ws + w.wpack;
-  if (adt_seq_lean(prec, L, d, hd)) { a.xn = nullptr; a.qkv = nullptr; a.saved_bf16 = 1; }
+  if (pl.lean) { a.xn = nullptr; a.qkv = nullptr; a.saved_bf16 = 1; }
   return a;
 }
-int dec_layer_seq_fwd(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, const float* P, float* ws, const int32_t* dec, float p,
+int dec_layer_seq_fwd(const Layout& lo, const WS& w, const StepPlan& pl, const float* P, float* ws, const int32_t* dec, float p,
                       const uint32_t* seed, uint32_t b_offset, int i, void* st) {
-  const adt::SeqFwdArgs a = dec_layer_seq_args(c, lo, w, P, ws, dec, p, seed, b_offset, i);
+  const adt::SeqFwdArgs a = dec_layer_seq_args(lo, w, pl, P, ws, dec, p, seed, b_offset, i);
   return adt_launch_seq_dec_fwd((int)(w.d / w.H), a, st);
 }
 
-// Training forward + loss assembly of the lean per-sequence path: log_feats is the tail of the last encoder layer's kernel (no k_final_fwd launch)
-// and the pos / neg logits + BCE seed are formed by the backward's first side kernel, which gathers E[pos], E[neg] and log_feats anyway
-// (adt_logits_bce_scatter; adt_sasrec_backward with phase bit 4).  Returns 1 when the shape is not covered (nothing launched).
-bool bce_deferred(const adt_sasrec_cfg* c) {
-  static const int on = adt_env_on("ADT_FWD_FUSED");
-  const int d = c->hidden, hd = d / c->num_heads;
-  return on && d == 64 && c->num_layers <= 4 && adt_seq_lean(c->prec, c->maxlen, d, hd) != 0;
-}
-// ADT_EMBED3=0: the two embedding gradients and the positive-logit rows keep their own scatters (default: one pass, adt_embed_bwd3 -- deferred
-// path only, without the sorted form)
-bool embed3_on(const WS& w) {
-  static const int on = adt_env_on("ADT_EMBED3");
-  return on != 0 && !item_det(w) && w.d == 64;
-}
-// ADT_BCE_MERGED=0: the forward's logits / BCE kernel (ADT_TRAIN_BCE_SIDE) goes to the side stream instead of into the loss launch
-bool bce_merged() {
-  static const int on = adt_env_on("ADT_BCE_MERGED");
-  return on != 0;
-}
+// Training forward + loss assembly of the lean per-sequence path (StepPlan::bce_deferred): log_feats is the tail of the last encoder layer's
+// kernel (no k_final_fwd launch) and the pos / neg logits + BCE seed are formed by the backward's first side kernel, which gathers E[pos], E[neg]
+// and log_feats anyway (adt_logits_bce_scatter; adt_sasrec_backward with phase bit 4): forward_loss_lean below.
 // the stream the forward's logits kernel runs on when it is not merged into the loss launch (nullptr: the caller's), and whose join_ev[0] the backward waits for
-SideStream* fwd_logits_stream(void* st) { return ((side_sites() & 1) && !bce_merged()) ? side_stream((hipStream_t)st) : nullptr; }
+SideStream* fwd_logits_stream(const StepPlan& pl, void* st) { return ((pl.side_sites & 1) && !pl.bce_merged) ? side_stream(pl, (hipStream_t)st) : nullptr; }
 // same step, same ring arguments: the forward's loss launch copies the first half of the next batch's ring slot exactly when the backward's
 // embedding scatter copies the second (and then marks the batch staged) -- 819 KB over PCIe do not fit behind either launch alone
-bool ring_prefetch_split(const adt::RingPrefetchArgs& rr, bool bce_by_forward, const WS& w) {
-  return rr.ring && rr.staging && rr.state && bce_by_forward && embed3_on(w);
+bool ring_prefetch_split(const adt::RingPrefetchArgs& rr, bool bce_by_forward, const StepPlan& pl) {
+  return rr.ring && rr.staging && rr.state && bce_by_forward && pl.embed3_on;
 }
 
 // Pointer arrays of the loss launch (AdtLossSeedsJob) and its reconstruction / independence terms: pair i = (enc_in[i], dec_out_rev[i] = DEC_X[nl - i])
@@ -514,32 +457,33 @@ AdtLossSeedsJob loss_terms(const WS& w, float* ws, const float* lambdas1, const 
   return j;
 }
 
+// Returns 1 when the shape is not covered (nothing launched).
 // bce_side (ADT_TRAIN_BCE_SIDE of adt_sasrec_forward_loss*): the logits + BCE + item-row scatter kernel of the deferred path is launched HERE, as the
 // first workgroups of the loss launch or (ADT_BCE_MERGED=0) on the library's side stream beside it (both are memory passes; under the backward's
 // first chain kernels it stretched the latency-bound cross-attention backward by about its own duration), and joined by
 // adt_sasrec_backward(ADT_PHASE_BCE_FWD) in front of the first kernel that reads d log_feats.  The item-table replicas are zero:
 // adt_sasrec_step_begin* of this step.
-int forward_loss_lean(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, const float* P, float* ws, const int32_t* seq, const int32_t* dec,
+int forward_loss_lean(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, const StepPlan& pl, const float* P, float* ws, const int32_t* seq, const int32_t* dec,
                       const int32_t* pos, const int32_t* neg, bool bce_side, float p, const uint32_t* seed, uint32_t b_offset, const float* lambdas1,
                       const float* lambdas2, const adt::RingPrefetchArgs& rr, void* st) {
   const int hd = (int)(w.d / w.H), nl = c->num_layers;
-  if (!bce_deferred(c)) return 1;
+  if (!pl.bce_deferred) return 1;
   for (int i = 0; i < nl; ++i) {
-    adt::SeqFwdArgs a = enc_layer_seq_args(c, lo, w, P, ws, seq, p, seed, b_offset, i, true, true);
+    adt::SeqFwdArgs a = enc_layer_seq_args(c, lo, w, pl, P, ws, seq, p, seed, b_offset, i, true, true);
     if (i == nl - 1) { a.lnl_gamma = P + lo.lnl_w(); a.lnl_beta = P + lo.lnl_b(); a.f_out = ws + w.f; }
     CK(adt_launch_seq_enc_fwd(hd, a, st));
   }
-  for (int j = 0; j < nl; ++j) CK(dec_layer_seq_fwd(c, lo, w, P, ws, dec, p, seed, b_offset, j, st));
+  for (int j = 0; j < nl; ++j) CK(dec_layer_seq_fwd(lo, w, pl, P, ws, dec, p, seed, b_offset, j, st));
   // reconstruction + independence seeds in one launch (no BCE block: no logits yet)
   LossPtrs q;
   AdtLossSeedsJob job = loss_terms(w, ws, lambdas1, lambdas2, false, &q);
   // (+ the next step's id batch, if its producer has published it: the PCIe read runs under this streaming pass)
-  job.ring = &rr; job.split = ring_prefetch_split(rr, bce_side, w);
+  job.ring = &rr; job.split = ring_prefetch_split(rr, bce_side, pl);
   const adt::LogitsBceArgs lb{ws + w.f, P + lo.item(), pos, neg, ws + w.norms, (int)w.T, ws + w.posl, ws + w.negl, ws + w.g_pos, ws + w.g_neg, ws + w.loss,
-                              ws + w.g_f, item_det(w) ? nullptr : ws + w.rep, NREP, (size_t)w.rep_stride, embed3_on(w) ? 1 : 0};
-  const bool merged = bce_side && bce_merged();
+                              ws + w.g_f, pl.det ? nullptr : ws + w.rep, NREP, (size_t)w.rep_stride, pl.embed3_on ? 1 : 0};
+  const bool merged = bce_side && pl.bce_merged;
   if (merged) job.logits = &lb;      // ... as the first workgroups of the loss launch itself: no second stream, no fork / join
-  SideStream* const sd = (bce_side && !merged) ? fwd_logits_stream(st) : nullptr;
+  SideStream* const sd = (bce_side && !merged) ? fwd_logits_stream(pl, st) : nullptr;
   if (bce_side && !merged) CK(side_mark(sd, 0, st));
   CK(adt_loss_seeds_prefetch(job, st));
   if (bce_side && !merged) {
@@ -569,6 +513,8 @@ inline void time_mark(int which, int layer, bool start, void* st) {
   }
 }
 
+// Defensive: StepPlan::parts implies adt_covers_post_bwd / adt_covers_mid_bwd for the argument blocks built here (ADT_SEQ_POST_BWD, bf16 weight
+// images, L <= ADT_SEQ_MAXLEN, T = B L, a head size of 16 / 32 / 64, H hd = 64): tests/test_step_plan_cpu.py asserts it over the whole table.
 const char* const NO_FALLBACK = "backward: shape L=%d hd=%d left the per-sequence kernels although the partial-gradient path was chosen";
 
 // What one adt_sasrec_backward* call works on: built once (bwd_init), read by the functions of the blocks below.
@@ -578,17 +524,12 @@ struct Bwd {
   const int32_t *seq, *dec, *pos, *neg;
   float p; const uint32_t* seed; uint32_t b_offset, ro;      // ro: b_offset in token rows
   void* st;                      // the caller's stream
-  BwdPlan plan;
+  BwdPlan plan;                  // the phase word of this call
+  StepPlan sp;                   // what the step launches: the forward of this step read the same plan
+  BwdCallPlan call;              // ... and this call of it
   adt::RingPrefetchArgs ring;      // the step's id ring as adt_sasrec_forward_loss_prefetch got it (ring == nullptr: none)
   int T, d, H, hd, L, prec, nl;
   int64_t Td, recsz;
-  bool use_seq;                  // the per-sequence kernels cover the shape
-  int lean;                      // what the forward of this step saved (same predicate, same process)
-  bool parts;                    // weight gradients through private per-sequence partials + one ordered sum instead of float atomics (adt_seqbwd_tt.cuh: sb_dw_tiles)
-  bool late_parts;               // adt_sasrec_fold_clip_adam sums those partials, and the bias / LayerNorm / classifier sums the chain kernels then STORE per workgroup
-  bool det;                      // item / positional table gradients by sorted segmented sums (no replicas, no float atomics)
-  bool embed3;                   // encoder / decoder embedding gradients and the positive-logit rows share ONE scatter at the end (adt_embed_bwd3)
-  bool lnl_fused;                // the last LayerNorm is reversed inside the last encoder block's first kernel (k_seqtt_post_bwd<ENC>: BwdChainArgs::lnl_x)
   // the backward chains flush their weight / bias / LayerNorm gradients into NREPP zeroed replicas of the non-item parameters
   // (Gq + lo.xxx() addresses replica 0); each phase folds its range into G at its end
   float* Gq;
@@ -600,17 +541,17 @@ struct Bwd {
     adt::BwdChainArgs a = bwd_args(T, L, (int)w.B, ids, pp, sdp, ro);
     a.nrep = NREPP; a.rep_stride = (size_t)w.prep_stride;
     a.wp_base = P + lo.posw(); a.wp_img = prec == ADT_PREC_BF16 ? (const void*)(ws + w.wpack) : nullptr;   // packed by the forward of this step
-    a.nsplit = seq_split((int)w.B);
+    a.nsplit = sp.seq_split;
     return a;
   }
-  float* PART(int layer, int slot) const { return parts ? ws + w.part + (int64_t)(16 * layer + slot) * 4096 : nullptr; }
-  float* VPART(int layer, int k) const { return late_parts ? ws + w.vpart + (int64_t)(5 * layer + k) * w.vcall : nullptr; }
+  float* PART(int layer, int slot) const { return sp.parts ? ws + w.part + (int64_t)(16 * layer + slot) * 4096 : nullptr; }
+  float* VPART(int layer, int k) const { return call.late_parts ? ws + w.vpart + (int64_t)(5 * layer + k) * w.vcall : nullptr; }
   // d log_feats + item rows of pos / neg (+ logits and BCE seed on the deferred path)   (sasrec/model.py:72-76)
   int logits_scatter(void* s) const {
     if (plan.bce_here)
       return adt_logits_bce_scatter_ex(f, P + lo.item(), pos, neg, ws + w.norms, T, ws + w.posl, ws + w.negl, ws + w.g_pos, ws + w.g_neg, ws + w.loss,
-                                       gf, det ? nullptr : ws + w.rep, NREP, w.rep_stride, embed3 ? 1 : 0, s);
-    if (det) return adt_logits_bwd_df(P + lo.item(), pos, neg, ws + w.g_pos, ws + w.g_neg, T, d, gf, d, s);
+                                       gf, sp.det ? nullptr : ws + w.rep, NREP, w.rep_stride, call.embed3 ? 1 : 0, s);
+    if (sp.det) return adt_logits_bwd_df(P + lo.item(), pos, neg, ws + w.g_pos, ws + w.g_neg, T, d, gf, d, s);
     return adt_logits_bwd_scatter(f, d, P + lo.item(), pos, neg, ws + w.g_pos, ws + w.g_neg, T, d, gf, d, ws + w.rep, NREP, w.rep_stride, s);
   }
   // a replica area that adt_sasrec_step_begin* did not zero for this step
@@ -621,8 +562,9 @@ struct Bwd {
 
 int bwd_init(Bwd& x, const adt_sasrec_cfg* c, const float* P, float* G, float* ws, const int32_t* seq, const int32_t* dec, const int32_t* pos,
              const int32_t* neg, int B, int training, const uint32_t* seed, uint32_t b_offset, int phase, const adt::RingPrefetchArgs& ring, void* st) {
-  CK(layout_ws(c, B, &x.lo, &x.w));
-  if (const char* err = adt_bwd_plan(phase, bce_deferred(c), &x.plan)) return adt_set_error("%s", err);
+  CK(layout_ws(c, B, &x.lo, &x.w, &x.sp));
+  if (const char* err = adt_bwd_plan(phase, x.sp.bce_deferred, &x.plan)) return adt_set_error("%s", err);
+  x.call = adt_bwd_call_plan(x.sp, x.plan);
   const WS& w = x.w;
   x.c = c; x.P = P; x.G = G; x.ws = ws; x.seq = seq; x.dec = dec; x.pos = pos; x.neg = neg; x.seed = seed; x.b_offset = b_offset; x.st = st; x.ring = ring;
   x.T = (int)w.T; x.d = (int)w.d; x.H = (int)w.H; x.hd = x.d / x.H; x.L = (int)w.L; x.prec = c->prec; x.nl = c->num_layers;
@@ -631,18 +573,8 @@ int bwd_init(Bwd& x, const adt_sasrec_cfg* c, const float* P, float* G, float* w
   x.ro = b_offset * (uint32_t)x.L;
   x.s1 = ws + w.s1; x.s3 = ws + w.s3; x.s4 = ws + w.s4; x.s5 = ws + w.s5; x.gf = ws + w.g_f; x.f = ws + w.f;
   x.Gq = ws + w.prep - x.lo.posw();
-  x.use_seq = adt_seq_supported(x.prec, x.L, x.d, x.hd) != 0;
-  x.lean = adt_seq_lean(x.prec, x.L, x.d, x.hd);
-  x.parts = w.part_stride > 0 && adt_seq_partials(x.prec, x.L, x.d, x.hd) != 0;
-  x.late_parts = x.plan.defer_fold && fold_sums_partials(c, w);
-  x.det = item_det(w);
-  x.embed3 = x.plan.seeds_virtual && embed3_on(w);
-  x.lnl_fused = x.parts && x.use_seq && lnl_fuse_on();      // (without the stored sums: float atomics into the replicas, like its other vectors)
-  x.sd_sort = x.det ? side_stream((hipStream_t)st) : nullptr;      // the id sort runs beside the decoder's chain kernels, also in the two-phase form
-  // (one-phase backward by default: the two-phase form belongs to the data-parallel step, whose capture already carries the collectives'
-  // stream; there the side stream measured 0.692 against 0.699 ms on a 1-rank RCCL group and is opt-in: ADT_SIDE_STREAM_DP=1)
-  static const int dp_on = adt_env_int("ADT_SIDE_STREAM_DP", 0) != 0;
-  x.sd = (x.plan.phase == 0 || dp_on) ? side_stream((hipStream_t)st) : nullptr;
+  x.sd_sort = x.sp.det ? side_stream(x.sp, (hipStream_t)st) : nullptr;      // the id sort runs beside the decoder's chain kernels, also in the two-phase form
+  x.sd = x.call.side ? side_stream(x.sp, (hipStream_t)st) : nullptr;
   return 0;
 }
 
@@ -656,10 +588,10 @@ struct LogitsSide {
     const WS& w = x.w;
     if (x.plan.bce_fwd) {      // nothing to launch: the forward put the kernel on the side stream (or, without one, on this stream); joined below
       at = BY_FORWARD;
-    } else if (x.det) {
+    } else if (x.sp.det) {
       CK(x.zero_unless_prezeroed(w.prep, (size_t)NREPP * w.prep_stride, x.st));
       CK(x.logits_scatter(x.st));      // no atomics left in it: a short streaming pass on the caller's stream
-    } else if (x.sd && (side_sites() & 1)) {
+    } else if (x.sd && (x.sp.side_sites & 1)) {
       CK(side_mark(x.sd, 0, x.st));
       CK(x.zero_unless_prezeroed(w.prep, (size_t)NREPP * w.prep_stride, x.st));
       at = MARKED;
@@ -682,7 +614,7 @@ struct LogitsSide {
   int join(const Bwd& x) {
     if (at == ENQUEUED) CK(side_join(x.sd, 0, x.st));
     if (at == BY_FORWARD) {
-      SideStream* const sl = fwd_logits_stream(x.st);
+      SideStream* const sl = fwd_logits_stream(x.sp, x.st);
       if (sl && hipStreamWaitEvent((hipStream_t)x.st, sl->join_ev[0], 0) != hipSuccess) return adt_set_error("backward: logits join");
     }
     at = DONE;
@@ -697,16 +629,16 @@ int dec_post_bwd(const Bwd& x, int i) {
   float* base = x.ws + i * w.d_stride;
   adt::BwdChainArgs a = x.BA(x.dec, x.p, x.seed);
   a.site1 = dec_site(i, 2); a.site2 = dec_site(i, 3);
-  a.gy = x.ws + w.g_dec_x + (i + 1) * x.Td; a.u = base + w.d_u; a.xin = base + w.d_a2; a.o = base + w.d_o2; a.saved_bf16 = x.lean;
+  a.gy = x.ws + w.g_dec_x + (i + 1) * x.Td; a.u = base + w.d_u; a.xin = base + w.d_a2; a.o = base + w.d_o2; a.saved_bf16 = x.sp.lean;
   a.W0 = P + lo.dec(i, D_C2W); a.W1 = P + lo.dec(i, D_C1W); a.W2 = P + lo.dec(i, D_EOW);
   a.dW0 = Gq + lo.dec(i, D_C2W); a.dW1 = Gq + lo.dec(i, D_C1W); a.dW2 = Gq + lo.dec(i, D_EOW);
   a.db0 = Gq + lo.dec(i, D_C2B); a.db1 = Gq + lo.dec(i, D_C1B); a.db2 = Gq + lo.dec(i, D_EOB);
   a.out0 = x.s1;
   a.part[0] = x.PART(i, PS_D_C2); a.part[1] = x.PART(i, PS_D_C1); a.part[2] = x.PART(i, PS_D_EO); a.part_stride = (size_t)w.part_stride;
   a.vpart = x.VPART(i, 0);
-  const int rc = x.use_seq ? adt_launch_seq_post_bwd(x.hd, 0, a, x.st) : 1;
+  const int rc = x.sp.use_seq ? adt_launch_seq_post_bwd(x.hd, 0, a, x.st) : 1;
   if (rc < 0) return rc;
-  if (rc && x.parts) return adt_set_error(NO_FALLBACK, x.L, x.hd);
+  if (rc && x.sp.parts) return adt_set_error(NO_FALLBACK, x.L, x.hd);
   return rc ? adt_launch_bwdchain(x.prec, 1, a, x.st) : 0;
 }
 
@@ -716,14 +648,14 @@ int dec_cross_attn_bwd(const Bwd& x, int i) {
   float* base = x.ws + i * w.d_stride;
   float *q2 = base + w.d_q2, *kv2 = base + w.d_kv2, *o2 = base + w.d_o2, *lse2 = base + w.d_lse2, *s4 = x.s4;
   const uint32_t* mask2 = reinterpret_cast<const uint32_t*>(base + w.d_mask2);
-  if (!x.lean)
+  if (!x.sp.lean)
     return adt_attn_bwd(x.prec, q2, d, kv2, 2 * d, kv2 + d, 2 * d, o2, d, lse2, x.s1, d, B, x.H, x.L, x.hd, 1, x.p, x.seed, dec_site(i, 1), x.b_offset,
                         x.s5, d, s4, 2 * d, s4 + d, 2 * d, mask2, x.st);
   const uint16_t* kvb = reinterpret_cast<const uint16_t*>(kv2);      // rows of 128 bf16: k2 | v2
   // dq2 / dk2 / dv2 go to k_seqtt_mid_bwd only (with `parts` a "not covered" from it is an error), which builds bf16 MFMA operands from
   // them: written as bf16 rows (the same rounding, half the bytes); s4 + d / 2 floats = 64 bf16 elements into the (k | v) row
   return adt_attn_bwd_saved_bf16(q2, d, kvb, 2 * d, kvb + d, 2 * d, o2, d, lse2, x.s1, d, B, x.H, x.L, x.hd, x.p, x.seed, dec_site(i, 1), x.b_offset,
-                                 x.s5, d, s4, 2 * d, x.parts ? s4 + d / 2 : s4 + d, 2 * d, mask2, x.parts ? 1 : 0, x.st);
+                                 x.s5, d, s4, 2 * d, x.sp.parts ? s4 + d / 2 : s4 + d, 2 * d, mask2, x.sp.parts ? 1 : 0, x.st);
 }
 
 // the per-sequence mid chain's argument block (adt_seqpost_tt.cuh: both projections' reverse in one launch)
@@ -735,8 +667,8 @@ adt::BwdChainArgs dec_mid_seq_args(const Bwd& x, int i) {
   float* geinw = Gq + lo.dec(i, D_EINW);
   float* geinb = Gq + lo.dec(i, D_EINB);
   adt::BwdChainArgs a = x.BA(x.dec, 0.f, nullptr);
-  a.dqkv = x.s5; a.lddqkv = d; a.xin = base + w.d_a1; a.o = base + w.d_o1; a.saved_bf16 = x.lean; a.dkv2 = x.s4; a.f = x.f;
-  a.grad_bf16 = (x.lean && x.parts) ? 1 : 0;
+  a.dqkv = x.s5; a.lddqkv = d; a.xin = base + w.d_a1; a.o = base + w.d_o1; a.saved_bf16 = x.sp.lean; a.dkv2 = x.s4; a.f = x.f;
+  a.grad_bf16 = (x.sp.lean && x.sp.parts) ? 1 : 0;
   a.W0 = einw; a.W1 = P + lo.dec(i, D_SOW); a.W2 = einw + dd; a.W3 = einw + 2 * dd;
   a.dW0 = geinw; a.dW1 = Gq + lo.dec(i, D_SOW); a.dW2 = geinw + dd; a.dW3 = geinw + 2 * dd;
   a.db0 = geinb; a.db1 = Gq + lo.dec(i, D_SOB); a.db2 = geinb + d; a.db3 = geinb + 2 * d;
@@ -766,14 +698,14 @@ int dec_mid_bwd(const Bwd& x, int i) {
   const float* einw = P + lo.dec(i, D_EINW);
   float* geinw = Gq + lo.dec(i, D_EINW);
   float* geinb = Gq + lo.dec(i, D_EINB);
-  if (x.use_seq) {   // both projections' reverse in one launch per sequence (adt_seqpost_tt.cuh)
+  if (x.sp.use_seq) {   // both projections' reverse in one launch per sequence (adt_seqpost_tt.cuh)
     const int rc = adt_launch_seq_mid_bwd(x.hd, dec_mid_seq_args(x, i), x.st);
     if (rc <= 0) return rc;
-    if (x.parts) return adt_set_error(NO_FALLBACK, x.L, x.hd);
+    if (x.sp.parts) return adt_set_error(NO_FALLBACK, x.L, x.hd);
   }
   {  // q2 = a1 Wq^T, a1 = o1 Wo1^T  -> dO1 (s1)
     adt::BwdChainArgs a = x.BA(x.dec, 0.f, nullptr);
-    a.dqkv = x.s5; a.lddqkv = d; a.xin = a1; a.o = o1; a.saved_bf16 = x.lean;
+    a.dqkv = x.s5; a.lddqkv = d; a.xin = a1; a.o = o1; a.saved_bf16 = x.sp.lean;
     a.W0 = einw; a.W1 = P + lo.dec(i, D_SOW);
     a.dW0 = geinw; a.dW1 = Gq + lo.dec(i, D_SOW); a.db0 = geinb; a.db1 = Gq + lo.dec(i, D_SOB);
     a.out0 = x.s1;
@@ -804,7 +736,7 @@ int attn_block_bwd(const Bwd& x, int i, bool dec) {
   const int64_t inw = dec ? lo.dec(i, D_SINW) : lo.enc(i, E_INW), inb = dec ? lo.dec(i, D_SINB) : lo.enc(i, E_INB);
   const uint32_t site = dec ? dec_site(i, 0) : enc_site(i, 0);
   const int acc = dec ? (i > 0 ? 1 : 0) : 1;
-  if (x.use_seq) {   // ... in one launch per sequence (adt_seqbwd_tt.cuh)
+  if (x.sp.use_seq) {   // ... in one launch per sequence (adt_seqbwd_tt.cuh)
     adt::SeqBwdArgs a = seq_bwd_args(x.L, (int)w.B, x.H, ids, x.p, x.seed, site, x.b_offset, x.hd);
     a.x = xi; a.gamma = P + lnw; a.beta = P + lnb; a.Win = P + inw; a.bin = P + inb;
     a.dO = x.s1; a.o = o; a.lse = lse; a.mask = mask; a.dres = dec ? gy : x.s5;
@@ -816,15 +748,16 @@ int attn_block_bwd(const Bwd& x, int i, bool dec) {
       a.acc = 0; a.seed_other = ws + w.dec_x + (nl - i) * x.Td; a.seed_coef = ws + w.norms + 8 + i;
       if (i > 0) { a.seed_loss = ws + w.loss + 64 * (2 + i); a.seed_norms = ws + w.norms; }      // pair i >= 1 is not touched by the loss pass at all
     }
-    a.nrep = NREPP; a.rep_stride = (size_t)w.prep_stride; a.wp_base = P + lo.posw(); a.wp_img = ws + w.wpack; a.saved_bf16 = x.lean;
+    a.nrep = NREPP; a.rep_stride = (size_t)w.prep_stride; a.wp_base = P + lo.posw(); a.wp_img = ws + w.wpack; a.saved_bf16 = x.sp.lean;
     a.part = x.PART(i, dec ? PS_D_SIN : PS_E_IN); a.part_stride = (size_t)w.part_stride;
     a.vpart = x.VPART(i, dec ? 2 : 4);
-    a.nsplit = a.part ? attn_split((int)w.B) : 1;
+    a.nsplit = a.part ? x.sp.attn_split : 1;
     time_mark(dec ? 2 : 1, i, true, x.st);
     const int rc = adt_launch_seq_attn_pre_bwd(x.hd, dec ? 1 : 0, a, x.st);
     time_mark(dec ? 2 : 1, i, false, x.st);
     if (rc <= 0) return rc;
-    if (x.lean) return adt_set_error("backward: the lean forward needs the fused attention-block backward (L=%d hd=%d)", x.L, x.hd);
+    // defensive: StepPlan::lean implies adt_covers_attn_pre_bwd (ADT_SEQ_BWD, weight images, L % 4 == 0, L <= ADT_SEQ_MAXLEN, H hd = 64)
+    if (x.sp.lean) return adt_set_error("backward: the lean forward needs the fused attention-block backward (L=%d hd=%d)", x.L, x.hd);
   }
   CK(adt_attn_bwd(x.prec, qkv, 3 * d, qkv + d, 3 * d, qkv + 2 * d, 3 * d, o, d, lse, x.s1, d, (int)w.B, x.H, x.L, x.hd, 1, x.p, x.seed, site, x.b_offset,
                   x.s3, 3 * d, x.s3 + d, 3 * d, x.s3 + 2 * d, 3 * d, mask, x.st));
@@ -841,12 +774,13 @@ int attn_block_bwd(const Bwd& x, int i, bool dec) {
 int dec_block_backward(const Bwd& x, int i, LogitsSide& logits) {
   CK(dec_post_bwd(x, i));
   CK(logits.after_first_chain_kernel(x));
-  if (x.use_seq && x.lean && x.parts) {      // dec_cross_attn_bwd + dec_mid_bwd in one launch per sequence where covered (adt_seqxattn_tt.cuh)
+  if (x.sp.use_seq && x.sp.lean && x.sp.parts) {      // dec_cross_attn_bwd + dec_mid_bwd in one launch per sequence where covered (adt_seqxattn_tt.cuh)
     const adt::AttnArgs at = dec_cross_attn_lean_args(x, i);
     const adt::BwdChainArgs mid = dec_mid_seq_args(x, i);
     if (adt_seq_xattn_mid_covered(x.hd, at, mid)) {
       CK(logits.join(x));      // the launch adds into d log_feats: the logits side joins in front of it
       const int rc = adt_launch_seq_xattn_mid_bwd(x.hd, at, mid, x.st);
+      // defensive: the launcher asks adt_seq_xattn_mid_covered of the same two argument blocks again
       if (rc) return rc < 0 ? rc : adt_set_error("backward: the fused cross-attention + mid launch refused a shape it covers (L=%d hd=%d)", x.L, x.hd);
       return attn_block_bwd(x, i, true);
     }
@@ -875,20 +809,20 @@ struct DecSide {
     const int64_t dec_begin = lo.dec(0, 0);
     // (embed3: the decoder embedding's rows go out with the encoder's at the very end -- with the sums left to the optimizer's fold there is then
     // nothing for the side stream here, and no fork)
-    if (x.plan.phase == 0 && x.sd && (side_sites() & 2) && !(x.embed3 && (x.late_parts || !x.parts))) {
+    if (x.plan.phase == 0 && x.sd && (x.sp.side_sites & 2) && !(x.call.embed3 && (x.call.late_parts || !x.sp.parts))) {
       CK(side_mark(x.sd, 1, x.st));
       at = MARKED;                      // enqueued behind the first kernel of the encoder phase
     } else if (x.plan.phase == 0) {
-      if (!x.det && !x.embed3) CK(embed(x, x.st));
-    } else if (x.det) {      // two-phase form: the decoder blocks' partial sums and the fold of the decoder range (nothing of the tables yet)
-      if (x.parts) CK(reduce_partials(x.c, lo, w, x.G, x.ws, false, true, x.st));
+      if (!x.sp.det && !x.call.embed3) CK(embed(x, x.st));
+    } else if (x.sp.det) {      // two-phase form: the decoder blocks' partial sums and the fold of the decoder range (nothing of the tables yet)
+      if (x.sp.parts) CK(reduce_partials(x.c, lo, w, x.sp, x.G, x.ws, false, true, x.st));
       CK(adt_replica_reduce(x.G + dec_begin, x.Gq + dec_begin, lo.total - dec_begin, NREPP, w.prep_stride, x.st));
     } else {
       void* s2 = nullptr;
       CK(side_mark(x.sd, 1, x.st));
-      if (!x.embed3) CK(embed(x, x.st));
+      if (!x.call.embed3) CK(embed(x, x.st));
       CK(side_enter(x.sd, 1, x.st, &s2));
-      if (x.parts) CK(reduce_partials(x.c, lo, w, x.G, x.ws, false, true, s2));
+      if (x.sp.parts) CK(reduce_partials(x.c, lo, w, x.sp, x.G, x.ws, false, true, s2));
       CK(side_join(x.sd, 1, x.st));
       CK(adt_replica_reduce2(x.G + lo.item(), x.ws + w.rep, (int64_t)(x.c->item_num + 1) * x.d, NREP, w.rep_stride, x.G + dec_begin, x.Gq + dec_begin,
                              lo.total - dec_begin, NREPP, w.prep_stride, x.st));
@@ -900,8 +834,8 @@ struct DecSide {
     if (at != MARKED) return 0;
     void* s2 = nullptr;
     CK(side_enter(x.sd, 1, x.st, &s2));
-    if (!x.det && !x.embed3) CK(embed(x, s2));
-    if (x.parts && !x.late_parts) { CK(reduce_partials(x.c, x.lo, x.w, x.G, x.ws, false, true, s2)); parts_done = true; }
+    if (!x.sp.det && !x.call.embed3) CK(embed(x, s2));
+    if (x.sp.parts && !x.call.late_parts) { CK(reduce_partials(x.c, x.lo, x.w, x.sp, x.G, x.ws, false, true, s2)); parts_done = true; }
     at = ENQUEUED;
     return 0;
   }
@@ -917,8 +851,8 @@ struct DecSide {
 int last_layernorm_bwd(const Bwd& x) {
   const WS& w = x.w; const Layout& lo = x.lo; float* const ws = x.ws;
   const int d = x.d;
-  if (x.lnl_fused) return 0;      // (nothing to launch: BwdChainArgs::lnl_x of the first encoder kernel)
-  if (x.late_parts) {
+  if (x.sp.lnl_fused) return 0;      // (nothing to launch: BwdChainArgs::lnl_x of the first encoder kernel)
+  if (x.call.late_parts) {
     const int nb = adt_layernorm_bwd_parts(x.gf, d, ws + w.enc_x + x.nl * x.Td, d, x.P + lo.lnl_w(), LN_EPS, x.T, d, ws + w.g_enc_x + x.nl * x.Td, d, 0,
                                            ws + w.lnpart, LN_PART_BLOCKS, x.st);
     return nb < 0 ? nb : 0;
@@ -935,7 +869,7 @@ int enc_post_bwd(const Bwd& x, int i) {
   float* base = ws + i * w.e_stride;
   adt::BwdChainArgs a = x.BA(x.seq, x.p, x.seed);
   a.site1 = enc_site(i, 1); a.site2 = enc_site(i, 2);
-  a.gy = ws + w.g_enc_x + (i + 1) * x.Td; a.u = base + w.e_u; a.xin = base + w.e_h; a.o = base + w.e_o; a.saved_bf16 = x.lean;
+  a.gy = ws + w.g_enc_x + (i + 1) * x.Td; a.u = base + w.e_u; a.xin = base + w.e_h; a.o = base + w.e_o; a.saved_bf16 = x.sp.lean;
   a.W0 = P + lo.enc(i, E_C2W); a.W1 = P + lo.enc(i, E_C1W); a.W2 = P + lo.enc(i, E_OW);
   a.gamma = P + lo.enc(i, E_LN2W); a.beta = P + lo.enc(i, E_LN2B);
   a.dW0 = Gq + lo.enc(i, E_C2W); a.dW1 = Gq + lo.enc(i, E_C1W); a.dW2 = Gq + lo.enc(i, E_OW);
@@ -950,21 +884,21 @@ int enc_post_bwd(const Bwd& x, int i) {
   }
   a.part[0] = x.PART(i, PS_E_C2); a.part[1] = x.PART(i, PS_E_C1); a.part[2] = x.PART(i, PS_E_O); a.part_stride = (size_t)w.part_stride;
   a.vpart = x.VPART(i, 3);
-  if (x.lnl_fused && i == nl - 1) {
+  if (x.sp.lnl_fused && i == nl - 1) {
     a.gy = x.gf; a.lnl_x = ws + w.enc_x + nl * x.Td; a.lnl_gamma = P + lo.lnl_w(); a.lnl_eps = LN_EPS;
-    a.vpart2 = x.late_parts ? ws + w.vpart + (int64_t)(5 * nl) * w.vcall : nullptr;
+    a.vpart2 = x.call.late_parts ? ws + w.vpart + (int64_t)(5 * nl) * w.vcall : nullptr;
     a.lnl_dgamma = Gq + lo.lnl_w(); a.lnl_dbeta = Gq + lo.lnl_b();
   }
-  const int rc = x.use_seq ? adt_launch_seq_post_bwd(x.hd, 1, a, x.st) : 1;
+  const int rc = x.sp.use_seq ? adt_launch_seq_post_bwd(x.hd, 1, a, x.st) : 1;
   if (rc < 0) return rc;
-  if (rc && x.parts) return adt_set_error(NO_FALLBACK, x.L, x.hd);
+  if (rc && x.sp.parts) return adt_set_error(NO_FALLBACK, x.L, x.hd);
   return rc ? adt_launch_bwdchain(x.prec, which, a, x.st) : 0;
 }
 
 int enc_block_backward(const Bwd& x, int i, DecSide& dec_side) {
   const WS& w = x.w; const Layout& lo = x.lo;
   CK(enc_post_bwd(x, i));
-  if (x.lnl_fused && i == x.nl - 1) CK(dec_side.enter(x));      // the first kernel of the encoder phase
+  if (x.sp.lnl_fused && i == x.nl - 1) CK(dec_side.enter(x));      // the first kernel of the encoder phase
   if (x.H > 4) {   // wider classifiers: separate kernel
     float* base = x.ws + i * w.e_stride;
     CK(adt_headcls_bwd(base + w.e_o, x.d, x.P + lo.enc(i, E_SW), base + w.e_rec, x.ws + w.g_rec + i * x.recsz, (int)w.B, x.L, x.H, x.hd, x.s1, x.d,
@@ -979,13 +913,13 @@ int enc_block_backward(const Bwd& x, int i, DecSide& dec_side) {
 int table_gradients(const Bwd& x, DecSide& dec_side) {
   const WS& w = x.w; const Layout& lo = x.lo; float* const ws = x.ws; float* const G = x.G;
   const int phase = x.plan.phase;
-  if (phase == 2 && !x.det && adt::zero_f32_async(ws + w.rep, (size_t)NREP * w.rep_stride, (hipStream_t)x.st)) return adt_set_error("replica zero");
+  if (phase == 2 && !x.sp.det && adt::zero_f32_async(ws + w.rep, (size_t)NREP * w.rep_stride, (hipStream_t)x.st)) return adt_set_error("replica zero");
   // (nothing to put beside the embedding gradient when the optimizer's fold sums the partials: no empty fork / join pair then)
-  SideStream* const sd2 = ((side_sites() & 4) && x.parts && !x.late_parts) ? x.sd : nullptr;
+  SideStream* const sd2 = ((x.sp.side_sites & 4) && x.sp.parts && !x.call.late_parts) ? x.sd : nullptr;
   CK(dec_side.join(x, sd2 != nullptr));
   void* s2 = nullptr;
   CK(side_mark(sd2, 2, x.st));
-  if (x.det) {
+  if (x.sp.det) {
     // item table: every item's rows (encoder ids, decoder ids, positive / negative items of the logits) summed by one owner in sorted
     // order ; positional table: one owner per position
     if (x.sd_sort && hipStreamWaitEvent((hipStream_t)x.st, x.sd_sort->join_ev[3], 0) != hipSuccess) return adt_set_error("backward: sort join");
@@ -994,18 +928,18 @@ int table_gradients(const Bwd& x, DecSide& dec_side) {
     const float* const dx2[2] = {ws + w.g_enc_x, ws + w.g_dec_x};
     CK(adt_item_segsum_posemb(reinterpret_cast<int32_t*>(ws + w.isort), 4, x.T, x.c->item_num + 1, 0xFu, site4, x.p, x.seed, sqrtf((float)x.d), G + lo.item(),
                               x.plan.prep_zeroed ? 0 : 1, ids2, dx2, site4, 2, (int)w.B, x.L, x.ro, G + lo.posw(), x.st));
-  } else if (x.embed3) {      // encoder + decoder embedding rows + the positive-logit rows: one atomic row-add per token where their ids line up
+  } else if (x.call.embed3) {      // encoder + decoder embedding rows + the positive-logit rows: one atomic row-add per token where their ids line up
     const bool by_forward = phase == 2 ? x.plan.seeds_virtual : x.plan.bce_fwd;      // (phase 2: the caller passes the ring only behind such a forward)
     CK(adt_embed_bwd3_prefetch(x.seq, x.dec, x.pos, ws + w.g_enc_x, ws + w.g_dec_x, x.f, ws + w.g_pos, x.T, x.L, x.p, x.seed, SITE_EMB_SEQ, SITE_EMB_DEC, x.ro,
-                               G + lo.posw(), ws + w.rep, NREP, w.rep_stride, ring_prefetch_split(x.ring, by_forward, w) ? &x.ring : nullptr, x.st));
+                               G + lo.posw(), ws + w.rep, NREP, w.rep_stride, ring_prefetch_split(x.ring, by_forward, x.sp) ? &x.ring : nullptr, x.st));
   } else {
     CK(adt_embed_bwd_rep(x.seq, ws + w.g_enc_x, x.T, x.L, x.d, x.p, x.seed, SITE_EMB_SEQ, x.ro, G + lo.posw(), ws + w.rep, NREP, w.rep_stride, x.st));
   }
   CK(side_enter(sd2, 2, x.st, &s2));
-  if (x.parts && !x.late_parts) CK(reduce_partials(x.c, lo, w, G, ws, true, phase == 0 && !dec_side.parts_done, s2));
+  if (x.sp.parts && !x.call.late_parts) CK(reduce_partials(x.c, lo, w, x.sp, G, ws, true, phase == 0 && !dec_side.parts_done, s2));
   CK(side_join(sd2, 2, x.st));
   if (x.plan.defer_fold) return 0;
-  return adt_replica_reduce2(G + lo.item(), ws + w.rep, (int64_t)(x.c->item_num + 1) * x.d, x.det ? 0 : NREP, w.rep_stride, G + lo.posw(), x.Gq + lo.posw(),
+  return adt_replica_reduce2(G + lo.item(), ws + w.rep, (int64_t)(x.c->item_num + 1) * x.d, x.sp.det ? 0 : NREP, w.rep_stride, G + lo.posw(), x.Gq + lo.posw(),
                              (phase == 0 ? lo.total : lo.dec(0, 0)) - lo.posw(), NREPP, w.prep_stride, x.st);
 }
 
@@ -1027,7 +961,7 @@ int item_sort_begin(const Bwd& x) {
 // phase 0 / 1: logits, decoder stack, the decoder-side table work
 int decoder_phase(const Bwd& x, DecSide& dec_side) {
   if (x.w.prep != x.w.rep + NREP * x.w.rep_stride) return adt_set_error("workspace layout: replica areas not adjacent");
-  if (x.det) CK(item_sort_begin(x));
+  if (x.sp.det) CK(item_sort_begin(x));
   LogitsSide logits;
   CK(logits.begin(x));
   for (int i = x.nl - 1; i >= 0; --i) CK(dec_block_backward(x, i, logits));
@@ -1037,7 +971,7 @@ int decoder_phase(const Bwd& x, DecSide& dec_side) {
 // phase 0 / 2: last LayerNorm, encoder stack, table gradients, fold
 int encoder_phase(const Bwd& x, DecSide& dec_side) {
   CK(last_layernorm_bwd(x));
-  if (!x.lnl_fused) CK(dec_side.enter(x));
+  if (!x.sp.lnl_fused) CK(dec_side.enter(x));
   for (int i = x.nl - 1; i >= 0; --i) CK(enc_block_backward(x, i, dec_side));
   return table_gradients(x, dec_side);
 }
@@ -1056,13 +990,13 @@ int64_t adt_sasrec_param_layout(const adt_sasrec_cfg* cfg, int64_t* offsets) {
 
 int64_t adt_sasrec_workspace_floats(const adt_sasrec_cfg* cfg, int B) {
   WS w;
-  make_ws(cfg, B, &w);
+  make_ws(cfg, B, step_plan(cfg, B), &w);
   return w.total;
 }
 
 int64_t adt_sasrec_ws_offset(const adt_sasrec_cfg* cfg, int B, int what, int layer) {
   WS w;
-  make_ws(cfg, B, &w);
+  make_ws(cfg, B, step_plan(cfg, B), &w);
   const int64_t Td = up64(w.T * w.d), rec = up64(w.T * w.H * w.H);
   switch (what) {
     case ADT_WS_ENC_X: return w.enc_x + layer * Td;
@@ -1088,14 +1022,15 @@ int adt_sasrec_forward(const adt_sasrec_cfg* c, const float* P, float* ws, const
                        uint32_t b_offset, void* st) {
   Layout lo;
   WS w;
-  CK(layout_ws(c, B, &lo, &w));
+  StepPlan pl;
+  CK(layout_ws(c, B, &lo, &w, &pl));
   const int T = (int)w.T, d = (int)w.d, H = (int)w.H, hd = d / H, L = (int)w.L, prec = c->prec;
   const int64_t Td = up64(w.T * w.d);
   const bool packed = (training & ADT_TRAIN_PACKED) != 0;       // the weight images were packed by adt_sasrec_step_begin* of this step
   training &= ADT_TRAIN_DROPOUT;
   const float p = training ? c->dropout : 0.f;
   const uint32_t ro = b_offset * (uint32_t)L;
-  CK(encoder_forward(c, lo, w, P, ws, seq, pos, neg, p, seed, b_offset, true, st, packed));
+  CK(encoder_forward(c, lo, w, pl, P, ws, seq, pos, neg, p, seed, b_offset, true, st, packed));
   const float* f = ws + w.f;
   const int dd = d * d;
   const int B_ = (int)w.B;
@@ -1110,8 +1045,8 @@ int adt_sasrec_forward(const adt_sasrec_cfg* c, const float* P, float* ws, const
     const float* sinb = P + lo.dec(i, D_SINB);
     const float* einw = P + lo.dec(i, D_EINW);
     const float* einb = P + lo.dec(i, D_EINB);
-    if (adt_seq_supported(prec, L, d, hd)) {   // the whole layer in one launch, one workgroup per sequence (adt_seqfwd.cuh)
-      CK(dec_layer_seq_fwd(c, lo, w, P, ws, dec, p, seed, b_offset, i, st));
+    if (pl.use_seq) {   // the whole layer in one launch, one workgroup per sequence (adt_seqfwd.cuh)
+      CK(dec_layer_seq_fwd(lo, w, pl, P, ws, dec, p, seed, b_offset, i, st));
       continue;
     }
     {  // [gather] ; D = LN(x) ; qkv = D Win^T + b                          (sasrec/model.py:53-59, modules.py:668-670)
@@ -1148,7 +1083,11 @@ int adt_sasrec_forward(const adt_sasrec_cfg* c, const float* P, float* ws, const
 // adt_sasrec_forward (training) + adt_sasrec_loss_seed_nz in one call; on the lean per-sequence path (adt_sasrec_bce_deferred) without the
 // k_final_fwd launch and without the BCE block of the loss assembly: the caller must then run adt_sasrec_backward with ADT_PHASE_BCE_HERE.
 // The loss slots must have been zeroed (adt_sasrec_step_begin*).
-int adt_sasrec_bce_deferred(const adt_sasrec_cfg* c) { return check_cfg(c) == 0 && bce_deferred(c) ? 1 : 0; }
+int adt_sasrec_bce_deferred(const adt_sasrec_cfg* c) {
+  const StepPlan pl = step_plan(c, 1);      // (no rule behind bce_deferred reads the batch size)
+  if (pl.cfg_error[0]) (void)adt_set_error("%s", pl.cfg_error);
+  return !pl.cfg_error[0] && pl.bce_deferred ? 1 : 0;
+}
 int adt_sasrec_forward_loss(const adt_sasrec_cfg* c, const float* P, float* ws, const int32_t* seq, const int32_t* dec, const int32_t* pos,
                             const int32_t* neg, int B, int training, const uint32_t* seed, uint32_t b_offset, const float* lambdas1,
                             const float* lambdas2, void* st) {
@@ -1162,10 +1101,11 @@ int adt_sasrec_forward_loss_prefetch(const adt_sasrec_cfg* c, const float* P, fl
                                      int32_t* staging, void* st) {
   Layout lo;
   WS w;
-  CK(layout_ws(c, B, &lo, &w));
+  StepPlan pl;
+  CK(layout_ws(c, B, &lo, &w, &pl));
   if ((training & ADT_TRAIN_DROPOUT) && (training & ADT_TRAIN_PACKED)) {      // training forward on weight images packed by this step's adt_sasrec_step_begin*
     const adt::RingPrefetchArgs rr{ring, (size_t)slot_ints, nslots, (size_t)(4 * w.T + 4), state, consumed, staging, 0, 0};
-    const int rc = forward_loss_lean(c, lo, w, P, ws, seq, dec, pos, neg, (training & ADT_TRAIN_BCE_SIDE) != 0, c->dropout, seed, b_offset, lambdas1, lambdas2, rr, st);
+    const int rc = forward_loss_lean(c, lo, w, pl, P, ws, seq, dec, pos, neg, (training & ADT_TRAIN_BCE_SIDE) != 0, c->dropout, seed, b_offset, lambdas1, lambdas2, rr, st);
     if (rc <= 0) return rc;
   }
   CK(adt_sasrec_forward(c, P, ws, seq, dec, pos, neg, B, training, seed, b_offset, st));
@@ -1178,18 +1118,19 @@ int adt_sasrec_probe_dec_layer_fwd(const adt_sasrec_cfg* c, const float* P, floa
                                    const uint32_t* seed, uint32_t b_offset, int layer, void* st) {
   Layout lo;
   WS w;
-  CK(layout_ws(c, B, &lo, &w));
-  const int d = (int)w.d, hd = d / (int)w.H;
+  StepPlan pl;
+  CK(layout_ws(c, B, &lo, &w, &pl));
   if (layer < 0 || layer >= c->num_layers) return adt_set_error("probe: layer %d", layer);
-  if (!adt_seq_supported(c->prec, (int)w.L, d, hd)) return adt_set_error("probe: the fused decoder layer does not cover this configuration");
-  return dec_layer_seq_fwd(c, lo, w, P, ws, dec, training ? c->dropout : 0.f, seed, b_offset, layer, st);
+  if (!pl.use_seq) return adt_set_error("probe: the fused decoder layer does not cover this configuration");
+  return dec_layer_seq_fwd(lo, w, pl, P, ws, dec, training ? c->dropout : 0.f, seed, b_offset, layer, st);
 }
 
 int adt_sasrec_step_begin(const adt_sasrec_cfg* c, float* ws, int B, uint32_t* seed, uint32_t seed_inc, const float* norms_src, const float* P,
                           float* G, int64_t n, float* scal, void* st) {
   Layout lo;
   WS w;
-  CK(layout_ws(c, B, &lo, &w));
+  StepPlan pl;
+  CK(layout_ws(c, B, &lo, &w, &pl));
   int offs[256];
   const int npack = pack_offsets(c, lo, offs);
   return adt_step_begin_launch(seed, seed_inc, ws + w.norms, norms_src, ws + w.loss, 64 * (2 + 2 * c->num_layers), scal, G, n, P + lo.item(),
@@ -1208,7 +1149,8 @@ int adt_sasrec_step_begin_ring_staged(const adt_sasrec_cfg* c, float* ws, int B,
                                       const uint32_t* produced, const float* P, float* G, int64_t n, float* scal, void* st) {
   Layout lo;
   WS w;
-  CK(layout_ws(c, B, &lo, &w));
+  StepPlan pl;
+  CK(layout_ws(c, B, &lo, &w, &pl));
   int offs[256];
   const int npack = pack_offsets(c, lo, offs);
   return adt_step_begin_ring_launch(seed, seed_inc, ws + w.norms, ws + w.loss, 64 * (2 + 2 * c->num_layers), scal, G, n, P + lo.item(),
@@ -1230,13 +1172,14 @@ int adt_sasrec_loss_seed_nz(const adt_sasrec_cfg* c, float* ws, const int32_t* p
 static int loss_seed_impl(const adt_sasrec_cfg* c, float* ws, const int32_t* pos, int B, const float* lambdas1, const float* lambdas2,
                           bool zero_loss, void* st) {
   WS w;
-  make_ws(c, B, &w);
+  const StepPlan pl = step_plan(c, B);
+  make_ws(c, B, pl, &w);
   const int nl = c->num_layers, T = (int)w.T, H = (int)w.H;
   const int64_t Td = up64(w.T * w.d), rec = up64(w.T * w.H * w.H);
   float* loss = ws + w.loss;
   const float* norms = ws + w.norms;
   if (zero_loss && adt::zero_f32_async(loss, (size_t)64 * (2 + 2 * nl), (hipStream_t)st)) return adt_set_error("loss zero");
-  if (nl <= 4) {   // one launch for all of them (adt_misc.cuh: k_loss_seeds)
+  if (pl.loss_one_launch) {   // one launch for all of them (adt_misc.cuh: k_loss_seeds)
     LossPtrs q;
     AdtLossSeedsJob job = loss_terms(w, ws, lambdas1, lambdas2, true, &q);
     job.pos_logits = ws + w.posl; job.neg_logits = ws + w.negl; job.pos = pos; job.dpos = ws + w.g_pos; job.dneg = ws + w.g_neg;
@@ -1280,17 +1223,18 @@ static int fold_impl(bool adam, const adt_sasrec_cfg* c, float* ws, int B, float
                      float b1, float b2, float eps, float* scal, void* st) {
   Layout lo;
   WS w;
-  CK(layout_ws(c, B, &lo, &w));
+  StepPlan pl;
+  CK(layout_ws(c, B, &lo, &w, &pl));
   float* const Gq = ws + w.prep - lo.posw();
-  if (fold_sums_partials(c, w)) {
+  if (pl.fold_parts) {      // single-GPU step: the partials are summed by the optimizer's first kernel, not by k_dwpart_reduce launches
     int slots[256], offs[256];
     const int ns = partial_slots(c, lo, true, true, slots, offs);
     int nwg[256];
-    for (int i = 0; i < ns; ++i) nwg[i] = partial_nwg(slots[i], B);
+    for (int i = 0; i < ns; ++i) nwg[i] = partial_nwg(pl, slots[i], B);
     // the stored bias / LayerNorm / classifier sums (BwdChainArgs::vpart: the kernels' sRed layouts) -> 64-float chunks of G
     int vsrc[128], vnwg[128], vstr[128], voff[128];
     int nv = 0;
-    const int nsplit_wg = B * seq_split(B), nattn_wg = B * attn_split(B), d = c->hidden;
+    const int nsplit_wg = B * pl.seq_split, nattn_wg = B * pl.attn_split, d = c->hidden;
     auto chunk = [&](int layer, int k, int t0, int nw, int64_t goff) {
       vsrc[nv] = (int)((int64_t)(5 * layer + k) * w.vcall + t0); vnwg[nv] = nw; vstr[nv] = 512; voff[nv] = (int)goff; ++nv;
     };
@@ -1306,7 +1250,7 @@ static int fold_impl(bool adam, const adt_sasrec_cfg* c, float* ws, int B, float
       chunk(i, 4, 0, nattn_wg, lo.enc(i, E_LN1W)); chunk(i, 4, 64, nattn_wg, lo.enc(i, E_LN1B));
       for (int j = 0; j < 3; ++j) chunk(i, 4, 128 + 64 * j, nattn_wg, lo.enc(i, E_INB) + j * d);
     }
-    if (lnl_fuse_on()) {      // the last LayerNorm: per-workgroup sums of the first encoder kernel of the backward (BwdChainArgs::vpart2)
+    if (pl.lnl_fused) {      // the last LayerNorm: per-workgroup sums of the first encoder kernel of the backward (BwdChainArgs::vpart2)
       chunk(c->num_layers, 0, 0, nsplit_wg, lo.lnl_w()); chunk(c->num_layers, 0, 64, nsplit_wg, lo.lnl_b());
     } else {      // per-block sums of k_ln_bwd (dgamma | dbeta, 128 floats per block)
       const int T = B * c->maxlen, nb = (T + 15) / 16 < LN_PART_BLOCKS ? (T + 15) / 16 : LN_PART_BLOCKS;
@@ -1315,18 +1259,18 @@ static int fold_impl(bool adam, const adt_sasrec_cfg* c, float* ws, int B, float
       vsrc[nv] = base + 64; vnwg[nv] = nb; vstr[nv] = 128; voff[nv] = (int)lo.lnl_b(); ++nv;
     }
     if (!adam)
-      return adt_fold_parts(P, G, lo.total, G + lo.item(), ws + w.rep, (int64_t)(c->item_num + 1) * c->hidden, item_det(w) ? 0 : NREP, w.rep_stride,
+      return adt_fold_parts(P, G, lo.total, G + lo.item(), ws + w.rep, (int64_t)(c->item_num + 1) * c->hidden, pl.det ? 0 : NREP, w.rep_stride,
                             G + lo.posw(), Gq + lo.posw(), lo.total - lo.posw(), 0, w.prep_stride, ws + w.part, w.part_stride, nwg, slots, offs, ns,
                             ws + w.vpart, vsrc, vnwg, vstr, voff, nv, ws + w.gnpart, scal, st);
-    return adt_fold_parts_clip_adam(P, G, M, V, lo.total, G + lo.item(), ws + w.rep, (int64_t)(c->item_num + 1) * c->hidden, item_det(w) ? 0 : NREP,
+    return adt_fold_parts_clip_adam(P, G, M, V, lo.total, G + lo.item(), ws + w.rep, (int64_t)(c->item_num + 1) * c->hidden, pl.det ? 0 : NREP,
                                     w.rep_stride, G + lo.posw(), Gq + lo.posw(), lo.total - lo.posw(), 0 /* no replicas: partials */, w.prep_stride,
                                     ws + w.part, w.part_stride, nwg, slots, offs, ns, ws + w.vpart, vsrc, vnwg, vstr, voff, nv, ws + w.gnpart,
                                     wd, clip, lr, b1, b2, eps, scal, st);
   }
   if (!adam)      // the replica fold the backward left out (phase bit 8)
-    return adt_replica_reduce2(G + lo.item(), ws + w.rep, (int64_t)(c->item_num + 1) * c->hidden, item_det(w) ? 0 : NREP, w.rep_stride, G + lo.posw(),
+    return adt_replica_reduce2(G + lo.item(), ws + w.rep, (int64_t)(c->item_num + 1) * c->hidden, pl.det ? 0 : NREP, w.rep_stride, G + lo.posw(),
                                Gq + lo.posw(), lo.total - lo.posw(), NREPP, w.prep_stride, st);
-  return adt_fold_clip_adam(P, G, M, V, lo.total, G + lo.item(), ws + w.rep, (int64_t)(c->item_num + 1) * c->hidden, item_det(w) ? 0 : NREP, w.rep_stride, G + lo.posw(),
+  return adt_fold_clip_adam(P, G, M, V, lo.total, G + lo.item(), ws + w.rep, (int64_t)(c->item_num + 1) * c->hidden, pl.det ? 0 : NREP, w.rep_stride, G + lo.posw(),
                             Gq + lo.posw(), lo.total - lo.posw(), NREPP, w.prep_stride, wd, clip, lr, b1, b2, eps, scal, st);
 }
 
@@ -1343,9 +1287,10 @@ int adt_sasrec_predict(const adt_sasrec_cfg* c, const float* P, float* ws, const
                        int B, int C, float* logits, int32_t* rank, void* st) {
   Layout lo;
   WS w;
-  CK(layout_ws(c, B, &lo, &w));
+  StepPlan pl;
+  CK(layout_ws(c, B, &lo, &w, &pl));
   const int T = (int)w.T, d = (int)w.d, L = (int)w.L;
-  CK(encoder_forward(c, lo, w, P, ws, seq, nullptr, nullptr, 0.f, nullptr, 0, false, st));
+  CK(encoder_forward(c, lo, w, pl, P, ws, seq, nullptr, nullptr, 0.f, nullptr, 0, false, st));
   // final_feat = log_feats[:, -1, :]  (sasrec/model.py:89): row b*L + L-1, i.e. ld = L*d starting at (L-1)*d
   return adt_score_rank(ws + w.f + (int64_t)(L - 1) * d, L * d, P + lo.item(), cand, B, C, d, logits, rank, st);
 }
@@ -1354,6 +1299,12 @@ int adt_sasrec_predict(const adt_sasrec_cfg* c, const float* P, float* ws, const
 // ---- one layer per call (the supernet's candidate layers): include/adt_hip.h --------------------------------------------------------
 namespace {
 struct LayerSave { float *o, *h, *u, *lse, *mask, *a1, *q2, *kv2, *o2, *lse2, *mask2; int64_t total; };
+// the plan of one layer per call: the shape alone (no tables, one layer)
+static StepPlan layer_plan(int prec, int L, int d, int hd, int B) {
+  const int H = (hd > 0 && d % hd == 0) ? d / hd : 0;
+  const StepFacts f{prec, L, d, H, 1, B, 0, false, H > 0 ? adt_seq_attn_bwd_lds(L, H) : 0};
+  return adt_step_plan(f, adt_seq_switches());
+}
 LayerSave layer_save(float* base, int B, int L, int H, int dec) {
   const int64_t T = (int64_t)B * L, row = up64(T * 32), ls = up64((int64_t)B * H * L), mk = up64((int64_t)B * H * L * 8);
   LayerSave s{};
@@ -1366,7 +1317,8 @@ LayerSave layer_save(float* base, int B, int L, int H, int dec) {
 }
 }  // namespace
 
-int adt_seq_layer_supported(int prec, int L, int d, int hd) { return adt_seq_lean(prec, L, d, hd) && adt_seq_partials(prec, L, d, hd) ? 1 : 0; }
+// the lean path with all five per-sequence backward kernels (StepPlan::parts)
+int adt_seq_layer_supported(int prec, int L, int d, int hd) { return layer_plan(prec, L, d, hd, 1).parts ? 1 : 0; }
 
 int64_t adt_seq_layer_save_floats(int B, int L, int H, int dec) { return layer_save(nullptr, B, L, H, dec).total; }
 
@@ -1374,9 +1326,10 @@ int adt_seq_enc_layer_fwd(int B, int L, int H, const int32_t* ids, const float* 
                           const void* wp_img, float p, const uint32_t* seed, uint32_t site_attn, uint32_t site_ffn1, uint32_t site_ffn2,
                           uint32_t b_offset, int training, float* save, float* y, float y_scale, int y_acc, float* rec, void* st) {
   const int hd = 64 / H;
-  if (!adt_seq_layer_supported(ADT_PREC_BF16, L, 64, hd)) return adt_set_error("seq_enc_layer_fwd: L=%d H=%d is not covered", L, H);
+  const StepPlan pl = layer_plan(ADT_PREC_BF16, L, 64, hd, B);
+  if (!pl.parts) return adt_set_error("seq_enc_layer_fwd: L=%d H=%d is not covered", L, H);
   const LayerSave s = layer_save(save, B, L, H, 0);
-  adt::SeqFwdArgs a = seq_args(L, B, H, ids, p, seed, b_offset, hd);
+  adt::SeqFwdArgs a = seq_args(pl.seq_split, L, B, H, ids, p, seed, b_offset, hd);
   a.x = x; a.site_attn = site_attn; a.site1 = site_ffn1; a.site2 = site_ffn2;
   a.gamma = P->ln1_w; a.beta = P->ln1_b; a.Win = P->in_w; a.bin = P->in_b; a.Wo = P->out_w; a.bo = P->out_b;
   a.gamma2 = P->ln2_w; a.beta2 = P->ln2_b; a.W1 = P->c1_w; a.b1 = P->c1_b; a.W2 = P->c2_w; a.b2 = P->c2_b;
@@ -1392,7 +1345,8 @@ int adt_seq_enc_layer_bwd(int B, int L, int H, const int32_t* ids, const float* 
                           uint32_t site_ffn2, uint32_t b_offset, const float* save, const float* gy, float gy_scale, const float* rec,
                           const float* drec, float* gx, int gx_acc, float* scratch, void* st) {
   const int hd = 64 / H, T = B * L;
-  if (!adt_seq_layer_supported(ADT_PREC_BF16, L, 64, hd)) return adt_set_error("seq_enc_layer_bwd: L=%d H=%d is not covered", L, H);
+  const StepPlan pl = layer_plan(ADT_PREC_BF16, L, 64, hd, B);
+  if (!pl.parts) return adt_set_error("seq_enc_layer_bwd: L=%d H=%d is not covered", L, H);
   const LayerSave s = layer_save(const_cast<float*>(save), B, L, H, 0);
   float *dO = scratch, *dh = scratch + up64((int64_t)T * 64);
   {  // FFN + mask + forward_layernorm + out_proj (+ head classifier) reverse -> dh, dO
@@ -1418,9 +1372,10 @@ int adt_seq_dec_layer_fwd(int B, int L, int H, const int32_t* ids, const float* 
                           const float* wp_base, const void* wp_img, float p, const uint32_t* seed, uint32_t site_slf, uint32_t site_enc,
                           uint32_t site_ffn1, uint32_t site_ffn2, uint32_t b_offset, float* save, float* y, float y_scale, int y_acc, void* st) {
   const int hd = 64 / H;
-  if (!adt_seq_layer_supported(ADT_PREC_BF16, L, 64, hd)) return adt_set_error("seq_dec_layer_fwd: L=%d H=%d is not covered", L, H);
+  const StepPlan pl = layer_plan(ADT_PREC_BF16, L, 64, hd, B);
+  if (!pl.parts) return adt_set_error("seq_dec_layer_fwd: L=%d H=%d is not covered", L, H);
   const LayerSave s = layer_save(save, B, L, H, 1);
-  adt::SeqFwdArgs a = seq_args(L, B, H, ids, p, seed, b_offset, hd);
+  adt::SeqFwdArgs a = seq_args(pl.seq_split, L, B, H, ids, p, seed, b_offset, hd);
   a.x = x; a.f = feats; a.site_attn = site_slf; a.site_attn2 = site_enc; a.site1 = site_ffn1; a.site2 = site_ffn2;
   a.gamma = P->ln_w; a.beta = P->ln_b; a.Win = P->sin_w; a.bin = P->sin_b; a.Wo = P->so_w; a.bo = P->so_b;
   a.Win2 = P->ein_w; a.bin2 = P->ein_b; a.Wo2 = P->eo_w; a.bo2 = P->eo_b; a.W1 = P->c1_w; a.b1 = P->c1_b; a.W2 = P->c2_w; a.b2 = P->c2_b;
@@ -1435,7 +1390,8 @@ int adt_seq_dec_layer_bwd(int B, int L, int H, const int32_t* ids, const float* 
                           uint32_t site_slf, uint32_t site_enc, uint32_t site_ffn1, uint32_t site_ffn2, uint32_t b_offset, const float* save,
                           const float* gy, float gy_scale, float* gx, int gx_acc, float* gfeats, float* scratch, void* st) {
   const int hd = 64 / H, T = B * L, d = 64;
-  if (!adt_seq_layer_supported(ADT_PREC_BF16, L, 64, hd)) return adt_set_error("seq_dec_layer_bwd: L=%d H=%d is not covered", L, H);
+  const StepPlan pl = layer_plan(ADT_PREC_BF16, L, 64, hd, B);
+  if (!pl.parts) return adt_set_error("seq_dec_layer_bwd: L=%d H=%d is not covered", L, H);
   const LayerSave s = layer_save(const_cast<float*>(save), B, L, H, 1);
   const int64_t Td = up64((int64_t)T * 64);
   float *s1 = scratch, *s5 = scratch + Td, *s4 = scratch + 2 * Td;      // dO (T x 64), dq2 (T x 64), dk2 | dv2 (T x 128)

@@ -29,18 +29,35 @@ extern "C" int adt_pack_wimg(const float* base, void* img, const int* offs, int 
   return adt_check_launch("pack_wimg");
 }
 
-int adt_seq_supported(int prec, int L, int d, int hd) {
-  static const int on = adt_env_on("ADT_SEQ");
-  return on && prec == ADT_PREC_BF16 && d == 64 && L <= SQ_LP && (hd == 16 || hd == 32 || hd == 64);
+static_assert(ADT_SEQ_MAXLEN == SQ_LP && ADT_SEQ_MAXLEN == SB_R, "adt_step_plan.h restates the image rows of these kernels");
+
+// The one place that reads the flagship switches from the environment: all of them, at the first flagship call of the process.
+const SeqSwitches& adt_seq_switches() {
+  static const SeqSwitches sw = [] {
+    SeqSwitches s;
+    s.seq = adt_env_on("ADT_SEQ"); s.seq_lean = adt_env_on("ADT_SEQ_LEAN"); s.seq_tt = adt_env_on("ADT_SEQ_TT"); s.seq_bwd = adt_env_on("ADT_SEQ_BWD");
+    s.seq_attn_bwd = adt_env_on("ADT_SEQ_ATTN_BWD"); s.seq_post_bwd = adt_env_on("ADT_SEQ_POST_BWD"); s.seq_partials = adt_env_on("ADT_SEQ_PARTIALS");
+    s.xattn_fused = adt_env_on("ADT_XATTN_FUSED");
+    s.seq_ablate = adt_env_int("ADT_SEQ_ABLATE", 0); s.seq_ablate_set = adt_env_int("ADT_SEQ_ABLATE", INT_MIN) != INT_MIN;
+    s.seq_split = adt_env_int("ADT_SEQ_SPLIT", 0); s.attn_split = adt_env_on("ADT_ATTN_SPLIT");
+    s.side_stream = adt_env_int("ADT_SIDE_STREAM", 7); s.side_stream_dp = adt_env_int("ADT_SIDE_STREAM_DP", 0) != 0;
+    s.item_sort = adt_env_int("ADT_ITEM_SORT", 0) != 0;      // opt-in: +12 us per flagship step (0.637 against 0.625 ms: DESIGN.md "item-table gradient")
+    s.lnl_fused = adt_env_on("ADT_LNL_FUSED"); s.fold_parts = adt_env_on("ADT_FOLD_PARTS"); s.fwd_fused = adt_env_on("ADT_FWD_FUSED");
+    s.embed3 = adt_env_on("ADT_EMBED3"); s.bce_merged = adt_env_on("ADT_BCE_MERGED");
+    return s;
+  }();
+  return sw;
 }
 
-// Lean saved tensors: the transposed-chain forward writes o, h, u, a1, q2, kv2, o2 as bf16 rows and does not write LN(x) / qkv at all (the fused
-// block backward recomputes them from x).  Only when every kernel of the backward that reads them is the per-sequence / flag-aware one:
-// the caller must then treat a "not covered" (1) from adt_launch_seq_attn_pre_bwd / adt_launch_seq_attn_bwd as an error.  ADT_SEQ_LEAN=0: off.
-int adt_seq_lean(int prec, int L, int d, int hd) {
-  static const int on = adt_env_on("ADT_SEQ_LEAN") && adt_env_on("ADT_SEQ_TT") && adt_env_on("ADT_SEQ_BWD") && adt_env_on("ADT_SEQ_ATTN_BWD") &&
-                        adt_env_int("ADT_SEQ_ABLATE", INT_MIN) == INT_MIN;      // ADT_SEQ_ABLATE set at all, to 0 included: off
-  return on && adt_seq_supported(prec, L, d, hd) && (L & 3) == 0 && L <= SB_R && L <= 224 && sab_lds_bytes(L, 64 / hd) <= ADT_LDS_MAX;
+// the shape of an argument block, as the coverage rules of adt_step_plan.h read it
+static SeqAttnFacts attn_facts(const AttnArgs& a) {
+  return {a.L, a.H, a.B, a.causal != 0, a.in_bf16 != 0, a.out_bf16 != 0, a.ldq, a.ldk, a.ldv, a.ldo, a.lddo, a.drop.thr != 0, a.mask != nullptr,
+          sab_lds_bytes(a.L, a.H), xm_lds_bytes(a.L, a.H)};
+}
+size_t adt_seq_attn_bwd_lds(int L, int H) { return sab_lds_bytes(L, H); }      // StepFacts::sab_lds
+static SeqChainFacts chain_facts(const BwdChainArgs& a) {
+  return {a.L, a.H, a.B, a.T, a.wp_img != nullptr, a.saved_bf16 != 0, a.grad_bf16 != 0, a.part[0] && a.part[1] && a.part[2] && a.part[3], a.nsplit, a.ablate,
+          a.drec != nullptr};
 }
 
 static unsigned long long* g_stamps = nullptr;
@@ -66,14 +83,13 @@ static unsigned long long* seq_stamp_buffer_mode(int mode) { return seq_stamps_m
 
 static void seq_ablate(SeqFwdArgs& a) {
   a.stamps = seq_stamp_buffer(false);
-  static const int ab = adt_env_int("ADT_SEQ_ABLATE", 0);
+  const int ab = adt_seq_switches().seq_ablate;
   a.ablate = ab;
   if (ab & 1) { a.qkv = nullptr; a.o = nullptr; a.h = nullptr; a.u = nullptr; a.a1 = nullptr; a.q2 = nullptr; a.kv2 = nullptr; a.o2 = nullptr; a.mask = nullptr; a.mask2 = nullptr; }
 }
 
 static bool seq_use_tt(const SeqFwdArgs& a) {     // register-resident transposed chains (adt_seqfwd_tt.cuh); ADT_SEQ_TT=0: the row-major fused form
-  static const int on = adt_env_on("ADT_SEQ_TT");
-  return on && a.wp_img != nullptr && (a.L & 3) == 0;      // L % 4 == 0: a quad of attention keys shares one dropout hash word
+  return adt_seq_fwd_tt(adt_seq_switches(), a.wp_img != nullptr, a.L);
 }
 
 int adt_launch_seq_enc_fwd(int hd, const SeqFwdArgs& a, void* stream) {
@@ -118,18 +134,13 @@ int adt_launch_seq_dec_fwd(int hd, const SeqFwdArgs& a, void* stream) {
 
 // causal attention backward, one workgroup per sequence (adt_seqattn.cuh); returns 1 when the shape is not covered (caller falls back)
 int adt_launch_seq_attn_bwd(int hd, const AttnArgs& a, void* stream) {
-  static const int on = adt_env_on("ADT_SEQ_ATTN_BWD");
-  if (!on || !a.causal || a.H * hd != 64 || a.L > 224) return 1;
-  if ((a.ldq % 4) || (a.ldk % 4) || (a.ldv % 4) || (a.ldo % 4)) return 1;
-  if (a.in_bf16 && ((a.ldq % 8) || (a.ldk % 8) || (a.ldv % 8) || (a.ldo % 8))) return 1;
+  if (!adt_covers_attn_bwd(adt_seq_switches(), hd, attn_facts(a))) return 1;
   const size_t smem = sab_lds_bytes(a.L, a.H);
-  if (smem > ADT_LDS_MAX) return 1;
   const int mode = a.drop.thr == 0 ? 0 : (a.mask != nullptr ? 1 : 2);
   static AdtLdsOptIn optin[9];
   const void* fns[9] = {(const void*)k_seq_attn_bwd<64, 0>, (const void*)k_seq_attn_bwd<64, 1>, (const void*)k_seq_attn_bwd<64, 2>,
                         (const void*)k_seq_attn_bwd<32, 0>, (const void*)k_seq_attn_bwd<32, 1>, (const void*)k_seq_attn_bwd<32, 2>,
                         (const void*)k_seq_attn_bwd<16, 0>, (const void*)k_seq_attn_bwd<16, 1>, (const void*)k_seq_attn_bwd<16, 2>};
-  if (hd != 64 && hd != 32 && hd != 16) return 1;
   const int slot = (hd == 64 ? 0 : hd == 32 ? 3 : 6) + mode;
   AttnArgs args = a;
   args.stamps = seq_stamp_buffer(true);
@@ -155,25 +166,19 @@ static int seq_attn_pre_bwd_t(int mode, const SeqBwdArgs& a, hipStream_t s) {
 }
 
 int adt_launch_seq_attn_pre_bwd(int hd, int dec, const SeqBwdArgs& a, void* stream) {
-  static const int on = adt_env_on("ADT_SEQ_BWD");
-  if (!on || a.wp_img == nullptr || a.L > SB_R || (a.L & 3) || a.H * hd != 64) return 1;
+  SeqChainFacts f{};
+  f.L = a.L; f.H = a.H; f.B = a.B; f.T = a.B * a.L; f.wimg = a.wp_img != nullptr;
+  if (!adt_covers_attn_pre_bwd(adt_seq_switches(), hd, f)) return 1;
   const int mode = a.drop.thr == 0 ? 0 : (a.mask != nullptr ? 1 : 2);
   hipStream_t s = (hipStream_t)stream;
   if (hd == 32) return dec ? seq_attn_pre_bwd_t<32, true>(mode, a, s) : seq_attn_pre_bwd_t<32, false>(mode, a, s);
   if (hd == 64) return dec ? seq_attn_pre_bwd_t<64, true>(mode, a, s) : seq_attn_pre_bwd_t<64, false>(mode, a, s);
-  if (hd == 16) return dec ? seq_attn_pre_bwd_t<16, true>(mode, a, s) : seq_attn_pre_bwd_t<16, false>(mode, a, s);
-  return 1;
+  return dec ? seq_attn_pre_bwd_t<16, true>(mode, a, s) : seq_attn_pre_bwd_t<16, false>(mode, a, s);
 }
 
 // per-sequence backward of the token-wise chains (adt_seqpost_tt.cuh); 0 launched, 1 not covered (the caller runs the row-major chain kernels)
-static bool seq_post_ok(const BwdChainArgs& a, int hd) {
-  static const int on = adt_env_on("ADT_SEQ_POST_BWD");
-  return on && a.wp_img != nullptr && a.L <= SB_R && a.T == a.B * a.L && (hd == 16 || hd == 32 || hd == 64);
-}
-
 int adt_launch_seq_post_bwd(int hd, int enc, const BwdChainArgs& a, void* stream) {
-  if (!seq_post_ok(a, hd)) return 1;
-  if (enc && a.drec != nullptr && a.H * hd != 64) return 1;
+  if (!adt_covers_post_bwd(adt_seq_switches(), hd, enc != 0, chain_facts(a))) return 1;
   static AdtLdsOptIn optin[6];
   const void* fns[6] = {(const void*)k_seqtt_post_bwd<64, false>, (const void*)k_seqtt_post_bwd<64, true>, (const void*)k_seqtt_post_bwd<32, false>,
                         (const void*)k_seqtt_post_bwd<32, true>, (const void*)k_seqtt_post_bwd<16, false>, (const void*)k_seqtt_post_bwd<16, true>};
@@ -184,7 +189,7 @@ int adt_launch_seq_post_bwd(int hd, int enc, const BwdChainArgs& a, void* stream
 }
 
 int adt_launch_seq_mid_bwd(int hd, const BwdChainArgs& a, void* stream) {
-  if (!seq_post_ok(a, hd)) return 1;
+  if (!adt_covers_mid_bwd(adt_seq_switches(), hd, chain_facts(a))) return 1;
   static AdtLdsOptIn optin;
   BwdChainArgs args = a;
   args.stamps = seq_stamp_buffer_mode(5);
@@ -202,18 +207,9 @@ static std::atomic<unsigned long long> g_xattn_fused_launches{0};
 extern "C" unsigned long long adt_seq_xattn_fused_launches() { return g_xattn_fused_launches.load(); }
 
 int adt_seq_xattn_mid_covered(int hd, const AttnArgs& at, const BwdChainArgs& ch) {
-  static const int on = adt_env_on("ADT_XATTN_FUSED");
-  if (!on || !seq_post_ok(ch, hd)) return 0;
-  if (!at.in_bf16 || !at.out_bf16 || !ch.saved_bf16 || !ch.grad_bf16 || !ch.part[0] || !ch.part[1] || !ch.part[2] || !ch.part[3]) return 0;
-  if (ch.nsplit > 1 || ch.ablate) return 0;
-  if (!at.causal || at.H * hd != 64 || (at.L & 3) || at.L > 224 || at.L != ch.L || at.B != ch.B) return 0;
-  if (at.drop.thr != 0 && at.mask == nullptr) return 0;
-  if ((at.ldq % 8) || (at.ldk % 8) || (at.ldv % 8) || (at.ldo % 8) || (at.lddo % 4)) return 0;
-  // one hand-over: what the attention would write is what the mid chain would read (bf16 rows: dq2 of 64, dk2 | dv2 of 128 elements)
-  if (ch.dqkv != at.dQ || ch.lddqkv != at.lddq || at.lddq != 64 || ch.dkv2 != at.dK || at.lddk != 128 || at.lddv != 128 ||
-      reinterpret_cast<const __bf16*>(at.dV) != reinterpret_cast<const __bf16*>(at.dK) + 64)
-    return 0;
-  return xm_lds_bytes(at.L, at.H) <= ADT_LDS_MAX;
+  const bool handover = ch.dqkv == at.dQ && ch.lddqkv == at.lddq && at.lddq == 64 && ch.dkv2 == at.dK && at.lddk == 128 && at.lddv == 128 &&
+                        reinterpret_cast<const __bf16*>(at.dV) == reinterpret_cast<const __bf16*>(at.dK) + 64;
+  return adt_covers_xattn_mid(adt_seq_switches(), hd, attn_facts(at), chain_facts(ch), handover);
 }
 
 int adt_launch_seq_xattn_mid_bwd(int hd, const AttnArgs& at, const BwdChainArgs& ch, void* stream) {
@@ -235,7 +231,7 @@ int adt_launch_seq_xattn_mid_bwd(int hd, const AttnArgs& at, const BwdChainArgs&
                         (const void*)k_seqtt_xattn_mid_bwd<32, 1>, (const void*)k_seqtt_xattn_mid_bwd<16, 0>, (const void*)k_seqtt_xattn_mid_bwd<16, 1>};
   const int slot = (hd == 64 ? 0 : hd == 32 ? 2 : 4) + mode;
   // smem takes one of two values with L: opt in once (during warm-up, not under capture) to the larger one this head count admits
-  const size_t most = xm_lds_bytes(224, at.H) <= ADT_LDS_MAX ? xm_lds_bytes(224, at.H) : xm_lds_bytes(128, at.H);
+  const size_t most = xm_lds_bytes(ADT_SEQ_MAXLEN, at.H) <= ADT_LDS_MAX ? xm_lds_bytes(ADT_SEQ_MAXLEN, at.H) : xm_lds_bytes(128, at.H);
   const int rc = seq_launch(fns[slot], xm_lds_bytes(at.L, at.H), optin[slot], at.B, &a, (hipStream_t)stream, "seqtt_xattn_mid_bwd", XM_NW, most);
   if (rc == 0) ++g_xattn_fused_launches;
   return rc;
@@ -305,10 +301,4 @@ int adt_dwpart_reduce_n(float* G, const float* part, size_t stride, int nwg, con
   for (int i = 0; i < nslots; ++i) { a.slot[i] = slots[i]; a.off[i] = offs[i]; a.nwg_slot[i] = nwg_slot ? nwg_slot[i] : nwg; }
   hipLaunchKernelGGL(k_dwpart_reduce, dim3(nslots, PR_SPLIT), dim3(256), 0, (hipStream_t)stream, a);
   return adt_check_launch("dwpart_reduce");
-}
-
-// every block-weight gradient of the backward can go through private partials: all five per-sequence backward kernels cover the shape
-int adt_seq_partials(int prec, int L, int d, int hd) {
-  static const int on = adt_env_on("ADT_SEQ_PARTIALS") && adt_env_on("ADT_SEQ_POST_BWD");
-  return on && adt_seq_lean(prec, L, d, hd);
 }

@@ -36,7 +36,7 @@ struct SeqFwdArgs {
   float* o2; float* lse2; uint32_t* mask2;         // decoder: cross attention
   float y_scale; int y_acc;            // layer output: y = (y_acc ? y : 0) + y_scale * layer(x)  (y_scale == 0 means 1: plain store) -- the supernet's
                                        // candidate mixing as an epilogue (sasrec/super_modules.py:42-49)
-  int saved_bf16;                      // o, h, u, a1, q2, kv2, o2 are written as bf16 rows (first half of the same buffers); see adt_seq_lean
+  int saved_bf16;                      // o, h, u, a1, q2, kv2, o2 are written as bf16 rows (first half of the same buffers); see StepPlan::lean (adt_step_plan.h)
   const float* wp_base; const void* wp_img;        // pre-packed bf16 weight images (adt_wave.cuh: WPack); wp_img == nullptr: none
   unsigned long long* stamps;          // timing experiments only (ADT_SEQ_STAMPS): s_memtime per wave of workgroup 0 at phase ends
   int ablate;                          // timing experiments only (ADT_SEQ_ABLATE): 1 no saved-tensor stores, 2 no attention, 4 no ffn
