@@ -132,6 +132,9 @@ SIGNATURES = {
     "adt_bertbatch_eval": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "adt_bertbatch_token": (_I, [_U, _U, _I, _I, _U, _I, _I, _P]),
     "adt_hit_hist": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P]),
+    "adt_evalcand_stream": (_I, [_P, _I, _U, _U, _I, _I, _I, _P]),
+    "adt_evalcand_draw": (_I, [_P, _I, _L, _P, _P, _P, _I, _I, _I, _I, _U, _U, _P, _I, _P, _P]),
+    "adt_cand_rank_hist": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "adt_item_sort_supported": (_I, [_I]),
     "adt_item_sort_work_ints": (_L, [_I, _I, _I]),
     "adt_item_sort": (_I, [_P, _I, _I, _I, _P, _P, _P, _U, _P, _P]),

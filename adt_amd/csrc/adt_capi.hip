@@ -857,4 +857,20 @@ int adt_score_rank(const float* F, int ldf, const float* E, const int32_t* cand,
   return adt_check_launch("score_rank");
 }
 
+int adt_cand_rank_hist(const float* F, int ldf, const float* E, const float* bias, const int32_t* cand, int n_rows, int rows_per_group, int C, int d,
+                       int64_t* hist, int32_t* rank, void* stream) {
+  if (C < 1) return adt_set_error("cand_rank_hist: C=%d < 1", C);
+  if (d < 4 || (d & 3)) return adt_set_error("cand_rank_hist: d=%d is not a positive multiple of 4", d);
+  if (ldf < d || (ldf & 3)) return adt_set_error("cand_rank_hist: ldf=%d is below d=%d or not a multiple of 4", ldf, d);
+  if (rows_per_group < 1) return adt_set_error("cand_rank_hist: rows_per_group=%d < 1", rows_per_group);
+  if (n_rows < 0 || n_rows % rows_per_group != 0)
+    return adt_set_error("cand_rank_hist: n_rows=%d is not a multiple of rows_per_group=%d", n_rows, rows_per_group);
+  if (n_rows == 0) return 0;      // nothing to rank: the pointers are not looked at
+  if (!F || !E || !cand || !hist) return adt_set_error("cand_rank_hist: NULL F, E, cand or hist");
+  if (!adt_aligned16(F) || !adt_aligned16(E)) return adt_set_error("cand_rank_hist: F and E must be 16-byte aligned");
+  CandRankArgs a{F, ldf, E, bias, cand, n_rows, rows_per_group, C, d, (unsigned long long*)hist, rank};
+  hipLaunchKernelGGL(k_cand_rank_hist, dim3(adt_grid_for((size_t)n_rows, 4, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("cand_rank_hist");
+}
+
 }  // extern "C"

@@ -2,6 +2,7 @@
 // clip + Adam.  HBM-bound integer/elementwise work: coalesced float4 accesses, no MFMA.
 #pragma once
 #include "adt_common.cuh"
+#include "adt_candrank.cuh"
 #include "adt_lossring_args.h"
 #include "adt_wave.cuh"
 
@@ -1147,14 +1148,7 @@ __global__ __launch_bounds__(256) void k_score(ScoreArgs a) {
   for (size_t i = (size_t)blockIdx.x * 16 + (threadIdx.x >> 4); i < n; i += (size_t)gridDim.x * 16) {
     const int b = (int)(i / a.C), cidx = (int)(i % a.C);
     const int item = a.cand ? a.cand[i] : cidx;
-    float s = 0.f;
-    for (int c4 = 4 * sub; c4 < a.d; c4 += 64) {
-      const float4 f = *reinterpret_cast<const float4*>(a.F + (size_t)b * a.ldf + c4);
-      const float4 e = *reinterpret_cast<const float4*>(a.E + (size_t)item * a.d + c4);
-      s += f.x * e.x + f.y * e.y + f.z * e.z + f.w * e.w;
-    }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    const float s = cand_dot16(a.F + (size_t)b * a.ldf, a.E + (size_t)item * a.d, a.d, sub);      // adt_candrank.cuh: shared with k_cand_rank_hist
     if (sub == 0) a.logits[i] = s + (a.bias ? a.bias[item] : 0.f);
   }
 }

@@ -1,9 +1,10 @@
-// C ABI (include/adt_hip.h, "STOSA-ADT batches built on the device", "full-sort scores on the device" and "BERT4Rec-ADT batches masked and
-// built on the device"): launch wrappers of adt_seqbatch.cuh, adt_hithist.cuh and adt_bertbatch.cuh, and the host-side draws.  Host code
-// only enqueues work on the caller's stream.
+// C ABI (include/adt_hip.h, "STOSA-ADT batches built on the device", "full-sort scores on the device", "BERT4Rec-ADT batches masked and
+// built on the device" and "SASRec-ADT evaluation candidates drawn on the device"): launch wrappers of adt_seqbatch.cuh, adt_hithist.cuh,
+// adt_bertbatch.cuh and adt_evalcand.cuh, and the host-side draws.  Host code only enqueues work on the caller's stream.
 #include "adt_host.h"
 
 #include "adt_bertbatch.cuh"
+#include "adt_evalcand.cuh"
 #include "adt_hithist.cuh"
 #include "adt_seqbatch.cuh"
 
@@ -58,6 +59,40 @@ int adt_hit_hist(const int32_t* top_idx, int ld, int n_rows, int K, const int32_
   HitHistArgs a{top_idx, ld, K, rows_per_group, chunks, answers, (unsigned long long*)hist, hit_pos};
   hipLaunchKernelGGL(k_hit_hist, dim3((unsigned)blocks), dim3(64 * ADT_HITHIST_WAVES), 0, (hipStream_t)stream, a);
   return adt_check_launch("hit_hist");
+}
+
+// what both evalcand entry points ask of the table's scalars (the table itself may be in device memory: `total` is the caller's word)
+static int evalcand_check_table(const char* what, const void* cum, int n_ids, int64_t total) {
+  if (!cum) return adt_set_error("%s: cum is NULL", what);
+  if (n_ids < 1) return adt_set_error("%s: n_ids=%d < 1", what, n_ids);
+  if (total < 1 || total >= ((int64_t)1 << 32)) return adt_set_error("%s: total=%lld outside 1 .. 2^32 - 1", what, (long long)total);
+  return 0;
+}
+
+int adt_evalcand_stream(const int64_t* cum, int n_ids, uint32_t seed, uint32_t salt, int row, int n0, int n, int32_t* out) {
+  if (evalcand_check_table("evalcand_stream", cum, n_ids, cum && n_ids >= 1 ? cum[n_ids] : 0)) return -1;
+  if (row < 0 || n0 < 0 || n < 0 || (int64_t)n0 + n > (int64_t)INT32_MAX)
+    return adt_set_error("evalcand_stream: row=%d, positions %d..%d+%d", row, n0, n0, n);
+  if (n > 0 && !out) return adt_set_error("evalcand_stream: out is NULL");
+  const uint32_t key = adt_evalcand_key(seed, salt, (uint32_t)row);
+  for (int i = 0; i < n; ++i) out[i] = adt_evalcand_item_key(key, (uint32_t)(n0 + i), cum, n_ids, (uint32_t)cum[n_ids]);
+  return 0;
+}
+
+int adt_evalcand_draw(const int64_t* cum, int n_ids, int64_t total, const int64_t* seen_off, const int32_t* seen_items, const int32_t* targets,
+                      int n_total, int row0, int n_rows, int S, uint32_t seed, uint32_t salt, int32_t* cand, int ldc, int32_t* filled,
+                      void* stream) {
+  if (evalcand_check_table("evalcand_draw", cum, n_ids, total)) return -1;
+  if (S < 1 || S > ADT_EVALCAND_MAX_S) return adt_set_error("evalcand_draw: S=%d outside 1..%d", S, ADT_EVALCAND_MAX_S);
+  if (!seen_off || !seen_items || !targets) return adt_set_error("evalcand_draw: NULL seen_off, seen_items or targets");
+  if (n_total < 0 || row0 < 0 || n_rows < 0 || (int64_t)row0 + n_rows > n_total)
+    return adt_set_error("evalcand_draw: rows %d..%d+%d outside the list of %d users", row0, row0, n_rows, n_total);
+  if (ldc < 1 + S) return adt_set_error("evalcand_draw: ldc=%d < 1 + S=%d", ldc, 1 + S);
+  if (n_rows == 0) return 0;
+  if (!cand) return adt_set_error("evalcand_draw: cand is NULL");
+  EvalCandArgs a{cum, n_ids, (uint32_t)total, seen_off, seen_items, targets, row0, n_rows, S, seed, salt, cand, ldc, filled};
+  hipLaunchKernelGGL(k_evalcand_draw, dim3((unsigned)n_rows), dim3(64), 0, (hipStream_t)stream, a);
+  return adt_check_launch("evalcand_draw");
 }
 
 int adt_bertbatch_token(uint32_t seed, uint32_t salt, int example, int pos, uint32_t thr_mask, int itemnum, int item, int* masked) {

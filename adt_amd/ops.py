@@ -781,3 +781,68 @@ def hit_hist(top_idx, answers, rows_per_group=None, hist=None, want_pos=False):
     ld = top_idx.stride(0) if N > 1 else max(top_idx.stride(0), K)
     _lib.check(_lib.load().adt_hit_hist(_p(top_idx), int(ld), N, K, _p(ans), rpg, _p(hist), _p(pos), _stream()), "hit_hist")
     return (hist, pos) if want_pos else hist
+
+
+# ---- SASRec-ADT sampled evaluation on the device (include/adt_hip.h: adt_evalcand_*, adt_cand_rank_hist; adt_evalcand.cuh, adt_candrank.cuh)
+EVALCAND_MAX_DRAWS, EVALCAND_MAX_S = 4096, 1024
+
+
+def evalcand_stream(cum, seed, salt, row, n0, n):
+    """Stream values n0 .. n0 + n - 1 of GLOBAL row `row` as a numpy int32 array (host only: the inline function adt_evalcand_draw's kernel
+    calls).  cum: HOST int64 prefix sums of the item counts, cum[0] = 0, total = cum[-1] < 2^32."""
+    import numpy as np
+    cum = np.ascontiguousarray(cum, dtype=np.int64)
+    out = np.empty(max(int(n), 0), np.int32)
+    _lib.check(_lib.load().adt_evalcand_stream(cum.ctypes.data, cum.size - 1, int(seed) & 0xFFFFFFFF, int(salt) & 0xFFFFFFFF, int(row), int(n0), int(n),
+                                               out.ctypes.data), "evalcand_stream")
+    return out
+
+
+def evalcand_draw(cum, total, seen_off, seen_items, targets, S, seed=0, salt=0, rows=None, out=None, want_filled=False):
+    """Rows rows=(lo, hi) (default: all) of the candidate table of the evaluation user list: (hi - lo, 1 + S) int32, column 0 =
+    targets[row], columns 1..S the first S distinct values outside the row's sorted seen ids (CSR seen_off int64 / seen_items int32, over
+    the GLOBAL rows) of the popularity stream of (seed, salt, GLOBAL row).  cum: device int64 prefix sums, total = its last entry (the
+    caller's host copy: nothing is read back).  out: an int32 (hi - lo, >= 1 + S) view to write into (row stride free, unit column
+    stride), default a new tensor.  With want_filled also the (hi - lo,) int32 count of properly filled slots (S unless a user has
+    fewer than S drawable ids: the open slots hold id 0)."""
+    assert cum.dtype == torch.int64 and cum.is_contiguous() and seen_off.dtype == torch.int64 and seen_off.is_contiguous(), (cum.dtype, seen_off.dtype)
+    _i32(seen_items), _i32(targets)
+    n_total, S = targets.numel(), int(S)
+    if seen_off.numel() != n_total + 1:
+        raise _lib.AdtError("evalcand_draw: %d targets, seen_off has %d entries" % (n_total, seen_off.numel()))
+    lo, hi = (0, n_total) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= lo <= hi <= n_total:
+        raise _lib.AdtError("evalcand_draw: rows (%d, %d) outside the list of %d users" % (lo, hi, n_total))
+    if out is None:
+        out = torch.empty(hi - lo, 1 + max(S, 0), device=targets.device, dtype=torch.int32)
+    elif out.dtype != torch.int32 or out.dim() != 2 or out.shape[0] != hi - lo or out.shape[1] < 1 + S or (out.shape[1] > 1 and out.stride(1) != 1):
+        raise _lib.AdtError("evalcand_draw: out must be an int32 (%d, >= %d) view with unit column stride" % (hi - lo, 1 + S))
+    filled = torch.empty(hi - lo, device=targets.device, dtype=torch.int32) if want_filled else None
+    ldc = out.stride(0) if hi - lo > 1 else max(out.stride(0), out.shape[1])
+    _lib.check(_lib.load().adt_evalcand_draw(_p(cum), cum.numel() - 1, int(total), _p(seen_off), _p(seen_items), _p(targets), n_total, lo, hi - lo, S,
+                                             int(seed) & 0xFFFFFFFF, int(salt) & 0xFFFFFFFF, _p(out), int(ldc), _p(filled), _stream()), "evalcand_draw")
+    return (out, filled) if want_filled else out
+
+
+def cand_rank_hist(F, ldf, E, cand, n_rows, rows_per_group=None, hist=None, bias=None, want_rank=False):
+    """score_rank's scores and ranks without the logit matrix, counted on the device: n_rows feature rows (F: any view whose first
+    element is row 0, row stride ldf), group-major -- row r is scored against candidate row r % rows_per_group of cand (rows_per_group, C)
+    int32, column 0 the held-out item -- and hist[r // rows_per_group][rank] += 1.  Returns hist (groups, C) int64: new zeros when `hist`
+    is None, otherwise `hist` itself, accumulated into; with want_rank also the (n_rows,) int32 ranks."""
+    if cand.dim() != 2 or cand.dtype != torch.int32 or not cand.is_contiguous():
+        raise _lib.AdtError("cand_rank_hist: cand must be a contiguous (rows_per_group, C) int32 tensor")
+    rpg = cand.shape[0] if rows_per_group is None else int(rows_per_group)
+    C, n_rows = cand.shape[1], int(n_rows)
+    if rpg < 1 or cand.shape[0] != rpg or n_rows % rpg != 0:
+        raise _lib.AdtError("cand_rank_hist: %d rows, %d candidate rows, rows_per_group=%d" % (n_rows, cand.shape[0], rpg))
+    if not E.is_contiguous() or (bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous())):
+        raise _lib.AdtError("cand_rank_hist: E and bias must be contiguous fp32")
+    groups = n_rows // rpg
+    if hist is None:
+        hist = torch.zeros(groups, C, device=E.device, dtype=torch.int64)
+    elif hist.dtype != torch.int64 or not hist.is_contiguous() or hist.numel() != groups * C:
+        raise _lib.AdtError("cand_rank_hist: hist must be contiguous int64 with %d x %d entries" % (groups, C))
+    rank = torch.empty(n_rows, device=E.device, dtype=torch.int32) if want_rank else None
+    _lib.check(_lib.load().adt_cand_rank_hist(_p(_f32(F)), int(ldf), _p(_f32(E)), _p(bias), _p(cand), n_rows, rpg, C, E.shape[1], _p(hist), _p(rank),
+                                              _stream()), "cand_rank_hist")
+    return (hist, rank) if want_rank else hist

@@ -7,7 +7,8 @@ get_lambdas() surface, best-by-valid-AUC selection, log/args files), with the tr
 
 Extra flags (not in the reference): --data_dir, --precision {bf16,f32}, --loop {fused,reference} (reference =
 the reference's own torch loss/backward/clip/Adam loop on the autograd-wired model), --synthetic PRESET
-(generate the seeded ml-1m-shaped file when the dataset is not shipped), --no_template, --frozen_eval.
+(generate the seeded ml-1m-shaped file when the dataset is not shipped), --no_template, --frozen_eval, --device_eval and
+--device_negatives (the sampled evaluation kept, built, scored and -- with the second flag -- drawn on the GPU).
 """
 import argparse
 import json
@@ -63,7 +64,19 @@ def parse_args(argv=None):
     p.add_argument("--frozen_eval", default=True, type=str2bool, help="draw evaluation negatives once (seed 23)")
     p.add_argument("--use_graph", default=True, type=str2bool)
     p.add_argument("--eval_full", default=False, type=str2bool, help="also rank the held-out item against the whole catalogue at every evaluation")
+    p.add_argument("--device_eval", default=False, type=str2bool,
+                   help="keep the evaluation data in HBM, build its batches on the device and score them with adt_cand_rank_hist (one "
+                        "histogram read per evaluation); the candidates are the host-drawn frozen sets, so the ranks are the host path's "
+                        "own; needs --frozen_eval true unless --device_negatives is set")
+    p.add_argument("--device_negatives", default=False, type=str2bool,
+                   help="draw the evaluation candidates on the device (adt_evalcand_draw; implies --device_eval): once at start-up, or at "
+                        "every evaluation with --frozen_eval false.  Same distribution as the reference's sampler, but a hash stream of "
+                        "its own: such a run is NOT the numpy run's trajectory")
     args = p.parse_args(argv)
+    if args.device_negatives:
+        args.device_eval = True
+    if args.device_eval and not args.device_negatives and not args.frozen_eval:
+        p.error("--device_eval uploads the frozen candidate sets: pass --frozen_eval true, or --device_negatives true to redraw on the device")
     if not args.no_template:
         args = U.set_template(args)          # sasrec/main.py:50: the template silently overrides the CLI
     if args.override:
@@ -109,8 +122,19 @@ def main(argv=None):
     user_train, user_valid, user_test, usernum, itemnum = U.data_partition(args.dataset, args.data_dir)
     sampler = U.PopularSampler(user_train, user_valid, user_test, usernum, itemnum, args.sample_size)
     warp = U.WarpDataset(user_train, usernum, itemnum, args.maxlen)
-    val_ds = U.EvalDataset(user_train, user_valid, user_test, usernum, itemnum, args.maxlen, sampler, "val", args.eval_set, args.frozen_eval)
-    test_ds = U.EvalDataset(user_train, user_valid, user_test, usernum, itemnum, args.maxlen, sampler, "test", args.eval_set, args.frozen_eval)
+    # with --device_negatives the host never draws: the EvalDatasets only carry the user lists (and the sequences --eval_full reads)
+    host_frozen = args.frozen_eval and not args.device_negatives
+    val_ds = U.EvalDataset(user_train, user_valid, user_test, usernum, itemnum, args.maxlen, sampler, "val", args.eval_set, host_frozen)
+    test_ds = U.EvalDataset(user_train, user_valid, user_test, usernum, itemnum, args.maxlen, sampler, "test", args.eval_set, host_frozen)
+    val_dev = test_dev = None
+    n_evals = 0
+    if args.device_eval:
+        from .device_eval import DeviceEvalData
+        val_dev = DeviceEvalData.from_dataset(val_ds, args.device, upload=not args.device_negatives)
+        test_dev = DeviceEvalData.from_dataset(test_ds, args.device, upload=not args.device_negatives)
+        if args.device_negatives and args.frozen_eval:      # one draw for the whole run; seeds 23 / 24 keep the two sets apart
+            val_dev.draw(23, 0)
+            test_dev.draw(24, 0)
 
     wide = args.hidden_units != 64     # the fused executor is 64-wide; other widths (the d = 256 template, the default 50) take the general kernels
     if wide:
@@ -194,8 +218,16 @@ def main(argv=None):
             torch.cuda.synchronize()
             T += time.time() - t0
             model.eval()
-            t_test, auc_test = U.evaluate_loader(model, test_ds.batches(args.eval_batch_size), args, "test", ks, process_group=pg)
-            t_valid, auc_valid = U.evaluate_loader(model, val_ds.batches(args.eval_batch_size), args, "val", ks, process_group=pg)
+            if args.device_eval:
+                if args.device_negatives and not args.frozen_eval:      # the reference redraws on every access: a new salt per evaluation
+                    n_evals += 1
+                    val_dev.draw(23, n_evals)
+                    test_dev.draw(24, n_evals)
+                t_test, auc_test = U.evaluate_device(model, test_dev, ks, args.eval_batch_size, process_group=pg)
+                t_valid, auc_valid = U.evaluate_device(model, val_dev, ks, args.eval_batch_size, process_group=pg)
+            else:
+                t_test, auc_test = U.evaluate_loader(model, test_ds.batches(args.eval_batch_size), args, "test", ks, process_group=pg)
+                t_valid, auc_valid = U.evaluate_loader(model, val_ds.batches(args.eval_batch_size), args, "val", ks, process_group=pg)
             if args.eval_full:     # the held-out item against ALL unseen items (adt_full_rank), beside the sampled-negative metrics
                 f_test, _ = U.evaluate_full(model, test_ds, "test", ks, args.eval_batch_size, process_group=pg)
                 f_valid, _ = U.evaluate_full(model, val_ds, "val", ks, args.eval_batch_size, process_group=pg)

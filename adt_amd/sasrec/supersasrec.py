@@ -423,13 +423,12 @@ class SuperSASRecModel(FlatModule):
         return (logits, rank) if want_rank else logits
 
     @torch.no_grad()
-    def predict_rank_candidates(self, log_seqs, item_indices, shared_list, stats=None):
-        """Ranks of the positive (column 0) under EVERY block choice of `shared_list` (get_shared output per candidate) in one pass:
-        (P, B).  Depth-0 layers are shared between candidates, deeper layers run once per distinct layer on the stacked inputs of
-        the candidates that select them (supersearch.candidate_features)."""
+    def _candidate_feature_rows(self, log_seqs, shared_list, stats=None):
+        """The encoder under EVERY block choice of `shared_list` (get_shared output per candidate) in one pass: the (P * B * L, d)
+        feature rows, stacked group-major, and (B, L).  Depth-0 layers are shared between candidates, deeper layers run once per
+        distinct layer on the stacked inputs of the candidates that select them (supersearch.candidate_features)."""
         seq = self.ids(log_seqs)
         B, L = seq.shape
-        d = self.hidden_units
         was = self.training
         self.eval()
         tp = Tape(self, self.prec, False)
@@ -455,8 +454,13 @@ class SuperSASRecModel(FlatModule):
             return (y,)
         feats = candidate_features(run_layer, (x0.t,), shared_list, self.num_layers, stats=stats)
         self.train(was)
-        P = len(shared_list)
-        F = feats[0][0] if P == 1 else torch.cat([f[0] for f in feats], 0)
+        return (feats[0][0] if len(shared_list) == 1 else torch.cat([f[0] for f in feats], 0)), B, L
+
+    @torch.no_grad()
+    def predict_rank_candidates(self, log_seqs, item_indices, shared_list, stats=None):
+        """Ranks of the positive (column 0) under every block choice of `shared_list` in one pass (_candidate_feature_rows): (P, B)."""
+        F, B, L = self._candidate_feature_rows(log_seqs, shared_list, stats)
+        P, d = len(shared_list), self.hidden_units
         full = item_indices is None
         cand = None if full else self.ids(item_indices)
         C = self.itemnum + 1 if full else cand.shape[1]
@@ -464,6 +468,14 @@ class SuperSASRecModel(FlatModule):
             cand = cand.repeat(P, 1)
         _, rank = ops.score_rank(F[L - 1:], L * d, self.P("item_emb.weight"), cand, P * B, C, True)
         return rank.view(P, B)
+
+    @torch.no_grad()
+    def rank_hist_candidates(self, log_seqs, cand, shared_list, hist, stats=None):
+        """predict_rank_candidates for the device-side evaluation: the same feature pass, then adt_cand_rank_hist on the stacked rows
+        with rows_per_group = B, so the (B, C) device int32 `cand` is read by every group and not repeated, and the ranks are counted
+        into hist (P, C) int64 (accumulated; returned) instead of being read back."""
+        F, B, L = self._candidate_feature_rows(log_seqs, shared_list, stats)
+        return ops.cand_rank_hist(F[L - 1:], L * self.hidden_units, self.P("item_emb.weight"), cand, len(shared_list) * B, B, hist=hist)
 
     def predict_rank(self, log_seqs, item_indices, want_rank=True):
         """(scores, rank of column 0) -- the interface adt_amd.sasrec.utils.evaluate_loader drives."""

@@ -355,6 +355,59 @@ def evaluate_loader(model, loader, args=None, mode="val", ks=(5, 10), process_gr
     return metrics_from_stats(reduce_rank_stats(rank_stats(ranks, ncand, ks), process_group), ks)
 
 
+# ---- sampled evaluation kept on the device (adt_amd/sasrec/device_eval.py; adt_cand_rank_hist) ------------------------------------------
+def metrics_from_hist(hist, n_candidates, ks=(5, 10)):
+    """metrics_from_ranks from the histogram of the ranks (hist[j] = number of users whose positive has rank j), in float64:
+    HR@k = sum(hist[:k]) / N, NDCG@k = sum(hist[j] / log2(j + 2), j < k) / N, AUC = sum(hist[j] * (S - (j + 1)) / (S - 1)) / N with the
+    same S = 1 + n_candidates.  HR is equal exactly; the two sums differ from metrics_from_ranks' by the order of addition only."""
+    hist = np.asarray(hist, np.int64).reshape(-1)
+    j = np.arange(len(hist), dtype=np.int64)
+    n = float(hist.sum())
+    ndcg, hr = {}, {}
+    for k in ks:
+        hr[k] = float(hist[:k].sum()) / n
+        ndcg[k] = float((hist[:k] / np.log2(j[:k] + 2.0)).sum()) / n
+    S = 1 + n_candidates
+    return (ndcg, hr), float((hist * ((S - (j + 1)) / (S - 1))).sum()) / n
+
+
+def evaluate_device(model, data, ks=(5, 10), batch_size=512, process_group=None, want_ranks=False):
+    """evaluate_loader over a DeviceEvalData -> ((NDCG, HT), AUC): every batch is built on the device (data.batch), encoded by the model's
+    own evaluation pass (_full_rank_operands: the last position's feature rows) and scored, ranked and counted by adt_cand_rank_hist
+    into one int64 histogram; the only device-to-host copy is the histogram, read once at the end.  With a process group, rank r takes
+    batches r, r + W, ... as evaluate_loader does and the histogram is sum-reduced: integers, so the result is exact.  want_ranks
+    (tests): also the int32 ranks of this process's rows, in row order, still on the device."""
+    import torch
+    from .. import ops
+    r, W = 0, 1
+    if process_group is not None:
+        import torch.distributed as dist
+        r, W = dist.get_rank(process_group), dist.get_world_size(process_group)
+    C = data.n_candidates
+    hist = torch.zeros(1, C, device=data.device, dtype=torch.int64)
+    ranks = []
+    for i, (lo, hi) in enumerate(data.batches(batch_size)):
+        if i % W != r:
+            continue
+        seq, cand = data.batch(lo, hi)
+        F, E, _, bias = model._full_rank_operands(seq)
+        out = ops.cand_rank_hist(F, F.stride(0), E, cand, hi - lo, hi - lo, hist=hist, bias=bias, want_rank=want_ranks)
+        if want_ranks:
+            ranks.append(out[1])
+    if W > 1:
+        import torch.distributed as dist
+        if dist.get_backend(process_group) == "nccl":
+            dist.all_reduce(hist, group=process_group)
+        else:
+            h = hist.cpu()
+            dist.all_reduce(h, group=process_group)
+            hist = h
+    res = metrics_from_hist(hist.cpu().numpy()[0], C, ks)
+    if want_ranks:
+        return res, (torch.cat(ranks) if ranks else torch.zeros(0, device=data.device, dtype=torch.int32))
+    return res
+
+
 # ---- full-catalogue evaluation (adt_full_rank: the rank of the held-out item among ALL unseen items) ----------------------------------
 def full_rank_stats(ranks, n_elig, ks=(5, 10)):
     """rank_stats for full-catalogue ranks: [N, sum((n_elig - rank) / n_elig), then per k: hits, sum 1/log2(rank+2)] as float64, where

@@ -421,6 +421,42 @@ int adt_bertbatch_token(uint32_t seed, uint32_t salt, int example, int pos, uint
 int adt_hit_hist(const int32_t* top_idx, int ld, int n_rows, int K, const int32_t* answers, int rows_per_group, int64_t* hist,
                  int32_t* hit_pos, void* stream);
 
+/* ---- SASRec-ADT evaluation candidates drawn on the device (adt_evalcand.cuh; sasrec/utils.py:57-69 get_negative_samples) --------------
+ * A user's sampled-evaluation candidates are the first S distinct values, outside the user's seen set, of an i.i.d. stream of ids drawn
+ * with probability proportional to count[id] -- the distribution of the reference's chunks of numpy.random.choice(replace = False, p).
+ * cum: exact integer prefix sums of count[0 .. n_ids - 1], n_ids + 1 int64 entries with cum[0] = 0 and total = cum[n_ids] in
+ * 1 .. 2^32 - 1.  Stream value n of GLOBAL row `row`: h = a chain of adt_hash32 over (seed, salt, row, n); u = (uint64_t)h * total >> 32
+ * (bias at most total / 2^32); the value is the id i with cum[i] <= u < cum[i + 1] (an id of count 0 is never drawn).  No floating
+ * point.
+ * adt_evalcand_stream (host only, like adt_seqbatch_draw; cum is a HOST table): out[i] = stream value n0 + i of `row`, i < n; the
+ * same inline function the kernel calls.  Errors: NULL cum, n_ids < 1, a total outside 1 .. 2^32 - 1, a negative index, NULL out.
+ * adt_evalcand_draw (device tables; `total` is the caller's copy of cum[n_ids]): rows row0 .. row0 + n_rows - 1 of the evaluation
+ * user list of n_total users.  seen_off (int64, n_total + 1) / seen_items: every user's SORTED seen ids as CSR; targets (n_total): the
+ * held-out items.  cand: (n_rows, 1 + S) int32 at row stride ldc; column 0 = targets[row], columns 1..S the accepted values in stream
+ * order.  A row depends on (seed, salt, GLOBAL row) alone: a shard draws what the whole call would.  Termination: after 4096 stream
+ * values the ids of non-zero count that are neither seen nor taken are filled in, walking upward from the last proposal, cyclically in
+ * [1, n_ids - 1] (n_ids - 1 steps in all); slots still open get id 0.  filled (n_rows, may be NULL) = the properly filled slots of
+ * each row (S unless the user has fewer than S drawable ids).
+ * Errors: the table errors above, S outside 1..1024, NULL seen_off / seen_items / targets, row0 + n_rows > n_total, ldc < 1 + S, NULL
+ * cand with n_rows > 0. */
+int adt_evalcand_stream(const int64_t* cum, int n_ids, uint32_t seed, uint32_t salt, int row, int n0, int n, int32_t* out);
+int adt_evalcand_draw(const int64_t* cum, int n_ids, int64_t total, const int64_t* seen_off, const int32_t* seen_items,
+                      const int32_t* targets, int n_total, int row0, int n_rows, int S, uint32_t seed, uint32_t salt, int32_t* cand,
+                      int ldc, int32_t* filled, void* stream);
+
+/* ---- sampled evaluation scored on the device (adt_candrank.cuh) -----------------------------------------------------------------------
+ * adt_score_rank's score and rank without the logit matrix, and the ranks counted where they are computed.  F: n_rows feature rows of
+ * width d at row stride ldf, group-major -- row r belongs to group r / rows_per_group and is scored against candidate row
+ * r % rows_per_group of cand, a contiguous (rows_per_group, C) int32 array of item ids (column 0 the held-out item); n_rows is a
+ * multiple of rows_per_group.  s_c = F[r] . E[cand[c]] (+ bias[cand[c]], bias may be NULL): the arithmetic of adt_score_rank, bit for
+ * bit (one shared inline function).  rank[r] (rank may be NULL) = #{c > 0 : s_c > s_0}, strict; hist[g][rank[r]] += 1 with hist
+ * (n_rows / rows_per_group, C) contiguous int64: the call ACCUMULATES, the caller supplies the zeros.  One integer atomic per row and
+ * no float atomics: the result does not depend on the order of execution.  n_rows = 0 is a no-op that looks at no pointer.
+ * Errors: C < 1, d not a positive multiple of 4, ldf < d or not a multiple of 4, rows_per_group < 1, n_rows % rows_per_group != 0, a
+ * NULL F, E, cand or hist, F or E not 16-byte aligned. */
+int adt_cand_rank_hist(const float* F, int ldf, const float* E, const float* bias, const int32_t* cand, int n_rows, int rows_per_group,
+                       int C, int d, int64_t* hist, int32_t* rank, void* stream);
+
 /* ==== model-level executor: SASRecADT (sasrec/model.py:8-97) + loop body (sasrec/main.py:146-173) ====== */
 typedef struct adt_sasrec_cfg {
   int32_t item_num;     /* V; item table has V+1 rows                      */
