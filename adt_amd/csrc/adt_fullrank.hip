@@ -4,6 +4,7 @@
 
 #include "adt_fullrank.cuh"
 #include "adt_wdist_pack.cuh"
+#include "adt_kldist_groups.cuh"
 
 using namespace adt;
 
@@ -86,6 +87,38 @@ int adt_wdist_pack(const float* M, const float* C, int ld, int rows, int d, int 
   WPackArgs a{M, C, ld, rows, d, elu != 0, img, ldi, nrm, nrm_scale};
   hipLaunchKernelGGL(k_wdist_pack, dim3(adt_grid_for((size_t)rows, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
   return adt_check_launch("wdist_pack");
+}
+
+int adt_kldist_pack(const float* Em, const float* Ec, int ld, int V, int d, float* img, int ldi, float* lv, void* stream) {
+  if (d < 4 || (d % 4)) return adt_set_error("kldist_pack: d=%d must be a positive multiple of 4", d);
+  if (ld < d || ldi < 2 * d) return adt_set_error("kldist_pack: ld=%d must be >= d=%d and ldi=%d >= 2d", ld, d, ldi);
+  if ((ld % 4) || (ldi % 4) || !adt_aligned16(Em) || !adt_aligned16(Ec) || !adt_aligned16(img))
+    return adt_set_error("kldist_pack: Em, Ec and img must be 16-byte aligned with ld %% 4 == 0 and ldi %% 4 == 0");
+  if (V <= 0) return 0;
+  if (!Em || !Ec || !img || !lv) return adt_set_error("kldist_pack: missing operand");
+  KlPackArgs a{Em, Ec, ld, V, d, img, ldi, lv};
+  hipLaunchKernelGGL(k_kldist_pack, dim3(adt_grid_for((size_t)V, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("kldist_pack");
+}
+
+int adt_kldist_full_groups(const float* Sm, const float* Sc, int lds, const float* img, int ldi, const float* lv, int rows, int E, int V, int d,
+                           float* dist, int ldo, void* stream) {
+  if (!Sm || !Sc || !img || !lv || !dist) return adt_set_error("kldist_full_groups: missing operand");
+  if (d < 4 || (d % 4)) return adt_set_error("kldist_full_groups: d=%d must be a positive multiple of 4", d);
+  if (E < 1) return adt_set_error("kldist_full_groups: E=%d < 1", E);
+  if (rows < 0 || rows % E) return adt_set_error("kldist_full_groups: rows=%d is not a multiple of E=%d", rows, E);
+  if (V < 0 || lds < d || ldi < 2 * d || ldo < V) return adt_set_error("kldist_full_groups: lds=%d must be >= d=%d, ldi=%d >= 2d, ldo=%d >= V=%d >= 0", lds, d, ldi, ldo, V);
+  if ((lds % 4) || (ldi % 4) || !adt_aligned16(Sm) || !adt_aligned16(Sc) || !adt_aligned16(img))
+    return adt_set_error("kldist_full_groups: Sm, Sc and img must be 16-byte aligned with lds %% 4 == 0 and ldi %% 4 == 0");
+  if ((int64_t)V + 2 * (int64_t)E + 32 > 0x7fffffff) return adt_set_error("kldist_full_groups: V=%d + 2 E=%d + 32 exceeds the item index range", V, E);
+  if (rows == 0 || V == 0) return 0;
+  const size_t smem = kldist_groups_lds_bytes(d);
+  if (smem > ADT_LDS_MAX) return adt_set_error("kldist_full_groups: d=%d needs %zu B of LDS (> 160 KB)", d, smem);
+  KlGroupsArgs a{Sm, Sc, lds, img, ldi, lv, rows, E, V, d, (E + 15) / 16, (V + E - 1) / E, dist, ldo};      // dist is indexed in size_t throughout
+  const size_t wgs = (size_t)(rows / E) * a.nch * a.nt;
+  if (wgs > 0x7fffffffu) return adt_set_error("kldist_full_groups: %zu workgroups (rows=%d, E=%d, V=%d) exceed the grid", wgs, rows, E, V);
+  static AdtLdsOptIn optin;      // smem follows d: the high-water mark in optin follows it
+  return adt_launch_lds1((const void*)k_kldist_full_groups, dim3((unsigned)wgs), dim3(256), smem, a, (hipStream_t)stream, "kldist_full_groups", optin);
 }
 
 }  // extern "C"

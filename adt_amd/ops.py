@@ -669,6 +669,29 @@ def wdist_pack(M, C, elu, nrm_scale):
     return img, nrm
 
 
+def kldist_pack(Em, Ec):
+    """The item image of the grouped KL full sort (adt_kldist_pack): img (V, 2d) = [Em | 1 / ci], lv (V,) = sum_c log ci, ci = ELU(Ec) + 1."""
+    assert Em.dim() == 2 and Em.shape == Ec.shape and Em.stride(0) == Ec.stride(0), (Em.shape, Ec.shape, Em.stride(), Ec.stride())
+    V, d = Em.shape
+    img = torch.empty(V, 2 * d, device=Em.device, dtype=torch.float32)
+    lv = torch.empty(V, device=Em.device, dtype=torch.float32)
+    _lib.check(_lib.load().adt_kldist_pack(_p(_f32(Em)), _p(_f32(Ec)), Em.stride(0), V, d, _p(img), 2 * d, _p(lv), _stream()), "kldist_pack")
+    return img, lv
+
+
+def kldist_full_groups(Sm, Sc, img, lv, E, V):
+    """kl_predict_full for the P = rows / E stacked eval batches of E users each (candidate-major rows of Sm / Sc) against the packed
+    items (kldist_pack): dist (rows, V).  The reference's chunking by E pairs the rows of one group only; rows == E is kldist_full to
+    fp32 rounding."""
+    assert Sm.dim() == 2 and Sm.shape == Sc.shape and Sm.stride(0) == Sc.stride(0), (Sm.shape, Sc.shape, Sm.stride(), Sc.stride())
+    rows, d = Sm.shape
+    assert img.shape[1] == 2 * d and img.shape[0] >= V and lv.numel() >= V, (img.shape, lv.shape, V, d)
+    dist = torch.empty(rows, V, device=Sm.device, dtype=torch.float32)
+    _lib.check(_lib.load().adt_kldist_full_groups(_p(_f32(Sm)), _p(_f32(Sc)), Sm.stride(0), _p(_f32(img)), img.stride(0), _p(_f32(lv)), rows, int(E),
+                                                  int(V), d, _p(dist), V, _stream()), "kldist_full_groups")
+    return dist
+
+
 # ---- STOSA-ADT batches built on the device (include/adt_hip.h: adt_seqbatch_build; adt_amd/csrc/adt_seqbatch.cuh) -----------------------
 def seqbatch_build(seq_off, seq_items, set_off, set_items, users, L, cut, item_size, seed=0, step=0, rows=None, want_neg=True,
                    want_inv_count=True, views=True):

@@ -38,8 +38,8 @@ def parse_args(argv=None):
     p.add_argument("--attention_dropout", type=float, default=0.5)
     p.add_argument("--dropout", type=float, default=0.5)
     p.add_argument("--initializer_range", type=float, default=0.02)
-    p.add_argument("--distance_metric", default="wasserstein", choices=["wasserstein"],
-                   help="the reference's default (stosa/main.py); its 'kl' variant (stosa/modules.py:52-70) is not built")
+    p.add_argument("--distance_metric", default="wasserstein", choices=["wasserstein", "kl"],
+                   help="attention / loss / full-sort distance (stosa/evolution.py:51): 'wasserstein' (the default) or 'kl' (stosa/modules.py:45-70)")
     p.add_argument("--kernel_param", type=float, default=1.0)
     p.add_argument("--warmup_epochs", default=200, type=int)
     p.add_argument("--search_epochs", default=50, type=int)
@@ -60,7 +60,10 @@ def parse_args(argv=None):
                         "stays on host batches")
     p.add_argument("--device_scores", action="store_true",
                    help="score candidates on the GPU: one histogram of hit positions per candidate (adt_hit_hist) instead of id lists on the host")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.fused_eval and args.distance_metric == "kl":
+        p.error("--fused_eval is built for --distance_metric wasserstein only: a KL score depends on the eval batch, not on (user, item) alone")
+    return args
 
 
 def main(argv=None):

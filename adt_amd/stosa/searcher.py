@@ -33,7 +33,7 @@ class SearcherEvolution:
         self.rec_choice = [0, 0.0001, 0.0005, 0.001, 0.005, 0.01]
         self.ind_choice = [0, 0.0001, 0.0005, 0.001, 0.005, 0.01]
         torch.manual_seed(args.seed)
-        self.model = DisenDistSASupernet(args, self.rec_choice, self.ind_choice)
+        self.model = DisenDistSASupernet(args, self.rec_choice, self.ind_choice, allow_kl=True)      # args.distance_metric: 'wasserstein' or 'kl'
         self.trainer = SuperStosaTrainer(self.model, lr=args.lr, betas=(args.adam_beta1, args.adam_beta2), weight_decay=args.weight_decay,
                                          seed=args.seed)
         self.search_state = EvolutionSearch(args.num_layers, self._evaluate_for_search, "MRR", args.select_num, args.population_num, args.m_prob,
@@ -108,10 +108,18 @@ class SearcherEvolution:
         the dataset's split ("valid" / "test"; `matrix` is not read: the resident rating matrix of that split is) and the stacked seen
         CSR is made on the device.  device_scores: the id lists stay on the GPU; every pass adds one group per stacked candidate to a
         (len(cands), 41) int64 histogram (ops.hit_hist), the fused / two-pass choice comes from the batch's min_unseen instead of a
-        read-back, and one copy after the last batch feeds scores_from_hist per candidate (kept as self.last_hists)."""
+        read-back, and one copy after the last batch feeds scores_from_hist per candidate (kept as self.last_hists).
+
+        distance_metric 'kl' (DESIGN.md section 19): the KL item image is packed once per call and every pass is one
+        adt_kldist_full_groups call with E = the batch's rows (the trailing batch has its own E); fused=True is an AdtError."""
         device_batches = bool(getattr(self.args, "device_batches", False)) if device_batches is None else device_batches
         device_scores = bool(getattr(self.args, "device_scores", False)) if device_scores is None else device_scores
+        kl = self.model.distance_metric == "kl"
+        if fused and kl:
+            raise AdtError("evaluate_candidates(fused=True): the fused ranking is built for distance_metric='wasserstein' only; 'kl' scores "
+                           "through the distance matrix (adt_kldist_full_groups)")
         image = self.model.item_image() if fused else None
+        kl_image = self.model.kl_item_image() if kl else None      # the candidates share the item tables: packed once per call
         ds = self.valid_ds if dataset is None else dataset
         matrix = self.valid_matrix if matrix is None else matrix
         dev = self.model.dev
@@ -132,7 +140,7 @@ class SearcherEvolution:
                 indptr, indices = st["stack"](len(sl))
 
                 def two_pass_device():
-                    dist = self.model.predict_full_candidates(inp, sl, stats=self.eval_stats)
+                    dist = self.model.predict_full_candidates(inp, sl, stats=self.eval_stats, image=kl_image)
                     return ops.topk_masked(dist, 40, indptr, indices)
 
                 def fused_device():

@@ -29,11 +29,13 @@ def _cand_sites(sites, k):
 
 
 class DisenDistSASupernet(DisenDistSAModel):
-    def __init__(self, args, rec_choice, ind_choice):
-        if getattr(args, "distance_metric", "wasserstein") != "wasserstein":
-            # the supernet's loss and full-sort paths call the Wasserstein kernels directly: refuse rather than mix the metrics
-            raise _lib.AdtError("DisenDistSASupernet (adt_amd): only distance_metric='wasserstein' is built for the supernet, got %r"
-                                % (args.distance_metric,))
+    def __init__(self, args, rec_choice, ind_choice, allow_kl=False):
+        """allow_kl: distance_metric='kl' is opt-in (SearcherEvolution passes True).  Without it the constructor refuses anything but
+        'wasserstein', as it always has; with it 'kl' runs the KL attention, the KL warm-up loss and the grouped KL full sort (DESIGN.md
+        section 19), and any other string still raises in the base class."""
+        if getattr(args, "distance_metric", "wasserstein") != "wasserstein" and not allow_kl:
+            raise _lib.AdtError("DisenDistSASupernet (adt_amd): only distance_metric='wasserstein' is built for the supernet unless allow_kl=True "
+                                "is passed, got %r" % (args.distance_metric,))
         self.rec_choice, self.ind_choice = np.asarray(rec_choice, np.float64), np.asarray(ind_choice, np.float64)
         self.block = len(self.rec_choice) * len(self.ind_choice)
         super().__init__(args, block=self.block, dec_layernorm=False)     # init_weights is the plain model's (supernet.py:101-111)
@@ -110,17 +112,31 @@ class DisenDistSASupernet(DisenDistSAModel):
         return ops.gather_rows(M, rows), ops.gather_rows(C, rows)
 
     @torch.no_grad()
-    def predict_full_candidates(self, input_ids, shared_list, stats=None):
-        """Full-sort Wasserstein distances of the last state to every item under EVERY block choice of `shared_list`: (P * B, item_size),
-        candidate-major (the feature pass of _last_state_candidates, then adt_wdist_full)."""
+    def kl_item_image(self):
+        """(img (item_size, 2d), lv (item_size,)) of the two item tables for the grouped KL full sort (ops.kldist_pack).  Packed on every
+        call, like item_image(): no cache, it is stale after any weight update; a caller that scores many passes under the same weights
+        holds on to it and passes it as `image`."""
+        return ops.kldist_pack(self.P("item_mean_embeddings.weight"), self.P("item_cov_embeddings.weight"))
+
+    @torch.no_grad()
+    def predict_full_candidates(self, input_ids, shared_list, stats=None, image=None):
+        """Full-sort distances of the last state to every item under EVERY block choice of `shared_list`: (P * B, item_size),
+        candidate-major (the feature pass of _last_state_candidates, then adt_wdist_full).  distance_metric 'kl': kl_predict_full per
+        candidate with the B rows of this call as the eval batch (adt_kldist_full_groups with E = B: the chunking never pairs rows of two
+        candidates); image: kl_item_image() of the current weights, packed here when None.  The Wasserstein path takes no image."""
         sm, sc = self._last_state_candidates(input_ids, shared_list, stats)
+        if self.distance_metric == "kl":
+            img, lv = self.kl_item_image() if image is None else image
+            return ops.kldist_full_groups(sm, sc, img, lv, sm.shape[0] // len(shared_list), self.item_size)
         return ops.wdist_full(sm, sc, self.P("item_mean_embeddings.weight"), self.P("item_cov_embeddings.weight"), self.item_size)
 
     @torch.no_grad()
     def rank_full_candidates(self, input_ids, shared_list, targets=None, seen=None, topk=0, image=None, stats=None, first_id=1):
         """DistRankMixin.rank_full under every block choice of `shared_list` with ONE fused call on the stacked P * B last states:
         (rank, n_elig, top_idx, top_dist) with P * B rows, candidate-major.  targets: (B,) (repeated per candidate), (P * B,) or None;
-        seen: the CSR of the P * B stacked rows (any form ops.seen_csr takes, or a device (indptr, indices) pair); image: item_image()."""
+        seen: the CSR of the P * B stacked rows (any form ops.seen_csr takes, or a device (indptr, indices) pair); image: item_image().
+        Wasserstein only (DistRankMixin._check_wasserstein): a KL score is not a function of (user, item) alone."""
+        self._check_wasserstein()
         sm, sc = self._last_state_candidates(input_ids, shared_list, stats)
         PB = sm.shape[0]
         if targets is not None:

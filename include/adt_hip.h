@@ -347,6 +347,19 @@ int adt_full_rank_from(const float* F, int ldf, const float* E, int lde, const f
  * d % 4 == 0, ld >= d, ldi >= 2d, both multiples of 4, M / C / img 16-byte aligned.  Bit-reproducible (fixed reduction order). */
 int adt_wdist_pack(const float* M, const float* C, int ld, int rows, int d, int elu, float* img, int ldi, float* nrm, float nrm_scale,
                    void* stream);
+/* kl_predict_full for P stacked groups of E users on a packed item image (adt_kldist_groups.cuh).  adt_kldist_pack, once per evaluation:
+ * img[v][0..d) = Em[v], img[v][d..2d) = 1 / ci_v, lv[v] = sum_c logf(ci_v[c]) with ci = ELU(Ec) + 1; d % 4 == 0, ld >= d, ldi >= 2d, both
+ * multiples of 4, Em / Ec / img 16-byte aligned.  Bit-reproducible (fixed reduction order). */
+int adt_kldist_pack(const float* Em, const float* Ec, int ld, int V, int d, float* img, int ldi, float* lv, void* stream);
+/* rows = P * E state rows, candidate-major: row r is user u = r % E of group g = r / E, and the reference's chunking by E items pairs rows
+ * of ONE group only.  For item v = cE + j and a = cE + u (a >= V: a padding item, zero mean and unit covariance)
+ *   dist[r][v] = 0.5 (lv[v] - sum_c logf(Sc[r][c]) + sum_c (Sm[gE + u][c] - img[a][c])^2 img[v][d + c] + sum_c Sc[gE + j][c] img[a][d + c] - d)
+ * in exact fp32 (v_mfma_f32_16x16x4_f32); with rows == E the function adt_kldist_full computes, to fp32 rounding (a product by the packed
+ * reciprocal replaces the division).  No atomics; the output does not depend on the order of execution.  Errors: a NULL operand, E < 1,
+ * rows % E != 0, d % 4 != 0, lds < d, ldi < 2d, ldo < V, lds or ldi not a multiple of 4, Sm / Sc / img not 16-byte aligned,
+ * V + 2E + 32 >= 2^31.  rows * V may exceed 2^31: dist is indexed in size_t. */
+int adt_kldist_full_groups(const float* Sm, const float* Sc, int lds, const float* img, int ldi, const float* lv, int rows, int E, int V,
+                           int d, float* dist, int ldo, void* stream);
 
 /* ---- STOSA-ADT batches built on the device (adt_seqbatch.cuh; stosa/datasets.py:202-300, utils.py:32-36 neg_sample) -----------------
  * Resident inputs: the user sequences as CSR (seq_off int64 (U + 1), seq_items int32, ids >= 1) and every user's sorted, de-duplicated

@@ -11,7 +11,15 @@ line per shape (ml-1m: V 3,416, d 64; ml-20m: V 26,744, d 256; B 512, K 10, 100 
 STOSA-ADT (Wasserstein) at the Beauty shape: item_size 12,103, d 64 (image width 128), B 512 (stosa/main.py's eval_batch_size; the
 template does not override it), K 40, 100 seen items per user, item 0 competing (first_id = 0, as full_sort(fused=True) runs it).
 Same timing scheme; one JSON line for one model (P = 1) and one for P = 8 stacked candidates: (a) two_pass = adt_wdist_full +
-adt_topk_masked, (b) fused = the user-state pack + adt_full_rank_from with a pre-packed item image, (c) pack = the item pack alone."""
+adt_topk_masked, (b) fused = the user-state pack + adt_full_rank_from with a pre-packed item image, (c) pack = the item pack alone.
+
+  python tools/bench_fullrank.py --stosa --metric kl [--out profiles/r18_stosa_kl_full.jsonl]
+
+STOSA-ADT (KL) full-sort distances at the same shape, E = B = 512, one line for P = 1 and one for P = 8 stacked candidates: (a) loop =
+P adt_kldist_full calls, one per candidate (the only correct route without the group rule), (b) groups = one adt_kldist_full_groups
+call on a pre-packed image, (c) pack = adt_kldist_pack alone.  Inputs have trained magnitudes (tables 0.3 N(0, 1), covariances
+exp(0.2 N(0, 1))).  The forms ALTERNATE inside every repetition (loop, groups, pack, loop, ...), so a drift of the clocks falls on
+all of them alike; 3 warm-up rounds, 5 timed ones."""
 import argparse
 import json
 import os
@@ -40,6 +48,54 @@ def timed(fn):
         b.synchronize()
         ms.append(a.elapsed_time(b))
     return {"median_ms": float(np.median(ms)), "min_ms": float(min(ms)), "max_ms": float(max(ms))}
+
+
+def timed_alternating(fns):
+    """{name: stats} of the callables of `fns`, one call of each per round, in the given order: WARMUP rounds, then REPS timed ones."""
+    for _ in range(WARMUP):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in fns}
+    for _ in range(REPS):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ms[k].append(a.elapsed_time(b))
+    return {k: {"median_ms": float(np.median(v)), "min_ms": float(min(v)), "max_ms": float(max(v))} for k, v in ms.items()}
+
+
+def stosa_kl_lines(dev):
+    V, d, E = 12103, 64, B
+    lines = []
+    for P in (1, 8):
+        rows = P * E
+        g = torch.Generator(device="cpu").manual_seed(V + P)
+        Em, Ec = (0.3 * torch.randn(V, d, generator=g)).to(dev), (0.3 * torch.randn(V, d, generator=g)).to(dev)
+        sm, sc = (0.3 * torch.randn(rows, d, generator=g)).to(dev), torch.exp(0.2 * torch.randn(rows, d, generator=g)).to(dev)
+        image = ops.kldist_pack(Em, Ec)
+
+        def loop():
+            return [ops.kldist_full(sm[k * E:(k + 1) * E], sc[k * E:(k + 1) * E], Em, Ec, V) for k in range(P)]
+
+        def groups():
+            return ops.kldist_full_groups(sm, sc, image[0], image[1], E, V)
+
+        a, b = torch.cat(loop()), groups()
+        agree = float((a - b).abs().max() / a.abs().max())
+        del a, b
+        rec = {"shape": "stosa-beauty", "metric": "kl", "V": V, "d": d, "E": E, "candidates": P, "max_diff_over_max": agree}
+        rec.update(timed_alternating({"loop": loop, "groups": groups, "pack": lambda: ops.kldist_pack(Em, Ec)}))
+        rec["hbm_bytes_dist"] = rows * V * 4
+        rec["groups_over_loop"] = rec["groups"]["median_ms"] / rec["loop"]["median_ms"]
+        spread = max(rec[k]["max_ms"] - rec[k]["min_ms"] for k in ("loop", "groups"))
+        rec["accepted"] = bool(rec["groups"]["median_ms"] <= rec["loop"]["median_ms"] + spread)      # not above the loop by more than the larger spread
+        print(json.dumps(rec), flush=True)
+        lines.append(json.dumps(rec))
+    return lines
 
 
 def stosa_lines(dev):
@@ -81,12 +137,16 @@ def stosa_lines(dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--stosa", action="store_true", help="the STOSA-ADT (Wasserstein) Beauty shape instead of the dot-product shapes")
+    ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl"], help="with --stosa: kl = the grouped KL full sort against P adt_kldist_full calls")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    kl = args.stosa and args.metric == "kl"
+    if args.metric == "kl" and not args.stosa:
+        ap.error("--metric kl goes with --stosa")
     if args.out is None:
-        args.out = os.path.join("profiles", "r08_stosa_fullrank.jsonl" if args.stosa else "r07_fullrank_bench.jsonl")
+        args.out = os.path.join("profiles", "r18_stosa_kl_full.jsonl" if kl else "r08_stosa_fullrank.jsonl" if args.stosa else "r07_fullrank_bench.jsonl")
     dev = "cuda:0"
-    lines = stosa_lines(dev) if args.stosa else []
+    lines = stosa_kl_lines(dev) if kl else stosa_lines(dev) if args.stosa else []
     for name, V, d in (() if args.stosa else SHAPES):
         g = torch.Generator(device="cpu").manual_seed(V)
         F = torch.randn(B, d, generator=g).to(dev)

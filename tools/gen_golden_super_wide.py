@@ -6,7 +6,7 @@ super_modules.py) in the build container.  Fixtures are data only: seeded inputs
 (bert4rec/evolution.py:266-296; stosa/super_trainer.py:205-235 with bpr_optimization :30-62) driven with the same torch calls;
 dropout is 0.
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_super_wide.py [bert] [stosa]
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_super_wide.py [bert] [stosa] [stosa_kl]
 """
 import os
 import sys
@@ -23,7 +23,7 @@ import torch.nn.functional as F  # noqa: E402
 
 from adt_amd.supersearch import cand_to_block  # noqa: E402  (host arithmetic only; checked against the reference's shared_idx below)
 from tools.gen_golden_inputs import compact, seeded_params  # noqa: E402
-from tools.gen_golden_stosa import stosa_batch  # noqa: E402
+from tools.gen_golden_stosa import kl_predict_full, stosa_batch  # noqa: E402
 from tools.gen_golden_wide import _import_from, bert_batch  # noqa: E402
 
 OUT = os.path.join(REPO, "tests", "golden")
@@ -110,14 +110,17 @@ def gen_bert(tag, item_num, L, d, H, nl, rec_choice, ind_choice, B, seed, cand, 
 _STOSA = []
 
 
-def gen_stosa(tag, item_size, L, d, H, nl, rec_choice, ind_choice, B, seed, cand, pvn_weight=0.05, lr=1e-3):
+def gen_stosa(tag, item_size, L, d, H, nl, rec_choice, ind_choice, B, seed, cand, pvn_weight=0.05, lr=1e-3, metric="wasserstein"):
+    """metric "kl": distance_metric='kl' (KL attention, kl_distance in the loss) and full_dist / full_dist2 through kl_predict_full's padded
+    chunking with the batch as E (tools/gen_golden_stosa.kl_predict_full); written as superstosa_kl_<tag>.npz."""
+    kl = metric == "kl"
     if not _STOSA:
         _STOSA.append(_import_from("/root/reference/stosa", "supernet"))
         _STOSA.append(sys.modules["modules"])
     sn, modules = _STOSA
     a = Args()
     a.item_size, a.hidden_units, a.maxlen, a.num_users, a.dropout, a.attention_dropout = item_size, d, L, 3, 0.0, 0.0
-    a.num_heads, a.num_layers, a.hidden_act, a.initializer_range, a.distance_metric, a.kernel_param = H, nl, "gelu", 0.02, "wasserstein", 1.0
+    a.num_heads, a.num_layers, a.hidden_act, a.initializer_range, a.distance_metric, a.kernel_param = H, nl, "gelu", 0.02, metric, 1.0
     a.cuda_condition, a.pvn_weight = False, pvn_weight
     m = sn.DisenDistSASupernet(a, np.array(rec_choice), np.array(ind_choice))
     P = seeded_params({k: tuple(v.shape) for k, v in m.state_dict().items()}, seed)
@@ -140,8 +143,12 @@ def gen_stosa(tag, item_size, L, d, H, nl, rec_choice, ind_choice, B, seed, cand
             out["enc_in_mean_%d" % i], out["enc_in_cov_%d" % i] = enc_in[i][0].numpy(), enc_in[i][1].numpy()
             out["rec_mean_%d" % i], out["rec_cov_%d" % i] = enc_rec[i][0].numpy(), enc_rec[i][1].numpy()
             out["dec_out_mean_%d" % i], out["dec_out_cov_%d" % i] = dec_out[i][0].numpy(), dec_out[i][1].numpy()
-        full = lambda mo_, co_: modules.wasserstein_distance_matmul(mo_[:, -1, :], co_[:, -1, :], m.item_mean_embeddings.weight,
-                                                                    elu(m.item_cov_embeddings.weight) + 1).numpy()
+        if kl:
+            full = lambda mo_, co_: kl_predict_full(modules, mo_[:, -1, :], co_[:, -1, :], m.item_mean_embeddings.weight,
+                                                    elu(m.item_cov_embeddings.weight) + 1).numpy()
+        else:
+            full = lambda mo_, co_: modules.wasserstein_distance_matmul(mo_[:, -1, :], co_[:, -1, :], m.item_mean_embeddings.weight,
+                                                                        elu(m.item_cov_embeddings.weight) + 1).numpy()
         out["full_dist"] = full(mo, co)
         cand2 = [1.0 - c for c in cand]
         m.set_choice(cand_to_block(rec_choice, ind_choice, cand2)[0])
@@ -150,7 +157,7 @@ def gen_stosa(tag, item_size, L, d, H, nl, rec_choice, ind_choice, B, seed, cand
         m.set_choice(block)
     m.train()
     opt = torch.optim.Adam(m.parameters(), lr=lr, betas=(0.9, 0.999), weight_decay=0.0)
-    wdist = modules.wasserstein_distance
+    wdist = modules.kl_distance if kl else modules.wasserstein_distance
     for step in range(2):
         mo, co, att, margins, enc_in, enc_rec, dec_out = m.finetune(t[0], t[1], uid)
         pos_mean, neg_mean = m.item_mean_embeddings(t[2]), m.item_mean_embeddings(t[3])
@@ -175,6 +182,7 @@ def gen_stosa(tag, item_size, L, d, H, nl, rec_choice, ind_choice, B, seed, cand
         loss.backward()
         if step == 0:
             out["loss"] = float(loss.item())
+            assert np.isfinite(out["loss"]), (tag, metric, out["loss"])
             _grads(m, out)
             out["grad_norm"] = float(torch.sqrt(sum((p.grad ** 2).sum() for p in m.parameters() if p.grad is not None)))
         opt.step()
@@ -182,7 +190,7 @@ def gen_stosa(tag, item_size, L, d, H, nl, rec_choice, ind_choice, B, seed, cand
             used = [k for k, p in m.named_parameters() if p.grad is not None]
             for k in used[:30]:
                 out["w1." + k] = dict(m.named_parameters())[k].detach().numpy().copy()
-    path = os.path.join(OUT, "superstosa_%s.npz" % tag)
+    path = os.path.join(OUT, ("superstosa_kl_%s.npz" if kl else "superstosa_%s.npz") % tag)
     np.savez_compressed(path, **compact(out, keep=("full_dist", "full_dist2"), k=96, thresh=600))
     print("wrote", path, "loss", out["loss"], "none", len(out["grad_none"]), "%.1f KB" % (os.path.getsize(path) / 1024))
 
@@ -195,3 +203,6 @@ if __name__ == "__main__":
     if "stosa" in which:
         gen_stosa("c3", 42, 12, 64, 4, 1, [0, 0.001, 0.01], [0, 0.001, 0.01], B=3, seed=51, cand=[0.7, 0.2])
         gen_stosa("l2", 33, 10, 64, 2, 2, [0, 0.01], [0, 0.01], B=2, seed=52, cand=[0.3, 0.9, 0.6, 0.4])
+    if "stosa_kl" in which:      # the same shapes and seeds; B divides neither item_size
+        gen_stosa("c3", 42, 12, 64, 4, 1, [0, 0.001, 0.01], [0, 0.001, 0.01], B=3, seed=51, cand=[0.7, 0.2], metric="kl")
+        gen_stosa("l2", 33, 10, 64, 2, 2, [0, 0.01], [0, 0.01], B=2, seed=52, cand=[0.3, 0.9, 0.6, 0.4], metric="kl")
