@@ -124,6 +124,7 @@ def attn_oracle(q, k, v, B, H, L, key_valid, causal, fill, p, seed, site, b_off,
                                               (2, 2, 200, 64, False, 0.0), (3, 2, 20, 32, True, 0.1), (2, 1, 128, 64, False, 0.0),
                                               (3, 4, 200, 64, False, 0.2), (2, 2, 160, 64, True, 0.1)])
 def test_masked_attention(prec, B, H, L, hd, causal, p):
+    """Every instantiation, mask mode and edge of L, the scaled entry points and the out= path: tests/test_attn_branches_hip.py."""
     from adt_amd import ops
     # (fp32, hd=64, L=200): the whole-(b, h) fp32 images of the backward (248 KB) exceed the LDS; it runs chunked (adt_wide.hip)
     r = np.random.RandomState(B * 1000 + L + hd)
