@@ -239,12 +239,21 @@ static __global__ __launch_bounds__(256) void k_zero_rows_f32(float* p, size_t l
   const size_t n = rows * (size_t)cols;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[(i / cols) * ld + (i % cols)] = 0.f;
 }
-static inline int zero_rows_f32_async(float* p, size_t ld, int cols, size_t rows, hipStream_t s) {
+// rows_dev: a DEVICE row count that caps `rows` (the t_dev of the dense layers): rows at or beyond it are not written
+static __global__ __launch_bounds__(256) void k_zero_rows_dev_f32(float* p, size_t ld, int cols, size_t rows, const int* rows_dev) {
+  const int lim = *rows_dev;
+  if (lim <= 0) return;
+  if ((size_t)lim < rows) rows = (size_t)lim;
+  const size_t n = rows * (size_t)cols;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[(i / cols) * ld + (i % cols)] = 0.f;
+}
+static inline int zero_rows_f32_async(float* p, size_t ld, int cols, size_t rows, hipStream_t s, const int* rows_dev = nullptr) {
   const size_t n = rows * (size_t)cols;
   if (n == 0) return 0;
   size_t blocks = (n + 1023) / 1024;
   if (blocks > 2048) blocks = 2048;
-  if (ld == (size_t)cols) hipLaunchKernelGGL(k_zero_f32, dim3((unsigned)blocks), dim3(256), 0, s, p, n);
+  if (rows_dev) hipLaunchKernelGGL(k_zero_rows_dev_f32, dim3((unsigned)blocks), dim3(256), 0, s, p, ld, cols, rows, rows_dev);
+  else if (ld == (size_t)cols) hipLaunchKernelGGL(k_zero_f32, dim3((unsigned)blocks), dim3(256), 0, s, p, n);
   else hipLaunchKernelGGL(k_zero_rows_f32, dim3((unsigned)blocks), dim3(256), 0, s, p, ld, cols, rows);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -342,7 +342,8 @@ struct DenseFwdArgs {
   const float* R2; int ldr2;  // optional second residual (sasrec decoder: dec_input + (x + ffn(x)), modules.py:672-673)
   const int* ids;             // optional row mask
   const int* t_dev;           // optional DEVICE row count: only rows < min(T, *t_dev) are computed (masked-row batches
-                              // whose size changes per step under a captured graph)
+                              // whose size changes per step under a captured graph); rows at or beyond it are left as they
+                              // were by every arm, the zero fill ahead of the split input gradient included
 };
 
 template <int PREC, int BN>
@@ -430,7 +431,7 @@ __global__ __launch_bounds__(GTH) void k_dense_bwd_dx(DenseBwdArgs a) {
   const int kend = a.nt_z > 1 ? (kbeg + a.n_chunk < kall ? kbeg + a.n_chunk : kall) : kall;
   if (kbeg >= kend) return;
   gemm_core<PREC, BN, false, true, GradSrc, PlainSrc, false>(acc, G, Bw, m0, n0, kbeg, kend, sA, sB, dummy);
-  const bool split = a.nt_z > 1;     // long contraction (all-item logits): the host zeroes dX first unless beta
+  const bool split = a.nt_z > 1;     // long contraction (all-item logits): unless beta, a launch ahead of this one zeroes the rows below min(T, *t_dev)
   constexpr int NE = GemmAcc<PREC, BN>::NE;
   acc.foreach_tile(m0, n0, [&](const int (&rows)[NE], int col, const float (&vals)[NE]) {
     if (col >= a.K) return;

@@ -364,7 +364,9 @@ static DenseBwdArgs dense_dx_tiled_args(const DenseBwdPlan& p, const DenseBwdArg
 
 template <int PREC>
 static int launch_dense_dx_tiled(const DenseBwdPlan& p, const DenseBwdArgs& a, hipStream_t s) {
-  if (p.dx_zero_fill && adt::zero_rows_f32_async(a.dX, (size_t)a.lddx, a.K, (size_t)a.G.T, s)) return adt_set_error("dense_bwd: zero");
+  // The splits add their partials with atomics in no order, so none of them can do the clearing: a launch ahead of them does, and it stops at
+  // *t_dev like every other arm (rows at or beyond it stay untouched, DenseFwdArgs::t_dev).
+  if (p.dx_zero_fill && adt::zero_rows_f32_async(a.dX, (size_t)a.lddx, a.K, (size_t)a.G.T, s, a.t_dev)) return adt_set_error("dense_bwd: zero");
   static AdtLdsOptIn optin[2];
   if (p.dx_bn == 128) return adt_launch_lds1((const void*)k_dense_bwd_dx<PREC, 128>, dim3(p.dx_grid_x), dim3(p.dx_block), p.dx_lds_bytes, a, s, "dense_bwd_dx", optin[0]);
   return adt_launch_lds1((const void*)k_dense_bwd_dx<PREC, 64>, dim3(p.dx_grid_x), dim3(p.dx_block), p.dx_lds_bytes, a, s, "dense_bwd_dx", optin[1]);

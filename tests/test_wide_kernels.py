@@ -44,6 +44,8 @@ def seed_tensor(seed):
                                               (260, 256, 1024, 2, 0.2, False), (300, 1024, 256, 0, 0.2, True), (130, 256, 512, 0, 0.0, False),
                                               (150, 256, 768, 0, 0.0, False), (97, 512, 768, 0, 0.2, True)])      # packed in-projections: contraction 768 in the input gradient   # 256 x 256: private partials      # 64 x 64: the stage kernel of the weight gradient (k_dense_dw64)
 def test_dense_forward_backward(prec, T, K, N, act, p, resid):
+    """Every arm of the dispatch in one stage and in several, every epilogue, unaligned operands, no workspace, elementwise against float64:
+    tests/test_dense_arms_hip.py."""
     from adt_amd import ops
     r = np.random.RandomState(T + K + N)
     X = r.standard_normal((T, K)).astype(np.float32)
