@@ -25,6 +25,10 @@ struct AttnArgs {
   int out_bf16;               // backward, adt_seqattn.cuh only: dQ, dK, dV are written as bf16 rows in the saved-row order (adt_tt.cuh: tt_store_bf16), lddq /
                               // lddk / lddv count bf16 elements -- for a consumer that only builds bf16 MFMA operands from them (k_seqtt_mid_bwd): the same
                               // values it would have rounded itself, half the bytes
+  const void* do_bf16; const float* do_delta;
+                              // backward, adt_seqattn.cuh with in_bf16 only: do_bf16 != nullptr: the out-projection reverse in front (k_seqtt_post_bwd<DEC>,
+                              // BwdChainArgs::do_bf16) handed dO over as bf16 rows of dO * drop.scale in the saved-row order (64 elements per row) and
+                              // delta[h] = rowsum(dO . O) of head h at do_delta[row * 4 + h]: dO and O are not read
 };
 
 }  // namespace adt

@@ -50,6 +50,12 @@ struct BwdChainArgs {
                               // rows lnl_x and weight lnl_gamma: the LayerNorm is reversed per tile in front of the chain, its dgamma | dbeta
                               // sums of this workgroup are stored at vpart2 + blockIdx * 512 (128 floats), or (vpart2 == nullptr) added to
                               // lnl_dgamma / lnl_dbeta (replicas like dgamma / dbeta) with float atomics
+  void* do_bf16; float* do_delta; float do_scale; int do_hd;
+                              // adt_seqpost_tt.cuh, hand-over of dO to the attention backward behind this chain (adt_tt.cuh: tt_head_delta).
+                              // do_bf16 != nullptr: k_seqtt_post_bwd (ENC: instead of out1 ; DEC: instead of out0) and k_seqtt_mid_bwd (instead
+                              // of out0) store bf16(dO * do_scale) rows there in the saved-row order, do_scale = the consumer's drop.scale, and
+                              // delta[h] = rowsum(dO . o) of head h (do_hd: head size) at do_delta[row * 4 + h], summed in the consumer's
+                              // order (the cross-attention's behind k_seqtt_post_bwd<DEC>).  nullptr: the fp32 store
   int nsplit;                 // adt_seqpost_tt.cuh: S > 1 workgroups per sequence (adt_seq_args.h): workgroup (blockIdx / S, blockIdx % S) runs the token
                               // chains of the tiles t with t % S == part; its weight-gradient partial (slot blockIdx) covers those tokens only
 };

@@ -77,6 +77,7 @@ struct WS {
   int64_t wpack;                                                        // pre-packed bf16 weight images (3 floats per parameter float)
   int64_t part, part_stride;                                            // per-sequence partials of the 64 x 64 weight gradients (bf16 mode, d = 64)
   int64_t isort, isort_n;                                               // scratch of the sorted item-table gradient (adt_item_sort), isort_n int32 (0: not used)
+  int64_t dodelta;                                                      // delta[T][4] of the dO hand-over (StepPlan::do_handover; adt_tt.cuh: tt_head_delta)
   int64_t vpart, vcall, lnpart, gnpart;                                 // per-workgroup bias / LayerNorm / classifier gradient sums: 5 * nl calls x vcall floats ;
                                                                         // the last LayerNorm's per-block sums ; per-block partials of ||g||^2
   int64_t total;
@@ -127,6 +128,7 @@ void make_ws(const adt_sasrec_cfg* c, int B, const StepPlan& pl, WS* w) {
   w->vpart = take(w->part_stride > 0 ? (5 * w->nl + 1) * w->vcall : 0);      // (+ 1: the last LayerNorm's sums from the first encoder kernel of the backward)
   w->lnpart = take(LN_PART_BLOCKS * 128);
   w->gnpart = take(4096);
+  w->dodelta = take(pl.do_handover ? up64(w->T * 4) : 0);
   w->total = o;
 }
 
@@ -534,6 +536,14 @@ struct Bwd {
   // (Gq + lo.xxx() addresses replica 0); each phase folds its range into G at its end
   float* Gq;
   float *s1, *s3, *s4, *s5, *gf;      // scratch ; d log_feats
+  // StepPlan::do_handover: every out-projection reverse hands dO to the attention backward behind it as bf16 rows of dO * drop.scale + delta
+  // (adt_bwdchain_args.h: do_bf16).  The cross-attention's dO2 rows live in the first half of s1; the self-attention blocks' rows in s3, which
+  // only the staged kernels use (never on this path): the launch that reads dO2 writes dO1, and the two do not share a buffer.  One delta area
+  // serves both: a sequence's dO2 delta is consumed by the prologue of the launch whose mid chain later writes its dO1 delta.
+  void* do_rows() const { return sp.do_handover ? (void*)s3 : nullptr; }
+  void* do_rows_cross() const { return sp.do_handover ? (void*)s1 : nullptr; }
+  float* do_delta() const { return sp.do_handover ? ws + w.dodelta : nullptr; }
+  float do_scale(uint32_t site) const { return adt_make_drop(p, seed, site).scale; }      // the consumer's drop.scale
   const float* f;                     // log_feats
   SideStream *sd, *sd_sort;           // side stream of the scatter / fold kernels ; of the id sort (nullptr: the caller's stream)
 
@@ -634,6 +644,7 @@ int dec_post_bwd(const Bwd& x, int i) {
   a.dW0 = Gq + lo.dec(i, D_C2W); a.dW1 = Gq + lo.dec(i, D_C1W); a.dW2 = Gq + lo.dec(i, D_EOW);
   a.db0 = Gq + lo.dec(i, D_C2B); a.db1 = Gq + lo.dec(i, D_C1B); a.db2 = Gq + lo.dec(i, D_EOB);
   a.out0 = x.s1;
+  a.do_bf16 = x.do_rows_cross(); a.do_delta = x.do_delta(); a.do_scale = x.do_scale(dec_site(i, 1)); a.do_hd = x.hd;      // -> the cross-attention backward
   a.part[0] = x.PART(i, PS_D_C2); a.part[1] = x.PART(i, PS_D_C1); a.part[2] = x.PART(i, PS_D_EO); a.part_stride = (size_t)w.part_stride;
   a.vpart = x.VPART(i, 0);
   const int rc = x.sp.use_seq ? adt_launch_seq_post_bwd(x.hd, 0, a, x.st) : 1;
@@ -641,6 +652,8 @@ int dec_post_bwd(const Bwd& x, int i) {
   if (rc && x.sp.parts) return adt_set_error(NO_FALLBACK, x.L, x.hd);
   return rc ? adt_launch_bwdchain(x.prec, 1, a, x.st) : 0;
 }
+
+adt::AttnArgs dec_cross_attn_lean_args(const Bwd& x, int i);
 
 // cross attention core: dq2 -> s5, dkv2 -> s4
 int dec_cross_attn_bwd(const Bwd& x, int i) {
@@ -651,6 +664,10 @@ int dec_cross_attn_bwd(const Bwd& x, int i) {
   if (!x.sp.lean)
     return adt_attn_bwd(x.prec, q2, d, kv2, 2 * d, kv2 + d, 2 * d, o2, d, lse2, x.s1, d, B, x.H, x.L, x.hd, 1, x.p, x.seed, dec_site(i, 1), x.b_offset,
                         x.s5, d, s4, 2 * d, s4 + d, 2 * d, mask2, x.st);
+  if (x.sp.do_handover) {      // (implies lean and parts) dO2 arrives as bf16 rows + delta: the same launch from the argument block that names them
+    const int rc = adt_launch_seq_attn_bwd(x.hd, dec_cross_attn_lean_args(x, i), x.st);
+    return rc == 1 ? adt_set_error(NO_FALLBACK, x.L, x.hd) : rc;
+  }
   const uint16_t* kvb = reinterpret_cast<const uint16_t*>(kv2);      // rows of 128 bf16: k2 | v2
   // dq2 / dk2 / dv2 go to k_seqtt_mid_bwd only (with `parts` a "not covered" from it is an error), which builds bf16 MFMA operands from
   // them: written as bf16 rows (the same rounding, half the bytes); s4 + d / 2 floats = 64 bf16 elements into the (k | v) row
@@ -676,6 +693,7 @@ adt::BwdChainArgs dec_mid_seq_args(const Bwd& x, int i) {
   a.part[0] = x.PART(i, PS_D_EIN); a.part[1] = x.PART(i, PS_D_SO); a.part[2] = x.PART(i, PS_D_EIN + 1); a.part[3] = x.PART(i, PS_D_EIN + 2);
   a.part_stride = (size_t)w.part_stride;
   a.vpart = x.VPART(i, 1);
+  a.do_bf16 = x.do_rows(); a.do_delta = x.do_delta(); a.do_scale = x.do_scale(dec_site(i, 0)); a.do_hd = x.hd;      // -> attn_block_bwd(dec)
   return a;
 }
 
@@ -684,9 +702,11 @@ adt::AttnArgs dec_cross_attn_lean_args(const Bwd& x, int i) {
   const WS& w = x.w; const int d = x.d;
   float* base = x.ws + i * w.d_stride;
   const uint16_t* kvb = reinterpret_cast<const uint16_t*>(base + w.d_kv2);      // rows of 128 bf16: k2 | v2
-  return adt_attn_bwd_saved_bf16_args(base + w.d_q2, d, kvb, 2 * d, kvb + d, 2 * d, base + w.d_o2, d, base + w.d_lse2, x.s1, d, (int)w.B, x.H, x.L, x.hd, x.p,
-                                      x.seed, dec_site(i, 1), x.b_offset, x.s5, d, x.s4, 2 * d, x.s4 + d / 2, 2 * d,
-                                      reinterpret_cast<const uint32_t*>(base + w.d_mask2), 1);
+  adt::AttnArgs a = adt_attn_bwd_saved_bf16_args(base + w.d_q2, d, kvb, 2 * d, kvb + d, 2 * d, base + w.d_o2, d, base + w.d_lse2, x.s1, d, (int)w.B, x.H, x.L,
+                                                 x.hd, x.p, x.seed, dec_site(i, 1), x.b_offset, x.s5, d, x.s4, 2 * d, x.s4 + d / 2, 2 * d,
+                                                 reinterpret_cast<const uint32_t*>(base + w.d_mask2), 1);
+  a.do_bf16 = x.do_rows_cross(); a.do_delta = x.do_delta();      // from dec_post_bwd
+  return a;
 }
 
 // enc_attn q / k / v projections and slf_attn.out_proj reverse -> dO1 (s1), g_f +=
@@ -740,6 +760,7 @@ int attn_block_bwd(const Bwd& x, int i, bool dec) {
     adt::SeqBwdArgs a = seq_bwd_args(x.L, (int)w.B, x.H, ids, x.p, x.seed, site, x.b_offset, x.hd);
     a.x = xi; a.gamma = P + lnw; a.beta = P + lnb; a.Win = P + inw; a.bin = P + inb;
     a.dO = x.s1; a.o = o; a.lse = lse; a.mask = mask; a.dres = dec ? gy : x.s5;
+    a.do_bf16 = x.do_rows(); a.do_delta = x.do_delta();      // from enc_post_bwd / the decoder's mid chain
     a.gx = gx; a.acc = acc; a.dWin = Gq + inw; a.dbin = Gq + inb; a.dgamma = Gq + lnw; a.dbeta = Gq + lnb;
     if (x.plan.seeds_virtual && dec && i > 0) {      // reconstruction pair (enc_in[nl - i], dec_x[i]): d / d dec_x[i] = -2 lambda (a - b) / n = coef * (x - a)
       a.acc = 0; a.seed_other = ws + w.enc_x + (nl - i) * x.Td; a.seed_coef = ws + w.norms + 8 + (nl - i);
@@ -759,6 +780,8 @@ int attn_block_bwd(const Bwd& x, int i, bool dec) {
     // defensive: StepPlan::lean implies adt_covers_attn_pre_bwd (ADT_SEQ_BWD, weight images, L % 4 == 0, L <= ADT_SEQ_MAXLEN, H hd = 64)
     if (x.sp.lean) return adt_set_error("backward: the lean forward needs the fused attention-block backward (L=%d hd=%d)", x.L, x.hd);
   }
+  // the staged pair below is the one user of s3, and reads fp32 dO from s1: never beside the hand-over, whose dO1 rows live in s3 (Bwd::do_rows)
+  if (x.sp.do_handover) return adt_set_error("backward: the staged attention backward was reached with the dO hand-over on (L=%d hd=%d)", x.L, x.hd);
   CK(adt_attn_bwd(x.prec, qkv, 3 * d, qkv + d, 3 * d, qkv + 2 * d, 3 * d, o, d, lse, x.s1, d, (int)w.B, x.H, x.L, x.hd, 1, x.p, x.seed, site, x.b_offset,
                   x.s3, 3 * d, x.s3 + d, 3 * d, x.s3 + 2 * d, 3 * d, mask, x.st));
   adt::BwdChainArgs a = x.BA(ids, 0.f, nullptr);
@@ -884,6 +907,7 @@ int enc_post_bwd(const Bwd& x, int i) {
   }
   a.part[0] = x.PART(i, PS_E_C2); a.part[1] = x.PART(i, PS_E_C1); a.part[2] = x.PART(i, PS_E_O); a.part_stride = (size_t)w.part_stride;
   a.vpart = x.VPART(i, 3);
+  a.do_bf16 = x.do_rows(); a.do_delta = x.do_delta(); a.do_scale = x.do_scale(enc_site(i, 0)); a.do_hd = x.hd;      // -> attn_block_bwd(enc)
   if (x.sp.lnl_fused && i == nl - 1) {
     a.gy = x.gf; a.lnl_x = ws + w.enc_x + nl * x.Td; a.lnl_gamma = P + lo.lnl_w(); a.lnl_eps = LN_EPS;
     a.vpart2 = x.call.late_parts ? ws + w.vpart + (int64_t)(5 * nl) * w.vcall : nullptr;

@@ -37,7 +37,7 @@ const SeqSwitches& adt_seq_switches() {
     SeqSwitches s;
     s.seq = adt_env_on("ADT_SEQ"); s.seq_lean = adt_env_on("ADT_SEQ_LEAN"); s.seq_tt = adt_env_on("ADT_SEQ_TT"); s.seq_bwd = adt_env_on("ADT_SEQ_BWD");
     s.seq_attn_bwd = adt_env_on("ADT_SEQ_ATTN_BWD"); s.seq_post_bwd = adt_env_on("ADT_SEQ_POST_BWD"); s.seq_partials = adt_env_on("ADT_SEQ_PARTIALS");
-    s.xattn_fused = adt_env_on("ADT_XATTN_FUSED");
+    s.xattn_fused = adt_env_on("ADT_XATTN_FUSED"); s.do_bf16 = adt_env_on("ADT_DO_BF16");
     s.seq_ablate = adt_env_int("ADT_SEQ_ABLATE", 0); s.seq_ablate_set = adt_env_int("ADT_SEQ_ABLATE", INT_MIN) != INT_MIN;
     s.seq_split = adt_env_int("ADT_SEQ_SPLIT", 0); s.attn_split = adt_env_on("ADT_ATTN_SPLIT");
     s.side_stream = adt_env_int("ADT_SIDE_STREAM", 7); s.side_stream_dp = adt_env_int("ADT_SIDE_STREAM_DP", 0) != 0;
@@ -132,9 +132,16 @@ int adt_launch_seq_dec_fwd(int hd, const SeqFwdArgs& a, void* stream) {
   return adt_set_error("seq_dec_fwd: head size %d", hd);
 }
 
+// Launches of an attention backward (k_seqtt_attn_pre_bwd, k_seq_attn_bwd, k_seqtt_xattn_mid_bwd) ISSUED by this process that took dO as
+// handed-over bf16 rows + delta (SeqBwdArgs / AttnArgs::do_bf16); like adt_seq_xattn_fused_launches below a debugging aid of the tests, not
+// part of include/adt_hip.h
+static std::atomic<unsigned long long> g_do_handover_launches{0};
+extern "C" unsigned long long adt_seq_do_handover_launches() { return g_do_handover_launches.load(); }
+
 // causal attention backward, one workgroup per sequence (adt_seqattn.cuh); returns 1 when the shape is not covered (caller falls back)
 int adt_launch_seq_attn_bwd(int hd, const AttnArgs& a, void* stream) {
   if (!adt_covers_attn_bwd(adt_seq_switches(), hd, attn_facts(a))) return 1;
+  if (a.do_bf16 && (!a.do_delta || !a.in_bf16)) return adt_set_error("seq_attn_bwd: handed-over dO rows need their delta and bf16 operand rows");
   const size_t smem = sab_lds_bytes(a.L, a.H);
   const int mode = a.drop.thr == 0 ? 0 : (a.mask != nullptr ? 1 : 2);
   static AdtLdsOptIn optin[9];
@@ -146,7 +153,9 @@ int adt_launch_seq_attn_bwd(int hd, const AttnArgs& a, void* stream) {
   args.stamps = seq_stamp_buffer(true);
   if (!args.stamps) args.stamps = seq_stamp_buffer_mode(4);
   // smem varies with L: opt in once to the most this kernel may ask for
-  return adt_launch_lds1(fns[slot], dim3(a.B), dim3(SAB_NW * 64), smem, args, (hipStream_t)stream, "seq_attn_bwd", optin[slot], ADT_LDS_MAX);
+  const int rc = adt_launch_lds1(fns[slot], dim3(a.B), dim3(SAB_NW * 64), smem, args, (hipStream_t)stream, "seq_attn_bwd", optin[slot], ADT_LDS_MAX);
+  if (rc == 0 && a.do_bf16) ++g_do_handover_launches;
+  return rc;
 }
 
 // fused backward of one attention block (adt_seqbwd_tt.cuh); dec = 0: encoder block, 1: decoder self-attention block.
@@ -162,13 +171,16 @@ static int seq_attn_pre_bwd_t(int mode, const SeqBwdArgs& a, hipStream_t s) {
   args.stamps = seq_stamp_buffer(true);
   if (a.nsplit == 2 && !a.part) return adt_set_error("seqtt_attn_pre_bwd: two workgroups per sequence need the weight-gradient partials");
   if (a.nsplit != 2) args.nsplit = 1;
-  return seq_launch(fns[mode], smem, optin[mode], a.B * args.nsplit, &args, s, "seqtt_attn_pre_bwd");
+  const int rc = seq_launch(fns[mode], smem, optin[mode], a.B * args.nsplit, &args, s, "seqtt_attn_pre_bwd");
+  if (rc == 0 && a.do_bf16) ++g_do_handover_launches;
+  return rc;
 }
 
 int adt_launch_seq_attn_pre_bwd(int hd, int dec, const SeqBwdArgs& a, void* stream) {
   SeqChainFacts f{};
   f.L = a.L; f.H = a.H; f.B = a.B; f.T = a.B * a.L; f.wimg = a.wp_img != nullptr;
   if (!adt_covers_attn_pre_bwd(adt_seq_switches(), hd, f)) return 1;
+  if (a.do_bf16 && !a.do_delta) return adt_set_error("seqtt_attn_pre_bwd: handed-over dO rows without their delta");
   const int mode = a.drop.thr == 0 ? 0 : (a.mask != nullptr ? 1 : 2);
   hipStream_t s = (hipStream_t)stream;
   if (hd == 32) return dec ? seq_attn_pre_bwd_t<32, true>(mode, a, s) : seq_attn_pre_bwd_t<32, false>(mode, a, s);
@@ -224,6 +236,9 @@ int adt_launch_seq_xattn_mid_bwd(int hd, const AttnArgs& at, const BwdChainArgs&
   a.db0 = ch.db0; a.db1 = ch.db1; a.db2 = ch.db2; a.db3 = ch.db3; a.vpart = ch.vpart;
   for (int k = 0; k < 4; ++k) a.part[k] = ch.part[k];
   a.part_stride = ch.part_stride;
+  a.do_bf16 = ch.do_bf16; a.do_delta = ch.do_delta; a.do_scale = ch.do_scale;
+  a.dO_bf16 = reinterpret_cast<const __bf16*>(at.do_bf16); a.dO_delta = at.do_delta;
+  if (at.do_bf16 && !at.do_delta) return adt_set_error("seqtt_xattn_mid_bwd: handed-over dO rows without their delta");
   a.stamps = seq_stamp_buffer_mode(6);
   const int mode = at.drop.thr == 0 ? 0 : 1;
   static AdtLdsOptIn optin[6];
@@ -234,6 +249,7 @@ int adt_launch_seq_xattn_mid_bwd(int hd, const AttnArgs& at, const BwdChainArgs&
   const size_t most = xm_lds_bytes(ADT_SEQ_MAXLEN, at.H) <= ADT_LDS_MAX ? xm_lds_bytes(ADT_SEQ_MAXLEN, at.H) : xm_lds_bytes(128, at.H);
   const int rc = seq_launch(fns[slot], xm_lds_bytes(at.L, at.H), optin[slot], at.B, &a, (hipStream_t)stream, "seqtt_xattn_mid_bwd", XM_NW, most);
   if (rc == 0) ++g_xattn_fused_launches;
+  if (rc == 0 && at.do_bf16) ++g_do_handover_launches;
   return rc;
 }
 

@@ -254,9 +254,11 @@ __global__ __launch_bounds__(SAB_NW * 64) void k_seq_attn_bwd(AttnArgs a) {
   for (int i = threadIdx.x; i < R * 8; i += NW * 64) {
     const int r = i >> 3, c8 = (i & 7) * 8;
     float q[8], k[8], v[8], d[8], o[8];
+    float dlt = 0.f;
+    const bool hand = a.in_bf16 && a.do_bf16 != nullptr;      // (workgroup-uniform) dO as bf16 rows of dO * drop.scale + delta (AttnArgs::do_bf16)
 #pragma unroll
     for (int j = 0; j < 8; ++j) q[j] = k[j] = v[j] = d[j] = o[j] = 0.f;
-    if (r < L && a.in_bf16) {          // operands saved as bf16 rows by the lean forward; the gradient dO is always fp32
+    if (r < L && a.in_bf16) {          // operands saved as bf16 rows by the lean forward; the gradient dO is fp32 unless handed over (`hand`)
       const __bf16* Qb = reinterpret_cast<const __bf16*>(a.Q); const __bf16* Kb = reinterpret_cast<const __bf16*>(a.K);
       const __bf16* Vb = reinterpret_cast<const __bf16*>(a.V); const __bf16* Ob = reinterpret_cast<const __bf16*>(a.O);
       // saved rows are in the register order of a transposed tile (adt_tt.cuh: tt_store_bf16): features c8 .. c8+3 and c8+4 .. c8+7 of a
@@ -266,12 +268,22 @@ __global__ __launch_bounds__(SAB_NW * 64) void k_seq_attn_bwd(AttnArgs a) {
       const bf16x4_t qa = *reinterpret_cast<const bf16x4_t*>(Qb + (row_b + r) * a.ldq + pa), qc = *reinterpret_cast<const bf16x4_t*>(Qb + (row_b + r) * a.ldq + pb);
       const bf16x4_t ka = *reinterpret_cast<const bf16x4_t*>(Kb + (row_b + r) * a.ldk + pa), kc = *reinterpret_cast<const bf16x4_t*>(Kb + (row_b + r) * a.ldk + pb);
       const bf16x4_t va = *reinterpret_cast<const bf16x4_t*>(Vb + (row_b + r) * a.ldv + pa), vc = *reinterpret_cast<const bf16x4_t*>(Vb + (row_b + r) * a.ldv + pb);
-      const bf16x4_t oa = *reinterpret_cast<const bf16x4_t*>(Ob + (row_b + r) * a.ldo + pa), oc = *reinterpret_cast<const bf16x4_t*>(Ob + (row_b + r) * a.ldo + pb);
       bf16x8 qb, kb, vb, ob;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { qb[j] = qa[j]; qb[4 + j] = qc[j]; kb[j] = ka[j]; kb[4 + j] = kc[j]; vb[j] = va[j]; vb[4 + j] = vc[j]; ob[j] = oa[j]; ob[4 + j] = oc[j]; }
-      *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(a.dO + (row_b + r) * a.lddo + c8);
-      *reinterpret_cast<float4*>(d + 4) = *reinterpret_cast<const float4*>(a.dO + (row_b + r) * a.lddo + c8 + 4);
+      for (int j = 0; j < 4; ++j) { qb[j] = qa[j]; qb[4 + j] = qc[j]; kb[j] = ka[j]; kb[4 + j] = kc[j]; vb[j] = va[j]; vb[4 + j] = vc[j]; ob[j] = (__bf16)0.f; ob[4 + j] = (__bf16)0.f; }
+      if (hand) {      // the row's pieces as stored (exact in fp32: pack8 below gives them back), and the head's delta
+        const __bf16* Db = reinterpret_cast<const __bf16*>(a.do_bf16) + (row_b + r) * 64;
+        const bf16x4_t da = *reinterpret_cast<const bf16x4_t*>(Db + pa), dc = *reinterpret_cast<const bf16x4_t*>(Db + pb);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { d[j] = (float)da[j]; d[4 + j] = (float)dc[j]; }
+        dlt = a.do_delta[(row_b + r) * 4 + (i & 7) / (HD / 8)];
+      } else {
+        const bf16x4_t oa = *reinterpret_cast<const bf16x4_t*>(Ob + (row_b + r) * a.ldo + pa), oc = *reinterpret_cast<const bf16x4_t*>(Ob + (row_b + r) * a.ldo + pb);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { ob[j] = oa[j]; ob[4 + j] = oc[j]; }
+        *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(a.dO + (row_b + r) * a.lddo + c8);
+        *reinterpret_cast<float4*>(d + 4) = *reinterpret_cast<const float4*>(a.dO + (row_b + r) * a.lddo + c8 + 4);
+      }
 #pragma unroll
       for (int j = 0; j < 8; ++j) { q[j] = (float)qb[j]; k[j] = (float)kb[j]; v[j] = (float)vb[j]; o[j] = (float)ob[j]; }
     } else if (r < L) {
@@ -286,15 +298,17 @@ __global__ __launch_bounds__(SAB_NW * 64) void k_seq_attn_bwd(AttnArgs a) {
       *reinterpret_cast<float4*>(o) = *reinterpret_cast<const float4*>(a.O + (row_b + r) * a.ldo + c8);
       *reinterpret_cast<float4*>(o + 4) = *reinterpret_cast<const float4*>(a.O + (row_b + r) * a.ldo + c8 + 4);
     }
-    float part = 0.f;
+    float part = hand ? dlt : tt_chunk_delta(d, o);      // (adt_tt.cuh: the chain k_seqtt_post_bwd<DEC> runs too)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { part += d[j] * o[j]; q[j] *= qmul; d[j] *= a.drop.scale; }      // the dO image carries 1 / (1 - p): see sab_pass_a
+    for (int j = 0; j < 8; ++j) { q[j] *= qmul; if (!hand) d[j] *= a.drop.scale; }      // the dO image carries 1 / (1 - p): see sab_pass_a
     *reinterpret_cast<bf16x8*>(sQ + r * TT_RS + c8) = pack8(q);
     *reinterpret_cast<bf16x8*>(sK + r * TT_RS + c8) = pack8(k);
     *reinterpret_cast<bf16x8*>(sV + r * TT_RS + c8) = pack8(v);
     *reinterpret_cast<bf16x8*>(sdO + r * TT_RS + c8) = pack8(d);
+    if (!hand) {
 #pragma unroll
-    for (int off = HD / 16; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);      // HD/8 adjacent lanes hold one head's chunks
+      for (int off = HD / 16; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);      // HD/8 adjacent lanes hold one head's chunks
+    }
     if (((i & 7) % (HD / 8)) == 0) sDelta[((i & 7) / (HD / 8)) * R + r] = part;
   }
   SAB_STAMP(1);

@@ -13,6 +13,8 @@ struct SeqBwdArgs {
   const float* gamma; const float* beta;           // LayerNorm in front of the in-projection
   const float* Win; const float* bin;              // packed in-projection (3 x 64 x 64, 3 x 64)
   const float* dO; const float* o;                 // gradient wrt the attention output ; the forward's attention output
+  const void* do_bf16; const float* do_delta;      // do_bf16 != nullptr (adt_bwdchain_args.h): bf16 rows of dO * drop.scale and delta[row * 4 + h]
+                                                   // from the out-projection reverse; dO is not read, o is not read
   const float* lse; const uint32_t* mask;          // (B*H*L) log-sum-exp ; (B*H*L x 8) dropout keep bits
   float dres_scale;                   // decoder only: the residual gradient is dres * dres_scale (0 means 1; the supernet's mixing weight)
   const float* dres;                  // encoder: gradient wrt LN(x) from the residual path ; decoder: gradient wrt the layer output (masked here)

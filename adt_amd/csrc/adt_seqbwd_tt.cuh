@@ -44,6 +44,20 @@ ADT_DEVICE_INLINE void sb_frags(const TT& t, float mul, bf16x8 (&f)[(64 / HD) * 
   }
 }
 
+// the same operands from handed-over bf16 rows (adt_tt.cuh: tt_load_bf16_raw), which hold bf16(t * mul) in tt_store_bf16's order
+template <int HD>
+ADT_DEVICE_INLINE void sb_frags_rows(const TTRowB& t, bf16x8 (&f)[(64 / HD) * ((HD + 31) / 32)]) {
+  if constexpr (HD >= 32) {
+    f[0] = t.lo;
+    f[1] = t.hi;
+  } else {
+#pragma unroll
+    for (int h = 0; h < 4; ++h)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { f[h][j] = (h < 2 ? t.lo : t.hi)[4 * (h & 1) + j]; f[h][4 + j] = (__bf16)0.f; }
+  }
+}
+
 // rows of a natural-order image from such operands (the inverse of sab_rowfrag)
 template <int HD>
 ADT_DEVICE_INLINE void sb_put_frags(__bf16* img, int token, const bf16x8 (&f)[(64 / HD) * ((HD + 31) / 32)], bool valid, int g) {
@@ -333,6 +347,9 @@ __global__ __launch_bounds__(SB_NW * 64) void k_seqtt_attn_pre_bwd(SeqBwdArgs a)
 #pragma unroll
   for (int k = 0; k < 3; ++k) adt_glds_block<NW>(src6[k], wpl + k * TT_WIMG, TT_WIMG * 2);
   TT xa[2], doa[2], oa[2];
+  TTRowB dob[2];                                 // SeqBwdArgs::do_bf16: the handed-over operand rows and delta in the place of dO and O
+  float delta[2][H];
+  const bool hand = a.do_bf16 != nullptr;        // (workgroup-uniform)
   int idv[2] = {1, 1};                           // decoder block: the pad mask of the residual-path gradient in P5 (read there it was an exposed round trip)
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
@@ -370,8 +387,13 @@ __global__ __launch_bounds__(SB_NW * 64) void k_seqtt_attn_pre_bwd(SeqBwdArgs a)
     const int tile = TM(s);
     const int l = tile * 16 + c, row = b * L + l;
     const bool valid = tile >= 0 && l < L;
-    doa[s] = tt_load(a.dO + (size_t)row * 64, valid, g);
-    oa[s] = tt_load_saved(a.o, row, valid, g, a.saved_bf16);
+    if (hand) {
+      dob[s] = tt_load_bf16_raw(reinterpret_cast<const __bf16*>(a.do_bf16) + (size_t)row * 64, valid, g);
+      tt_delta_load<H>(a.do_delta, (size_t)row, valid, delta[s]);
+    } else {
+      doa[s] = tt_load(a.dO + (size_t)row * 64, valid, g);
+      oa[s] = tt_load_saved(a.o, row, valid, g, a.saved_bf16);
+    }
   }
 #pragma unroll
   for (int k = 3; k < 6; ++k) adt_glds_block<NW>(src6[k], wtr + (k - 3) * TT_WIMG, TT_WIMG * 2);      // waited for in front of the barrier behind pass A
@@ -379,7 +401,6 @@ __global__ __launch_bounds__(SB_NW * 64) void k_seqtt_attn_pre_bwd(SeqBwdArgs a)
   const uint32_t key_rng = drop_key(a.drop);
   // ---- P1: recompute LN + in-projection; operands to registers, K / V images ------------------------------------------------------
   bf16x8 fq[2][NF], fdo[2][NF];
-  float delta[2][H];
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
     const int tile = TM(s);
@@ -400,19 +421,16 @@ __global__ __launch_bounds__(SB_NW * 64) void k_seqtt_attn_pre_bwd(SeqBwdArgs a)
     TT v = tt_gemm(DEC ? bn : bx, wpl + 2 * TT_WIMG, c, g);
     tt_add_vec(v, vbin + 128, g);
     tt_put_rows(img1, l, v, valid, g);
-    const TT& dO = doa[s];
-    const TT& o = oa[s];
-    sb_frags<HD>(dO, a.drop.scale, fdo[s]);          // the dO operands / image carry 1 / (1 - p) (adt_seqattn.cuh: sab_pass_a); delta below does not
-#pragma unroll
-    for (int h = 0; h < H; ++h) {
-      float part = 0.f;
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) part += dO.v[h * NT + nt][r] * o.v[h * NT + nt][r];
-      delta[s][h] = tt_colsum(part);
-      if (g == 0 && valid) sDelta[h * R + l] = delta[s][h];
+    // the dO operands / image carry 1 / (1 - p) (adt_seqattn.cuh: sab_pass_a); delta does not
+    if (hand) {
+      sb_frags_rows<HD>(dob[s], fdo[s]);               // rounded to bf16 by the producer, with the scale: the values sb_frags makes below
+    } else {
+      sb_frags<HD>(doa[s], a.drop.scale, fdo[s]);
+      tt_head_delta<HD>(doa[s], oa[s], delta[s]);      // (the producer's function: one summation order on both sides)
     }
+#pragma unroll
+    for (int h = 0; h < H; ++h)
+      if (g == 0 && valid) sDelta[h * R + l] = delta[s][h];
   }
   __syncthreads();
   SB_STAMP(2);

@@ -46,6 +46,23 @@ ADT_DEVICE_INLINE void sp_zero_images(__bf16* img0) {
   uint4* z = reinterpret_cast<uint4*>(img0);
   for (int i = threadIdx.x; i < (int)((2 * ibytes + 64) / 16); i += NW * 64) z[i] = make_uint4(0u, 0u, 0u, 0u);
 }
+// dO1 of the decoder's mid chain (k_seqtt_mid_bwd, k_seqtt_xattn_mid_bwd), row `row`: fp32 to out0, or (do_bf16 != nullptr,
+// adt_bwdchain_args.h) handed to the self-attention backward as bf16 rows of dO1 * scale plus delta of every head from dO1 and o1.
+// CHUNKS: delta in the cross-attention kernels' order (k_seqtt_post_bwd<DEC>: tt_head_delta_chunks)
+template <int HD, bool CHUNKS = false>
+ADT_DEVICE_INLINE void sp_hand_do(void* do_bf16, float* do_delta, float scale, size_t row, const TT& dO, const TT& o, bool valid, int g) {
+  float dl[64 / HD];
+  if constexpr (CHUNKS) tt_head_delta_chunks<HD>(dO, o, dl);
+  else tt_head_delta<HD>(dO, o, dl);
+  tt_store_bf16(reinterpret_cast<__bf16*>(do_bf16) + row * 64, dO, valid, g, scale);
+  tt_delta_store<64 / HD>(do_delta, row, dl, valid, g, CHUNKS ? 1 : 0);
+}
+ADT_DEVICE_INLINE void sp_store_do1(float* out0, void* do_bf16, float* do_delta, float scale, int hd, size_t row, const TT& dO, const TT& o, bool valid, int g) {
+  if (!do_bf16) { tt_store(out0 + row * 64, dO, valid, g); return; }      // (workgroup-uniform, like hd)
+  if (hd == 32) sp_hand_do<32>(do_bf16, do_delta, scale, row, dO, o, valid, g);
+  else if (hd == 64) sp_hand_do<64>(do_bf16, do_delta, scale, row, dO, o, valid, g);
+  else sp_hand_do<16>(do_bf16, do_delta, scale, row, dO, o, valid, g);
+}
 // Wave count of the token-chain backward kernels.  Every tile costs the same here (no causal weights), so with 13 tiles at L = 200 the eight-wave
 // form is paced by the five waves that own two tiles; sixteen waves (<= 128 VGPRs, one tile slot per wave) give every tile its own wave and
 // four waves per SIMD to cover each other's LDS and MFMA latency.
@@ -259,7 +276,11 @@ __global__ __launch_bounds__(SP_NW * 64) void k_seqtt_post_bwd(BwdChainArgs a) {
         }
       }
     }
-    tt_store((ENC ? a.out1 : a.out0) + (size_t)row * 64, dO, valid, g);
+    if (a.do_bf16) {      // (workgroup-uniform) the hand-over to the attention backward behind: its operand rows and its delta, in ITS order
+      sp_hand_do<HD, !ENC>(a.do_bf16, a.do_delta, a.do_scale, (size_t)row, dO, oraw_s, valid, g);      // (adt_tt.cuh: tt_head_delta / _chunks)
+    } else {
+      tt_store((ENC ? a.out1 : a.out0) + (size_t)row * 64, dO, valid, g);
+    }
   }
   SB_STAMP(12);
   __syncthreads();
@@ -387,8 +408,9 @@ __global__ __launch_bounds__(SP_MID_NW * 64) void k_seqtt_mid_bwd(BwdChainArgs a
     dk[s] = a.grad_bf16 ? tt_load_bf16(reinterpret_cast<const __bf16*>(a.dkv2) + (size_t)row * 128, valid, g) : tt_load(a.dkv2 + (size_t)row * 128, valid, g);
     fx[s] = tt_load(a.f + (size_t)row * 64, valid, g);
     tt_put_rows(img0, l, da1[s], valid, g);
-    tt_put_rows(img1, l, tt_saved_value(oreq[s], a.saved_bf16), valid, g);
-    tt_store(a.out0 + (size_t)row * 64, tt_gemm(tt_bfrags(da1[s]), wimg + TT_WIMG, c, g), valid, g);
+    const TT o1 = tt_saved_value(oreq[s], a.saved_bf16);
+    tt_put_rows(img1, l, o1, valid, g);
+    sp_store_do1(a.out0, a.do_bf16, a.do_delta, a.do_scale, a.do_hd, (size_t)row, tt_gemm(tt_bfrags(da1[s]), wimg + TT_WIMG, c, g), o1, valid, g);
   }
   __syncthreads();
   sb_dw_product16<NW>(img0, img1, npair, a.dW1, a.part[1] ? a.part[1] + (size_t)blockIdx.x * a.part_stride : nullptr, sRed + 64, w, c, g);

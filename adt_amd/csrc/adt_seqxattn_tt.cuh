@@ -14,7 +14,7 @@
 // rows are taken into registers in front of it) and stream under pass B, as does a1; o1, f and d log_feats are requested a phase ahead of their use.
 //
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; VGPRs / scratch bytes per lane), 16 waves = 4 per SIMD = at most 128 VGPRs:
-//   <64, 0> 126 / 0   <64, 1> 128 / 0   <32, 0> 118 / 0   <32, 1> 128 / 0 (the flagship)   <16, 0> 124 / 0   <16, 1> 126 / 0
+//   <64, 0> 128 / 0   <64, 1> 128 / 0   <32, 0> 118 / 0   <32, 1> 128 / 20 (the flagship)   <16, 0> 128 / 0   <16, 1> 128 / 0
 // dynamic LDS 147,968 B at L > 128 with two heads (84,992 B at L <= 128); four 16-wide heads fit up to L = 128 only (ADT_LDS_MAX).
 // What made it fit: the hand-over tiles are held as packed bf16 operands (xm_put_rows), pass B's key / value operands of a 16-wide head as
 // their low halves, and o1 / f / d log_feats are requested between the passes' barriers and not under pass B.
@@ -39,6 +39,8 @@ struct XattnMidArgs {
   float* out0; float* out1; int acc1; int nrep; size_t rep_stride;
   float* db0; float* db1; float* db2; float* db3; float* vpart;
   float* part[4]; size_t part_stride;
+  void* do_bf16; float* do_delta; float do_scale;      // hand-over of dO1 to the self-attention backward (BwdChainArgs: do_bf16 ; the head size is HD)
+  const __bf16* dO_bf16; const float* dO_delta;        // hand-over of dO2 FROM k_seqtt_post_bwd<DEC> (AttnArgs: do_bf16, do_delta): dO and O are not read
   unsigned long long* stamps;      // timing experiments only (ADT_SEQ_STAMPS=6): s_memtime per wave of workgroup 0
 };
 
@@ -129,8 +131,10 @@ __global__ __launch_bounds__(XM_NW * 64) void k_seqtt_xattn_mid_bwd(XattnMidArgs
   });
   // images: 8 features per thread and step.  Saved rows are in the register order of a transposed tile (adt_tt.cuh: tt_store_bf16): features
   // c8 .. c8+3 and c8+4 .. c8+7 of a 64-feature row are two 8-byte pieces at 16 g + 4 nt and 16 (g + 1) + 4 nt, nt = c8 / 16, g = (c8 / 4) % 4
-  bf16x4 qa[II], qc[II], ka[II], kc[II], va[II], vc[II], oa[II], oc[II];
+  bf16x4 qa[II], qc[II], ka[II], kc[II], va[II], vc[II], oa[II], oc[II], da[II], dc[II];
   f32x4 d0[II], d1[II];
+  float dlt[II];
+  const bool hand = a.dO_bf16 != nullptr;      // (workgroup-uniform) dO as bf16 operand rows + delta: no fp32 dO, no O
   adt_static_for<II>([&](auto k) {
     const int i = threadIdx.x + k * NTH, r = i >> 3, c8 = (i & 7) * 8;
     const bool ok = r < L;
@@ -141,9 +145,16 @@ __global__ __launch_bounds__(XM_NW * 64) void k_seqtt_xattn_mid_bwd(XattnMidArgs
     const gb4 zb = (gb4)tt_zero_row + (i & 7);
     const gb4 pq = ok ? (gb4)(a.Q + row * a.ldq + pa) : zb, pk = ok ? (gb4)(a.K + row * a.ldk + pa) : zb;
     const gb4 pv = ok ? (gb4)(a.V + row * a.ldv + pa) : zb, po = ok ? (gb4)(a.O + row * a.ldo + pa) : zb;
-    const gp4 pd = ok ? (gp4)(a.dO + row * a.lddo + c8) : (gp4)tt_zero_row + (i & 7);
-    qa[k] = pq[0]; qc[k] = pq[4]; ka[k] = pk[0]; kc[k] = pk[4]; va[k] = pv[0]; vc[k] = pv[4]; oa[k] = po[0]; oc[k] = po[4];      // pb = pa + 16 elements
-    d0[k] = pd[0]; d1[k] = pd[1];
+    qa[k] = pq[0]; qc[k] = pq[4]; ka[k] = pk[0]; kc[k] = pk[4]; va[k] = pv[0]; vc[k] = pv[4];      // pb = pa + 16 elements
+    if (hand) {
+      const gb4 pdb = ok ? (gb4)(a.dO_bf16 + row * 64 + pa) : zb;
+      da[k] = pdb[0]; dc[k] = pdb[4];
+      dlt[k] = *(ok ? (gf1)(a.dO_delta + row * 4 + (i & 7) / (HD / 8)) : (gf1)tt_zero_row);      // the chunk's head
+    } else {
+      const gp4 pd = ok ? (gp4)(a.dO + row * a.lddo + c8) : (gp4)tt_zero_row + (i & 7);
+      oa[k] = po[0]; oc[k] = po[4];
+      d0[k] = pd[0]; d1[k] = pd[1];
+    }
   });
   XM_STAMP(1);
   if constexpr (MODE == 1) {
@@ -160,25 +171,38 @@ __global__ __launch_bounds__(XM_NW * 64) void k_seqtt_xattn_mid_bwd(XattnMidArgs
   // delta from the same dO / O chunks, in the order of k_seq_attn_bwd: the eight products of a chunk, then the chunks of a head (adjacent lanes)
   adt_static_for<II>([&](auto k) {
     const int i = threadIdx.x + k * NTH, r = i >> 3, c8 = (i & 7) * 8;
-    float q[8], kk[8], v[8], d[8], o[8];
+    float q[8], kk[8], v[8];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       q[j] = (float)qa[k][j]; q[4 + j] = (float)qc[k][j]; kk[j] = (float)ka[k][j]; kk[4 + j] = (float)kc[k][j];
-      v[j] = (float)va[k][j]; v[4 + j] = (float)vc[k][j]; o[j] = (float)oa[k][j]; o[4 + j] = (float)oc[k][j];
-      d[j] = d0[k][j]; d[4 + j] = d1[k][j];
+      v[j] = (float)va[k][j]; v[4 + j] = (float)vc[k][j];
     }
-    float part = 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { part += d[j] * o[j]; q[j] *= qmul; d[j] *= a.drop.scale; }      // the dO image carries 1 / (1 - p): see sab_pass_a
+    for (int j = 0; j < 8; ++j) q[j] *= qmul;
     const bool in = i < R * 8;      // (wave-uniform)
     if (in) {
       *reinterpret_cast<bf16x8*>(sQ + r * TT_RS + c8) = pack8(q);
       *reinterpret_cast<bf16x8*>(sK + r * TT_RS + c8) = pack8(kk);
       *reinterpret_cast<bf16x8*>(sV + r * TT_RS + c8) = pack8(v);
-      *reinterpret_cast<bf16x8*>(sdO + r * TT_RS + c8) = pack8(d);
     }
+    float part;
+    if (hand) {      // the rows already are bf16(dO * drop.scale), delta the head's sum in this kernel's order (adt_tt.cuh: tt_head_delta_chunks)
+      bf16x8 db;
 #pragma unroll
-    for (int off = HD / 16; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);      // HD/8 adjacent lanes hold one head's chunks
+      for (int j = 0; j < 4; ++j) { db[j] = da[k][j]; db[4 + j] = dc[k][j]; }
+      if (in) *reinterpret_cast<bf16x8*>(sdO + r * TT_RS + c8) = db;
+      part = dlt[k];
+    } else {
+      float d[8], o[8];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { o[j] = (float)oa[k][j]; o[4 + j] = (float)oc[k][j]; d[j] = d0[k][j]; d[4 + j] = d1[k][j]; }
+      part = tt_chunk_delta(d, o);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) d[j] *= a.drop.scale;      // the dO image carries 1 / (1 - p): see sab_pass_a
+      if (in) *reinterpret_cast<bf16x8*>(sdO + r * TT_RS + c8) = pack8(d);
+#pragma unroll
+      for (int off = HD / 16; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);      // HD/8 adjacent lanes hold one head's chunks
+    }
     if (in && ((i & 7) % (HD / 8)) == 0) sDelta[((i & 7) / (HD / 8)) * R + r] = part;
   });
   XM_STAMP(2);
@@ -291,8 +315,9 @@ __global__ __launch_bounds__(XM_NW * 64) void k_seqtt_xattn_mid_bwd(XattnMidArgs
   const TT acc1v = tt_load(a.out1 + rowB * 64, validB && a.acc1, g);
   if (has) {
     tt_put_rows(img0, lA, da1, validA, g);
-    tt_put_rows(img1, lA, tt_saved_value(oreq, 1), validA, g);
-    tt_store(a.out0 + rowA * 64, tt_gemm(tt_bfrags(da1), wimg + TT_WIMG, c, g), validA, g);
+    const TT o1 = tt_saved_value(oreq, 1);
+    tt_put_rows(img1, lA, o1, validA, g);
+    sp_store_do1(a.out0, a.do_bf16, a.do_delta, a.do_scale, HD, rowA, tt_gemm(tt_bfrags(da1), wimg + TT_WIMG, c, g), o1, validA, g);
   }
   __syncthreads();
   sb_dw_product16<NW>(img0, img1, npair, nullptr, a.part[1] + (size_t)blockIdx.x * a.part_stride, sRed + 64, w, c, g);

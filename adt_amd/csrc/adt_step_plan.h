@@ -32,6 +32,8 @@ struct SeqSwitches {
   bool fwd_fused = true;       // ADT_FWD_FUSED      log_feats from the last encoder kernel, logits + BCE deferred to the backward's first side kernel
   bool embed3 = true;          // ADT_EMBED3         both embedding gradients and the positive-logit rows in one scatter (deferred path)
   bool bce_merged = true;      // ADT_BCE_MERGED     the forward's logits / BCE kernel rides on the loss launch (off: on the side stream)
+  // hand-overs between the backward's kernels (on by default)
+  bool do_bf16{true};          // ADT_DO_BF16        dO from an out-projection reverse to the attention backward behind it as bf16 operand rows + delta
 };
 
 constexpr bool adt_seq_head_ok(int hd) { return hd == 16 || hd == 32 || hd == 64; }
@@ -110,6 +112,7 @@ struct StepPlan {
   int side_sites;          // ADT_SIDE_STREAM bits
   bool side_dp;            // side stream in the two-phase backward
   bool loss_one_launch;    // every loss term in one k_loss_seeds launch
+  bool do_handover;        // the out-projection reverses hand dO to the attention backward behind them as bf16 rows + delta (adt_tt.cuh: tt_head_delta)
 };
 
 static inline StepPlan adt_step_plan(const StepFacts& f, const SeqSwitches& sw) {
@@ -146,6 +149,9 @@ static inline StepPlan adt_step_plan(const StepFacts& f, const SeqSwitches& sw) 
   p.side_sites = sw.side_stream & 7;
   p.side_dp = sw.side_stream_dp;
   p.loss_one_launch = nl <= 4;
+  // every producer (k_seqtt_post_bwd, k_seqtt_mid_bwd / k_seqtt_xattn_mid_bwd) and every consumer (k_seqtt_attn_pre_bwd, k_seq_attn_bwd /
+  // k_seqtt_xattn_mid_bwd) is a per-sequence kernel exactly where `parts` holds: the lean path, whose "not covered" is an error and never a staged fallback
+  p.do_handover = sw.do_bf16 && p.parts;
   return p;
 }
 

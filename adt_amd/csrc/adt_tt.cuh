@@ -130,10 +130,10 @@ ADT_DEVICE_INLINE void tt_store(float* row, const TT& t, bool valid, int g) {
 // token's row 128 contiguous bytes.  In natural order a lane wrote four 8-byte pieces and the write counter showed 1.6x the bytes
 // stored (profiles/r02_dec_fwd_pmc.json).  Every reader of these buffers goes through tt_load_bf16 / rows_load_saved / the bf16 staging
 // of k_seq_attn_bwd, which undo the permutation.
-ADT_DEVICE_INLINE void tt_store_bf16(__bf16* row, const TT& t, bool valid, int g) {
+ADT_DEVICE_INLINE void tt_store_bf16(__bf16* row, const TT& t, bool valid, int g, float mul = 1.0f) {
   if (!valid) return;
-  *reinterpret_cast<bf16x8*>(row + 16 * g) = tt_pack(t.v[0], t.v[1]);
-  *reinterpret_cast<bf16x8*>(row + 16 * g + 8) = tt_pack(t.v[2], t.v[3]);
+  *reinterpret_cast<bf16x8*>(row + 16 * g) = tt_pack(t.v[0], t.v[1], mul);
+  *reinterpret_cast<bf16x8*>(row + 16 * g + 8) = tt_pack(t.v[2], t.v[3], mul);
 }
 ADT_DEVICE_INLINE TT tt_load_bf16(const __bf16* row, bool valid, int g) {
   TT t;
@@ -238,6 +238,102 @@ ADT_DEVICE_INLINE uint32_t tt_color(uint32_t v) {
   v |= tt_xor16u(v);
   v |= tt_xor32u(v);
   return v;
+}
+
+// ---- dO handed from an out-projection reverse to the attention backward behind it ---------------------------------------------------
+// The attention backward wants two things of dO: bf16 MFMA operands of dO * drop.scale, and delta[h] = rowsum(dO . O) over the features of
+// head h in fp32.  The out-projection reverse in front of it holds dO and O of the same tokens as transposed tiles, so it forms both and
+// stores bf16 rows in the saved-row order (tt_store_bf16 with the scale: the consumer's own rounding, done earlier) plus delta[h] at
+// delta[row * 4 + h].  tt_head_delta is THE summation of the self-attention blocks' delta: producer and consumer both call it.
+//
+// Its multiply-adds are written out, fused or not, element by element.  As `part += dO * o` the contraction was the compiler's choice, and in
+// k_seqtt_attn_pre_bwd (every instantiation, both tile slots) it had fused the products of the tile's first TT_DELTA_FUSED<HD> elements
+// (e = 4 (h NT + nt) + r) into v_fma / v_fmac and paired the others into v_pk_mul_f32 followed by plain adds; the same loop in another kernel
+// came out differently (all v_pk_fma_f32), one rounding per product apart.  The pattern below is that of the consumer before the hand-over
+// existed, so that every result stays what it was; it has no other meaning.
+template <int HD> constexpr int TT_DELTA_FUSED = HD == 64 ? 6 : (HD == 32 ? 8 : 12);
+ADT_DEVICE_INLINE float tt_mul_then_add(float acc, float a, float b) {
+#pragma clang fp contract(off)
+  const float p = a * b;
+  return acc + p;
+}
+template <int HD>
+ADT_DEVICE_INLINE void tt_head_delta(const TT& dO, const TT& o, float (&delta)[64 / HD]) {
+  constexpr int H = 64 / HD, NT = HD / 16;
+#pragma unroll
+  for (int h = 0; h < H; ++h) {
+    float part = 0.f;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float d = dO.v[h * NT + nt][r], x = o.v[h * NT + nt][r];
+        part = 4 * (h * NT + nt) + r < TT_DELTA_FUSED<HD> ? __builtin_fmaf(d, x, part) : tt_mul_then_add(part, d, x);
+      }
+    delta[h] = tt_colsum(part);
+  }
+}
+// The cross-attention kernels (k_seq_attn_bwd, the prologue of k_seqtt_xattn_mid_bwd) sum delta differently: a thread holds the 8-feature chunk
+// c8 .. c8 + 7 of a row in natural order, sums its eight products in sequence (tt_chunk_delta: every step fused, as the compiler had
+// made them) and joins the HD / 8 chunks of a head over adjacent lanes by __shfl_xor with offsets HD / 16, .., 1.  In a transposed tile
+// chunk k = 2 nt + (g >> 1) of a token sits on the lane pair (g & ~1, g | 1): features 8 k .. 8 k + 3 on the even lane's v[nt], the next
+// four on the odd lane's.  tt_head_delta_chunks runs the first four steps of the chain on the even lane, hands the sum to the odd lane
+// (one permlane per tile row) which runs the other four -- the same chain, step for step -- and joins the chunks in the shuffles' order:
+// off >= 2 pairs chunks k and k ^ off of one lane pair (tiles nt and nt ^ (off / 2)), off = 1 the two lane pairs.  The sums are those of
+// the ODD lanes (g = 1, 3); the even lanes run the same instructions on values nobody reads.
+ADT_DEVICE_INLINE float tt_chunk_fma4(float part, const float* d, const float* o) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) part = __builtin_fmaf(d[j], o[j], part);
+  return part;
+}
+ADT_DEVICE_INLINE float tt_chunk_delta(const float (&d)[8], const float (&o)[8]) { return tt_chunk_fma4(tt_chunk_fma4(0.f, d, o), d + 4, o + 4); }
+template <int HD>
+ADT_DEVICE_INLINE void tt_head_delta_chunks(const TT& dO, const TT& o, float (&delta)[64 / HD]) {
+  constexpr int H = 64 / HD, NT = HD / 16;
+  float p[4];
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) {
+    const float d4[4] = {dO.v[nt][0], dO.v[nt][1], dO.v[nt][2], dO.v[nt][3]}, o4[4] = {o.v[nt][0], o.v[nt][1], o.v[nt][2], o.v[nt][3]};
+    p[nt] = tt_chunk_fma4(tt_xor16(tt_chunk_fma4(0.f, d4, o4)), d4, o4);
+  }
+#pragma unroll
+  for (int h = 0; h < H; ++h) {
+#pragma unroll
+    for (int off = NT / 2; off > 0; off >>= 1)
+#pragma unroll
+      for (int nt = 0; nt < off; ++nt) p[h * NT + nt] += p[h * NT + nt + off];
+    delta[h] = p[h * NT] + tt_xor32(p[h * NT]);
+  }
+}
+template <int H>
+ADT_DEVICE_INLINE void tt_delta_store(float* delta, size_t row, const float (&d)[H], bool valid, int g, int gsrc = 0) {
+  if (!valid || g != gsrc) return;      // tt_head_delta: every g lane of a token column holds the same sums ; tt_head_delta_chunks: the odd ones
+  float* p = delta + row * 4;
+  if constexpr (H == 4) *reinterpret_cast<float4*>(p) = make_float4(d[0], d[1], d[2], d[3]);
+  else if constexpr (H == 2) *reinterpret_cast<float2*>(p) = make_float2(d[0], d[1]);
+  else *p = d[0];
+}
+template <int H>
+ADT_DEVICE_INLINE void tt_delta_load(const float* delta, size_t row, bool valid, float (&d)[H]) {      // zeros for lanes without a token (see tt_load)
+  typedef float tt_fH __attribute__((ext_vector_type(H == 1 ? 2 : H)));      // (a one-element vector type does not exist: H == 1 reads the plain float below)
+  if constexpr (H == 1) {
+    typedef const float __attribute__((address_space(1))) * gf1;
+    d[0] = *(valid ? (gf1)(delta + row * 4) : (gf1)tt_zero_row);
+  } else {
+    typedef const tt_fH __attribute__((address_space(1))) * gfh;
+    const tt_fH v = *(valid ? (gfh)(delta + row * 4) : (gfh)tt_zero_row);
+#pragma unroll
+    for (int h = 0; h < H; ++h) d[h] = v[h];
+  }
+}
+// the handed-over rows of a lane's token, as stored: lo = elements (nt 0, 1), hi = (nt 2, 3) -- for head sizes 32 and 64 the operand fragments
+struct TTRowB { bf16x8 lo, hi; };
+ADT_DEVICE_INLINE TTRowB tt_load_bf16_raw(const __bf16* row, bool valid, int g) {
+  typedef const bf16x8 __attribute__((address_space(1))) * gp8;       // see tt_load
+  const gp8 p = valid ? (gp8)(row + 16 * g) : (gp8)(tt_zero_row + 8 * g);
+  TTRowB t;
+  t.lo = p[0]; t.hi = p[1];
+  return t;
 }
 
 // sum over the 16 lanes of a row (the 16 tokens of a tile, for one g): every lane ends up with the row total.  Four DPP steps in the
