@@ -127,6 +127,7 @@ SIGNATURES = {
     "adt_full_rank_from": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P]),
     "adt_wdist_pack": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _F, _P]),
     "adt_kldist_pack": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
+    "adt_klrow_pack": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P]),
     "adt_kldist_full_groups": (_I, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P]),
     "adt_seqbatch_build": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U, _U, _P, _P, _P, _P, _P, _P]),
     "adt_seqbatch_draw": (_I, [_U, _U, _I, _I, _I, _I]),

@@ -5,6 +5,7 @@
 #include "adt_fullrank.cuh"
 #include "adt_wdist_pack.cuh"
 #include "adt_kldist_groups.cuh"
+#include "adt_klrow_pack.cuh"
 
 using namespace adt;
 
@@ -99,6 +100,19 @@ int adt_kldist_pack(const float* Em, const float* Ec, int ld, int V, int d, floa
   KlPackArgs a{Em, Ec, ld, V, d, img, ldi, lv};
   hipLaunchKernelGGL(k_kldist_pack, dim3(adt_grid_for((size_t)V, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
   return adt_check_launch("kldist_pack");
+}
+
+int adt_klrow_pack(const float* M, const float* C, int ld, int rows, int d, int items, float* img, int ldi, float* off, void* stream) {
+  if (items != 0 && items != 1) return adt_set_error("klrow_pack: items=%d must be 0 (user states) or 1 (item tables)", items);
+  if (d < 4 || (d % 4)) return adt_set_error("klrow_pack: d=%d must be a positive multiple of 4", d);
+  if (ld < d || ldi < 2 * d) return adt_set_error("klrow_pack: ld=%d must be >= d=%d and ldi=%d >= 2d", ld, d, ldi);
+  if ((ld % 4) || (ldi % 4) || !adt_aligned16(M) || !adt_aligned16(C) || !adt_aligned16(img))
+    return adt_set_error("klrow_pack: M, C and img must be 16-byte aligned with ld %% 4 == 0 and ldi %% 4 == 0");
+  if (rows <= 0) return 0;
+  if (!M || !C || !img || !off) return adt_set_error("klrow_pack: missing operand");
+  KlRowPackArgs a{M, C, ld, rows, d, items, img, ldi, off};
+  hipLaunchKernelGGL(k_klrow_pack, dim3(adt_grid_for((size_t)rows, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("klrow_pack");
 }
 
 int adt_kldist_full_groups(const float* Sm, const float* Sc, int lds, const float* img, int ldi, const float* lv, int rows, int E, int V, int d,

@@ -1,0 +1,62 @@
+// STOSA-ADT full-catalogue ranking under distance_metric='kl': the row images that turn the ROW-WISE KL divergence -- kl_distance
+// (stosa/modules.py:45-50), the function bpr_optimization trains on, of the user's Gaussian (mu, cu) from the item's (mi, ci) -- into
+// the dot-product score of adt_fullrank.cuh.  With ci = w_elu1(Ec[v]):
+//
+//   KL[u][v] = 0.5 (sum cu / ci + sum (mi - mu)^2 / ci - d + sum log ci - sum log cu) = nu[u] - (A[u] . W[v] + bias[v])
+//
+//   A[u] = [mu^2 + cu | mu]      W[v] = [-0.5 / ci | mi / ci]      bias[v] = -0.5 (sum log ci + sum mi^2 / ci)      nu[u] = -0.5 (d + sum log cu)
+//
+// k_klrow_pack writes, per row r of a (mean, covariance) pair of tables, one of the two images and its offset:
+//   items = 1   c = w_elu1(C[r]);  img[r] = [-0.5 / c | M[r] / c];  off[r] = -0.5 (sum logf(c) + sum M[r]^2 / c)      -> (W, bias)
+//   items = 0   c = C[r];          img[r] = [M[r]^2 + c | M[r]];    off[r] = -0.5 (d + sum logf(c))                    -> (A, nu)
+// w_elu1 of adt_common.cuh is the function the KL loss and full-sort kernels apply to the same table entries; the user covariances are
+// the rows _last_state returns, the rows k_kldist_full takes logf of.  DESIGN.md section 20.
+//
+// The layout and the reduction of k_wdist_pack: 16 lanes per row, lane `sub` owns the float4 column groups sub, sub + 16, ... (16-byte
+// loads and stores); the two partial sums (logs, squared means over the covariance) are accumulated in ascending column order per lane
+// and meet in four xor-shuffles (8, 4, 2, 1), the same order for every row wherever it lands in the grid: the output is
+// bit-reproducible.  No atomics.
+#pragma once
+#include "adt_common.cuh"
+
+namespace adt {
+
+struct KlRowPackArgs {
+  const float* M; const float* C; int ld;      // rows x d each, row stride ld
+  int rows, d, items;
+  float* img; int ldi;                         // rows x 2d, row stride ldi
+  float* off;                                  // rows
+};
+
+__global__ __launch_bounds__(256) void k_klrow_pack(KlRowPackArgs a) {
+  const int sub = threadIdx.x & 15;
+  for (int r = blockIdx.x * 16 + (threadIdx.x >> 4); r < a.rows; r += gridDim.x * 16) {      // the 16 lanes of a row share r
+    const float* m = a.M + (size_t)r * a.ld;
+    const float* c = a.C + (size_t)r * a.ld;
+    float* o = a.img + (size_t)r * a.ldi;
+    float pl = 0.f, pq = 0.f;
+    for (int c4 = 4 * sub; c4 < a.d; c4 += 64) {
+      const float4 mv = *reinterpret_cast<const float4*>(m + c4);
+      float4 cv = *reinterpret_cast<const float4*>(c + c4);
+      if (a.items) {
+        cv = make_float4(w_elu1(cv.x), w_elu1(cv.y), w_elu1(cv.z), w_elu1(cv.w));
+        const float4 q = make_float4(mv.x / cv.x, mv.y / cv.y, mv.z / cv.z, mv.w / cv.w);
+        pq += mv.x * q.x; pq += mv.y * q.y; pq += mv.z * q.z; pq += mv.w * q.w;
+        *reinterpret_cast<float4*>(o + c4) = make_float4(-0.5f / cv.x, -0.5f / cv.y, -0.5f / cv.z, -0.5f / cv.w);
+        *reinterpret_cast<float4*>(o + a.d + c4) = q;
+      } else {
+        *reinterpret_cast<float4*>(o + c4) = make_float4(mv.x * mv.x + cv.x, mv.y * mv.y + cv.y, mv.z * mv.z + cv.z, mv.w * mv.w + cv.w);
+        *reinterpret_cast<float4*>(o + a.d + c4) = mv;
+      }
+      pl += logf(cv.x); pl += logf(cv.y); pl += logf(cv.z); pl += logf(cv.w);
+    }
+#pragma unroll
+    for (int s = 8; s > 0; s >>= 1) {
+      pl += __shfl_xor(pl, s, 64);
+      pq += __shfl_xor(pq, s, 64);
+    }
+    if (sub == 0) a.off[r] = -0.5f * (a.items ? pl + pq : (float)a.d + pl);
+  }
+}
+
+}  // namespace adt

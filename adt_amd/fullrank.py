@@ -3,7 +3,9 @@ adt_full_rank call on the final feature rows and the item table (include/adt_hip
 matrix exists at any point; only B ranks, B counts and the (B, k) best items come back.
 
 STOSA-ADT (DistRankMixin) ranks by ascending Wasserstein distance through the same kernel: adt_wdist_pack turns the two item tables and
-the users' last states into 2d-wide row images with dist[b][j] = na[b] - 2 (A[b] . W[j] + bias[j]) ("STOSA")."""
+the users' last states into 2d-wide row images with dist[b][j] = na[b] - 2 (A[b] . W[j] + bias[j]) ("STOSA").
+A distance_metric='kl' model ranks on request (rowwise=True) by the row-wise KL divergence it is trained on, the same way:
+adt_klrow_pack's images give KL[b][j] = nu[b] - (A[b] . W[j] + bias[j])."""
 import numpy as np
 import torch
 
@@ -66,14 +68,30 @@ def fused_ids_or_two_pass(top_idx, two_pass):
     return ids, False
 
 
+def kl_dist_from_scores(nu, top_idx, top_val):
+    """Scores of adt_full_rank on adt_klrow_pack's images back to row-wise KL divergences: top_dist = nu[:, None] - top_val (ascending, as
+    top_val descends); +inf where top_idx is -1."""
+    dist = nu[:, None] - top_val
+    return torch.where(top_idx < 0, torch.full_like(dist, float("inf")), dist)
+
+
 class DistRankMixin:
     """A model supplies _dist_tables() -> (Em, Ec, n_items): the item mean / raw covariance tables (n_items + 1 rows are ranked) and
-    _last_state(input_ids) -> (sm, sc): the (B, d) mean / covariance of the last position.  Wasserstein distance only."""
+    _last_state(input_ids) -> (sm, sc): the (B, d) mean / covariance of the last position.  Wasserstein distance by default; a model with
+    distance_metric 'kl' ranks only on request (rowwise=True), by the row-wise KL divergence it is trained on."""
 
     def _check_wasserstein(self):
         if getattr(self, "distance_metric", "wasserstein") != "wasserstein":
             raise _lib.AdtError("fused full-catalogue ranking is built for distance_metric='wasserstein' only: the %r scores depend on the eval "
                                 "batch's size and row order, not on (user, item) alone; use predict_full + topk_masked" % (self.distance_metric,))
+
+    def _rowwise_kl(self, rowwise):
+        """True when this call ranks by the row-wise KL divergence: a KL model that was asked to.  A KL model that was not asked raises as
+        it always has; a Wasserstein model is row-wise already, so `rowwise` changes nothing for it."""
+        if getattr(self, "distance_metric", "wasserstein") == "kl" and rowwise:
+            return True
+        self._check_wasserstein()
+        return False
 
     @torch.no_grad()
     def item_image(self):
@@ -84,28 +102,47 @@ class DistRankMixin:
         return ops.wdist_pack(Em, Ec, True, -0.5)
 
     @torch.no_grad()
-    def _rank_states(self, sm, sc, targets, seen, topk, image, first_id):
-        W, bias = self.item_image() if image is None else image
+    def kl_row_image(self):
+        """item_image() of a KL model for rowwise=True: (W, bias) with KL[u][v] = nu[u] - (A[u] . W[v] + bias[v]) (ops.klrow_pack).  Packed
+        on every call, no cache, as item_image().  A Wasserstein model raises."""
+        if getattr(self, "distance_metric", "wasserstein") != "kl":
+            raise _lib.AdtError("kl_row_image is the item image of distance_metric='kl'; a %r model ranks on item_image()"
+                                % (getattr(self, "distance_metric", "wasserstein"),))
+        Em, Ec, _ = self._dist_tables()
+        return ops.klrow_pack(Em, Ec, True)
+
+    @torch.no_grad()
+    def _rank_states(self, sm, sc, targets, seen, topk, image, first_id, rowwise=False):
+        kl = self._rowwise_kl(rowwise)
+        if image is None:
+            image = self.kl_row_image() if kl else self.item_image()
+        W, bias = image
         n_items = self._dist_tables()[2]
-        A, na = ops.wdist_pack(sm, sc, False, 1.0)
+        A, na = ops.klrow_pack(sm, sc, False) if kl else ops.wdist_pack(sm, sc, False, 1.0)
         B = A.shape[0]
         indptr, indices = _seen(seen, B, A.device)
         rank, n_elig, top_idx, top_val = ops.full_rank(A, A.stride(0), W, n_items, _targets(targets, B, A.device), bias, indptr, indices, topk,
                                                        first_id=first_id)
-        return rank, n_elig, top_idx, (None if top_idx is None else dist_from_scores(na, top_idx, top_val))
+        if top_idx is None:
+            return rank, n_elig, None, None
+        return rank, n_elig, top_idx, (kl_dist_from_scores if kl else dist_from_scores)(na, top_idx, top_val)
 
     @torch.no_grad()
-    def rank_full(self, input_ids, targets, seen=None, topk=0, image=None, first_id=1):
+    def rank_full(self, input_ids, targets, seen=None, topk=0, image=None, first_id=1, rowwise=False):
         """As FullRankMixin.rank_full with `smaller distance` for `higher score`: (rank (B,) -- eligible items strictly closer than the
         target, -1 without one --, n_elig (B,), top_idx (B, topk), top_dist (B, topk) ascending, ties to the smaller id, -1 / +inf
         tail).  image: item_image() of the current weights; first_id = 0 lets the padding item 0 compete, as the reference's full sort
-        does (targets stay 1..n_items)."""
-        self._check_wasserstein()
-        sm, sc = self._last_state(input_ids)
-        return self._rank_states(sm, sc, targets, seen, topk, image, first_id)
+        does (targets stay 1..n_items).
 
-    def recommend(self, input_ids, k, seen=None, image=None):
+        rowwise=True on a distance_metric='kl' model (which raises without it): the distance is the row-wise KL divergence of the user's
+        last state from the item, kl_distance -- the function the model is trained on -- NOT the reference's batch-dependent
+        kl_predict_full score; image is then kl_row_image().  On a Wasserstein model rowwise changes nothing."""
+        self._rowwise_kl(rowwise)
+        sm, sc = self._last_state(input_ids)
+        return self._rank_states(sm, sc, targets, seen, topk, image, first_id, rowwise)
+
+    def recommend(self, input_ids, k, seen=None, image=None, rowwise=False):
         """The k closest unseen items of every user: (ids (B, k) int32, distances (B, k)), closest first; -1 / +inf where fewer than k
-        items are left.  The padding item 0 is never recommended."""
-        _, _, idx, dist = self.rank_full(input_ids, None, seen, k, image, 1)
+        items are left.  The padding item 0 is never recommended.  rowwise: as rank_full."""
+        _, _, idx, dist = self.rank_full(input_ids, None, seen, k, image, 1, rowwise)
         return idx, dist

@@ -679,6 +679,19 @@ def kldist_pack(Em, Ec):
     return img, lv
 
 
+def klrow_pack(M, C, items):
+    """Row images for full-catalogue ranking by the row-wise KL divergence (adt_klrow_pack), KL[u][v] = nu[u] - (A[u] . W[v] + bias[v]).
+    Items (items=True): c = ELU(C) + 1, img (rows, 2d) = [-0.5 / c | M / c], off (rows,) = -0.5 (sum log c + sum M^2 / c) -> (W, bias) of
+    full_rank; user states (items=False): c = C, img = [M^2 + c | M], off = -0.5 (d + sum log c) -> (A, nu)."""
+    assert M.dim() == 2 and M.shape == C.shape and M.stride(0) == C.stride(0), (M.shape, C.shape, M.stride(), C.stride())
+    rows, d = M.shape
+    img = torch.empty(rows, 2 * d, device=M.device, dtype=torch.float32)
+    off = torch.empty(rows, device=M.device, dtype=torch.float32)
+    _lib.check(_lib.load().adt_klrow_pack(_p(_f32(M)), _p(_f32(C)), M.stride(0), rows, d, int(bool(items)), _p(img), 2 * d, _p(off), _stream()),
+               "klrow_pack")
+    return img, off
+
+
 def kldist_full_groups(Sm, Sc, img, lv, E, V):
     """kl_predict_full for the P = rows / E stacked eval batches of E users each (candidate-major rows of Sm / Sc) against the packed
     items (kldist_pack): dist (rows, V).  The reference's chunking by E pairs the rows of one group only; rows == E is kldist_full to

@@ -60,7 +60,13 @@ def parse_args(argv=None):
                         "stays on host batches")
     p.add_argument("--device_scores", action="store_true",
                    help="score candidates on the GPU: one histogram of hit positions per candidate (adt_hit_hist) instead of id lists on the host")
+    p.add_argument("--rowwise_eval", action="store_true",
+                   help="with --distance_metric kl: score candidates by the row-wise KL divergence the supernet is trained on (kl_distance of the "
+                        "user's last state from each item; adt_klrow_pack + adt_full_rank_from, no distance matrix).  These are NOT the "
+                        "reference's kl_predict_full metrics, whose scores depend on the eval batch's size and row order")
     args = p.parse_args(argv)
+    if args.rowwise_eval and args.distance_metric != "kl":
+        p.error("--rowwise_eval needs --distance_metric kl: the Wasserstein distance is row-wise already")
     if args.fused_eval and args.distance_metric == "kl":
         p.error("--fused_eval is built for --distance_metric wasserstein only: a KL score depends on the eval batch, not on (user, item) alone")
     return args

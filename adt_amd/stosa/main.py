@@ -57,7 +57,18 @@ def parse_args(argv=None):
                    help="build the training and evaluation batches on the GPU from resident sequences (adt_seqbatch_build) instead of on the host")
     p.add_argument("--device_scores", action="store_true",
                    help="score the full sort on the GPU: a histogram of hit positions (adt_hit_hist) instead of the (N, 40) id lists on the host")
-    return p.parse_args(argv)
+    p.add_argument("--rowwise_eval", action="store_true",
+                   help="with --distance_metric kl: full-sort evaluation by the row-wise KL divergence the model is trained on (kl_distance of "
+                        "the user's last state from each item; adt_klrow_pack + adt_full_rank_from, no (B, item_size) matrix).  These are NOT "
+                        "the reference's kl_predict_full metrics, whose scores depend on the eval batch's size and row order; they do not "
+                        "move with --eval_batch_size or the number of GPUs")
+    args = p.parse_args(argv)
+    if args.rowwise_eval and args.distance_metric != "kl":
+        p.error("--rowwise_eval needs --distance_metric kl: the Wasserstein distance is row-wise already")
+    if args.fused_eval and args.distance_metric == "kl":      # full_sort(fused=True) raises under KL: refuse before an epoch is trained
+        p.error("--fused_eval is built for --distance_metric wasserstein only: a KL score depends on the eval batch, not on (user, item) alone "
+                "(--rowwise_eval ranks by the row-wise divergence)")
+    return args
 
 
 def _write_synthetic(path, users=22363, items=12101, seed=42):
@@ -73,12 +84,13 @@ def _write_synthetic(path, users=22363, items=12101, seed=42):
             f.write("%d %s\n" % (u, " ".join(str(int(x)) for x in seq)))
 
 
-def _evaluate(trainer, ds, matrix, batch_size, fused=False, dev_data=None, device_scores=False):
+def _evaluate(trainer, ds, matrix, batch_size, fused=False, dev_data=None, device_scores=False, rowwise=False):
     """Full-sort scores of the whole user set on every rank: under data parallelism rank r sorts batches r, r+W, ... on its GPU
     and the (N, 40) id lists are gathered (a few hundred KB).  dev_data (--device_batches): the same batches of the same users, cut on
     the GPU by DeviceDisenData.eval_batch.  device_scores (--device_scores): the id lists stay on the GPU; every rank keeps the
     41-entry histogram of hit positions (FusedStosaTrainer.full_sort_hist), the ranks sum theirs with one all-reduce, and the 13
-    numbers come from scores_from_hist."""
+    numbers come from scores_from_hist.  rowwise (--rowwise_eval): FusedStosaTrainer.full_sort(rowwise=True), a per-user score, so the
+    metrics do not depend on how the batches are cut or dealt to the ranks."""
     def gen():
         if dev_data is not None:
             cut = dev_data.eval_stage if device_scores else dev_data.eval_batch
@@ -90,11 +102,11 @@ def _evaluate(trainer, ds, matrix, batch_size, fused=False, dev_data=None, devic
             if i % trainer.world == trainer.rank:
                 yield inp, matrix[users], ans
     if device_scores:
-        hist = trainer.full_sort_hist(gen(), fused=fused)
+        hist = trainer.full_sort_hist(gen(), fused=fused, rowwise=rowwise)
         if trainer.world > 1:
             torch.distributed.all_reduce(hist, op=torch.distributed.ReduceOp.SUM, group=trainer.pg)
         return scores_from_hist(hist.cpu().numpy())
-    pred, answers = trainer.full_sort(gen(), fused=fused)
+    pred, answers = trainer.full_sort(gen(), fused=fused, rowwise=rowwise)
     if trainer.world > 1:
         parts = [None] * trainer.world
         torch.distributed.all_gather_object(parts, (pred, answers), group=trainer.pg)
@@ -172,7 +184,7 @@ def main(argv=None):
                 nseq += len(users)
         torch.cuda.synchronize()
         T += time.time() - t0
-        scores = _evaluate(trainer, valid_ds, valid_matrix, args.eval_batch_size, args.fused_eval, dev_data, args.device_scores)
+        scores = _evaluate(trainer, valid_ds, valid_matrix, args.eval_batch_size, args.fused_eval, dev_data, args.device_scores, args.rowwise_eval)
         parts = trainer.loss_parts().cpu().numpy()      # a collective under data parallelism: every rank calls it
         if rank == 0:
             print(json.dumps({"epoch": epoch, "train_seconds": T, "sequences_per_sec": nseq / max(T, 1e-9), "n_gpus": world,
@@ -189,8 +201,8 @@ def main(argv=None):
     if world > 1:
         torch.distributed.barrier()
     model.load_state_dict(torch.load(ckpt))
-    valid_scores = _evaluate(trainer, valid_ds, valid_matrix, args.eval_batch_size, args.fused_eval, dev_data, args.device_scores)
-    scores = _evaluate(trainer, test_ds, test_matrix, args.eval_batch_size, args.fused_eval, dev_data, args.device_scores)
+    valid_scores = _evaluate(trainer, valid_ds, valid_matrix, args.eval_batch_size, args.fused_eval, dev_data, args.device_scores, args.rowwise_eval)
+    scores = _evaluate(trainer, test_ds, test_matrix, args.eval_batch_size, args.fused_eval, dev_data, args.device_scores, args.rowwise_eval)
     if rank == 0:
         print("(%s, %s, %s, %s, %s, %s, %s, %s)" % (valid_scores[0], valid_scores[2], valid_scores[3], valid_scores[-1], scores[0], scores[2], scores[3], scores[-1]))
     if pg is not None:

@@ -48,7 +48,8 @@ class SearcherEvolution:
         return self.search_state.vis_dict
 
     def _evaluate_for_search(self, cands):
-        return self.evaluate_candidates(cands, fused=bool(getattr(self.args, "fused_eval", False)))
+        return self.evaluate_candidates(cands, fused=bool(getattr(self.args, "fused_eval", False)),
+                                        rowwise=bool(getattr(self.args, "rowwise_eval", False)))
 
     def _stack_csr(self, ip, ix, copies):
         """Host CSR (indptr, indices) of one batch, repeated for `copies` stacked candidates, on the device."""
@@ -96,7 +97,8 @@ class SearcherEvolution:
             yield {"inp": inp, "answers_host": np.asarray(ans), "min_unseen": self.args.item_size - most,
                    "stack": lambda copies, csr=csr: self._stack_csr(csr.indptr, csr.indices, copies)}
 
-    def evaluate_candidates(self, cands, dataset=None, matrix=None, group=8, prefix="V", fused=False, device_batches=None, device_scores=None):
+    def evaluate_candidates(self, cands, dataset=None, matrix=None, group=8, prefix="V", fused=False, device_batches=None, device_scores=None,
+                            rowwise=False):
         """Full-sort scores (Trainer.get_full_sort_score, stosa/trainer.py:62-86) of the supernet under every candidate of `cands`:
         every validation batch is ranked for `group` candidates per pass (distances, seen-item masking and top-40 on the device).
         fused (the search passes args.fused_eval; default off): the item image is packed once per call -- the candidates share the item tables --
@@ -111,7 +113,12 @@ class SearcherEvolution:
         read-back, and one copy after the last batch feeds scores_from_hist per candidate (kept as self.last_hists).
 
         distance_metric 'kl' (DESIGN.md section 19): the KL item image is packed once per call and every pass is one
-        adt_kldist_full_groups call with E = the batch's rows (the trailing batch has its own E); fused=True is an AdtError."""
+        adt_kldist_full_groups call with E = the batch's rows (the trailing batch has its own E); fused=True is an AdtError.
+
+        rowwise=True under 'kl' (nothing changes under Wasserstein): candidates are ranked by the row-wise KL
+        divergence the model is trained on, not by kl_predict_full's batch-dependent score.  kl_row_image() is packed once per call and
+        every pass is one rank_full_candidates(first_id=0, rowwise=True); no pass falls back -- a row with fewer than 40 unseen items
+        keeps its -1 tail, which the metrics count as no hit."""
         device_batches = bool(getattr(self.args, "device_batches", False)) if device_batches is None else device_batches
         device_scores = bool(getattr(self.args, "device_scores", False)) if device_scores is None else device_scores
         kl = self.model.distance_metric == "kl"
@@ -119,7 +126,9 @@ class SearcherEvolution:
             raise AdtError("evaluate_candidates(fused=True): the fused ranking is built for distance_metric='wasserstein' only; 'kl' scores "
                            "through the distance matrix (adt_kldist_full_groups)")
         image = self.model.item_image() if fused else None
-        kl_image = self.model.kl_item_image() if kl else None      # the candidates share the item tables: packed once per call
+        rowwise = bool(rowwise) and kl
+        kl_image = self.model.kl_item_image() if kl and not rowwise else None      # the candidates share the item tables: packed once per call
+        row_image = self.model.kl_row_image() if rowwise else None
         ds = self.valid_ds if dataset is None else dataset
         matrix = self.valid_matrix if matrix is None else matrix
         dev = self.model.dev
@@ -145,12 +154,19 @@ class SearcherEvolution:
 
                 def fused_device():
                     return self.model.rank_full_candidates(inp, sl, None, (indptr, indices), 40, image, self.eval_stats, first_id=0)[2]
+
+                def rowwise_device():
+                    return self.model.rank_full_candidates(inp, sl, None, (indptr, indices), 40, row_image, self.eval_stats, first_id=0,
+                                                           rowwise=True)[2]
                 if device_scores:
-                    top_idx = fused_device() if fused and st["min_unseen"] >= 40 else two_pass_device()
+                    top_idx = rowwise_device() if rowwise else fused_device() if fused and st["min_unseen"] >= 40 else two_pass_device()
                     ops.hit_hist(top_idx, ans_dev, rows_per_group=B, hist=H[g0:g0 + len(sl)])
                     continue
                 two_pass = lambda: two_pass_device().cpu().numpy().astype(np.int64)
-                top = fused_ids_or_two_pass(fused_device(), two_pass)[0] if fused else two_pass()
+                if rowwise:
+                    top = rowwise_device().cpu().numpy().astype(np.int64)
+                else:
+                    top = fused_ids_or_two_pass(fused_device(), two_pass)[0] if fused else two_pass()
                 for k in range(len(sl)):
                     preds[g0 + k].append(top[k * B:(k + 1) * B])
         if device_scores:

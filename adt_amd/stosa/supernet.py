@@ -131,19 +131,21 @@ class DisenDistSASupernet(DisenDistSAModel):
         return ops.wdist_full(sm, sc, self.P("item_mean_embeddings.weight"), self.P("item_cov_embeddings.weight"), self.item_size)
 
     @torch.no_grad()
-    def rank_full_candidates(self, input_ids, shared_list, targets=None, seen=None, topk=0, image=None, stats=None, first_id=1):
+    def rank_full_candidates(self, input_ids, shared_list, targets=None, seen=None, topk=0, image=None, stats=None, first_id=1, rowwise=False):
         """DistRankMixin.rank_full under every block choice of `shared_list` with ONE fused call on the stacked P * B last states:
         (rank, n_elig, top_idx, top_dist) with P * B rows, candidate-major.  targets: (B,) (repeated per candidate), (P * B,) or None;
         seen: the CSR of the P * B stacked rows (any form ops.seen_csr takes, or a device (indptr, indices) pair); image: item_image().
-        Wasserstein only (DistRankMixin._check_wasserstein): a KL score is not a function of (user, item) alone."""
-        self._check_wasserstein()
+        Wasserstein by default (DistRankMixin._check_wasserstein): the reference's KL score is not a function of (user, item) alone.
+        rowwise=True under 'kl' ranks by the row-wise KL divergence instead (DistRankMixin.rank_full); image: kl_row_image(), packed
+        once here when None -- the candidates share the item tables."""
+        self._rowwise_kl(rowwise)
         sm, sc = self._last_state_candidates(input_ids, shared_list, stats)
         PB = sm.shape[0]
         if targets is not None:
             targets = torch.as_tensor(np.asarray(targets.cpu() if isinstance(targets, torch.Tensor) else targets)).reshape(-1)
             if targets.numel() != PB:
                 targets = targets.repeat(len(shared_list))
-        return self._rank_states(sm, sc, targets, seen, topk, image, first_id)
+        return self._rank_states(sm, sc, targets, seen, topk, image, first_id, rowwise)
 
 
 class SuperStosaTrainer(SupernetTrainer):

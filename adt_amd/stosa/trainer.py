@@ -59,8 +59,13 @@ class FusedStosaTrainer(TapeTrainer):
         self.step_staged(dict(st, norms=self._device_norms[key]), b_offset)
 
     # ------------------------------------------------------------------------------------------------------------------
+    def _rowwise_kl(self, rowwise):
+        """rowwise=True on a KL model: rank by the row-wise KL divergence (DistRankMixin.rank_full).  On a Wasserstein
+        model the keyword changes nothing: that distance is row-wise already."""
+        return bool(rowwise) and self.model.distance_metric == "kl"
+
     @torch.no_grad()
-    def full_sort(self, batches, topk=40, fused=False):
+    def full_sort(self, batches, topk=40, fused=False, rowwise=False):
         """Full-sort evaluation (stosa/trainer.py:583-612) over an iterable of (input_ids (B, L), seen, answers (B, A)): rank all
         items by ascending distance with the seen items pushed to 1e24 and keep `topk`, all on the device (model.predict_full: adt_wdist_full,
         or adt_kldist_full for distance_metric 'kl', whose scores depend on each batch's rows being the eval batch -- pass the reference's
@@ -72,11 +77,18 @@ class FusedStosaTrainer(TapeTrainer):
         fused=True (Wasserstein only; 'kl' raises): no (B, item_size) distance matrix -- the item image is packed once for all batches
         (adt_wdist_pack) and every batch is one adt_full_rank_from call with first_id = 0 (the padding item competes, as in the
         reference).  A batch in which some user has fewer than `topk` unseen items is recomputed by the two-pass form, whose list
-        continues into the seen items the way the reference's does."""
+        continues into the seen items the way the reference's does.
+
+        rowwise=True on a 'kl' model (fused=True still raises): the ranking by the row-wise KL divergence the model is trained on, not
+        by kl_predict_full's batch-dependent score -- kl_row_image() packed once, every batch one rank_full(first_id=0, rowwise=True).
+        There is no matrix form to fall back to: a row with fewer than `topk` unseen items keeps its -1 tail, which holds no held-out
+        item (one is never in the seen list) and which the metrics count as no hit."""
         preds, answers = [], []
         m = self.model
         dev = m.dev
         image = m.item_image() if fused else None
+        rowwise = self._rowwise_kl(rowwise)
+        row_image = m.kl_row_image() if rowwise else None
         self.fused_fallbacks = 0
 
         def two_pass(input_ids, indptr, indices):
@@ -85,7 +97,9 @@ class FusedStosaTrainer(TapeTrainer):
             indptr, indices = _seen(seen, len(input_ids), dev)
             if indices is not None and indices.numel() == 0:      # a device pair that lists nothing: as the host forms, no seen list
                 indptr, indices = None, None
-            if fused:
+            if rowwise:
+                preds.append(m.rank_full(input_ids, None, (indptr, indices), topk, row_image, first_id=0, rowwise=True)[2].cpu().numpy().astype(np.int64))
+            elif fused:
                 _, _, top_idx, _ = m.rank_full(input_ids, None, (indptr, indices), topk, image, first_id=0)
                 ids, fell_back = fused_ids_or_two_pass(top_idx, lambda: two_pass(input_ids, indptr, indices))
                 self.fused_fallbacks += int(fell_back)
@@ -96,7 +110,7 @@ class FusedStosaTrainer(TapeTrainer):
         return np.concatenate(preds), np.concatenate(answers)
 
     @torch.no_grad()
-    def full_sort_scores(self, batches, topk=40, fused=False):
+    def full_sort_scores(self, batches, topk=40, fused=False, rowwise=False):
         """full_sort + get_full_sort_score without the id lists leaving the GPU: the same loop over the same
         batches, both distance metrics ('kl' two-pass only: fused=True raises as in full_sort), but every batch's (B, topk) device ids go
         straight into ops.hit_hist with the batch's held-out ids (one per user; uploaded as int32 when they arrive as numpy, used where
@@ -108,17 +122,19 @@ class FusedStosaTrainer(TapeTrainer):
         item_size - (its seen count) candidates (first_id = 0: all item_size ids compete), so the batch falls back when the smallest such
         count is below topk.  The count comes from the host indptr of a host `seen` (a repeated stored id only makes it larger: more
         fallbacks, never fewer, and the two-pass form is the reference's own); for a device (indptr, indices) pair the caller passes it as
-        min_unseen.  Sets self.fused_fallbacks as full_sort does."""
-        hist = self.full_sort_hist(batches, topk, fused).cpu().numpy()
+        min_unseen.  Sets self.fused_fallbacks as full_sort does.  rowwise: as full_sort; no batch falls back and min_unseen is not read."""
+        hist = self.full_sort_hist(batches, topk, fused, rowwise).cpu().numpy()
         return scores_from_hist(hist), hist
 
     @torch.no_grad()
-    def full_sort_hist(self, batches, topk=40, fused=False):
+    def full_sort_hist(self, batches, topk=40, fused=False, rowwise=False):
         """The loop of full_sort_scores; returns the (topk + 1,) int64 histogram still on the device (data-parallel callers all-reduce it
         before the copy)."""
         m = self.model
         dev = m.dev
         image = m.item_image() if fused else None
+        rowwise = self._rowwise_kl(rowwise)
+        row_image = m.kl_row_image() if rowwise else None
         self.fused_fallbacks = 0
         hist = torch.zeros(1, topk + 1, device=dev, dtype=torch.int64)
         for batch in batches:
@@ -143,7 +159,9 @@ class FusedStosaTrainer(TapeTrainer):
                 ans = np.asarray(ans)
                 assert ans.ndim == 1 or ans.shape[1] == 1, "scores_from_hist needs one held-out item per user"
                 ans = torch.from_numpy(np.ascontiguousarray(ans.reshape(-1), dtype=np.int32)).to(dev)
-            if fused and min_unseen >= topk:
+            if rowwise:
+                top_idx = m.rank_full(input_ids, None, (indptr, indices), topk, row_image, first_id=0, rowwise=True)[2]
+            elif fused and min_unseen >= topk:
                 top_idx = m.rank_full(input_ids, None, (indptr, indices), topk, image, first_id=0)[2]
             else:
                 self.fused_fallbacks += int(bool(fused))

@@ -351,6 +351,15 @@ int adt_wdist_pack(const float* M, const float* C, int ld, int rows, int d, int 
  * img[v][0..d) = Em[v], img[v][d..2d) = 1 / ci_v, lv[v] = sum_c logf(ci_v[c]) with ci = ELU(Ec) + 1; d % 4 == 0, ld >= d, ldi >= 2d, both
  * multiples of 4, Em / Ec / img 16-byte aligned.  Bit-reproducible (fixed reduction order). */
 int adt_kldist_pack(const float* Em, const float* Ec, int ld, int V, int d, float* img, int ldi, float* lv, void* stream);
+/* Row images for full-catalogue ranking by the ROW-WISE KL divergence (adt_klrow_pack.cuh): kl_distance (stosa/modules.py:45-50) of the
+ * user's Gaussian (mu, cu) from the item's (mi, ci), ci = ELU(Ec) + 1 -- the function a KL model is trained on, of (user, item) alone:
+ *   KL[u][v] = 0.5 (sum cu / ci + sum (mi - mu)^2 / ci - d + sum log ci - sum log cu) = nu[u] - (A[u] . W[v] + bias[v])
+ * so ascending KL is descending A[u] . W[v] + bias[v] = adt_full_rank's score.  Per row r:
+ *   items = 1: c = ELU(C[r]) + 1, img[r][0..d) = -0.5 / c, img[r][d..2d) = M[r] / c, off[r] = -0.5 (sum logf(c) + sum M[r]^2 / c)  (W, bias)
+ *   items = 0: c = C[r] as given, img[r][0..d) = M[r]^2 + c, img[r][d..2d) = M[r],    off[r] = -0.5 (d + sum logf(c))               (A, nu)
+ * d % 4 == 0, ld >= d, ldi >= 2d, both multiples of 4, M / C / img 16-byte aligned, items 0 or 1; rows <= 0 does nothing.
+ * Bit-reproducible (fixed reduction order). */
+int adt_klrow_pack(const float* M, const float* C, int ld, int rows, int d, int items, float* img, int ldi, float* off, void* stream);
 /* rows = P * E state rows, candidate-major: row r is user u = r % E of group g = r / E, and the reference's chunking by E items pairs rows
  * of ONE group only.  For item v = cE + j and a = cE + u (a >= V: a padding item, zero mean and unit covariance)
  *   dist[r][v] = 0.5 (lv[v] - sum_c logf(Sc[r][c]) + sum_c (Sm[gE + u][c] - img[a][c])^2 img[v][d + c] + sum_c Sc[gE + j][c] img[a][d + c] - d)

@@ -19,7 +19,14 @@ STOSA-ADT (KL) full-sort distances at the same shape, E = B = 512, one line for 
 P adt_kldist_full calls, one per candidate (the only correct route without the group rule), (b) groups = one adt_kldist_full_groups
 call on a pre-packed image, (c) pack = adt_kldist_pack alone.  Inputs have trained magnitudes (tables 0.3 N(0, 1), covariances
 exp(0.2 N(0, 1))).  The forms ALTERNATE inside every repetition (loop, groups, pack, loop, ...), so a drift of the clocks falls on
-all of them alike; 3 warm-up rounds, 5 timed ones."""
+all of them alike; 3 warm-up rounds, 5 timed ones.
+
+  python tools/bench_fullrank.py --stosa --metric kl --rowwise [--out profiles/r20_stosa_kl_rowwise.jsonl]
+
+STOSA-ADT (KL) ranked by the ROW-WISE divergence at the same shape (K 40, 100 seen items per user, first_id = 0), P = 1 and 8, the same
+inputs and the same alternating scheme: (a) rowwise = the user-state pack (adt_klrow_pack, items = 0) + adt_full_rank_from on a
+pre-packed image, (b) pack = the item pack alone (items = 1), (c) matrix = adt_kldist_full_groups + adt_topk_masked, for context only:
+it ranks by kl_predict_full's batch-dependent score, a different function."""
 import argparse
 import json
 import os
@@ -98,6 +105,38 @@ def stosa_kl_lines(dev):
     return lines
 
 
+def stosa_kl_rowwise_lines(dev):
+    V, d, E, K = 12103, 64, B, 40
+    lines = []
+    for P in (1, 8):
+        rows = P * E
+        g = torch.Generator(device="cpu").manual_seed(V + P)
+        Em, Ec = (0.3 * torch.randn(V, d, generator=g)).to(dev), (0.3 * torch.randn(V, d, generator=g)).to(dev)
+        sm, sc = (0.3 * torch.randn(rows, d, generator=g)).to(dev), torch.exp(0.2 * torch.randn(rows, d, generator=g)).to(dev)
+        r = np.random.RandomState(V + P)
+        indptr = torch.arange(0, (rows + 1) * SEEN, SEEN, dtype=torch.int32, device=dev)
+        indices = torch.from_numpy(r.randint(0, V, rows * SEEN).astype(np.int32)).to(dev)
+        image = ops.klrow_pack(Em, Ec, True)
+        kl_image = ops.kldist_pack(Em, Ec)
+
+        def rowwise():
+            A, nu = ops.klrow_pack(sm, sc, False)
+            return ops.full_rank(A, 2 * d, image[0], V - 1, None, image[1], indptr, indices, K, first_id=0)
+
+        def matrix():      # for context only: kl_predict_full's matrix and its selection -- a DIFFERENT, batch-dependent score
+            return ops.topk_masked(ops.kldist_full_groups(sm, sc, kl_image[0], kl_image[1], E, V), K, indptr, indices, want_val=True)
+
+        rec = {"shape": "stosa-beauty", "metric": "kl", "rowwise": True, "V": V, "d": d, "B": B, "candidates": P, "K": K, "seen_per_user": SEEN,
+               "first_id": 0}
+        rec.update(timed_alternating({"rowwise": rowwise, "pack": lambda: ops.klrow_pack(Em, Ec, True), "matrix": matrix}))
+        rec["hbm_bytes_rowwise"] = V * (2 * d + 1) * 4 + 3 * rows * 2 * d * 4      # the image and bias; the states read, their image written and read
+        rec["hbm_bytes_pack"] = 2 * V * d * 4 + V * (2 * d + 1) * 4
+        rec["hbm_bytes_matrix"] = V * (2 * d + 1) * 4 + rows * 2 * d * 4 + 2 * rows * V * 4
+        print(json.dumps(rec), flush=True)
+        lines.append(json.dumps(rec))
+    return lines
+
+
 def stosa_lines(dev):
     V, d, K = 12103, 64, 40
     lines = []
@@ -138,15 +177,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--stosa", action="store_true", help="the STOSA-ADT (Wasserstein) Beauty shape instead of the dot-product shapes")
     ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl"], help="with --stosa: kl = the grouped KL full sort against P adt_kldist_full calls")
+    ap.add_argument("--rowwise", action="store_true", help="with --stosa --metric kl: the ranking by the row-wise KL divergence (adt_klrow_pack + adt_full_rank_from)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     kl = args.stosa and args.metric == "kl"
     if args.metric == "kl" and not args.stosa:
         ap.error("--metric kl goes with --stosa")
+    if args.rowwise and not kl:
+        ap.error("--rowwise goes with --stosa --metric kl")
     if args.out is None:
-        args.out = os.path.join("profiles", "r18_stosa_kl_full.jsonl" if kl else "r08_stosa_fullrank.jsonl" if args.stosa else "r07_fullrank_bench.jsonl")
+        args.out = os.path.join("profiles", "r20_stosa_kl_rowwise.jsonl" if args.rowwise else "r18_stosa_kl_full.jsonl" if kl else
+                                "r08_stosa_fullrank.jsonl" if args.stosa else "r07_fullrank_bench.jsonl")
     dev = "cuda:0"
-    lines = stosa_kl_lines(dev) if kl else stosa_lines(dev) if args.stosa else []
+    lines = stosa_kl_rowwise_lines(dev) if args.rowwise else stosa_kl_lines(dev) if kl else stosa_lines(dev) if args.stosa else []
     for name, V, d in (() if args.stosa else SHAPES):
         g = torch.Generator(device="cpu").manual_seed(V)
         F = torch.randn(B, d, generator=g).to(dev)

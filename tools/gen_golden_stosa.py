@@ -56,7 +56,9 @@ def kl_predict_full(modules, mo, co, Em, Ec):
     return res[:, :V]
 
 
-def gen_stosa(tag, cfg_kw, B, seed, lam1, lam2, lr=1e-3, keep_w3=True, compact=False, steps=3, metric="wasserstein", keep_w1=True, thresh=8192):
+def reference_model(cfg_kw, B, seed, metric):
+    """The reference's DisenDistSAModel with the seeded weights of a fixture and that fixture's batch: (cfg, args, model, the
+    reference's modules, (input_ids, dec_ids, pos_ids, neg_ids))."""
     from tools.gen_golden_wide import _import_from
     from oracle import stosa_oracle as so
     models = _import_from("/root/reference/stosa", "models")
@@ -67,13 +69,18 @@ def gen_stosa(tag, cfg_kw, B, seed, lam1, lam2, lr=1e-3, keep_w3=True, compact=F
     for k in P:   # biases away from zero so that their gradients are exercised
         if k.endswith(".bias") and "LayerNorm" not in k:
             P[k] = (0.02 * r.standard_normal(P[k].shape)).astype(np.float32)
-    inp, dec, pos, neg = stosa_batch(r, B, cfg.maxlen, cfg.item_size)
+    batch = stosa_batch(r, B, cfg.maxlen, cfg.item_size)
     a = Args()
     a.item_size, a.hidden_units, a.maxlen, a.num_users, a.dropout, a.attention_dropout = cfg.item_size, cfg.hidden_units, cfg.maxlen, cfg.num_users, 0.0, 0.0
     a.num_heads, a.num_layers, a.hidden_act, a.initializer_range, a.distance_metric, a.kernel_param = cfg.num_heads, cfg.num_layers, "gelu", 0.02, metric, 1.0
     a.cuda_condition, a.pvn_weight = False, cfg.pvn_weight
     m = models.DisenDistSAModel(a)
     m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in P.items()}, strict=True)
+    return cfg, a, m, modules, batch
+
+
+def gen_stosa(tag, cfg_kw, B, seed, lam1, lam2, lr=1e-3, keep_w3=True, compact=False, steps=3, metric="wasserstein", keep_w1=True, thresh=8192):
+    cfg, a, m, modules, (inp, dec, pos, neg) = reference_model(cfg_kw, B, seed, metric)
     t = [torch.from_numpy(x) for x in (inp, dec, pos, neg)]
     uid = torch.zeros(B, dtype=torch.long)
     out = {"seed": seed, "input_ids": inp, "dec_ids": dec, "pos_ids": pos, "neg_ids": neg, "lambda1": np.array(lam1), "lambda2": np.array(lam2),
@@ -179,9 +186,31 @@ def main_kl():
               seed=33, lam1=[0.0021], lam2=[0.0009], **kw)
 
 
+def main_kl_rowwise():
+    """stosa_kl_rowwise.npz: the model, seed and input_ids of stosa_kl_small.npz; rowwise_dist[b][v] = the reference's kl_distance
+    (stosa/modules.py:45-50) of user b's last-position (mean, cov) from item v's (mean, ELU(cov) + 1), every row of the item tables --
+    the row-wise divergence bpr_optimization trains on, not kl_predict_full's score."""
+    cfg_kw = dict(item_size=42, maxlen=12, hidden_units=64, num_heads=4, num_layers=1, num_users=4, pvn_weight=0.005)
+    B, seed = 4, 21
+    cfg, a, m, modules, (inp, dec, pos, neg) = reference_model(cfg_kw, B, seed, "kl")
+    m.eval()
+    with torch.no_grad():
+        mo, co = m.finetune(torch.from_numpy(inp), torch.from_numpy(dec), torch.zeros(B, dtype=torch.long))[:2]
+        sm, sc = mo[:, -1, :], co[:, -1, :]
+        Em, Ec = m.item_mean_embeddings.weight, nn.ELU()(m.item_cov_embeddings.weight) + 1
+        V = Em.shape[0]
+        dist = torch.stack([modules.kl_distance(sm[b:b + 1].expand(V, -1), sc[b:b + 1].expand(V, -1), Em, Ec) for b in range(B)])
+    out = {"seed": seed, "input_ids": inp, "pvn_weight": cfg.pvn_weight, "last_mean": sm.numpy(), "last_cov": sc.numpy(), "rowwise_dist": dist.numpy(),
+           "cfg": np.array([cfg.item_size, cfg.maxlen, cfg.hidden_units, cfg.num_heads, cfg.num_layers, cfg.num_users])}
+    path = os.path.join(OUT, "stosa_kl_rowwise.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, "rowwise_dist", out["rowwise_dist"].shape, "%.1f KB" % (os.path.getsize(path) / 1024))
+
+
 if __name__ == "__main__":
     import argparse
     sys.path.insert(0, REPO)
     ap = argparse.ArgumentParser()
-    ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl"])
-    main(ap.parse_args().metric)
+    ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl", "kl_rowwise"])
+    metric = ap.parse_args().metric
+    main_kl_rowwise() if metric == "kl_rowwise" else main(metric)
