@@ -29,6 +29,8 @@ struct AttnArgs {
                               // backward, adt_seqattn.cuh with in_bf16 only: do_bf16 != nullptr: the out-projection reverse in front (k_seqtt_post_bwd<DEC>,
                               // BwdChainArgs::do_bf16) handed dO over as bf16 rows of dO * drop.scale in the saved-row order (64 elements per row) and
                               // delta[h] = rowsum(dO . O) of head h at do_delta[row * 4 + h]: dO and O are not read
+  const int* pad_pre;         // backward, k_seqtt_xattn_mid_bwd only: pad prefix of every QUERY sequence (adt_seq_args.h; nullptr: none): the handed-over
+                              // dO rows and delta of a query tile wholly inside it are exact zeros (the producer masks its gradient) and are not requested
 };
 
 }  // namespace adt

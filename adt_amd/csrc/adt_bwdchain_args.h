@@ -58,6 +58,9 @@ struct BwdChainArgs {
                               // order (the cross-attention's behind k_seqtt_post_bwd<DEC>).  nullptr: the fp32 store
   int nsplit;                 // adt_seqpost_tt.cuh: S > 1 workgroups per sequence (adt_seq_args.h): workgroup (blockIdx / S, blockIdx % S) runs the token
                               // chains of the tiles t with t % S == part; its weight-gradient partial (slot blockIdx) covers those tokens only
+  const int* pad_pre;         // adt_seqpost_tt.cuh, adt_seqxattn_tt.cuh: pad prefix of every sequence of this stack (adt_seq_args.h; nullptr: none).  The
+                              // gradient of a padded token is zeroed before use, so the saved rows of a tile wholly inside the prefix only multiply
+                              // exact zeros: they are not requested (k_seqtt_post_bwd: gy, u, xin, o ; k_seqtt_xattn_mid_bwd: xin, o)
 };
 
 }  // namespace adt

@@ -78,6 +78,7 @@ struct WS {
   int64_t part, part_stride;                                            // per-sequence partials of the 64 x 64 weight gradients (bf16 mode, d = 64)
   int64_t isort, isort_n;                                               // scratch of the sorted item-table gradient (adt_item_sort), isort_n int32 (0: not used)
   int64_t dodelta;                                                      // delta[T][4] of the dO hand-over (StepPlan::do_handover; adt_tt.cuh: tt_head_delta)
+  int64_t padpre;                                                       // int32 pad prefix of every sequence: B of the encoder ids, B of the decoder ids (StepPlan::pad_elide)
   int64_t vpart, vcall, lnpart, gnpart;                                 // per-workgroup bias / LayerNorm / classifier gradient sums: 5 * nl calls x vcall floats ;
                                                                         // the last LayerNorm's per-block sums ; per-block partials of ||g||^2
   int64_t total;
@@ -129,6 +130,7 @@ void make_ws(const adt_sasrec_cfg* c, int B, const StepPlan& pl, WS* w) {
   w->lnpart = take(LN_PART_BLOCKS * 128);
   w->gnpart = take(4096);
   w->dodelta = take(pl.do_handover ? up64(w->T * 4) : 0);
+  w->padpre = take(pl.pad_elide ? up64(2 * (int64_t)B) : 0);
   w->total = o;
 }
 
@@ -300,7 +302,7 @@ adt::SeqFwdArgs seq_args(int nsplit, int L, int B, int H, const int32_t* ids, fl
 
 // argument block of one encoder layer's fused forward (adt_seqfwd_tt.cuh / adt_seqfwd.cuh)
 adt::SeqFwdArgs enc_layer_seq_args(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, const StepPlan& pl, const float* P, float* ws, const int32_t* seq,
-                                   float p, const uint32_t* seed, uint32_t b_offset, int i, bool training_outputs, bool lean) {
+                                   float p, const uint32_t* seed, uint32_t b_offset, int i, bool training_outputs, bool lean, const int32_t* dec = nullptr) {
   const int d = (int)w.d, H = (int)w.H, hd = d / H, L = (int)w.L, B = (int)w.B, prec = c->prec;
   const int64_t Td = up64(w.T * w.d);
   float* x = ws + w.enc_x + i * Td;
@@ -317,6 +319,9 @@ adt::SeqFwdArgs enc_layer_seq_args(const adt_sasrec_cfg* c, const Layout& lo, co
   if (training_outputs && H > 1) { a.rec = base + w.e_rec; a.Ws = P + lo.enc(i, E_SW); a.bs = P + lo.enc(i, E_SB); }
   a.wp_base = P + lo.posw(); a.wp_img = prec == ADT_PREC_BF16 ? (const void*)(ws + w.wpack) : nullptr;
   if (lean) { a.xn = nullptr; a.qkv = nullptr; a.saved_bf16 = 1; }
+  // the encoder's layer 0, the step's first kernel, writes the prefixes of both stacks (it is given the decoder's ids for that) ; every per-sequence kernel
+  // of the step behind it reads its stack's
+  if (lean && pl.pad_elide && dec) { a.pad_pre = reinterpret_cast<int*>(ws + w.padpre); a.pad_ids2 = dec; }
   return a;
 }
 
@@ -324,7 +329,7 @@ adt::SeqFwdArgs enc_layer_seq_args(const adt_sasrec_cfg* c, const Layout& lo, co
 // cross-attention k/v projections of every decoder layer when training_outputs)
 int encoder_forward(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, const StepPlan& pl, const float* P, float* ws,
                     const int32_t* seq, const int32_t* pos, const int32_t* neg, float p, const uint32_t* seed,
-                    uint32_t b_offset, bool training_outputs, void* st, bool packed = false) {
+                    uint32_t b_offset, bool training_outputs, void* st, bool packed = false, const int32_t* dec = nullptr) {
   const int T = (int)w.T, d = (int)w.d, H = (int)w.H, hd = d / H, L = (int)w.L, B = (int)w.B, prec = c->prec, nl = c->num_layers;
   const int64_t Td = up64(w.T * w.d);
   const uint32_t ro = b_offset * (uint32_t)L;
@@ -343,7 +348,7 @@ int encoder_forward(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, cons
     const float* inw = P + lo.enc(i, E_INW);
     const float* inb = P + lo.enc(i, E_INB);
     if (use_seq) {   // the whole layer in one launch, one workgroup per sequence (adt_seqfwd.cuh)
-      const adt::SeqFwdArgs a = enc_layer_seq_args(c, lo, w, pl, P, ws, seq, p, seed, b_offset, i, training_outputs, lean);
+      const adt::SeqFwdArgs a = enc_layer_seq_args(c, lo, w, pl, P, ws, seq, p, seed, b_offset, i, training_outputs, lean, dec);
       CK(adt_launch_seq_enc_fwd(hd, a, st));
       continue;
     }
@@ -416,6 +421,7 @@ adt::SeqFwdArgs dec_layer_seq_args(const Layout& lo, const WS& w, const StepPlan
   a.h = a2; a.u = u; a.y = y;
   a.wp_base = P + lo.posw(); a.wp_img = ws + w.wpack;
   if (pl.lean) { a.xn = nullptr; a.qkv = nullptr; a.saved_bf16 = 1; }
+  if (pl.pad_elide) a.pad_pre = reinterpret_cast<int*>(ws + w.padpre) + B_;      // the decoder ids' prefixes behind the encoder ids' (pad_elide implies lean)
   return a;
 }
 int dec_layer_seq_fwd(const Layout& lo, const WS& w, const StepPlan& pl, const float* P, float* ws, const int32_t* dec, float p,
@@ -470,8 +476,9 @@ int forward_loss_lean(const adt_sasrec_cfg* c, const Layout& lo, const WS& w, co
                       const float* lambdas2, const adt::RingPrefetchArgs& rr, void* st) {
   const int hd = (int)(w.d / w.H), nl = c->num_layers;
   if (!pl.bce_deferred) return 1;
+  if (pl.pad_elide && !dec) return adt_set_error("forward: the pad prefixes need the decoder's ids");
   for (int i = 0; i < nl; ++i) {
-    adt::SeqFwdArgs a = enc_layer_seq_args(c, lo, w, pl, P, ws, seq, p, seed, b_offset, i, true, true);
+    adt::SeqFwdArgs a = enc_layer_seq_args(c, lo, w, pl, P, ws, seq, p, seed, b_offset, i, true, true, dec);
     if (i == nl - 1) { a.lnl_gamma = P + lo.lnl_w(); a.lnl_beta = P + lo.lnl_b(); a.f_out = ws + w.f; }
     CK(adt_launch_seq_enc_fwd(hd, a, st));
   }
@@ -544,6 +551,8 @@ struct Bwd {
   void* do_rows_cross() const { return sp.do_handover ? (void*)s1 : nullptr; }
   float* do_delta() const { return sp.do_handover ? ws + w.dodelta : nullptr; }
   float do_scale(uint32_t site) const { return adt_make_drop(p, seed, site).scale; }      // the consumer's drop.scale
+  // StepPlan::pad_elide: the pad prefixes the encoder's embedding layer of this step's forward left in the workspace (adt_seq_args.h: pad_pre)
+  const int* pad_pre(bool dec_stack) const { return sp.pad_elide ? reinterpret_cast<const int*>(ws + w.padpre) + (dec_stack ? w.B : 0) : nullptr; }
   const float* f;                     // log_feats
   SideStream *sd, *sd_sort;           // side stream of the scatter / fold kernels ; of the id sort (nullptr: the caller's stream)
 
@@ -645,6 +654,7 @@ int dec_post_bwd(const Bwd& x, int i) {
   a.db0 = Gq + lo.dec(i, D_C2B); a.db1 = Gq + lo.dec(i, D_C1B); a.db2 = Gq + lo.dec(i, D_EOB);
   a.out0 = x.s1;
   a.do_bf16 = x.do_rows_cross(); a.do_delta = x.do_delta(); a.do_scale = x.do_scale(dec_site(i, 1)); a.do_hd = x.hd;      // -> the cross-attention backward
+  a.pad_pre = x.pad_pre(true);
   a.part[0] = x.PART(i, PS_D_C2); a.part[1] = x.PART(i, PS_D_C1); a.part[2] = x.PART(i, PS_D_EO); a.part_stride = (size_t)w.part_stride;
   a.vpart = x.VPART(i, 0);
   const int rc = x.sp.use_seq ? adt_launch_seq_post_bwd(x.hd, 0, a, x.st) : 1;
@@ -694,6 +704,7 @@ adt::BwdChainArgs dec_mid_seq_args(const Bwd& x, int i) {
   a.part_stride = (size_t)w.part_stride;
   a.vpart = x.VPART(i, 1);
   a.do_bf16 = x.do_rows(); a.do_delta = x.do_delta(); a.do_scale = x.do_scale(dec_site(i, 0)); a.do_hd = x.hd;      // -> attn_block_bwd(dec)
+  a.pad_pre = x.pad_pre(true);
   return a;
 }
 
@@ -706,6 +717,7 @@ adt::AttnArgs dec_cross_attn_lean_args(const Bwd& x, int i) {
                                                  x.hd, x.p, x.seed, dec_site(i, 1), x.b_offset, x.s5, d, x.s4, 2 * d, x.s4 + d / 2, 2 * d,
                                                  reinterpret_cast<const uint32_t*>(base + w.d_mask2), 1);
   a.do_bf16 = x.do_rows_cross(); a.do_delta = x.do_delta();      // from dec_post_bwd
+  a.pad_pre = x.pad_pre(true);      // the queries are the decoder's
   return a;
 }
 
@@ -761,6 +773,7 @@ int attn_block_bwd(const Bwd& x, int i, bool dec) {
     a.x = xi; a.gamma = P + lnw; a.beta = P + lnb; a.Win = P + inw; a.bin = P + inb;
     a.dO = x.s1; a.o = o; a.lse = lse; a.mask = mask; a.dres = dec ? gy : x.s5;
     a.do_bf16 = x.do_rows(); a.do_delta = x.do_delta();      // from enc_post_bwd / the decoder's mid chain
+    a.pad_pre = x.pad_pre(dec);
     a.gx = gx; a.acc = acc; a.dWin = Gq + inw; a.dbin = Gq + inb; a.dgamma = Gq + lnw; a.dbeta = Gq + lnb;
     if (x.plan.seeds_virtual && dec && i > 0) {      // reconstruction pair (enc_in[nl - i], dec_x[i]): d / d dec_x[i] = -2 lambda (a - b) / n = coef * (x - a)
       a.acc = 0; a.seed_other = ws + w.enc_x + (nl - i) * x.Td; a.seed_coef = ws + w.norms + 8 + (nl - i);
@@ -908,6 +921,7 @@ int enc_post_bwd(const Bwd& x, int i) {
   a.part[0] = x.PART(i, PS_E_C2); a.part[1] = x.PART(i, PS_E_C1); a.part[2] = x.PART(i, PS_E_O); a.part_stride = (size_t)w.part_stride;
   a.vpart = x.VPART(i, 3);
   a.do_bf16 = x.do_rows(); a.do_delta = x.do_delta(); a.do_scale = x.do_scale(enc_site(i, 0)); a.do_hd = x.hd;      // -> attn_block_bwd(enc)
+  a.pad_pre = x.pad_pre(false);
   if (x.sp.lnl_fused && i == nl - 1) {
     a.gy = x.gf; a.lnl_x = ws + w.enc_x + nl * x.Td; a.lnl_gamma = P + lo.lnl_w(); a.lnl_eps = LN_EPS;
     a.vpart2 = x.call.late_parts ? ws + w.vpart + (int64_t)(5 * nl) * w.vcall : nullptr;
@@ -1054,7 +1068,8 @@ int adt_sasrec_forward(const adt_sasrec_cfg* c, const float* P, float* ws, const
   training &= ADT_TRAIN_DROPOUT;
   const float p = training ? c->dropout : 0.f;
   const uint32_t ro = b_offset * (uint32_t)L;
-  CK(encoder_forward(c, lo, w, pl, P, ws, seq, pos, neg, p, seed, b_offset, true, st, packed));
+  if (pl.pad_elide && !dec) return adt_set_error("forward: the pad prefixes need the decoder's ids");
+  CK(encoder_forward(c, lo, w, pl, P, ws, seq, pos, neg, p, seed, b_offset, true, st, packed, dec));
   const float* f = ws + w.f;
   const int dd = d * d;
   const int B_ = (int)w.B;

@@ -37,7 +37,7 @@ const SeqSwitches& adt_seq_switches() {
     SeqSwitches s;
     s.seq = adt_env_on("ADT_SEQ"); s.seq_lean = adt_env_on("ADT_SEQ_LEAN"); s.seq_tt = adt_env_on("ADT_SEQ_TT"); s.seq_bwd = adt_env_on("ADT_SEQ_BWD");
     s.seq_attn_bwd = adt_env_on("ADT_SEQ_ATTN_BWD"); s.seq_post_bwd = adt_env_on("ADT_SEQ_POST_BWD"); s.seq_partials = adt_env_on("ADT_SEQ_PARTIALS");
-    s.xattn_fused = adt_env_on("ADT_XATTN_FUSED"); s.do_bf16 = adt_env_on("ADT_DO_BF16");
+    s.xattn_fused = adt_env_on("ADT_XATTN_FUSED"); s.do_bf16 = adt_env_on("ADT_DO_BF16"); s.pad_elide = adt_env_on("ADT_PAD_ELIDE");
     s.seq_ablate = adt_env_int("ADT_SEQ_ABLATE", 0); s.seq_ablate_set = adt_env_int("ADT_SEQ_ABLATE", INT_MIN) != INT_MIN;
     s.seq_split = adt_env_int("ADT_SEQ_SPLIT", 0); s.attn_split = adt_env_on("ADT_ATTN_SPLIT");
     s.side_stream = adt_env_int("ADT_SIDE_STREAM", 7); s.side_stream_dp = adt_env_int("ADT_SIDE_STREAM_DP", 0) != 0;
@@ -92,18 +92,32 @@ static bool seq_use_tt(const SeqFwdArgs& a) {     // register-resident transpose
   return adt_seq_fwd_tt(adt_seq_switches(), a.wp_img != nullptr, a.L);
 }
 
+// Launches of a chain kernel ISSUED by this process that were given the pad prefixes (SeqFwdArgs / SeqBwdArgs / BwdChainArgs / AttnArgs::pad_pre;
+// StepPlan::pad_elide): like adt_seq_do_handover_launches below a debugging aid of the tests, not part of include/adt_hip.h
+static std::atomic<unsigned long long> g_pad_elide_launches{0};
+extern "C" unsigned long long adt_seq_pad_elide_launches() { return g_pad_elide_launches.load(); }
+static int pad_refused(int hd, const void* pad_pre) {      // the 16-wide-head instantiations ignore the prefixes: StepPlan::pad_elide never names them there
+  return (pad_pre && hd == 16) ? adt_set_error("per-sequence kernels: pad prefixes with 16-wide heads") : 0;
+}
+static int pad_counted(int rc, const void* pad_pre) {
+  if (rc == 0 && pad_pre) ++g_pad_elide_launches;
+  return rc;
+}
+
 int adt_launch_seq_enc_fwd(int hd, const SeqFwdArgs& a, void* stream) {
   static AdtLdsOptIn optin[3], optin_tt[3];
+  if (pad_refused(hd, a.pad_pre)) return -1;
   SeqFwdArgs args = a;
   seq_ablate(args);
   hipStream_t s = (hipStream_t)stream;
   if (seq_use_tt(args)) {
     const int nsp = args.nsplit > 1 ? args.nsplit : 1;
     const size_t smem_tt = SeqTtLds<6>::bytes;
-    if (hd == 64) return seq_launch((const void*)k_seqtt_enc_fwd<64>, smem_tt, optin_tt[0], a.B * nsp, &args, s, "seqtt_enc_fwd<64>", TQ_FWD_NW);
-    if (hd == 32) return seq_launch((const void*)k_seqtt_enc_fwd<32>, smem_tt, optin_tt[1], a.B * nsp, &args, s, "seqtt_enc_fwd<32>", TQ_FWD_NW);
-    if (hd == 16) return seq_launch((const void*)k_seqtt_enc_fwd<16>, smem_tt, optin_tt[2], a.B * nsp, &args, s, "seqtt_enc_fwd<16>", TQ_FWD_NW);
+    if (hd == 64) return pad_counted(seq_launch((const void*)k_seqtt_enc_fwd<64>, smem_tt, optin_tt[0], a.B * nsp, &args, s, "seqtt_enc_fwd<64>", TQ_FWD_NW), a.pad_pre);
+    if (hd == 32) return pad_counted(seq_launch((const void*)k_seqtt_enc_fwd<32>, smem_tt, optin_tt[1], a.B * nsp, &args, s, "seqtt_enc_fwd<32>", TQ_FWD_NW), a.pad_pre);
+    if (hd == 16) return pad_counted(seq_launch((const void*)k_seqtt_enc_fwd<16>, smem_tt, optin_tt[2], a.B * nsp, &args, s, "seqtt_enc_fwd<16>", TQ_FWD_NW), a.pad_pre);
   }
+  if (a.pad_pre) return adt_set_error("seq_enc_fwd: the pad prefixes belong to the transposed-chain kernels (L=%d hd=%d)", a.L, hd);
   args.nsplit = 0;
   const size_t smem = SeqFwdLds<6>::bytes;
   if (hd == 64) return seq_launch((const void*)k_seq_enc_fwd<64, 2>, smem, optin[0], a.B, &args, s, "seq_enc_fwd<64>");
@@ -114,16 +128,18 @@ int adt_launch_seq_enc_fwd(int hd, const SeqFwdArgs& a, void* stream) {
 
 int adt_launch_seq_dec_fwd(int hd, const SeqFwdArgs& a, void* stream) {
   static AdtLdsOptIn optin[3], optin_tt[3];
+  if (pad_refused(hd, a.pad_pre)) return -1;
   SeqFwdArgs args = a;
   seq_ablate(args);
   hipStream_t s = (hipStream_t)stream;
   if (seq_use_tt(args)) {
     const int nsp = args.nsplit > 1 ? args.nsplit : 1;
     const size_t smem_tt = SeqTtLds<5>::bytes;
-    if (hd == 64) return seq_launch((const void*)k_seqtt_dec_fwd<64>, smem_tt, optin_tt[0], a.B * nsp, &args, s, "seqtt_dec_fwd<64>", TQ_FWD_NW);
-    if (hd == 32) return seq_launch((const void*)k_seqtt_dec_fwd<32>, smem_tt, optin_tt[1], a.B * nsp, &args, s, "seqtt_dec_fwd<32>", TQ_FWD_NW);
-    if (hd == 16) return seq_launch((const void*)k_seqtt_dec_fwd<16>, smem_tt, optin_tt[2], a.B * nsp, &args, s, "seqtt_dec_fwd<16>", TQ_FWD_NW);
+    if (hd == 64) return pad_counted(seq_launch((const void*)k_seqtt_dec_fwd<64>, smem_tt, optin_tt[0], a.B * nsp, &args, s, "seqtt_dec_fwd<64>", TQ_FWD_NW), a.pad_pre);
+    if (hd == 32) return pad_counted(seq_launch((const void*)k_seqtt_dec_fwd<32>, smem_tt, optin_tt[1], a.B * nsp, &args, s, "seqtt_dec_fwd<32>", TQ_FWD_NW), a.pad_pre);
+    if (hd == 16) return pad_counted(seq_launch((const void*)k_seqtt_dec_fwd<16>, smem_tt, optin_tt[2], a.B * nsp, &args, s, "seqtt_dec_fwd<16>", TQ_FWD_NW), a.pad_pre);
   }
+  if (a.pad_pre) return adt_set_error("seq_dec_fwd: the pad prefixes belong to the transposed-chain kernels (L=%d hd=%d)", a.L, hd);
   args.nsplit = 0;
   const size_t smem = SeqFwdLds<5>::bytes;
   if (hd == 64) return seq_launch((const void*)k_seq_dec_fwd<64>, smem, optin[0], a.B, &args, s, "seq_dec_fwd<64>");
@@ -173,7 +189,7 @@ static int seq_attn_pre_bwd_t(int mode, const SeqBwdArgs& a, hipStream_t s) {
   if (a.nsplit != 2) args.nsplit = 1;
   const int rc = seq_launch(fns[mode], smem, optin[mode], a.B * args.nsplit, &args, s, "seqtt_attn_pre_bwd");
   if (rc == 0 && a.do_bf16) ++g_do_handover_launches;
-  return rc;
+  return pad_counted(rc, a.pad_pre);
 }
 
 int adt_launch_seq_attn_pre_bwd(int hd, int dec, const SeqBwdArgs& a, void* stream) {
@@ -181,6 +197,7 @@ int adt_launch_seq_attn_pre_bwd(int hd, int dec, const SeqBwdArgs& a, void* stre
   f.L = a.L; f.H = a.H; f.B = a.B; f.T = a.B * a.L; f.wimg = a.wp_img != nullptr;
   if (!adt_covers_attn_pre_bwd(adt_seq_switches(), hd, f)) return 1;
   if (a.do_bf16 && !a.do_delta) return adt_set_error("seqtt_attn_pre_bwd: handed-over dO rows without their delta");
+  if (pad_refused(hd, a.pad_pre)) return -1;
   const int mode = a.drop.thr == 0 ? 0 : (a.mask != nullptr ? 1 : 2);
   hipStream_t s = (hipStream_t)stream;
   if (hd == 32) return dec ? seq_attn_pre_bwd_t<32, true>(mode, a, s) : seq_attn_pre_bwd_t<32, false>(mode, a, s);
@@ -191,13 +208,14 @@ int adt_launch_seq_attn_pre_bwd(int hd, int dec, const SeqBwdArgs& a, void* stre
 // per-sequence backward of the token-wise chains (adt_seqpost_tt.cuh); 0 launched, 1 not covered (the caller runs the row-major chain kernels)
 int adt_launch_seq_post_bwd(int hd, int enc, const BwdChainArgs& a, void* stream) {
   if (!adt_covers_post_bwd(adt_seq_switches(), hd, enc != 0, chain_facts(a))) return 1;
+  if (pad_refused(hd, a.pad_pre)) return -1;
   static AdtLdsOptIn optin[6];
   const void* fns[6] = {(const void*)k_seqtt_post_bwd<64, false>, (const void*)k_seqtt_post_bwd<64, true>, (const void*)k_seqtt_post_bwd<32, false>,
                         (const void*)k_seqtt_post_bwd<32, true>, (const void*)k_seqtt_post_bwd<16, false>, (const void*)k_seqtt_post_bwd<16, true>};
   const int slot = (hd == 64 ? 0 : hd == 32 ? 2 : 4) + (enc ? 1 : 0);
   BwdChainArgs args = a;
   args.stamps = enc ? seq_stamp_buffer_post() : nullptr;
-  return seq_launch(fns[slot], SeqPostLds<3>::bytes, optin[slot], a.B * (a.nsplit > 1 ? a.nsplit : 1), &args, (hipStream_t)stream, "seqtt_post_bwd", SP_NW);
+  return pad_counted(seq_launch(fns[slot], SeqPostLds<3>::bytes, optin[slot], a.B * (a.nsplit > 1 ? a.nsplit : 1), &args, (hipStream_t)stream, "seqtt_post_bwd", SP_NW), a.pad_pre);
 }
 
 int adt_launch_seq_mid_bwd(int hd, const BwdChainArgs& a, void* stream) {
@@ -238,6 +256,9 @@ int adt_launch_seq_xattn_mid_bwd(int hd, const AttnArgs& at, const BwdChainArgs&
   a.part_stride = ch.part_stride;
   a.do_bf16 = ch.do_bf16; a.do_delta = ch.do_delta; a.do_scale = ch.do_scale;
   a.dO_bf16 = reinterpret_cast<const __bf16*>(at.do_bf16); a.dO_delta = at.do_delta;
+  if (at.pad_pre && ch.pad_pre && at.pad_pre != ch.pad_pre) return adt_set_error("seqtt_xattn_mid_bwd: the two argument blocks name different pad prefixes");
+  a.pad_pre = at.pad_pre ? at.pad_pre : ch.pad_pre;      // the queries' stack is the mid chain's: the decoder
+  if (pad_refused(hd, a.pad_pre)) return -1;
   if (at.do_bf16 && !at.do_delta) return adt_set_error("seqtt_xattn_mid_bwd: handed-over dO rows without their delta");
   a.stamps = seq_stamp_buffer_mode(6);
   const int mode = at.drop.thr == 0 ? 0 : 1;
@@ -250,7 +271,7 @@ int adt_launch_seq_xattn_mid_bwd(int hd, const AttnArgs& at, const BwdChainArgs&
   const int rc = seq_launch(fns[slot], xm_lds_bytes(at.L, at.H), optin[slot], at.B, &a, (hipStream_t)stream, "seqtt_xattn_mid_bwd", XM_NW, most);
   if (rc == 0) ++g_xattn_fused_launches;
   if (rc == 0 && at.do_bf16) ++g_do_handover_launches;
-  return rc;
+  return pad_counted(rc, a.pad_pre);
 }
 
 // ---- sum of the per-workgroup weight-gradient partials (adt_seqbwd_tt.cuh: sb_dw_tiles) --------------------------------------------

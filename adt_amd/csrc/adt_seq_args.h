@@ -47,6 +47,12 @@ struct SeqFwdArgs {
   // (b, part) = (blockIdx / S, blockIdx % S) computes the key / value rows of EVERY tile (each workgroup needs them all: recomputed, not
   // exchanged) but queries, attention, out_proj, feed-forward and every store only for the tiles t with t % S == part.  0 / 1: one workgroup.
   int nsplit;
+  // Pad prefix of every sequence of this stack (StepPlan::pad_elide; nullptr: none): pad_pre[b] = leading positions of sequence b whose id is 0.
+  // The layers behind the embedding layer (x != nullptr) read it and request no layer-input row of a 16-token tile that lies wholly inside the
+  // prefix: those rows are exact zeros (the mask at the end of every layer), which is what a lane without a row holds (adt_tt.cuh: tt_load).
+  // The ENCODER's embedding layer (x == nullptr, the first kernel of a step) WRITES the prefixes of both stacks: pad_pre[b] from ids, and
+  // pad_pre[B + b] from pad_ids2, the decoder's ids (k_seqtt_dec_fwd sits at its register budget: with the write, <32> took 20 B of scratch).
+  int* pad_pre; const int* pad_ids2;
 };
 
 }  // namespace adt

@@ -32,6 +32,8 @@ struct SeqBwdArgs {
   float* vpart;                       // non-null: dgamma[64] | dbeta[64] | dbin[192] of this workgroup stored at vpart + blockIdx * 512 (no atomics)
   int nsplit;                         // 2: two workgroups per sequence (grid 2 B; workgroup 2 b + part owns the tiles t % 2 == part; needs `part`)
   unsigned long long* stamps;
+  const int* pad_pre;                 // pad prefix of every sequence of this stack (adt_seq_args.h; nullptr: none): the rows of x, and in the decoder
+                                      // block of dres, of a tile wholly inside it are not requested -- x is an exact zero there, dres is masked by ids
 };
 
 }  // namespace adt

@@ -301,6 +301,9 @@ __global__ __launch_bounds__(SB_NW * 64) void k_seqtt_attn_pre_bwd(SeqBwdArgs a)
     a.dWin += off; a.dbin += off; a.dgamma += off; a.dbeta += off;
   }
   float* const part = a.part ? a.part + (size_t)blockIdx.x * a.part_stride : nullptr;      // three consecutive blocks: Wq, Wk, Wv
+  // (workgroup-uniform) the sequence's pad prefix, requested first and consumed behind the small tables and the weight-image DMA: the block input of a
+  // tile wholly inside it is zeros (what a lane without a row holds), the decoder block's residual gradient there is masked by the ids in P5
+  const int padn = (HD != 16 && a.pad_pre) ? a.pad_pre[b] : 0;      // (not with 16-wide heads: StepPlan::pad_elide)
   SB_STAMP(0);
   // The weight images are requested first and P1's activations right behind them: every workgroup of the launch runs the same phase at
   // the same time, so HBM streams the activations while the prologue runs instead of idling through it (adt_seqpost_tt.cuh)
@@ -355,7 +358,7 @@ __global__ __launch_bounds__(SB_NW * 64) void k_seqtt_attn_pre_bwd(SeqBwdArgs a)
   for (int s = 0; s < 2; ++s) {
     const int tile = TM(s);
     const int l = tile * 16 + c, row = b * L + l;
-    xa[s] = tt_load(a.x + (size_t)row * 64, tile >= 0 && l < L, g);               // unconditional (address-select) loads: all in flight together
+    xa[s] = tt_load(a.x + (size_t)row * 64, tile >= 0 && l < L && !tt_pad_tile(tile, padn, L), g);      // unconditional (address-select) loads: all in flight together
     if (DEC) idv[s] = tt_load_id(a.ids, row, tile >= 0 && l < L);
   }
   SB_STAMP(11);
@@ -388,8 +391,11 @@ __global__ __launch_bounds__(SB_NW * 64) void k_seqtt_attn_pre_bwd(SeqBwdArgs a)
     const int l = tile * 16 + c, row = b * L + l;
     const bool valid = tile >= 0 && l < L;
     if (hand) {
-      dob[s] = tt_load_bf16_raw(reinterpret_cast<const __bf16*>(a.do_bf16) + (size_t)row * 64, valid, g);
-      tt_delta_load<H>(a.do_delta, (size_t)row, valid, delta[s]);
+      // decoder block: dO1 and delta of a tile inside the pad prefix are the zeros a lane without a row holds (the mid chain in front formed them
+      // from dq2 = 0).  Not in the encoder block: the head classifier's reverse adds to dO at padded rows too
+      const bool live = valid && !(DEC && tt_pad_tile(tile, padn, L));
+      dob[s] = tt_load_bf16_raw(reinterpret_cast<const __bf16*>(a.do_bf16) + (size_t)row * 64, live, g);
+      tt_delta_load<H>(a.do_delta, (size_t)row, live, delta[s]);
     } else {
       doa[s] = tt_load(a.dO + (size_t)row * 64, valid, g);
       oa[s] = tt_load_saved(a.o, row, valid, g, a.saved_bf16);
@@ -493,7 +499,7 @@ __global__ __launch_bounds__(SB_NW * 64) void k_seqtt_attn_pre_bwd(SeqBwdArgs a)
       for (int s2 = 0; s2 < 2; ++s2) {
         const int tile2 = TM(s2);
         const int l2 = tile2 * 16 + c;
-        xk[s2] = tt_load(a.x + (size_t)(b * L + l2) * 64, tile2 >= 0 && l2 < L, g);
+        xk[s2] = tt_load(a.x + (size_t)(b * L + l2) * 64, tile2 >= 0 && l2 < L && !tt_pad_tile(tile2, padn, L), g);
       }
     }
     const int tile = TB(s);
@@ -543,7 +549,7 @@ __global__ __launch_bounds__(SB_NW * 64) void k_seqtt_attn_pre_bwd(SeqBwdArgs a)
   for (int s = 0; s < 2; ++s) {
     const int tile = TA(s);
     const int l = tile * 16 + c;
-    resa[s] = tt_load(a.dres + (size_t)(b * L + l) * 64, tile >= 0 && l < L, g);
+    resa[s] = tt_load(a.dres + (size_t)(b * L + l) * 64, tile >= 0 && l < L && !(DEC && tt_pad_tile(tile, padn, L)), g);
   }
   sb_dw_product16(img0, img1, npair, a.dWin, part, sRed + 128, w, c, g);
   if (DEC) sb_dw_product16(img2, img1, npair, a.dWin + 4096, part ? part + 4096 : nullptr, sRed + 192, w, c, g);

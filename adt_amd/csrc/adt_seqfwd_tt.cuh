@@ -153,6 +153,25 @@ ADT_DEVICE_INLINE void tq_zero(__bf16* p, size_t nbytes) {
   for (int i = threadIdx.x; i < (int)(nbytes / 16); i += NTHREADS) q[i] = make_uint4(0u, 0u, 0u, 0u);
 }
 
+// The pad prefixes of the sequence (SeqFwdArgs::pad_pre), formed by the encoder's embedding layer: TWO waves of the sequence's first workgroup
+// read the ids of one stack each (L <= 224: four per lane; the encoder's are L2 hits behind the kernel's own id loads) and store the first
+// position whose id is not 0.  At the END of the kernel, by the waves with the lightest causal tiles, which the two-tile wave outlasts by
+// thousands of cycles: nothing in this launch reads the prefixes, and at the end no register is live.
+constexpr int TQ_PAD_WAVE = 8;
+ADT_DEVICE_INLINE void tq_pad_finish(const int* ids, int* pad_pre, int b, int L, int lane) {
+  static_assert(TQ_LP <= 256, "four ids per lane cover a sequence");
+  int id[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) id[k] = tt_load_id(ids, b * L + lane + 64 * k, lane + 64 * k < L);
+  int first = L;
+#pragma unroll
+  for (int k = 3; k >= 0; --k) {
+    const unsigned long long nz = __ballot(id[k] != 0);
+    if (nz) first = 64 * k + __builtin_ctzll(nz);
+  }
+  if (lane == 0) pad_pre[b] = first;
+}
+
 // layer input of this lane's token: a load, or the embedding gather x = dropout(E[id] * sqrt(d) + P[l]) * (id != 0)   (model.py:34-41).
 // In two steps, so that the prologue can put the requests of BOTH of a wave's tiles in flight beside the weight images (they used to be
 // issued inside the tile loop behind the first barrier: one exposed round trip per tile, two for the gather, whose row address needs the id):
@@ -268,6 +287,8 @@ __global__ __launch_bounds__(TQ_FWD_NW * 64) void k_seqtt_enc_fwd(SeqFwdArgs a) 
   const int nsp = a.nsplit > 1 ? a.nsplit : 1, b = blockIdx.x / nsp, part = blockIdx.x % nsp;      // adt_seq_args.h: several workgroups per sequence
   const int L = a.L, ntiles = (L + 15) / 16;
   const bool own[2] = {tq_tile12(0, w, ntiles) >= 0 && tq_tile12(0, w, ntiles) % nsp == part, tq_tile12(1, w, ntiles) >= 0 && tq_tile12(1, w, ntiles) % nsp == part};
+  // (workgroup-uniform) requested first, consumed behind the weight-image requests.  Not with 16-wide heads: StepPlan::pad_elide (adt_step_plan.h)
+  const int padn = (HD != 16 && a.pad_pre && a.x) ? a.pad_pre[b] : 0;
   TQ_STAMP(0);
   uint32_t seedv = 0u;
   TqX xr[2];
@@ -295,7 +316,7 @@ __global__ __launch_bounds__(TQ_FWD_NW * 64) void k_seqtt_enc_fwd(SeqFwdArgs a) 
 #pragma unroll
     for (int s = 0; s < 2; ++s) {             // the layer input of both tiles, in flight while the images are stored
       const int tile = (s == 1 && htile >= 0) ? htile : tq_tile12(s, w, ntiles), l = tile * 16 + c;
-      xr[s] = tq_x_request(a, b * L + l, l, tile >= 0 && l < L, idr[s], g);
+      xr[s] = tq_x_request(a, b * L + l, l, tile >= 0 && l < L && !tt_pad_tile(tile, padn, L), idr[s], g);      // a padded tile's input rows are zeros
     }
     if (a.x) {                                // later layers: the ids are only the output's pad mask -- behind every other request
 #pragma unroll
@@ -393,6 +414,8 @@ __global__ __launch_bounds__(TQ_FWD_NW * 64) void k_seqtt_enc_fwd(SeqFwdArgs a) 
     if (a.f_out) tt_store(a.f_out + (size_t)row * 64, tt_layernorm(y, lds.vec + SV_LNL_G, lds.vec + SV_LNL_B, a.ln_eps, g), valid, g);   // log_feats (model.py:48)
     TQ_STAMP(7 + 3 * s);
   }
+  if (HD != 16 && a.pad_pre && !a.x && part == 0 && (w == TQ_PAD_WAVE || w == TQ_PAD_WAVE + 1))      // (wave-uniform)
+    tq_pad_finish(w == TQ_PAD_WAVE ? a.ids : a.pad_ids2, a.pad_pre + (w == TQ_PAD_WAVE ? 0 : a.B), b, L, lane);
 }
 
 // ---- decoder layer: set A: 0 Wq, 1 Wk, 2 Wv (slf_attn), 3 slf out_proj, 4 enc_attn Wq ; set B: 0 enc_attn Wk, 1 Wv, 2 enc_attn out_proj,
@@ -408,6 +431,8 @@ __global__ __launch_bounds__(TQ_FWD_NW * 64) void k_seqtt_dec_fwd(SeqFwdArgs a) 
   const int nsp = a.nsplit > 1 ? a.nsplit : 1, b = blockIdx.x / nsp, part = blockIdx.x % nsp;      // adt_seq_args.h: several workgroups per sequence
   const int L = a.L, ntiles = (L + 15) / 16;
   const bool own[2] = {tq_tile12(0, w, ntiles) >= 0 && tq_tile12(0, w, ntiles) % nsp == part, tq_tile12(1, w, ntiles) >= 0 && tq_tile12(1, w, ntiles) % nsp == part};
+  // (workgroup-uniform) requested first, consumed behind the weight-image requests.  Not with 16-wide heads: StepPlan::pad_elide (adt_step_plan.h)
+  const int padn = (HD != 16 && a.pad_pre && a.x) ? a.pad_pre[b] : 0;
   uint32_t seedv = 0u;
   const bool tq_body = TQW * 64 <= TQ_CH || threadIdx.x < TQ_CH;
   const bool tq_tail = (int)threadIdx.x < TQ_CH - TQW * 64;        // chunks beyond the first TQW * 64 (wave-uniform: whole waves)
@@ -432,7 +457,7 @@ __global__ __launch_bounds__(TQ_FWD_NW * 64) void k_seqtt_dec_fwd(SeqFwdArgs a) 
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const int tile = (s == 1 && htile >= 0) ? htile : tq_tile12(s, w, ntiles), l = tile * 16 + c;
-      xr[s] = tq_x_request(a, b * L + l, l, tile >= 0 && l < L, idr[s], g);
+      xr[s] = tq_x_request(a, b * L + l, l, tile >= 0 && l < L && !tt_pad_tile(tile, padn, L), idr[s], g);      // a padded tile's input rows are zeros
     }
     if (a.x) {
 #pragma unroll

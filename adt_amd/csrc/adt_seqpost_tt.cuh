@@ -63,9 +63,10 @@ ADT_DEVICE_INLINE void sp_store_do1(float* out0, void* do_bf16, float* do_delta,
   else if (hd == 64) sp_hand_do<64>(do_bf16, do_delta, scale, row, dO, o, valid, g);
   else sp_hand_do<16>(do_bf16, do_delta, scale, row, dO, o, valid, g);
 }
-// Wave count of the token-chain backward kernels.  Every tile costs the same here (no causal weights), so with 13 tiles at L = 200 the eight-wave
-// form is paced by the five waves that own two tiles; sixteen waves (<= 128 VGPRs, one tile slot per wave) give every tile its own wave and
-// four waves per SIMD to cover each other's LDS and MFMA latency.
+// Wave count of the token-chain backward kernels: eight, two tile slots per wave.  Every tile costs the same here (no causal weights), so with 13
+// tiles at L = 200 the kernel is paced by the five waves that own two tiles.  Sixteen waves (one tile slot per wave, four waves per SIMD) were
+// tried and were slower: at their 128-register budget the kernels took 76-112 B of scratch per lane and k_seqtt_post_bwd<ENC> 35.2 us against
+// 32.4 (EXPERIMENTS.md).  The wave count stays a parameter (SP_NS follows it).
 constexpr int SP_NW = 8;
 constexpr int SP_NS = (14 + SP_NW - 1) / SP_NW;          // tile slots per wave (L <= 224)
 
@@ -95,6 +96,7 @@ __global__ __launch_bounds__(SP_NW * 64) void k_seqtt_post_bwd(BwdChainArgs a) {
   SB_STAMP(0);
   // every workgroup of the launch runs the same phases at the same time: the activations of phase A are requested right behind the
   // weight images, so that HBM streams them while the prologue runs (requested at the top of phase A they arrived ~8k cycles after it)
+  const int padn = (HD != 16 && a.pad_pre) ? a.pad_pre[b] : 0;      // (workgroup-uniform) requested first, consumed behind the weight-image DMA (not with 16-wide heads: StepPlan::pad_elide)
   const float* const ws3[3] = {a.W0, a.W1, a.W2};
   sp_wdma<3, NW>(a, ws3, wimg);
   TT dy[NS], xl[NS];
@@ -105,10 +107,13 @@ __global__ __launch_bounds__(SP_NW * 64) void k_seqtt_post_bwd(BwdChainArgs a) {
     const int tile = tileof(s);
     const int l = tile * 16 + c, row = b * L + l;
     const bool valid = tile >= 0 && l < L;
-    dy[s] = tt_load(a.gy + (size_t)row * 64, valid, g);
+    // a tile wholly inside the pad prefix: its gradient is zeroed below (idv == 0), so u and xin only multiply exact zeros and gy itself is
+    // dead -- unless it first runs through the last LayerNorm's reverse, whose gamma / beta sums count padded rows too
+    const bool live = valid && !tt_pad_tile(tile, padn, L);
+    dy[s] = tt_load(a.gy + (size_t)row * 64, lnl ? valid : live, g);
     if (ENC) xl[s] = tt_load(a.lnl_x + (size_t)row * 64, valid && lnl, g);
-    uraw[s] = tt_saved_request(a.u, row, valid, g, a.saved_bf16);
-    hreq[s] = tt_saved_request(a.xin, row, valid, g, a.saved_bf16);
+    uraw[s] = tt_saved_request(a.u, row, live, g, a.saved_bf16);
+    hreq[s] = tt_saved_request(a.xin, row, live, g, a.saved_bf16);
     idv[s] = tt_load_id(a.ids, row, valid);
   }
   if (a.gy_scale != 0.f) {                                 // after every load of the prologue has been issued: a use is a wait
@@ -193,7 +198,7 @@ __global__ __launch_bounds__(SP_NW * 64) void k_seqtt_post_bwd(BwdChainArgs a) {
     if (tile < 0) continue;
     const int l = tile * 16 + c, row = b * L + l;
     const bool valid = l < L;
-    oreq[s] = tt_saved_request(a.o, row, valid, g, a.saved_bf16);           // consumed in C
+    oreq[s] = tt_saved_request(a.o, row, valid && (cls || !tt_pad_tile(tile, padn, L)), g, a.saved_bf16);      // consumed in C (padded tile: dh = 0, o is read by the classifier's reverse only)
     if constexpr (H == 2) {                                                  // the head classifier's H x H values of this token, consumed in C
       if (cls) {                                                             // (read there they were two exposed round trips per tile)
         typedef const f32x4 __attribute__((address_space(1))) * gf4;

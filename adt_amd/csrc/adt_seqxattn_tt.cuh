@@ -42,6 +42,9 @@ struct XattnMidArgs {
   void* do_bf16; float* do_delta; float do_scale;      // hand-over of dO1 to the self-attention backward (BwdChainArgs: do_bf16 ; the head size is HD)
   const __bf16* dO_bf16; const float* dO_delta;        // hand-over of dO2 FROM k_seqtt_post_bwd<DEC> (AttnArgs: do_bf16, do_delta): dO and O are not read
   unsigned long long* stamps;      // timing experiments only (ADT_SEQ_STAMPS=6): s_memtime per wave of workgroup 0
+  const int* pad_pre;              // pad prefix of every DECODER sequence (AttnArgs / BwdChainArgs::pad_pre; nullptr: none).  A query tile wholly inside it:
+                                   // the handed-over dO2 rows and delta are exact zeros (k_seqtt_post_bwd<DEC> masks its gradient), hence dq2 = 0 and
+                                   // a1 / o1 only multiply zeros -- none of the four is requested.  K, V, f (encoder rows) and the keys' gradients stay
 };
 
 __host__ __device__ inline int xm_rows(int L) { return (L + 31) / 32 <= 4 ? 128 : SB_R; }       // image rows = rows sb_dw_product16 sweeps
@@ -98,6 +101,7 @@ __global__ __launch_bounds__(XM_NW * 64) void k_seqtt_xattn_mid_bwd(XattnMidArgs
   const int nqt = (L + 15) / 16, npair = (L + 31) / 32;
 #define XM_STAMP(k) do { if (a.stamps && blockIdx.x == 0 && lane == 0) a.stamps[w * 16 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
   XM_STAMP(0);
+  const int padn = (HD != 16 && a.pad_pre) ? a.pad_pre[b] : 0;      // (workgroup-uniform) requested first, consumed behind the keep-bit and log-sum-exp requests (not with 16-wide heads: StepPlan::pad_elide)
   if (a.nrep > 1) {      // bias-gradient replicas (vpart == nullptr): see sp_replica
     const size_t off = (size_t)(blockIdx.x % a.nrep) * a.rep_stride;
     if (a.db0) a.db0 += off;
@@ -147,9 +151,10 @@ __global__ __launch_bounds__(XM_NW * 64) void k_seqtt_xattn_mid_bwd(XattnMidArgs
     const gb4 pv = ok ? (gb4)(a.V + row * a.ldv + pa) : zb, po = ok ? (gb4)(a.O + row * a.ldo + pa) : zb;
     qa[k] = pq[0]; qc[k] = pq[4]; ka[k] = pk[0]; kc[k] = pk[4]; va[k] = pv[0]; vc[k] = pv[4];      // pb = pa + 16 elements
     if (hand) {
-      const gb4 pdb = ok ? (gb4)(a.dO_bf16 + row * 64 + pa) : zb;
+      const bool okd = ok && !tt_pad_tile(r >> 4, padn, L);      // (wave-uniform: a wave holds eight whole rows of one tile) zeros, as stored
+      const gb4 pdb = okd ? (gb4)(a.dO_bf16 + row * 64 + pa) : zb;
       da[k] = pdb[0]; dc[k] = pdb[4];
-      dlt[k] = *(ok ? (gf1)(a.dO_delta + row * 4 + (i & 7) / (HD / 8)) : (gf1)tt_zero_row);      // the chunk's head
+      dlt[k] = *(okd ? (gf1)(a.dO_delta + row * 4 + (i & 7) / (HD / 8)) : (gf1)tt_zero_row);      // the chunk's head
     } else {
       const gp4 pd = ok ? (gp4)(a.dO + row * a.lddo + c8) : (gp4)tt_zero_row + (i & 7);
       oa[k] = po[0]; oc[k] = po[4];
@@ -218,6 +223,7 @@ __global__ __launch_bounds__(XM_NW * 64) void k_seqtt_xattn_mid_bwd(XattnMidArgs
   const int lA = qt * 16 + c, lB = kt * 16 + c;
   const bool validA = has && lA < L, validB = has && lB < L;
   const size_t rowA = row_b + lA, rowB = row_b + lB;
+  const bool liveA = validA && !(hand && tt_pad_tile(qt, padn, L));      // a1 / o1 of a padded query tile multiply dq2 = 0 and da1 = 0
 
   // ---- pass A: dQ (the wave owns query tile qt, keys on the accumulator rows) ------------------------------------------------------------
   TTB dq = xm_zero();
@@ -261,7 +267,7 @@ __global__ __launch_bounds__(XM_NW * 64) void k_seqtt_xattn_mid_bwd(XattnMidArgs
   }
   // (four 16-wide heads: pass B has no eight registers to spare -- 20 bytes of scratch per lane -- and a1 is requested behind it)
   TTSaved a1req;
-  if constexpr (HD != 16) a1req = tt_saved_request(a.xin, rowA, validA, g, 1);
+  if constexpr (HD != 16) a1req = tt_saved_request(a.xin, rowA, liveA, g, 1);
 
   // ---- pass B: dK, dV (the wave owns key tile kt, queries on the accumulator rows) -------------------------------------------------------
   TTB dk = xm_zero(), dv = xm_zero();
@@ -289,7 +295,7 @@ __global__ __launch_bounds__(XM_NW * 64) void k_seqtt_xattn_mid_bwd(XattnMidArgs
         }
     }
   }
-  if constexpr (HD == 16) a1req = tt_saved_request(a.xin, rowA, validA, g, 1);
+  if constexpr (HD == 16) a1req = tt_saved_request(a.xin, rowA, liveA, g, 1);
   XM_STAMP(6);
   adt_wait_vm0();           // the LDS-DMA of the weight images has landed: published by this barrier
   __syncthreads();          // nobody reads the Q / dO images any more: they become the token images (rows beyond the sequence are zero)
@@ -300,7 +306,7 @@ __global__ __launch_bounds__(XM_NW * 64) void k_seqtt_xattn_mid_bwd(XattnMidArgs
   // retires loads and stores in issue order.  o1 and f (consumed in B and C) are requested here, d log_feats (consumed in D) in front of phase
   // B's dO1 stores and not behind them.  (Stamps of single workgroups do not separate this order from k_seqtt_mid_bwd's, f in B and d log_feats
   // in C: 76.0k and 72.9k cycles for the kernel in two samples against 73.3k, the waits move between the phases -- profiles/r11_xattn_mid_fused.txt.)
-  const TTSaved oreq = tt_saved_request(a.o, rowA, validA, g, 1);
+  const TTSaved oreq = tt_saved_request(a.o, rowA, liveA, g, 1);
   const TT fx = tt_load(a.f + rowB * 64, validB, g);
   if (has) {
     xm_put_rows(img0, lA, dq);

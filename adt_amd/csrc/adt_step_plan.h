@@ -34,6 +34,7 @@ struct SeqSwitches {
   bool bce_merged = true;      // ADT_BCE_MERGED     the forward's logits / BCE kernel rides on the loss launch (off: on the side stream)
   // hand-overs between the backward's kernels (on by default)
   bool do_bf16{true};          // ADT_DO_BF16        dO from an out-projection reverse to the attention backward behind it as bf16 operand rows + delta
+  bool pad_elide{true};        // ADT_PAD_ELIDE      the chain kernels request no row of a 16-token tile inside a sequence's pad prefix whose value is known or dead
 };
 
 constexpr bool adt_seq_head_ok(int hd) { return hd == 16 || hd == 32 || hd == 64; }
@@ -112,6 +113,7 @@ struct StepPlan {
   int side_sites;          // ADT_SIDE_STREAM bits
   bool side_dp;            // side stream in the two-phase backward
   bool loss_one_launch;    // every loss term in one k_loss_seeds launch
+  bool pad_elide;          // the per-sequence chain kernels get the pad prefix of every sequence (adt_seq_args.h: pad_pre) and leave the rows it covers in HBM
   bool do_handover;        // the out-projection reverses hand dO to the attention backward behind them as bf16 rows + delta (adt_tt.cuh: tt_head_delta)
 };
 
@@ -152,6 +154,10 @@ static inline StepPlan adt_step_plan(const StepFacts& f, const SeqSwitches& sw) 
   // every producer (k_seqtt_post_bwd, k_seqtt_mid_bwd / k_seqtt_xattn_mid_bwd) and every consumer (k_seqtt_attn_pre_bwd, k_seq_attn_bwd /
   // k_seqtt_xattn_mid_bwd) is a per-sequence kernel exactly where `parts` holds: the lean path, whose "not covered" is an error and never a staged fallback
   p.do_handover = sw.do_bf16 && p.parts;
+  // the prefixes are written by the encoder's embedding layer (k_seqtt_enc_fwd) and read by per-sequence kernels only: the lean path with partials again.
+  // Not with 16-wide heads: those instantiations sit at their register budgets and spill already, and every form of the prefix code tried
+  // added scratch to one of them ("Pad prefix")
+  p.pad_elide = sw.pad_elide && p.parts && hd != 16;
   return p;
 }
 

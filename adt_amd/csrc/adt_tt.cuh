@@ -107,6 +107,9 @@ ADT_DEVICE_INLINE TT tt_load(const float* row, bool valid, int g) {
   for (int nt = 0; nt < 4; ++nt) t.v[nt] = p[4 * nt];
   return t;
 }
+// The 16-token tile `tile` of a sequence of L positions lies wholly inside a pad prefix of `pad` positions (adt_seq_args.h: pad_pre; 0: no prefix
+// known).  Wave-uniform: it joins the `valid` of the tile's loads whose value is an exact zero or dead at padded tokens.
+ADT_DEVICE_INLINE bool tt_pad_tile(int tile, int pad, int L) { return pad > 0 && min(tile * 16 + 16, L) <= pad; }
 // The branching form (a load only where there is a row).  k_seqtt_attn_pre_bwd keeps it: at its 256-register budget the 26 loads that the
 // unconditional form puts in flight at once spilled 208 bytes per lane and cost 5 us per launch (52.5 -> 57.0 us).
 ADT_DEVICE_INLINE TT tt_load_if(const float* row, bool valid, int g) {
