@@ -90,6 +90,10 @@ SIGNATURES = {
     "adt_attn_masked_scaled_fwd": (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, _F, _F, _P, _U, _U, _P, _I, _P, _P]),
     "adt_attn_masked_scaled_bwd": (_I, [_I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _F, _F, _P, _U, _U,
                                         _P, _I, _P, _I, _P, _I, _P]),
+    "adt_attn_masked_max_len": (_I, [_I]),
+    "adt_attn_long_fwd": (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, _F, _F, _P, _U, _U, _P, _I, _P, _P]),
+    "adt_attn_long_bwd": (_I, [_I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _F, _F, _P, _U, _U,
+                               _P, _I, _P, _I, _P, _I, _P]),
     "adt_dropact_fwd": (_I, [_P, _L, _F, _P, _U, _U, _I, _P, _P]),
     "adt_dropact_bwd": (_I, [_P, _P, _L, _F, _P, _U, _U, _I, _P, _I, _P]),
     "adt_gather_rows": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P]),

@@ -327,4 +327,35 @@ static inline AttnPlan adt_attn_masked_plan(int prec, int hd, int L, bool bwd, b
   return p;
 }
 
+// The longest sequence adt_attn_masked_plan takes at a head size (0: a head size it does not take at all): the bound its branches apply,
+// stated once for the callers that choose between it and adt_attn_long_plan.  The C ABI exports it under the same name (adt_attn_long.hip):
+// where both are visible, qualify this one as adt::.
+constexpr int adt_attn_masked_max_len(int hd) { return hd == 16 || hd == 32 || hd == 64 ? 224 : (hd == 128 || hd == 256 ? 256 : 0); }
+
+// ---- masked attention at 1 <= L <= 1024 (adt_attn_long.cuh) --------------------------------------------------------------------------
+// Always streamed, every head size.  Beside the images: LSE and delta of 1024 rows (backward), key validity as 1024 bytes and 32 bytes of
+// per-wave scratch for the first attendable key.  adt_attn_long.hip asserts the footprint against AttnLongLds.
+constexpr int ATTN_LONG_LMAX = 1024;
+constexpr size_t attn_long_lds(int prec, int hd, int kc, bool bwd) {
+  const size_t img = (size_t)kc * (hd + 8) + (size_t)hd * (kc + 8), masks = ATTN_LONG_LMAX + 32;
+  return bwd ? 2 * img * attn_esz(prec) + 2 * ATTN_LONG_LMAX * sizeof(float) + masks : img * attn_esz(prec) + masks;
+}
+
+static inline AttnPlan adt_attn_long_plan(int prec, int hd, int L, bool bwd, bool causal, bool has_key_ids, float fill) {
+  AttnPlan p{};
+  const int P = prec == ADT_PREC_F32 ? ADT_PREC_F32 : ADT_PREC_BF16;
+  p.family = ATTN_STREAMED; p.nch = 1; p.grid_y = 1;
+  if (hd != 16 && hd != 32 && hd != 64 && hd != 128 && hd != 256) {
+    snprintf(p.error, sizeof p.error, "long attention: head_dim=%d unsupported (16/32/64/128/256)", hd);
+    return p;
+  }
+  if (L < 1 || L > ATTN_LONG_LMAX) { snprintf(p.error, sizeof p.error, "long attention: L=%d outside 1..%d", L, ATTN_LONG_LMAX); return p; }
+  p.waves = ATTN_STREAMED_NW; p.kc = attn_streamed_kc(P, bwd);
+  p.grid_y = plan_ceil(plan_ceil(L, 16), p.waves);
+  p.csk = causal && !has_key_ids && fill <= -1e9f;
+  p.lds_bytes = attn_long_lds(P, hd, p.kc, bwd);
+  if (p.lds_bytes > ADT_LDS_MAX) snprintf(p.error, sizeof p.error, "long attention: hd=%d prec=%d needs %zu B of LDS (> 160 KB)", hd, P, p.lds_bytes);
+  return p;
+}
+
 }  // namespace adt

@@ -291,6 +291,40 @@ def attn_masked_bwd(prec, Q, K, V, O, LSE, dO, B, H, L, causal=False, key_ids=No
     return dQ, dK, dV
 
 
+def attn_masked_max_len(hd):
+    """The longest sequence attn_masked_fwd / attn_masked_bwd take at head size hd (0: a head size they do not take); attn_long_* go on to 1024."""
+    return _lib.load().adt_attn_masked_max_len(int(hd))
+
+
+def attn_long_fwd(prec, Q, K, V, B, H, L, causal=False, key_ids=None, fill=-1e9, p=0.0, seed=None, site=0, b_offset=0, scale=None):
+    """attn_masked_fwd for 1 <= L <= 1024 (every head size streamed); same arguments and results."""
+    d = Q.shape[1]
+    hd = d // H
+    O = torch.empty(B * L, d, device=Q.device, dtype=torch.float32)
+    LSE = torch.empty(B * H * L, device=Q.device, dtype=torch.float32)
+    scale = float(hd) ** -0.5 if scale is None else scale
+    _lib.check(_lib.load().adt_attn_long_fwd(prec, _p(_f32(Q)), _ld(Q), _p(_f32(K)), _ld(K), _p(_f32(V)), _ld(V), B, H, L, hd, float(scale), int(causal),
+                                             _p(key_ids), float(fill), float(p), _p(seed), site, b_offset, _p(O), d, _p(LSE), _stream()), "attn_long_fwd")
+    return O, LSE
+
+
+def attn_long_bwd(prec, Q, K, V, O, LSE, dO, B, H, L, causal=False, key_ids=None, fill=-1e9, p=0.0, seed=None, site=0, b_offset=0, out=None,
+                  scale=None):
+    d = Q.shape[1]
+    hd = d // H
+    if out is None:
+        dQ = torch.empty(B * L, d, device=Q.device, dtype=torch.float32)
+        dK = torch.empty_like(dQ)
+        dV = torch.empty_like(dQ)
+    else:
+        dQ, dK, dV = out
+    scale = float(hd) ** -0.5 if scale is None else scale
+    _lib.check(_lib.load().adt_attn_long_bwd(prec, _p(_f32(Q)), _ld(Q), _p(_f32(K)), _ld(K), _p(_f32(V)), _ld(V), _p(_f32(O)), _ld(O), _p(LSE),
+                                             _p(_f32(dO)), _ld(dO), B, H, L, hd, float(scale), int(causal), _p(key_ids), float(fill), float(p), _p(seed),
+                                             site, b_offset, _p(dQ), _ld(dQ), _p(dK), _ld(dK), _p(dV), _ld(dV), _stream()), "attn_long_bwd")
+    return dQ, dK, dV
+
+
 def embed_sum_fwd(ids, E, P, L, S0=None, scale=1.0):
     T = ids.numel()
     d = E.shape[1]

@@ -136,7 +136,8 @@ def main(argv=None):
             val_dev.draw(23, 0)
             test_dev.draw(24, 0)
 
-    wide = args.hidden_units != 64     # the fused executor is 64-wide; other widths (the d = 256 template, the default 50) take the general kernels
+    # the fused executor is 64-wide and stops at maxlen 224; other widths (the d = 256 template, the default 50) and longer sequences take the general kernels
+    wide = args.hidden_units != 64 or args.maxlen > 224
     if wide:
         from .model_wide import SASRecADTWide, WideSasrecTrainer
         model = SASRecADTWide(usernum, itemnum, args)

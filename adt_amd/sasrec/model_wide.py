@@ -72,8 +72,10 @@ class SASRecADTWide(FullRankMixin, FlatModule):
             self.hd, self.hd_pad, self.dp = padded_layout(d, H)
         except _lib.AdtError as e:
             raise _lib.AdtError("SASRecADT (adt_amd, wide path): %s" % e) from None
-        if self.maxlen > 256:
-            raise _lib.AdtError("SASRecADT (adt_amd, wide path): maxlen <= 256; got d=%d H=%d L=%d" % (d, H, self.maxlen))
+        if self.maxlen > 1024:
+            raise _lib.AdtError("SASRecADT (adt_amd, wide path): maxlen <= 1024; got d=%d H=%d L=%d" % (d, H, self.maxlen))
+        # past the length the resident / chunked attention kernels take at this head size the streamed long kernels run; below it, the calls are as before
+        self._long_attn = self.maxlen > ops.attn_masked_max_len(self.hd_pad)
         # dp == d: the kernels tile the width as it is.  Otherwise activations and parameters are padded to dp columns (head h at
         # [h * hd_pad, h * hd_pad + hd), zero pad lanes) and LayerNorm, the scales and the dropout indices keep the true width.
         self.lanes = (H, self.hd, self.hd_pad) if self.dp != d else None
@@ -142,7 +144,8 @@ class SASRecADTWide(FullRankMixin, FlatModule):
         else:
             Q, K, V = q.t, kv.t[:, :d], kv.t[:, d:]
         fill = float("-inf")     # the float causal mask of sasrec/modules.py:504-507
-        O, LSE = ops.attn_masked_fwd(self.prec, Q, K, V, B, H, L, True, None, fill, p, self._seed, site, tp.b_offset, scale=scale)
+        attn_fwd, attn_bwd = (ops.attn_long_fwd, ops.attn_long_bwd) if self._long_attn else (ops.attn_masked_fwd, ops.attn_masked_bwd)
+        O, LSE = attn_fwd(self.prec, Q, K, V, B, H, L, True, None, fill, p, self._seed, site, tp.b_offset, scale=scale)
         o = Act(O)
 
         def bw():
@@ -154,7 +157,7 @@ class SASRecADTWide(FullRankMixin, FlatModule):
             else:
                 q.g, kv.g = torch.empty_like(q.t), torch.empty_like(kv.t)
                 out = (q.g, kv.g[:, :d], kv.g[:, d:])
-            ops.attn_masked_bwd(self.prec, Q, K, V, O, LSE, o.g, B, H, L, True, None, fill, p, self._seed, site, tp.b_offset, out=out, scale=scale)
+            attn_bwd(self.prec, Q, K, V, O, LSE, o.g, B, H, L, True, None, fill, p, self._seed, site, tp.b_offset, out=out, scale=scale)
         tp.bw.append(bw)
         return o
 

@@ -705,6 +705,20 @@ int adt_attn_masked_scaled_bwd(int prec, const float* Q, int ldq, const float* K
                                int causal, const int32_t* key_ids, float fill, float p, const uint32_t* seed, uint32_t site,
                                uint32_t b_offset, float* dQ, int lddq, float* dK, int lddk, float* dV, int lddv, void* stream);
 
+/* ---- masked attention at 1 <= L <= 1024 ----
+ * The longest sequence adt_attn_masked_* take at a head size: 224 (hd 16 / 32 / 64), 256 (hd 128 / 256), 0 (any other hd). */
+int adt_attn_masked_max_len(int hd);
+/* adt_attn_masked_scaled_fwd / _bwd (same arguments, semantics, dropout indices and results) for 1 <= L <= 1024 at
+ * hd 16 / 32 / 64 / 128 / 256 in either precision: key / query chunks streamed through LDS at every head size.  scale > 0.
+ * With p > 0 the dropout index space (b_offset + B) * H * L * L must not exceed 2^32. */
+int adt_attn_long_fwd(int prec, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int B, int H, int L,
+                      int hd, float scale, int causal, const int32_t* key_ids, float fill, float p, const uint32_t* seed,
+                      uint32_t site, uint32_t b_offset, float* O, int ldo, float* LSE, void* stream);
+int adt_attn_long_bwd(int prec, const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, const float* O, int ldo,
+                      const float* LSE, const float* dO, int lddo, int B, int H, int L, int hd, float scale, int causal,
+                      const int32_t* key_ids, float fill, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset,
+                      float* dQ, int lddq, float* dK, int lddk, float* dV, int lddv, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

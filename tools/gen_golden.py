@@ -313,6 +313,11 @@ if __name__ == "__main__":
         for nm, d, H, seed in (("sasrec_w50_h1", 50, 1, 41), ("sasrec_w50_h2", 50, 2, 43), ("sasrec_w100_h2", 100, 2, 47)):
             case_sampled(nm, V=50, L=24, d=d, H=H, nl=2, B=3, seed=seed, lam1=[0.104292, 0.065892], lam2=[0.100833, 0.000607])
         sys.exit(0)
+    if sys.argv[1:] == ["long"]:
+        # the flagship width past the resident attention kernels' 224 rows (the streamed long kernels, head size 32): pins the oracle to the
+        # reference beyond L = 200.  Sampled like the d = 256 cases: the full tensors of case_small would pass the size limit of a fixture.
+        case_sampled("sasrec_l272", V=50, L=272, d=64, H=2, nl=1, B=3, seed=53, lam1=[0.104292], lam2=[0.100833])
+        sys.exit(0)
     case_small("sasrec_small", B=4, L=16, d=32, H=2, nl=2, V=50, seed=11,
                lam1=[0.104292, 0.065892], lam2=[0.100833, 0.000607], wd=1e-3)
     case_small("sasrec_small_h1", B=3, L=12, d=16, H=1, nl=1, V=30, seed=13, lam1=[0.05], lam2=[0.02], wd=1e-4)
