@@ -121,6 +121,13 @@ SIGNATURES = {
     "adt_klattn_mfma_fwd": (_I, [_I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _P, _U, _U, _P, _I, _P, _I, _P, _P]),
     "adt_klattn_mfma_bwd": (_I, [_I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F,
                                  _P, _U, _U, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "adt_wattn_max_len": (_I, [_I]),
+    "adt_wattn_long_fwd": (_I, [_I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _P, _U, _U, _P, _I, _P, _I, _P, _P]),
+    "adt_wattn_long_bwd": (_I, [_I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F,
+                                _P, _U, _U, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "adt_klattn_long_fwd": (_I, [_I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _P, _U, _U, _P, _I, _P, _I, _P, _P]),
+    "adt_klattn_long_bwd": (_I, [_I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F,
+                                 _P, _U, _U, _P, _P, _P, _P, _P, _P, _I, _P]),
     "adt_dense_rows_enable": (_I, [_I]),
     "adt_dense_workspace": (_I, [_P, _L]),
     "adt_dense_bwd_ws_bytes": (_L, [_I, _I, _I, _I]),

@@ -5,7 +5,8 @@
 // All of it is exact fp32 on the vector ALUs: the attention is 0.65 GFLOP per launch at the Beauty template
 // (B 256, H 4, L 100, hd 16), so the work is organised for wavefront-level reductions instead of MFMA tiles --
 // one workgroup per (sequence, head) with the key side (or, backward pass B, the query side) of the head resident
-// in LDS, one wave per query row, one key per lane (up to 4 for L <= 256); softmax statistics are wave reductions,
+// in LDS, one wave per query row, one key per lane (up to 4 for L <= 256; at hd 64 the LDS ends it at L = 141, adt_wattn_max_len -- longer
+// sequences run adt_wattn_long.cuh); softmax statistics are wave reductions,
 // and the probability row goes through LDS once so the lanes can re-map to (feature, partition) for P V.
 //
 //   s_ij = -(|mq_i|^2 + sum(Sq_i) + |mk_j|^2 + sum(Sk_j) - 2 (mq_i . mk_j + sqrt(Sq_i) . sqrt(Sk_j))) / sqrt(hd) + A_ij
@@ -14,32 +15,9 @@
 //   mean context = Pd Vm, covariance context = (Pd * Pd) Vc                      (modules.py:253-256)
 #pragma once
 #include "adt_common.cuh"
+#include "adt_stosa_args.cuh"      // WAttnArgs, W_MASK, W_KPL, wattn_lds_bytes, w_score
 
 namespace adt {
-
-struct WAttnArgs {
-  const float* Qm; int ldqm; const float* Qc; int ldqc;   // query mean / covariance (T x >= H*hd), cov = ELU(.)+1 already
-  const float* Km; int ldkm; const float* Kc; int ldkc;
-  const float* Vm; int ldvm; const float* Vc; int ldvc;
-  const int* kid;            // (B*L) ids of the KEY sequence: key j is padding when kid <= 0
-  int B, H, L, hd;
-  float scale;               // 1/sqrt(hd) (unused: the kernels divide, like the reference)
-  DropCfg drop; uint32_t bh_offset;     // idx = ((bh + bh_offset) * L + i) * L + j
-  float* Om; int ldom; float* Oc; int ldoc;   // contexts (T x H*hd)
-  float* LSE;                // (B*H*L)
-  const float* dOm; int lddom; const float* dOc; int lddoc;
-  float *dQm, *dQc, *dKm, *dKc, *dVm, *dVc; int ldd;   // gradients (T x ldd), overwritten
-};
-
-constexpr float W_MASK = -4294967296.0f;   // float32(-2**32 + 1), stosa/models.py:226,230
-constexpr int W_KPL = 4;                    // keys per lane: L <= 256
-
-static inline size_t wattn_lds_bytes(int L, int hd, bool bwd) {
-  // 4 resident tensors [L][hd+1], 2 row vectors [L] (+ 2 more in the backward), per-wave scratch 4 x (3*L' + 4*hd)
-  const int Lp = (L + 63) / 64 * 64;
-  size_t f = (size_t)4 * L * (hd + 1) + (size_t)(bwd ? 4 : 2) * Lp + (size_t)4 * (3 * Lp + 4 * hd);
-  return f * sizeof(float);
-}
 
 // stage a head slice (L x hd) into LDS rows of stride hd+1, optionally through sqrt(clamp(.)); also return via `norm`
 // (if non-null) the per-row sums |m|^2 (SQUARE) or sum(c) (plain) ACCUMULATED into norm[r]
@@ -61,15 +39,6 @@ ADT_DEVICE_INLINE void w_stage(float* dst, const float* g, int ld, int L, int hd
       if (sub == 0) norm[r] += part;
     }
   }
-}
-
-// A query with no attendable key (the left-padded prefix) has EVERY score shifted by the mask: in fp32 x - 2^32 rounds to a
-// multiple of 512, so all of them collapse to -2^32 and the row is uniform over all L keys.  -2^32 + log(L) is not
-// representable, so such rows keep the reference's rounding but drop the common shift (softmax is shift-invariant and
-// (x + MASK) - MASK is exact): probabilities and gradients are unchanged, the saved LSE stays accurate.
-ADT_DEVICE_INLINE float w_score(float x, bool masked, bool dead_row) {
-  if (dead_row) return (x + W_MASK) - W_MASK;
-  return masked ? x + W_MASK : x;
 }
 
 // The scaled negative Wasserstein distance of one (query, key) pair, computed by ONE sequence of fused multiply-adds so that

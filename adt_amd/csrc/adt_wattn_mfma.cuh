@@ -5,7 +5,8 @@
 // v_mfma_f32_16x16x32_bf16 per 16 x 16 score tile (exact mode: eight v_mfma_f32_16x16x4_f32).  The contexts P~ Vm and (P~ * P~) Vc, the
 // gradient products dP~ = dOm Vm^T + 2 P~ (dOc Vc^T), dQ = -2 dW [mk | sk], dK, dVm, dVc are MFMA products too; only the softmax
 // statistics, the additive mask and the dropout hash stay on the vector ALUs.  k_wattn_fwd / k_wattn_bwd of adt_stosa.cuh (one wave
-// per query row, one key per lane, all VALU) remain for the shapes this file does not cover (hd = 64 or L > 128).
+// per query row, one key per lane, all VALU) remain for the shapes this file does not cover (hd = 64 or L > 128) up to their own bound
+// (L <= 256 and the LDS: adt_wattn_max_len, 141 at hd 64); past it the streamed kernels of adt_wattn_long.cuh take every L <= 1024.
 //
 // One workgroup per (sequence, head), four waves, a wave owns 16-query tiles (forward, backward pass A) or 16-key tiles (pass B).
 // LDS holds fp32 row images (stride K + 4: conflict-free 8-float fragments, adt_common.cuh) and, for the products that contract over
@@ -24,7 +25,7 @@
 // Covered, for both metrics: hd 16 and 32, L <= 128 (MAXKT = 8 tiles of 16 keys); the LDS footprint is wattn_mfma_lds_bytes() for
 // both (about 142 KB in the backward at hd 32 / L 128).
 #pragma once
-#include "adt_stosa.cuh"
+#include "adt_stosa_args.cuh"
 
 namespace adt {
 

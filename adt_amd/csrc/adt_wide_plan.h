@@ -358,4 +358,50 @@ static inline AttnPlan adt_attn_long_plan(int prec, int hd, int L, bool bwd, boo
   return p;
 }
 
+// ---- STOSA-ADT distance attention (adt_stosa.cuh, adt_klattn.cuh: vector ALU; adt_wattn_long.cuh: streamed, matrix cores) ---------------
+// The vector-ALU kernels keep the whole (b, h) in LDS: four tensors of L rows of hd + 1 floats, 2 (forward) or 4 (backward) row vectors of
+// L rounded up to 64 and four waves' scratch of 3 such vectors + 4 hd floats.  adt_stosa_args.cuh's wattn_lds_bytes, restated here for the host
+// program and asserted equal in adt_wattn_long.hip.
+constexpr int WATTN_VALU_LMAX = 256;            // W_KPL = 4 keys per lane
+constexpr size_t wattn_valu_lds(int L, int hd, bool bwd) {
+  const size_t lp = (size_t)plan_round(L, 64);
+  return ((size_t)4 * L * (hd + 1) + (bwd ? 4 : 2) * lp + 4 * (3 * lp + 4 * (size_t)hd)) * sizeof(float);
+}
+// The longest L at which adt_wattn_* / adt_klattn_* run both directions at a head size: the smaller of 256 and what the LDS allows
+// (0: a head size they do not take).  The footprint grows with L, so the first L that fits from above is the bound.  The C ABI exports it
+// under the same name (adt_wattn_long.hip): where both are visible, qualify this one as adt::.
+constexpr int adt_wattn_max_len(int hd) {
+  if (hd != 16 && hd != 32 && hd != 64) return 0;
+  int L = WATTN_VALU_LMAX;
+  while (L > 0 && (wattn_valu_lds(L, hd, false) > ADT_LDS_MAX || wattn_valu_lds(L, hd, true) > ADT_LDS_MAX)) --L;
+  return L;
+}
+
+// The streamed family at 1 <= L <= 1024, head size 16 / 32 / 64, both metrics: the scheme of adt_attn_long_plan (grid (B*H, groups of four
+// 16-row tiles), one tile per wave) over fp32 images whatever the precision (bf16 operands are converted at the MFMA, as in
+// adt_wattn_mfma.cuh), so the footprint does not depend on prec.  A chunk of kc rows holds the cross-term image (2 hd + 4 floats a row), its
+// norms / biases and two transposed value images (forward), or the image, its norms, its transpose, two natural and two transposed images
+// (backward) plus LSE and delta of 1024 rows; then 1024 key-validity bytes + 32.  adt_wattn_long.hip asserts it against WattnLongLds.
+constexpr int wattn_long_kc(bool bwd) { return bwd ? 32 : 64; }
+constexpr size_t wattn_long_lds(int hd, int kc, bool bwd) {
+  const size_t cat = (size_t)kc * (2 * hd + 4) + kc, t = (size_t)hd * (kc + 4), nat = (size_t)kc * (hd + 4), masks = ATTN_LONG_LMAX + 32;
+  return (bwd ? cat + 2 * t + 2 * nat + 2 * t + 2 * ATTN_LONG_LMAX : cat + 2 * t) * sizeof(float) + masks;
+}
+
+// csk: the attention is always causal, so the tiles above the diagonal are always skipped -- by the kernels' own rule, which exempts every
+// tile that holds a query without an attendable key (such a row attends to all L keys; adt_wattn_long.cuh).
+static inline AttnPlan adt_wattn_long_plan(int prec, int hd, int L, bool bwd) {
+  AttnPlan p{};
+  p.family = ATTN_STREAMED; p.nch = 1; p.grid_y = 1;
+  if (prec != ADT_PREC_F32 && prec != ADT_PREC_BF16) { snprintf(p.error, sizeof p.error, "long distance attention: prec=%d unsupported", prec); return p; }
+  if (hd != 16 && hd != 32 && hd != 64) { snprintf(p.error, sizeof p.error, "long distance attention: head_dim=%d unsupported (16/32/64)", hd); return p; }
+  if (L < 1 || L > ATTN_LONG_LMAX) { snprintf(p.error, sizeof p.error, "long distance attention: L=%d outside 1..%d", L, ATTN_LONG_LMAX); return p; }
+  p.waves = ATTN_STREAMED_NW; p.kc = wattn_long_kc(bwd);
+  p.grid_y = plan_ceil(plan_ceil(L, 16), p.waves);
+  p.csk = true;
+  p.lds_bytes = wattn_long_lds(hd, p.kc, bwd);
+  if (p.lds_bytes > ADT_LDS_MAX) snprintf(p.error, sizeof p.error, "long distance attention: hd=%d needs %zu B of LDS (> 160 KB)", hd, p.lds_bytes);
+  return p;
+}
+
 }  // namespace adt

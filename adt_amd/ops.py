@@ -473,6 +473,65 @@ def klattn_bwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, 
     return _stosa_attn_bwd("klattn_mfma_bwd", "klattn_bwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site, b_offset, out, prec)
 
 
+def wattn_max_len(hd):
+    """The longest sequence at which wattn_* / klattn_* run both directions at head size hd (256 at hd 16 / 32, 141 at hd 64: their LDS
+    footprint; 0: a head size they do not take); wattn_long_* / klattn_long_* go on to 1024."""
+    n = _lib.load().adt_wattn_max_len(int(hd))
+    if n < 0:
+        _lib.check(n, "wattn_max_len")
+    return n
+
+
+def _stosa_long_prec(prec):
+    return PREC_F32 if prec is None else int(prec)
+
+
+def _stosa_long_fwd(name, Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, site, b_offset, prec):
+    d = Qm.shape[1]
+    hd = d // H
+    Om = torch.empty(B * L, d, device=Qm.device, dtype=torch.float32)
+    Oc = torch.empty_like(Om)
+    LSE = torch.empty(B * H * L, device=Qm.device, dtype=torch.float32)
+    _lib.check(getattr(_lib.load(), "adt_" + name)(
+        _stosa_long_prec(prec), _p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc), _p(_f32(Vm)), _ld(Vm),
+        _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), B, H, L, hd, float(p), _p(seed), site, b_offset, _p(Om), d, _p(Oc), d, _p(LSE), _stream()), name)
+    return Om, Oc, LSE
+
+
+def _stosa_long_bwd(name, Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site, b_offset, out, prec):
+    d = Qm.shape[1]
+    hd = d // H
+    outs = [torch.empty(B * L, d, device=Qm.device, dtype=torch.float32) for _ in range(6)] if out is None else list(out)
+    ldd = _ld(outs[0])
+    assert all(_ld(o) == ldd for o in outs)
+    _lib.check(getattr(_lib.load(), "adt_" + name)(
+        _stosa_long_prec(prec), _p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc), _p(_f32(Vm)), _ld(Vm),
+        _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), _p(Om), _ld(Om), _p(Oc), _ld(Oc), _p(LSE), _p(_f32(dOm)), _ld(dOm), _p(_f32(dOc)), _ld(dOc), B, H, L,
+        hd, float(p), _p(seed), site, b_offset, *[_p(o) for o in outs], ldd, _stream()), name)
+    return outs
+
+
+def wattn_long_fwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p=0.0, seed=None, site=0, b_offset=0, prec=None):
+    """wattn_fwd for every 1 <= L <= 1024 on the streamed matrix-core kernels (adt_wattn_long.cuh); same arguments and results.  prec:
+    PREC_BF16, or PREC_F32 / None for the exact fp32 MFMA.  A shape they do not take is an error: there is nothing to fall back to."""
+    return _stosa_long_fwd("wattn_long_fwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, site, b_offset, prec)
+
+
+def wattn_long_bwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p=0.0, seed=None, site=0, b_offset=0, out=None, prec=None):
+    """wattn_bwd for every 1 <= L <= 1024; LSE (and the contexts) must come from wattn_long_fwd at the same prec."""
+    return _stosa_long_bwd("wattn_long_bwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site, b_offset, out, prec)
+
+
+def klattn_long_fwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p=0.0, seed=None, site=0, b_offset=0, prec=None):
+    """klattn_fwd for every 1 <= L <= 1024; as wattn_long_fwd."""
+    return _stosa_long_fwd("klattn_long_fwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, site, b_offset, prec)
+
+
+def klattn_long_bwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p=0.0, seed=None, site=0, b_offset=0, out=None, prec=None):
+    """klattn_bwd for every 1 <= L <= 1024; as wattn_long_bwd."""
+    return _stosa_long_bwd("klattn_long_bwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site, b_offset, out, prec)
+
+
 def kldist_bpr(Sm, Sc, Em, Ec, pos, neg, pvn_weight, inv_count, dEm, dEc, loss3):
     """bpr_optimization on row-wise KL divergences; arguments and outputs as wdist_bpr."""
     T, d = Sm.shape

@@ -6,7 +6,8 @@ Same constructor (`DisenDistSAModel(args)`), `finetune(input_ids, dec_ids, user_
 shapes, `item_mean_embeddings` / `item_cov_embeddings` reachable as attributes (the reference's trainer
 reads them directly, stosa/trainer.py:361-364,466-467).  All arithmetic runs in libadt_hip.so: dense layers
 (adt_gemm.cuh), the Wasserstein attention and the BPR / full-sort distance kernels (adt_stosa.cuh, exact fp32 wave-level
-reductions), LayerNorm / dropout / ELU row kernels.
+reductions), LayerNorm / dropout / ELU row kernels.  maxlen up to 1024: past ops.wattn_max_len(head size) rows (256; 141 at head size 64)
+the attention runs on the streamed matrix-core kernels of adt_wattn_long.cuh.
 """
 import numpy as np
 import torch
@@ -16,6 +17,7 @@ from ..fullrank import DistRankMixin
 from ..wide import Act, FlatModule, Tape, give
 
 LN_EPS = 1e-12
+MAXLEN_MAX = 1024      # the streamed distance attention's bound (ops.wattn_long_fwd)
 SITE_EMB = {"seq_mean": 1, "seq_cov": 2, "dec_mean": 3, "dec_cov": 4}
 
 
@@ -97,6 +99,12 @@ class DisenDistSAModel(DistRankMixin, FlatModule):
         kl = self.distance_metric == "kl"
         # attention, BPR loss and full-sort score of the chosen metric (stosa/modules.py:244-248, trainer.py:372-379, :597-600)
         self._attn_fwd, self._attn_bwd = (ops.klattn_fwd, ops.klattn_bwd) if kl else (ops.wattn_fwd, ops.wattn_bwd)
+        # past the length the whole-(b, h) kernels hold in LDS (256; 141 at head size 64): the streamed kernels, up to 1024 (adt_wattn_long.cuh)
+        if not 1 <= int(args.maxlen) <= MAXLEN_MAX:
+            raise _lib.AdtError("DisenDistSAModel (adt_amd): maxlen must be in 1..%d, got %r" % (MAXLEN_MAX, args.maxlen))
+        self._long_attn = self.maxlen > ops.wattn_max_len(d // H)
+        if self._long_attn:
+            self._attn_fwd, self._attn_bwd = (ops.klattn_long_fwd, ops.klattn_long_bwd) if kl else (ops.wattn_long_fwd, ops.wattn_long_bwd)
         self._dist_bpr, self._dist_full = (ops.kldist_bpr, ops.kldist_full) if kl else (ops.wdist_bpr, ops.wdist_full)
         table, n_trained = param_table(args.item_size, args.maxlen, d, H, args.num_layers, args.num_users, block, dec_layernorm)
         self._build_flat(table, getattr(args, "device", "cuda:0"), REF_ORDER)

@@ -280,7 +280,8 @@ int adt_wdist_full(const float* Sm, const float* Sc, int lds, const float* Em, c
                    float* dist, int ldo, void* stream);
 /* STOSA-ADT with distance_metric='kl' (adt_klattn.cuh).  KL-divergence attention (stosa/modules.py:52-70 kl_distance_matmul with its
  * broadcasts: the mean term reads key row i, the trace term is transposed; log(prod c) taken as sum(log c)): the same arguments,
- * shapes (head size 16 / 32 / 64, L <= 256) and outputs as adt_wattn_fwd / adt_wattn_bwd, exact fp32. */
+ * shapes (head size 16 / 32 / 64, L <= 256 and within the 160 KB of LDS: adt_wattn_max_len, 141 at head size 64) and outputs as
+ * adt_wattn_fwd / adt_wattn_bwd, exact fp32.  Longer sequences: adt_klattn_long_fwd / _bwd below. */
 int adt_klattn_fwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
                    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd,
                    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc,
@@ -718,6 +719,33 @@ int adt_attn_long_bwd(int prec, const float* Q, int ldq, const float* K, int ldk
                       const float* LSE, const float* dO, int lddo, int B, int H, int L, int hd, float scale, int causal,
                       const int32_t* key_ids, float fill, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset,
                       float* dQ, int lddq, float* dK, int lddk, float* dV, int lddv, void* stream);
+
+/* ---- STOSA-ADT distance attention at 1 <= L <= 1024 ----
+ * The longest sequence at which adt_wattn_* / adt_klattn_* run both directions at a head size: the smaller of 256 and what their
+ * whole-(b, h) LDS footprint allows (hd 16 / 32: 256, hd 64: 141), 0 for any other hd. */
+int adt_wattn_max_len(int hd);
+/* adt_wattn_fwd / _bwd and adt_klattn_fwd / _bwd (same arguments after prec, same semantics, mask rule, dropout indices and results) for
+ * every 1 <= L <= 1024 at hd 16 / 32 / 64 on the matrix cores: key / query chunks streamed through LDS with an online softmax.  prec:
+ * ADT_PREC_BF16 (bf16 operands) or ADT_PREC_F32 (exact fp32 MFMA).  Every row stride a multiple of 4 floats; with p > 0 the dropout
+ * index space (b_offset + B) * H * L * L must stay below 2^32.  Anything not covered is an error (< 0), never 1. */
+int adt_wattn_long_fwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                       const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float p,
+                       const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE,
+                       void* stream);
+int adt_wattn_long_bwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                       const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc,
+                       int ldoc, const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd, float p,
+                       const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc, float* dKm, float* dKc, float* dVm,
+                       float* dVc, int ldd, void* stream);
+int adt_klattn_long_fwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                        const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd,
+                        float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc,
+                        float* LSE, void* stream);
+int adt_klattn_long_bwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                        const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom,
+                        const float* Oc, int ldoc, const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B,
+                        int H, int L, int hd, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc,
+                        float* dKm, float* dKc, float* dVm, float* dVc, int ldd, void* stream);
 
 #ifdef __cplusplus
 }

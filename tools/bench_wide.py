@@ -3,7 +3,7 @@
 one GPU, synthetic ids, HIP graph).  Not the driver's bench (bench.py measures configs[1]); results go to profiles/.
 
     python tools/bench_wide.py bert  [--steps 20] [--batch 256]
-    python tools/bench_wide.py stosa [--steps 20] [--metric wasserstein|kl]
+    python tools/bench_wide.py stosa [--steps 20] [--metric wasserstein|kl] [--stosa_maxlen 100] [--stosa_heads 4]
 """
 import argparse
 import json
@@ -70,13 +70,13 @@ def run_stosa(args):
     from adt_amd.stosa.models import DisenDistSAModel
     from adt_amd.stosa.trainer import FusedStosaTrainer
     a = Args()
-    a.device, a.item_size, a.maxlen, a.hidden_units, a.num_heads, a.num_layers, a.num_users = "cuda:0", 12103, 100, 64, 4, 1, 22364
+    a.device, a.item_size, a.maxlen, a.hidden_units, a.num_heads, a.num_layers, a.num_users = "cuda:0", 12103, args.stosa_maxlen, 64, args.stosa_heads, 1, 22364
     a.dropout, a.attention_dropout, a.pvn_weight, a.precision, a.distance_metric = 0.3, 0.3, 0.005, "bf16", args.metric
     torch.manual_seed(42)
     m = DisenDistSAModel(a)
     tr = FusedStosaTrainer(m, [0.1], [0.1], use_graph=not args.no_graph, seed=42)
     r = np.random.RandomState(2)
-    B, L, V = args.batch, 100, a.item_size
+    B, L, V = args.batch, a.maxlen, a.item_size
 
     def batch():
         inp = np.zeros((B, L), np.int32)
@@ -100,8 +100,8 @@ def run_stosa(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     kl = args.metric == "kl"
-    print(json.dumps({"workload": "STOSA-ADT Beauty shape: d=64 H=4 L=100 1+1 layers item_size=12103, batch %d, dropout 0.3, full train step%s"
-                      % (B, ", distance_metric kl" if kl else ""),
+    print(json.dumps({"workload": "STOSA-ADT Beauty shape: d=64 H=%d L=%d 1+1 layers item_size=12103, batch %d, dropout 0.3, full train step%s"
+                      % (a.num_heads, L, B, ", distance_metric kl" if kl else ""),
                       "ms_per_step": round(dt / args.steps * 1e3, 3), "sequences_per_s": round(B * args.steps / dt, 1), "loss": round(float(tr.loss()), 4),
                       "steps": args.steps, "warmup": args.warmup,
                       "dtype": "bf16 MFMA operands (dense layers and %s attention), fp32 accumulation, statistics and losses" % ("KL" if kl else "Wasserstein")}))
@@ -150,6 +150,8 @@ if __name__ == "__main__":
     ap.add_argument("--mcap", type=float, default=0.3)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl"], help="stosa: distance_metric")
+    ap.add_argument("--stosa_maxlen", type=int, default=100, help="stosa: maxlen (the Beauty template's 100; up to 1024)")
+    ap.add_argument("--stosa_heads", type=int, default=4, help="stosa: heads of the 64-wide model (4: Beauty / Tools, 1: Home / Office / Toys)")
     ap.add_argument("--hidden_units", type=int, default=256, help="sasrec256: width (default: the template's)")
     ap.add_argument("--num_heads", type=int, default=2)
     ap.add_argument("--maxlen", type=int, default=200)

@@ -27,15 +27,15 @@ class Args:
     pass
 
 
-def stosa_batch(r, B, L, V):
+def stosa_batch(r, B, L, V, pad_min=0):
     """Batch in the layout of stosa/datasets.py (left-padded input_ids, dec_ids shifted by one, target_pos = next item,
-    target_neg sampled, 0 where padded)."""
+    target_neg sampled, 0 where padded).  Row 0 is full length; every other row has a padded prefix of at least pad_min positions."""
     inp = np.zeros((B, L), np.int64)
     dec = np.zeros((B, L), np.int64)
     pos = np.zeros((B, L), np.int64)
     neg = np.zeros((B, L), np.int64)
     for b in range(B):
-        n = L if b == 0 else int(r.randint(2, L + 1))
+        n = L if b == 0 else int(r.randint(2, L + 1 - pad_min))
         items = r.randint(1, V, size=n + 1)
         inp[b, L - n:] = items[:-1]
         pos[b, L - n:] = items[1:]
@@ -56,7 +56,7 @@ def kl_predict_full(modules, mo, co, Em, Ec):
     return res[:, :V]
 
 
-def reference_model(cfg_kw, B, seed, metric):
+def reference_model(cfg_kw, B, seed, metric, pad_min=0):
     """The reference's DisenDistSAModel with the seeded weights of a fixture and that fixture's batch: (cfg, args, model, the
     reference's modules, (input_ids, dec_ids, pos_ids, neg_ids))."""
     from tools.gen_golden_wide import _import_from
@@ -69,7 +69,7 @@ def reference_model(cfg_kw, B, seed, metric):
     for k in P:   # biases away from zero so that their gradients are exercised
         if k.endswith(".bias") and "LayerNorm" not in k:
             P[k] = (0.02 * r.standard_normal(P[k].shape)).astype(np.float32)
-    batch = stosa_batch(r, B, cfg.maxlen, cfg.item_size)
+    batch = stosa_batch(r, B, cfg.maxlen, cfg.item_size, pad_min)
     a = Args()
     a.item_size, a.hidden_units, a.maxlen, a.num_users, a.dropout, a.attention_dropout = cfg.item_size, cfg.hidden_units, cfg.maxlen, cfg.num_users, 0.0, 0.0
     a.num_heads, a.num_layers, a.hidden_act, a.initializer_range, a.distance_metric, a.kernel_param = cfg.num_heads, cfg.num_layers, "gelu", 0.02, metric, 1.0
@@ -79,8 +79,9 @@ def reference_model(cfg_kw, B, seed, metric):
     return cfg, a, m, modules, batch
 
 
-def gen_stosa(tag, cfg_kw, B, seed, lam1, lam2, lr=1e-3, keep_w3=True, compact=False, steps=3, metric="wasserstein", keep_w1=True, thresh=8192):
-    cfg, a, m, modules, (inp, dec, pos, neg) = reference_model(cfg_kw, B, seed, metric)
+def gen_stosa(tag, cfg_kw, B, seed, lam1, lam2, lr=1e-3, keep_w3=True, compact=False, steps=3, metric="wasserstein", keep_w1=True, thresh=8192,
+              pad_min=0):
+    cfg, a, m, modules, (inp, dec, pos, neg) = reference_model(cfg_kw, B, seed, metric, pad_min)
     t = [torch.from_numpy(x) for x in (inp, dec, pos, neg)]
     uid = torch.zeros(B, dtype=torch.long)
     out = {"seed": seed, "input_ids": inp, "dec_ids": dec, "pos_ids": pos, "neg_ids": neg, "lambda1": np.array(lam1), "lambda2": np.array(lam2),
@@ -186,6 +187,16 @@ def main_kl():
               seed=33, lam1=[0.0021], lam2=[0.0009], **kw)
 
 
+def main_long():
+    """stosa_l272.npz and stosa_kl_l272.npz: past the length the whole-(b, h) attention kernels hold in LDS (256; 141 at head size 64), at
+    the head size of the Home / Office / Toys templates (d 64, one head).  Row 0 is full length, row 1 has a padded prefix of at least 40
+    positions (queries without an attendable key over several 16-row tiles); compacted like the KL fixtures."""
+    cfg_kw = dict(item_size=40, maxlen=272, hidden_units=64, num_heads=1, num_layers=1, num_users=2, pvn_weight=0.05)
+    kw = dict(keep_w3=False, keep_w1=False, compact=True, steps=1, thresh=2048, pad_min=40)
+    for metric in ("wasserstein", "kl"):
+        gen_stosa("l272", cfg_kw, B=2, seed=27, lam1=[0.1], lam2=[0.05], metric=metric, **kw)
+
+
 def main_kl_rowwise():
     """stosa_kl_rowwise.npz: the model, seed and input_ids of stosa_kl_small.npz; rowwise_dist[b][v] = the reference's kl_distance
     (stosa/modules.py:45-50) of user b's last-position (mean, cov) from item v's (mean, ELU(cov) + 1), every row of the item tables --
@@ -211,6 +222,6 @@ if __name__ == "__main__":
     import argparse
     sys.path.insert(0, REPO)
     ap = argparse.ArgumentParser()
-    ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl", "kl_rowwise"])
+    ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl", "kl_rowwise", "long"])
     metric = ap.parse_args().metric
-    main_kl_rowwise() if metric == "kl_rowwise" else main(metric)
+    main_kl_rowwise() if metric == "kl_rowwise" else (main_long() if metric == "long" else main(metric))

@@ -4,7 +4,7 @@
 fixtures are data only: seeded inputs, the seed that regenerates the numpy weights, and the tensors the reference
 produced for them.
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_wide.py [bert|stosa|stosa_cfg5|stosa_kl|stosa_kl_rowwise]
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_wide.py [bert|stosa|stosa_cfg5|stosa_kl|stosa_kl_rowwise|stosa_long]
 
 The loss assembly calls the same torch functions, in the same order, as the reference's training loops
 (bert4rec/trainer.py:100-138, stosa/trainer.py:392-447 + :358-391), which are not importable as functions without the
@@ -158,6 +158,9 @@ def main():
     if "stosa_kl_rowwise" in which:
         from tools import gen_golden_stosa
         gen_golden_stosa.main_kl_rowwise()
+    if "stosa_long" in which:
+        from tools import gen_golden_stosa
+        gen_golden_stosa.main_long()
 
 
 if __name__ == "__main__":
