@@ -60,6 +60,11 @@ def parse_args(argv=None):
                         "not the host run's trajectory")
     p.add_argument("--remask_every_epoch", action="store_true",
                    help="with --device_batches: draw a fresh set of masks every epoch instead of one per example for the whole run")
+    p.add_argument("--fused_head", action="store_true",
+                   help="at --hidden_units 64: compute the all-item logits and the cross-entropy in the fused kernels (adt_lce_fwd_bwd), which keep "
+                        "no (rows, items) logit matrix in memory, instead of the dense head; the probabilities enter the gradient products rounded "
+                        "to bf16, so such a run is not the unfused run's trajectory.  Widths 128 / 256 use the fused head already; under "
+                        "--precision f32 the flag has no effect")
     args = p.parse_args(argv)
     if args.remask_every_epoch and not args.device_batches:
         p.error("--remask_every_epoch needs --device_batches")

@@ -4,7 +4,7 @@ bidirectional masked-item encoder + reconstruction decoder + per-head independen
 Same constructor (`BertModel(usernum, itemnum, args)`), `forward(src_ids, dec_ids, seq_pos_ids, seq_sent_ids, deq_pos_ids,
 deq_sent_ids)` 4-tuple, `predict(user_ids, seqs, seq_pos_ids, seq_sent_ids, candidates)` and state_dict names/shapes
 (SURVEY.md 8b), but every parameter is a view into one flat fp32 buffer and all arithmetic runs in libadt_hip.so:
-dense layers on MFMA (adt_gemm.cuh), masked bidirectional attention (adt_attn_gen.cuh), LayerNorm / dropout / embedding
+dense layers on MFMA (adt_gemm.cuh), masked bidirectional attention (adt_attn_gen.cuh; past 224 rows, up to maxlen 1024, the streamed adt_attn_long.cuh), LayerNorm / dropout / embedding
 row kernels, and an all-item logits + cross-entropy evaluated on the masked rows only (the reference materialises
 (B, L, V+100) logits; rows whose label is 0 contribute neither loss nor gradient, bert4rec/trainer.py:45).
 
@@ -22,6 +22,7 @@ from ..wide import Act, FlatModule, Tape, give
 
 LN_EPS = 1e-5
 MASK_FILL = -1e9
+MAX_LEN = 1024          # the streamed attention kernels' bound (ops.attn_long_*)
 SITE_EMB_SEQ, SITE_EMB_DEC = 1, 2
 _MHA = ("query_transfer", "key_transfer", "value_transfer", "out_transfer")
 
@@ -86,12 +87,18 @@ class BertModel(FullRankMixin, FlatModule):
         self.dropout, self.attention_dropout = _lib.dropout_rate(args.dropout, "dropout"), _lib.dropout_rate(args.attention_dropout, "attention_dropout")
         self.vocab = itemnum + 100 if vocab is None else vocab          # bert4rec/model/bert.py:20 (the supernet: itemnum + 2)
         self.ldv = (self.vocab + 3) // 4 * 4
-        self.use_lce = os.environ.get("ADT_LCE", "1") != "0"            # fused all-item logits + CE where the shape allows (bf16, d 128 / 256)
+        # fused all-item logits + CE where the shape allows (bf16; d 128 / 256 always, d 64 only with args.fused_head: without the flag a
+        # d 64 model keeps the unfused head and its numbers)
+        self.use_lce = os.environ.get("ADT_LCE", "1") != "0"
+        self.fused_head = bool(getattr(args, "fused_head", False))
         self.args = args
         self.prec = {"f32": ops.PREC_F32, "fp32": ops.PREC_F32, "bf16": ops.PREC_BF16}[getattr(args, "precision", "bf16")]
         if self.hidden_units % 64 or (self.hidden_units // self.num_heads) not in (16, 32, 64):
             raise _lib.AdtError("BertModel (adt_amd): hidden_units must be a multiple of 64 with head size 16/32/64, got d=%d H=%d"
                                 % (self.hidden_units, self.num_heads))
+        if not 1 <= self.maxlen <= MAX_LEN:
+            raise _lib.AdtError("BertModel (adt_amd): maxlen must be in 1..%d, got d=%d H=%d L=%d"
+                                % (MAX_LEN, self.hidden_units, self.num_heads, self.maxlen))
         self._build_flat(param_table(itemnum, args.maxlen, args.hidden_units, args.num_heads, args.num_layers, self.inner_units,
                                      getattr(args, "type_vocab_size", 2), self.vocab, block), args.device, REF_ORDER)
         # bert4rec/trainer.py:29-37 re-initialises every Linear/Embedding weight N(0.01, initializer_range), LayerNorm 1/0,
@@ -170,14 +177,17 @@ class BertModel(FullRankMixin, FlatModule):
                            self.span(kw, p + ".value_transfer.weight", (2 * d, d), grad=True), self.span(p + ".key_transfer.bias", vb, (2 * d,), grad=True))
             q, k, v = qa.t, kva.t[:, :d], kva.t[:, d:]
             holders = (qa, kva)
-        O, LSE = ops.attn_masked_fwd(self.prec, q, k, v, B, H, L, False, key_ids, MASK_FILL, pa, self._seed, site_attn, tp.b_offset)
+        # past the length the resident kernels hold (224 rows at head size 16 / 32 / 64) the streamed ones take the same arguments
+        streamed = L > ops.attn_masked_max_len(d // H)
+        attn_fwd, attn_bwd = (ops.attn_long_fwd, ops.attn_long_bwd) if streamed else (ops.attn_masked_fwd, ops.attn_masked_bwd)
+        O, LSE = attn_fwd(self.prec, q, k, v, B, H, L, False, key_ids, MASK_FILL, pa, self._seed, site_attn, tp.b_offset)
         o = Act(O)
 
         def bw():
             if o.g is None:
                 return
-            ops.attn_masked_bwd(self.prec, q, k, v, O, LSE, o.g, B, H, L, False, key_ids, MASK_FILL, pa, self._seed, site_attn, tp.b_offset,
-                                out=self._dqkv(holders, d))
+            attn_bwd(self.prec, q, k, v, O, LSE, o.g, B, H, L, False, key_ids, MASK_FILL, pa, self._seed, site_attn, tp.b_offset,
+                     out=self._dqkv(holders, d))
         tp.bw.append(bw)
         ow = p + ".out_transfer.weight"
         z = tp.dense(o, P(ow), P(p + ".out_transfer.bias"), G(ow), G(p + ".out_transfer.bias"), p=self.attention_dropout, site=site_drop, R=xq)
@@ -329,7 +339,7 @@ class BertModel(FullRankMixin, FlatModule):
         Mdev = st["M"]
         E, gE = self.P("item_emb.word_emb.weight"), self.G("item_emb.word_emb.weight")
         h.g = torch.zeros_like(h.t)
-        if self.use_lce and ops.lce_supported(self.prec, d):
+        if self.use_lce and ops.lce_supported(self.prec, d) and (d != 64 or self.fused_head):
             # fused: online log-sum-exp forward, tile-recomputing backward; no (rows, V) logits in memory (adt_amd/csrc/adt_lce.cuh)
             ops.lce_fwd_bwd(h.t, st["rows"], st["labels"], mcap, Mdev, E, self.P("mask_bias"), st["inv_count"], loss_slots[0], h.g, gE,
                             self.G("mask_bias"))

@@ -18,7 +18,11 @@
 // conflict-free for the ds_read_b128 row reads and for the transposed reads (one image serves both).  Tiles are fetched by LDS-DMA
 // (global_load_lds_dwordx4: the swizzle goes on the per-lane SOURCE address, the LDS side is linear) into a three-slot ring, two
 // tiles ahead, with a counted s_waitcnt vmcnt and one raw s_barrier per tile.  The LDS-DMA is issued from inline asm: hipcc would
-// otherwise wait vmcnt(0) in front of every ds_read that follows a pending global_load_lds.
+// otherwise wait vmcnt(0) in front of every ds_read that follows a pending global_load_lds.  A tile is KD / 32 pieces of 1 KiB, one
+// LDS-DMA instruction each: at KD 256 / 128 every wave fetches two / one; at KD 64 the tile is four pieces for eight waves, so waves
+// 0 - 3 fetch one each and waves 4 - 7 none (the branch is on the wave index, a scalar).  Every wave fetches its own copy of the row
+// constants, and every wave waits on the count IT issued per tile (vmcnt(2) where it fetched a piece, vmcnt(1) where it did not): the
+// barrier that follows then covers the pieces of the other waves.
 //
 // Work split: an item = (X block of the workgroup, one of C ranges of Y tiles); C is derived on the device from the live row count
 // so that the items fill the grid once.  FWD writes (max, sum) partials, DH / DE write their fp32 partial products in register order
@@ -41,7 +45,7 @@ constexpr int LCE_XR_BWD = LCE_NW * 32;
 constexpr float LCE_L2E = 1.4426950408889634f;
 
 template <int KD> struct LceGeo {
-  static_assert(KD == 128 || KD == 256, "contraction width 128 or 256");
+  static_assert(KD == 64 || KD == 128 || KD == 256, "contraction width 64, 128 or 256");
   static constexpr int NCH = KD / 8;                 // 16-byte chunks per row
   static constexpr int NKS = KD / 16;                // k-steps of the score product
   static constexpr int NFT = KD / 32;                // 32-feature tiles of the gradient product
@@ -50,9 +54,10 @@ template <int KD> struct LceGeo {
   static constexpr int YV = LCE_NW * 256;            // one copy per wave of the tile's 32 row constants (filled by that wave's own LDS-DMA)
   static constexpr int BUF = IMG + YV;
   static constexpr int PIECES = IMG / 1024;          // 1 KiB LDS-DMA pieces per tile
-  static constexpr int PPW = PIECES / LCE_NW;        // per wave
+  static constexpr int FW = PIECES < LCE_NW ? PIECES : LCE_NW;   // waves that fetch image pieces: waves 0 .. FW - 1 (KD 64: a 4 KiB tile, four)
+  static constexpr int PPW = PIECES / FW;            // per fetching wave
   static constexpr int LDS = LCE_NBUF * BUF;
-  static constexpr int VM = PPW + 1;                 // vector-memory operations a wave issues per tile
+  static constexpr int VM = PPW + 1;                 // vector-memory operations a fetching wave issues per tile; the others issue VM - PPW
 };
 
 struct LceArgs {
@@ -101,6 +106,7 @@ ADT_DEVICE_INLINE void lce_glds4(const void* gsrc, uint32_t lds_dst) {
 }
 template <int N> ADT_DEVICE_INLINE void lce_wait_vm() {
   if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
   else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
   else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
   else static_assert(N < 0, "add the count");
@@ -160,8 +166,10 @@ __global__ __launch_bounds__(LCE_NTH) void k_lce(LceArgs a) {
       const uint32_t base = lds0 + slot * G::BUF;
       lce_glds4(a.yv + (size_t)tt * 32 + r, base + G::IMG + w * 256);
       const __bf16* src = a.Yb + (size_t)tt * 32 * KD;
+      if (G::FW == LCE_NW || w < G::FW) {                 // wave-uniform: at KD 64 the tile has fewer pieces than the workgroup has waves
 #pragma unroll
-      for (int i = 0; i < G::PPW; ++i) lce_glds16(src + srcoff[i], base + (w * G::PPW + i) * 1024);
+        for (int i = 0; i < G::PPW; ++i) lce_glds16(src + srcoff[i], base + (w * G::PPW + i) * 1024);
+      }
     };
     issue(t0, 0);
     issue(t0 + 1, 1);
@@ -197,7 +205,9 @@ __global__ __launch_bounds__(LCE_NTH) void k_lce(LceArgs a) {
 
     int slot = 0;
     for (int t = t0; t < t1; ++t) {
-      lce_wait_vm<G::VM>();                               // tile t has landed (tile t + 1 may still be in flight)
+      // tile t has landed (tile t + 1 may still be in flight): each wave counts what IT issued per tile
+      if (G::FW == LCE_NW || w < G::FW) lce_wait_vm<G::VM>();
+      else lce_wait_vm<G::VM - G::PPW>();
       __builtin_amdgcn_s_barrier();                       // ... for every wave; and every wave is done with tile t - 1
       issue(t + 2, slot >= 1 ? slot - 1 : LCE_NBUF - 1);
       const unsigned char* buf = lce_smem + slot * G::BUF;

@@ -105,7 +105,7 @@ int adt_lce_slots(int slots) {
   return lce_slots();
 }
 
-int adt_lce_supported(int prec, int K) { return prec == PREC_BF16 && (K == 128 || K == 256); }
+int adt_lce_supported(int prec, int K) { return prec == PREC_BF16 && (K == 64 || K == 128 || K == 256); }
 
 int64_t adt_lce_workspace_bytes(int mcap, int V, int K) { return (int64_t)lce_layout(mcap, V, K, lce_slots()).total; }
 
@@ -113,7 +113,7 @@ int adt_lce_fwd_bwd(const float* h, int ldh, const int32_t* rows, const int32_t*
                     const float* bias, int V, int K, const float* inv_count, float* loss64, float* lse_out, float* dh, int lddh, float* dE, int lddE,
                     float* dbias, void* workspace, int64_t workspace_bytes, void* stream) {
   if (mcap <= 0) return 0;
-  if (!(K == 128 || K == 256)) return adt_set_error("lce: K=%d (128 or 256)", K);
+  if (!(K == 64 || K == 128 || K == 256)) return adt_set_error("lce: K=%d (64, 128 or 256)", K);
   if ((ldh % 4) || (lde % 4) || (dh && (lddh % 4)) || (lddE % 4)) return adt_set_error("lce: leading dimensions %% 4");
   if (((uintptr_t)h | (uintptr_t)E | (uintptr_t)dh | (uintptr_t)dE | (uintptr_t)workspace) & 15u) return adt_set_error("lce: 16-byte alignment");
   if (!dE || !dbias || !bias || !inv_count || !loss64) return adt_set_error("lce: NULL argument");
@@ -121,7 +121,8 @@ int adt_lce_fwd_bwd(const float* h, int ldh, const int32_t* rows, const int32_t*
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   hipStream_t s = (hipStream_t)stream;
   return K == 256 ? lce_run<256>(h, ldh, rows, labels, mcap, m_dev, E, lde, bias, V, inv_count, loss64, lse_out, dh, lddh, dE, lddE, dbias, ws, s)
-                  : lce_run<128>(h, ldh, rows, labels, mcap, m_dev, E, lde, bias, V, inv_count, loss64, lse_out, dh, lddh, dE, lddE, dbias, ws, s);
+         : K == 128 ? lce_run<128>(h, ldh, rows, labels, mcap, m_dev, E, lde, bias, V, inv_count, loss64, lse_out, dh, lddh, dE, lddE, dbias, ws, s)
+                    : lce_run<64>(h, ldh, rows, labels, mcap, m_dev, E, lde, bias, V, inv_count, loss64, lse_out, dh, lddh, dE, lddE, dbias, ws, s);
 }
 
 }  // extern "C"

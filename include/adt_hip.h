@@ -148,7 +148,7 @@ int adt_score_rank(const float* F, int ldf, const float* E, const int32_t* cand,
 int adt_dense_gradsrc(const float* dY, int lddy, int T, int N, const int32_t* mask_ids, float p, const uint32_t* seed,
                       uint32_t site, uint32_t row_offset, int act, const float* U, int ldu, float* G, int ldg,
                       const int32_t* t_dev, void* stream);
-/* ---- fused all-item logits + cross-entropy on the masked rows (bf16 operands; K = 128 or 256) ---------------------------------
+/* ---- fused all-item logits + cross-entropy on the masked rows (bf16 operands; K = 64, 128 or 256) -----------------------------
  * Replaces, for BERT4Rec-ADT's output layer, `logits = h @ word_emb^T + bias` over all V (+100) items (bert4rec/model/bert.py:80-90)
  * followed by CrossEntropyLoss(ignore_index=0) (bert4rec/trainer.py:45,113-115) and their backward, without ever writing the
  * (rows x V) logits: an online log-sum-exp forward and a backward that recomputes each score tile on the matrix cores
@@ -158,7 +158,8 @@ int adt_dense_gradsrc(const float* dY, int lddy, int T, int N, const int32_t* ma
  *   dh[rows[m]] = sum_v (softmax_m[v] - [v == label_m]) / n * E[v]            (plain store; dh NULL = loss only)
  *   dE[v] += sum_m (softmax_m[v] - [v == label_m]) / n * h[rows[m]];  dbias[v] += sum_m (...)      (accumulated)
  * m_dev (optional) is a DEVICE count, so a captured graph replays with a different number of masked rows.  workspace: at least
- * adt_lce_workspace_bytes(mcap, V, K) bytes, 256-byte aligned, contents irrelevant on entry. */
+ * adt_lce_workspace_bytes(mcap, V, K) bytes, 256-byte aligned, contents irrelevant on entry.  adt_lce_supported(prec, K) is 1 for bf16
+ * at K 64 / 128 / 256, else 0; at K 64 BertModel calls the fused path only on request (args.fused_head). */
 int adt_lce_supported(int prec, int K);
 /* Workgroups the passes are split over (default: the device's CU count); slots > 0 sets it (tests use a small grid so that every
  * workgroup walks several work items), returns the value in force.  The workspace size depends on it. */

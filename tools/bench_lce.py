@@ -2,7 +2,10 @@
 """GPU: time the fused all-item logits + cross-entropy path (adt_lce_fwd_bwd) at the BASELINE config-3 shape of BERT4Rec-ADT's output
 layer (V + 100 = 26,844 items, d = 256, ~5.9k masked rows of a 256 x 200 batch) against the unfused sequence it replaces
 (gather_rows -> dense_fwd -> ce_rows -> dense_bwd -> scatter_rows).  Prints one JSON line; run under rocprofv3 --kernel-trace --stats
-for the per-kernel split.  Usage: python tools/bench_lce.py [--rows 5921] [--iters 20] [--no-unfused]"""
+for the per-kernel split.  K is 64, 128 or 256 (the Beauty template: --K 64 --V 12204 --T 131072 --rows 78643).  With --rounds N the two
+paths alternate N times within the process and the median and the spread (min .. max) of the per-round means are printed; peak_MB is
+torch.cuda.max_memory_allocated over a path's rounds beyond what was allocated before it ran.
+Usage: python tools/bench_lce.py [--rows 5921] [--K 256] [--iters 20] [--rounds 1] [--no-unfused]"""
 import argparse
 import json
 import os
@@ -22,6 +25,7 @@ def main():
     ap.add_argument("--V", type=int, default=26844)
     ap.add_argument("--K", type=int, default=256)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=1)
     ap.add_argument("--no-unfused", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -67,12 +71,26 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / a.iters * 1e3
 
-    out = {"rows": M, "V": V, "K": K, "fused_us": round(timeit(fused), 1)}
+    paths = [("fused", fused)] + ([] if a.no_unfused else [("unfused", unfused)])
+    times, peak = {n: [] for n, _ in paths}, {n: 0 for n, _ in paths}
+    for _ in range(a.rounds):
+        for n, fn in paths:
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            times[n].append(timeit(fn))
+            peak[n] = max(peak[n], torch.cuda.max_memory_allocated() - base)
+    out = {"rows": M, "V": V, "K": K, "fused_us": round(float(np.median(times["fused"])), 1)}
     flops = 2.0 * M * V * K
     out["gemm_flops_one_pass"] = flops
     out["fused_equiv_TFLOPs_5_passes"] = round(5 * flops / out["fused_us"] / 1e6, 1)
     if not a.no_unfused:
-        out["unfused_us"] = round(timeit(unfused), 1)
+        out["unfused_us"] = round(float(np.median(times["unfused"])), 1)
+    if a.rounds > 1:
+        out["rounds"] = a.rounds
+        for n in times:
+            out[n + "_us_min_max"] = [round(min(times[n]), 1), round(max(times[n]), 1)]
+    for n in peak:
+        out[n + "_peak_MB"] = round(peak[n] / 2 ** 20, 1)
     print(json.dumps(out))
 
 

@@ -2,7 +2,7 @@
 """Step-time measurement of the BERT4Rec-ADT and STOSA-ADT training steps (BASELINE.json configs[2] and configs[4] shapes,
 one GPU, synthetic ids, HIP graph).  Not the driver's bench (bench.py measures configs[1]); results go to profiles/.
 
-    python tools/bench_wide.py bert  [--steps 20] [--batch 256]
+    python tools/bench_wide.py bert  [--steps 20] [--batch 256] [--maxlen 200] [--bert_template ml-20m|beauty] [--fused_head]
     python tools/bench_wide.py stosa [--steps 20] [--metric wasserstein|kl] [--stosa_maxlen 100] [--stosa_heads 4]
 """
 import argparse
@@ -42,14 +42,17 @@ def run_bert(args):
     from adt_amd.bert4rec.model import BertModel
     from adt_amd.bert4rec.trainer import FusedBertTrainer
     a = Args()
-    a.device, a.maxlen, a.num_heads, a.num_layers, a.hidden_units, a.inner_units = "cuda:0", 200, 4, 2, 256, 1024
-    a.dropout, a.attention_dropout, a.type_vocab_size, a.precision = 0.5, 0.5, 2, "bf16"
-    V = args.items
+    L = args.maxlen
+    beauty = args.bert_template == "beauty"       # templates/beauty.json: d 64, H 2, mask_prob 0.6, 12,101 items; else the ml-1m / ml-20m width
+    d, H, pa, mask_prob, mcap = (64, 2, 0.2, 0.6, 1.0) if beauty else (256, 4, 0.5, 0.2, args.mcap)
+    a.device, a.maxlen, a.num_heads, a.num_layers, a.hidden_units, a.inner_units = "cuda:0", L, H, 2, d, 1024
+    a.dropout, a.attention_dropout, a.type_vocab_size, a.precision, a.fused_head = 0.5, pa, 2, "bf16", args.fused_head
+    V = 12101 if beauty and args.items == 26744 else args.items
     torch.manual_seed(23)
     m = BertModel(1, V, a)
-    tr = FusedBertTrainer(m, [0.1, 0.05], [0.1, 0.05], weight_decay=1e-4, use_graph=not args.no_graph, seed=23, mcap_frac=args.mcap)
+    tr = FusedBertTrainer(m, [0.1, 0.05], [0.1, 0.05], weight_decay=1e-4, use_graph=not args.no_graph, seed=23, mcap_frac=mcap)
     r = np.random.RandomState(1)
-    staged = [tr.stage(*bert_batch(r, args.batch, 200, V, 0.2)) for _ in range(4)]
+    staged = [tr.stage(*bert_batch(r, args.batch, L, V, mask_prob)) for _ in range(4)]
     for i in range(args.warmup):
         tr.step_staged(staged[i % 4])
     torch.cuda.synchronize()
@@ -59,10 +62,13 @@ def run_bert(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     M = float(np.mean([s["M_host"] for s in staged]))
-    flops_logits = 3 * 2 * M * 256 * (V + 100)
-    print(json.dumps({"workload": "BERT4Rec-ADT ml-20m shape: d=256 H=4 inner=1024 L=200 2+2 layers V+100=%d, batch %d, dropout 0.5, full train step" % (V + 100, args.batch),
+    flops_logits = 3 * 2 * M * d * (V + 100)
+    what = "Beauty template" if beauty else "ml-20m shape"
+    print(json.dumps({"workload": "BERT4Rec-ADT %s: d=%d H=%d inner=1024 L=%d 2+2 layers V+100=%d, batch %d, dropout 0.5, full train step%s"
+                                  % (what, d, H, L, V + 100, args.batch, ", fused head" if m.fused_head else ""),
                       "ms_per_step": round(dt / args.steps * 1e3, 3), "sequences_per_s": round(args.batch * args.steps / dt, 1), "masked_rows": M,
-                      "logits_gemm_tflops_per_step": round(flops_logits / 1e12, 3), "loss": round(float(tr.loss()), 4), "dtype": "bf16"}))
+                      "logits_gemm_tflops_per_step": round(flops_logits / 1e12, 3), "loss": round(float(tr.loss()), 4), "dtype": "bf16",
+                      "max_memory_allocated_MB": round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)}))
 
 
 def run_stosa(args):
@@ -154,7 +160,9 @@ if __name__ == "__main__":
     ap.add_argument("--stosa_heads", type=int, default=4, help="stosa: heads of the 64-wide model (4: Beauty / Tools, 1: Home / Office / Toys)")
     ap.add_argument("--hidden_units", type=int, default=256, help="sasrec256: width (default: the template's)")
     ap.add_argument("--num_heads", type=int, default=2)
-    ap.add_argument("--maxlen", type=int, default=200)
+    ap.add_argument("--maxlen", type=int, default=200, help="bert, sasrec256: maxlen (up to 1024)")
+    ap.add_argument("--bert_template", default="ml-20m", choices=["ml-20m", "beauty"], help="bert: the d 256 / H 4 shape or templates/beauty.json's")
+    ap.add_argument("--fused_head", action="store_true", help="bert at d 64: the fused logits + cross-entropy head (adt_lce_fwd_bwd)")
     ap.add_argument("--num_layers", type=int, default=2)
     args = ap.parse_args()
     {"bert": run_bert, "stosa": run_stosa, "sasrec256": run_sasrec256}[args.which](args)
