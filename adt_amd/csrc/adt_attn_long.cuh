@@ -1,36 +1,43 @@
-// General masked attention for sequences of 1 <= L <= 1024 rows at head sizes 16 .. 256, either precision: the scheme of
-// adt_attn_stream.cuh (grid (B*H, groups of NW 16-row tiles), one tile per wave; the forward streams key chunks past the query tiles with
-// an online softmax; the backward streams key chunks past the dQ tiles, then query chunks past the dK / dV tiles, P recomputed from the
-// forward's LSE) with the per-sequence state sized for 1024 rows.  Same semantics, fill rule, dropout indices and fragment interface as
-// adt_attn_gen.cuh; a separate header and translation unit so that the kernels of the shorter lengths are not touched.
+// General masked attention with key / query chunks streamed through LDS, for the shapes whose whole-(b, h) images do not fit it: sequences of
+// 1 <= L <= LMAX rows at head sizes 16 .. 256, either precision.  LMAX, the rows of per-sequence state, is 256 (adt_attn_masked_*: head size
+// 256, and head size 128 in the exact-fp32 mode at L > 64) or 1024 (adt_attn_long_*, every head size).  Same semantics, fill rule, dropout
+// indices and fragment interface as adt_attn_gen.cuh.
 //
-// What 1024 rows change: two int[1024] mask arrays no longer fit beside the fp32 hd = 256 backward images (149,504 B of 163,840), so
+// One 264-element padded row per key is 135 KB (bf16) / 270 KB (fp32) at hd = 256, L = 256, before V^T: no (b, h) fits in LDS.  So:
+//  * the grid is (B*H, query / key groups of NW 16-row tiles), one tile per wave;
+//  * the forward streams key chunks (K row image + V^T image) through LDS with an online softmax: each wave keeps its
+//    16 x HD fp32 output tile (64 registers at hd 256) and running row max / sum across chunks, rescaling the tile when the max moves;
+//  * the backward streams key chunks (K, V, K^T) past the dQ tiles of the group (pass A), then query chunks (Q, dO, Q^T,
+//    dO^T) past the dK / dV tiles (pass B), P recomputed from the forward's LSE as in k_attn_gen_bwd_chunked.
+// Under a causal mask without key padding and fill <= -1e9 (csk) chunks and tile pairs entirely above the diagonal are skipped.
+//
+// Two int[1024] mask arrays do not fit beside the fp32 hd = 256 backward images (149,504 B of 163,840), so at either LMAX
 //  * key validity is one byte per key;
-//  * the per-query "no attendable key" flags become one number per sequence, the index f of its first attendable key (L: none):
+//  * the per-query "no attendable key" flags are one number per sequence, the index f of its first attendable key (L: none):
 //    query q is dead exactly when f >= (causal ? min(q + 1, L) : L), and the mask set-up is O(L);
 //  * heads narrower than one 32-wide MFMA block read zero fragments past HD (rfrag_g, gfrag), as the resident kernels do.
 #pragma once
 #include "adt_attn_gen.cuh"
-#include "adt_wide_plan.h"      // ATTN_LONG_LMAX
 
 namespace adt {
 
-template <int PREC, int HD, int KC>
+template <int PREC, int HD, int KC, int LMAX>
 struct AttnLongLds {
   typedef typename Img<PREC>::E E;
-  static constexpr int RS = HD + 8, KCT = KC + 8, LPMAX = ATTN_LONG_LMAX;
-  static constexpr size_t mask_bytes = LPMAX + 32;      // key validity bytes + one first-attendable-key candidate per wave (<= 8 waves)
+  static_assert(LMAX == 256 || LMAX == 1024, "rows of per-sequence state");
+  static constexpr int RS = HD + 8, KCT = KC + 8;
+  static constexpr size_t mask_bytes = LMAX + 32;      // key validity bytes + one first-attendable-key candidate per wave (<= 8 waves)
   static constexpr size_t fwd_bytes = (size_t)(KC * RS + HD * KCT) * sizeof(E) + mask_bytes;
-  static constexpr size_t bwd_bytes = (size_t)(2 * KC * RS + 2 * HD * KCT) * sizeof(E) + 2 * LPMAX * sizeof(float) + mask_bytes;
+  static constexpr size_t bwd_bytes = (size_t)(2 * KC * RS + 2 * HD * KCT) * sizeof(E) + 2 * LMAX * sizeof(float) + mask_bytes;
 };
 
 // Key validity of the sequence as bytes; returns the index of its first attendable key (L when there is none).  Each thread walks its keys in
 // increasing order, the waves fold their minima with shuffles and exchange them through sF: no atomics.  Ends with the workgroup in step.
-template <int NTH>
+template <int NTH, int LMAX>
 ADT_DEVICE_INLINE int attn_long_masks(unsigned char* sKv, int* sF, const int* kid, size_t row_b, int L) {
   static_assert(NTH % 64 == 0 && NTH / 64 <= 8, "one sF slot per wave");
   int first = L;
-  for (int i = threadIdx.x; i < ATTN_LONG_LMAX; i += NTH) {
+  for (int i = threadIdx.x; i < LMAX; i += NTH) {
     const bool ok = i < L && (!kid || kid[row_b + i] > 0);
     sKv[i] = ok ? 1 : 0;
     if (ok && i < first) first = i;
@@ -50,7 +57,7 @@ ADT_DEVICE_INLINE int attn_long_masks(unsigned char* sKv, int* sF, const int* ki
 // the dead-row rule of mark_dead_rows from the first attendable key
 ADT_DEVICE_INLINE bool attn_long_dead(int first, int q, int L, int causal) { return first >= (causal && q + 1 < L ? q + 1 : L); }
 
-template <int PREC, int HD, int NW, int KC>
+template <int PREC, int HD, int NW, int KC, int LMAX>
 __global__ __launch_bounds__(NW * 64) void k_attn_long_fwd(AttnGenArgs ga) {
   typedef Img<PREC> I;
   typedef typename I::E E;
@@ -58,18 +65,18 @@ __global__ __launch_bounds__(NW * 64) void k_attn_long_fwd(AttnGenArgs ga) {
   const AttnArgs& a = ga.a;
   constexpr int KCT = KC + 8, NT = HD / 16, KB = (HD + 31) / 32, KT = KC / 16;
   static_assert(HD == 16 || HD == 32 || HD == 64 || HD == 128 || HD == 256, "head sizes");
-  static_assert(KC % 32 == 0 && ATTN_LONG_LMAX % KC == 0, "chunks hold whole tile pairs");
+  static_assert(KC % 32 == 0 && LMAX % KC == 0, "chunks hold whole tile pairs");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   E* sK = reinterpret_cast<E*>(smem_raw);    // [KC][RS]   keys k0 .. k0 + KC - 1
   E* sVT = sK + KC * (HD + 8);                // [HD][KCT]
   unsigned char* sKv = reinterpret_cast<unsigned char*>(sVT + HD * KCT);
-  int* sF = reinterpret_cast<int*>(sKv + ATTN_LONG_LMAX);
+  int* sF = reinterpret_cast<int*>(sKv + LMAX);
   const int bh = blockIdx.x, b = bh / a.H, h = bh % a.H;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int L = a.L;
   const size_t row_b = (size_t)b * L;
   const bool csk = a.causal && ga.kid == nullptr && ga.fill <= -1e9f;
-  const int first = attn_long_masks<NW * 64>(sKv, sF, ga.kid, row_b, L);
+  const int first = attn_long_masks<NW * 64, LMAX>(sKv, sF, ga.kid, row_b, L);
   const int nqt = (L + 15) / 16;
   const int qt = blockIdx.y * NW + w;
   const bool active = qt < nqt;
@@ -112,7 +119,7 @@ __global__ __launch_bounds__(NW * 64) void k_attn_long_fwd(AttnGenArgs ga) {
         for (int kb = 0; kb < KB; ++kb) s = I::mma(s, rfrag_g<PREC, HD>(sK, kt * 16 + c, kb, g), fq[kb]);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int key = k0 + kt * 16 + 4 * g + r;   // < ATTN_LONG_LMAX: k0 < L and chunks divide it
+          const int key = k0 + kt * 16 + 4 * g + r;   // < LMAX: k0 < L and chunks divide it
           const bool masked = (a.causal && key > q) || !sKv[key];
           const float v = masked ? fill_q : s[r];
           sc[kt][r] = key < L ? v : -INFINITY;
@@ -172,7 +179,7 @@ __global__ __launch_bounds__(NW * 64) void k_attn_long_fwd(AttnGenArgs ga) {
     }
 }
 
-template <int PREC, int HD, int NW, int KC>
+template <int PREC, int HD, int NW, int KC, int LMAX>
 __global__ __launch_bounds__(NW * 64) void k_attn_long_bwd(AttnGenArgs ga) {
   typedef Img<PREC> I;
   typedef typename I::E E;
@@ -180,16 +187,16 @@ __global__ __launch_bounds__(NW * 64) void k_attn_long_bwd(AttnGenArgs ga) {
   const AttnArgs& a = ga.a;
   constexpr int RS = HD + 8, KCT = KC + 8, NT = HD / 16, KB = (HD + 31) / 32, V8 = HD / 8, TPC = KC / 16;
   static_assert(HD == 16 || HD == 32 || HD == 64 || HD == 128 || HD == 256, "head sizes");
-  static_assert(KC % 32 == 0 && ATTN_LONG_LMAX % KC == 0, "chunks hold whole tile pairs");
+  static_assert(KC % 32 == 0 && LMAX % KC == 0, "chunks hold whole tile pairs");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   E* sR0 = reinterpret_cast<E*>(smem_raw);   // pass A: K chunk   | pass B: Q chunk (scaled)
   E* sR1 = sR0 + KC * RS;                     // pass A: V chunk   | pass B: dO chunk
   E* sT0 = sR1 + KC * RS;                     // pass A: K^T chunk | pass B: Q^T chunk (scaled)
   E* sT1 = sT0 + HD * KCT;                    //                   | pass B: dO^T chunk
   float* sLse = reinterpret_cast<float*>(sT1 + HD * KCT);   // +inf for padded queries -> P = 0
-  float* sDelta = sLse + ATTN_LONG_LMAX;                     // rowsum(dO * O)
-  unsigned char* sKv = reinterpret_cast<unsigned char*>(sDelta + ATTN_LONG_LMAX);
-  int* sF = reinterpret_cast<int*>(sKv + ATTN_LONG_LMAX);
+  float* sDelta = sLse + LMAX;                     // rowsum(dO * O)
+  unsigned char* sKv = reinterpret_cast<unsigned char*>(sDelta + LMAX);
+  int* sF = reinterpret_cast<int*>(sKv + LMAX);
   const int bh = blockIdx.x, b = bh / a.H, h = bh % a.H;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int L = a.L;
@@ -221,7 +228,7 @@ __global__ __launch_bounds__(NW * 64) void k_attn_long_bwd(AttnGenArgs ga) {
       sLse[r] = (r >= rlo && r < L) ? a.LSE[(size_t)bh * L + r] : INFINITY;
     }
   }
-  const int first = attn_long_masks<NW * 64>(sKv, sF, ga.kid, row_b, L);
+  const int first = attn_long_masks<NW * 64, LMAX>(sKv, sF, ga.kid, row_b, L);
   const uint32_t key_rng = drop_key(a.drop);
   const uint32_t idx_bh = (uint32_t)(bh + a.bh_offset) * (uint32_t)L;
   const int nqt = (L + 15) / 16;
@@ -269,7 +276,7 @@ __global__ __launch_bounds__(NW * 64) void k_attn_long_bwd(AttnGenArgs ga) {
           const uint32_t kbits = a.drop.thr ? adt_keep4_any(key_rng, idx_q + (uint32_t)(k0 + ktl * 16 + 4 * g), a.drop.thr, (L & 3) == 0) : 0u;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int key = k0 + ktl * 16 + 4 * g + r;   // < rend <= ATTN_LONG_LMAX
+            const int key = k0 + ktl * 16 + 4 * g + r;   // < rend <= LMAX
             const bool masked = (a.causal && key > q) || !sKv[key];
             const float sv = masked ? fill_q : sacc[r];
             const float p = key < L ? __expf(sv - lse_q) : 0.f;

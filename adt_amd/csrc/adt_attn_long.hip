@@ -1,32 +1,20 @@
-// C ABI (include/adt_hip.h): masked attention at 1 <= L <= 1024 (adt_attn_long.cuh), every head size, either precision.  A translation unit of
-// its own: the code objects of the shorter lengths (adt_wide.hip) stay as they are.  Host code only enqueues work on the caller's stream.
-#include "adt_host.h"
-
-#include "adt_attn_long.cuh"
+// C ABI (include/adt_hip.h): masked attention at 1 <= L <= 1024 (the 1024-row instantiations of adt_attn_long.cuh), every head size, either
+// precision.  A translation unit of its own, compiled beside adt_wide.hip.  Host code only enqueues work on the caller's stream.
+#include "adt_attn_long_launch.h"
 
 using namespace adt;
 
 static_assert(PREC_F32 == ADT_PREC_F32 && PREC_BF16 == ADT_PREC_BF16, "adt_wide_plan.h speaks of the ABI's prec values");
-static_assert(attn_long_lds(ADT_PREC_F32, 256, attn_streamed_kc(ADT_PREC_F32, true), true) <= ADT_LDS_MAX, "the tightest instantiation fits the LDS");
-
-// adt_attn_long_plan (adt_wide_plan.h) chooses the grid and the footprint; this names the instantiation
-template <int PREC, int HD>
-static int launch_attn_long(const AttnPlan& p, bool bwd, const AttnGenArgs& a, hipStream_t s) {
-  constexpr int NW = ATTN_STREAMED_NW, KCF = attn_streamed_kc(PREC, false), KCB = attn_streamed_kc(PREC, true);
-  static_assert(attn_long_lds(PREC, HD, KCF, false) == AttnLongLds<PREC, HD, KCF>::fwd_bytes, "plan and kernel disagree on the LDS footprint");
-  static_assert(attn_long_lds(PREC, HD, KCB, true) == AttnLongLds<PREC, HD, KCB>::bwd_bytes, "plan and kernel disagree on the LDS footprint");
-  const void* fn = bwd ? (const void*)k_attn_long_bwd<PREC, HD, NW, KCB> : (const void*)k_attn_long_fwd<PREC, HD, NW, KCF>;
-  static AdtLdsOptIn optin[2];
-  return adt_launch_lds1(fn, dim3(a.a.B * a.a.H, p.grid_y), dim3(p.waves * 64), p.lds_bytes, a, s, bwd ? "attn_long_bwd" : "attn_long_fwd", optin[bwd ? 1 : 0]);
-}
+static_assert(attn_long_lds(ADT_PREC_F32, 256, attn_streamed_kc(ADT_PREC_F32, true), true, ATTN_LONG_LMAX) <= ADT_LDS_MAX, "the tightest instantiation fits the LDS");
 
 template <int PREC>
 static int launch_attn_long_hd(const AttnPlan& p, bool bwd, int hd, const AttnGenArgs& a, hipStream_t s) {
-  if (hd == 16) return launch_attn_long<PREC, 16>(p, bwd, a, s);
-  if (hd == 32) return launch_attn_long<PREC, 32>(p, bwd, a, s);
-  if (hd == 64) return launch_attn_long<PREC, 64>(p, bwd, a, s);
-  if (hd == 128) return launch_attn_long<PREC, 128>(p, bwd, a, s);
-  return launch_attn_long<PREC, 256>(p, bwd, a, s);
+  const char *wf = "attn_long_fwd", *wb = "attn_long_bwd";
+  if (hd == 16) return launch_attn_long<PREC, 16, ATTN_LONG_LMAX>(p, bwd, a, s, wf, wb);
+  if (hd == 32) return launch_attn_long<PREC, 32, ATTN_LONG_LMAX>(p, bwd, a, s, wf, wb);
+  if (hd == 64) return launch_attn_long<PREC, 64, ATTN_LONG_LMAX>(p, bwd, a, s, wf, wb);
+  if (hd == 128) return launch_attn_long<PREC, 128, ATTN_LONG_LMAX>(p, bwd, a, s, wf, wb);
+  return launch_attn_long<PREC, 256, ATTN_LONG_LMAX>(p, bwd, a, s, wf, wb);
 }
 
 // the checks and the argument block both directions share; the plan's refusals (head size, length, LDS) come first

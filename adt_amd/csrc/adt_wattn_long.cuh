@@ -23,7 +23,8 @@
 //    the head of adt_wattn_mfma.cuh): the chunk images go through wm_stage_cat / wm_kl_stage, the owned tiles through wm_cat_frag /
 //    wm_kl_frag and wm_row_norm / wm_kl_logsum, exactly as in the resident kernels.
 #pragma once
-#include "adt_attn_long.cuh"      // attn_long_masks, ATTN_LONG_LMAX
+#include "adt_attn_long.cuh"      // attn_long_masks
+#include "adt_wide_plan.h"       // ATTN_LONG_LMAX
 #include "adt_wattn_mfma.cuh"
 
 namespace adt {
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_fwd(WAttnArgs a) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int L = a.L, co = h * HD;
   const size_t row_b = (size_t)b * L;
-  const int first = attn_long_masks<WM_NW * 64>(sKv, sF, a.kid, row_b, L);
+  const int first = attn_long_masks<WM_NW * 64, ATTN_LONG_LMAX>(sKv, sF, a.kid, row_b, L);
   const int nt16 = (L + 15) / 16;
   const int qt = blockIdx.y * WM_NW + w;
   const bool active = qt < nt16;
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
     sDelta[i] = dl;
     sLse[i] = i < L ? a.LSE[(size_t)bh * L + i] : INFINITY;
   }
-  const int first = attn_long_masks<WM_NW * 64>(sKv, sF, a.kid, row_b, L);      // ends with the workgroup in step
+  const int first = attn_long_masks<WM_NW * 64, ATTN_LONG_LMAX>(sKv, sF, a.kid, row_b, L);      // ends with the workgroup in step
   const int nt16 = (L + 15) / 16;
   const int tile = blockIdx.y * WM_NW + w;     // the wave's query tile (pass A) / key tile (pass B)
   const bool active = tile < nt16;

@@ -4,7 +4,7 @@
 #include "adt_host.h"
 
 #include "adt_attn_gen.cuh"
-#include "adt_attn_stream.cuh"
+#include "adt_attn_long_launch.h"
 #include "adt_gemm.cuh"
 #include "adt_dense_rows.cuh"
 #include "adt_stosa.cuh"
@@ -50,16 +50,10 @@ static int launch_attn_gen_l(const AttnPlan& p, bool bwd, const AttnGenArgs& a, 
   return launch_attn_gen<PREC, HD, 14>(p, bwd, a, s);
 }
 
-// key / query chunks streamed through LDS (adt_attn_stream.cuh), grid (B*H, groups of NW 16-row tiles)
+// key / query chunks streamed through LDS: the 256-row instantiations of adt_attn_long.cuh, grid (B*H, groups of NW 16-row tiles)
 template <int PREC, int HD>
 static int launch_attn_stream(const AttnPlan& p, bool bwd, const AttnGenArgs& a, hipStream_t s) {
-  constexpr int NW = ATTN_STREAMED_NW, KCF = attn_streamed_kc(PREC, false), KCB = attn_streamed_kc(PREC, true);
-  static_assert(attn_streamed_lds(PREC, HD, KCF, false) == AttnStreamLds<PREC, HD, KCF>::fwd_bytes, "plan and kernel disagree on the LDS footprint");
-  static_assert(attn_streamed_lds(PREC, HD, KCB, true) == AttnStreamLds<PREC, HD, KCB>::bwd_bytes, "plan and kernel disagree on the LDS footprint");
-  const void* fn = bwd ? (const void*)k_attn_stream_bwd<PREC, HD, NW, KCB> : (const void*)k_attn_stream_fwd<PREC, HD, NW, KCF>;
-  static AdtLdsOptIn optin[2];
-  return adt_launch_lds1(fn, dim3(a.a.B * a.a.H, p.grid_y), dim3(p.waves * 64), p.lds_bytes, a, s, bwd ? "attn_masked_bwd(streamed)" : "attn_masked_fwd(streamed)",
-                         optin[bwd ? 1 : 0]);
+  return launch_attn_long<PREC, HD, ATTN_STREAMED_LMAX>(p, bwd, a, s, "attn_masked_fwd(streamed)", "attn_masked_bwd(streamed)");
 }
 
 // hd = 128: streamed (exact fp32 only), resident forward with or without the causal tile skip, chunked backward

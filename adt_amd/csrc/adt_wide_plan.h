@@ -250,8 +250,8 @@ static inline int64_t adt_dense_bwd_ws_need(int prec, int T, int K, int N) {
   return adt_dense_bwd_plan(f).ws_used;
 }
 
-// ---- masked attention (adt_attn_gen.cuh, adt_attn_stream.cuh) ------------------------------------------------------------------------
-// LDS footprints; esz: 2 (bf16 images) or 4 (exact fp32).  adt_wide.hip asserts them against AttnGenLds / AttnChunkLds / AttnStreamLds.
+// ---- masked attention (adt_attn_gen.cuh, adt_attn_long.cuh) --------------------------------------------------------------------------
+// LDS footprints; esz: 2 (bf16 images) or 4 (exact fp32).  The launchers assert them against AttnGenLds / AttnChunkLds / AttnLongLds.
 constexpr size_t attn_esz(int prec) { return prec == ADT_PREC_F32 ? 4 : 2; }
 constexpr size_t attn_resident_lds(int prec, int hd, int maxkt, bool bwd) {
   const size_t lp = (size_t)maxkt * 16, img = lp * (hd + 8) + hd * (lp + 8);
@@ -261,9 +261,11 @@ constexpr size_t attn_chunked_lds(int prec, int hd, int maxkt, int nch) {
   const size_t lp = (size_t)maxkt * 16, lpc = lp / nch;
   return 2 * (lpc * (hd + 8) + hd * (lpc + 8)) * attn_esz(prec) + 2 * lp * sizeof(float) + 2 * lp * sizeof(int);
 }
-constexpr size_t attn_streamed_lds(int prec, int hd, int kc, bool bwd) {
-  const size_t img = (size_t)kc * (hd + 8) + (size_t)hd * (kc + 8);
-  return bwd ? 2 * img * attn_esz(prec) + 2 * 256 * sizeof(float) + 2 * 256 * sizeof(int) : img * attn_esz(prec) + 2 * 256 * sizeof(int);
+// streamed (adt_attn_long.cuh), lmax rows of per-sequence state: beside the chunk images, LSE and delta of lmax rows (backward), key validity
+// as lmax bytes and 32 bytes of per-wave scratch for the first attendable key
+constexpr size_t attn_long_lds(int prec, int hd, int kc, bool bwd, int lmax) {
+  const size_t img = (size_t)kc * (hd + 8) + (size_t)hd * (kc + 8), masks = (size_t)lmax + 32;
+  return bwd ? 2 * img * attn_esz(prec) + 2 * lmax * sizeof(float) + masks : img * attn_esz(prec) + masks;
 }
 
 // bf16 operands: the forward (<= 106 VGPRs at every head size) and the backward at head size <= 64 (<= 124) fit the 128-register budget of
@@ -271,6 +273,7 @@ constexpr size_t attn_streamed_lds(int prec, int hd, int kc, bool bwd) {
 constexpr int attn_resident_waves(int prec, int hd, bool bwd) { return prec != ADT_PREC_F32 && (!bwd || hd <= 64) ? 16 : 8; }
 constexpr int ATTN_CHUNKED_NW = 8, ATTN_STREAMED_NW = 4;
 constexpr int attn_streamed_kc(int prec, bool bwd) { return prec != ADT_PREC_F32 && !bwd ? 64 : 32; }      // key / query rows per streamed chunk
+constexpr int ATTN_STREAMED_LMAX = 256, ATTN_LONG_LMAX = 1024;      // rows of per-sequence state: adt_attn_masked_* | adt_attn_long_*, adt_wattn_long_*
 
 // RESIDENT: the whole (b, h) in LDS (k_attn_gen_fwd / k_attn_gen_bwd).  CHUNKED: backward staged in NCH chunks of the sequence
 // (k_attn_gen_bwd_chunked).  STREAMED: key / query chunks of KC rows streamed through LDS, grid (B*H, groups of `waves` 16-row tiles).
@@ -283,6 +286,13 @@ struct AttnPlan {
   size_t lds_bytes;
   char error[128];          // "" or the message for adt_last_error
 };
+
+// STREAMED at either lmax: waves, chunk, grid and footprint
+static inline void attn_streamed_plan(AttnPlan& p, int P, int hd, int L, bool bwd, int lmax) {
+  p.waves = ATTN_STREAMED_NW; p.kc = attn_streamed_kc(P, bwd);
+  p.grid_y = plan_ceil(plan_ceil(L, 16), p.waves);
+  p.lds_bytes = attn_long_lds(P, hd, p.kc, bwd, lmax);
+}
 
 static inline AttnPlan adt_attn_masked_plan(int prec, int hd, int L, bool bwd, bool causal, bool has_key_ids, float fill) {
   AttnPlan p{};
@@ -319,9 +329,7 @@ static inline AttnPlan adt_attn_masked_plan(int prec, int hd, int L, bool bwd, b
     p.lds_bytes = attn_chunked_lds(P, hd, p.maxkt, p.nch);
     if (p.lds_bytes > ADT_LDS_MAX) snprintf(p.error, sizeof p.error, "masked attention bwd: L=%d hd=%d prec=%d needs %zu B of LDS (> 160 KB)", L, hd, P, p.lds_bytes);
   } else {
-    p.waves = ATTN_STREAMED_NW; p.kc = attn_streamed_kc(P, bwd);
-    p.grid_y = plan_ceil(plan_ceil(L, 16), p.waves);
-    p.lds_bytes = attn_streamed_lds(P, hd, p.kc, bwd);
+    attn_streamed_plan(p, P, hd, L, bwd, ATTN_STREAMED_LMAX);
     if (p.lds_bytes > ADT_LDS_MAX) snprintf(p.error, sizeof p.error, "masked attention: hd=%d prec=%d needs %zu B of LDS (> 160 KB)", hd, P, p.lds_bytes);
   }
   return p;
@@ -333,13 +341,7 @@ static inline AttnPlan adt_attn_masked_plan(int prec, int hd, int L, bool bwd, b
 constexpr int adt_attn_masked_max_len(int hd) { return hd == 16 || hd == 32 || hd == 64 ? 224 : (hd == 128 || hd == 256 ? 256 : 0); }
 
 // ---- masked attention at 1 <= L <= 1024 (adt_attn_long.cuh) --------------------------------------------------------------------------
-// Always streamed, every head size.  Beside the images: LSE and delta of 1024 rows (backward), key validity as 1024 bytes and 32 bytes of
-// per-wave scratch for the first attendable key.  adt_attn_long.hip asserts the footprint against AttnLongLds.
-constexpr int ATTN_LONG_LMAX = 1024;
-constexpr size_t attn_long_lds(int prec, int hd, int kc, bool bwd) {
-  const size_t img = (size_t)kc * (hd + 8) + (size_t)hd * (kc + 8), masks = ATTN_LONG_LMAX + 32;
-  return bwd ? 2 * img * attn_esz(prec) + 2 * ATTN_LONG_LMAX * sizeof(float) + masks : img * attn_esz(prec) + masks;
-}
+// Always streamed, every head size, 1024 rows of per-sequence state.
 
 static inline AttnPlan adt_attn_long_plan(int prec, int hd, int L, bool bwd, bool causal, bool has_key_ids, float fill) {
   AttnPlan p{};
@@ -350,10 +352,8 @@ static inline AttnPlan adt_attn_long_plan(int prec, int hd, int L, bool bwd, boo
     return p;
   }
   if (L < 1 || L > ATTN_LONG_LMAX) { snprintf(p.error, sizeof p.error, "long attention: L=%d outside 1..%d", L, ATTN_LONG_LMAX); return p; }
-  p.waves = ATTN_STREAMED_NW; p.kc = attn_streamed_kc(P, bwd);
-  p.grid_y = plan_ceil(plan_ceil(L, 16), p.waves);
+  attn_streamed_plan(p, P, hd, L, bwd, ATTN_LONG_LMAX);
   p.csk = causal && !has_key_ids && fill <= -1e9f;
-  p.lds_bytes = attn_long_lds(P, hd, p.kc, bwd);
   if (p.lds_bytes > ADT_LDS_MAX) snprintf(p.error, sizeof p.error, "long attention: hd=%d prec=%d needs %zu B of LDS (> 160 KB)", hd, P, p.lds_bytes);
   return p;
 }

@@ -1,4 +1,4 @@
-"""GPU check of the general masked attention at head size 256 (adt_amd/csrc/adt_attn_stream.cuh: key / query chunks streamed through
+"""GPU check of the general masked attention at head size 256 (adt_amd/csrc/adt_attn_long.cuh at 256 rows: key / query chunks streamed through
 LDS, online softmax in the forward; also head size 128 in the exact-fp32 mode at L > 64, which runs there) against the float64 restatement of tests/test_wide_kernels.py::test_masked_attention, with that
 test's tolerances: causal only (fill -inf, the SASRec mask), key padding only and both (fill -1e9, BERT's: a fully padded sequence
 attends uniformly), dropout off and on with a nonzero b_offset, both precisions, L from 1 to 256."""

@@ -165,9 +165,9 @@ def lds_chunked(prec, hd, maxkt, nch):      # adt_attn_gen.cuh: AttnChunkLds
     return 2 * (lpc * (hd + 8) + hd * (lpc + 8)) * esz(prec) + 2 * lp * 4 + 2 * lp * 4
 
 
-def lds_streamed(prec, hd, kc, bwd):      # adt_attn_stream.cuh: AttnStreamLds
+def lds_streamed(prec, hd, kc, bwd):      # adt_attn_long.cuh: AttnLongLds at 256 rows (LSE + delta in the backward, 256 validity bytes + 32)
     img = kc * (hd + 8) + hd * (kc + 8)
-    return 2 * img * esz(prec) + 2 * 256 * 4 + 2 * 256 * 4 if bwd else img * esz(prec) + 2 * 256 * 4
+    return 2 * img * esz(prec) + 2 * 256 * 4 + 256 + 32 if bwd else img * esz(prec) + 256 + 32
 
 
 def expect_attn(prec, hd, L, bwd, causal, kid, fill):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Stand-alone timing of the masked / general attention kernels (adt_attn_masked_fwd/bwd) at the BERT ml-20m and SASRec d=256 shapes,
 with and without dropout (the backward regenerates the dropout hash in both of its passes); head size 256 (d = 256, one head: the
-reference's search default, adt_attn_stream.cuh) next to head size 128 at the same L, with achieved TFLOP/s (causal: half the
+reference's search default, adt_attn_long.cuh at 256 rows) next to head size 128 at the same L, with achieved TFLOP/s (causal: half the
 score / PV work of the full L x L products is counted).  `python tools/bench_attn_gen.py long [out.jsonl]` times the entry points for
 L up to 1024 (adt_attn_long_fwd/bwd) instead, next to the older ones at the longest L those take (main_long)."""
 import os
