@@ -86,6 +86,8 @@ SIGNATURES = {
     "adt_layernorm_lanes_fwd": (_I, [_P, _I, _P, _P, _F, _I, _I, _I, _I, _P, _I, _P]),
     "adt_layernorm_lanes_bwd": (_I, [_P, _I, _P, _I, _P, _F, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
     "adt_drop_lanes": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _P, _U, _U, _P, _I, _P]),
+    "adt_drn_lanes_fwd": (_I, [_P, _I, _P, _I, _P, _P, _F, _I, _I, _I, _I, _F, _P, _U, _U, _P, _I, _P, _I, _P]),
+    "adt_drn_lanes_bwd": (_I, [_P, _I, _P, _I, _P, _F, _I, _I, _I, _I, _F, _P, _U, _U, _P, _I, _I, _P, _I, _P, _P, _P]),
     "adt_lane_map": (_I, [_P, _P, _P, _L, _I, _P]),
     "adt_attn_masked_scaled_fwd": (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, _F, _F, _P, _U, _U, _P, _I, _P, _P]),
     "adt_attn_masked_scaled_bwd": (_I, [_I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _F, _F, _P, _U, _U,

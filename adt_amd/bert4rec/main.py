@@ -127,7 +127,8 @@ def main(argv=None):
     torch.manual_seed(23)
     model = BertModel(usernum, itemnum, args)
     if world > 1:
-        torch.distributed.broadcast(model.flat, 0)
+        torch.distributed.broadcast(model.master, 0)      # padded widths: the reference-shaped buffer travels, then push()
+        model.push()
     trainer = FusedBertTrainer(model, lambda1, lambda2, lr=args.lr, betas=(0.9, 0.999), weight_decay=args.weight_decay, clip=args.clip,
                                process_group=pg, use_graph=args.use_graph, seed=23)
     rng = np.random.RandomState(23)

@@ -8,9 +8,14 @@ dense layers on MFMA (adt_gemm.cuh), masked bidirectional attention (adt_attn_ge
 row kernels, and an all-item logits + cross-entropy evaluated on the masked rows only (the reference materialises
 (B, L, V+100) logits; rows whose label is 0 contribute neither loss nor gradient, bert4rec/trainer.py:45).
 
+Widths the kernels do not tile (hidden_units 50, 100, 150, ...) run on a padded layout (adt_amd/wide.py:padded_layout):
+the parameters keep the reference's shapes, the kernels see d_pad columns with zero pad lanes, and the drop-residual-normalise sites run
+one fused pass per direction (adt_drn_lanes_fwd / _bwd).
+
 `train_step()` runs forward, loss assembly (bert4rec/trainer.py:112-134), backward, clip_grad_norm_ and Adam with its
 coupled weight decay on the device; it is HIP-graph capturable (masked-row counts live in device memory).
 """
+import math
 import os
 
 import numpy as np
@@ -18,7 +23,7 @@ import torch
 
 from .. import _lib, custom_ops, ops
 from ..fullrank import FullRankMixin
-from ..wide import Act, FlatModule, Tape, give
+from ..wide import Act, FlatModule, Tape, give, padded_layout
 
 LN_EPS = 1e-5
 MASK_FILL = -1e9
@@ -78,6 +83,25 @@ def param_table(item_num, maxlen, d, H, nl, inner, type_vocab, vocab=None, block
     return t
 
 
+def padded_tables(item_num, maxlen, d, H, nl, inner, type_vocab, vocab=None):
+    """(ref_table, pad_table, prefix) of a width the kernels do not tile (adt_amd/wide.py:padded_layout; pure arithmetic): the reference's
+    shapes, the same names at the padded shapes -- d -> d_pad with head h at [h * hd_pad, h * hd_pad + hd), head_classifier (H, hd_pad),
+    inner_units rounded up to a multiple of 4 (the dense kernels' leading dimensions) -- and the (name, axis) pairs of that zero-filled
+    inner tail for lane_index.  GELU(0) = 0, the bias pad is 0 and the pad columns of fc2 are 0, so the tail changes nothing."""
+    _, _, dp = padded_layout(d, H)
+    inner_pad = (inner + 3) // 4 * 4
+    ref = param_table(item_num, maxlen, d, H, nl, inner, type_vocab, vocab)
+    pad = param_table(item_num, maxlen, dp, H, nl, inner_pad, type_vocab, vocab)
+    prefix = set()
+    if inner_pad != inner:
+        for name, _ in ref:
+            if name.endswith(".fc1.weight") or name.endswith(".fc1.bias"):
+                prefix.add((name, 0))
+            elif name.endswith(".fc2.weight"):
+                prefix.add((name, 1))
+    return ref, pad, prefix
+
+
 class BertModel(FullRankMixin, FlatModule):
     def __init__(self, usernum, itemnum, args, vocab=None, inner_units=None, block=0):
         super().__init__()
@@ -93,24 +117,45 @@ class BertModel(FullRankMixin, FlatModule):
         self.fused_head = bool(getattr(args, "fused_head", False))
         self.args = args
         self.prec = {"f32": ops.PREC_F32, "fp32": ops.PREC_F32, "bf16": ops.PREC_BF16}[getattr(args, "precision", "bf16")]
-        if self.hidden_units % 64 or (self.hidden_units // self.num_heads) not in (16, 32, 64):
-            raise _lib.AdtError("BertModel (adt_amd): hidden_units must be a multiple of 64 with head size 16/32/64, got d=%d H=%d"
-                                % (self.hidden_units, self.num_heads))
+        d, H = self.hidden_units, self.num_heads
+        tiled = d >= 64 and d % 64 == 0 and d % H == 0 and (d // H) in (16, 32, 64)      # the widths this model has always taken, as they are
+        if block and not tiled:
+            raise _lib.AdtError("SuperBertModel (adt_amd): the supernet is built for hidden_units a multiple of 64 with head size 16/32/64 only "
+                                "(padded widths and head sizes 128 / 256 run on BertModel), got d=%d H=%d" % (d, H))
+        if tiled:
+            self.hd, self.hd_pad, self.dp = d // H, d // H, d
+        else:
+            try:
+                self.hd, self.hd_pad, self.dp = padded_layout(d, H)
+            except _lib.AdtError as e:
+                raise _lib.AdtError("BertModel (adt_amd): %s" % e) from None
         if not 1 <= self.maxlen <= MAX_LEN:
             raise _lib.AdtError("BertModel (adt_amd): maxlen must be in 1..%d, got d=%d H=%d L=%d"
                                 % (MAX_LEN, self.hidden_units, self.num_heads, self.maxlen))
-        self._build_flat(param_table(itemnum, args.maxlen, args.hidden_units, args.num_heads, args.num_layers, self.inner_units,
-                                     getattr(args, "type_vocab_size", 2), self.vocab, block), args.device, REF_ORDER)
+        # dp == d: the kernels tile the width as it is.  Otherwise activations and parameters are padded to dp columns (head h at
+        # [h * hd_pad, h * hd_pad + hd), zero pad lanes) and LayerNorm, the attention scale and the dropout indices
+        # keep the true width.  hidden_units stays the true d (loss normalisers, checkpoints); dp is the row length the kernels see.
+        self.lanes = (H, self.hd, self.hd_pad) if self.dp != d else None
+        self.drn_fused = os.environ.get("ADT_DRN_LANES", "1") != "0"     # 0: the two-pass form (adt_drop_lanes + adt_layernorm_lanes_*)
+        tv = getattr(args, "type_vocab_size", 2)
+        if self.lanes is None:
+            self._build_flat(param_table(itemnum, args.maxlen, d, H, args.num_layers, self.inner_units, tv, self.vocab, block), args.device,
+                             REF_ORDER)
+            ref_table = self.table
+        else:
+            ref_table, table, prefix = padded_tables(itemnum, args.maxlen, d, H, args.num_layers, self.inner_units, tv, self.vocab)
+            self._build_flat(table, args.device, REF_ORDER, ref_table=ref_table, width=(d, H), prefix=prefix)
         # bert4rec/trainer.py:29-37 re-initialises every Linear/Embedding weight N(0.01, initializer_range), LayerNorm 1/0,
         # Linear bias 0; do the same here so that a freshly constructed model is usable
         g = torch.Generator(device="cpu").manual_seed(torch.initial_seed() % (1 << 31))
         std = float(getattr(args, "initializer_range", 0.02))
-        for name, shape in self.table:
-            v = self.P(name)
+        for name, shape in ref_table:
+            v = self.R(name)         # reference shape (a view of the flat buffer itself without padding)
             if "layer_norm.weight" in name:
                 v.fill_(1.0)
             elif name.endswith(".weight"):
                 v.copy_(0.01 + std * torch.randn(shape, generator=g))
+        self.push()
 
     # ------------------------------------------------------------------------------------------------------------------
     def _embed(self, tp, ids, site):
@@ -150,10 +195,18 @@ class BertModel(FullRankMixin, FlatModule):
             return g[:, :d], g[:, d:2 * d], g[:, 2 * d:]
         return holders[0].g, holders[1].g[:, :d], holders[1].g[:, d:]
 
+    def _drn_lanes(self, tp):
+        """Padded width with the dropout on: the drop-residual-normalise sites run the fused pass (ADT_DRN_LANES=0: the two-pass form)."""
+        return tp.lanes is not None and self.drn_fused and tp.p_eff(self.attention_dropout) > 0.0
+
     def _ffn_drn(self, tp, p, x, ln_prefix, site):
         """FFN (modules.py:135-139, GELU) followed by its DropResidualNormalizeLayer."""
         P, G = self.P, self.G
         h = tp.dense(x, P(p + ".fc1.weight"), P(p + ".fc1.bias"), G(p + ".fc1.weight"), G(p + ".fc1.bias"), act=ops.ACT_GELU)
+        if self._drn_lanes(tp):
+            return tp.drn_lanes(h, P(p + ".fc2.weight"), P(p + ".fc2.bias"), G(p + ".fc2.weight"), G(p + ".fc2.bias"), self.attention_dropout, site, x,
+                                P(ln_prefix + ".layer_norm.weight"), P(ln_prefix + ".layer_norm.bias"), G(ln_prefix + ".layer_norm.weight"),
+                                G(ln_prefix + ".layer_norm.bias"), LN_EPS)
         z = tp.dense(h, P(p + ".fc2.weight"), P(p + ".fc2.bias"), G(p + ".fc2.weight"), G(p + ".fc2.bias"), p=self.attention_dropout, site=site, R=x)
         return tp.layernorm(z, P(ln_prefix + ".layer_norm.weight"), P(ln_prefix + ".layer_norm.bias"), G(ln_prefix + ".layer_norm.weight"),
                             G(ln_prefix + ".layer_norm.bias"), LN_EPS)
@@ -161,7 +214,8 @@ class BertModel(FullRankMixin, FlatModule):
     def _attn_drn(self, tp, p, ln_prefix, xq, xkv, key_ids, B, site_attn, site_drop, want_o=False):
         """Attention sublayer + DropResidualNormalizeLayer: LN(dropout(out_transfer(attn)) + xq)."""
         P, G = self.P, self.G
-        d, H, L = self.hidden_units, self.num_heads, self.maxlen
+        d, H, L = self.dp, self.num_heads, self.maxlen
+        scale = None if self.lanes is None else 1.0 / math.sqrt(self.hd)       # padded heads: 1 / sqrt(true head size)
         pa = tp.p_eff(self.attention_dropout)
         # projections
         qw, vb = p + ".query_transfer.weight", p + ".value_transfer.bias"
@@ -180,16 +234,21 @@ class BertModel(FullRankMixin, FlatModule):
         # past the length the resident kernels hold (224 rows at head size 16 / 32 / 64) the streamed ones take the same arguments
         streamed = L > ops.attn_masked_max_len(d // H)
         attn_fwd, attn_bwd = (ops.attn_long_fwd, ops.attn_long_bwd) if streamed else (ops.attn_masked_fwd, ops.attn_masked_bwd)
-        O, LSE = attn_fwd(self.prec, q, k, v, B, H, L, False, key_ids, MASK_FILL, pa, self._seed, site_attn, tp.b_offset)
+        O, LSE = attn_fwd(self.prec, q, k, v, B, H, L, False, key_ids, MASK_FILL, pa, self._seed, site_attn, tp.b_offset, scale=scale)
         o = Act(O)
 
         def bw():
             if o.g is None:
                 return
             attn_bwd(self.prec, q, k, v, O, LSE, o.g, B, H, L, False, key_ids, MASK_FILL, pa, self._seed, site_attn, tp.b_offset,
-                     out=self._dqkv(holders, d))
+                     out=self._dqkv(holders, d), scale=scale)
         tp.bw.append(bw)
         ow = p + ".out_transfer.weight"
+        if self._drn_lanes(tp):
+            y = tp.drn_lanes(o, P(ow), P(p + ".out_transfer.bias"), G(ow), G(p + ".out_transfer.bias"), self.attention_dropout, site_drop, xq,
+                             P(ln_prefix + ".layer_norm.weight"), P(ln_prefix + ".layer_norm.bias"), G(ln_prefix + ".layer_norm.weight"),
+                             G(ln_prefix + ".layer_norm.bias"), LN_EPS)
+            return y, o
         z = tp.dense(o, P(ow), P(p + ".out_transfer.bias"), G(ow), G(p + ".out_transfer.bias"), p=self.attention_dropout, site=site_drop, R=xq)
         y = tp.layernorm(z, P(ln_prefix + ".layer_norm.weight"), P(ln_prefix + ".layer_norm.bias"), G(ln_prefix + ".layer_norm.weight"),
                          G(ln_prefix + ".layer_norm.bias"), LN_EPS)
@@ -247,6 +306,10 @@ class BertModel(FullRankMixin, FlatModule):
         (bert4rec/trainer.py:100-138: CrossEntropyLoss over all items, loss.backward(), clip, Adam) runs on them unchanged -- with the
         reference's (B, L, V+100) logits materialised; FusedBertTrainer.step (masked rows only) is the fast way to train."""
         ids = [self.ids(src_ids), self.ids(dec_ids)]
+        if self.lanes is not None and custom_ops.wants_grad(self):
+            raise _lib.AdtError("BertModel (adt_amd): autograd through forward() (the reference's loop body) is not built for padded widths "
+                                "(d=%d H=%d runs as d_pad=%d); train with FusedBertTrainer (the fused loop) or call forward() under torch.no_grad()"
+                                % (self.hidden_units, self.num_heads, self.dp))
         if custom_ops.wants_grad(self):
             outs = custom_ops.forward_with_grad(self, ids)
         else:
@@ -261,15 +324,22 @@ class BertModel(FullRankMixin, FlatModule):
         d, H = self.hidden_units, self.num_heads
         if training:
             self.next_seed()
+        self.push()      # padded widths: the reference-shaped parameters are the truth between steps (no-op otherwise)
         tp = Tape(self, self.prec, training)
         enc, enc_inputs, recs = self._encode(tp, src.view(-1), B)
         dec_outs = self._decode(tp, dec.view(-1), src.view(-1), enc, B)
         h = self._head(tp, enc)
         logits = tp.dense(h, self.P("item_emb.word_emb.weight"), self.P("mask_bias"), self.G("item_emb.word_emb.weight"), self.G("mask_bias"))
         dec_outs.reverse()
-        outs = [logits.t.view(B, L, self.vocab)] + [a.t.view(B, L, d) for a in enc_inputs] + [a.t.view(B, L, d) for a in dec_outs] + \
+        outs = [logits.t.view(B, L, self.vocab)] + [self._live(a.t, B, L) for a in enc_inputs] + [self._live(a.t, B, L) for a in dec_outs] + \
                [r.t.view(B, L, H, H) for r in recs]
         return outs, {"tp": tp, "acts": [logits] + list(enc_inputs) + list(dec_outs) + list(recs)}
+
+    def _live(self, t, B, L):
+        """(B * L, dp) activation as the reference's (B, L, d): the live lanes of a padded width (a copy, outside the training step)."""
+        if self.lanes is None:
+            return t.view(B, L, self.dp)
+        return t.view(B, L, self.num_heads, self.hd_pad)[..., :self.hd].reshape(B, L, self.hidden_units)
 
     def _op_backward(self, st, grads):
         self.flat_grad.zero_()
@@ -285,10 +355,11 @@ class BertModel(FullRankMixin, FlatModule):
         src = self.ids(seqs)
         cand = self.ids(candidates)
         B, L = src.shape
+        self.push()
         tp = Tape(self, self.prec, False)
         enc, _, _ = self._encode(tp, src.view(-1), B)
         h = self._head(tp, Act(ops.gather_rows(enc.t, torch.arange(L - 1, B * L, L, device=self.dev, dtype=torch.int32))))
-        logits, rank = ops.score_rank_bias(h.t, self.hidden_units, self.P("item_emb.word_emb.weight"), self.P("mask_bias"), cand, B, cand.shape[1],
+        logits, rank = ops.score_rank_bias(h.t, self.dp, self.P("item_emb.word_emb.weight"), self.P("mask_bias"), cand, B, cand.shape[1],
                                            want_rank)
         return (logits, rank) if want_rank else logits
 
@@ -298,6 +369,7 @@ class BertModel(FullRankMixin, FlatModule):
         1..itemnum; the [MASK] row and the other rows of the 100-row vocabulary tail are never scored."""
         src = self.ids(seqs)
         B, L = src.shape
+        self.push()
         tp = Tape(self, self.prec, False)
         enc, _, _ = self._encode(tp, src.view(-1), B)
         h = self._head(tp, Act(ops.gather_rows(enc.t, torch.arange(L - 1, B * L, L, device=self.dev, dtype=torch.int32))))
@@ -339,7 +411,7 @@ class BertModel(FullRankMixin, FlatModule):
         Mdev = st["M"]
         E, gE = self.P("item_emb.word_emb.weight"), self.G("item_emb.word_emb.weight")
         h.g = torch.zeros_like(h.t)
-        if self.use_lce and ops.lce_supported(self.prec, d) and (d != 64 or self.fused_head):
+        if self.use_lce and ops.lce_supported(self.prec, self.dp) and (self.dp != 64 or self.fused_head):
             # fused: online log-sum-exp forward, tile-recomputing backward; no (rows, V) logits in memory (adt_amd/csrc/adt_lce.cuh)
             ops.lce_fwd_bwd(h.t, st["rows"], st["labels"], mcap, Mdev, E, self.P("mask_bias"), st["inv_count"], loss_slots[0], h.g, gE,
                             self.G("mask_bias"))

@@ -50,9 +50,12 @@ class FusedBertTrainer(TapeTrainer):
     def _body(self, st, b_offset):
         m = self.model
         T = st["B"] * m.maxlen
+        m.push()        # padded widths: the reference-shaped parameters are the truth between steps (no-op otherwise)
         m.loss_forward_backward(st, self.lambda1, self.lambda2, st["norms"], self.loss_slots, b_offset, int(np.ceil(self.mcap_frac * T)))
         self._buckets.finish()
+        # pad weights and pad gradients are exact zeros, so the coupled weight decay keeps them zero
         ops.clip_adam_l2(m.flat, m.flat_grad, self.m, self.v, self.wd, self.clip, self.lr, self.betas[0], self.betas[1], self.eps, self.scal)
+        m.pull()
 
     def step(self, src, dec, labels, n_valid_global=None, b_offset=0, norms_scale=1):
         self.step_staged(self.stage(src, dec, labels, n_valid_global, norms_scale), b_offset)

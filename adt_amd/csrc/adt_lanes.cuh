@@ -199,6 +199,173 @@ __global__ __launch_bounds__(256) void k_drop_lanes(DropLanesArgs a) {
   }
 }
 
+// Fused drop-residual-normalise on padded lanes (BERT4Rec-ADT's repeating unit LN(dropout(dense(x)) + residual)), one pass per direction
+// instead of k_drop_lanes + k_ln_lanes_*.  Geometry of k_ln_lanes_*: 16 lanes per row, float4 accesses, grid-stride over rows.
+//   forward:  Z = live ? R + keep * scale * S : 0 (kept for the backward; may alias S), Y = LN_live(Z) * gamma + beta, pad lanes +0.0;
+//   backward: dZ = LN backward of dY at Z, written (or accumulated) into dR; dS = keep * scale * dZ; dgamma / dbeta as k_ln_lanes_bwd.
+// keep is indexed at the TRUE width, (t + row_offset) * d + true_col(c), every element hashing for itself (see the head of this file).
+struct DrnLanesArgs {
+  const float* S; int lds;
+  const float* R; int ldr;
+  const float* gamma; const float* beta;
+  float eps;
+  float* Z; int ldz;
+  float* Y; int ldy;
+  int T; Lanes ln; DropCfg drop; uint32_t row_offset;
+  const float* dY; int lddy;
+  float* dR; int lddr; int acc;
+  float* dS; int ldds;
+  float* dgamma; float* dbeta;
+};
+
+template <int KP>
+__global__ __launch_bounds__(LN_LANES_THREADS) void k_drn_lanes_fwd(DrnLanesArgs a) {
+  constexpr int E = KP / 16;
+  constexpr int rows_per_block = LN_LANES_THREADS / 16;
+  const int sub = threadIdx.x & 15;
+  const int d = a.ln.H * a.ln.hd;
+  const float inv_d = 1.0f / (float)d;
+  const uint32_t key = drop_key(a.drop);
+  bool lv[E];
+  uint32_t tc[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const int col = (e / 4) * 64 + 4 * sub + (e & 3);
+    lv[e] = a.ln.live(col);
+    tc[e] = (uint32_t)a.ln.true_col(col);
+  }
+  for (int row = blockIdx.x * rows_per_block + (threadIdx.x >> 4); row < a.T; row += gridDim.x * rows_per_block) {
+    float x[E], r[E];
+#pragma unroll
+    for (int e = 0; e < E; e += 4) {
+      const int col = (e / 4) * 64 + 4 * sub;
+      *reinterpret_cast<float4*>(x + e) = *reinterpret_cast<const float4*>(a.S + (size_t)row * a.lds + col);
+      *reinterpret_cast<float4*>(r + e) = *reinterpret_cast<const float4*>(a.R + (size_t)row * a.ldr + col);
+    }
+    const uint32_t base = ((uint32_t)row + a.row_offset) * (uint32_t)d;
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      float ks = 1.0f;
+      if (a.drop.thr) ks = (lv[e] && adt_keep(key, base + tc[e], a.drop.thr)) ? a.drop.scale : 0.f;
+      x[e] = lv[e] ? r[e] + ks * x[e] : 0.f;
+      s += x[e];
+    }
+#pragma unroll
+    for (int e = 0; e < E; e += 4)
+      *reinterpret_cast<float4*>(a.Z + (size_t)row * a.ldz + (e / 4) * 64 + 4 * sub) = *reinterpret_cast<float4*>(x + e);
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    const float mu = s * inv_d;
+    float q = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) { x[e] = lv[e] ? x[e] - mu : 0.f; q += x[e] * x[e]; }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+    const float rstd = 1.0f / sqrtf(q * inv_d + a.eps);
+#pragma unroll
+    for (int e = 0; e < E; e += 4) {
+      const int col = (e / 4) * 64 + 4 * sub;
+      float gm[4], bt[4], y[4];
+      *reinterpret_cast<float4*>(gm) = *reinterpret_cast<const float4*>(a.gamma + col);
+      *reinterpret_cast<float4*>(bt) = *reinterpret_cast<const float4*>(a.beta + col);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) y[j] = lv[e + j] ? x[e + j] * rstd * gm[j] + bt[j] : 0.f;
+      *reinterpret_cast<float4*>(a.Y + (size_t)row * a.ldy + col) = *reinterpret_cast<float4*>(y);
+    }
+  }
+}
+
+template <int KP>
+__global__ __launch_bounds__(LN_LANES_THREADS) void k_drn_lanes_bwd(DrnLanesArgs a) {
+  constexpr int E = KP / 16;
+  constexpr int rows_per_block = LN_LANES_THREADS / 16;
+  __shared__ float sred[2][rows_per_block][KP];
+  const int sub = threadIdx.x & 15, rg = threadIdx.x >> 4;
+  const int d = a.ln.H * a.ln.hd;
+  const float inv_d = 1.0f / (float)d;
+  const uint32_t key = drop_key(a.drop);
+  float dg[E] = {}, dbt[E] = {};
+  float gm[E];
+  bool lv[E];
+#pragma unroll
+  for (int e = 0; e < E; e += 4) *reinterpret_cast<float4*>(gm + e) = *reinterpret_cast<const float4*>(a.gamma + (e / 4) * 64 + 4 * sub);
+#pragma unroll
+  for (int e = 0; e < E; ++e) lv[e] = a.ln.live((e / 4) * 64 + 4 * sub + (e & 3));
+  for (int row = blockIdx.x * rows_per_block + rg; row < a.T; row += gridDim.x * rows_per_block) {
+    float x[E], dy[E];
+#pragma unroll
+    for (int e = 0; e < E; e += 4) {
+      const int col = (e / 4) * 64 + 4 * sub;
+      *reinterpret_cast<float4*>(x + e) = *reinterpret_cast<const float4*>(a.Z + (size_t)row * a.ldz + col);
+      *reinterpret_cast<float4*>(dy + e) = *reinterpret_cast<const float4*>(a.dY + (size_t)row * a.lddy + col);
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) s += lv[e] ? x[e] : 0.f;
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    const float mu = s * inv_d;
+    float q = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) { x[e] = lv[e] ? x[e] - mu : 0.f; q += x[e] * x[e]; }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+    const float rstd = 1.0f / sqrtf(q * inv_d + a.eps);
+    float m1 = 0.f, m2 = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      x[e] *= rstd;                              // xhat (0 on pad lanes)
+      dy[e] = lv[e] ? dy[e] : 0.f;
+      dg[e] += dy[e] * x[e];
+      dbt[e] += dy[e];
+      dy[e] *= gm[e];                            // dxhat
+      m1 += dy[e];
+      m2 += dy[e] * x[e];
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) { m1 += __shfl_xor(m1, o, 64); m2 += __shfl_xor(m2, o, 64); }
+    m1 *= inv_d;
+    m2 *= inv_d;
+    const uint32_t base = ((uint32_t)row + a.row_offset) * (uint32_t)d;
+#pragma unroll
+    for (int e = 0; e < E; e += 4) {
+      const int col = (e / 4) * 64 + 4 * sub;
+      float* dst = a.dR + (size_t)row * a.lddr + col;
+      float r[4], ds[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        r[j] = lv[e + j] ? rstd * (dy[e + j] - m1 - x[e + j] * m2) : 0.f;      // dZ
+        float ks = 1.0f;
+        if (a.drop.thr) ks = (lv[e + j] && adt_keep(key, base + (uint32_t)a.ln.true_col(col + j), a.drop.thr)) ? a.drop.scale : 0.f;
+        ds[j] = lv[e + j] ? ks * r[j] : 0.f;
+      }
+      *reinterpret_cast<float4*>(a.dS + (size_t)row * a.ldds + col) = *reinterpret_cast<float4*>(ds);
+      if (a.acc) {                                 // pad lanes are written as +0.0 whatever the old dR held there
+        float o[4];
+        *reinterpret_cast<float4*>(o) = *reinterpret_cast<const float4*>(dst);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r[j] += lv[e + j] ? o[j] : 0.f;
+      }
+      *reinterpret_cast<float4*>(dst) = *reinterpret_cast<float4*>(r);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const int col = (e / 4) * 64 + 4 * sub + (e & 3);
+    sred[0][rg][col] = dg[e];
+    sred[1][rg][col] = dbt[e];
+  }
+  __syncthreads();
+  for (int col = threadIdx.x; col < KP; col += LN_LANES_THREADS) {
+    if (!a.ln.live(col)) continue;               // pad entries of dgamma / dbeta are never touched
+    float s0 = 0.f, s1 = 0.f;
+    for (int r = 0; r < rows_per_block; ++r) { s0 += sred[0][r][col]; s1 += sred[1][r][col]; }
+    atomicAdd(a.dgamma + col, s0);
+    atomicAdd(a.dbeta + col, s1);
+  }
+}
+
 // compact[i] = padded[map[i]] (gather) / padded[map[i]] = compact[i] (scatter; the map is injective): the reference-shaped copy of the
 // parameters or of an optimizer moment against the padded flat buffer the kernels compute on.
 struct LaneMapArgs { float* padded; float* compact; const int* map; size_t n; int scatter; };

@@ -666,8 +666,8 @@ static int make_lanes(Lanes& ln, int H, int hd, int hd_pad, const char* what) {
   return 0;
 }
 
-template <typename K64, typename K128, typename K192, typename K256>
-static void launch_by_width(int dp, K64 k64, K128 k128, K192 k192, K256 k256, int grid, hipStream_t s, const LnLanesArgs& a) {
+template <typename K64, typename K128, typename K192, typename K256, typename Args>
+static void launch_by_width(int dp, K64 k64, K128 k128, K192 k192, K256 k256, int grid, hipStream_t s, const Args& a) {
   if (dp == 64) hipLaunchKernelGGL(k64, dim3(grid), dim3(LN_LANES_THREADS), 0, s, a);
   else if (dp == 128) hipLaunchKernelGGL(k128, dim3(grid), dim3(LN_LANES_THREADS), 0, s, a);
   else if (dp == 192) hipLaunchKernelGGL(k192, dim3(grid), dim3(LN_LANES_THREADS), 0, s, a);
@@ -716,6 +716,44 @@ int adt_drop_lanes(const float* S, int lds, const float* R, int ldr, const float
   a.drop = adt_make_drop(p, seed, site); a.row_offset = row_offset;
   hipLaunchKernelGGL(k_drop_lanes, dim3(adt_grid_for((size_t)T * (dp / 4), 1024, 4096)), dim3(256), 0, (hipStream_t)stream, a);
   return adt_check_launch("drop_lanes");
+}
+
+int adt_drn_lanes_fwd(const float* S, int lds, const float* R, int ldr, const float* gamma, const float* beta, float eps, int T, int H, int hd,
+                      int hd_pad, float p, const uint32_t* seed, uint32_t site, uint32_t row_offset, float* Z, int ldz, float* Y, int ldy,
+                      void* stream) {
+  DrnLanesArgs a{};
+  if (make_lanes(a.ln, H, hd, hd_pad, "drn_lanes_fwd")) return -1;
+  if (T <= 0) return 0;
+  const int dp = H * hd_pad;
+  if (!S || !R || !Z || !Y || !gamma || !beta) return adt_set_error("drn_lanes_fwd: S, R, gamma, beta, Z and Y are required");
+  if ((lds % 4) || (ldr % 4) || (ldz % 4) || (ldy % 4) || lds < dp || ldr < dp || ldz < dp || ldy < dp || !adt_aligned16(S) || !adt_aligned16(R) ||
+      !adt_aligned16(Z) || !adt_aligned16(Y) || !adt_aligned16(gamma) || !adt_aligned16(beta))
+    return adt_set_error("drn_lanes_fwd: ld %% 4, ld >= d_pad and 16-byte alignment required");
+  a.S = S; a.lds = lds; a.R = R; a.ldr = ldr; a.gamma = gamma; a.beta = beta; a.eps = eps; a.Z = Z; a.ldz = ldz; a.Y = Y; a.ldy = ldy; a.T = T;
+  a.drop = adt_make_drop(p, seed, site); a.row_offset = row_offset;
+  launch_by_width(dp, k_drn_lanes_fwd<64>, k_drn_lanes_fwd<128>, k_drn_lanes_fwd<192>, k_drn_lanes_fwd<256>, adt_grid_for(T, 16, 2048),
+                  (hipStream_t)stream, a);
+  return adt_check_launch("drn_lanes_fwd");
+}
+
+int adt_drn_lanes_bwd(const float* dY, int lddy, const float* Z, int ldz, const float* gamma, float eps, int T, int H, int hd, int hd_pad, float p,
+                      const uint32_t* seed, uint32_t site, uint32_t row_offset, float* dR, int lddr, int accumulate, float* dS, int ldds,
+                      float* dgamma, float* dbeta, void* stream) {
+  DrnLanesArgs a{};
+  if (make_lanes(a.ln, H, hd, hd_pad, "drn_lanes_bwd")) return -1;
+  if (T <= 0) return 0;
+  const int dp = H * hd_pad;
+  if (!dY || !Z || !gamma || !dR || !dS || !dgamma || !dbeta) return adt_set_error("drn_lanes_bwd: dY, Z, gamma, dR, dS, dgamma and dbeta are required");
+  if ((lddy % 4) || (ldz % 4) || (lddr % 4) || (ldds % 4) || lddy < dp || ldz < dp || lddr < dp || ldds < dp || !adt_aligned16(dY) || !adt_aligned16(Z) ||
+      !adt_aligned16(dR) || !adt_aligned16(dS) || !adt_aligned16(gamma))
+    return adt_set_error("drn_lanes_bwd: ld %% 4, ld >= d_pad and 16-byte alignment required");
+  // the backward only reads Z
+  a.dY = dY; a.lddy = lddy; a.Z = const_cast<float*>(Z); a.ldz = ldz; a.gamma = gamma; a.eps = eps; a.T = T; a.dR = dR; a.lddr = lddr; a.acc = accumulate;
+  a.dS = dS; a.ldds = ldds; a.dgamma = dgamma; a.dbeta = dbeta;
+  a.drop = adt_make_drop(p, seed, site); a.row_offset = row_offset;
+  launch_by_width(dp, k_drn_lanes_bwd<64>, k_drn_lanes_bwd<128>, k_drn_lanes_bwd<192>, k_drn_lanes_bwd<256>, adt_grid_for(T, 16, 256),
+                  (hipStream_t)stream, a);
+  return adt_check_launch("drn_lanes_bwd");
 }
 
 int adt_lane_map(float* padded, float* compact, const int32_t* map, int64_t n, int scatter, void* stream) {

@@ -677,6 +677,31 @@ def drop_lanes(S, lanes, p=0.0, seed=None, site=0, row_offset=0, R=None, R2=None
     return out
 
 
+def drn_lanes_fwd(S, R, gamma, beta, eps, lanes, p=0.0, seed=None, site=0, row_offset=0, Z=None, Y=None):
+    """Fused drop-residual-normalise on padded rows: Z = R + dropout(S) on the live lanes (dropout indexed at the true width), Y = LayerNorm
+    of Z over the live lanes; exact zeros on the pad lanes of both.  Z may be S itself.  Returns (Z, Y)."""
+    H, hd, hd_pad = lanes
+    T, dp = S.shape
+    assert dp == H * hd_pad and R.shape == S.shape, (S.shape, R.shape, lanes)
+    if Z is None:
+        Z = torch.empty(T, dp, device=S.device, dtype=torch.float32)
+    if Y is None:
+        Y = torch.empty(T, dp, device=S.device, dtype=torch.float32)
+    _lib.check(_lib.load().adt_drn_lanes_fwd(_p(_f32(S)), _ld(S), _p(_f32(R)), _ld(R), _p(gamma), _p(beta), eps, T, H, hd, hd_pad, float(p), _p(seed),
+                                             site, row_offset, _p(_f32(Z)), _ld(Z), _p(_f32(Y)), _ld(Y), _stream()), "drn_lanes_fwd")
+    return Z, Y
+
+
+def drn_lanes_bwd(dY, Z, gamma, eps, lanes, p, seed, site, row_offset, dR, accumulate, dS, dgamma, dbeta):
+    """Backward of drn_lanes_fwd: dR (+)= dZ, dS = keep / (1 - p) * dZ, dgamma / dbeta += their sums over the rows."""
+    H, hd, hd_pad = lanes
+    T, dp = Z.shape
+    assert dp == H * hd_pad, (Z.shape, lanes)
+    _lib.check(_lib.load().adt_drn_lanes_bwd(_p(_f32(dY)), _ld(dY), _p(_f32(Z)), _ld(Z), _p(gamma), eps, T, H, hd, hd_pad, float(p), _p(seed), site,
+                                             row_offset, _p(_f32(dR)), _ld(dR), int(accumulate), _p(_f32(dS)), _ld(dS), _p(dgamma), _p(dbeta),
+                                             _stream()), "drn_lanes_bwd")
+
+
 def lane_map(padded, compact, index, scatter):
     """compact[i] = padded[index[i]] (scatter False) or padded[index[i]] = compact[i] (scatter True)."""
     assert padded.dtype == torch.float32 and compact.dtype == torch.float32 and compact.is_contiguous() and compact.numel() == index.numel()

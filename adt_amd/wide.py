@@ -70,10 +70,11 @@ def padded_layout(d, H):
     return hd, hd_pad, d_pad
 
 
-def lane_index(ref_table, pad_table, pad_offsets, d, H):
+def lane_index(ref_table, pad_table, pad_offsets, d, H, prefix=()):
     """For every element of the reference-shaped parameters (ref_table order, packed densely) its position in the padded flat buffer.
     A dimension of size d (or 3d, or hd) that the padded table widens to d_pad (3 d_pad, hd_pad) maps channel h * hd + j to
-    h * hd_pad + j; equal dimensions map to themselves."""
+    h * hd_pad + j; equal dimensions map to themselves.  prefix: (name, axis) pairs whose dimension the padded table widens by a
+    zero-filled TAIL (BERT4Rec-ADT's inner_units rounded up to a multiple of 4): element j stays at j."""
     hd, hd_pad, d_pad = padded_layout(d, H)
     chan = (np.arange(d) // hd) * hd_pad + np.arange(d) % hd
     maps = {(d, d_pad): chan, (3 * d, 3 * d_pad): np.concatenate([chan + k * d_pad for k in range(3)]), (hd, hd_pad): np.arange(hd)}
@@ -84,8 +85,8 @@ def lane_index(ref_table, pad_table, pad_offsets, d, H):
         assert len(pshape) == len(shape), (name, shape, pshape)
         idx = np.zeros((), dtype=np.int64)
         stride = 1
-        for r, q in zip(shape[::-1], pshape[::-1]):
-            m = np.arange(r) if r == q else maps[(r, q)]
+        for ax, (r, q) in enumerate(zip(shape[::-1], pshape[::-1])):
+            m = np.arange(r) if r == q or (name, len(shape) - 1 - ax) in prefix else maps[(r, q)]
             idx = m.reshape((-1,) + (1,) * idx.ndim) * stride + idx
             stride *= q
         out.append((idx + pad_offsets[name]).reshape(-1))
@@ -100,7 +101,7 @@ class FlatModule(torch.nn.Module):
     boundaries; tensors listed consecutively with sizes that are multiples of 4 floats are contiguous, which is what
     lets q/k/v projections run as one GEMM over a (3d, d) view."""
 
-    def _build_flat(self, table, device, ref_order=None, ref_table=None, width=None):
+    def _build_flat(self, table, device, ref_order=None, ref_table=None, width=None, prefix=()):
         """ref_table / width=(d, H): `table` is the PADDED layout of a width the kernels do not tile (padded_layout); the registered
         parameters then have the reference's shapes and live in a second, densely packed buffer `ref_flat`, copied to and from the
         live lanes of `flat` by push() / pull() (one kernel each).  Between steps ref_flat is the truth; the pad lanes of `flat`
@@ -126,7 +127,7 @@ class FlatModule(torch.nn.Module):
         if ref_table is not None:
             ref_table = [(n, tuple(s)) for n, s in ref_table]
             assert [n for n, _ in ref_table] == names
-            index = lane_index(ref_table, self.table, {n: v[0] for n, v in self._views.items()}, *width)
+            index = lane_index(ref_table, self.table, {n: v[0] for n, v in self._views.items()}, *width, prefix=prefix)
             self.lane_idx = torch.from_numpy(index).to(self.dev)
             self.ref_flat = torch.zeros(index.size, device=self.dev, dtype=torch.float32)
             self._ref_views, o = {}, 0
@@ -428,6 +429,9 @@ class Tape:
         p = self.p_eff(p)
         if p == 0.0 and act == ops.ACT_NONE:
             return x
+        if self.lanes is not None:
+            assert act == ops.ACT_NONE, "padded widths: dropout without an activation only"
+            return self._drop_lanes(x, p, site)
         off = self.row_offset * x.t.shape[1]
         y = Act(ops.dropact_fwd(x.t, p, self.seed, site, off, act))
 
@@ -438,6 +442,41 @@ class Tape:
             if not acc:
                 x.g = torch.empty_like(x.t)
             ops.dropact_bwd(y.g, x.t, p, self.seed, site, x.g, acc, off, act)
+        self.bw.append(bw)
+        return y
+
+    def _drop_lanes(self, x, p, site):
+        """dropact() on a padded width: the dropout index runs over the true width (adt_drop_lanes)."""
+        y = Act(ops.drop_lanes(x.t, self.lanes, p, self.seed, site, self.row_offset))
+
+        def bw():
+            if y.g is None:
+                return
+            give(x, ops.drop_lanes(y.g, self.lanes, p, self.seed, site, self.row_offset))
+        self.bw.append(bw)
+        return y
+
+    def drn_lanes(self, x, W, b, gW, gb, p, site, R, w, bn, gw, gbn, eps):
+        """LN(R + dropout(x W^T + b)) on a padded width with dropout on: the GEMM without an epilogue, then ONE pass that drops (indexed
+        at the true width), adds the residual and normalises over the live lanes (adt_drn_lanes_fwd; Z overwrites the GEMM's output).
+        The backward is one pass too: dZ into the residual's gradient, dS for the two backward GEMMs."""
+        p = self.p_eff(p)
+        S, _ = ops.dense_fwd(self.prec, x.t, W, b)
+        Z, Y = ops.drn_lanes_fwd(S, R.t, w, bn, eps, self.lanes, p, self.seed, site, self.row_offset, Z=S)
+        y = Act(Y)
+
+        def bw():
+            if y.g is None:
+                return
+            acc = R.g is not None
+            if not acc:
+                R.g = torch.empty_like(R.t)
+            dS = torch.empty_like(Z)
+            ops.drn_lanes_bwd(y.g, Z, w, eps, self.lanes, p, self.seed, site, self.row_offset, R.g, acc, dS, gw, gbn)
+            beta = x.g is not None
+            if not beta:
+                x.g = torch.empty_like(x.t)
+            ops.dense_bwd(self.prec, dS, x.t, W, gW, gb, x.g, beta)
         self.bw.append(bw)
         return y
 

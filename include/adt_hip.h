@@ -693,6 +693,17 @@ int adt_layernorm_lanes_bwd(const float* dY, int lddy, const float* X, int ldx, 
 int adt_drop_lanes(const float* S, int lds, const float* R, int ldr, const float* R2, int ldr2, const int32_t* mask_ids, int T,
                    int H, int hd, int hd_pad, float p, const uint32_t* seed, uint32_t site, uint32_t row_offset, float* out,
                    int ldo, void* stream);
+/* Fused drop-residual-normalise on padded lanes, BERT4Rec-ADT's LN(dropout(S) + R) in one pass per direction.
+ * fwd: Z = live ? R + keep / (1 - p) * S : 0 (kept for the backward; Z may be S itself), Y = LayerNorm over the live lanes of Z;
+ * bwd: dZ = LayerNorm backward of dY at Z, written into dR (accumulate != 0: added to it; pad lanes written +0.0 either way),
+ *      dS = keep / (1 - p) * dZ (dS may be dY itself), dgamma / dbeta += their sums (pad entries untouched).
+ * keep is indexed at the true width, (t + row_offset) * d + true column, as adt_drop_lanes. */
+int adt_drn_lanes_fwd(const float* S, int lds, const float* R, int ldr, const float* gamma, const float* beta, float eps, int T,
+                      int H, int hd, int hd_pad, float p, const uint32_t* seed, uint32_t site, uint32_t row_offset, float* Z,
+                      int ldz, float* Y, int ldy, void* stream);
+int adt_drn_lanes_bwd(const float* dY, int lddy, const float* Z, int ldz, const float* gamma, float eps, int T, int H, int hd,
+                      int hd_pad, float p, const uint32_t* seed, uint32_t site, uint32_t row_offset, float* dR, int lddr,
+                      int accumulate, float* dS, int ldds, float* dgamma, float* dbeta, void* stream);
 /* compact[i] = padded[map[i]] (scatter == 0) or padded[map[i]] = compact[i] (scatter != 0; map injective): reference-shaped
  * parameters / optimizer moments against the padded flat buffer. */
 int adt_lane_map(float* padded, float* compact, const int32_t* map, int64_t n, int scatter, void* stream);

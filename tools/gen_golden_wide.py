@@ -4,7 +4,7 @@
 fixtures are data only: seeded inputs, the seed that regenerates the numpy weights, and the tensors the reference
 produced for them.
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_wide.py [bert|bert_cfg3|bert_long|stosa|stosa_cfg5|stosa_kl|stosa_kl_rowwise|stosa_long]
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_wide.py [bert|bert_cfg3|bert_long|bert_odd|stosa|stosa_cfg5|stosa_kl|stosa_kl_rowwise|stosa_long]
 
 The loss assembly calls the same torch functions, in the same order, as the reference's training loops
 (bert4rec/trainer.py:100-138, stosa/trainer.py:392-447 + :358-391), which are not importable as functions without the
@@ -24,6 +24,7 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 OUT = os.path.join(REPO, "tests", "golden")
+BERT_ODD_COMPACT = dict(thresh=2048, k=320)      # bert_odd: what tools/gen_golden_inputs.py:golden_err is called with for these files
 
 
 class Args:
@@ -113,7 +114,10 @@ def gen_bert(tag, cfg_kw, B, seed, lam1, lam2, wd=1e-4, lr=1e-3, clip=5.0, keep_
         if step == 0:
             out["loss"] = float(loss.item())
             for k, p in m.named_parameters():
-                out["grad." + k] = p.grad.numpy().copy()
+                if p.grad is None:        # one head: the reference never runs head_classifier (the tests assert an exactly-zero gradient)
+                    out["gnone." + k] = np.zeros(0, np.float32)
+                else:
+                    out["grad." + k] = p.grad.numpy().copy()
         tn = torch.nn.utils.clip_grad_norm_(m.parameters(), clip)
         if step == 0:
             out["grad_norm"] = float(tn)
@@ -155,6 +159,23 @@ def main():
         # the value, above every bound the tests use.  Seed 46 draws b0 - b1 = -0.03: the gradient is 6.9e-4, that error 4e-6 of it
         gen_bert("l272", dict(item_num=40, maxlen=272, hidden_units=64, num_heads=2, num_layers=1, inner_units=96), B=2, seed=46,
                  lam1=[0.2], lam2=[0.1], compact=True, lens=[250, 31], compact_kw=dict(thresh=2048, k=512))
+    if "bert_odd" in which:
+        # widths the kernels pad (adt_amd/wide.py:padded_layout): 50 with one head (64 lanes) and two (2 x 32), 100 as 2 x 64, 150 as
+        # 3 x 64 = 192, and the head sizes 128 / 256 that need no padding.  One head: the reference leaves head_classifier.* at grad None
+        # (gnone.<name> keys).  Compacted like bert_l272.npz so that every file stays below its size
+        odd = dict(keep_w3=False, compact=True, compact_kw=BERT_ODD_COMPACT)
+        gen_bert("w50_h1", dict(item_num=40, maxlen=12, hidden_units=50, num_heads=1, num_layers=2, inner_units=100), B=4, seed=21,
+                 lam1=[0.3, 0.2], lam2=[0.2, 0.1], **odd)
+        gen_bert("w50_h2", dict(item_num=40, maxlen=12, hidden_units=50, num_heads=2, num_layers=2, inner_units=100), B=4, seed=22,
+                 lam1=[0.3, 0.2], lam2=[0.2, 0.1], **odd)
+        gen_bert("w100_h2", dict(item_num=30, maxlen=20, hidden_units=100, num_heads=2, num_layers=1, inner_units=200), B=3, seed=23,
+                 lam1=[0.25], lam2=[0.15], **odd)
+        gen_bert("w150_h3", dict(item_num=30, maxlen=9, hidden_units=150, num_heads=3, num_layers=1, inner_units=64), B=2, seed=24,
+                 lam1=[0.1], lam2=[0.05], **odd)
+        gen_bert("hd128", dict(item_num=25, maxlen=9, hidden_units=128, num_heads=1, num_layers=1, inner_units=64), B=2, seed=25,
+                 lam1=[0.1], lam2=[0.05], **odd)
+        gen_bert("hd256", dict(item_num=25, maxlen=9, hidden_units=256, num_heads=1, num_layers=1, inner_units=64), B=2, seed=26,
+                 lam1=[0.1], lam2=[0.05], **odd)
     if "stosa" in which:
         from tools import gen_golden_stosa
         gen_golden_stosa.main()
