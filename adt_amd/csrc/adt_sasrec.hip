@@ -1364,6 +1364,7 @@ int64_t adt_seq_layer_save_floats(int B, int L, int H, int dec) { return layer_s
 int adt_seq_enc_layer_fwd(int B, int L, int H, const int32_t* ids, const float* x, const adt_enc_layer_ptrs* P, const float* wp_base,
                           const void* wp_img, float p, const uint32_t* seed, uint32_t site_attn, uint32_t site_ffn1, uint32_t site_ffn2,
                           uint32_t b_offset, int training, float* save, float* y, float y_scale, int y_acc, float* rec, void* st) {
+  if (H != 1 && H != 2 && H != 4) return adt_set_error("seq_enc_layer_fwd: H=%d (d = 64 takes 1, 2 or 4 heads)", H);
   const int hd = 64 / H;
   const StepPlan pl = layer_plan(ADT_PREC_BF16, L, 64, hd, B);
   if (!pl.parts) return adt_set_error("seq_enc_layer_fwd: L=%d H=%d is not covered", L, H);
@@ -1383,6 +1384,7 @@ int adt_seq_enc_layer_bwd(int B, int L, int H, const int32_t* ids, const float* 
                           const float* wp_base, const void* wp_img, float p, const uint32_t* seed, uint32_t site_attn, uint32_t site_ffn1,
                           uint32_t site_ffn2, uint32_t b_offset, const float* save, const float* gy, float gy_scale, const float* rec,
                           const float* drec, float* gx, int gx_acc, float* scratch, void* st) {
+  if (H != 1 && H != 2 && H != 4) return adt_set_error("seq_enc_layer_bwd: H=%d (d = 64 takes 1, 2 or 4 heads)", H);
   const int hd = 64 / H, T = B * L;
   const StepPlan pl = layer_plan(ADT_PREC_BF16, L, 64, hd, B);
   if (!pl.parts) return adt_set_error("seq_enc_layer_bwd: L=%d H=%d is not covered", L, H);
@@ -1410,6 +1412,7 @@ int adt_seq_enc_layer_bwd(int B, int L, int H, const int32_t* ids, const float* 
 int adt_seq_dec_layer_fwd(int B, int L, int H, const int32_t* ids, const float* x, const float* feats, const adt_dec_layer_ptrs* P,
                           const float* wp_base, const void* wp_img, float p, const uint32_t* seed, uint32_t site_slf, uint32_t site_enc,
                           uint32_t site_ffn1, uint32_t site_ffn2, uint32_t b_offset, float* save, float* y, float y_scale, int y_acc, void* st) {
+  if (H != 1 && H != 2 && H != 4) return adt_set_error("seq_dec_layer_fwd: H=%d (d = 64 takes 1, 2 or 4 heads)", H);
   const int hd = 64 / H;
   const StepPlan pl = layer_plan(ADT_PREC_BF16, L, 64, hd, B);
   if (!pl.parts) return adt_set_error("seq_dec_layer_fwd: L=%d H=%d is not covered", L, H);
@@ -1428,6 +1431,7 @@ int adt_seq_dec_layer_bwd(int B, int L, int H, const int32_t* ids, const float* 
                           const adt_dec_layer_ptrs* G, const float* wp_base, const void* wp_img, float p, const uint32_t* seed,
                           uint32_t site_slf, uint32_t site_enc, uint32_t site_ffn1, uint32_t site_ffn2, uint32_t b_offset, const float* save,
                           const float* gy, float gy_scale, float* gx, int gx_acc, float* gfeats, float* scratch, void* st) {
+  if (H != 1 && H != 2 && H != 4) return adt_set_error("seq_dec_layer_bwd: H=%d (d = 64 takes 1, 2 or 4 heads)", H);
   const int hd = 64 / H, T = B * L, d = 64;
   const StepPlan pl = layer_plan(ADT_PREC_BF16, L, 64, hd, B);
   if (!pl.parts) return adt_set_error("seq_dec_layer_bwd: L=%d H=%d is not covered", L, H);

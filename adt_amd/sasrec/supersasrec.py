@@ -164,24 +164,30 @@ class SuperSASRecModel(FlatModule):
         p = tp.p_eff(self.dropout)
         y = Act(torch.empty(T, self.hidden_units, device=self.dev, dtype=torch.float32))
         nsave = self.lib.adt_seq_layer_save_floats(B, L, H, 0)
-        recs, saves = [], []
+        recs, saves = [None] * len(idxs), [None] * len(idxs)
+        live = [k for k, wk in enumerate(ws) if float(wk) != 0.0]      # a zero-weight candidate contributes nothing, forward or backward: it is not run
+        if not live:                                                    # (the kernels read a scale of 0 as "plain store", include/adt_hip.h)
+            y.t.zero_()
         for k, (idx, wk) in enumerate(zip(idxs, ws)):
+            if k not in live:
+                continue
             pre = "encoder.encoder_layers.%d.%d" % (depth, idx)
             st = enc_sites(depth, k)
             save = torch.empty(nsave, device=self.dev, dtype=torch.float32)
             rec = Act(torch.empty(T, H * H, device=self.dev, dtype=torch.float32)) if H > 1 else None
             _lib.check(self.lib.adt_seq_enc_layer_fwd(B, L, H, ops._p(ids), ops._p(x.t), ctypes.byref(self._ptrs("enc", pre, False)), ops._p(self.flat),
                                                       ops._p(self._wimg), float(p), ops._p(self._seed), st["attn"], st["ffn1"], st["ffn2"], tp.b_offset,
-                                                      int(tp.training), ops._p(save), ops._p(y.t), float(wk), int(k > 0),
+                                                      int(tp.training), ops._p(save), ops._p(y.t), float(wk), int(k != live[0]),
                                                       ops._p(rec.t) if rec is not None else None, ops._stream()), "seq_enc_layer_fwd")
-            recs.append(rec)
-            saves.append(save)
+            recs[k], saves[k] = rec, save
 
         def bw():
             if y.g is None and all(r is None or r.g is None for r in recs):
                 return
             gy = y.g if y.g is not None else torch.zeros_like(y.t)
             for k, (idx, wk) in enumerate(zip(idxs, ws)):
+                if k not in live:
+                    continue
                 pre = "encoder.encoder_layers.%d.%d" % (depth, idx)
                 st = enc_sites(depth, k)
                 acc = x.g is not None
@@ -205,16 +211,21 @@ class SuperSASRecModel(FlatModule):
         p = tp.p_eff(self.dropout)
         y = Act(torch.empty(T, self.hidden_units, device=self.dev, dtype=torch.float32))
         nsave = self.lib.adt_seq_layer_save_floats(B, L, H, 1)
-        saves = []
+        saves = [None] * len(idxs)
+        live = [k for k, wk in enumerate(ws) if float(wk) != 0.0]      # as in _enc_layers_fused
+        if not live:
+            y.t.zero_()
         for k, (idx, wk) in enumerate(zip(idxs, ws)):
+            if k not in live:
+                continue
             pre = "decoder.decoder_layers.%d.%d" % (depth, idx)
             st = dec_sites(depth, k)
             save = torch.empty(nsave, device=self.dev, dtype=torch.float32)
             _lib.check(self.lib.adt_seq_dec_layer_fwd(B, L, H, ops._p(ids), ops._p(x.t), ops._p(feats.t), ctypes.byref(self._ptrs("dec", pre, False)),
                                                       ops._p(self.flat), ops._p(self._wimg), float(p), ops._p(self._seed), st["slf"], st["enc"], st["ffn1"],
-                                                      st["ffn2"], tp.b_offset, ops._p(save), ops._p(y.t), float(wk), int(k > 0), ops._stream()),
+                                                      st["ffn2"], tp.b_offset, ops._p(save), ops._p(y.t), float(wk), int(k != live[0]), ops._stream()),
                        "seq_dec_layer_fwd")
-            saves.append(save)
+            saves[k] = save
 
         def bw():
             if y.g is None:
@@ -222,6 +233,8 @@ class SuperSASRecModel(FlatModule):
             if feats.g is None:
                 feats.g = torch.zeros_like(feats.t)
             for k, (idx, wk) in enumerate(zip(idxs, ws)):
+                if k not in live:
+                    continue
                 pre = "decoder.decoder_layers.%d.%d" % (depth, idx)
                 st = dec_sites(depth, k)
                 acc = x.g is not None
@@ -340,7 +353,9 @@ class SuperSASRecModel(FlatModule):
             if fused:
                 x, rk, wk = self._enc_layers_fused(tp, i, x, seq, B)
                 if self.num_heads > 1:
-                    recs.append(tp.log_softmax(tp.mix([(r, float(w)) for r, w in zip(rk, wk)]), self.num_heads))
+                    ran = [(r, float(w)) for r, w in zip(rk, wk) if r is not None]
+                    mixed = tp.mix(ran) if ran else Act(torch.zeros(x.t.shape[0], self.num_heads ** 2, device=self.dev, dtype=torch.float32))
+                    recs.append(tp.log_softmax(mixed, self.num_heads))
                 else:
                     recs.append(Act(torch.zeros(x.t.shape[0], 1, device=self.dev, dtype=torch.float32)))     # log_softmax over one class
                 continue

@@ -534,7 +534,11 @@ int adt_sasrec_probe_dec_layer_fwd(const adt_sasrec_cfg* cfg, const float* param
  * their gradient accumulators in the backward: gradients are ADDED).  wp_base / wp_img: the packed bf16 weight images of the 64x64
  * blocks (adt_pack_wimg over the same flat buffer: image of block W at wp_img + 6 * (W - wp_base) bf16 elements).  `save`: the layer's
  * saved activations (adt_seq_layer_save_floats floats), written by the forward, read by the backward.  y = (y_acc ? y : 0) + y_scale *
- * layer(x): the candidate-mixing epilogue; the backward takes the gradient of the MIXED output and the same scale. */
+ * layer(x): the candidate-mixing epilogue; the backward takes the gradient of the MIXED output and the same scale.
+ * y_scale == 0 and gy_scale == 0 do NOT mean "times zero": they mean scale 1 -- and for y_scale a plain store that ignores y_acc -- the form
+ * the callers without mixing use.  A candidate whose mixing weight is exactly 0 contributes nothing and must not be run at all, forward or
+ * backward (SuperSASRecModel skips it); the first candidate that does run stores (y_acc = 0, gx_acc = 0), the later ones accumulate.
+ * H must be 1, 2 or 4; any other value, an L that adt_seq_layer_supported refuses, returns non-zero with adt_last_error set. */
 typedef struct { float *ln1_w, *ln1_b, *in_w, *in_b, *out_w, *out_b, *ln2_w, *ln2_b, *c1_w, *c1_b, *c2_w, *c2_b, *cls_w, *cls_b; } adt_enc_layer_ptrs;
 typedef struct { float *ln_w, *ln_b, *sin_w, *sin_b, *so_w, *so_b, *ein_w, *ein_b, *eo_w, *eo_b, *c1_w, *c1_b, *c2_w, *c2_b; } adt_dec_layer_ptrs;
 int adt_seq_layer_supported(int prec, int L, int d, int hd);

@@ -108,6 +108,8 @@ def init_params(cfg, seed=0, dtype=np.float32):
 # ----------------------------------------------------------------------------------------------
 # primitives
 _OPERANDS = [None]
+_BIAS_AS_PRODUCT = [False]
+_SAVED_O_BF16 = [False]
 
 
 def bf16_round(x):
@@ -121,23 +123,34 @@ class operands:
     """`with operands("bf16"):` -- every MATRIX product below rounds both operands to bfloat16 first and accumulates in fp32,
     the arithmetic of the MFMA path's bf16 mode.  Everything else (LayerNorm, softmax statistics, dropout,
     residuals, head classifier, logits, losses) stays fp32, as in the kernels.  Default (None): plain fp32, the reference's
-    arithmetic.  Used by the GPU tests to hold the bf16 kernels to a tighter bound than fp32-vs-bf16 rounding noise allows."""
+    arithmetic.  Used by the GPU tests to hold the bf16 kernels to a tighter bound than fp32-vs-bf16 rounding noise allows.
+    `with operands("bf16x64"):` -- the same operand rounding, but the product of the rounded operands is formed in float64: for float64
+    inputs (tests/seq_layer_cases.py) the only roundings left are the operands', so the distance to the plain float64 run is one pass
+    of bf16 operand rounding and nothing else.
+    bias_as_product=True (with either bf16 mode; off by default, so the modes compute what they always did): the gradient of a linear layer's
+    bias is the column sum of the ROUNDED dY, as the per-sequence kernels form it -- a ones column in the X operand image of the dW product
+    (adt_seqpost_tt.cuh, adt_seqbwd_tt.cuh: sb_dw_product) -- instead of the sum of the fp32 dY.
+    saved_o_bf16=True (likewise): the softmax backward's row term delta = sum_j dP_j P_j is formed the way the lean kernels form it, as
+    dO . o from the fp32 dO and the attention output SAVED as bf16 (SeqFwdArgs::saved_bf16; tt_head_delta in adt_tt.cuh) -- the same
+    number in exact arithmetic, one more rounding in theirs, and it sits in a difference (dP - delta) that cancels."""
 
-    def __init__(self, mode):
-        assert mode in (None, "bf16")
-        self.mode = mode
+    def __init__(self, mode, bias_as_product=False, saved_o_bf16=False):
+        assert mode in (None, "bf16", "bf16x64")
+        self.mode, self.bias_as_product, self.saved_o_bf16 = mode, bool(bias_as_product and mode), bool(saved_o_bf16 and mode)
 
     def __enter__(self):
-        self.prev = _OPERANDS[0]
-        _OPERANDS[0] = self.mode
+        self.prev = (_OPERANDS[0], _BIAS_AS_PRODUCT[0], _SAVED_O_BF16[0])
+        _OPERANDS[0], _BIAS_AS_PRODUCT[0], _SAVED_O_BF16[0] = self.mode, self.bias_as_product, self.saved_o_bf16
 
     def __exit__(self, *exc):
-        _OPERANDS[0] = self.prev
+        _OPERANDS[0], _BIAS_AS_PRODUCT[0], _SAVED_O_BF16[0] = self.prev
 
 
 def _mm(a, b):
     if _OPERANDS[0] == "bf16":
         return bf16_round(a) @ bf16_round(b)
+    if _OPERANDS[0] == "bf16x64":
+        return bf16_round(a).astype(np.float64) @ bf16_round(b).astype(np.float64)
     return a @ b
 
 
@@ -185,7 +198,8 @@ def linear_bwd(dy, x, w):
     n = w.shape[0]
     dy2 = dy.reshape(-1, n)
     x2 = x.reshape(-1, w.shape[1])
-    return _mm(dy, w), _mm(dy2.T, x2), dy2.sum(0)
+    db = _mm(np.ones((1, dy2.shape[0]), dy2.dtype), dy2)[0] if _BIAS_AS_PRODUCT[0] else dy2.sum(0)
+    return _mm(dy, w), _mm(dy2.T, x2), db
 
 
 def embed(ids, E, P, p, seed, site, b_offset=0):
@@ -239,7 +253,11 @@ def attention_bwd(do, cache, H):
         dpr = dpd * keep * pr.dtype.type(1.0 / (1.0 - rng.drop_prob(p)))
     else:
         dpr = dpd
-    ds = pr * (dpr - (dpr * pr).sum(-1, keepdims=True))
+    if _SAVED_O_BF16[0]:
+        delta = (doh * bf16_round(_mm(pd, vh)).astype(pr.dtype)).sum(-1, keepdims=True)
+    else:
+        delta = (dpr * pr).sum(-1, keepdims=True)
+    ds = pr * (dpr - delta)
     dqh = _mm(ds, kh) / qh.dtype.type(math.sqrt(hd))
     dkh = _mm(ds.transpose(0, 1, 3, 2), qh)  # qh already carries the 1/sqrt(hd)
     unh = lambda t: t.transpose(0, 2, 1, 3).reshape(B, L, d)
@@ -259,13 +277,16 @@ def ffn(x, w1, b1, w2, b2, p, seed, s1, s2, b_offset=0):
     return f, (x, u, k1, k2, p)
 
 
-def ffn_bwd(df, cache, w1, w2):
+def ffn_bwd(df, cache, w1, w2, gate=None):
+    """gate (optional, boolean like u): the ReLU's derivative taken from there instead of from this run's own u > 0 -- for a comparison with a
+    kernel at the gates the KERNEL's forward saved, so that a pre-activation which rounding puts on the other side of zero is the same
+    on both sides (tests/seq_layer_cases.py; tests/dense_cases.py does the same with the saved U)."""
     x, u, k1, k2, p = cache
     sc = x.dtype.type(1.0 / (1.0 - rng.drop_prob(p))) if p > 0 else x.dtype.type(1.0)
     if k2 is not None:
         df = df * k2 * sc
     du, dw2, db2 = linear_bwd(df, u, w2)
-    dt = du * (u > 0)
+    dt = du * ((u > 0) if gate is None else gate)
     if k1 is not None:
         dt = dt * k1 * sc
     dx, dw1, db1 = linear_bwd(dt, x, w1)
@@ -300,13 +321,13 @@ def encoder_layer(x, m, P, pre, H, p, seed, sites, b_offset):
     return y, rec, dict(x=x, Q=Q, lnc1=lnc1, o=o, ac=ac, lnc2=lnc2, fc=fc, m=m, oh=oh, rec=rec)
 
 
-def encoder_layer_bwd(dy, drec, c, P, pre, H, G):
+def encoder_layer_bwd(dy, drec, c, P, pre, H, G, gate=None):
     d = dy.shape[-1]
     Win = P[pre + "attention_layer.in_proj_weight"]
     g = dy * c["m"]
     dh2 = g
     dx_f, dw1, db1, dw2, db2 = ffn_bwd(g, c["fc"], P[pre + "forward_layer.conv1.weight"][..., 0],
-                                       P[pre + "forward_layer.conv2.weight"][..., 0])
+                                       P[pre + "forward_layer.conv2.weight"][..., 0], gate)
     G[pre + "forward_layer.conv1.weight"] = dw1[..., None]
     G[pre + "forward_layer.conv1.bias"] = db1
     G[pre + "forward_layer.conv2.weight"] = dw2[..., None]
@@ -381,10 +402,10 @@ def decoder_layer(x, enc, m, P, pre, H, p, seed, sites, b_offset):
     return y, dict(lnc=lnc, c1=c1, c2=c2, fc=fc, m=m)
 
 
-def decoder_layer_bwd(dy, c, P, pre, H, G):
+def decoder_layer_bwd(dy, c, P, pre, H, G, gate=None):
     g = dy * c["m"]
     da2_f, dw1, db1, dw2, db2 = ffn_bwd(g, c["fc"], P[pre + "pos_ffn.conv1.weight"][..., 0],
-                                        P[pre + "pos_ffn.conv2.weight"][..., 0])
+                                        P[pre + "pos_ffn.conv2.weight"][..., 0], gate)
     G[pre + "pos_ffn.conv1.weight"] = dw1[..., None]
     G[pre + "pos_ffn.conv1.bias"] = db1
     G[pre + "pos_ffn.conv2.weight"] = dw2[..., None]
