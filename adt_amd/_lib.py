@@ -130,6 +130,21 @@ SIGNATURES = {
     "adt_klattn_long_fwd": (_I, [_I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _P, _U, _U, _P, _I, _P, _I, _P, _P]),
     "adt_klattn_long_bwd": (_I, [_I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F,
                                  _P, _U, _U, _P, _P, _P, _P, _P, _P, _I, _P]),
+    # STOSA-ADT at padded widths: (scale, hd_live) after hd; lane-aware distances; the lane activation pass
+    "adt_wattn_scaled_fwd": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _I, _F, _P, _U, _U, _P, _I, _P, _I, _P, _P]),
+    "adt_wattn_scaled_bwd": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _F,
+                                   _P, _U, _U, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "adt_wattn_mfma_scaled_fwd": (_I, [_I] + [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _I, _F, _P, _U, _U, _P, _I, _P, _I, _P, _P]),
+    "adt_wattn_mfma_scaled_bwd": (_I, [_I] + [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _F,
+                                   _P, _U, _U, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "adt_wattn_long_scaled_fwd": (_I, [_I] + [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _I, _F, _P, _U, _U, _P, _I, _P, _I, _P, _P]),
+    "adt_wattn_long_scaled_bwd": (_I, [_I] + [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _F,
+                                   _P, _U, _U, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "adt_wdist_bpr_lanes": (_I, [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "adt_wdist_full_lanes": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "adt_wdist_pack_lanes": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _F, _P]),
+    "adt_act_lanes_fwd": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _U, _U, _I, _P, _I, _P]),
+    "adt_act_lanes_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _U, _U, _I, _P, _I, _I, _P]),
     "adt_dense_rows_enable": (_I, [_I]),
     "adt_dense_workspace": (_I, [_P, _L]),
     "adt_dense_bwd_ws_bytes": (_L, [_I, _I, _I, _I]),

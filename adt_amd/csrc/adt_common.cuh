@@ -170,6 +170,15 @@ __device__ __forceinline__ float wave_max(float v) {
 ADT_DEVICE_INLINE float w_sqrt_cov(float c) { return sqrtf(fmaxf(c, 1e-24f)); }
 ADT_DEVICE_INLINE float w_elu1(float x) { return (x > 0.f ? x : expf(x) - 1.0f) + 1.0f; }
 
+// The padded layout of a width the kernels do not tile (adt_lanes.cuh): H heads of hd live lanes, head h at columns
+// [h * hd_pad, h * hd_pad + hd) of a row of H * hd_pad floats, hd_pad a power of two.  Here because the STOSA-ADT distance kernels
+// (adt_stosa.cuh, adt_wdist_pack.cuh: two more translation units) skip the pad lanes too.
+struct Lanes {
+  int H, hd, hd_pad, sh;      // sh = log2(hd_pad)
+  __device__ __forceinline__ bool live(int col) const { return (col & (hd_pad - 1)) < hd; }
+  __device__ __forceinline__ int true_col(int col) const { return (col >> sh) * hd + (col & (hd_pad - 1)); }
+};
+
 // wave sum that stays in the vector ALU: four DPP steps inside each row of 16 lanes, then v_permlane16_swap / v_permlane32_swap across the
 // rows (gfx950).  wave_sum above goes through ds_bpermute_b32 six times: a dependent chain of LDS-crossbar round trips.
 __device__ __forceinline__ float wave_sum_valu(float v) {

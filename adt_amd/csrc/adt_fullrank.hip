@@ -86,8 +86,23 @@ int adt_wdist_pack(const float* M, const float* C, int ld, int rows, int d, int 
   if (rows <= 0) return 0;
   if (!M || !C || !img || !nrm) return adt_set_error("wdist_pack: missing operand");
   WPackArgs a{M, C, ld, rows, d, elu != 0, img, ldi, nrm, nrm_scale};
-  hipLaunchKernelGGL(k_wdist_pack, dim3(adt_grid_for((size_t)rows, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_wdist_pack<false>, dim3(adt_grid_for((size_t)rows, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
   return adt_check_launch("wdist_pack");
+}
+
+// adt_wdist_pack on padded rows (d_pad = H * hd_pad columns): the pad lanes of both halves of the image are +0.0 and stay out of the norm
+int adt_wdist_pack_lanes(const float* M, const float* C, int ld, int rows, int H, int hd, int hd_pad, int elu, float* img, int ldi, float* nrm,
+                         float nrm_scale, void* stream) {
+  const int d = H * hd_pad;
+  WPackArgs a{M, C, ld, rows, d, elu != 0, img, ldi, nrm, nrm_scale};
+  if (adt_make_lanes(a.ln, H, hd, hd_pad, "wdist_pack_lanes")) return -1;
+  if (ld < d || ldi < 2 * d) return adt_set_error("wdist_pack_lanes: ld=%d must be >= d_pad=%d and ldi=%d >= 2 d_pad", ld, d, ldi);
+  if ((ld % 4) || (ldi % 4) || !adt_aligned16(M) || !adt_aligned16(C) || !adt_aligned16(img))
+    return adt_set_error("wdist_pack_lanes: M, C and img must be 16-byte aligned with ld %% 4 == 0 and ldi %% 4 == 0");
+  if (rows <= 0) return 0;
+  if (!M || !C || !img || !nrm) return adt_set_error("wdist_pack_lanes: missing operand");
+  hipLaunchKernelGGL(k_wdist_pack<true>, dim3(adt_grid_for((size_t)rows, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("wdist_pack_lanes");
 }
 
 int adt_kldist_pack(const float* Em, const float* Ec, int ld, int V, int d, float* img, int ldi, float* lv, void* stream) {

@@ -28,6 +28,18 @@ static inline int adt_grid_for(size_t work_items, int per_block, int cap) {
 
 static inline bool adt_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
+// Lanes (adt_common.cuh) of a padded layout from the ABI's (H, hd, hd_pad), checked: hd_pad a power of two in 16..256 that holds hd,
+// H * hd_pad one of 64 / 128 / 192 / 256.  0, or -1 with the error set.
+static inline int adt_make_lanes(Lanes& ln, int H, int hd, int hd_pad, const char* what) {
+  int sh = 0;
+  while ((1 << sh) < hd_pad) ++sh;
+  const int dp = H * hd_pad;
+  if (H < 1 || hd < 1 || hd > hd_pad || (1 << sh) != hd_pad || hd_pad < 16 || hd_pad > 256 || (dp % 64) || dp > 256)
+    return adt_set_error("%s: lanes H=%d hd=%d hd_pad=%d: hd_pad a power of two in 16..256, H * hd_pad in {64,128,192,256}", what, H, hd, hd_pad);
+  ln.H = H; ln.hd = hd; ln.hd_pad = hd_pad; ln.sh = sh;
+  return 0;
+}
+
 // Dynamic LDS a kernel has been allowed so far (hipFuncAttributeMaxDynamicSharedMemorySize): one slot per kernel instantiation, kept as a
 // function-local static (or an array of them) by its launcher.  A high-water mark, so a later launch that needs more opts in again.
 struct AdtLdsOptIn { int bytes = 0; };

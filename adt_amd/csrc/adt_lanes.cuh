@@ -13,11 +13,7 @@
 
 namespace adt {
 
-struct Lanes {
-  int H, hd, hd_pad, sh;      // sh = log2(hd_pad)
-  __device__ __forceinline__ bool live(int col) const { return (col & (hd_pad - 1)) < hd; }
-  __device__ __forceinline__ int true_col(int col) const { return (col >> sh) * hd + (col & (hd_pad - 1)); }
-};
+// struct Lanes {H, hd, hd_pad, sh; live(col); true_col(col)}: adt_common.cuh
 
 struct LnLanesArgs {
   const float* X; int ldx;
@@ -363,6 +359,49 @@ __global__ __launch_bounds__(LN_LANES_THREADS) void k_drn_lanes_bwd(DrnLanesArgs
     for (int r = 0; r < rows_per_block; ++r) { s0 += sred[0][r][col]; s1 += sred[1][r][col]; }
     atomicAdd(a.dgamma + col, s0);
     atomicAdd(a.dbeta + col, s1);
+  }
+}
+
+// Activation on padded lanes (STOSA-ADT: ELU after the embedding LayerNorm, ELU + 1 on every covariance -- and ELU(0) + 1 = 1, so the
+// whole-row k_dropact would turn every pad lane into 1):
+//   forward:  Y[t][c] = live(c) ? act(keep(t, c) / (1 - p) * X[t][c]) : +0.0           (act(dropout(x)), the order of k_dropact)
+//   backward: dX[t][c] (+)= live(c) ? dY[t][c] * act'(u) * keep / (1 - p) : +0.0, pad lanes WRITTEN as +0.0 whatever dX or dY held there.
+// keep is indexed at the true width, (t + row_offset) * d + true_col(c), every element hashing for itself (see the head of this file).
+// Elementwise and HBM-bound as k_drop_lanes: one float4 per thread, any d_pad; a (T, n * d_pad) tensor of n padded rows side by side
+// (the q / k / v projections) is n * T rows to this kernel when p = 0.
+struct ActLanesArgs {
+  const float* X; int ldx;
+  const float* dY; int lddy;
+  float* out; int ldo;          // Y, or dX
+  int T; Lanes ln; DropCfg drop; uint32_t row_offset; int act; int acc;
+};
+
+template <bool BWD>
+__global__ __launch_bounds__(256) void k_act_lanes(ActLanesArgs a) {
+  const uint32_t key = drop_key(a.drop);
+  const int dp = a.ln.H * a.ln.hd_pad, d = a.ln.H * a.ln.hd, V = dp / 4;
+  const size_t n = (size_t)a.T * V;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const int t = (int)(i / V), c4 = (int)(i % V) * 4;
+    float x[4], dy[4] = {0.f, 0.f, 0.f, 0.f}, o[4] = {0.f, 0.f, 0.f, 0.f}, v[4];
+    *reinterpret_cast<float4*>(x) = *reinterpret_cast<const float4*>(a.X + (size_t)t * a.ldx + c4);
+    if constexpr (BWD) {
+      *reinterpret_cast<float4*>(dy) = *reinterpret_cast<const float4*>(a.dY + (size_t)t * a.lddy + c4);
+      if (a.acc) *reinterpret_cast<float4*>(o) = *reinterpret_cast<const float4*>(a.out + (size_t)t * a.ldo + c4);
+    }
+    const uint32_t base = (uint32_t)(t + a.row_offset) * (uint32_t)d;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = c4 + j;
+      v[j] = 0.f;
+      if (!a.ln.live(c)) continue;
+      float ks = 1.0f;
+      if (a.drop.thr) ks = adt_keep(key, base + (uint32_t)a.ln.true_col(c), a.drop.thr) ? a.drop.scale : 0.f;
+      const float u = x[j] * ks;
+      if constexpr (BWD) v[j] = o[j] + dy[j] * act_grad(a.act, u) * ks;
+      else v[j] = act_apply(a.act, u);
+    }
+    *reinterpret_cast<float4*>(a.out + (size_t)t * a.ldo + c4) = *reinterpret_cast<float4*>(v);
   }
 }
 

@@ -60,6 +60,10 @@ ADT_DEVICE_INLINE float w_pair_x(const float* qm, const float* qs, const float* 
   return (-wd) / sq_hd;
 }
 
+// sqrt(hd), or 1 / xscale where an entry point gave the scale (padded heads: 1 / sqrt(true head size)).  The forward and the backward
+// take it from here, so both see the same number.
+ADT_DEVICE_INLINE float w_sq_hd(const WAttnArgs& a) { return a.xscale > 0.f ? 1.0f / a.xscale : sqrtf((float)a.hd); }
+
 ADT_DEVICE_INLINE void w_mark_dead(float* sDead, const float* sKv, int L, int Lp) {
   for (int i = threadIdx.x; i < Lp; i += 256) {
     float cnt = 0.f;
@@ -95,7 +99,7 @@ __global__ __launch_bounds__(256) void k_wattn_fwd(WAttnArgs a) {
   float* sQm = sP + 3 * Lp;
   float* sQs = sQm + hd;
   const uint32_t key_rng = drop_key(a.drop);
-  const float sq_hd = sqrtf((float)hd);
+  const float sq_hd = w_sq_hd(a);
   const int nd = 64 / hd >= 1 ? hd : 64;      // lanes along the feature index in the P V step
   const int nparts = 64 / nd;                  // partitions of the key range (hd = 16: 4, 32: 2, 64: 1)
   for (int i = w; i < L; i += 4) {
@@ -175,7 +179,8 @@ __global__ __launch_bounds__(256) void k_wattn_bwd(WAttnArgs a) {
   const int bh = blockIdx.x, b = bh / a.H, h = bh % a.H;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const size_t row_b = (size_t)b * L;
-  const float sq_hd = sqrtf((float)hd);
+  const float sq_hd = w_sq_hd(a);
+  const int hl = a.hd_live > 0 ? a.hd_live : hd;      // lanes at and above hl are zero padding: +0.0 gradients
   const uint32_t key_rng = drop_key(a.drop);
   const uint32_t idx_bh = (uint32_t)(bh + a.bh_offset) * (uint32_t)L;
   const int nd = 64 / hd >= 1 ? hd : 64;
@@ -259,8 +264,9 @@ __global__ __launch_bounds__(256) void k_wattn_bwd(WAttnArgs a) {
       for (int o = nd; o < 64; o <<= 1) { am += __shfl_xor(am, o, 64); as += __shfl_xor(as, o, 64); }
       if (part == 0) {
         // W = |mq|^2 + sum(Sq) + ... - 2 (mq . mk + sqrt(Sq) . sqrt(Sk))
-        a.dQm[(row_b + i) * a.ldd + h * hd + d0] = 2.0f * sV0[d0] * dwsum - 2.0f * am;
-        a.dQc[(row_b + i) * a.ldd + h * hd + d0] = dwsum - (sV1[d0] > 1.00001e-12f ? as / sV1[d0] : 0.f);   // clamp(min=1e-24) gates the sqrt path (cov = 0 exactly -> no gradient)
+        const bool lv = d0 < hl;
+        a.dQm[(row_b + i) * a.ldd + h * hd + d0] = lv ? 2.0f * sV0[d0] * dwsum - 2.0f * am : 0.f;
+        a.dQc[(row_b + i) * a.ldd + h * hd + d0] = lv ? dwsum - (sV1[d0] > 1.00001e-12f ? as / sV1[d0] : 0.f) : 0.f;   // clamp(min=1e-24) gates the sqrt path (cov = 0 exactly -> no gradient)
       }
     }
   }
@@ -323,10 +329,11 @@ __global__ __launch_bounds__(256) void k_wattn_bwd(WAttnArgs a) {
         vm += __shfl_xor(vm, o, 64); vc += __shfl_xor(vc, o, 64);
       }
       if (part == 0) {
-        a.dKm[(row_b + j) * a.ldd + h * hd + d0] = 2.0f * sV0[d0] * dwsum - 2.0f * am;
-        a.dKc[(row_b + j) * a.ldd + h * hd + d0] = dwsum - (sV1[d0] > 1.00001e-12f ? as / sV1[d0] : 0.f);
-        a.dVm[(row_b + j) * a.ldd + h * hd + d0] = vm;
-        a.dVc[(row_b + j) * a.ldd + h * hd + d0] = vc;
+        const bool lv = d0 < hl;
+        a.dKm[(row_b + j) * a.ldd + h * hd + d0] = lv ? 2.0f * sV0[d0] * dwsum - 2.0f * am : 0.f;
+        a.dKc[(row_b + j) * a.ldd + h * hd + d0] = lv ? dwsum - (sV1[d0] > 1.00001e-12f ? as / sV1[d0] : 0.f) : 0.f;
+        a.dVm[(row_b + j) * a.ldd + h * hd + d0] = lv ? vm : 0.f;
+        a.dVc[(row_b + j) * a.ldd + h * hd + d0] = lv ? vc : 0.f;
       }
     }
   }
@@ -342,10 +349,14 @@ struct WBprArgs {
   float* dSm; float* dSc; int ldds;              // overwritten
   float* dEm; float* dEc;                        // accumulated with atomics (rows of id 0 skipped: padding_idx)
   float* loss3;                                  // 3 x 64 slots: bpr, pvn (weighted), auc
+  Lanes ln;                                      // k_wdist_bpr<true> only: d = H * hd_pad, the pad lanes of every row are skipped
 };
 
 ADT_DEVICE_INLINE float w_elu_grad(float x) { return x > 0.f ? 1.f : expf(x); }
 
+// LN: rows are padded (a.ln); a pad lane of the item covariance table is 0, ELU(0) + 1 = 1 against a sequence-side 0, so the pad lanes
+// stay out of the three sums and every gradient gets +0.0 there (the tables' pad lanes receive no atomic at all).
+template <bool LN>
 __global__ __launch_bounds__(256) void k_wdist_bpr(WBprArgs a) {
   const int lane = threadIdx.x & 63;
   const float wgt = *a.inv_count;
@@ -357,6 +368,7 @@ __global__ __launch_bounds__(256) void k_wdist_bpr(WBprArgs a) {
     float dp = 0.f, dn = 0.f, dpn = 0.f;
     if (tgt) {
       for (int c = lane; c < a.d; c += 64) {
+        if (LN && !a.ln.live(c)) continue;
         const float sm = a.Sm[(size_t)t * a.lds + c], ss = w_sqrt_cov(a.Sc[(size_t)t * a.lds + c]);
         const float pm = a.Em[(size_t)ip * a.d + c], ps = w_sqrt_cov(w_elu1(a.Ec[(size_t)ip * a.d + c]));
         const float nm = a.Em[(size_t)in * a.d + c], ns = w_sqrt_cov(w_elu1(a.Ec[(size_t)in * a.d + c]));
@@ -384,7 +396,7 @@ __global__ __launch_bounds__(256) void k_wdist_bpr(WBprArgs a) {
     }
     for (int c = lane; c < a.d; c += 64) {
       float dsm = 0.f, dsc = 0.f;
-      if (tgt) {
+      if (tgt && (!LN || a.ln.live(c))) {
         const float sm = a.Sm[(size_t)t * a.lds + c], ss = w_sqrt_cov(a.Sc[(size_t)t * a.lds + c]);
         const float pe = a.Ec[(size_t)ip * a.d + c], ne = a.Ec[(size_t)in * a.d + c];
         const float pm = a.Em[(size_t)ip * a.d + c], ps = w_sqrt_cov(w_elu1(pe));
@@ -422,8 +434,10 @@ struct WFullArgs {
   const float* Em; const float* Ec;            // V rows; covariance through ELU(.)+1
   int B, V, d;
   float* dist; int ldo;
+  Lanes ln;                                    // k_wdist_full<true> only: d = H * hd_pad, pad lanes skipped
 };
 
+template <bool LN>
 __global__ __launch_bounds__(256) void k_wdist_full(WFullArgs a) {
   const int sub = threadIdx.x & 15;
   const size_t n = (size_t)a.B * a.V;
@@ -433,6 +447,7 @@ __global__ __launch_bounds__(256) void k_wdist_full(WFullArgs a) {
     for (int c4 = 4 * sub; c4 < a.d; c4 += 64) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
+        if (LN && !a.ln.live(c4 + e)) continue;
         const float sm = a.Sm[(size_t)b * a.lds + c4 + e], sc = a.Sc[(size_t)b * a.lds + c4 + e];
         const float em = a.Em[(size_t)v * a.d + c4 + e], ec = w_elu1(a.Ec[(size_t)v * a.d + c4 + e]);
         dm += sm * em;

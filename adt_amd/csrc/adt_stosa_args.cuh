@@ -18,6 +18,10 @@ struct WAttnArgs {
   float* LSE;                // (B*H*L)
   const float* dOm; int lddom; const float* dOc; int lddoc;
   float *dQm, *dQc, *dKm, *dKc, *dVm, *dVc; int ldd;   // gradients (T x ldd), overwritten
+  // Padded heads (the adt_wattn_*_scaled_* entry points; both 0 everywhere else): xscale > 0 replaces 1 / sqrt(hd) as the score scale in
+  // the forward and both backward passes alike; hd_live > 0: only lanes [0, hd_live) of a head are live, the zero pad lanes above them
+  // get a +0.0 gradient (sum(cov) has gradient 1 at cov = 0, so dQc / dKc would otherwise carry sum_j dW there).
+  float xscale; int hd_live;
 };
 
 constexpr float W_MASK = -4294967296.0f;   // float32(-2**32 + 1), stosa/models.py:226,230

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_fwd(WAttnArgs a) {
   const int g0 = blockIdx.y * WM_NW * 16;      // the group's first query
   const int kend = (g0 < first || g0 + WM_NW * 16 > L) ? L : g0 + WM_NW * 16;
   const uint32_t key_rng = drop_key(a.drop);
-  const float rsq_hd = 1.0f / sqrtf((float)HD);
+  const float rsq_hd = a.xscale > 0.f ? a.xscale : 1.0f / sqrtf((float)HD);      // xscale: the scaled entry points (padded heads)
   const uint32_t idx_q = ((uint32_t)(bh + a.bh_offset) * (uint32_t)L + (uint32_t)i) * (uint32_t)L;
   f32x4 om[S::NT], oc[S::NT];
 #pragma unroll
@@ -190,7 +190,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int L = a.L, co = h * HD;
   const size_t row_b = (size_t)b * L;
-  const float rsq_hd = 1.0f / sqrtf((float)HD);
+  const float rsq_hd = a.xscale > 0.f ? a.xscale : 1.0f / sqrtf((float)HD);      // xscale: the scaled entry points (padded heads)
   const uint32_t key_rng = drop_key(a.drop);
   const uint32_t idx_bh = (uint32_t)(bh + a.bh_offset) * (uint32_t)L;
   for (int i = threadIdx.x; i < ATTN_LONG_LMAX; i += WM_NW * 64) {
@@ -340,8 +340,8 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
           const float s0 = w_sqrt_cov(qc.x), s1 = w_sqrt_cov(qc.y), s2 = w_sqrt_cov(qc.z), s3 = w_sqrt_cov(qc.w);
           // clamp(min = 1e-24) gates the sqrt path (cov = 0 exactly -> no gradient)
           *reinterpret_cast<float4*>(a.dQc + qrow * a.ldd + co + k0 - HD) =
-              make_float4(dwsum - (s0 > 1.00001e-12f ? acc[0] / s0 : 0.f), dwsum - (s1 > 1.00001e-12f ? acc[1] / s1 : 0.f),
-                          dwsum - (s2 > 1.00001e-12f ? acc[2] / s2 : 0.f), dwsum - (s3 > 1.00001e-12f ? acc[3] / s3 : 0.f));
+              make_float4(wm_live(a, k0 - HD) ? dwsum - (s0 > 1.00001e-12f ? acc[0] / s0 : 0.f) : 0.f, wm_live(a, k0 - HD + 1) ? dwsum - (s1 > 1.00001e-12f ? acc[1] / s1 : 0.f) : 0.f,
+                          wm_live(a, k0 - HD + 2) ? dwsum - (s2 > 1.00001e-12f ? acc[2] / s2 : 0.f) : 0.f, wm_live(a, k0 - HD + 3) ? dwsum - (s3 > 1.00001e-12f ? acc[3] / s3 : 0.f) : 0.f);
         }
       }
     }
@@ -483,8 +483,8 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
           const float4 kc = *reinterpret_cast<const float4*>(a.Kc + krow * a.ldkc + co + k0 - HD);
           const float s0 = w_sqrt_cov(kc.x), s1 = w_sqrt_cov(kc.y), s2 = w_sqrt_cov(kc.z), s3 = w_sqrt_cov(kc.w);
           *reinterpret_cast<float4*>(a.dKc + krow * a.ldd + co + k0 - HD) =
-              make_float4(dwsum - (s0 > 1.00001e-12f ? acc[0] / s0 : 0.f), dwsum - (s1 > 1.00001e-12f ? acc[1] / s1 : 0.f),
-                          dwsum - (s2 > 1.00001e-12f ? acc[2] / s2 : 0.f), dwsum - (s3 > 1.00001e-12f ? acc[3] / s3 : 0.f));
+              make_float4(wm_live(a, k0 - HD) ? dwsum - (s0 > 1.00001e-12f ? acc[0] / s0 : 0.f) : 0.f, wm_live(a, k0 - HD + 1) ? dwsum - (s1 > 1.00001e-12f ? acc[1] / s1 : 0.f) : 0.f,
+                          wm_live(a, k0 - HD + 2) ? dwsum - (s2 > 1.00001e-12f ? acc[2] / s2 : 0.f) : 0.f, wm_live(a, k0 - HD + 3) ? dwsum - (s3 > 1.00001e-12f ? acc[3] / s3 : 0.f) : 0.f);
         }
       }
     }

@@ -52,20 +52,22 @@ static int wattn_long(int prec, bool bwd, const WAttnArgs& a, float p, uint32_t 
 
 static WAttnArgs wattn_long_args(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
                                  const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float p,
-                                 const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE) {
+                                 const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE, float xscale, int hd_live) {
   WAttnArgs a{};
   a.Qm = Qm; a.ldqm = ldqm; a.Qc = Qc; a.ldqc = ldqc; a.Km = Km; a.ldkm = ldkm; a.Kc = Kc; a.ldkc = ldkc; a.Vm = Vm; a.ldvm = ldvm;
   a.Vc = Vc; a.ldvc = ldvc; a.kid = key_ids; a.B = B; a.H = H; a.L = L; a.hd = hd; a.scale = 1.0f / sqrtf((float)(hd > 0 ? hd : 1));
   a.drop = adt_make_drop(p, seed, site); a.bh_offset = b_offset * (uint32_t)H; a.Om = Om; a.ldom = ldom; a.Oc = Oc; a.ldoc = ldoc; a.LSE = LSE;
+  a.xscale = xscale; a.hd_live = hd_live;      // 0, 0: the scale and the live lanes follow hd
   return a;
 }
 
 template <int MET>
 static int wattn_long_fwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
                           const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float p,
-                          const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE, void* stream) {
+                          const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE, void* stream,
+                          float xscale = 0.f, int hd_live = 0) {
   const WAttnArgs a = wattn_long_args(Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, B, H, L, hd, p, seed, site, b_offset, Om, ldom,
-                                      Oc, ldoc, LSE);
+                                      Oc, ldoc, LSE, xscale, hd_live);
   const int lds[8] = {ldqm, ldqc, ldkm, ldkc, ldvm, ldvc, ldom, ldoc};
   return wattn_long<MET>(prec, false, a, p, b_offset, lds, 8, stream);
 }
@@ -75,9 +77,9 @@ static int wattn_long_bwd(int prec, const float* Qm, int ldqm, const float* Qc, 
                           const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc,
                           int ldoc, const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd, float p,
                           const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc, float* dKm, float* dKc, float* dVm,
-                          float* dVc, int ldd, void* stream) {
+                          float* dVc, int ldd, void* stream, float xscale = 0.f, int hd_live = 0) {
   WAttnArgs a = wattn_long_args(Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, B, H, L, hd, p, seed, site, b_offset,
-                                const_cast<float*>(Om), ldom, const_cast<float*>(Oc), ldoc, const_cast<float*>(LSE));
+                                const_cast<float*>(Om), ldom, const_cast<float*>(Oc), ldoc, const_cast<float*>(LSE), xscale, hd_live);
   a.dOm = dOm; a.lddom = lddom; a.dOc = dOc; a.lddoc = lddoc;
   a.dQm = dQm; a.dQc = dQc; a.dKm = dKm; a.dKc = dKc; a.dVm = dVm; a.dVc = dVc; a.ldd = ldd;
   const int lds[11] = {ldqm, ldqc, ldkm, ldkc, ldvm, ldvc, ldom, ldoc, lddom, lddoc, ldd};
@@ -114,6 +116,27 @@ int adt_wattn_long_bwd(int prec, const float* Qm, int ldqm, const float* Qc, int
                        float* dVc, int ldd, void* stream) {
   return wattn_long_bwd<WM_W>(prec, Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, Om, ldom, Oc, ldoc, LSE, dOm, lddom, dOc, lddoc,
                               B, H, L, hd, p, seed, site, b_offset, dQm, dQc, dKm, dKc, dVm, dVc, ldd, stream);
+}
+
+// Padded heads: the score scale is given (1 / sqrt(true head size)) and only lanes [0, hd_live) of a head are live; everything else as
+// adt_wattn_long_fwd / _bwd.  The forward and the backward must be given the same scale.
+int adt_wattn_long_scaled_fwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                              const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float scale,
+                              int hd_live, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc,
+                              float* LSE, void* stream) {
+  if (!(scale > 0.f) || hd_live < 1 || hd_live > hd) return adt_set_error("wattn_long_scaled_fwd: scale %g must be positive and 1 <= hd_live=%d <= hd=%d", (double)scale, hd_live, hd);
+  return wattn_long_fwd<WM_W>(prec, Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, B, H, L, hd, p, seed, site, b_offset, Om, ldom,
+                              Oc, ldoc, LSE, stream, scale, hd_live);
+}
+
+int adt_wattn_long_scaled_bwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                              const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc,
+                              int ldoc, const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd,
+                              float scale, int hd_live, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc,
+                              float* dKm, float* dKc, float* dVm, float* dVc, int ldd, void* stream) {
+  if (!(scale > 0.f) || hd_live < 1 || hd_live > hd) return adt_set_error("wattn_long_scaled_bwd: scale %g must be positive and 1 <= hd_live=%d <= hd=%d", (double)scale, hd_live, hd);
+  return wattn_long_bwd<WM_W>(prec, Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, Om, ldom, Oc, ldoc, LSE, dOm, lddom, dOc, lddoc,
+                              B, H, L, hd, p, seed, site, b_offset, dQm, dQc, dKm, dKc, dVm, dVc, ldd, stream, scale, hd_live);
 }
 
 int adt_klattn_long_fwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,

@@ -265,7 +265,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_fwd(WAttnArgs a) {
   }
   __syncthreads();
   const uint32_t key_rng = drop_key(a.drop);
-  const float rsq_hd = 1.0f / sqrtf((float)HD);
+  const float rsq_hd = a.xscale > 0.f ? a.xscale : 1.0f / sqrtf((float)HD);      // xscale: the scaled entry points (padded heads)
   for (int qt = w; qt < nt16; qt += WM_NW) {
     const int i = qt * 16 + c;
     const bool vi = i < L;
@@ -360,6 +360,10 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_fwd(WAttnArgs a) {
 // delta_i = sum_j P_ij dP_ij needs no sweep of its own: with P~ = P * keep, sum_j P_ij dP_ij = dOm_i . Om_i + 2 dOc_i . Oc_i (the saved
 // contexts), so each pass makes ONE sweep over the other side in pairs of 16-row tiles, turns each pair of dW / P~ tiles straight into
 // MFMA operands and keeps only the output accumulators (the first version held every tile of a sweep: 299 registers, one wave per SIMD).
+// lane f of a head is live (hd_live = 0: every lane).  The pad lanes of a padded head hold cov = 0, where the sqrt path is gated but
+// sum(cov) still has gradient 1: without this dQc / dKc would carry sum_j dW on them.
+ADT_DEVICE_INLINE bool wm_live(const WAttnArgs& a, int f) { return a.hd_live <= 0 || f < a.hd_live; }
+
 template <int HD>
 ADT_DEVICE_INLINE void wm_pair_bwd(float x, bool masked, bool dead_row, float lse, float ks_, float gm, float gc, float delta, float rsq_hd,
                                    float& dw, float& pd) {
@@ -390,7 +394,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
   const int bh = blockIdx.x, b = bh / a.H, h = bh % a.H;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const size_t row_b = (size_t)b * L;
-  const float rsq_hd = 1.0f / sqrtf((float)HD);
+  const float rsq_hd = a.xscale > 0.f ? a.xscale : 1.0f / sqrtf((float)HD);      // xscale: the scaled entry points (padded heads)
   const uint32_t key_rng = drop_key(a.drop);
   const uint32_t idx_bh = (uint32_t)(bh + a.bh_offset) * (uint32_t)L;
   for (int i = threadIdx.x; i < Lp; i += WM_NW * 64) {
@@ -531,8 +535,8 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
           const float s0 = w_sqrt_cov(qc.x), s1 = w_sqrt_cov(qc.y), s2 = w_sqrt_cov(qc.z), s3 = w_sqrt_cov(qc.w);
           // clamp(min = 1e-24) gates the sqrt path (cov = 0 exactly -> no gradient)
           *reinterpret_cast<float4*>(a.dQc + qrow * a.ldd + h * HD + k0 - HD) =
-              make_float4(dwsum - (s0 > 1.00001e-12f ? acc[0] / s0 : 0.f), dwsum - (s1 > 1.00001e-12f ? acc[1] / s1 : 0.f),
-                          dwsum - (s2 > 1.00001e-12f ? acc[2] / s2 : 0.f), dwsum - (s3 > 1.00001e-12f ? acc[3] / s3 : 0.f));
+              make_float4(wm_live(a, k0 - HD) ? dwsum - (s0 > 1.00001e-12f ? acc[0] / s0 : 0.f) : 0.f, wm_live(a, k0 - HD + 1) ? dwsum - (s1 > 1.00001e-12f ? acc[1] / s1 : 0.f) : 0.f,
+                          wm_live(a, k0 - HD + 2) ? dwsum - (s2 > 1.00001e-12f ? acc[2] / s2 : 0.f) : 0.f, wm_live(a, k0 - HD + 3) ? dwsum - (s3 > 1.00001e-12f ? acc[3] / s3 : 0.f) : 0.f);
         }
       }
     }
@@ -669,8 +673,8 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
           const float4 kc = *reinterpret_cast<const float4*>(a.Kc + krow * a.ldkc + h * HD + k0 - HD);
           const float s0 = w_sqrt_cov(kc.x), s1 = w_sqrt_cov(kc.y), s2 = w_sqrt_cov(kc.z), s3 = w_sqrt_cov(kc.w);
           *reinterpret_cast<float4*>(a.dKc + krow * a.ldd + h * HD + k0 - HD) =
-              make_float4(dwsum - (s0 > 1.00001e-12f ? acc[0] / s0 : 0.f), dwsum - (s1 > 1.00001e-12f ? acc[1] / s1 : 0.f),
-                          dwsum - (s2 > 1.00001e-12f ? acc[2] / s2 : 0.f), dwsum - (s3 > 1.00001e-12f ? acc[3] / s3 : 0.f));
+              make_float4(wm_live(a, k0 - HD) ? dwsum - (s0 > 1.00001e-12f ? acc[0] / s0 : 0.f) : 0.f, wm_live(a, k0 - HD + 1) ? dwsum - (s1 > 1.00001e-12f ? acc[1] / s1 : 0.f) : 0.f,
+                          wm_live(a, k0 - HD + 2) ? dwsum - (s2 > 1.00001e-12f ? acc[2] / s2 : 0.f) : 0.f, wm_live(a, k0 - HD + 3) ? dwsum - (s3 > 1.00001e-12f ? acc[3] / s3 : 0.f) : 0.f);
         }
       }
     }

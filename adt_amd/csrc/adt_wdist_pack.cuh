@@ -20,8 +20,12 @@ struct WPackArgs {
   int rows, d, elu;
   float* img; int ldi;                         // rows x 2d, row stride ldi
   float* nrm; float nrm_scale;                 // rows
+  Lanes ln;                                    // k_wdist_pack<true> only: d = H * hd_pad; pad lanes of both halves of the image are +0.0
 };
 
+// LN: padded rows.  ELU(0) + 1 = 1 and sqrt(max(0, 1e-24)) = 1e-12 on a pad lane; the image and the norm take live lanes only, so the
+// ranking kernel, which knows nothing of lanes, sees zeros there.
+template <bool LN>
 __global__ __launch_bounds__(256) void k_wdist_pack(WPackArgs a) {
   const int sub = threadIdx.x & 15;
   for (int r = blockIdx.x * 16 + (threadIdx.x >> 4); r < a.rows; r += gridDim.x * 16) {      // the 16 lanes of a row share r
@@ -33,10 +37,16 @@ __global__ __launch_bounds__(256) void k_wdist_pack(WPackArgs a) {
       const float4 mv = *reinterpret_cast<const float4*>(m + c4);
       float4 cv = *reinterpret_cast<const float4*>(c + c4);
       if (a.elu) cv = make_float4(w_elu1(cv.x), w_elu1(cv.y), w_elu1(cv.z), w_elu1(cv.w));
+      float4 sv = make_float4(w_sqrt_cov(cv.x), w_sqrt_cov(cv.y), w_sqrt_cov(cv.z), w_sqrt_cov(cv.w));
+      if constexpr (LN) {
+        const bool l0 = a.ln.live(c4), l1 = a.ln.live(c4 + 1), l2 = a.ln.live(c4 + 2), l3 = a.ln.live(c4 + 3);
+        cv = make_float4(l0 ? cv.x : 0.f, l1 ? cv.y : 0.f, l2 ? cv.z : 0.f, l3 ? cv.w : 0.f);
+        sv = make_float4(l0 ? sv.x : 0.f, l1 ? sv.y : 0.f, l2 ? sv.z : 0.f, l3 ? sv.w : 0.f);
+      }
       pm += mv.x * mv.x; pm += mv.y * mv.y; pm += mv.z * mv.z; pm += mv.w * mv.w;
       pc += cv.x; pc += cv.y; pc += cv.z; pc += cv.w;
       *reinterpret_cast<float4*>(o + c4) = mv;
-      *reinterpret_cast<float4*>(o + a.d + c4) = make_float4(w_sqrt_cov(cv.x), w_sqrt_cov(cv.y), w_sqrt_cov(cv.z), w_sqrt_cov(cv.w));
+      *reinterpret_cast<float4*>(o + a.d + c4) = sv;
     }
 #pragma unroll
     for (int s = 8; s > 0; s >>= 1) {

@@ -599,7 +599,7 @@ int adt_wdist_bpr(const float* Sm, const float* Sc, int lds, const float* Em, co
                   void* stream) {
   if (d % 64) return adt_set_error("wdist_bpr: d=%d must be a multiple of 64", d);
   WBprArgs a{Sm, Sc, lds, Em, Ec, pos, neg, T, d, pvn_weight, inv_count, dSm, dSc, ldds, dEm, dEc, loss3};
-  hipLaunchKernelGGL(k_wdist_bpr, dim3(adt_grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_wdist_bpr<false>, dim3(adt_grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, a);
   return adt_check_launch("wdist_bpr");
 }
 
@@ -607,7 +607,7 @@ int adt_wdist_full(const float* Sm, const float* Sc, int lds, const float* Em, c
                    void* stream) {
   if (d % 4) return adt_set_error("wdist_full: d %% 4");
   WFullArgs a{Sm, Sc, lds, Em, Ec, B, V, d, dist, ldo};
-  hipLaunchKernelGGL(k_wdist_full, dim3(adt_grid_for((size_t)B * V, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_wdist_full<false>, dim3(adt_grid_for((size_t)B * V, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
   return adt_check_launch("wdist_full");
 }
 
@@ -656,15 +656,7 @@ int adt_dense_gradsrc(const float* dY, int lddy, int T, int N, const int32_t* ma
 }  // extern "C"
 
 // ---- widths that are not multiples of 64: padded lanes, true-width arithmetic (adt_lanes.cuh) -----------------------------------------
-static int make_lanes(Lanes& ln, int H, int hd, int hd_pad, const char* what) {
-  int sh = 0;
-  while ((1 << sh) < hd_pad) ++sh;
-  const int dp = H * hd_pad;
-  if (H < 1 || hd < 1 || hd > hd_pad || (1 << sh) != hd_pad || hd_pad < 16 || hd_pad > 256 || (dp % 64) || dp > 256)
-    return adt_set_error("%s: lanes H=%d hd=%d hd_pad=%d: hd_pad a power of two in 16..256, H * hd_pad in {64,128,192,256}", what, H, hd, hd_pad);
-  ln.H = H; ln.hd = hd; ln.hd_pad = hd_pad; ln.sh = sh;
-  return 0;
-}
+static int make_lanes(Lanes& ln, int H, int hd, int hd_pad, const char* what) { return adt_make_lanes(ln, H, hd, hd_pad, what); }
 
 template <typename K64, typename K128, typename K192, typename K256, typename Args>
 static void launch_by_width(int dp, K64 k64, K128 k128, K192 k192, K256 k256, int grid, hipStream_t s, const Args& a) {
@@ -777,6 +769,110 @@ int adt_attn_masked_scaled_bwd(int prec, const float* Q, int ldq, const float* K
   if (!(scale > 0.f)) return adt_set_error("attn_masked_scaled_bwd: scale %g must be positive", (double)scale);
   return attn_masked_bwd_impl(prec, Q, ldq, K, ldk, V, ldv, O, ldo, LSE, dO, lddo, B, H, L, hd, scale, causal, key_ids, fill, p, seed, site, b_offset,
                               dQ, lddq, dK, lddk, dV, lddv, stream);
+}
+
+// ---- STOSA-ADT at padded widths --------------------------------------------------------------------------------
+// The Wasserstein attention with the score scale given (1 / sqrt(true head size)) and only lanes [0, hd_live) of a head live: arguments
+// as adt_wattn_fwd / _bwd and adt_wattn_mfma_fwd / _bwd with (scale, hd_live) after hd.  The forward and the backward take the same scale.
+static int wattn_scaled_check(const char* what, float scale, int hd_live, int hd) {
+  if (!(scale > 0.f) || hd_live < 1 || hd_live > hd) return adt_set_error("%s: scale %g must be positive and 1 <= hd_live=%d <= hd=%d", what, (double)scale, hd_live, hd);
+  return 0;
+}
+
+int adt_wattn_scaled_fwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                         const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float scale,
+                         int hd_live, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc,
+                         float* LSE, void* stream) {
+  if (wattn_scaled_check("wattn_scaled_fwd", scale, hd_live, hd)) return -1;
+  WAttnArgs a = make_wattn_args(Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, B, H, L, hd, p, seed, site, b_offset, Om, ldom, Oc, ldoc, LSE);
+  a.xscale = scale; a.hd_live = hd_live;
+  return stosa_attn<WM_W>(false, a, stream);
+}
+
+int adt_wattn_scaled_bwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                         const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc,
+                         int ldoc, const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd,
+                         float scale, int hd_live, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc,
+                         float* dKm, float* dKc, float* dVm, float* dVc, int ldd, void* stream) {
+  if (wattn_scaled_check("wattn_scaled_bwd", scale, hd_live, hd)) return -1;
+  WAttnArgs a = make_wattn_args_bwd(Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, Om, ldom, Oc, ldoc, LSE, dOm, lddom, dOc, lddoc,
+                                    B, H, L, hd, p, seed, site, b_offset, dQm, dQc, dKm, dKc, dVm, dVc, ldd);
+  a.xscale = scale; a.hd_live = hd_live;
+  return stosa_attn<WM_W>(true, a, stream);
+}
+
+int adt_wattn_mfma_scaled_fwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                              const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float scale,
+                              int hd_live, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc,
+                              float* LSE, void* stream) {
+  if (wattn_scaled_check("wattn_mfma_scaled_fwd", scale, hd_live, hd)) return -1;
+  WAttnArgs a = make_wattn_args(Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, B, H, L, hd, p, seed, site, b_offset, Om, ldom, Oc, ldoc, LSE);
+  a.xscale = scale; a.hd_live = hd_live;
+  return wattn_mfma_dispatch<WM_W>(prec, false, a, (hipStream_t)stream);
+}
+
+int adt_wattn_mfma_scaled_bwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                              const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc,
+                              int ldoc, const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd,
+                              float scale, int hd_live, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc,
+                              float* dKm, float* dKc, float* dVm, float* dVc, int ldd, void* stream) {
+  if (wattn_scaled_check("wattn_mfma_scaled_bwd", scale, hd_live, hd)) return -1;
+  WAttnArgs a = make_wattn_args_bwd(Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, Om, ldom, Oc, ldoc, LSE, dOm, lddom, dOc, lddoc,
+                                    B, H, L, hd, p, seed, site, b_offset, dQm, dQc, dKm, dKc, dVm, dVc, ldd);
+  a.xscale = scale; a.hd_live = hd_live;
+  return wattn_mfma_dispatch<WM_W>(prec, true, a, (hipStream_t)stream);
+}
+
+// adt_wdist_bpr / adt_wdist_full on padded rows and tables (d_pad = H * hd_pad columns each): the pad lanes stay out of every sum, and
+// dSm / dSc get +0.0 there; the tables' pad lanes receive no atomic.
+int adt_wdist_bpr_lanes(const float* Sm, const float* Sc, int lds, const float* Em, const float* Ec, const int32_t* pos, const int32_t* neg, int T,
+                        int H, int hd, int hd_pad, float pvn_weight, const float* inv_count, float* dSm, float* dSc, int ldds, float* dEm, float* dEc,
+                        float* loss3, void* stream) {
+  WBprArgs a{Sm, Sc, lds, Em, Ec, pos, neg, T, H * hd_pad, pvn_weight, inv_count, dSm, dSc, ldds, dEm, dEc, loss3};
+  if (make_lanes(a.ln, H, hd, hd_pad, "wdist_bpr_lanes")) return -1;
+  if (lds < a.d || ldds < a.d) return adt_set_error("wdist_bpr_lanes: lds=%d and ldds=%d must be >= d_pad=%d", lds, ldds, a.d);
+  hipLaunchKernelGGL(k_wdist_bpr<true>, dim3(adt_grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("wdist_bpr_lanes");
+}
+
+int adt_wdist_full_lanes(const float* Sm, const float* Sc, int lds, const float* Em, const float* Ec, int B, int V, int H, int hd, int hd_pad,
+                         float* dist, int ldo, void* stream) {
+  WFullArgs a{Sm, Sc, lds, Em, Ec, B, V, H * hd_pad, dist, ldo};
+  if (make_lanes(a.ln, H, hd, hd_pad, "wdist_full_lanes")) return -1;
+  if (lds < a.d || ldo < V) return adt_set_error("wdist_full_lanes: lds=%d must be >= d_pad=%d and ldo=%d >= V=%d", lds, a.d, ldo, V);
+  if (B <= 0 || V <= 0) return 0;
+  hipLaunchKernelGGL(k_wdist_full<true>, dim3(adt_grid_for((size_t)B * V, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("wdist_full_lanes");
+}
+
+// Activation (with its dropout site) on padded lanes: adt_lanes.cuh, k_act_lanes
+int adt_act_lanes_fwd(const float* X, int ldx, int T, int H, int hd, int hd_pad, float p, const uint32_t* seed, uint32_t site, uint32_t row_offset,
+                      int act, float* Y, int ldy, void* stream) {
+  ActLanesArgs a{};
+  if (make_lanes(a.ln, H, hd, hd_pad, "act_lanes_fwd")) return -1;
+  if (T <= 0) return 0;
+  const int dp = H * hd_pad;
+  if (!X || !Y) return adt_set_error("act_lanes_fwd: X and Y are required");
+  if ((ldx % 4) || (ldy % 4) || ldx < dp || ldy < dp || !adt_aligned16(X) || !adt_aligned16(Y))
+    return adt_set_error("act_lanes_fwd: ld %% 4, ld >= d_pad and 16-byte alignment required");
+  a.X = X; a.ldx = ldx; a.out = Y; a.ldo = ldy; a.T = T; a.drop = adt_make_drop(p, seed, site); a.row_offset = row_offset; a.act = act;
+  hipLaunchKernelGGL(k_act_lanes<false>, dim3(adt_grid_for((size_t)T * (dp / 4), 1024, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("act_lanes_fwd");
+}
+
+int adt_act_lanes_bwd(const float* dY, int lddy, const float* X, int ldx, int T, int H, int hd, int hd_pad, float p, const uint32_t* seed,
+                      uint32_t site, uint32_t row_offset, int act, float* dX, int lddx, int accumulate, void* stream) {
+  ActLanesArgs a{};
+  if (make_lanes(a.ln, H, hd, hd_pad, "act_lanes_bwd")) return -1;
+  if (T <= 0) return 0;
+  const int dp = H * hd_pad;
+  if (!dY || !X || !dX) return adt_set_error("act_lanes_bwd: dY, X and dX are required");
+  if ((ldx % 4) || (lddy % 4) || (lddx % 4) || ldx < dp || lddy < dp || lddx < dp || !adt_aligned16(X) || !adt_aligned16(dY) || !adt_aligned16(dX))
+    return adt_set_error("act_lanes_bwd: ld %% 4, ld >= d_pad and 16-byte alignment required");
+  a.X = X; a.ldx = ldx; a.dY = dY; a.lddy = lddy; a.out = dX; a.ldo = lddx; a.acc = accumulate; a.T = T;
+  a.drop = adt_make_drop(p, seed, site); a.row_offset = row_offset; a.act = act;
+  hipLaunchKernelGGL(k_act_lanes<true>, dim3(adt_grid_for((size_t)T * (dp / 4), 1024, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("act_lanes_bwd");
 }
 
 }  // extern "C"

@@ -99,7 +99,13 @@ class DistRankMixin:
         weight update -- so a caller that ranks many batches under the same weights holds on to it and passes it as `image`."""
         self._check_wasserstein()
         Em, Ec, _ = self._dist_tables()
-        return ops.wdist_pack(Em, Ec, True, -0.5)
+        return self._wdist_pack(Em, Ec, True, -0.5)
+
+    def _wdist_pack(self, M, C, elu, nrm_scale):
+        """ops.wdist_pack, lane-aware for a model at a padded width (model.lanes): ELU(0) + 1 = 1 on a pad lane of
+        the item covariances must not reach the image; with zero pad columns on both sides the ranking kernel needs no change."""
+        lanes = getattr(self, "lanes", None)
+        return ops.wdist_pack(M, C, elu, nrm_scale) if lanes is None else ops.wdist_pack_lanes(M, C, elu, nrm_scale, lanes)
 
     @torch.no_grad()
     def kl_row_image(self):
@@ -118,7 +124,7 @@ class DistRankMixin:
             image = self.kl_row_image() if kl else self.item_image()
         W, bias = image
         n_items = self._dist_tables()[2]
-        A, na = ops.klrow_pack(sm, sc, False) if kl else ops.wdist_pack(sm, sc, False, 1.0)
+        A, na = ops.klrow_pack(sm, sc, False) if kl else self._wdist_pack(sm, sc, False, 1.0)
         B = A.shape[0]
         indptr, indices = _seen(seen, B, A.device)
         rank, n_elig, top_idx, top_val = ops.full_rank(A, A.stride(0), W, n_items, _targets(targets, B, A.device), bias, indptr, indices, topk,

@@ -408,26 +408,27 @@ def _stosa_attn_call(mfma, valu, args, prec):
     _lib.check(getattr(lib, "adt_" + valu)(*args), valu)
 
 
-def _stosa_attn_fwd(mfma, valu, Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, site, b_offset, prec):
+def _stosa_attn_fwd(mfma, valu, Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, site, b_offset, prec, scaled=()):
+    """scaled: () or (scale, hd_live), the two arguments the *_scaled_* entry points take after hd."""
     d = Qm.shape[1]
     hd = d // H
     Om = torch.empty(B * L, d, device=Qm.device, dtype=torch.float32)
     Oc = torch.empty_like(Om)
     LSE = torch.empty(B * H * L, device=Qm.device, dtype=torch.float32)
     args = [_p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc), _p(_f32(Vm)), _ld(Vm), _p(_f32(Vc)), _ld(Vc),
-            _p(_i32(key_ids)), B, H, L, hd, float(p), _p(seed), site, b_offset, _p(Om), d, _p(Oc), d, _p(LSE), _stream()]
+            _p(_i32(key_ids)), B, H, L, hd, *scaled, float(p), _p(seed), site, b_offset, _p(Om), d, _p(Oc), d, _p(LSE), _stream()]
     _stosa_attn_call(mfma, valu, args, prec)
     return Om, Oc, LSE
 
 
-def _stosa_attn_bwd(mfma, valu, Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site, b_offset, out, prec):
+def _stosa_attn_bwd(mfma, valu, Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site, b_offset, out, prec, scaled=()):
     d = Qm.shape[1]
     hd = d // H
     outs = [torch.empty(B * L, d, device=Qm.device, dtype=torch.float32) for _ in range(6)] if out is None else list(out)
     ldd = _ld(outs[0])
     assert all(_ld(o) == ldd for o in outs)
     args = [_p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc), _p(_f32(Vm)), _ld(Vm), _p(_f32(Vc)), _ld(Vc),
-            _p(_i32(key_ids)), _p(Om), _ld(Om), _p(Oc), _ld(Oc), _p(LSE), _p(_f32(dOm)), _ld(dOm), _p(_f32(dOc)), _ld(dOc), B, H, L, hd, float(p),
+            _p(_i32(key_ids)), _p(Om), _ld(Om), _p(Oc), _ld(Oc), _p(LSE), _p(_f32(dOm)), _ld(dOm), _p(_f32(dOc)), _ld(dOc), B, H, L, hd, *scaled, float(p),
             _p(seed), site, b_offset, *[_p(o) for o in outs], ldd, _stream()]
     _stosa_attn_call(mfma, valu, args, prec)
     return outs
@@ -486,7 +487,7 @@ def _stosa_long_prec(prec):
     return PREC_F32 if prec is None else int(prec)
 
 
-def _stosa_long_fwd(name, Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, site, b_offset, prec):
+def _stosa_long_fwd(name, Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, site, b_offset, prec, scaled=()):
     d = Qm.shape[1]
     hd = d // H
     Om = torch.empty(B * L, d, device=Qm.device, dtype=torch.float32)
@@ -494,11 +495,11 @@ def _stosa_long_fwd(name, Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, sit
     LSE = torch.empty(B * H * L, device=Qm.device, dtype=torch.float32)
     _lib.check(getattr(_lib.load(), "adt_" + name)(
         _stosa_long_prec(prec), _p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc), _p(_f32(Vm)), _ld(Vm),
-        _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), B, H, L, hd, float(p), _p(seed), site, b_offset, _p(Om), d, _p(Oc), d, _p(LSE), _stream()), name)
+        _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), B, H, L, hd, *scaled, float(p), _p(seed), site, b_offset, _p(Om), d, _p(Oc), d, _p(LSE), _stream()), name)
     return Om, Oc, LSE
 
 
-def _stosa_long_bwd(name, Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site, b_offset, out, prec):
+def _stosa_long_bwd(name, Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site, b_offset, out, prec, scaled=()):
     d = Qm.shape[1]
     hd = d // H
     outs = [torch.empty(B * L, d, device=Qm.device, dtype=torch.float32) for _ in range(6)] if out is None else list(out)
@@ -507,7 +508,7 @@ def _stosa_long_bwd(name, Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc
     _lib.check(getattr(_lib.load(), "adt_" + name)(
         _stosa_long_prec(prec), _p(_f32(Qm)), _ld(Qm), _p(_f32(Qc)), _ld(Qc), _p(_f32(Km)), _ld(Km), _p(_f32(Kc)), _ld(Kc), _p(_f32(Vm)), _ld(Vm),
         _p(_f32(Vc)), _ld(Vc), _p(_i32(key_ids)), _p(Om), _ld(Om), _p(Oc), _ld(Oc), _p(LSE), _p(_f32(dOm)), _ld(dOm), _p(_f32(dOc)), _ld(dOc), B, H, L,
-        hd, float(p), _p(seed), site, b_offset, *[_p(o) for o in outs], ldd, _stream()), name)
+        hd, *scaled, float(p), _p(seed), site, b_offset, *[_p(o) for o in outs], ldd, _stream()), name)
     return outs
 
 
@@ -706,6 +707,104 @@ def lane_map(padded, compact, index, scatter):
     """compact[i] = padded[index[i]] (scatter False) or padded[index[i]] = compact[i] (scatter True)."""
     assert padded.dtype == torch.float32 and compact.dtype == torch.float32 and compact.is_contiguous() and compact.numel() == index.numel()
     _lib.check(_lib.load().adt_lane_map(_p(padded), _p(compact), _p(_i32(index)), index.numel(), int(bool(scatter)), _stream()), "lane_map")
+
+
+# ---- STOSA-ADT at padded widths (DESIGN.md section 26): lanes = (H, hd, hd_pad), rows of H * hd_pad floats with zero pad lanes ------------
+def _lane_chunks(dp, *ts):
+    """The (rows, views) one adt_act_lanes_* call covers: tensors of n padded rows side by side are n * T rows when all are contiguous,
+    else n column slices of T rows at the tensors' own row strides."""
+    T, w = ts[0].shape
+    assert w % dp == 0 and all(t.shape == ts[0].shape and t.stride(1) == 1 and t.stride(0) % 4 == 0 for t in ts), ([t.shape for t in ts], dp)
+    if all(t.is_contiguous() for t in ts):
+        return [(T * (w // dp), ts, (dp,) * len(ts))]
+    return [(T, tuple(t[:, k:k + dp] for t in ts), tuple(t.stride(0) for t in ts)) for k in range(0, w, dp)]
+
+
+def act_lanes_fwd(X, lanes, act, p=0.0, seed=None, site=0, row_offset=0):
+    """Y = act(dropout(X)) on the live lanes (dropout indexed at the true width), +0.0 on the pad lanes (adt_act_lanes_fwd).  X may hold
+    n padded rows side by side, (T, n * H * hd_pad) -- the q / k / v projections -- when p = 0."""
+    H, hd, hd_pad = lanes
+    dp = H * hd_pad
+    assert X.shape[1] == dp or p == 0.0, (X.shape, lanes, p)
+    Y = torch.empty(X.shape, device=X.device, dtype=torch.float32)
+    for rows, (x, y), (ldx, ldy) in _lane_chunks(dp, _f32(X), Y):
+        _lib.check(_lib.load().adt_act_lanes_fwd(_p(x), ldx, rows, H, hd, hd_pad, float(p), _p(seed), site, row_offset, int(act), _p(y), ldy, _stream()),
+                   "act_lanes_fwd")
+    return Y
+
+
+def act_lanes_bwd(dY, X, lanes, act, dX, accumulate, p=0.0, seed=None, site=0, row_offset=0):
+    """dX (+)= dY * act'(dropout(X)) * keep / (1 - p) on the live lanes; the pad lanes of dX are written +0.0 (adt_act_lanes_bwd)."""
+    H, hd, hd_pad = lanes
+    dp = H * hd_pad
+    assert X.shape[1] == dp or p == 0.0, (X.shape, lanes, p)
+    for rows, (dy, x, dx), (lddy, ldx, lddx) in _lane_chunks(dp, _f32(dY), _f32(X), _f32(dX)):
+        _lib.check(_lib.load().adt_act_lanes_bwd(_p(dy), lddy, _p(x), ldx, rows, H, hd, hd_pad, float(p), _p(seed), site, row_offset, int(act), _p(dx),
+                                                 lddx, int(accumulate), _stream()), "act_lanes_bwd")
+
+
+def _scaled(scale, hd_live):
+    return (float(scale), int(hd_live))
+
+
+def wattn_scaled_fwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, scale, hd_live, p=0.0, seed=None, site=0, b_offset=0, prec=None):
+    """wattn_fwd on heads padded from hd_live to Qm.shape[1] / H lanes, with the score scale given (1 / sqrt(true head size))."""
+    return _stosa_attn_fwd("wattn_mfma_scaled_fwd", "wattn_scaled_fwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, site, b_offset, prec,
+                           _scaled(scale, hd_live))
+
+
+def wattn_scaled_bwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, scale, hd_live, p=0.0, seed=None, site=0, b_offset=0, out=None,
+                     prec=None):
+    """wattn_bwd for wattn_scaled_fwd (the same scale, hd_live and prec): the pad lanes of all six gradients are +0.0."""
+    return _stosa_attn_bwd("wattn_mfma_scaled_bwd", "wattn_scaled_bwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site,
+                           b_offset, out, prec, _scaled(scale, hd_live))
+
+
+def wattn_long_scaled_fwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, scale, hd_live, p=0.0, seed=None, site=0, b_offset=0, prec=None):
+    """wattn_long_fwd (1 <= L <= 1024, streamed) with the score scale given and hd_live live lanes per head."""
+    return _stosa_long_fwd("wattn_long_scaled_fwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, site, b_offset, prec, _scaled(scale, hd_live))
+
+
+def wattn_long_scaled_bwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, scale, hd_live, p=0.0, seed=None, site=0, b_offset=0,
+                          out=None, prec=None):
+    return _stosa_long_bwd("wattn_long_scaled_bwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site, b_offset, out, prec,
+                           _scaled(scale, hd_live))
+
+
+def wdist_bpr_lanes(Sm, Sc, Em, Ec, pos, neg, pvn_weight, inv_count, dEm, dEc, loss3, lanes):
+    """wdist_bpr on padded rows and tables: the pad lanes stay out of the three distances and get +0.0 in dSm / dSc."""
+    H, hd, hd_pad = lanes
+    T, dp = Sm.shape
+    assert dp == H * hd_pad and Em.shape[1] == dp and Ec.shape[1] == dp, (Sm.shape, Em.shape, lanes)
+    dSm = torch.empty(T, dp, device=Sm.device, dtype=torch.float32)
+    dSc = torch.empty_like(dSm)
+    _lib.check(_lib.load().adt_wdist_bpr_lanes(_p(_f32(Sm)), _p(_f32(Sc)), _ld(Sm), _p(Em), _p(Ec), _p(_i32(pos)), _p(_i32(neg)), T, H, hd, hd_pad,
+                                               float(pvn_weight), _p(inv_count), _p(dSm), _p(dSc), dp, _p(dEm), _p(dEc), _p(loss3), _stream()),
+               "wdist_bpr_lanes")
+    return dSm, dSc
+
+
+def wdist_full_lanes(Sm, Sc, Em, Ec, V, lanes):
+    """wdist_full on padded rows and tables: the distance over the live lanes."""
+    H, hd, hd_pad = lanes
+    B, dp = Sm.shape
+    assert dp == H * hd_pad and Em.shape[1] == dp and Ec.shape[1] == dp, (Sm.shape, Em.shape, lanes)
+    dist = torch.empty(B, V, device=Sm.device, dtype=torch.float32)
+    _lib.check(_lib.load().adt_wdist_full_lanes(_p(_f32(Sm)), _p(_f32(Sc)), _ld(Sm), _p(Em), _p(Ec), B, V, H, hd, hd_pad, _p(dist), V, _stream()),
+               "wdist_full_lanes")
+    return dist
+
+
+def wdist_pack_lanes(M, C, elu, nrm_scale, lanes):
+    """wdist_pack on padded rows: img (rows, 2 d_pad) with +0.0 on the pad lanes of both halves, nrm over the live lanes."""
+    H, hd, hd_pad = lanes
+    assert M.dim() == 2 and M.shape == C.shape and M.stride(0) == C.stride(0) and M.shape[1] == H * hd_pad, (M.shape, C.shape, lanes)
+    rows, dp = M.shape
+    img = torch.empty(rows, 2 * dp, device=M.device, dtype=torch.float32)
+    nrm = torch.empty(rows, device=M.device, dtype=torch.float32)
+    _lib.check(_lib.load().adt_wdist_pack_lanes(_p(_f32(M)), _p(_f32(C)), M.stride(0), rows, H, hd, hd_pad, int(bool(elu)), _p(img), 2 * dp, _p(nrm),
+                                                float(nrm_scale), _stream()), "wdist_pack_lanes")
+    return img, nrm
 
 
 # ---- full-catalogue ranking (include/adt_hip.h: adt_full_rank; adt_amd/csrc/adt_fullrank.cuh) ---------------------------------------------

@@ -25,7 +25,8 @@ def parse_args(argv=None):
     p.add_argument("--data_dir", default="./data/")
     p.add_argument("--output_dir", default="./experiment/")
     p.add_argument("--dataset", default="Beauty")
-    p.add_argument("--synthetic", type=int, default=0, help="write a seeded Beauty-shaped sequence file when the data file is missing")
+    p.add_argument("--synthetic", type=lambda s: s if s == "tiny" else int(s), default=0,
+                   help="write a seeded Beauty-shaped sequence file when the data file is missing; 'tiny': 96 users and 150 items (a smoke run)")
     p.add_argument("--hidden_units", type=int, default=64)
     p.add_argument("--num_layers", type=int, default=2)
     p.add_argument("--num_heads", type=int, default=2)
@@ -147,7 +148,7 @@ def main(argv=None):
     if not os.path.exists(data_file) and args.synthetic:
         if rank == 0:
             os.makedirs(args.data_dir, exist_ok=True)
-            _write_synthetic(data_file)
+            _write_synthetic(data_file, **(dict(users=96, items=150, seed=3) if args.synthetic == "tiny" else {}))
         if world > 1:
             torch.distributed.barrier()
     user_seq, max_item, valid_matrix, test_matrix, num_users = get_user_seqs(data_file)
@@ -159,7 +160,8 @@ def main(argv=None):
     test_ds = DisenDataset(args, user_seq, "test", args.eval_set, seed=args.seed + 2)
     model = DisenDistSAModel(args)
     if world > 1:
-        torch.distributed.broadcast(model.flat, 0)
+        torch.distributed.broadcast(model.master, 0)      # the reference-shaped buffer at a padded width, the flat one otherwise
+        model.push()
     trainer = FusedStosaTrainer(model, lambda1, lambda2, lr=args.lr, betas=(args.adam_beta1, args.adam_beta2), weight_decay=args.weight_decay,
                                 process_group=pg, use_graph=args.use_graph, seed=args.seed)
     ckpt = os.path.join(args.output_dir, "adt-%s-%d-%d-%d.pt" % (args.dataset, args.hidden_units, args.num_layers, args.num_heads))

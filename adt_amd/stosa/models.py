@@ -8,13 +8,18 @@ reads them directly, stosa/trainer.py:361-364,466-467).  All arithmetic runs in 
 (adt_gemm.cuh), the Wasserstein attention and the BPR / full-sort distance kernels (adt_stosa.cuh, exact fp32 wave-level
 reductions), LayerNorm / dropout / ELU row kernels.  maxlen up to 1024: past ops.wattn_max_len(head size) rows (256; 141 at head size 64)
 the attention runs on the streamed matrix-core kernels of adt_wattn_long.cuh.
+Under the Wasserstein distance any (hidden_units, num_heads) that wide.padded_layout accepts with heads of up to 64 lanes runs too (50 / 1,
+100 / 2, 48 / 4, 150 / 3): activations and parameters are padded to d_pad columns, the registered parameters keep the reference's shapes
+(DESIGN.md section 26).
 """
+import math
+
 import numpy as np
 import torch
 
 from .. import _lib, custom_ops, ops
 from ..fullrank import DistRankMixin
-from ..wide import Act, FlatModule, Tape, give
+from ..wide import Act, FlatModule, Tape, give, padded_layout
 
 LN_EPS = 1e-12
 MAXLEN_MAX = 1024      # the streamed distance attention's bound (ops.wattn_long_fwd)
@@ -82,6 +87,38 @@ def param_table(item_size, maxlen, d, H, nl, num_users, block=0, dec_layernorm=T
     return t, n_trained
 
 
+def padded_tables(item_size, maxlen, d, H, nl, num_users, dec_layernorm=True):
+    """(ref_table, padded table, prefix, n_trained as param_table's) of a width the kernels do not tile (wide.padded_layout): every d becomes
+    d_pad (channel h * hd + j at h * hd_pad + j), the head classifiers' (H, hd) become (H, hd_pad), and the 4d of the intermediates becomes
+    4 * d_pad with the 4d live channels as a zero-tailed PREFIX (element j stays at j; wide.lane_index's `prefix`): ELU(0) = 0, so the tail
+    of the inner activation is zero, and (4 d_pad, d_pad) / (d_pad, 4 d_pad) are the shapes the dense arms run at width d_pad today.
+    Pure arithmetic: no GPU, no library."""
+    hd, hd_pad, dp = padded_layout(d, H)
+    ref, n_trained = param_table(item_size, maxlen, d, H, nl, num_users, 0, dec_layernorm)
+    pad, prefix = [], set()
+    for name, shape in ref:
+        if name.endswith("_independence_layer.weight"):
+            q = (H, hd_pad)
+        elif name.endswith(".dense_1.weight"):
+            q = (4 * dp, dp)
+            prefix.add((name, 0))
+        elif name.endswith(".dense_1.bias"):
+            q = (4 * dp,)
+            prefix.add((name, 0))
+        elif name.endswith(".dense_2.weight"):
+            q = (dp, 4 * dp)
+            prefix.add((name, 1))
+        elif name == "user_margins.weight" or name.endswith("_independence_layer.bias"):
+            q = shape
+        elif "_embeddings." in name:
+            q = (shape[0], dp)          # (item_size | maxlen, d)
+        else:
+            assert all(n == d for n in shape), (name, shape)
+            q = (dp,) * len(shape)      # (d, d) projections, (d,) biases and LayerNorm vectors
+        pad.append((name, q))
+    return ref, pad, prefix, n_trained
+
+
 class DisenDistSAModel(DistRankMixin, FlatModule):
     def __init__(self, args, block=0, dec_layernorm=True):
         super().__init__()
@@ -91,33 +128,66 @@ class DisenDistSAModel(DistRankMixin, FlatModule):
         self.dropout, self.attention_dropout = _lib.dropout_rate(args.dropout, "dropout"), _lib.dropout_rate(args.attention_dropout, "attention_dropout")
         self.prec = {"f32": ops.PREC_F32, "fp32": ops.PREC_F32, "bf16": ops.PREC_BF16}[getattr(args, "precision", "bf16")]
         d, H = self.hidden_units, self.num_heads
-        if d % 64 or (d // H) not in (16, 32, 64):
-            raise _lib.AdtError("DisenDistSAModel (adt_amd): hidden_units must be a multiple of 64 with head size 16/32/64, got d=%d H=%d" % (d, H))
+        tiled = d >= 64 and d % 64 == 0 and d % H == 0 and (d // H) in (16, 32, 64)      # the widths this model has always taken, as they are
+        if tiled:
+            self.hd, self.hd_pad, self.dp = d // H, d // H, d
+        else:
+            try:
+                self.hd, self.hd_pad, self.dp = padded_layout(d, H)
+            except _lib.AdtError as e:
+                raise _lib.AdtError("DisenDistSAModel (adt_amd): %s" % e) from None
+            if self.hd_pad > 64:
+                raise _lib.AdtError("DisenDistSAModel (adt_amd): d=%d H=%d has head size %d, which pads to %d lanes; the distance attention is "
+                                    "built for head sizes up to 64" % (d, H, self.hd, self.hd_pad))
+            if block:
+                raise _lib.AdtError("DisenDistSASupernet (adt_amd): the supernet is built for hidden_units a multiple of 64 with head size "
+                                    "16/32/64 only (padded widths run on DisenDistSAModel), got d=%d H=%d" % (d, H))
+        # dp == d: the kernels tile the width as it is.  Otherwise activations and parameters are padded to dp columns (head h at
+        # [h * hd_pad, h * hd_pad + hd), zero pad lanes; DESIGN.md sections 11 and 26); LayerNorm, the score scale, the dropout indices, the
+        # ELU + 1 of the covariances and the distances keep the true width.  hidden_units stays the true d; dp is the row the kernels see.
+        self.lanes = (H, self.hd, self.hd_pad) if self.dp != d else None
         self.distance_metric = getattr(args, "distance_metric", "wasserstein")
         if self.distance_metric not in ("wasserstein", "kl"):
             raise _lib.AdtError("DisenDistSAModel (adt_amd): distance_metric must be 'wasserstein' or 'kl', got %r" % (self.distance_metric,))
         kl = self.distance_metric == "kl"
+        if kl and self.lanes is not None:
+            raise _lib.AdtError("DisenDistSAModel (adt_amd): distance_metric='kl' is not built for padded widths (d=%d H=%d runs as d_pad=%d): "
+                                "its kernels form 1 / cov and log-determinants, where a zero pad lane is not neutral; use 'wasserstein' or a "
+                                "hidden_units that is a multiple of 64 with head size 16/32/64" % (d, H, self.dp))
         # attention, BPR loss and full-sort score of the chosen metric (stosa/modules.py:244-248, trainer.py:372-379, :597-600)
         self._attn_fwd, self._attn_bwd = (ops.klattn_fwd, ops.klattn_bwd) if kl else (ops.wattn_fwd, ops.wattn_bwd)
         # past the length the whole-(b, h) kernels hold in LDS (256; 141 at head size 64): the streamed kernels, up to 1024 (adt_wattn_long.cuh)
         if not 1 <= int(args.maxlen) <= MAXLEN_MAX:
             raise _lib.AdtError("DisenDistSAModel (adt_amd): maxlen must be in 1..%d, got %r" % (MAXLEN_MAX, args.maxlen))
-        self._long_attn = self.maxlen > ops.wattn_max_len(d // H)
+        self._long_attn = self.maxlen > ops.wattn_max_len(self.hd_pad)
         if self._long_attn:
             self._attn_fwd, self._attn_bwd = (ops.klattn_long_fwd, ops.klattn_long_bwd) if kl else (ops.wattn_long_fwd, ops.wattn_long_bwd)
         self._dist_bpr, self._dist_full = (ops.kldist_bpr, ops.kldist_full) if kl else (ops.wdist_bpr, ops.wdist_full)
-        table, n_trained = param_table(args.item_size, args.maxlen, d, H, args.num_layers, args.num_users, block, dec_layernorm)
-        self._build_flat(table, getattr(args, "device", "cuda:0"), REF_ORDER)
+        if self.lanes is None:
+            table, n_trained = param_table(args.item_size, args.maxlen, d, H, args.num_layers, args.num_users, block, dec_layernorm)
+            self._build_flat(table, getattr(args, "device", "cuda:0"), REF_ORDER)
+            ref_table = self.table
+        else:
+            ln, scaled = self.lanes, (1.0 / math.sqrt(self.hd), self.hd)       # the score scale of the TRUE head size, for both directions
+            fwd, bwd = (ops.wattn_long_scaled_fwd, ops.wattn_long_scaled_bwd) if self._long_attn else (ops.wattn_scaled_fwd, ops.wattn_scaled_bwd)
+            self._attn_fwd = lambda Qm, Qc, Km, Kc, Vm, Vc, kid, B, H, L, *a, **k: fwd(Qm, Qc, Km, Kc, Vm, Vc, kid, B, H, L, *scaled, *a, **k)
+            self._attn_bwd = lambda Qm, Qc, Km, Kc, Vm, Vc, kid, Om, Oc, LSE, dOm, dOc, B, H, L, *a, **k: \
+                bwd(Qm, Qc, Km, Kc, Vm, Vc, kid, Om, Oc, LSE, dOm, dOc, B, H, L, *scaled, *a, **k)
+            self._dist_bpr = lambda *a: ops.wdist_bpr_lanes(*a, ln)
+            self._dist_full = lambda *a: ops.wdist_full_lanes(*a, ln)
+            ref_table, table, prefix, n_trained = padded_tables(args.item_size, args.maxlen, d, H, args.num_layers, args.num_users, dec_layernorm)
+            self._build_flat(table, getattr(args, "device", "cuda:0"), REF_ORDER, ref_table=ref_table, width=(d, H), prefix=prefix)
         self.n_trained_floats = self._views[table[n_trained][0]][0]     # optimizer prefix (flat floats)
         # init_weights (stosa/models.py:262-272): N(0.01, initializer_range) on Linear/Embedding weights, LayerNorm 1/0, biases 0
         g = torch.Generator(device="cpu").manual_seed(torch.initial_seed() % (1 << 31))
         std = float(getattr(args, "initializer_range", 0.02))
-        for name, shape in self.table:
-            v = self.P(name)
+        for name, shape in ref_table:
+            v = self.R(name)         # reference shape (a view of the flat buffer itself without padding)
             if "LayerNorm.weight" in name:
                 v.fill_(1.0)
             elif name.endswith(".weight"):
                 v.copy_(0.01 + std * torch.randn(shape, generator=g))
+        self.push()
 
     # ------------------------------------------------------------------------------------------------------------------
     def _embed(self, tp, ids, which, site):
@@ -147,12 +217,17 @@ class DisenDistSAModel(DistRankMixin, FlatModule):
         """DistAttention.forward / DistEDAttention.forward (stosa/modules.py:222-275, 311-361) -> (mean_hidden, cov_hidden,
         mean context, cov context)."""
         P, G, sp = self.P, self.G, self.span
-        d, H, L = self.hidden_units, self.num_heads, self.maxlen
+        d, H, L = self.dp, self.num_heads, self.maxlen
         pa = tp.p_eff(self.attention_dropout)
 
         def proj(x, kind, first, last, n, act):
             w0, w1 = p + ".%s_%s.weight" % (kind, first), p + ".%s_%s.weight" % (kind, last)
             b0, b1 = p + ".%s_%s.bias" % (kind, first), p + ".%s_%s.bias" % (kind, last)
+            if act != ops.ACT_NONE and tp.lanes is not None:
+                # padded widths: ELU(0) + 1 = 1 on a pad lane would feed the next layer's pad weight columns a gradient; the projection
+                # runs without its epilogue and one lane pass applies the activation to the live lanes (no dense instantiation changes)
+                y = tp.dense(x, sp(w0, w1, (n * d, d)), sp(b0, b1, (n * d,)), sp(w0, w1, (n * d, d), grad=True), sp(b0, b1, (n * d,), grad=True))
+                return tp.act_lanes(y, act)
             return tp.dense(x, sp(w0, w1, (n * d, d)), sp(b0, b1, (n * d,)), sp(w0, w1, (n * d, d), grad=True), sp(b0, b1, (n * d,), grad=True), act=act)
         if mq is mkv:
             pm, pc = proj(mq, "mean", "query", "value", 3, ops.ACT_NONE), proj(cq, "cov", "query", "value", 3, ops.ACT_ELU1)
@@ -244,6 +319,10 @@ class DisenDistSAModel(DistRankMixin, FlatModule):
         bpr_optimization :358-391) runs unchanged; FusedStosaTrainer.step is the fast way to train."""
         ids = [self.ids(input_ids), self.ids(dec_ids)]
         B, L = ids[0].shape
+        if self.lanes is not None and custom_ops.wants_grad(self):
+            raise _lib.AdtError("DisenDistSAModel (adt_amd): autograd through finetune() (the reference's loop body) is not built for padded "
+                                "widths (d=%d H=%d runs as d_pad=%d); train with FusedStosaTrainer (the fused loop) or call finetune() under "
+                                "torch.no_grad()" % (self.hidden_units, self.num_heads, self.dp))
         if custom_ops.wants_grad(self):
             outs = custom_ops.forward_with_grad(self, ids)
         else:
@@ -260,6 +339,7 @@ class DisenDistSAModel(DistRankMixin, FlatModule):
         d, H = self.hidden_units, self.num_heads
         if training:
             self.next_seed()
+        self.push()      # padded widths: the reference-shaped parameters are the truth between steps (no-op otherwise)
         tp = Tape(self, self.prec, training)
         m, c, enc_inputs, enc_recs, dec_outs = self._finetune(tp, inp.view(-1), dec.view(-1), B)
         acts = [m, c] + [x for pr in enc_inputs for x in pr] + [x for pr in enc_recs for x in pr] + [x for pr in dec_outs for x in pr]
@@ -267,8 +347,14 @@ class DisenDistSAModel(DistRankMixin, FlatModule):
         outs = []
         for k, a in enumerate(acts):
             is_rec = 2 + 2 * nl <= k < 2 + 4 * nl
-            outs.append(a.t.view(B, L, H, H) if is_rec else a.t.view(B, L, d))
+            outs.append(a.t.view(B, L, H, H) if is_rec else self._live(a.t, B, L))
         return outs, {"tp": tp, "acts": acts}
+
+    def _live(self, t, B, L):
+        """(B * L, dp) activation as the reference's (B, L, d): the live lanes of a padded width (a copy, outside the training step)."""
+        if self.lanes is None:
+            return t.view(B, L, self.dp)
+        return t.view(B, L, self.num_heads, self.hd_pad)[..., :self.hd].reshape(B, L, self.hidden_units)
 
     def _op_backward(self, st, grads):
         self.flat_grad.zero_()
@@ -286,6 +372,7 @@ class DisenDistSAModel(DistRankMixin, FlatModule):
         B, L = inp.shape
         was = self.training
         self.eval()
+        self.push()
         tp = Tape(self, self.prec, False)
         m, c, _, _, _ = self._finetune(tp, inp.view(-1), dec.view(-1), B)
         rows = torch.arange(L - 1, B * L, L, device=self.dev, dtype=torch.int32)
@@ -294,7 +381,7 @@ class DisenDistSAModel(DistRankMixin, FlatModule):
         return sm, sc
 
     def _dist_tables(self):
-        """The item tables for DistRankMixin.  Every row 0..item_size - 1 of the tables takes part in the reference's full sort (the
+        """The item tables for DistRankMixin (at a padded width: the padded tables, which DistRankMixin packs lane-aware).  Every row 0..item_size - 1 of the tables takes part in the reference's full sort (the
         padding row 0 only with first_id = 0), so n_items = item_size - 1."""
         return self.P("item_mean_embeddings.weight"), self.P("item_cov_embeddings.weight"), self.item_size - 1
 

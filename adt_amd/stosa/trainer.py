@@ -41,10 +41,13 @@ class FusedStosaTrainer(TapeTrainer):
 
     def _body(self, st, b_offset):
         m = self.model
+        m.push()        # padded widths: the reference-shaped parameters are the truth between steps (no-op otherwise)
         m.loss_forward_backward(st, self.lambda1, self.lambda2, st["norms"], self.loss_slots, b_offset)
         self._buckets.finish()
+        # pad weights and pad gradients are exact zeros, so Adam (and its coupled weight decay) keeps them zero
         ops.clip_adam_l2(m.flat, m.flat_grad, self.m, self.v, self.wd, self.clip, self.lr, self.betas[0], self.betas[1], self.eps, self.scal,
                          n=m.n_trained_floats)
+        m.pull()
 
     def step(self, input_ids, dec_ids, pos_ids, neg_ids, n_target_global=None, b_offset=0, norms_scale=1):
         self.step_staged(self.stage(input_ids, dec_ids, pos_ids, neg_ids, n_target_global, norms_scale), b_offset)

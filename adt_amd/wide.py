@@ -430,8 +430,7 @@ class Tape:
         if p == 0.0 and act == ops.ACT_NONE:
             return x
         if self.lanes is not None:
-            assert act == ops.ACT_NONE, "padded widths: dropout without an activation only"
-            return self._drop_lanes(x, p, site)
+            return self._drop_lanes(x, p, site) if act == ops.ACT_NONE else self.act_lanes(x, act, p, site)
         off = self.row_offset * x.t.shape[1]
         y = Act(ops.dropact_fwd(x.t, p, self.seed, site, off, act))
 
@@ -453,6 +452,22 @@ class Tape:
             if y.g is None:
                 return
             give(x, ops.drop_lanes(y.g, self.lanes, p, self.seed, site, self.row_offset))
+        self.bw.append(bw)
+        return y
+
+    def act_lanes(self, x, act, p=0.0, site=0):
+        """act(dropout(x)) on a padded width: the activation on the live lanes only (ELU(0) + 1 = 1 must not reach a pad lane), the dropout
+        index over the true width (adt_act_lanes_fwd / _bwd).  x may be n padded rows side by side (the q / k / v projections) when p = 0."""
+        p = self.p_eff(p)
+        y = Act(ops.act_lanes_fwd(x.t, self.lanes, act, p, self.seed, site, self.row_offset))
+
+        def bw():
+            if y.g is None:
+                return
+            acc = x.g is not None
+            if not acc:
+                x.g = torch.empty_like(x.t)
+            ops.act_lanes_bwd(y.g, x.t, self.lanes, act, x.g, acc, p, self.seed, site, self.row_offset)
         self.bw.append(bw)
         return y
 

@@ -763,6 +763,56 @@ int adt_klattn_long_bwd(int prec, const float* Qm, int ldqm, const float* Qc, in
                         int H, int L, int hd, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc,
                         float* dKm, float* dKc, float* dVm, float* dVc, int ldd, void* stream);
 
+/* ---- STOSA-ADT at padded widths ----
+ * The Wasserstein attention on heads padded from hd_live to hd lanes (zero pad lanes): arguments, mask rule, dropout indices and
+ * results of adt_wattn_fwd / _bwd, adt_wattn_mfma_fwd / _bwd (1 = shape not covered) and adt_wattn_long_fwd / _bwd, with the score
+ * scale given -- 1 / sqrt(true head size); the forward and the backward must be given the same value, the backward reproduces the
+ * forward's scores bit for bit -- and 1 <= hd_live <= hd: lanes [hd_live, hd) of every head get a +0.0 gradient in all six outputs
+ * (sum(cov) has gradient 1 at cov = 0, so dQc / dKc would carry sum_j dW there otherwise).  With scale = 1 / sqrt(hd) at hd 16 or 64
+ * and hd_live = hd the results are bit-equal to the plain entry points'. */
+int adt_wattn_scaled_fwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float scale, int hd_live,
+    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE, void* stream);
+int adt_wattn_scaled_bwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc, int ldoc,
+    const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd, float scale, int hd_live,
+    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc, float* dKm, float* dKc, float* dVm,
+    float* dVc, int ldd, void* stream);
+int adt_wattn_mfma_scaled_fwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float scale, int hd_live,
+    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE, void* stream);
+int adt_wattn_mfma_scaled_bwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc, int ldoc,
+    const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd, float scale, int hd_live,
+    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc, float* dKm, float* dKc, float* dVm,
+    float* dVc, int ldd, void* stream);
+int adt_wattn_long_scaled_fwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float scale, int hd_live,
+    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE, void* stream);
+int adt_wattn_long_scaled_bwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc, int ldoc,
+    const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd, float scale, int hd_live,
+    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc, float* dKm, float* dKc, float* dVm,
+    float* dVc, int ldd, void* stream);
+/* adt_wdist_bpr / adt_wdist_full / adt_wdist_pack on padded rows and tables of d_pad = H * hd_pad columns (head h at columns
+ * [h * hd_pad, h * hd_pad + hd)): a pad lane of the covariance table is 0 and ELU(0) + 1 = 1, so the pad lanes are left out of every sum
+ * and of the image (both halves +0.0 there); dSm / dSc get +0.0 on them and the tables' pad lanes receive no atomic. */
+int adt_wdist_bpr_lanes(const float* Sm, const float* Sc, int lds, const float* Em, const float* Ec, const int32_t* pos,
+                        const int32_t* neg, int T, int H, int hd, int hd_pad, float pvn_weight, const float* inv_count, float* dSm,
+                        float* dSc, int ldds, float* dEm, float* dEc, float* loss3, void* stream);
+int adt_wdist_full_lanes(const float* Sm, const float* Sc, int lds, const float* Em, const float* Ec, int B, int V, int H, int hd,
+                         int hd_pad, float* dist, int ldo, void* stream);
+int adt_wdist_pack_lanes(const float* M, const float* C, int ld, int rows, int H, int hd, int hd_pad, int elu, float* img, int ldi,
+                         float* nrm, float nrm_scale, void* stream);
+/* Activation with its dropout site on padded lanes: Y = act(dropout(X)) on the live lanes, +0.0 on the pad lanes (ELU(0) + 1 = 1 must
+ * not appear there); dX (+)= dY * act'(dropout(X)) * keep / (1 - p) on the live lanes, pad lanes written +0.0.  The dropout index of
+ * (row t, live lane c) is (t + row_offset) * d + true column, as adt_drop_lanes.  act: ADT_ACT_*. */
+int adt_act_lanes_fwd(const float* X, int ldx, int T, int H, int hd, int hd_pad, float p, const uint32_t* seed, uint32_t site,
+                      uint32_t row_offset, int act, float* Y, int ldy, void* stream);
+int adt_act_lanes_bwd(const float* dY, int lddy, const float* X, int ldx, int T, int H, int hd, int hd_pad, float p,
+                      const uint32_t* seed, uint32_t site, uint32_t row_offset, int act, float* dX, int lddx, int accumulate,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,7 +80,7 @@ def reference_model(cfg_kw, B, seed, metric, pad_min=0):
 
 
 def gen_stosa(tag, cfg_kw, B, seed, lam1, lam2, lr=1e-3, keep_w3=True, compact=False, steps=3, metric="wasserstein", keep_w1=True, thresh=8192,
-              pad_min=0):
+              pad_min=0, nsample=1024):
     cfg, a, m, modules, (inp, dec, pos, neg) = reference_model(cfg_kw, B, seed, metric, pad_min)
     t = [torch.from_numpy(x) for x in (inp, dec, pos, neg)]
     uid = torch.zeros(B, dtype=torch.long)
@@ -151,7 +151,7 @@ def gen_stosa(tag, cfg_kw, B, seed, lam1, lam2, lr=1e-3, keep_w3=True, compact=F
     path = os.path.join(OUT, ("stosa_kl_%s.npz" if metric == "kl" else "stosa_%s.npz") % tag)
     if compact:
         from tools.gen_golden_inputs import compact as _compact
-        out = _compact(out, thresh=thresh)
+        out = _compact(out, k=nsample, thresh=thresh)
     np.savez_compressed(path, **out)
     print("wrote", path, "loss", out["loss"], "none-grads", len(out["grad_none"]), "%.1f KB" % (os.path.getsize(path) / 1024))
 
@@ -197,6 +197,24 @@ def main_long():
         gen_stosa("l272", cfg_kw, B=2, seed=27, lam1=[0.1], lam2=[0.05], metric=metric, **kw)
 
 
+STOSA_ODD_COMPACT = 320      # samples per compacted tensor of the odd-width fixtures (tests/test_stosa_oddwidth_*.py: K)
+
+
+def main_odd():
+    """stosa_w50_h1 / w100_h2 / w48_h4 / w150_h3.npz: hidden widths the kernels pad (head size 50 -> 64 lanes, 2 x 50 -> 128, 4 x 12 -> 4 x 16,
+    3 x 50 -> 192) at the small shapes of main(): dropout 0, three Adam steps, every gen_stosa field.  Compacted
+    (every float tensor above 2048 entries: its norm and 320 samples) so that each file stays far below 1 MiB."""
+    kw = dict(compact=True, thresh=2048, nsample=STOSA_ODD_COMPACT)
+    gen_stosa("w50_h1", dict(item_size=42, maxlen=12, hidden_units=50, num_heads=1, num_layers=1, num_users=4, pvn_weight=0.005), B=4, seed=41,
+              lam1=[0.3], lam2=[0.2], **kw)
+    gen_stosa("w100_h2", dict(item_size=33, maxlen=20, hidden_units=100, num_heads=2, num_layers=2, num_users=3, pvn_weight=0.1), B=3, seed=42,
+              lam1=[0.25, 0.1], lam2=[0.15, 0.05], **kw)
+    gen_stosa("w48_h4", dict(item_size=28, maxlen=9, hidden_units=48, num_heads=4, num_layers=1, num_users=2, pvn_weight=0.05), B=3, seed=43,
+              lam1=[0.1], lam2=[0.05], **kw)
+    gen_stosa("w150_h3", dict(item_size=42, maxlen=12, hidden_units=150, num_heads=3, num_layers=1, num_users=4, pvn_weight=0.005), B=3, seed=44,
+              lam1=[0.3], lam2=[0.2], **kw)
+
+
 def main_kl_rowwise():
     """stosa_kl_rowwise.npz: the model, seed and input_ids of stosa_kl_small.npz; rowwise_dist[b][v] = the reference's kl_distance
     (stosa/modules.py:45-50) of user b's last-position (mean, cov) from item v's (mean, ELU(cov) + 1), every row of the item tables --
@@ -222,6 +240,9 @@ if __name__ == "__main__":
     import argparse
     sys.path.insert(0, REPO)
     ap = argparse.ArgumentParser()
-    ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl", "kl_rowwise", "long"])
+    ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl", "kl_rowwise", "long", "stosa_odd"])
     metric = ap.parse_args().metric
-    main_kl_rowwise() if metric == "kl_rowwise" else (main_long() if metric == "long" else main(metric))
+    if metric == "stosa_odd":
+        main_odd()
+    else:
+        main_kl_rowwise() if metric == "kl_rowwise" else (main_long() if metric == "long" else main(metric))
