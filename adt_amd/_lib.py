@@ -145,6 +145,19 @@ SIGNATURES = {
     "adt_wdist_pack_lanes": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _F, _P]),
     "adt_act_lanes_fwd": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _U, _U, _I, _P, _I, _P]),
     "adt_act_lanes_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _U, _U, _I, _P, _I, _I, _P]),
+    # STOSA-ADT under KL at padded widths: the signatures of the Wasserstein entries above
+    "adt_klattn_scaled_fwd": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _I, _F, _P, _U, _U, _P, _I, _P, _I, _P, _P]),
+    "adt_klattn_scaled_bwd": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _F,
+                                    _P, _U, _U, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "adt_klattn_mfma_scaled_fwd": (_I, [_I] + [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _I, _F, _P, _U, _U, _P, _I, _P, _I, _P, _P]),
+    "adt_klattn_mfma_scaled_bwd": (_I, [_I] + [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _F,
+                                    _P, _U, _U, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "adt_klattn_long_scaled_fwd": (_I, [_I] + [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _I, _F, _P, _U, _U, _P, _I, _P, _I, _P, _P]),
+    "adt_klattn_long_scaled_bwd": (_I, [_I] + [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _F,
+                                    _P, _U, _U, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "adt_kldist_bpr_lanes": (_I, [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "adt_kldist_full_lanes": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "adt_klrow_pack_lanes": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
     "adt_dense_rows_enable": (_I, [_I]),
     "adt_dense_workspace": (_I, [_P, _L]),
     "adt_dense_bwd_ws_bytes": (_L, [_I, _I, _I, _I]),

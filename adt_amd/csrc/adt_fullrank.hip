@@ -126,8 +126,25 @@ int adt_klrow_pack(const float* M, const float* C, int ld, int rows, int d, int 
   if (rows <= 0) return 0;
   if (!M || !C || !img || !off) return adt_set_error("klrow_pack: missing operand");
   KlRowPackArgs a{M, C, ld, rows, d, items, img, ldi, off};
-  hipLaunchKernelGGL(k_klrow_pack, dim3(adt_grid_for((size_t)rows, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_klrow_pack<false>, dim3(adt_grid_for((size_t)rows, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
   return adt_check_launch("klrow_pack");
+}
+
+// adt_klrow_pack on padded rows (d_pad = H * hd_pad columns): the pad lanes of both halves of the image are +0.0 and stay out of off[r],
+// which takes the true d = H * hd
+int adt_klrow_pack_lanes(const float* M, const float* C, int ld, int rows, int H, int hd, int hd_pad, int items, float* img, int ldi, float* off,
+                         void* stream) {
+  if (items != 0 && items != 1) return adt_set_error("klrow_pack_lanes: items=%d must be 0 (user states) or 1 (item tables)", items);
+  const int d = H * hd_pad;
+  KlRowPackArgs a{M, C, ld, rows, d, items, img, ldi, off};
+  if (adt_make_lanes(a.ln, H, hd, hd_pad, "klrow_pack_lanes")) return -1;
+  if (ld < d || ldi < 2 * d) return adt_set_error("klrow_pack_lanes: ld=%d must be >= d_pad=%d and ldi=%d >= 2 d_pad", ld, d, ldi);
+  if ((ld % 4) || (ldi % 4) || !adt_aligned16(M) || !adt_aligned16(C) || !adt_aligned16(img))
+    return adt_set_error("klrow_pack_lanes: M, C and img must be 16-byte aligned with ld %% 4 == 0 and ldi %% 4 == 0");
+  if (rows <= 0) return 0;
+  if (!M || !C || !img || !off) return adt_set_error("klrow_pack_lanes: missing operand");
+  hipLaunchKernelGGL(k_klrow_pack<true>, dim3(adt_grid_for((size_t)rows, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("klrow_pack_lanes");
 }
 
 int adt_kldist_full_groups(const float* Sm, const float* Sc, int lds, const float* img, int ldi, const float* lv, int rows, int E, int V, int d,

@@ -22,76 +22,86 @@ namespace adt {
 
 // sum_d log c[d] over one row, by the 16 lanes that share (lane & 15) and in one fixed order (per-lane strided partial sums,
 // then an xor tree): the forward, pass A and pass B all obtain the row bias from this function, so that every recomputation
-// of a score is bit-identical (see w_pair_x on why that matters for fully masked rows).
-ADT_DEVICE_INLINE float kl_row_logsum(const float* g, int hd, int sub) {
+// of a score is bit-identical (see w_pair_x on why that matters for fully masked rows).  hl: the live lanes of the head (hd, or hd_live of
+// a padded head, whose pad lanes hold cov = 0 and stay out of the sum: log 0 = -inf).
+ADT_DEVICE_INLINE float kl_row_logsum(const float* g, int hl, int sub) {
   float part = 0.f;
-  for (int c = sub; c < hd; c += 16) part += logf(g[c]);
+  for (int c = sub; c < hl; c += 16) part += logf(g[c]);
 #pragma unroll
   for (int o = 8; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
   return part;
 }
 
+// 1 / c on a live lane, +0.0 on a pad lane (c = 0 there): a select on the lane index, never a product with zero (0 * inf = NaN)
+ADT_DEVICE_INLINE float kl_inv(float c, bool live) { return live ? 1.0f / c : 0.f; }
+
 // stage the column images of a head slice: y1[r] = 1/ck_r (+ colbias_r at index hd), y2[r] = cq_r
-ADT_DEVICE_INLINE void kl_stage_y(float* y1, float* y2, const float* Kc, int ldkc, const float* Qc, int ldqc, int L, int hd) {
+ADT_DEVICE_INLINE void kl_stage_y(float* y1, float* y2, const float* Kc, int ldkc, const float* Qc, int ldqc, int L, int hd, int hl) {
   const int RS = hd + 1, sub = threadIdx.x & 15;
   for (int r = threadIdx.x >> 4; r < L; r += 16) {
     for (int c = sub; c < hd; c += 16) {
-      y1[r * RS + c] = 1.0f / Kc[(size_t)r * ldkc + c];
+      y1[r * RS + c] = kl_inv(Kc[(size_t)r * ldkc + c], c < hl);
       y2[r * RS + c] = Qc[(size_t)r * ldqc + c];
     }
-    const float lb = kl_row_logsum(Kc + (size_t)r * ldkc, hd, sub);
+    const float lb = kl_row_logsum(Kc + (size_t)r * ldkc, hl, sub);
     if (sub == 0) y1[r * RS + hd] = lb;
   }
 }
 
 // stage the row images: x1[r] = (mq_r - mk_r)^2 (+ rowbias_r at index hd), x2[r] = 1/ck_r
 ADT_DEVICE_INLINE void kl_stage_x(float* x1, float* x2, const float* Qm, int ldqm, const float* Km, int ldkm, const float* Qc, int ldqc,
-                                  const float* Kc, int ldkc, int L, int hd) {
+                                  const float* Kc, int ldkc, int L, int hd, int hl) {
   const int RS = hd + 1, sub = threadIdx.x & 15;
   for (int r = threadIdx.x >> 4; r < L; r += 16) {
     for (int c = sub; c < hd; c += 16) {
       const float df = Qm[(size_t)r * ldqm + c] - Km[(size_t)r * ldkm + c];
       x1[r * RS + c] = df * df;
-      x2[r * RS + c] = 1.0f / Kc[(size_t)r * ldkc + c];
+      x2[r * RS + c] = kl_inv(Kc[(size_t)r * ldkc + c], c < hl);
     }
-    const float lb = kl_row_logsum(Qc + (size_t)r * ldqc, hd, sub);
+    const float lb = kl_row_logsum(Qc + (size_t)r * ldqc, hl, sub);
     if (sub == 0) x1[r * RS + hd] = lb;
   }
 }
 
 // one wave's own row image (lanes < hd write the features; every lane returns the row bias)
-ADT_DEVICE_INLINE float kl_wave_x(float* x1, float* x2, const float* qm, const float* km, const float* qc, const float* kc, int hd, int lane) {
+ADT_DEVICE_INLINE float kl_wave_x(float* x1, float* x2, const float* qm, const float* km, const float* qc, const float* kc, int hd, int hl, int lane) {
   for (int c = lane; c < hd; c += 64) {
     const float df = qm[c] - km[c];
     x1[c] = df * df;
-    x2[c] = 1.0f / kc[c];
+    x2[c] = kl_inv(kc[c], c < hl);
   }
-  return kl_row_logsum(qc, hd, lane & 15);
+  return kl_row_logsum(qc, hl, lane & 15);
 }
 
-ADT_DEVICE_INLINE float kl_wave_y(float* y1, float* y2, const float* kc, const float* qc, int hd, int lane) {
+ADT_DEVICE_INLINE float kl_wave_y(float* y1, float* y2, const float* kc, const float* qc, int hd, int hl, int lane) {
   for (int c = lane; c < hd; c += 64) {
-    y1[c] = 1.0f / kc[c];
+    y1[c] = kl_inv(kc[c], c < hl);
     y2[c] = qc[c];
   }
-  return kl_row_logsum(kc, hd, lane & 15);
+  return kl_row_logsum(kc, hl, lane & 15);
 }
 
-// the scaled negative KL of one (query, key) pair: one fixed sequence of operations for the forward and both backward passes
-ADT_DEVICE_INLINE float kl_pair_x(const float* x1, const float* x2, const float* y1, const float* y2, float rowb, float colb, int hd,
+// the scaled negative KL of one (query, key) pair: one fixed sequence of operations for the forward and both backward passes.
+// hl: the true head size the divergence subtracts (the pad lanes of a padded head add fmaf(0, 0, t) = t to both sums).
+ADT_DEVICE_INLINE float kl_pair_x(const float* x1, const float* x2, const float* y1, const float* y2, float rowb, float colb, int hd, int hl,
                                   float sq_hd) {
   float t = 0.f, u = 0.f;
   for (int d0 = 0; d0 < hd; ++d0) {
     t = fmaf(x1[d0], y1[d0], t);
     u = fmaf(x2[d0], y2[d0], u);
   }
-  const float kl = 0.5f * ((((colb - rowb) + t) + u) - (float)hd);
+  const float kl = 0.5f * ((((colb - rowb) + t) + u) - (float)hl);
   return (-kl) / sq_hd;
 }
 
-__global__ __launch_bounds__(256) void k_klattn_fwd(WAttnArgs a) {
+// LN: padded heads (the adt_klattn_scaled_* entry points): hl = hd_live live lanes and the given scale.  <false> is the kernel as it
+// always was (hl = hd and sqrt(hd) fold into it: 86 / 128 VGPRs, 5 / 4 waves per SIMD).  <true> carries (256, 5) / (256, 4): the two
+// extra scalars tip the allocator's occupancy heuristic one step down without the bound (112 / 129 VGPRs); with it the kernels stay at
+// 85 / 128 and scratch 0.  The LDS footprint decides how many workgroups are resident, not this.
+template <bool LN>
+__global__ __launch_bounds__(256, LN ? 5 : 1) void k_klattn_fwd(WAttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int L = a.L, hd = a.hd, RS = hd + 1, Lp = (L + 63) / 64 * 64;
+  const int L = a.L, hd = a.hd, hl = LN ? a.hd_live : hd, RS = hd + 1, Lp = (L + 63) / 64 * 64;
   float* sY1 = smem;                 // [L][RS] 1/ck_j, colbias_j at [hd]
   float* sY2 = sY1 + L * RS;         // cq_j
   float* sVm = sY2 + L * RS;
@@ -105,7 +115,7 @@ __global__ __launch_bounds__(256) void k_klattn_fwd(WAttnArgs a) {
   for (int i = threadIdx.x; i < Lp; i += 256) sKv[i] = (i < L && a.kid[row_b + i] > 0) ? 1.f : 0.f;
   __syncthreads();
   w_mark_dead(sDead, sKv, L, Lp);
-  kl_stage_y(sY1, sY2, a.Kc + row_b * a.ldkc + h * hd, a.ldkc, a.Qc + row_b * a.ldqc + h * hd, a.ldqc, L, hd);
+  kl_stage_y(sY1, sY2, a.Kc + row_b * a.ldkc + h * hd, a.ldkc, a.Qc + row_b * a.ldqc + h * hd, a.ldqc, L, hd, hl);
   w_stage<false, false>(sVm, a.Vm + row_b * a.ldvm + h * hd, a.ldvm, L, hd, nullptr);
   w_stage<false, false>(sVc, a.Vc + row_b * a.ldvc + h * hd, a.ldvc, L, hd, nullptr);
   __syncthreads();
@@ -114,13 +124,13 @@ __global__ __launch_bounds__(256) void k_klattn_fwd(WAttnArgs a) {
   float* sX1 = sP + 3 * Lp;
   float* sX2 = sX1 + hd;
   const uint32_t key_rng = drop_key(a.drop);
-  const float sq_hd = sqrtf((float)hd);
+  const float sq_hd = LN ? w_sq_hd(a) : sqrtf((float)hd);
   const int nd = 64 / hd >= 1 ? hd : 64;
   const int nparts = 64 / nd;
   for (int i = w; i < L; i += 4) {
     const size_t r = row_b + i;
     const float rowb = kl_wave_x(sX1, sX2, a.Qm + r * a.ldqm + h * hd, a.Km + r * a.ldkm + h * hd, a.Qc + r * a.ldqc + h * hd,
-                                 a.Kc + r * a.ldkc + h * hd, hd, lane);
+                                 a.Kc + r * a.ldkc + h * hd, hd, hl, lane);
     const bool dead_i = sDead[i] != 0.f;
     float s[W_KPL];
     float m = -INFINITY;
@@ -129,7 +139,7 @@ __global__ __launch_bounds__(256) void k_klattn_fwd(WAttnArgs a) {
       const int j = lane + 64 * t;
       s[t] = -INFINITY;
       if (j < L) {
-        s[t] = w_score(kl_pair_x(sX1, sX2, sY1 + j * RS, sY2 + j * RS, rowb, sY1[j * RS + hd], hd, sq_hd), j > i || sKv[j] == 0.f, dead_i);
+        s[t] = w_score(kl_pair_x(sX1, sX2, sY1 + j * RS, sY2 + j * RS, rowb, sY1[j * RS + hd], hd, hl, sq_hd), j > i || sKv[j] == 0.f, dead_i);
         m = fmaxf(m, s[t]);
       }
     }
@@ -183,9 +193,10 @@ __global__ __launch_bounds__(256) void k_klattn_fwd(WAttnArgs a) {
 //   dVm_j, dVc_j as in k_wattn_bwd.
 // Row i of pass A and row j = i of pass B are handled by the same wave and lane, so the pass-B read-add-write of dKc / dQc
 // sees pass A's value in program order: a fixed summation order, no atomics.
-__global__ __launch_bounds__(256) void k_klattn_bwd(WAttnArgs a) {
+template <bool LN>
+__global__ __launch_bounds__(256, LN ? 4 : 1) void k_klattn_bwd(WAttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int L = a.L, hd = a.hd, RS = hd + 1, Lp = (L + 63) / 64 * 64;
+  const int L = a.L, hd = a.hd, hl = LN ? a.hd_live : hd, RS = hd + 1, Lp = (L + 63) / 64 * 64;      // lanes at and above hl: zero padding, +0.0 gradients
   float* sA0 = smem;                 // phase A: Y1 (colbias at [hd]) | phase B: X1 (rowbias at [hd])
   float* sA1 = sA0 + L * RS;         // phase A: Y2                   | phase B: X2
   float* sA2 = sA1 + L * RS;         // phase A: Vm                   | phase B: dOm
@@ -198,7 +209,7 @@ __global__ __launch_bounds__(256) void k_klattn_bwd(WAttnArgs a) {
   const int bh = blockIdx.x, b = bh / a.H, h = bh % a.H;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const size_t row_b = (size_t)b * L;
-  const float sq_hd = sqrtf((float)hd);
+  const float sq_hd = LN ? w_sq_hd(a) : sqrtf((float)hd);
   const uint32_t key_rng = drop_key(a.drop);
   const uint32_t idx_bh = (uint32_t)(bh + a.bh_offset) * (uint32_t)L;
   const int nd = 64 / hd >= 1 ? hd : 64;
@@ -217,7 +228,7 @@ __global__ __launch_bounds__(256) void k_klattn_bwd(WAttnArgs a) {
     sLse[i] = i < L ? a.LSE[(size_t)bh * L + i] : INFINITY;
     sDelta[i] = 0.f;
   }
-  kl_stage_y(sA0, sA1, a.Kc + row_b * a.ldkc + co, a.ldkc, a.Qc + row_b * a.ldqc + co, a.ldqc, L, hd);
+  kl_stage_y(sA0, sA1, a.Kc + row_b * a.ldkc + co, a.ldkc, a.Qc + row_b * a.ldqc + co, a.ldqc, L, hd, hl);
   w_stage<false, false>(sA2, a.Vm + row_b * a.ldvm + co, a.ldvm, L, hd, nullptr);
   w_stage<false, false>(sA3, a.Vc + row_b * a.ldvc + co, a.ldvc, L, hd, nullptr);
   __syncthreads();
@@ -228,7 +239,7 @@ __global__ __launch_bounds__(256) void k_klattn_bwd(WAttnArgs a) {
   for (int i = w; i < L; i += 4) {
     const size_t r = row_b + i;
     const float rowb = kl_wave_x(sV0, sV1, a.Qm + r * a.ldqm + co, a.Km + r * a.ldkm + co, a.Qc + r * a.ldqc + co, a.Kc + r * a.ldkc + co,
-                                 hd, lane);
+                                 hd, hl, lane);
     for (int d0 = lane; d0 < hd; d0 += 64) {
       sV2[d0] = a.dOm[r * a.lddom + co + d0];
       sV3[d0] = a.dOc[r * a.lddoc + co + d0];
@@ -248,7 +259,7 @@ __global__ __launch_bounds__(256) void k_klattn_bwd(WAttnArgs a) {
           gm += sV2[d0] * sA2[j * RS + d0];
           gc += sV3[d0] * sA3[j * RS + d0];
         }
-        const float sv = w_score(kl_pair_x(sV0, sV1, sA0 + j * RS, sA1 + j * RS, rowb, sA0[j * RS + hd], hd, sq_hd), j > i || sKv[j] == 0.f, dead_i);
+        const float sv = w_score(kl_pair_x(sV0, sV1, sA0 + j * RS, sA1 + j * RS, rowb, sA0[j * RS + hd], hd, hl, sq_hd), j > i || sKv[j] == 0.f, dead_i);
         const float pr = expf(sv - lse);
         float ks_ = 1.0f;
         if (a.drop.thr) ks_ = adt_keep(key_rng, idx_q + (uint32_t)j, a.drop.thr) ? a.drop.scale : 0.f;
@@ -282,10 +293,11 @@ __global__ __launch_bounds__(256) void k_klattn_bwd(WAttnArgs a) {
       if (part == 0) {
         const float df = a.Qm[r * a.ldqm + co + d0] - a.Km[r * a.ldkm + co + d0];
         const float x2 = sV1[d0];
-        a.dQm[r * a.ldd + co + d0] = df * am;
-        a.dKm[r * a.ldd + co + d0] = -(df * am);
-        a.dKc[r * a.ldd + co + d0] = -0.5f * x2 * x2 * as;
-        a.dQc[r * a.ldd + co + d0] = -0.5f * gsum / a.Qc[r * a.ldqc + co + d0];
+        const bool lv = d0 < hl;
+        a.dQm[r * a.ldd + co + d0] = lv ? df * am : 0.f;
+        a.dKm[r * a.ldd + co + d0] = lv ? -(df * am) : 0.f;
+        a.dKc[r * a.ldd + co + d0] = lv ? -0.5f * x2 * x2 * as : 0.f;
+        a.dQc[r * a.ldd + co + d0] = lv ? -0.5f * gsum / a.Qc[r * a.ldqc + co + d0] : 0.f;      // cq = 0 on a pad lane
       }
     }
   }
@@ -293,7 +305,7 @@ __global__ __launch_bounds__(256) void k_klattn_bwd(WAttnArgs a) {
   // ---- phase B staging: the row images and dO over the same LDS ------------------------------------------------------
   __syncthreads();
   kl_stage_x(sA0, sA1, a.Qm + row_b * a.ldqm + co, a.ldqm, a.Km + row_b * a.ldkm + co, a.ldkm, a.Qc + row_b * a.ldqc + co, a.ldqc,
-             a.Kc + row_b * a.ldkc + co, a.ldkc, L, hd);
+             a.Kc + row_b * a.ldkc + co, a.ldkc, L, hd, hl);
   w_stage<false, false>(sA2, a.dOm + row_b * a.lddom + co, a.lddom, L, hd, nullptr);
   w_stage<false, false>(sA3, a.dOc + row_b * a.lddoc + co, a.lddoc, L, hd, nullptr);
   __syncthreads();
@@ -301,7 +313,7 @@ __global__ __launch_bounds__(256) void k_klattn_bwd(WAttnArgs a) {
   // ---- pass B: wave owns key j, lanes over queries i ------------------------------------------------------------------
   for (int j = w; j < L; j += 4) {
     const size_t r = row_b + j;
-    const float colb = kl_wave_y(sV0, sV1, a.Kc + r * a.ldkc + co, a.Qc + r * a.ldqc + co, hd, lane);
+    const float colb = kl_wave_y(sV0, sV1, a.Kc + r * a.ldkc + co, a.Qc + r * a.ldqc + co, hd, hl, lane);
     for (int d0 = lane; d0 < hd; d0 += 64) {
       sV2[d0] = a.Vm[r * a.ldvm + co + d0];
       sV3[d0] = a.Vc[r * a.ldvc + co + d0];
@@ -319,7 +331,7 @@ __global__ __launch_bounds__(256) void k_klattn_bwd(WAttnArgs a) {
             gm += sA2[i * RS + d0] * sV2[d0];
             gc += sA3[i * RS + d0] * sV3[d0];
           }
-          const float sv = w_score(kl_pair_x(sA0 + i * RS, sA1 + i * RS, sV0, sV1, sA0[i * RS + hd], colb, hd, sq_hd), j > i || key_pad,
+          const float sv = w_score(kl_pair_x(sA0 + i * RS, sA1 + i * RS, sV0, sV1, sA0[i * RS + hd], colb, hd, hl, sq_hd), j > i || key_pad,
                                    sDead[i] != 0.f);
           const float pr = expf(sv - sLse[i]);
           float ks_ = 1.0f;
@@ -350,10 +362,11 @@ __global__ __launch_bounds__(256) void k_klattn_bwd(WAttnArgs a) {
       }
       if (part == 0) {
         const float y1 = sV0[d0];
-        a.dKc[r * a.ldd + co + d0] += 0.5f * gsum * y1 - 0.5f * bm * y1 * y1;
-        a.dQc[r * a.ldd + co + d0] += 0.5f * bs;
-        a.dVm[r * a.ldd + co + d0] = vm;
-        a.dVc[r * a.ldd + co + d0] = vc;
+        const bool lv = d0 < hl;
+        a.dKc[r * a.ldd + co + d0] = lv ? a.dKc[r * a.ldd + co + d0] + (0.5f * gsum * y1 - 0.5f * bm * y1 * y1) : 0.f;
+        a.dQc[r * a.ldd + co + d0] = lv ? a.dQc[r * a.ldd + co + d0] + 0.5f * bs : 0.f;
+        a.dVm[r * a.ldd + co + d0] = lv ? vm : 0.f;
+        a.dVc[r * a.ldd + co + d0] = lv ? vc : 0.f;
       }
     }
   }
@@ -362,11 +375,15 @@ __global__ __launch_bounds__(256) void k_klattn_bwd(WAttnArgs a) {
 // ---- BPR + positive-vs-negative loss on row-wise KL divergences (stosa/trainer.py:358-391, kl_distance modules.py:45-50) ----
 //   KL(a||b) = 0.5 (sum c_a / c_b + sum (m_b - m_a)^2 / c_b - d + sum log c_b - sum log c_a)
 //   pos = KL(seq||pos), neg = KL(seq||neg), pvn = KL(pos||neg); item covariances through ELU(.)+1.  Arguments as k_wdist_bpr.
+// LN: rows and tables are padded (a.ln, d = H * hd_pad).  A pad lane holds a sequence covariance 0 (1 / sc, log sc) and an item covariance
+// ELU(0) + 1 = 1, so it is skipped by its index in every sum and log, the divergences subtract the true d, dSm / dSc get +0.0 there and the
+// tables' pad lanes receive no atomic.
+template <bool LN>
 __global__ __launch_bounds__(256) void k_kldist_bpr(WBprArgs a) {
   const int lane = threadIdx.x & 63;
   const float wgt = *a.inv_count;
   const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
-  const float fd = (float)a.d;
+  const float fd = LN ? (float)(a.ln.H * a.ln.hd) : (float)a.d;
   float l_bpr = 0.f, l_pvn = 0.f, l_auc = 0.f;
   for (int t = wave; t < a.T; t += nwaves) {
     const int ip = a.pos[t], in = a.neg[t];
@@ -374,6 +391,7 @@ __global__ __launch_bounds__(256) void k_kldist_bpr(WBprArgs a) {
     float tp = 0.f, mp = 0.f, tn = 0.f, mn = 0.f, tpn = 0.f, mpn = 0.f, ls = 0.f, lp = 0.f, ln = 0.f;
     if (tgt) {
       for (int c = lane; c < a.d; c += 64) {
+        if (LN && !a.ln.live(c)) continue;
         const float sm = a.Sm[(size_t)t * a.lds + c], sc = a.Sc[(size_t)t * a.lds + c];
         const float pm = a.Em[(size_t)ip * a.d + c], pc = w_elu1(a.Ec[(size_t)ip * a.d + c]);
         const float nm = a.Em[(size_t)in * a.d + c], nc = w_elu1(a.Ec[(size_t)in * a.d + c]);
@@ -404,7 +422,7 @@ __global__ __launch_bounds__(256) void k_kldist_bpr(WBprArgs a) {
     }
     for (int c = lane; c < a.d; c += 64) {
       float dsm = 0.f, dsc = 0.f;
-      if (tgt) {
+      if (tgt && (!LN || a.ln.live(c))) {
         const float sm = a.Sm[(size_t)t * a.lds + c], sc = a.Sc[(size_t)t * a.lds + c];
         const float pe = a.Ec[(size_t)ip * a.d + c], ne = a.Ec[(size_t)in * a.d + c];
         const float pm = a.Em[(size_t)ip * a.d + c], pc = w_elu1(pe);
@@ -442,7 +460,9 @@ __global__ __launch_bounds__(256) void k_kldist_bpr(WBprArgs a) {
 // The reference pads the item table to a multiple of the batch size E = B (zero means, unit covariances) and calls
 // kl_distance_matmul on the B users against each B-item chunk; with its broadcasts, for item v = cE + j and a = cE + u:
 //   dist[u][v] = 0.5 (sum log ci_v - sum log cu_u + sum (mu_u - mi_a)^2 / ci_v + sum cu_j / ci_a - d)
-// (item a >= V is a padding item).  16 lanes per (user, item) pair.
+// (item a >= V is a padding item).  16 lanes per (user, item) pair.  LN: padded rows and tables (a.ln), the pad lanes skipped by their
+// index (cu = 0 there, and ELU(0) + 1 = 1 on the item side) and the true d subtracted.
+template <bool LN>
 __global__ __launch_bounds__(256) void k_kldist_full(WFullArgs a) {
   const int sub = threadIdx.x & 15;
   const size_t n = (size_t)a.B * a.V;
@@ -452,6 +472,7 @@ __global__ __launch_bounds__(256) void k_kldist_full(WFullArgs a) {
     const bool real_a = ia < a.V;
     float lv = 0.f, lu = 0.f, mc = 0.f, tr = 0.f;
     for (int c = sub; c < a.d; c += 16) {
+      if (LN && !a.ln.live(c)) continue;
       const float cv = w_elu1(a.Ec[(size_t)v * a.d + c]);
       const float ma = real_a ? a.Em[(size_t)ia * a.d + c] : 0.f;
       const float ca = real_a ? w_elu1(a.Ec[(size_t)ia * a.d + c]) : 1.f;
@@ -466,7 +487,7 @@ __global__ __launch_bounds__(256) void k_kldist_full(WFullArgs a) {
       lv += __shfl_xor(lv, o, 64); lu += __shfl_xor(lu, o, 64);
       mc += __shfl_xor(mc, o, 64); tr += __shfl_xor(tr, o, 64);
     }
-    if (sub == 0) a.dist[(size_t)u * a.ldo + v] = 0.5f * ((((lv - lu) + mc) + tr) - (float)a.d);
+    if (sub == 0) a.dist[(size_t)u * a.ldo + v] = 0.5f * ((((lv - lu) + mc) + tr) - (LN ? (float)(a.ln.H * a.ln.hd) : (float)a.d));
   }
 }
 

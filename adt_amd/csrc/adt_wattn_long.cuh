@@ -45,6 +45,8 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_fwd(WAttnArgs a) {
   constexpr int KT = CH / 16, RST = CH + 4;
   static_assert(CH % 32 == 0 && ATTN_LONG_LMAX % CH == 0, "chunks hold whole tile pairs");
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int hl = MET == WM_KLP ? a.hd_live : WM_ALL_LIVE;      // KL: the live lanes of a head (WM_ALL_LIVE: every lane test folds to true)
+  const float fhl = MET == WM_KLP ? (float)a.hd_live : (float)HD;      // the dimension the divergence subtracts
   float* sK = smem;                          // [CH][RSK]  [mk | sqrt Sk] of keys k0 .. k0 + CH - 1     (KL: Y = [1/ck | cq])
   float* sNk = sK + CH * S::RSK;             // [CH]       norms                                         (KL: column bias sum log ck)
   float* sVmT = sNk + CH;                    // [HD][RST]
@@ -64,11 +66,11 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_fwd(WAttnArgs a) {
   const size_t qrow = row_b + (vi ? i : 0);
   Frag8 fq[S::KB];
   float nq;                                    // KL: the row bias sum log cq_i
-  if constexpr (MET == WM_KL) {
+  if constexpr (wm_kl(MET)) {
 #pragma unroll
     for (int kb = 0; kb < S::KB; ++kb)
-      fq[kb] = wm_kl_frag<HD, true>(a.Qm + qrow * a.ldqm + co, a.Km + qrow * a.ldkm + co, a.Qc + qrow * a.ldqc + co, a.Kc + qrow * a.ldkc + co, kb, g, vi);
-    nq = vi ? wm_kl_logsum<HD>(a.Qc + qrow * a.ldqc + co) : 0.f;
+      fq[kb] = wm_kl_frag<HD, true>(a.Qm + qrow * a.ldqm + co, a.Km + qrow * a.ldkm + co, a.Qc + qrow * a.ldqc + co, a.Kc + qrow * a.ldkc + co, kb, g, vi, hl);
+    nq = vi ? wm_kl_logsum<HD>(a.Qc + qrow * a.ldqc + co, hl) : 0.f;
   } else {
 #pragma unroll
     for (int kb = 0; kb < S::KB; ++kb) fq[kb] = wm_cat_frag<HD>(a.Qm + qrow * a.ldqm + co, a.Qc + qrow * a.ldqc + co, kb, g, vi);
@@ -91,8 +93,8 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_fwd(WAttnArgs a) {
     __syncthreads();
     wm_stage_t<false>(sVmT, a.Vm + (row_b + k0) * a.ldvm + co, a.ldvm, Lc, CH, HD);
     wm_stage_t<false>(sVcT, a.Vc + (row_b + k0) * a.ldvc + co, a.ldvc, Lc, CH, HD);
-    if constexpr (MET == WM_KL)
-      wm_kl_stage<HD, false>(sK, sNk, nullptr, 0, nullptr, 0, a.Qc + (row_b + k0) * a.ldqc + co, a.ldqc, a.Kc + (row_b + k0) * a.ldkc + co, a.ldkc, Lc, CH);
+    if constexpr (wm_kl(MET))
+      wm_kl_stage<HD, false>(sK, sNk, nullptr, 0, nullptr, 0, a.Qc + (row_b + k0) * a.ldqc + co, a.ldqc, a.Kc + (row_b + k0) * a.ldkc + co, a.ldkc, Lc, CH, hl);
     else
       wm_stage_cat<HD>(sK, sNk, a.Km + (row_b + k0) * a.ldkm + co, a.ldkm, a.Kc + (row_b + k0) * a.ldkc + co, a.ldkc, Lc, CH);
     __syncthreads();
@@ -112,7 +114,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_fwd(WAttnArgs a) {
         for (int r = 0; r < 4; ++r) {
           const int jl = kt * 16 + 4 * g + r, j = k0 + jl;
           if (j < L) {
-            const float x = MET == WM_KL ? wm_kl_x(sNk[jl], nq, acc[r], (float)HD, rsq_hd) : -((sNk[jl] + nq) - 2.0f * acc[r]) * rsq_hd;
+            const float x = wm_kl(MET) ? wm_kl_x(sNk[jl], nq, acc[r], fhl, rsq_hd) : -((sNk[jl] + nq) - 2.0f * acc[r]) * rsq_hd;
             const bool masked = j > i || sKv[j] == 0;
             if (!masked || dead_i) {           // masked keys of a live row: exp(x - 2^32 - m) == 0, left at -inf
               s[kt][r] = w_score(x, masked, dead_i);
@@ -175,6 +177,8 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
   constexpr int KBV = (HD + 31) / 32, RST = CH + 4, NP = CH / 32;
   static_assert(CH % 32 == 0 && ATTN_LONG_LMAX % CH == 0, "chunks hold whole tile pairs");
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int hl = MET == WM_KLP ? a.hd_live : WM_ALL_LIVE;      // KL: the live lanes of a head (WM_ALL_LIVE: every lane test folds to true)
+  const float fhl = MET == WM_KLP ? (float)a.hd_live : (float)HD;      // the dimension the divergence subtracts
   float* sC = smem;                          // A: [mk | sqrt Sk] rows of the key chunk (KL: Y) | B: [mq | sqrt Sq] rows of the query chunk (KL: X)
   float* sN = sC + CH * S::RSK;              // A: key norms / column biases                     | B: query norms / row biases
   float* sCT = sN + CH;                      // [KC][RST] transposed image
@@ -220,11 +224,11 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
     const size_t qrow = row_b + (vi ? i : 0);
     Frag8 fq[S::KB], fdm[KBV], fdc[KBV];
     float nq;
-    if constexpr (MET == WM_KL) {
+    if constexpr (wm_kl(MET)) {
 #pragma unroll
       for (int kb = 0; kb < S::KB; ++kb)
-        fq[kb] = wm_kl_frag<HD, true>(a.Qm + qrow * a.ldqm + co, a.Km + qrow * a.ldkm + co, a.Qc + qrow * a.ldqc + co, a.Kc + qrow * a.ldkc + co, kb, g, vi);
-      nq = vi ? wm_kl_logsum<HD>(a.Qc + qrow * a.ldqc + co) : 0.f;
+        fq[kb] = wm_kl_frag<HD, true>(a.Qm + qrow * a.ldqm + co, a.Km + qrow * a.ldkm + co, a.Qc + qrow * a.ldqc + co, a.Kc + qrow * a.ldkc + co, kb, g, vi, hl);
+      nq = vi ? wm_kl_logsum<HD>(a.Qc + qrow * a.ldqc + co, hl) : 0.f;
     } else {
 #pragma unroll
       for (int kb = 0; kb < S::KB; ++kb) fq[kb] = wm_cat_frag<HD>(a.Qm + qrow * a.ldqm + co, a.Qc + qrow * a.ldqc + co, kb, g, vi);
@@ -254,8 +258,8 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
       __syncthreads();
       wm_stage_nat<HD>(sX0, a.Vm + (row_b + k0) * a.ldvm + co, a.ldvm, Lc, CH);
       wm_stage_nat<HD>(sX1, a.Vc + (row_b + k0) * a.ldvc + co, a.ldvc, Lc, CH);
-      if constexpr (MET == WM_KL) {      // Y = [1/ck | cq] rows and column biases; the transpose after the barrier
-        wm_kl_stage<HD, false>(sC, sN, nullptr, 0, nullptr, 0, a.Qc + (row_b + k0) * a.ldqc + co, a.ldqc, a.Kc + (row_b + k0) * a.ldkc + co, a.ldkc, Lc, CH);
+      if constexpr (wm_kl(MET)) {      // Y = [1/ck | cq] rows and column biases; the transpose after the barrier
+        wm_kl_stage<HD, false>(sC, sN, nullptr, 0, nullptr, 0, a.Qc + (row_b + k0) * a.ldqc + co, a.ldqc, a.Kc + (row_b + k0) * a.ldkc + co, a.ldkc, Lc, CH, hl);
         __syncthreads();
         wm_kl_transpose<HD>(sCT, sC, CH);
       } else {
@@ -289,7 +293,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
             for (int r = 0; r < 4; ++r) {
               const int jl = ktl * 16 + 4 * g + r, j = k0 + jl;
               if (j < L && vi) {
-                const float x = MET == WM_KL ? wm_kl_x(sN[jl], nq, acc[r], (float)HD, rsq_hd) : -((sN[jl] + nq) - 2.0f * acc[r]) * rsq_hd;
+                const float x = wm_kl(MET) ? wm_kl_x(sN[jl], nq, acc[r], fhl, rsq_hd) : -((sN[jl] + nq) - 2.0f * acc[r]) * rsq_hd;
                 float dw, pd;
                 wm_pair_bwd<HD>(x, j > i || sKv[j] == 0, dead_i, lse, ks4[r], gm[r], gc[r], delta, rsq_hd, dw, pd);
                 dwt[t][r] = dw;
@@ -304,7 +308,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
       }
     }
     dwsum = wm_colsum(dwsum);
-    if (MET == WM_KL && vi) {
+    if (wm_kl(MET) && vi) {
       // dmq = (mq - mk) sum_j dW Y1, dmk = -dmq; row parts: dck = -0.5 / ck^2 sum_j dW Y2, dcq = -0.5 / cq sum_j dW
 #pragma unroll
       for (int ft = 0; ft < S::KC / 16; ++ft) {
@@ -314,16 +318,17 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
           const float4 q = *reinterpret_cast<const float4*>(a.Qm + qrow * a.ldqm + co + k0);
           const float4 k = *reinterpret_cast<const float4*>(a.Km + qrow * a.ldkm + co + k0);
           const float4 dq = make_float4((q.x - k.x) * acc[0], (q.y - k.y) * acc[1], (q.z - k.z) * acc[2], (q.w - k.w) * acc[3]);
-          *reinterpret_cast<float4*>(a.dQm + qrow * a.ldd + co + k0) = dq;
-          *reinterpret_cast<float4*>(a.dKm + qrow * a.ldd + co + k0) = make_float4(-dq.x, -dq.y, -dq.z, -dq.w);
+          *reinterpret_cast<float4*>(a.dQm + qrow * a.ldd + co + k0) = wm_gate4(hl, k0, dq);
+          *reinterpret_cast<float4*>(a.dKm + qrow * a.ldd + co + k0) = wm_gate4(hl, k0, make_float4(-dq.x, -dq.y, -dq.z, -dq.w));
         } else {
           const int f0 = k0 - HD;
           const float4 kc = *reinterpret_cast<const float4*>(a.Kc + qrow * a.ldkc + co + f0);
           const float4 qc = *reinterpret_cast<const float4*>(a.Qc + qrow * a.ldqc + co + f0);
-          *reinterpret_cast<float4*>(a.dKc + qrow * a.ldd + co + f0) =
-              make_float4(-0.5f * acc[0] / (kc.x * kc.x), -0.5f * acc[1] / (kc.y * kc.y), -0.5f * acc[2] / (kc.z * kc.z), -0.5f * acc[3] / (kc.w * kc.w));
-          *reinterpret_cast<float4*>(a.dQc + qrow * a.ldd + co + f0) =
-              make_float4(-0.5f * dwsum / qc.x, -0.5f * dwsum / qc.y, -0.5f * dwsum / qc.z, -0.5f * dwsum / qc.w);
+          // a pad lane (kc = qc = 0) takes +0.0 by the select: 0 / 0 and dwsum / 0 are never stored
+          *reinterpret_cast<float4*>(a.dKc + qrow * a.ldd + co + f0) = wm_gate4(hl, f0,
+              make_float4(-0.5f * acc[0] / (kc.x * kc.x), -0.5f * acc[1] / (kc.y * kc.y), -0.5f * acc[2] / (kc.z * kc.z), -0.5f * acc[3] / (kc.w * kc.w)));
+          *reinterpret_cast<float4*>(a.dQc + qrow * a.ldd + co + f0) = wm_gate4(hl, f0,
+              make_float4(-0.5f * dwsum / qc.x, -0.5f * dwsum / qc.y, -0.5f * dwsum / qc.z, -0.5f * dwsum / qc.w));
         }
       }
     } else if (vi) {
@@ -354,10 +359,10 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
     const size_t krow = row_b + (vj ? j : 0);
     Frag8 fk[S::KB], fvm[KBV], fvc[KBV];
     float nk;                                  // KL: the column bias sum log ck_j
-    if constexpr (MET == WM_KL) {
+    if constexpr (wm_kl(MET)) {
 #pragma unroll
-      for (int kb = 0; kb < S::KB; ++kb) fk[kb] = wm_kl_frag<HD, false>(nullptr, nullptr, a.Qc + krow * a.ldqc + co, a.Kc + krow * a.ldkc + co, kb, g, vj);
-      nk = vj ? wm_kl_logsum<HD>(a.Kc + krow * a.ldkc + co) : 0.f;
+      for (int kb = 0; kb < S::KB; ++kb) fk[kb] = wm_kl_frag<HD, false>(nullptr, nullptr, a.Qc + krow * a.ldqc + co, a.Kc + krow * a.ldkc + co, kb, g, vj, hl);
+      nk = vj ? wm_kl_logsum<HD>(a.Kc + krow * a.ldkc + co, hl) : 0.f;
     } else {
 #pragma unroll
       for (int kb = 0; kb < S::KB; ++kb) fk[kb] = wm_cat_frag<HD>(a.Km + krow * a.ldkm + co, a.Kc + krow * a.ldkc + co, kb, g, vj);
@@ -388,9 +393,9 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
       wm_stage_nat<HD>(sX1, a.dOc + (row_b + q0) * a.lddoc + co, a.lddoc, Lc, CH);
       wm_stage_t<false>(sT0, a.dOm + (row_b + q0) * a.lddom + co, a.lddom, Lc, CH, HD);
       wm_stage_t<false>(sT1, a.dOc + (row_b + q0) * a.lddoc + co, a.lddoc, Lc, CH, HD);
-      if constexpr (MET == WM_KL) {      // X = [(mq - mk)^2 | 1/ck] rows and row biases; the transpose after the barrier
+      if constexpr (wm_kl(MET)) {      // X = [(mq - mk)^2 | 1/ck] rows and row biases; the transpose after the barrier
         wm_kl_stage<HD, true>(sC, sN, a.Qm + (row_b + q0) * a.ldqm + co, a.ldqm, a.Km + (row_b + q0) * a.ldkm + co, a.ldkm,
-                              a.Qc + (row_b + q0) * a.ldqc + co, a.ldqc, a.Kc + (row_b + q0) * a.ldkc + co, a.ldkc, Lc, CH);
+                              a.Qc + (row_b + q0) * a.ldqc + co, a.ldqc, a.Kc + (row_b + q0) * a.ldkc + co, a.ldkc, Lc, CH, hl);
         __syncthreads();
         wm_kl_transpose<HD>(sCT, sC, CH);
       } else {
@@ -424,7 +429,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
             for (int r = 0; r < 4; ++r) {
               const int il = itl * 16 + 4 * g + r, i = q0 + il;
               if (i < L && vj) {
-                const float x = MET == WM_KL ? wm_kl_x(nk, sN[il], acc[r], (float)HD, rsq_hd)
+                const float x = wm_kl(MET) ? wm_kl_x(nk, sN[il], acc[r], fhl, rsq_hd)
                                              : -((nk + sN[il]) - 2.0f * acc[r]) * rsq_hd;      // nk + nq: the same two numbers as in the forward, addition commutes
                 const float ks_ = wm_keep_scale(a.drop, key_rng, (idx_bh + (uint32_t)i) * (uint32_t)L + (uint32_t)j);
                 float dw, pd;
@@ -451,7 +456,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
       }
     }
     dwsum = wm_colsum(dwsum);
-    if (MET == WM_KL && vj) {
+    if (wm_kl(MET) && vj) {
       // column parts, added to pass A's row parts (same wave, same lane): dck += 0.5 / ck sum_i dW - 0.5 / ck^2 sum_i dW X1,
       // dcq += 0.5 sum_i dW X2
 #pragma unroll
@@ -462,12 +467,12 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
           const float4 kc = *reinterpret_cast<const float4*>(a.Kc + krow * a.ldkc + co + k0);
           float4* dkc = reinterpret_cast<float4*>(a.dKc + krow * a.ldd + co + k0);
           const float4 y = make_float4(1.0f / kc.x, 1.0f / kc.y, 1.0f / kc.z, 1.0f / kc.w), o = *dkc;
-          *dkc = make_float4(o.x + (0.5f * dwsum * y.x - 0.5f * acc[0] * y.x * y.x), o.y + (0.5f * dwsum * y.y - 0.5f * acc[1] * y.y * y.y),
-                             o.z + (0.5f * dwsum * y.z - 0.5f * acc[2] * y.z * y.z), o.w + (0.5f * dwsum * y.w - 0.5f * acc[3] * y.w * y.w));
+          *dkc = wm_gate4(hl, k0, make_float4(o.x + (0.5f * dwsum * y.x - 0.5f * acc[0] * y.x * y.x), o.y + (0.5f * dwsum * y.y - 0.5f * acc[1] * y.y * y.y),
+                                              o.z + (0.5f * dwsum * y.z - 0.5f * acc[2] * y.z * y.z), o.w + (0.5f * dwsum * y.w - 0.5f * acc[3] * y.w * y.w)));
         } else {
           float4* dqc = reinterpret_cast<float4*>(a.dQc + krow * a.ldd + co + k0 - HD);
           const float4 o = *dqc;
-          *dqc = make_float4(o.x + 0.5f * acc[0], o.y + 0.5f * acc[1], o.z + 0.5f * acc[2], o.w + 0.5f * acc[3]);
+          *dqc = wm_gate4(hl, k0 - HD, make_float4(o.x + 0.5f * acc[0], o.y + 0.5f * acc[1], o.z + 0.5f * acc[2], o.w + 0.5f * acc[3]));
         }
       }
     } else if (vj) {

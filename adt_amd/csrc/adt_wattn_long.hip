@@ -22,7 +22,7 @@ static int launch_wattn_long(const AttnPlan& p, bool bwd, const WAttnArgs& a, hi
   const void* fn = bwd ? (const void*)k_wattn_long_bwd<PREC, HD, MET, CHB> : (const void*)k_wattn_long_fwd<PREC, HD, MET, CHF>;
   static AdtLdsOptIn optin[2];
   return adt_launch_lds1(fn, dim3(a.B * a.H, p.grid_y), dim3(p.waves * 64), p.lds_bytes, a, s,
-                         MET == WM_KL ? (bwd ? "klattn_long_bwd" : "klattn_long_fwd") : (bwd ? "wattn_long_bwd" : "wattn_long_fwd"), optin[bwd ? 1 : 0]);
+                         wm_kl(MET) ? (bwd ? "klattn_long_bwd" : "klattn_long_fwd") : (bwd ? "wattn_long_bwd" : "wattn_long_fwd"), optin[bwd ? 1 : 0]);
 }
 
 template <int PREC, int MET>
@@ -36,7 +36,7 @@ static int launch_wattn_long_hd(const AttnPlan& p, bool bwd, const WAttnArgs& a,
 // the call (16-byte loads and stores along the features).
 template <int MET>
 static int wattn_long(int prec, bool bwd, const WAttnArgs& a, float p, uint32_t b_offset, const int* lds, int nlds, void* stream) {
-  const char* what = MET == WM_KL ? (bwd ? "klattn_long_bwd" : "klattn_long_fwd") : (bwd ? "wattn_long_bwd" : "wattn_long_fwd");
+  const char* what = wm_kl(MET) ? (bwd ? "klattn_long_bwd" : "klattn_long_fwd") : (bwd ? "wattn_long_bwd" : "wattn_long_fwd");
   const AttnPlan plan = adt_wattn_long_plan(prec, a.hd, a.L, bwd);
   if (plan.error[0]) return adt_set_error("%s: %s", what, plan.error);
   if (a.B <= 0 || a.H <= 0) return adt_set_error("%s: empty shape", what);
@@ -154,6 +154,27 @@ int adt_klattn_long_bwd(int prec, const float* Qm, int ldqm, const float* Qc, in
                         float* dVc, int ldd, void* stream) {
   return wattn_long_bwd<WM_KL>(prec, Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, Om, ldom, Oc, ldoc, LSE, dOm, lddom, dOc, lddoc,
                                B, H, L, hd, p, seed, site, b_offset, dQm, dQc, dKm, dKc, dVm, dVc, ldd, stream);
+}
+
+// The KL attention on padded heads: the scale given, lanes [0, hd_live) live, the pad lanes (cov = 0) left out of
+// 1 / ck, the log-determinants and the subtracted head size, and +0.0 in all six gradients.
+int adt_klattn_long_scaled_fwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                               const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float scale,
+                               int hd_live, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc,
+                               float* LSE, void* stream) {
+  if (!(scale > 0.f) || hd_live < 1 || hd_live > hd) return adt_set_error("klattn_long_scaled_fwd: scale %g must be positive and 1 <= hd_live=%d <= hd=%d", (double)scale, hd_live, hd);
+  return wattn_long_fwd<WM_KLP>(prec, Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, B, H, L, hd, p, seed, site, b_offset, Om, ldom,
+                               Oc, ldoc, LSE, stream, scale, hd_live);
+}
+
+int adt_klattn_long_scaled_bwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                               const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc,
+                               int ldoc, const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd,
+                               float scale, int hd_live, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc,
+                               float* dKm, float* dKc, float* dVm, float* dVc, int ldd, void* stream) {
+  if (!(scale > 0.f) || hd_live < 1 || hd_live > hd) return adt_set_error("klattn_long_scaled_bwd: scale %g must be positive and 1 <= hd_live=%d <= hd=%d", (double)scale, hd_live, hd);
+  return wattn_long_bwd<WM_KLP>(prec, Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, Om, ldom, Oc, ldoc, LSE, dOm, lddom, dOc, lddoc,
+                               B, H, L, hd, p, seed, site, b_offset, dQm, dQc, dKm, dKc, dVm, dVc, ldd, stream, scale, hd_live);
 }
 
 }  // extern "C"

@@ -30,7 +30,9 @@
 namespace adt {
 
 constexpr int WM_NW = 4;
-constexpr int WM_W = 0, WM_KL = 1;      // score of the pair: Wasserstein or KL divergence
+constexpr int WM_W = 0, WM_KL = 1, WM_KLP = 2;      // score of the pair: Wasserstein, KL divergence, KL divergence on padded heads (hd_live)
+constexpr bool wm_kl(int met) { return met != WM_W; }
+constexpr int WM_ALL_LIVE = 0x7fffffff;      // hl of an unpadded head: `lane < hl` is true for every lane the compiler cannot bound
 
 template <int HD>
 struct WmShape {
@@ -99,18 +101,27 @@ ADT_DEVICE_INLINE void wm_stage_nat(float* dst, const float* g, int ld, int L, i
 
 // ---- KL images -------------------------------------------------------------------------------------------------------------------
 // sum_d log c[d] of one token in one fixed order: the staged bias of a row and the one a pass computes for a row it owns are one number
+// Padded heads (the adt_klattn_*_scaled_* entry points): hl = a.hd_live lanes of a head are live, the pad lanes above them hold cov = 0.
+// They stay out of the sum (log 0 = -inf) and their 1 / kc is +0.0, by selects on the lane index -- never a product with zero, 0 * inf is
+// NaN and the matrix cores would carry it into whole tiles.  Only MET = WM_KLP reads hd_live: under WM_KL hl is the constant WM_ALL_LIVE,
+// every select folds away and the kernel is the code it was (the tiled widths' step time is the reason: a runtime hl cost them 4.7 %,
+// and hl = HD, which leaves the selects the compiler cannot prove, still 0.6 %).
+ADT_DEVICE_INLINE float4 wm_gate4(int hl, int f0, float4 v) {
+  return make_float4(f0 < hl ? v.x : 0.f, f0 + 1 < hl ? v.y : 0.f, f0 + 2 < hl ? v.z : 0.f, f0 + 3 < hl ? v.w : 0.f);
+}
+
 template <int HD>
-ADT_DEVICE_INLINE float wm_kl_logsum(const float* c_row) {
+ADT_DEVICE_INLINE float wm_kl_logsum(const float* c_row, int hl) {
   float s = 0.f;
-  for (int k = 0; k < HD; ++k) s += logf(c_row[k]);
+  for (int k = 0; k < HD; ++k) s += k < hl ? logf(c_row[k]) : 0.f;
   return s;
 }
 
 // the KL row image X (XIMG) = [(qm - km)^2 | 1/kc] or column image Y = [1/kc | qc] of one token, 4 features from 16-byte loads
 template <bool XIMG>
-ADT_DEVICE_INLINE void wm_kl_img4(const float* qm, const float* km, const float* qc, const float* kc, int c4, int HD_, float4& lo, float4& hi) {
+ADT_DEVICE_INLINE void wm_kl_img4(const float* qm, const float* km, const float* qc, const float* kc, int c4, int hl, float4& lo, float4& hi) {
   const float4 k = *reinterpret_cast<const float4*>(kc + c4);
-  const float4 ik = make_float4(1.0f / k.x, 1.0f / k.y, 1.0f / k.z, 1.0f / k.w);
+  const float4 ik = wm_gate4(hl, c4, make_float4(1.0f / k.x, 1.0f / k.y, 1.0f / k.z, 1.0f / k.w));
   if (XIMG) {
     const float4 q = *reinterpret_cast<const float4*>(qm + c4), m = *reinterpret_cast<const float4*>(km + c4);
     const float4 d = make_float4(q.x - m.x, q.y - m.y, q.z - m.z, q.w - m.w);
@@ -125,17 +136,17 @@ ADT_DEVICE_INLINE void wm_kl_img4(const float* qm, const float* km, const float*
 // rows [0, Lp) of the KL image (rows >= L zero) and their log-det biases: X with sum log qc, Y with sum log kc
 template <int HD, bool XIMG>
 ADT_DEVICE_INLINE void wm_kl_stage(float* sImg, float* sBias, const float* qm, int ldqm, const float* km, int ldkm, const float* qc, int ldqc,
-                                   const float* kc, int ldkc, int L, int Lp) {
+                                   const float* kc, int ldkc, int L, int Lp, int hl) {
   constexpr int RS = WmShape<HD>::RSK, V = HD / 4;
   for (int i = threadIdx.x; i < Lp * V; i += WM_NW * 64) {
     const int r = i / V, c4 = (i % V) * 4;
     float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
-    if (r < L) wm_kl_img4<XIMG>(qm + (size_t)r * ldqm, km + (size_t)r * ldkm, qc + (size_t)r * ldqc, kc + (size_t)r * ldkc, c4, HD, lo, hi);
+    if (r < L) wm_kl_img4<XIMG>(qm + (size_t)r * ldqm, km + (size_t)r * ldkm, qc + (size_t)r * ldqc, kc + (size_t)r * ldkc, c4, hl, lo, hi);
     *reinterpret_cast<float4*>(sImg + r * RS + c4) = lo;
     *reinterpret_cast<float4*>(sImg + r * RS + HD + c4) = hi;
   }
   for (int r = threadIdx.x; r < Lp; r += WM_NW * 64)
-    sBias[r] = r < L ? wm_kl_logsum<HD>(XIMG ? qc + (size_t)r * ldqc : kc + (size_t)r * ldkc) : 0.f;
+    sBias[r] = r < L ? wm_kl_logsum<HD>(XIMG ? qc + (size_t)r * ldqc : kc + (size_t)r * ldkc, hl) : 0.f;
 }
 
 // transposed copy dst[k][r] (row stride Lp + 4) of a staged image (call after the barrier that follows wm_kl_stage)
@@ -151,7 +162,7 @@ ADT_DEVICE_INLINE void wm_kl_transpose(float* dst, const float* sImg, int Lp) {
 
 // slots 8g .. 8g+7 of block kb of the KL image of one token straight from global memory (the same arithmetic as wm_kl_stage)
 template <int HD, bool XIMG>
-ADT_DEVICE_INLINE Frag8 wm_kl_frag(const float* qm, const float* km, const float* qc, const float* kc, int kb, int g, bool valid) {
+ADT_DEVICE_INLINE Frag8 wm_kl_frag(const float* qm, const float* km, const float* qc, const float* kc, int kb, int g, bool valid, int hl) {
   Frag8 f;
 #pragma unroll
   for (int j = 0; j < 8; ++j) f.v[j] = 0.f;
@@ -160,7 +171,7 @@ ADT_DEVICE_INLINE Frag8 wm_kl_frag(const float* qm, const float* km, const float
 #pragma unroll
   for (int h4 = 0; h4 < 2; ++h4) {
     float4 lo, hi;
-    wm_kl_img4<XIMG>(qm, km, qc, kc, c + 4 * h4, HD, lo, hi);
+    wm_kl_img4<XIMG>(qm, km, qc, kc, c + 4 * h4, hl, lo, hi);
     const float4 v = k0 < HD ? lo : hi;
     f.v[4 * h4 + 0] = v.x; f.v[4 * h4 + 1] = v.y; f.v[4 * h4 + 2] = v.z; f.v[4 * h4 + 3] = v.w;
   }
@@ -239,6 +250,8 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_fwd(WAttnArgs a) {
   adt_prefetch_kernargs<sizeof(WAttnArgs) <= 512 ? sizeof(WAttnArgs) : 512>();      // every kernarg line in one scalar-cache round trip (adt_common.cuh)
   typedef WmShape<HD> S;
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int hl = MET == WM_KLP ? a.hd_live : WM_ALL_LIVE;      // KL: the live lanes of a head (WM_ALL_LIVE: every lane test folds to true)
+  const float fhl = MET == WM_KLP ? (float)a.hd_live : (float)HD;      // the dimension the divergence subtracts
   const int L = a.L, Lp = (L + 31) / 32 * 32, nt16 = (L + 15) / 16, RST = Lp + 4;
   float* sK = smem;                          // [Lp][RSK]  [mk | sqrt Sk]     (KL: Y = [1/ck | cq])
   float* sNk = sK + Lp * S::RSK;             // [Lp]                          (KL: column bias sum log ck)
@@ -253,8 +266,8 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_fwd(WAttnArgs a) {
   for (int i = threadIdx.x; i < Lp; i += WM_NW * 64) sKv[i] = (i < L && a.kid[row_b + i] > 0) ? 1.f : 0.f;
   wm_stage_t<false>(sVmT, a.Vm + row_b * a.ldvm + h * HD, a.ldvm, L, Lp, HD);
   wm_stage_t<false>(sVcT, a.Vc + row_b * a.ldvc + h * HD, a.ldvc, L, Lp, HD);
-  if constexpr (MET == WM_KL)
-    wm_kl_stage<HD, false>(sK, sNk, nullptr, 0, nullptr, 0, a.Qc + row_b * a.ldqc + h * HD, a.ldqc, a.Kc + row_b * a.ldkc + h * HD, a.ldkc, L, Lp);
+  if constexpr (wm_kl(MET))
+    wm_kl_stage<HD, false>(sK, sNk, nullptr, 0, nullptr, 0, a.Qc + row_b * a.ldqc + h * HD, a.ldqc, a.Kc + row_b * a.ldkc + h * HD, a.ldkc, L, Lp, hl);
   else
     wm_stage_cat<HD>(sK, sNk, a.Km + row_b * a.ldkm + h * HD, a.ldkm, a.Kc + row_b * a.ldkc + h * HD, a.ldkc, L, Lp);
   __syncthreads();
@@ -273,12 +286,12 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_fwd(WAttnArgs a) {
     const float* qc_row = a.Qc + (row_b + (vi ? i : 0)) * a.ldqc + h * HD;
     Frag8 fq[S::KB];
     float nq;                                  // KL: the row bias sum log cq_i
-    if constexpr (MET == WM_KL) {
+    if constexpr (wm_kl(MET)) {
       const float* km_row = a.Km + (row_b + (vi ? i : 0)) * a.ldkm + h * HD;
       const float* kc_row = a.Kc + (row_b + (vi ? i : 0)) * a.ldkc + h * HD;
 #pragma unroll
-      for (int kb = 0; kb < S::KB; ++kb) fq[kb] = wm_kl_frag<HD, true>(qm_row, km_row, qc_row, kc_row, kb, g, vi);
-      nq = vi ? wm_kl_logsum<HD>(qc_row) : 0.f;
+      for (int kb = 0; kb < S::KB; ++kb) fq[kb] = wm_kl_frag<HD, true>(qm_row, km_row, qc_row, kc_row, kb, g, vi, hl);
+      nq = vi ? wm_kl_logsum<HD>(qc_row, hl) : 0.f;
     } else {
 #pragma unroll
       for (int kb = 0; kb < S::KB; ++kb) fq[kb] = wm_cat_frag<HD>(qm_row, qc_row, kb, g, vi);
@@ -298,7 +311,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_fwd(WAttnArgs a) {
         for (int r = 0; r < 4; ++r) {
           const int j = kt * 16 + 4 * g + r;
           if (j < L) {
-            const float x = MET == WM_KL ? wm_kl_x(sNk[j], nq, acc[r], (float)HD, rsq_hd) : -((sNk[j] + nq) - 2.0f * acc[r]) * rsq_hd;
+            const float x = wm_kl(MET) ? wm_kl_x(sNk[j], nq, acc[r], fhl, rsq_hd) : -((sNk[j] + nq) - 2.0f * acc[r]) * rsq_hd;
             const bool masked = j > i || sKv[j] == 0.f;
             if (!masked || dead_i) {           // masked keys of a live row: exp(x - 2^32 - m) == 0, left at -inf
               s[kt][r] = w_score(x, masked, dead_i);
@@ -379,6 +392,8 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
   typedef WmShape<HD> S;
   constexpr int KBV = (HD + 31) / 32;
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int hl = MET == WM_KLP ? a.hd_live : WM_ALL_LIVE;      // KL: the live lanes of a head (WM_ALL_LIVE: every lane test folds to true)
+  const float fhl = MET == WM_KLP ? (float)a.hd_live : (float)HD;      // the dimension the divergence subtracts
   const int L = a.L, Lp = (L + 31) / 32 * 32, nt16 = (L + 15) / 16, npair = (nt16 + 1) / 2, RST = Lp + 4;
   float* sC = smem;                          // A: [mk | sqrt Sk] rows   | B: [mq | sqrt Sq] rows
   float* sN = sC + Lp * S::RSK;              // A: key norms            | B: query norms
@@ -413,17 +428,17 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
     sDelta[i] = dl;
   }
   const int co = h * HD;
-  if constexpr (MET == WM_KL) {      // A: Y = [1/ck | cq] rows and column biases; its transpose after the barrier
-    wm_kl_stage<HD, false>(sC, sN, nullptr, 0, nullptr, 0, a.Qc + row_b * a.ldqc + co, a.ldqc, a.Kc + row_b * a.ldkc + co, a.ldkc, L, Lp);
+  if constexpr (wm_kl(MET)) {      // A: Y = [1/ck | cq] rows and column biases; its transpose after the barrier
+    wm_kl_stage<HD, false>(sC, sN, nullptr, 0, nullptr, 0, a.Qc + row_b * a.ldqc + co, a.ldqc, a.Kc + row_b * a.ldkc + co, a.ldkc, L, Lp, hl);
   } else {
     wm_stage_t<false>(sCT, a.Km + row_b * a.ldkm + h * HD, a.ldkm, L, Lp, HD);
     wm_stage_t<true>(sCT + HD * RST, a.Kc + row_b * a.ldkc + h * HD, a.ldkc, L, Lp, HD);
   }
   wm_stage_nat<HD>(sX0, a.Vm + row_b * a.ldvm + h * HD, a.ldvm, L, Lp);
   wm_stage_nat<HD>(sX1, a.Vc + row_b * a.ldvc + h * HD, a.ldvc, L, Lp);
-  if constexpr (MET != WM_KL) wm_stage_cat<HD>(sC, sN, a.Km + row_b * a.ldkm + h * HD, a.ldkm, a.Kc + row_b * a.ldkc + h * HD, a.ldkc, L, Lp);
+  if constexpr (!wm_kl(MET)) wm_stage_cat<HD>(sC, sN, a.Km + row_b * a.ldkm + h * HD, a.ldkm, a.Kc + row_b * a.ldkc + h * HD, a.ldkc, L, Lp);
   __syncthreads();
-  if constexpr (MET == WM_KL) wm_kl_transpose<HD>(sCT, sC, Lp);
+  if constexpr (wm_kl(MET)) wm_kl_transpose<HD>(sCT, sC, Lp);
   for (int i = threadIdx.x; i < Lp; i += WM_NW * 64) {
     float cnt = 0.f;
     for (int j = 0; j <= i && j < L; ++j) cnt += sKv[j];
@@ -438,11 +453,11 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
     const size_t qrow = row_b + (vi ? i : 0);
     Frag8 fq[S::KB], fdm[KBV], fdc[KBV];
     float nq;
-    if constexpr (MET == WM_KL) {
+    if constexpr (wm_kl(MET)) {
 #pragma unroll
       for (int kb = 0; kb < S::KB; ++kb)
-        fq[kb] = wm_kl_frag<HD, true>(a.Qm + qrow * a.ldqm + co, a.Km + qrow * a.ldkm + co, a.Qc + qrow * a.ldqc + co, a.Kc + qrow * a.ldkc + co, kb, g, vi);
-      nq = vi ? wm_kl_logsum<HD>(a.Qc + qrow * a.ldqc + co) : 0.f;
+        fq[kb] = wm_kl_frag<HD, true>(a.Qm + qrow * a.ldqm + co, a.Km + qrow * a.ldkm + co, a.Qc + qrow * a.ldqc + co, a.Kc + qrow * a.ldkc + co, kb, g, vi, hl);
+      nq = vi ? wm_kl_logsum<HD>(a.Qc + qrow * a.ldqc + co, hl) : 0.f;
     } else {
 #pragma unroll
       for (int kb = 0; kb < S::KB; ++kb) fq[kb] = wm_cat_frag<HD>(a.Qm + qrow * a.ldqm + h * HD, a.Qc + qrow * a.ldqc + h * HD, kb, g, vi);
@@ -485,7 +500,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
           for (int r = 0; r < 4; ++r) {
             const int j = kt * 16 + 4 * g + r;
             if (j < L && vi) {
-              const float x = MET == WM_KL ? wm_kl_x(sN[j], nq, acc[r], (float)HD, rsq_hd) : -((sN[j] + nq) - 2.0f * acc[r]) * rsq_hd;
+              const float x = wm_kl(MET) ? wm_kl_x(sN[j], nq, acc[r], fhl, rsq_hd) : -((sN[j] + nq) - 2.0f * acc[r]) * rsq_hd;
               float dw, pd;
               wm_pair_bwd<HD>(x, j > i || sKv[j] == 0.f, dead_i, lse, ks4[r], gm[r], gc[r], delta, rsq_hd, dw, pd);
               dwt[t][r] = dw;
@@ -499,7 +514,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
       for (int ft = 0; ft < S::KC / 16; ++ft) accq[ft] = mma16<PREC>(accq[ft], frag_slotc(sCT + (16 * ft + c) * RST + 32 * kp, g), bdw);
     }
     dwsum = wm_colsum(dwsum);
-    if (MET == WM_KL && vi) {
+    if (wm_kl(MET) && vi) {
       // dmq = (mq - mk) sum_j dW Y1, dmk = -dmq; row parts: dck = -0.5 / ck^2 sum_j dW Y2, dcq = -0.5 / cq sum_j dW
 #pragma unroll
       for (int ft = 0; ft < S::KC / 16; ++ft) {
@@ -509,16 +524,17 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
           const float4 q = *reinterpret_cast<const float4*>(a.Qm + qrow * a.ldqm + co + k0);
           const float4 k = *reinterpret_cast<const float4*>(a.Km + qrow * a.ldkm + co + k0);
           const float4 dq = make_float4((q.x - k.x) * acc[0], (q.y - k.y) * acc[1], (q.z - k.z) * acc[2], (q.w - k.w) * acc[3]);
-          *reinterpret_cast<float4*>(a.dQm + qrow * a.ldd + co + k0) = dq;
-          *reinterpret_cast<float4*>(a.dKm + qrow * a.ldd + co + k0) = make_float4(-dq.x, -dq.y, -dq.z, -dq.w);
+          *reinterpret_cast<float4*>(a.dQm + qrow * a.ldd + co + k0) = wm_gate4(hl, k0, dq);
+          *reinterpret_cast<float4*>(a.dKm + qrow * a.ldd + co + k0) = wm_gate4(hl, k0, make_float4(-dq.x, -dq.y, -dq.z, -dq.w));
         } else {
           const int f0 = k0 - HD;
           const float4 kc = *reinterpret_cast<const float4*>(a.Kc + qrow * a.ldkc + co + f0);
           const float4 qc = *reinterpret_cast<const float4*>(a.Qc + qrow * a.ldqc + co + f0);
-          *reinterpret_cast<float4*>(a.dKc + qrow * a.ldd + co + f0) =
-              make_float4(-0.5f * acc[0] / (kc.x * kc.x), -0.5f * acc[1] / (kc.y * kc.y), -0.5f * acc[2] / (kc.z * kc.z), -0.5f * acc[3] / (kc.w * kc.w));
-          *reinterpret_cast<float4*>(a.dQc + qrow * a.ldd + co + f0) =
-              make_float4(-0.5f * dwsum / qc.x, -0.5f * dwsum / qc.y, -0.5f * dwsum / qc.z, -0.5f * dwsum / qc.w);
+          // a pad lane (kc = qc = 0) takes +0.0 by the select: 0 / 0 and dwsum / 0 are never stored
+          *reinterpret_cast<float4*>(a.dKc + qrow * a.ldd + co + f0) = wm_gate4(hl, f0,
+              make_float4(-0.5f * acc[0] / (kc.x * kc.x), -0.5f * acc[1] / (kc.y * kc.y), -0.5f * acc[2] / (kc.z * kc.z), -0.5f * acc[3] / (kc.w * kc.w)));
+          *reinterpret_cast<float4*>(a.dQc + qrow * a.ldd + co + f0) = wm_gate4(hl, f0,
+              make_float4(-0.5f * dwsum / qc.x, -0.5f * dwsum / qc.y, -0.5f * dwsum / qc.z, -0.5f * dwsum / qc.w));
         }
       }
     } else if (vi) {
@@ -544,7 +560,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
 
   // ---- phase B staging: the query side over the same LDS ------------------------------------------------------------------------------
   __syncthreads();
-  if constexpr (MET != WM_KL) {
+  if constexpr (!wm_kl(MET)) {
     wm_stage_t<false>(sCT, a.Qm + row_b * a.ldqm + h * HD, a.ldqm, L, Lp, HD);
     wm_stage_t<true>(sCT + HD * RST, a.Qc + row_b * a.ldqc + h * HD, a.ldqc, L, Lp, HD);
   }
@@ -552,9 +568,9 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
   wm_stage_nat<HD>(sX1, a.dOc + row_b * a.lddoc + h * HD, a.lddoc, L, Lp);
   wm_stage_t<false>(sT0, a.dOm + row_b * a.lddom + h * HD, a.lddom, L, Lp, HD);
   wm_stage_t<false>(sT1, a.dOc + row_b * a.lddoc + h * HD, a.lddoc, L, Lp, HD);
-  if constexpr (MET == WM_KL) {      // B: X = [(mq - mk)^2 | 1/ck] rows and row biases; its transpose after the barrier
+  if constexpr (wm_kl(MET)) {      // B: X = [(mq - mk)^2 | 1/ck] rows and row biases; its transpose after the barrier
     wm_kl_stage<HD, true>(sC, sN, a.Qm + row_b * a.ldqm + co, a.ldqm, a.Km + row_b * a.ldkm + co, a.ldkm, a.Qc + row_b * a.ldqc + co, a.ldqc,
-                          a.Kc + row_b * a.ldkc + co, a.ldkc, L, Lp);
+                          a.Kc + row_b * a.ldkc + co, a.ldkc, L, Lp, hl);
     __syncthreads();
     wm_kl_transpose<HD>(sCT, sC, Lp);
   } else {
@@ -569,10 +585,10 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
     const size_t krow = row_b + (vj ? j : 0);
     Frag8 fk[S::KB], fvm[KBV], fvc[KBV];
     float nk;                                  // KL: the column bias sum log ck_j
-    if constexpr (MET == WM_KL) {
+    if constexpr (wm_kl(MET)) {
 #pragma unroll
-      for (int kb = 0; kb < S::KB; ++kb) fk[kb] = wm_kl_frag<HD, false>(nullptr, nullptr, a.Qc + krow * a.ldqc + co, a.Kc + krow * a.ldkc + co, kb, g, vj);
-      nk = vj ? wm_kl_logsum<HD>(a.Kc + krow * a.ldkc + co) : 0.f;
+      for (int kb = 0; kb < S::KB; ++kb) fk[kb] = wm_kl_frag<HD, false>(nullptr, nullptr, a.Qc + krow * a.ldqc + co, a.Kc + krow * a.ldkc + co, kb, g, vj, hl);
+      nk = vj ? wm_kl_logsum<HD>(a.Kc + krow * a.ldkc + co, hl) : 0.f;
     } else {
 #pragma unroll
       for (int kb = 0; kb < S::KB; ++kb) fk[kb] = wm_cat_frag<HD>(a.Km + krow * a.ldkm + h * HD, a.Kc + krow * a.ldkc + h * HD, kb, g, vj);
@@ -615,7 +631,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
           for (int r = 0; r < 4; ++r) {
             const int i = it * 16 + 4 * g + r;
             if (i < L && vj) {
-              const float x = MET == WM_KL ? wm_kl_x(nk, sN[i], acc[r], (float)HD, rsq_hd)
+              const float x = wm_kl(MET) ? wm_kl_x(nk, sN[i], acc[r], fhl, rsq_hd)
                                            : -((nk + sN[i]) - 2.0f * acc[r]) * rsq_hd;      // nk + nq: the same two numbers as in the forward, addition commutes
               const float ks_ = wm_keep_scale(a.drop, key_rng, (idx_bh + (uint32_t)i) * (uint32_t)L + (uint32_t)j);
               float dw, pd;
@@ -641,7 +657,7 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
       }
     }
     dwsum = wm_colsum(dwsum);
-    if (MET == WM_KL && vj) {
+    if (wm_kl(MET) && vj) {
       // column parts, added to pass A's row parts (same wave, same lane): dck += 0.5 / ck sum_i dW - 0.5 / ck^2 sum_i dW X1,
       // dcq += 0.5 sum_i dW X2
 #pragma unroll
@@ -652,12 +668,12 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_mfma_bwd(WAttnArgs a) {
           const float4 kc = *reinterpret_cast<const float4*>(a.Kc + krow * a.ldkc + co + k0);
           float4* dkc = reinterpret_cast<float4*>(a.dKc + krow * a.ldd + co + k0);
           const float4 y = make_float4(1.0f / kc.x, 1.0f / kc.y, 1.0f / kc.z, 1.0f / kc.w), o = *dkc;
-          *dkc = make_float4(o.x + (0.5f * dwsum * y.x - 0.5f * acc[0] * y.x * y.x), o.y + (0.5f * dwsum * y.y - 0.5f * acc[1] * y.y * y.y),
-                             o.z + (0.5f * dwsum * y.z - 0.5f * acc[2] * y.z * y.z), o.w + (0.5f * dwsum * y.w - 0.5f * acc[3] * y.w * y.w));
+          *dkc = wm_gate4(hl, k0, make_float4(o.x + (0.5f * dwsum * y.x - 0.5f * acc[0] * y.x * y.x), o.y + (0.5f * dwsum * y.y - 0.5f * acc[1] * y.y * y.y),
+                                              o.z + (0.5f * dwsum * y.z - 0.5f * acc[2] * y.z * y.z), o.w + (0.5f * dwsum * y.w - 0.5f * acc[3] * y.w * y.w)));
         } else {
           float4* dqc = reinterpret_cast<float4*>(a.dQc + krow * a.ldd + co + k0 - HD);
           const float4 o = *dqc;
-          *dqc = make_float4(o.x + 0.5f * acc[0], o.y + 0.5f * acc[1], o.z + 0.5f * acc[2], o.w + 0.5f * acc[3]);
+          *dqc = wm_gate4(hl, k0 - HD, make_float4(o.x + 0.5f * acc[0], o.y + 0.5f * acc[1], o.z + 0.5f * acc[2], o.w + 0.5f * acc[3]));
         }
       }
     } else if (vj) {

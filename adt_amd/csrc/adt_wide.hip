@@ -141,11 +141,13 @@ static WAttnArgs make_wattn_args_bwd(const float* Qm, int ldqm, const float* Qc,
 // the same shapes, arguments and LDS footprint)
 template <int MET>
 static int stosa_attn(bool bwd, const WAttnArgs& a, void* stream) {
-  const char* nm = MET == WM_KL ? "klattn" : "wattn";
+  const char* nm = wm_kl(MET) ? "klattn" : "wattn";
   if (a.hd != 16 && a.hd != 32 && a.hd != 64) return adt_set_error("%s: head_dim=%d unsupported (16/32/64)", nm, a.hd);
   if (a.L > 256) return adt_set_error("%s: L=%d > 256 unsupported", nm, a.L);
-  const void* fn = MET == WM_KL ? (bwd ? (const void*)k_klattn_bwd : (const void*)k_klattn_fwd) : (bwd ? (const void*)k_wattn_bwd : (const void*)k_wattn_fwd);
-  const char* what = MET == WM_KL ? (bwd ? "klattn_bwd" : "klattn_fwd") : (bwd ? "wattn_bwd" : "wattn_fwd");
+  const void* fn = MET == WM_KLP ? (bwd ? (const void*)k_klattn_bwd<true> : (const void*)k_klattn_fwd<true>)
+                   : MET == WM_KL ? (bwd ? (const void*)k_klattn_bwd<false> : (const void*)k_klattn_fwd<false>)
+                                  : (bwd ? (const void*)k_wattn_bwd : (const void*)k_wattn_fwd);
+  const char* what = wm_kl(MET) ? (bwd ? "klattn_bwd" : "klattn_fwd") : (bwd ? "wattn_bwd" : "wattn_fwd");
   static AdtLdsOptIn optin[2];
   return adt_launch_lds1(fn, dim3(a.B * a.H), dim3(256), wattn_lds_bytes(a.L, a.hd, bwd), a, (hipStream_t)stream, what, optin[bwd], ADT_LDS_MAX);
 }
@@ -169,7 +171,8 @@ static int wattn_mfma_launch(bool bwd, const WAttnArgs& a, hipStream_t s) {
   return adt_launch_lds1(fn, dim3(a.B * a.H), dim3(WM_NW * 64), smem, a, s, bwd ? "wattn_mfma_bwd" : "wattn_mfma_fwd", optin[bwd], ADT_LDS_MAX);
 }
 
-// MET = WM_W: the Wasserstein score; WM_KL: the KL-divergence score on the same kernels, shapes and LDS.
+// MET = WM_W: the Wasserstein score; WM_KL: the KL-divergence score on the same kernels, shapes and LDS; WM_KLP: the KL score on padded
+// heads (the adt_klattn_*_scaled_* entry points: hd_live live lanes, the pad lanes gated by selects).
 // Returns 1 when the shape is not covered (the caller uses the vector-ALU entry point).
 template <int MET>
 static int wattn_mfma_dispatch(int prec, bool bwd, const WAttnArgs& a, hipStream_t s) {
@@ -617,7 +620,7 @@ int adt_kldist_bpr(const float* Sm, const float* Sc, int lds, const float* Em, c
                   void* stream) {
   if (d % 64) return adt_set_error("kldist_bpr: d=%d must be a multiple of 64", d);
   WBprArgs a{Sm, Sc, lds, Em, Ec, pos, neg, T, d, pvn_weight, inv_count, dSm, dSc, ldds, dEm, dEc, loss3};
-  hipLaunchKernelGGL(k_kldist_bpr, dim3(adt_grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_kldist_bpr<false>, dim3(adt_grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, a);
   return adt_check_launch("kldist_bpr");
 }
 
@@ -625,7 +628,7 @@ int adt_kldist_full(const float* Sm, const float* Sc, int lds, const float* Em, 
                    void* stream) {
   if (B <= 0 || V <= 0) return 0;
   WFullArgs a{Sm, Sc, lds, Em, Ec, B, V, d, dist, ldo};
-  hipLaunchKernelGGL(k_kldist_full, dim3(adt_grid_for((size_t)B * V, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_kldist_full<false>, dim3(adt_grid_for((size_t)B * V, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
   return adt_check_launch("kldist_full");
 }
 
@@ -873,6 +876,76 @@ int adt_act_lanes_bwd(const float* dY, int lddy, const float* X, int ldx, int T,
   a.drop = adt_make_drop(p, seed, site); a.row_offset = row_offset; a.act = act;
   hipLaunchKernelGGL(k_act_lanes<true>, dim3(adt_grid_for((size_t)T * (dp / 4), 1024, 4096)), dim3(256), 0, (hipStream_t)stream, a);
   return adt_check_launch("act_lanes_bwd");
+}
+
+// ---- STOSA-ADT under KL at padded widths -----------------------------------------------------------------------
+// The KL attention with the score scale given and lanes [0, hd_live) of a head live: the same launchers as adt_klattn_* / adt_klattn_mfma_*.
+// A pad lane holds cov = 0: the kernels leave it out of 1 / ck, of both log-determinants and of the subtracted head size, and write +0.0
+// to it in all six gradients, by selects on the lane index.
+int adt_klattn_scaled_fwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                          const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float scale,
+                          int hd_live, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc,
+                          float* LSE, void* stream) {
+  if (wattn_scaled_check("klattn_scaled_fwd", scale, hd_live, hd)) return -1;
+  WAttnArgs a = make_wattn_args(Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, B, H, L, hd, p, seed, site, b_offset, Om, ldom, Oc, ldoc, LSE);
+  a.xscale = scale; a.hd_live = hd_live;
+  return stosa_attn<WM_KLP>(false, a, stream);
+}
+
+int adt_klattn_scaled_bwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                          const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc,
+                          int ldoc, const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd,
+                          float scale, int hd_live, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc,
+                          float* dKm, float* dKc, float* dVm, float* dVc, int ldd, void* stream) {
+  if (wattn_scaled_check("klattn_scaled_bwd", scale, hd_live, hd)) return -1;
+  WAttnArgs a = make_wattn_args_bwd(Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, Om, ldom, Oc, ldoc, LSE, dOm, lddom, dOc, lddoc,
+                                    B, H, L, hd, p, seed, site, b_offset, dQm, dQc, dKm, dKc, dVm, dVc, ldd);
+  a.xscale = scale; a.hd_live = hd_live;
+  return stosa_attn<WM_KLP>(true, a, stream);
+}
+
+int adt_klattn_mfma_scaled_fwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                               const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float scale,
+                               int hd_live, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc,
+                               float* LSE, void* stream) {
+  if (wattn_scaled_check("klattn_mfma_scaled_fwd", scale, hd_live, hd)) return -1;
+  WAttnArgs a = make_wattn_args(Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, B, H, L, hd, p, seed, site, b_offset, Om, ldom, Oc, ldoc, LSE);
+  a.xscale = scale; a.hd_live = hd_live;
+  return wattn_mfma_dispatch<WM_KLP>(prec, false, a, (hipStream_t)stream);
+}
+
+int adt_klattn_mfma_scaled_bwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+                               const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc,
+                               int ldoc, const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd,
+                               float scale, int hd_live, float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc,
+                               float* dKm, float* dKc, float* dVm, float* dVc, int ldd, void* stream) {
+  if (wattn_scaled_check("klattn_mfma_scaled_bwd", scale, hd_live, hd)) return -1;
+  WAttnArgs a = make_wattn_args_bwd(Qm, ldqm, Qc, ldqc, Km, ldkm, Kc, ldkc, Vm, ldvm, Vc, ldvc, key_ids, Om, ldom, Oc, ldoc, LSE, dOm, lddom, dOc, lddoc,
+                                    B, H, L, hd, p, seed, site, b_offset, dQm, dQc, dKm, dKc, dVm, dVc, ldd);
+  a.xscale = scale; a.hd_live = hd_live;
+  return wattn_mfma_dispatch<WM_KLP>(prec, true, a, (hipStream_t)stream);
+}
+
+// adt_kldist_bpr / adt_kldist_full on padded rows and tables (d_pad = H * hd_pad columns each): the pad lanes stay out of every sum and
+// log, the divergences subtract the true d = H * hd, dSm / dSc get +0.0 on them and the tables' pad lanes receive no atomic.
+int adt_kldist_bpr_lanes(const float* Sm, const float* Sc, int lds, const float* Em, const float* Ec, const int32_t* pos, const int32_t* neg, int T,
+                         int H, int hd, int hd_pad, float pvn_weight, const float* inv_count, float* dSm, float* dSc, int ldds, float* dEm, float* dEc,
+                         float* loss3, void* stream) {
+  WBprArgs a{Sm, Sc, lds, Em, Ec, pos, neg, T, H * hd_pad, pvn_weight, inv_count, dSm, dSc, ldds, dEm, dEc, loss3};
+  if (make_lanes(a.ln, H, hd, hd_pad, "kldist_bpr_lanes")) return -1;
+  if (lds < a.d || ldds < a.d) return adt_set_error("kldist_bpr_lanes: lds=%d and ldds=%d must be >= d_pad=%d", lds, ldds, a.d);
+  hipLaunchKernelGGL(k_kldist_bpr<true>, dim3(adt_grid_for(T, 4, 2048)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("kldist_bpr_lanes");
+}
+
+int adt_kldist_full_lanes(const float* Sm, const float* Sc, int lds, const float* Em, const float* Ec, int B, int V, int H, int hd, int hd_pad,
+                          float* dist, int ldo, void* stream) {
+  WFullArgs a{Sm, Sc, lds, Em, Ec, B, V, H * hd_pad, dist, ldo};
+  if (make_lanes(a.ln, H, hd, hd_pad, "kldist_full_lanes")) return -1;
+  if (lds < a.d || ldo < V) return adt_set_error("kldist_full_lanes: lds=%d must be >= d_pad=%d and ldo=%d >= V=%d", lds, a.d, ldo, V);
+  if (B <= 0 || V <= 0) return 0;
+  hipLaunchKernelGGL(k_kldist_full<true>, dim3(adt_grid_for((size_t)B * V, 16, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  return adt_check_launch("kldist_full_lanes");
 }
 
 }  // extern "C"

@@ -115,7 +115,13 @@ class DistRankMixin:
             raise _lib.AdtError("kl_row_image is the item image of distance_metric='kl'; a %r model ranks on item_image()"
                                 % (getattr(self, "distance_metric", "wasserstein"),))
         Em, Ec, _ = self._dist_tables()
-        return ops.klrow_pack(Em, Ec, True)
+        return self._klrow_pack(Em, Ec, True)
+
+    def _klrow_pack(self, M, C, items):
+        """ops.klrow_pack, lane-aware for a model at a padded width as _wdist_pack: a pad lane holds ELU(0) + 1 = 1
+        on the item side and a covariance 0 on the user side, and neither may reach an image or an offset."""
+        lanes = getattr(self, "lanes", None)
+        return ops.klrow_pack(M, C, items) if lanes is None else ops.klrow_pack_lanes(M, C, items, lanes)
 
     @torch.no_grad()
     def _rank_states(self, sm, sc, targets, seen, topk, image, first_id, rowwise=False):
@@ -124,7 +130,7 @@ class DistRankMixin:
             image = self.kl_row_image() if kl else self.item_image()
         W, bias = image
         n_items = self._dist_tables()[2]
-        A, na = ops.klrow_pack(sm, sc, False) if kl else self._wdist_pack(sm, sc, False, 1.0)
+        A, na = self._klrow_pack(sm, sc, False) if kl else self._wdist_pack(sm, sc, False, 1.0)
         B = A.shape[0]
         indptr, indices = _seen(seen, B, A.device)
         rank, n_elig, top_idx, top_val = ops.full_rank(A, A.stride(0), W, n_items, _targets(targets, B, A.device), bias, indptr, indices, topk,

@@ -807,6 +807,69 @@ def wdist_pack_lanes(M, C, elu, nrm_scale, lanes):
     return img, nrm
 
 
+# ---- the same under distance_metric='kl' (DESIGN.md section 27): a pad lane holds cov = 0, which 1 / ck and log c do not take ----------
+def klattn_scaled_fwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, scale, hd_live, p=0.0, seed=None, site=0, b_offset=0, prec=None):
+    """klattn_fwd on heads padded from hd_live to Qm.shape[1] / H lanes (mean 0, covariance 0 on the pad lanes), with the score scale given
+    (1 / sqrt(true head size)); the matrix-core or the vector-ALU kernels by klattn_fwd's rule."""
+    return _stosa_attn_fwd("klattn_mfma_scaled_fwd", "klattn_scaled_fwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, site, b_offset, prec,
+                           _scaled(scale, hd_live))
+
+
+def klattn_scaled_bwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, scale, hd_live, p=0.0, seed=None, site=0, b_offset=0, out=None,
+                      prec=None):
+    """klattn_bwd for klattn_scaled_fwd (the same scale, hd_live and prec): the pad lanes of all six gradients are +0.0."""
+    return _stosa_attn_bwd("klattn_mfma_scaled_bwd", "klattn_scaled_bwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site,
+                           b_offset, out, prec, _scaled(scale, hd_live))
+
+
+def klattn_long_scaled_fwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, scale, hd_live, p=0.0, seed=None, site=0, b_offset=0, prec=None):
+    """klattn_long_fwd (1 <= L <= 1024, streamed) with the score scale given and hd_live live lanes per head."""
+    return _stosa_long_fwd("klattn_long_scaled_fwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, site, b_offset, prec, _scaled(scale, hd_live))
+
+
+def klattn_long_scaled_bwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, scale, hd_live, p=0.0, seed=None, site=0, b_offset=0,
+                           out=None, prec=None):
+    return _stosa_long_bwd("klattn_long_scaled_bwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site, b_offset, out, prec,
+                           _scaled(scale, hd_live))
+
+
+def kldist_bpr_lanes(Sm, Sc, Em, Ec, pos, neg, pvn_weight, inv_count, dEm, dEc, loss3, lanes):
+    """kldist_bpr on padded rows and tables: the pad lanes stay out of every sum and log, the divergences subtract the true d, dSm / dSc
+    get +0.0 there."""
+    H, hd, hd_pad = lanes
+    T, dp = Sm.shape
+    assert dp == H * hd_pad and Em.shape[1] == dp and Ec.shape[1] == dp, (Sm.shape, Em.shape, lanes)
+    dSm = torch.empty(T, dp, device=Sm.device, dtype=torch.float32)
+    dSc = torch.empty_like(dSm)
+    _lib.check(_lib.load().adt_kldist_bpr_lanes(_p(_f32(Sm)), _p(_f32(Sc)), _ld(Sm), _p(Em), _p(Ec), _p(_i32(pos)), _p(_i32(neg)), T, H, hd, hd_pad,
+                                                float(pvn_weight), _p(inv_count), _p(dSm), _p(dSc), dp, _p(dEm), _p(dEc), _p(loss3), _stream()),
+               "kldist_bpr_lanes")
+    return dSm, dSc
+
+
+def kldist_full_lanes(Sm, Sc, Em, Ec, V, lanes):
+    """kldist_full on padded rows and tables (the B rows are the eval batch): the score over the live lanes, with the true d."""
+    H, hd, hd_pad = lanes
+    B, dp = Sm.shape
+    assert dp == H * hd_pad and Em.shape[1] == dp and Ec.shape[1] == dp, (Sm.shape, Em.shape, lanes)
+    dist = torch.empty(B, V, device=Sm.device, dtype=torch.float32)
+    _lib.check(_lib.load().adt_kldist_full_lanes(_p(_f32(Sm)), _p(_f32(Sc)), _ld(Sm), _p(Em), _p(Ec), B, V, H, hd, hd_pad, _p(dist), V, _stream()),
+               "kldist_full_lanes")
+    return dist
+
+
+def klrow_pack_lanes(M, C, items, lanes):
+    """klrow_pack on padded rows: img (rows, 2 d_pad) with +0.0 on the pad lanes of both halves, off over the live lanes with the true d."""
+    H, hd, hd_pad = lanes
+    assert M.dim() == 2 and M.shape == C.shape and M.stride(0) == C.stride(0) and M.shape[1] == H * hd_pad, (M.shape, C.shape, lanes)
+    rows, dp = M.shape
+    img = torch.empty(rows, 2 * dp, device=M.device, dtype=torch.float32)
+    off = torch.empty(rows, device=M.device, dtype=torch.float32)
+    _lib.check(_lib.load().adt_klrow_pack_lanes(_p(_f32(M)), _p(_f32(C)), M.stride(0), rows, H, hd, hd_pad, int(bool(items)), _p(img), 2 * dp, _p(off),
+                                                _stream()), "klrow_pack_lanes")
+    return img, off
+
+
 # ---- full-catalogue ranking (include/adt_hip.h: adt_full_rank; adt_amd/csrc/adt_fullrank.cuh) ---------------------------------------------
 def seen_csr_host(seen, rows):
     """The seen items of `rows` users as int32 CSR (indptr (rows + 1,), indices) numpy arrays.  `seen`: a scipy sparse matrix (its stored

@@ -8,7 +8,7 @@ reads them directly, stosa/trainer.py:361-364,466-467).  All arithmetic runs in 
 (adt_gemm.cuh), the Wasserstein attention and the BPR / full-sort distance kernels (adt_stosa.cuh, exact fp32 wave-level
 reductions), LayerNorm / dropout / ELU row kernels.  maxlen up to 1024: past ops.wattn_max_len(head size) rows (256; 141 at head size 64)
 the attention runs on the streamed matrix-core kernels of adt_wattn_long.cuh.
-Under the Wasserstein distance any (hidden_units, num_heads) that wide.padded_layout accepts with heads of up to 64 lanes runs too (50 / 1,
+Under the Wasserstein distance -- and, with allow_kl_lanes=True, under 'kl'  -- any (hidden_units, num_heads) that wide.padded_layout accepts with heads of up to 64 lanes runs too (50 / 1,
 100 / 2, 48 / 4, 150 / 3): activations and parameters are padded to d_pad columns, the registered parameters keep the reference's shapes
 (DESIGN.md section 26).
 """
@@ -120,7 +120,8 @@ def padded_tables(item_size, maxlen, d, H, nl, num_users, dec_layernorm=True):
 
 
 class DisenDistSAModel(DistRankMixin, FlatModule):
-    def __init__(self, args, block=0, dec_layernorm=True):
+    def __init__(self, args, block=0, dec_layernorm=True, allow_kl_lanes=False):
+        """allow_kl_lanes: take distance_metric='kl' at a padded width; without it that pair raises, as it always has."""
         super().__init__()
         self.args = args
         self.item_size, self.maxlen, self.hidden_units = args.item_size, args.maxlen, args.hidden_units
@@ -150,10 +151,11 @@ class DisenDistSAModel(DistRankMixin, FlatModule):
         if self.distance_metric not in ("wasserstein", "kl"):
             raise _lib.AdtError("DisenDistSAModel (adt_amd): distance_metric must be 'wasserstein' or 'kl', got %r" % (self.distance_metric,))
         kl = self.distance_metric == "kl"
-        if kl and self.lanes is not None:
-            raise _lib.AdtError("DisenDistSAModel (adt_amd): distance_metric='kl' is not built for padded widths (d=%d H=%d runs as d_pad=%d): "
-                                "its kernels form 1 / cov and log-determinants, where a zero pad lane is not neutral; use 'wasserstein' or a "
-                                "hidden_units that is a multiple of 64 with head size 16/32/64" % (d, H, self.dp))
+        if kl and self.lanes is not None and not allow_kl_lanes:
+            raise _lib.AdtError("DisenDistSAModel (adt_amd): distance_metric='kl' at a padded width (d=%d H=%d runs as d_pad=%d) is opt-in: "
+                                "its kernels form 1 / cov and log-determinants, which the lane-aware KL kernels keep off the zero pad lanes; "
+                                "pass allow_kl_lanes=True to DisenDistSAModel (stosa/main.py does), or use 'wasserstein' or a hidden_units that "
+                                "is a multiple of 64 with head size 16/32/64" % (d, H, self.dp))
         # attention, BPR loss and full-sort score of the chosen metric (stosa/modules.py:244-248, trainer.py:372-379, :597-600)
         self._attn_fwd, self._attn_bwd = (ops.klattn_fwd, ops.klattn_bwd) if kl else (ops.wattn_fwd, ops.wattn_bwd)
         # past the length the whole-(b, h) kernels hold in LDS (256; 141 at head size 64): the streamed kernels, up to 1024 (adt_wattn_long.cuh)
@@ -169,12 +171,16 @@ class DisenDistSAModel(DistRankMixin, FlatModule):
             ref_table = self.table
         else:
             ln, scaled = self.lanes, (1.0 / math.sqrt(self.hd), self.hd)       # the score scale of the TRUE head size, for both directions
-            fwd, bwd = (ops.wattn_long_scaled_fwd, ops.wattn_long_scaled_bwd) if self._long_attn else (ops.wattn_scaled_fwd, ops.wattn_scaled_bwd)
+            if kl:
+                fwd, bwd = (ops.klattn_long_scaled_fwd, ops.klattn_long_scaled_bwd) if self._long_attn else (ops.klattn_scaled_fwd, ops.klattn_scaled_bwd)
+            else:
+                fwd, bwd = (ops.wattn_long_scaled_fwd, ops.wattn_long_scaled_bwd) if self._long_attn else (ops.wattn_scaled_fwd, ops.wattn_scaled_bwd)
             self._attn_fwd = lambda Qm, Qc, Km, Kc, Vm, Vc, kid, B, H, L, *a, **k: fwd(Qm, Qc, Km, Kc, Vm, Vc, kid, B, H, L, *scaled, *a, **k)
             self._attn_bwd = lambda Qm, Qc, Km, Kc, Vm, Vc, kid, Om, Oc, LSE, dOm, dOc, B, H, L, *a, **k: \
                 bwd(Qm, Qc, Km, Kc, Vm, Vc, kid, Om, Oc, LSE, dOm, dOc, B, H, L, *scaled, *a, **k)
-            self._dist_bpr = lambda *a: ops.wdist_bpr_lanes(*a, ln)
-            self._dist_full = lambda *a: ops.wdist_full_lanes(*a, ln)
+            dist_bpr, dist_full = (ops.kldist_bpr_lanes, ops.kldist_full_lanes) if kl else (ops.wdist_bpr_lanes, ops.wdist_full_lanes)
+            self._dist_bpr = lambda *a: dist_bpr(*a, ln)
+            self._dist_full = lambda *a: dist_full(*a, ln)
             ref_table, table, prefix, n_trained = padded_tables(args.item_size, args.maxlen, d, H, args.num_layers, args.num_users, dec_layernorm)
             self._build_flat(table, getattr(args, "device", "cuda:0"), REF_ORDER, ref_table=ref_table, width=(d, H), prefix=prefix)
         self.n_trained_floats = self._views[table[n_trained][0]][0]     # optimizer prefix (flat floats)

@@ -813,6 +813,49 @@ int adt_act_lanes_bwd(const float* dY, int lddy, const float* X, int ldx, int T,
                       const uint32_t* seed, uint32_t site, uint32_t row_offset, int act, float* dX, int lddx, int accumulate,
                       void* stream);
 
+/* ---- STOSA-ADT under the KL divergence at padded widths ----
+ * The KL attention on heads padded from hd_live to hd lanes: arguments, mask rule, dropout indices and results of adt_klattn_fwd / _bwd,
+ * adt_klattn_mfma_fwd / _bwd (1 = shape not covered) and adt_klattn_long_fwd / _bwd, with the score scale given -- 1 / sqrt(true head
+ * size), the same value for the forward and the backward -- and 1 <= hd_live <= hd.  Lanes [hd_live, hd) of every head must hold mean 0
+ * and covariance 0; they are left out of 1 / ck, of both log-determinants and of the subtracted head size (hd_live), and every one of
+ * the six gradients gets +0.0 there.  The kernels select on the lane index and never multiply by zero (0 * inf = NaN).  With
+ * scale = 1 / sqrt(hd) at hd 16 or 64 and hd_live = hd the results are bit-equal to the plain entry points'. */
+int adt_klattn_scaled_fwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float scale, int hd_live,
+    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE, void* stream);
+int adt_klattn_scaled_bwd(const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc, int ldoc,
+    const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd, float scale, int hd_live,
+    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc, float* dKm, float* dKc, float* dVm,
+    float* dVc, int ldd, void* stream);
+int adt_klattn_mfma_scaled_fwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float scale, int hd_live,
+    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE, void* stream);
+int adt_klattn_mfma_scaled_bwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc, int ldoc,
+    const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd, float scale, int hd_live,
+    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc, float* dKm, float* dKc, float* dVm,
+    float* dVc, int ldd, void* stream);
+int adt_klattn_long_scaled_fwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float scale, int hd_live,
+    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE, void* stream);
+int adt_klattn_long_scaled_bwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc, int ldoc,
+    const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd, float scale, int hd_live,
+    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc, float* dKm, float* dKc, float* dVm,
+    float* dVc, int ldd, void* stream);
+/* adt_kldist_bpr / adt_kldist_full / adt_klrow_pack on padded rows and tables of d_pad = H * hd_pad columns (head h at columns
+ * [h * hd_pad, h * hd_pad + hd)): a pad lane holds a sequence covariance 0 and an item covariance ELU(0) + 1 = 1, so the pad lanes are
+ * left out of every sum and log and the divergences subtract the true d = H * hd; dSm / dSc get +0.0 on them, the tables' pad lanes
+ * receive no atomic, and both halves of the row-wise images are +0.0 there. */
+int adt_kldist_bpr_lanes(const float* Sm, const float* Sc, int lds, const float* Em, const float* Ec, const int32_t* pos,
+                         const int32_t* neg, int T, int H, int hd, int hd_pad, float pvn_weight, const float* inv_count, float* dSm,
+                         float* dSc, int ldds, float* dEm, float* dEc, float* loss3, void* stream);
+int adt_kldist_full_lanes(const float* Sm, const float* Sc, int lds, const float* Em, const float* Ec, int B, int V, int H, int hd,
+                          int hd_pad, float* dist, int ldo, void* stream);
+int adt_klrow_pack_lanes(const float* M, const float* C, int ld, int rows, int H, int hd, int hd_pad, int items, float* img, int ldi,
+                         float* off, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

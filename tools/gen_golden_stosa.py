@@ -215,6 +215,18 @@ def main_odd():
               lam1=[0.3], lam2=[0.2], **kw)
 
 
+def main_kl_odd():
+    """stosa_kl_w50_h1 / w100_h2 / w48_h4.npz: main_odd()'s configurations, batch sizes, seeds and lambdas under distance_metric='kl'
+    (DESIGN.md section 27), compacted the same way."""
+    kw = dict(compact=True, thresh=2048, nsample=STOSA_ODD_COMPACT, metric="kl")
+    gen_stosa("w50_h1", dict(item_size=42, maxlen=12, hidden_units=50, num_heads=1, num_layers=1, num_users=4, pvn_weight=0.005), B=4, seed=41,
+              lam1=[0.3], lam2=[0.2], **kw)
+    gen_stosa("w100_h2", dict(item_size=33, maxlen=20, hidden_units=100, num_heads=2, num_layers=2, num_users=3, pvn_weight=0.1), B=3, seed=42,
+              lam1=[0.25, 0.1], lam2=[0.15, 0.05], **kw)
+    gen_stosa("w48_h4", dict(item_size=28, maxlen=9, hidden_units=48, num_heads=4, num_layers=1, num_users=2, pvn_weight=0.05), B=3, seed=43,
+              lam1=[0.1], lam2=[0.05], **kw)
+
+
 def main_kl_rowwise():
     """stosa_kl_rowwise.npz: the model, seed and input_ids of stosa_kl_small.npz; rowwise_dist[b][v] = the reference's kl_distance
     (stosa/modules.py:45-50) of user b's last-position (mean, cov) from item v's (mean, ELU(cov) + 1), every row of the item tables --
@@ -240,9 +252,11 @@ if __name__ == "__main__":
     import argparse
     sys.path.insert(0, REPO)
     ap = argparse.ArgumentParser()
-    ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl", "kl_rowwise", "long", "stosa_odd"])
+    ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl", "kl_rowwise", "long", "stosa_odd", "stosa_kl_odd"])
     metric = ap.parse_args().metric
     if metric == "stosa_odd":
         main_odd()
+    elif metric == "stosa_kl_odd":
+        main_kl_odd()
     else:
         main_kl_rowwise() if metric == "kl_rowwise" else (main_long() if metric == "long" else main(metric))
