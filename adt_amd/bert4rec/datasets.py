@@ -60,6 +60,42 @@ class PopularSampler:
         return self._cache[key]
 
 
+def device_candidate_tables(train, val, test, itemnum, users, sample_size):
+    """What DeviceBertData.add_eval(candidates="device") uploads for `users`, prepared on the host (no GPU): PopularSampler's table and
+    seen sets in the form adt_evalcand_draw reads.  Returns (cum, total, seen_off, seen_items): cum (itemnum + 2,) int64, the exact prefix
+    sums of the item counts over train + val + test indexed by item id, cum[0] = 0 and cum[i + 1] - cum[i] = count of id i, so that ids
+    1..itemnum are drawable and id 0, [MASK] = itemnum + 1 and the vocabulary tail never are; total = cum[-1]; the sorted, de-duplicated
+    train | val | test items of every user as CSR (int64 offsets, int32 ids).  Refused with an AdtError: a sample size outside
+    1..EVALCAND_MAX_S, counts that sum to 2^32 or more (the stream maps 32 hash bits onto [0, total)), and a user with fewer than
+    sample_size drawable unseen items (the reference's rejection loop would spin forever; the kernel would fill id 0)."""
+    from .. import ops
+    from .._lib import AdtError
+    S = int(sample_size)
+    if not 1 <= S <= ops.EVALCAND_MAX_S:
+        raise AdtError("DeviceBertData: sample_size=%d outside 1..%d" % (S, ops.EVALCAND_MAX_S))
+    acts = [np.asarray(items, np.int64) for d in (train, val, test) for items in d.values() if len(items)]
+    acts = np.concatenate(acts) if acts else np.zeros(0, np.int64)
+    if acts.size and (acts.min() < 1 or acts.max() > itemnum):
+        raise AdtError("DeviceBertData: item ids must lie in [1, %d]" % itemnum)
+    count = np.bincount(acts, minlength=itemnum + 1)
+    cum = np.zeros(itemnum + 2, np.int64)
+    np.cumsum(count, out=cum[1:])
+    total = int(cum[-1])
+    if not 1 <= total < 2 ** 32:
+        raise AdtError("DeviceBertData: the item counts sum to %d, outside 1 .. 2^32 - 1" % total)
+    seen = [np.unique(np.asarray(list(train.get(u, [])) + list(val.get(u, [])) + list(test.get(u, [])), np.int64)) for u in users]
+    n_drawable = int((count > 0).sum())
+    for u, s in zip(users, seen):      # every seen id has a non-zero count: it is one of the counted actions
+        if n_drawable - len(s) < S:
+            raise AdtError("DeviceBertData: user %d has %d drawable items, sample_size is %d" % (u, n_drawable - len(s), S))
+    seen_off = np.zeros(len(seen) + 1, np.int64)
+    np.cumsum([len(s) for s in seen], out=seen_off[1:])
+    seen_items = np.zeros(max(int(seen_off[-1]), 1), np.int32)      # never empty: the kernel takes its address
+    if seen_off[-1]:
+        seen_items[:seen_off[-1]] = np.concatenate(seen)
+    return cum, total, seen_off, seen_items
+
+
 class BertTrainDataset:
     def __init__(self, user_train, usernum, itemnum, maxlen, mask_prob, seed, dupe_factor=10, prop_sliding_window=0.5):
         self.itemnum, self.maxlen, self.mask_prob = itemnum, maxlen, mask_prob
@@ -131,7 +167,9 @@ class DeviceBertData:
     and the table of the W sliding windows BertTrainDataset cuts (offset into the items, length).  Examples are numbered, not stored:
     with D = dupe_factor, example e < W * D is random copy e % D of window e // D and example W * D + u is the mask-last example of the
     u-th user, so len(self) == len(BertTrainDataset(...)).  The masks are a function of (seed, salt, example, position): one salt keeps
-    one mask per example for a whole run (the reference's dupe_factor copies), salt = epoch draws a fresh set every epoch."""
+    one mask per example for a whole run (the reference's dupe_factor copies), salt = epoch draws a fresh set every epoch.  Per evaluation
+    mode (add_eval) the user list and the (N, 1 + C) candidate table stay resident too: the host sampler's frozen candidates, or, with
+    candidates="device", a table that draw_eval fills on the GPU from the resident popularity table and seen rows."""
 
     def __init__(self, user_train, usernum, itemnum, maxlen, mask_prob, device, dupe_factor=10, prop_sliding_window=0.5):
         import torch
@@ -168,6 +206,7 @@ class DeviceBertData:
         self.win_len = torch.from_numpy(np.asarray(win_len, np.int32)).to(self.dev)
         self.order = None
         self._eval = {}
+        self._draw = {}       # mode -> the tables draw_eval reads (add_eval(candidates="device") only)
 
     def __len__(self):
         return self.W * self.dupe_factor + self.U
@@ -193,13 +232,46 @@ class DeviceBertData:
             self.thr_mask, seed, salt, (lo, hi), want_labels=False)
         return {"B": hi - lo, "B_global": B, "src": src, "dec": dec, "rows": rows_c, "labels": labels_c, "M": M, "inv_count": inv_count}
 
-    def add_eval(self, eval_ds):
-        """Keep a BertEvalDataset's user list and its (N, 1 + C) candidate matrix (the positive, then the sampler's negatives, which it
-        freezes per (user, mode)) resident, under eval_ds.mode."""
+    def add_eval(self, eval_ds, candidates="host"):
+        """Keep a BertEvalDataset's user list and its (N, 1 + C) candidate matrix resident, under eval_ds.mode.  candidates="host": the
+        positive, then the sampler's negatives, which it freezes per (user, mode).  candidates="device" (DESIGN.md section 28): the host
+        sampler is not called; the targets, the seen rows and the popularity table of device_candidate_tables stay resident beside a
+        candidate table that holds the targets only until draw_eval fills it."""
         import torch
-        users = np.array([self.user_index[u] for u in eval_ds.users], np.int32)
-        cand = np.array([eval_ds.sample_data(u)[1] for u in eval_ds.users], np.int32).reshape(len(users), -1)
-        self._eval[eval_ds.mode] = (torch.from_numpy(users).to(self.dev), torch.from_numpy(cand).to(self.dev))
+        from .._lib import AdtError
+        if candidates not in ("host", "device"):
+            raise AdtError("DeviceBertData.add_eval: candidates=%r (host or device)" % (candidates,))
+        mode = eval_ds.mode
+        users = torch.from_numpy(np.array([self.user_index[u] for u in eval_ds.users], np.int32)).to(self.dev)
+        self._draw.pop(mode, None)
+        if candidates == "host":
+            cand = np.array([eval_ds.sample_data(u)[1] for u in eval_ds.users], np.int32).reshape(len(eval_ds.users), -1)
+            self._eval[mode] = (users, torch.from_numpy(cand).to(self.dev))
+            return
+        sp = eval_ds.sampler
+        S = int(sp.sample_size)
+        cum, total, seen_off, seen_items = device_candidate_tables(sp.train, sp.val, sp.test, self.itemnum, eval_ds.users, S)
+        tgt = eval_ds.user_val if mode == "val" else eval_ds.user_test
+        targets = torch.from_numpy(np.array([tgt[u][0] for u in eval_ds.users], np.int32)).to(self.dev)
+        cand = torch.zeros(len(eval_ds.users), 1 + S, device=self.dev, dtype=torch.int32)
+        cand[:, 0] = targets
+        self._eval[mode] = (users, cand)
+        self._draw[mode] = {"cum": torch.from_numpy(cum).to(self.dev), "total": total, "seen_off": torch.from_numpy(seen_off).to(self.dev),
+                            "seen_items": torch.from_numpy(seen_items).to(self.dev), "targets": targets, "S": S, "drawn": False}
+
+    def draw_eval(self, mode, seed, salt=0):
+        """Fill the mode's resident (N, 1 + S) candidate table with adt_evalcand_draw: column 0 the target, then the first S distinct
+        unseen values of the popularity stream of (seed, salt, row) -- PopularSampler's distribution over a hash stream of its own, not
+        numpy's.  Returns the table."""
+        from .. import ops
+        from .._lib import AdtError
+        if mode not in self._draw:
+            raise AdtError("DeviceBertData.draw_eval: mode %r was not added with add_eval(candidates=\"device\")" % (mode,))
+        t, cand = self._draw[mode], self._eval[mode][1]
+        if cand.shape[0]:
+            ops.evalcand_draw(t["cum"], t["total"], t["seen_off"], t["seen_items"], t["targets"], t["S"], seed, salt, out=cand)
+        t["drawn"] = True
+        return cand
 
     def eval_len(self, mode):
         return self._eval[mode][0].numel()
@@ -208,7 +280,10 @@ class DeviceBertData:
         """(seq (B, L), candidates (B, 1 + C)), both device int32, of users start .. start + B - 1 of the mode's list: what
         BertEvalDataset.batches yields, for FusedBertTrainer.evaluate."""
         from .. import ops
+        from .._lib import AdtError
         users, cand = self._eval[mode]
+        if mode in self._draw and not self._draw[mode]["drawn"]:
+            raise AdtError("DeviceBertData.eval_batch: mode %r has no candidates yet (draw_eval first)" % (mode,))
         assert 0 <= start and start + B <= users.numel(), (mode, start, B, users.numel())
         return ops.bertbatch_eval(self.seq_off, self.seq_items, users[start:start + B], self.maxlen, self.itemnum), cand[start:start + B]
 

@@ -65,9 +65,18 @@ def parse_args(argv=None):
                         "no (rows, items) logit matrix in memory, instead of the dense head; the probabilities enter the gradient products rounded "
                         "to bf16, so such a run is not the unfused run's trajectory.  Widths 128 / 256 use the fused head already; under "
                         "--precision f32 the flag has no effect")
+    p.add_argument("--device_scores", action="store_true",
+                   help="count the evaluation ranks on the GPU (adt_cand_rank_hist) and read one histogram per evaluation instead of the ranks of "
+                        "every batch; the same candidates and the same ranks, with or without --device_batches")
+    p.add_argument("--device_negatives", action="store_true",
+                   help="with --device_batches: draw the evaluation candidates on the GPU (adt_evalcand_draw), once per run, instead of with the "
+                        "host sampler.  Same distribution as the numpy sampler's candidates, but a hash stream of its own: different "
+                        "candidates and therefore different metrics")
     args = p.parse_args(argv)
     if args.remask_every_epoch and not args.device_batches:
         p.error("--remask_every_epoch needs --device_batches")
+    if args.device_negatives and not args.device_batches:
+        p.error("--device_negatives needs --device_batches")
     return args
 
 
@@ -122,7 +131,10 @@ def main(argv=None):
     sampler = D.PopularSampler(user_train, user_valid, user_test, usernum, itemnum, args.eval_negative_sample_size)
     val_ds = D.BertEvalDataset(user_train, user_valid, user_test, usernum, itemnum, args.maxlen, sampler, "val", args.eval_set_size)
     test_ds = D.BertEvalDataset(user_train, user_valid, user_test, usernum, itemnum, args.maxlen, sampler, "test", args.eval_set_size)
-    if args.device_batches:
+    if args.device_negatives:       # the host sampler is never called; one draw for the whole run, seeds 23 / 24 keep the two sets apart
+        train_ds.add_eval(val_ds, candidates="device"), train_ds.add_eval(test_ds, candidates="device")
+        train_ds.draw_eval("val", 23), train_ds.draw_eval("test", 24)
+    elif args.device_batches:
         train_ds.add_eval(val_ds), train_ds.add_eval(test_ds)
     torch.manual_seed(23)
     model = BertModel(usernum, itemnum, args)
@@ -155,8 +167,8 @@ def main(argv=None):
         torch.cuda.synchronize()
         T += time.time() - t0
         if (epoch + 1) % args.eval_interval == 0 or epoch + 1 == args.num_epochs:
-            t_test, auc_test = trainer.evaluate(eval_batches(test_ds))
-            t_valid, auc_valid = trainer.evaluate(eval_batches(val_ds))
+            t_test, auc_test = trainer.evaluate(eval_batches(test_ds), device_scores=args.device_scores)
+            t_valid, auc_valid = trainer.evaluate(eval_batches(val_ds), device_scores=args.device_scores)
             for k in (5, 10) if rank == 0 else ():
                 print("epoch: %d, time: %f, valid (NDCG@%d: %.4f, HR@%d: %.4f, AUC: %s), test (NDCG@%d: %.4f, HR@%d: %.4f, AUC: %s)"
                       % (epoch + 1, T, k, t_valid[0][k], k, t_valid[1][k], auc_valid, k, t_test[0][k], k, t_test[1][k], auc_test))

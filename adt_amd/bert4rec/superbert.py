@@ -108,13 +108,11 @@ class SuperBertModel(BertModel):
             outs.append(x)
         return outs
 
-    @torch.no_grad()
-    def predict_rank_candidates(self, seqs, candidates, shared_list, stats=None):
-        """Ranks of the positive (column 0 of `candidates`) at the last position under EVERY block choice of `shared_list`: (P, B).
-        One pass: depth-0 layers shared between candidates, deeper layers once per distinct layer on the stacked inputs
+    def _candidate_head_rows(self, seqs, shared_list, stats=None):
+        """(h, B): the head's input to the item scores at the last position under EVERY block choice of `shared_list`, (P * B, d) stacked
+        group-major.  One pass: depth-0 layers shared between candidates, deeper layers once per distinct layer on the stacked inputs
         (supersearch.candidate_features)."""
         src = self.ids(seqs)
-        cand = self.ids(candidates)
         B, L = src.shape
         was = self.training
         self.eval()
@@ -125,17 +123,41 @@ class SuperBertModel(BertModel):
         def run_layer(depth, idx, x, n):
             ids = flat if n == 1 else flat.repeat(n)
             y, _ = self._enc_layer(tp, "encoder.encoder_layers.%d.%d" % (depth, idx), Act(x[0]), ids, B * n, enc_sites(depth))
+            # no backward follows: drop the layer's closures now, and with them its intermediate activations.  Left on the tape (which
+            # they reference back, so only the cycle collector frees them) they add up over the stacked layers of a pass: at the ml-1m
+            # template shape, about 1 GB per layer evaluation of 256 sequences
+            del tp.bw[:]
             return (y.t,)
         feats = candidate_features(run_layer, (x0.t,), shared_list, self.num_layers, stats=stats)
         P = len(shared_list)
         F = feats[0][0] if P == 1 else torch.cat([f[0] for f in feats], 0)
         rows = torch.arange(L - 1, P * B * L, L, device=self.dev, dtype=torch.int32)
         h = self._head(tp, Act(ops.gather_rows(F, rows)))
+        del tp.bw[:]
         self.train(was)
+        return h.t, B
+
+    @torch.no_grad()
+    def predict_rank_candidates(self, seqs, candidates, shared_list, stats=None):
+        """Ranks of the positive (column 0 of `candidates`) at the last position under EVERY block choice of `shared_list`: (P, B), in one
+        pass (_candidate_head_rows)."""
+        cand = self.ids(candidates)
+        h, B = self._candidate_head_rows(seqs, shared_list, stats)
+        P = len(shared_list)
         if P > 1:
             cand = cand.repeat(P, 1)
-        _, rank = ops.score_rank_bias(h.t, self.hidden_units, self.P("item_emb.word_emb.weight"), self.P("mask_bias"), cand, P * B, cand.shape[1], True)
+        _, rank = ops.score_rank_bias(h, self.hidden_units, self.P("item_emb.word_emb.weight"), self.P("mask_bias"), cand, P * B, cand.shape[1], True)
         return rank.view(P, B)
+
+    @torch.no_grad()
+    def rank_hist_candidates(self, seqs, candidates, shared_list, hist, stats=None):
+        """predict_rank_candidates with the scores counted on the device: the same pass, then adt_cand_rank_hist on the stacked rows with
+        rows_per_group = B, so the (B, C) candidates are read by every group and not repeated P times, and the ranks are counted into hist
+        (P, C) int64 (accumulated in place; returned) instead of being read back.  seqs / candidates: host arrays or device int32."""
+        cand = self.ids(candidates)
+        h, B = self._candidate_head_rows(seqs, shared_list, stats)
+        return ops.cand_rank_hist(h, h.stride(0), self.P("item_emb.word_emb.weight"), cand, len(shared_list) * B, rows_per_group=B, hist=hist,
+                                  bias=self.P("mask_bias"))
 
 
 class SuperBertTrainer(SupernetTrainer):
@@ -145,11 +167,19 @@ class SuperBertTrainer(SupernetTrainer):
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, clip=5.0, seed=2022):
         super().__init__(model, 1 + 2 * model.num_layers, lr, betas, eps, weight_decay, clip, seed)
+        self._norms = {}      # step_device: rows -> device normalisers
 
     def _stage(self, src, dec, labels):
         m = self.model
         st = m.stage(src, dec, labels)
         return st, loss_norms(m, st["B"] * m.maxlen)
+
+    def _device_norms(self, st):
+        """step_device (DeviceBertData.train_stage): one loss_norms per row count, kept, so a step uploads nothing -- as
+        FusedBertTrainer.step_device does.  The masked-row count stays on the device; the masked-row GEMMs are launched for B * L rows."""
+        if st["B"] not in self._norms:
+            self._norms[st["B"]] = loss_norms(self.model, st["B"] * self.model.maxlen)
+        return self._norms[st["B"]]
 
     def _ind_lambdas(self):
         nl = self.model.num_layers

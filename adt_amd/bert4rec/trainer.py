@@ -74,12 +74,15 @@ class FusedBertTrainer(TapeTrainer):
 
     # ------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def evaluate(self, batches, ks=(5, 10)):
+    def evaluate(self, batches, ks=(5, 10), device_scores=False):
         """BertTrainer.evaluate (trainer.py:49-86) over an iterable of (seq (B, L), candidates (B, C)) -- host arrays or device int32
         tensors (DeviceBertData.eval_batch), which are used where they are -- with the positive in column 0: rank = number of
-        candidates scored above it, HR@k, NDCG@k, and the AUC with the reference's candidates_size = 1 + C."""
+        candidates scored above it, HR@k, NDCG@k, and the AUC with the reference's candidates_size = 1 + C.  device_scores (DESIGN.md
+        section 28): the ranks are counted on the device and one histogram is read after the last batch (_evaluate_hist)."""
         self.model.eval()
         ks = tuple(ks)
+        if device_scores:
+            return self._evaluate_hist(batches, ks)
         # additive statistics [n, sum of AUC terms, per k: hits, sum 1/log2(rank+2)]: under data parallelism rank r scores batches
         # r, r+W, ... and the statistics are sum-reduced in float64, so every rank ends up with the metrics of the whole user set
         stats = np.zeros(2 + 2 * len(ks), np.float64)
@@ -101,3 +104,33 @@ class FusedBertTrainer(TapeTrainer):
         ndcg = {k: float(stats[3 + 2 * j] / n) for j, k in enumerate(ks)}
         hr = {k: float(stats[2 + 2 * j] / n) for j, k in enumerate(ks)}
         return (ndcg, hr), float(stats[1] / n)
+
+    def _evaluate_hist(self, batches, ks):
+        """evaluate() without a copy per batch: every batch is encoded as predict() encodes it (_full_rank_operands: the head rows of the
+        last position) and scored, ranked and counted by adt_cand_rank_hist into one (1, C) int64 histogram, which is read once and
+        turned into the metrics by metrics_from_hist with the same n_candidates = C (size = 1 + C).  Under data parallelism rank r
+        takes batches r, r + W, ... as evaluate() does and the histogram is sum-reduced: integers, so the result is exact."""
+        from ..sasrec.utils import metrics_from_hist
+        m = self.model
+        C, hist = None, None
+        for i, (seq, cand) in enumerate(batches):
+            c = (cand if isinstance(cand, torch.Tensor) else np.asarray(cand)).shape[1]
+            if C is None:       # every rank sees every batch's shape, so all of them reach the same decision
+                C, hist = c, torch.zeros(1, c, device=m.dev, dtype=torch.int64)
+            elif c != C:
+                raise AdtError("evaluate(device_scores=True): batch %d has %d candidates, the first batch has %d (one histogram per pass)" % (i, c, C))
+            if i % self.world != self.rank:
+                continue
+            cand = m.ids(cand)
+            F, E, _, bias = m._full_rank_operands(seq)
+            ops.cand_rank_hist(F, F.stride(0), E, cand, cand.shape[0], cand.shape[0], hist=hist, bias=bias)
+        if C is None:
+            raise AdtError("evaluate(device_scores=True): no batches")
+        if self.world > 1:
+            if torch.distributed.get_backend(self.pg) == "nccl":
+                torch.distributed.all_reduce(hist, group=self.pg)
+            else:
+                h = hist.cpu()
+                torch.distributed.all_reduce(h, group=self.pg)
+                hist = h
+        return metrics_from_hist(hist.cpu().numpy()[0], C, ks)

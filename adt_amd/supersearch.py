@@ -76,7 +76,7 @@ class SupernetTrainer:
     the flat ranges that received a gradient -- the tensors outside the candidate layers and the candidates that were mixed in -- are
     clipped (global norm), decayed and stepped, each with its own step count; the others keep their moments.  A subclass supplies
     `_stage(*batch)` -> (what its model's loss_forward_backward takes, norms), `_ranges()`, `_adam_range` (ops.adam_range or
-    ops.adamw_range) and `_loss_w()`."""
+    ops.adamw_range) and `_loss_w()`; one whose batches can be built on the device also `_device_norms(staged)` for step_device."""
 
     def __init__(self, model, n_slots, lr, betas, eps, weight_decay, clip, seed):
         self.model = model
@@ -103,10 +103,21 @@ class SupernetTrainer:
     def _ind_lambdas(self):
         return self.ind_weights
 
+    def _device_norms(self, staged):
+        from ._lib import AdtError
+        raise AdtError("%s.step_device: this supernet trainer stages host batches only (step)" % type(self).__name__)
+
     def step(self, *batch):
+        self._step(*self._stage(*batch))
+
+    def step_device(self, staged):
+        """step() for a batch that is on the device already, in the form the model's loss_forward_backward takes: nothing is staged, and
+        the subclass supplies the normalisers (`_device_norms(staged)`)."""
+        self._step(staged, self._device_norms(staged))
+
+    def _step(self, staged, norms):
         m = self.model
         m.train()
-        staged, norms = self._stage(*batch)
         m.advance_seed()
         self.loss_slots.zero_()
         m.flat_grad.zero_()
