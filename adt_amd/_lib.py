@@ -155,6 +155,13 @@ SIGNATURES = {
     "adt_klattn_long_scaled_fwd": (_I, [_I] + [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _I, _F, _P, _U, _U, _P, _I, _P, _I, _P, _P]),
     "adt_klattn_long_scaled_bwd": (_I, [_I] + [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _F,
                                     _P, _U, _U, _P, _P, _P, _P, _P, _P, _I, _P]),
+    # the distance attention at head size 128: the *_long_scaled_* signatures
+    "adt_wattn_hd128_fwd": (_I, [_I] + [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _I, _F, _P, _U, _U, _P, _I, _P, _I, _P, _P]),
+    "adt_wattn_hd128_bwd": (_I, [_I] + [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _F,
+                             _P, _U, _U, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "adt_klattn_hd128_fwd": (_I, [_I] + [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _I, _F, _P, _U, _U, _P, _I, _P, _I, _P, _P]),
+    "adt_klattn_hd128_bwd": (_I, [_I] + [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _F,
+                              _P, _U, _U, _P, _P, _P, _P, _P, _P, _I, _P]),
     "adt_kldist_bpr_lanes": (_I, [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _I, _P, _P, _P, _P]),
     "adt_kldist_full_lanes": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
     "adt_klrow_pack_lanes": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P]),

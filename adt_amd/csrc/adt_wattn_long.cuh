@@ -6,7 +6,8 @@
 // cross term of inner width 2 hd over [m | sqrt S] (KL: the X / Y images with their log-det biases), contexts P~ Vm and (P~ * P~) Vc,
 // dP~ = dOm Vm^T + 2 P~ (dOc Vc^T), the sqrt(clamp(cov, 1e-24)) chain, and the KL gradient split between pass A and pass B with the same
 // lane (same workgroup, same wave: tile = blockIdx.y * 4 + wave in both passes) adding in the same order.  A separate header and
-// translation unit: the kernels of the shorter lengths are not touched.
+// translation unit: the kernels of the shorter lengths are not touched.  adt_wattn_hd128.hip instantiates the same templates at head size 128 (one wave per
+// SIMD, the whole 512-entry register file).
 //
 // What streaming changes:
 //  * Online softmax.  The dropout keep scale multiplies the unnormalised probability BEFORE the square, so when the running maximum
@@ -38,6 +39,15 @@ struct WattnLongLds {
   static constexpr size_t fwd_bytes = (cat + 2 * t) * sizeof(float) + mask_bytes;
   static constexpr size_t bwd_bytes = (cat + 2 * t + 2 * nat + 2 * t + 2 * LPMAX) * sizeof(float) + mask_bytes;
 };
+
+// Wasserstein dQm / dKm of features f0 .. f0 + 3.  On a pad lane the operands are zero and 2 * 0 * dwsum - 2 * 0 is -0.0 whenever dwsum is
+// negative: head size 128 (adt_wattn_hd128.hip) selects +0.0 there by the lane index, as the covariance gradients always have.  Head sizes
+// 16 / 32 / 64 store the value as it is: their code objects (adt_wattn_long.hip) do not change.
+template <int HD>
+ADT_DEVICE_INLINE float4 wl_mean_grad4(const WAttnArgs& a, int f0, float4 v) {
+  if constexpr (HD > 64) return make_float4(wm_live(a, f0) ? v.x : 0.f, wm_live(a, f0 + 1) ? v.y : 0.f, wm_live(a, f0 + 2) ? v.z : 0.f, wm_live(a, f0 + 3) ? v.w : 0.f);
+  else return v;
+}
 
 template <int PREC, int HD, int MET, int CH>
 __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_fwd(WAttnArgs a) {
@@ -338,8 +348,8 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
         const f32x4& acc = accq[ft];
         if (k0 < HD) {
           const float4 q = *reinterpret_cast<const float4*>(a.Qm + qrow * a.ldqm + co + k0);
-          *reinterpret_cast<float4*>(a.dQm + qrow * a.ldd + co + k0) =
-              make_float4(2.0f * q.x * dwsum - 2.0f * acc[0], 2.0f * q.y * dwsum - 2.0f * acc[1], 2.0f * q.z * dwsum - 2.0f * acc[2], 2.0f * q.w * dwsum - 2.0f * acc[3]);
+          *reinterpret_cast<float4*>(a.dQm + qrow * a.ldd + co + k0) = wl_mean_grad4<HD>(a, k0,
+              make_float4(2.0f * q.x * dwsum - 2.0f * acc[0], 2.0f * q.y * dwsum - 2.0f * acc[1], 2.0f * q.z * dwsum - 2.0f * acc[2], 2.0f * q.w * dwsum - 2.0f * acc[3]));
         } else {
           const float4 qc = *reinterpret_cast<const float4*>(a.Qc + qrow * a.ldqc + co + k0 - HD);
           const float s0 = w_sqrt_cov(qc.x), s1 = w_sqrt_cov(qc.y), s2 = w_sqrt_cov(qc.z), s3 = w_sqrt_cov(qc.w);
@@ -482,8 +492,8 @@ __global__ __launch_bounds__(WM_NW * 64) void k_wattn_long_bwd(WAttnArgs a) {
         const f32x4& acc = acck[ft];
         if (k0 < HD) {
           const float4 k = *reinterpret_cast<const float4*>(a.Km + krow * a.ldkm + co + k0);
-          *reinterpret_cast<float4*>(a.dKm + krow * a.ldd + co + k0) =
-              make_float4(2.0f * k.x * dwsum - 2.0f * acc[0], 2.0f * k.y * dwsum - 2.0f * acc[1], 2.0f * k.z * dwsum - 2.0f * acc[2], 2.0f * k.w * dwsum - 2.0f * acc[3]);
+          *reinterpret_cast<float4*>(a.dKm + krow * a.ldd + co + k0) = wl_mean_grad4<HD>(a, k0,
+              make_float4(2.0f * k.x * dwsum - 2.0f * acc[0], 2.0f * k.y * dwsum - 2.0f * acc[1], 2.0f * k.z * dwsum - 2.0f * acc[2], 2.0f * k.w * dwsum - 2.0f * acc[3]));
         } else {
           const float4 kc = *reinterpret_cast<const float4*>(a.Kc + krow * a.ldkc + co + k0 - HD);
           const float s0 = w_sqrt_cov(kc.x), s1 = w_sqrt_cov(kc.y), s2 = w_sqrt_cov(kc.z), s3 = w_sqrt_cov(kc.w);

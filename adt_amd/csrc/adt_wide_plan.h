@@ -404,4 +404,35 @@ static inline AttnPlan adt_wattn_long_plan(int prec, int hd, int L, bool bwd) {
   return p;
 }
 
+// The same streamed family at head size 128 (adt_wattn_hd128.hip: entry points of their own, adt_wattn_long_plan keeps its refusals).
+// The chunk is the largest of 64 / 32 rows whose footprint leaves room for two workgroups on a CU (half the LDS), else the largest that
+// fits at all: 32 keys in the forward (71,328 B; 64 keys take 137,504 B and a CU to themselves), 32 rows in the backward (150,176 B, the
+// only chunk of whole tile pairs that fits).  Head size 256 is refused: its backward fits the LDS only at a 16-row chunk, which the
+// kernels' 32-row tile pairs do not allow, and its operand and accumulator fragments (2 x this head size's 256 registers in pass B)
+// exceed the 512 registers of a lane.
+constexpr int wattn_hd128_kc(bool bwd) {
+  for (int kc = 64; kc >= 32; kc /= 2)
+    if (wattn_long_lds(128, kc, bwd) <= ADT_LDS_MAX / 2) return kc;
+  for (int kc = 64; kc >= 32; kc /= 2)
+    if (wattn_long_lds(128, kc, bwd) <= ADT_LDS_MAX) return kc;
+  return 0;
+}
+
+static inline AttnPlan adt_wattn_hd128_plan(int prec, int hd, int L, bool bwd) {
+  AttnPlan p{};
+  p.family = ATTN_STREAMED; p.nch = 1; p.grid_y = 1;
+  if (prec != ADT_PREC_F32 && prec != ADT_PREC_BF16) { snprintf(p.error, sizeof p.error, "distance attention at head size 128: prec=%d unsupported", prec); return p; }
+  if (hd != 128) {
+    snprintf(p.error, sizeof p.error, "distance attention at head size 128: head_dim=%d unsupported (%s)", hd,
+             hd == 256 ? "256 fits neither the LDS at a 32-row chunk nor 512 registers" : "16/32/64 run on the *_long entry points");
+    return p;
+  }
+  if (L < 1 || L > ATTN_LONG_LMAX) { snprintf(p.error, sizeof p.error, "distance attention at head size 128: L=%d outside 1..%d", L, ATTN_LONG_LMAX); return p; }
+  p.waves = ATTN_STREAMED_NW; p.kc = wattn_hd128_kc(bwd);
+  p.grid_y = plan_ceil(plan_ceil(L, 16), p.waves);
+  p.csk = true;
+  p.lds_bytes = wattn_long_lds(hd, p.kc, bwd);
+  return p;
+}
+
 }  // namespace adt

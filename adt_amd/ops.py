@@ -833,6 +833,32 @@ def klattn_long_scaled_bwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dO
                            _scaled(scale, hd_live))
 
 
+# ---- the distance attention at head size 128: every 1 <= L <= 1024, scale and hd_live always given ---------------
+def wattn_hd128_fwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, scale, hd_live, p=0.0, seed=None, site=0, b_offset=0, prec=None):
+    """wattn_long_scaled_fwd at head size Qm.shape[1] / H = 128 (adt_wattn_hd128.hip); an unpadded head passes 1 / sqrt(128) and 128.
+    Any other head size is an error."""
+    return _stosa_long_fwd("wattn_hd128_fwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, site, b_offset, prec, _scaled(scale, hd_live))
+
+
+def wattn_hd128_bwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, scale, hd_live, p=0.0, seed=None, site=0, b_offset=0, out=None,
+                    prec=None):
+    """wattn_long_scaled_bwd at head size 128, for wattn_hd128_fwd (the same scale, hd_live and prec)."""
+    return _stosa_long_bwd("wattn_hd128_bwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site, b_offset, out, prec,
+                           _scaled(scale, hd_live))
+
+
+def klattn_hd128_fwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, scale, hd_live, p=0.0, seed=None, site=0, b_offset=0, prec=None):
+    """klattn_long_scaled_fwd at head size 128; hd_live = 128 runs the unpadded KL kernel, fewer the lane-aware one."""
+    return _stosa_long_fwd("klattn_hd128_fwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, B, H, L, p, seed, site, b_offset, prec, _scaled(scale, hd_live))
+
+
+def klattn_hd128_bwd(Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, scale, hd_live, p=0.0, seed=None, site=0, b_offset=0, out=None,
+                     prec=None):
+    """klattn_long_scaled_bwd at head size 128, for klattn_hd128_fwd (the same scale, hd_live and prec)."""
+    return _stosa_long_bwd("klattn_hd128_bwd", Qm, Qc, Km, Kc, Vm, Vc, key_ids, Om, Oc, LSE, dOm, dOc, B, H, L, p, seed, site, b_offset, out, prec,
+                           _scaled(scale, hd_live))
+
+
 def kldist_bpr_lanes(Sm, Sc, Em, Ec, pos, neg, pvn_weight, inv_count, dEm, dEc, loss3, lanes):
     """kldist_bpr on padded rows and tables: the pad lanes stay out of every sum and log, the divergences subtract the true d, dSm / dSc
     get +0.0 there."""

@@ -158,7 +158,7 @@ def main(argv=None):
     train_ds = DisenDataset(args, user_seq, "train", seed=args.seed)
     valid_ds = DisenDataset(args, user_seq, "valid", args.eval_set, seed=args.seed + 1)
     test_ds = DisenDataset(args, user_seq, "test", args.eval_set, seed=args.seed + 2)
-    model = DisenDistSAModel(args, allow_kl_lanes=True)      # --distance_metric kl at any width
+    model = DisenDistSAModel(args, allow_kl_lanes=True, allow_wide_heads=True)      # --distance_metric kl at any width, heads of up to 128 lanes (DESIGN.md sections 27, 29)
     if world > 1:
         torch.distributed.broadcast(model.master, 0)      # the reference-shaped buffer at a padded width, the flat one otherwise
         model.push()

@@ -10,7 +10,8 @@ reductions), LayerNorm / dropout / ELU row kernels.  maxlen up to 1024: past ops
 the attention runs on the streamed matrix-core kernels of adt_wattn_long.cuh.
 Under the Wasserstein distance -- and, with allow_kl_lanes=True, under 'kl'  -- any (hidden_units, num_heads) that wide.padded_layout accepts with heads of up to 64 lanes runs too (50 / 1,
 100 / 2, 48 / 4, 150 / 3): activations and parameters are padded to d_pad columns, the registered parameters keep the reference's shapes
-(DESIGN.md section 26).
+(DESIGN.md section 26).  With allow_wide_heads=True heads of 128 lanes run as well (128 / 1, 256 / 2; 100 / 1 and 200 / 2 padded): their attention
+is the streamed family at head size 128 (ops.wattn_hd128_* / klattn_hd128_*) at every maxlen.
 """
 import math
 
@@ -120,8 +121,10 @@ def padded_tables(item_size, maxlen, d, H, nl, num_users, dec_layernorm=True):
 
 
 class DisenDistSAModel(DistRankMixin, FlatModule):
-    def __init__(self, args, block=0, dec_layernorm=True, allow_kl_lanes=False):
-        """allow_kl_lanes: take distance_metric='kl' at a padded width; without it that pair raises, as it always has."""
+    def __init__(self, args, block=0, dec_layernorm=True, allow_kl_lanes=False, allow_wide_heads=False):
+        """allow_kl_lanes: take distance_metric='kl' at a padded width; without it that pair raises, as it always has.
+        allow_wide_heads: take a head that pads to 128 lanes (128 / 1, 256 / 2, 100 / 1, 200 / 2); without it such a
+        width raises, as it always has."""
         super().__init__()
         self.args = args
         self.item_size, self.maxlen, self.hidden_units = args.item_size, args.maxlen, args.hidden_units
@@ -137,9 +140,14 @@ class DisenDistSAModel(DistRankMixin, FlatModule):
                 self.hd, self.hd_pad, self.dp = padded_layout(d, H)
             except _lib.AdtError as e:
                 raise _lib.AdtError("DisenDistSAModel (adt_amd): %s" % e) from None
-            if self.hd_pad > 64:
+            if self.hd_pad > 128:
                 raise _lib.AdtError("DisenDistSAModel (adt_amd): d=%d H=%d has head size %d, which pads to %d lanes; the distance attention is "
-                                    "built for head sizes up to 64" % (d, H, self.hd, self.hd_pad))
+                                    "built for head sizes up to 128 (at 256 lanes its backward fits neither the LDS nor the register file)"
+                                    % (d, H, self.hd, self.hd_pad))
+            if self.hd_pad > 64 and not allow_wide_heads:
+                raise _lib.AdtError("DisenDistSAModel (adt_amd): d=%d H=%d has head size %d, which pads to %d lanes; the distance attention is "
+                                    "built for head sizes up to 64, and head size 128 is opt-in: pass allow_wide_heads=True to DisenDistSAModel "
+                                    "(stosa/main.py does)" % (d, H, self.hd, self.hd_pad))
             if block:
                 raise _lib.AdtError("DisenDistSASupernet (adt_amd): the supernet is built for hidden_units a multiple of 64 with head size "
                                     "16/32/64 only (padded widths run on DisenDistSAModel), got d=%d H=%d" % (d, H))
@@ -164,20 +172,23 @@ class DisenDistSAModel(DistRankMixin, FlatModule):
         self._long_attn = self.maxlen > ops.wattn_max_len(self.hd_pad)
         if self._long_attn:
             self._attn_fwd, self._attn_bwd = (ops.klattn_long_fwd, ops.klattn_long_bwd) if kl else (ops.wattn_long_fwd, ops.wattn_long_bwd)
+        # head size 128 (allow_wide_heads): its own streamed family at every maxlen, scale and live lanes always given
+        wide_heads = self.hd_pad == 128
+        if wide_heads:
+            self._set_scaled_attn(*((ops.klattn_hd128_fwd, ops.klattn_hd128_bwd) if kl else (ops.wattn_hd128_fwd, ops.wattn_hd128_bwd)))
         self._dist_bpr, self._dist_full = (ops.kldist_bpr, ops.kldist_full) if kl else (ops.wdist_bpr, ops.wdist_full)
         if self.lanes is None:
             table, n_trained = param_table(args.item_size, args.maxlen, d, H, args.num_layers, args.num_users, block, dec_layernorm)
             self._build_flat(table, getattr(args, "device", "cuda:0"), REF_ORDER)
             ref_table = self.table
         else:
-            ln, scaled = self.lanes, (1.0 / math.sqrt(self.hd), self.hd)       # the score scale of the TRUE head size, for both directions
-            if kl:
-                fwd, bwd = (ops.klattn_long_scaled_fwd, ops.klattn_long_scaled_bwd) if self._long_attn else (ops.klattn_scaled_fwd, ops.klattn_scaled_bwd)
-            else:
-                fwd, bwd = (ops.wattn_long_scaled_fwd, ops.wattn_long_scaled_bwd) if self._long_attn else (ops.wattn_scaled_fwd, ops.wattn_scaled_bwd)
-            self._attn_fwd = lambda Qm, Qc, Km, Kc, Vm, Vc, kid, B, H, L, *a, **k: fwd(Qm, Qc, Km, Kc, Vm, Vc, kid, B, H, L, *scaled, *a, **k)
-            self._attn_bwd = lambda Qm, Qc, Km, Kc, Vm, Vc, kid, Om, Oc, LSE, dOm, dOc, B, H, L, *a, **k: \
-                bwd(Qm, Qc, Km, Kc, Vm, Vc, kid, Om, Oc, LSE, dOm, dOc, B, H, L, *scaled, *a, **k)
+            ln = self.lanes
+            if not wide_heads:
+                if kl:
+                    fwd, bwd = (ops.klattn_long_scaled_fwd, ops.klattn_long_scaled_bwd) if self._long_attn else (ops.klattn_scaled_fwd, ops.klattn_scaled_bwd)
+                else:
+                    fwd, bwd = (ops.wattn_long_scaled_fwd, ops.wattn_long_scaled_bwd) if self._long_attn else (ops.wattn_scaled_fwd, ops.wattn_scaled_bwd)
+                self._set_scaled_attn(fwd, bwd)
             dist_bpr, dist_full = (ops.kldist_bpr_lanes, ops.kldist_full_lanes) if kl else (ops.wdist_bpr_lanes, ops.wdist_full_lanes)
             self._dist_bpr = lambda *a: dist_bpr(*a, ln)
             self._dist_full = lambda *a: dist_full(*a, ln)
@@ -194,6 +205,13 @@ class DisenDistSAModel(DistRankMixin, FlatModule):
             elif name.endswith(".weight"):
                 v.copy_(0.01 + std * torch.randn(shape, generator=g))
         self.push()
+
+    def _set_scaled_attn(self, fwd, bwd):
+        """The attention through entry points that take (scale, hd_live): the score scale of the TRUE head size, for both directions."""
+        scaled = (1.0 / math.sqrt(self.hd), self.hd)
+        self._attn_fwd = lambda Qm, Qc, Km, Kc, Vm, Vc, kid, B, H, L, *a, **k: fwd(Qm, Qc, Km, Kc, Vm, Vc, kid, B, H, L, *scaled, *a, **k)
+        self._attn_bwd = lambda Qm, Qc, Km, Kc, Vm, Vc, kid, Om, Oc, LSE, dOm, dOc, B, H, L, *a, **k: \
+            bwd(Qm, Qc, Km, Kc, Vm, Vc, kid, Om, Oc, LSE, dOm, dOc, B, H, L, *scaled, *a, **k)
 
     # ------------------------------------------------------------------------------------------------------------------
     def _embed(self, tp, ids, which, site):

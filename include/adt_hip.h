@@ -844,6 +844,28 @@ int adt_klattn_long_scaled_bwd(int prec, const float* Qm, int ldqm, const float*
     const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd, float scale, int hd_live,
     float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc, float* dKm, float* dKc, float* dVm,
     float* dVc, int ldd, void* stream);
+/* The distance attention at head size 128 (hd must be 128; 1 <= L <= 1024; adt_wattn_hd128.hip): the streamed kernels
+ * of the *_long_* entry points, which keep refusing that head size, with the argument lists of the *_long_scaled_* ones: scale and hd_live
+ * are always given (an unpadded head passes 1 / sqrt(128) and 128; a head padded from 100 lanes 1 / sqrt(100) and 100).  Errors, in this
+ * order and before anything is launched: an unknown prec, hd != 128 (256 fits neither the LDS nor the register file), L outside 1..1024,
+ * an empty shape, null key_ids, a row stride that is no multiple of 4, scale <= 0 or hd_live outside 1..128, and with p > 0 a dropout
+ * index space (b_offset + B) * H * L * L that reaches 2^32. */
+int adt_wattn_hd128_fwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float scale, int hd_live,
+    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE, void* stream);
+int adt_wattn_hd128_bwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc, int ldoc,
+    const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd, float scale, int hd_live,
+    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc, float* dKm, float* dKc, float* dVm,
+    float* dVc, int ldd, void* stream);
+int adt_klattn_hd128_fwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, int B, int H, int L, int hd, float scale, int hd_live,
+    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* Om, int ldom, float* Oc, int ldoc, float* LSE, void* stream);
+int adt_klattn_hd128_bwd(int prec, const float* Qm, int ldqm, const float* Qc, int ldqc, const float* Km, int ldkm, const float* Kc, int ldkc,
+    const float* Vm, int ldvm, const float* Vc, int ldvc, const int32_t* key_ids, const float* Om, int ldom, const float* Oc, int ldoc,
+    const float* LSE, const float* dOm, int lddom, const float* dOc, int lddoc, int B, int H, int L, int hd, float scale, int hd_live,
+    float p, const uint32_t* seed, uint32_t site, uint32_t b_offset, float* dQm, float* dQc, float* dKm, float* dKc, float* dVm,
+    float* dVc, int ldd, void* stream);
 /* adt_kldist_bpr / adt_kldist_full / adt_klrow_pack on padded rows and tables of d_pad = H * hd_pad columns (head h at columns
  * [h * hd_pad, h * hd_pad + hd)): a pad lane holds a sequence covariance 0 and an item covariance ELU(0) + 1 = 1, so the pad lanes are
  * left out of every sum and log and the divergences subtract the true d = H * hd; dSm / dSc get +0.0 on them, the tables' pad lanes

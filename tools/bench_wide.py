@@ -82,7 +82,7 @@ def run_stosa(args):
     a.device, a.item_size, a.maxlen, a.hidden_units, a.num_heads, a.num_layers, a.num_users = "cuda:0", 12103, args.stosa_maxlen, d, H, 1, 22364
     a.dropout, a.attention_dropout, a.pvn_weight, a.precision, a.distance_metric = 0.3, 0.3, 0.005, "bf16", args.metric
     torch.manual_seed(42)
-    m = DisenDistSAModel(a, allow_kl_lanes=True)
+    m = DisenDistSAModel(a, allow_kl_lanes=True, allow_wide_heads=True)
     tr = FusedStosaTrainer(m, [0.1], [0.1], use_graph=not args.no_graph, seed=42)
     r = np.random.RandomState(2)
     B, L, V = args.batch, a.maxlen, a.item_size

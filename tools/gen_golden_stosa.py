@@ -56,9 +56,9 @@ def kl_predict_full(modules, mo, co, Em, Ec):
     return res[:, :V]
 
 
-def reference_model(cfg_kw, B, seed, metric, pad_min=0):
+def reference_model(cfg_kw, B, seed, metric, pad_min=0, cov_qk_bias=0.0):
     """The reference's DisenDistSAModel with the seeded weights of a fixture and that fixture's batch: (cfg, args, model, the
-    reference's modules, (input_ids, dec_ids, pos_ids, neg_ids))."""
+    reference's modules, (input_ids, dec_ids, pos_ids, neg_ids)).  cov_qk_bias is added to every cov_query / cov_key bias (main_hd128)."""
     from tools.gen_golden_wide import _import_from
     from oracle import stosa_oracle as so
     models = _import_from("/root/reference/stosa", "models")
@@ -69,6 +69,8 @@ def reference_model(cfg_kw, B, seed, metric, pad_min=0):
     for k in P:   # biases away from zero so that their gradients are exercised
         if k.endswith(".bias") and "LayerNorm" not in k:
             P[k] = (0.02 * r.standard_normal(P[k].shape)).astype(np.float32)
+            if k.endswith(("cov_query.bias", "cov_key.bias")):
+                P[k] += np.float32(cov_qk_bias)
     batch = stosa_batch(r, B, cfg.maxlen, cfg.item_size, pad_min)
     a = Args()
     a.item_size, a.hidden_units, a.maxlen, a.num_users, a.dropout, a.attention_dropout = cfg.item_size, cfg.hidden_units, cfg.maxlen, cfg.num_users, 0.0, 0.0
@@ -80,13 +82,15 @@ def reference_model(cfg_kw, B, seed, metric, pad_min=0):
 
 
 def gen_stosa(tag, cfg_kw, B, seed, lam1, lam2, lr=1e-3, keep_w3=True, compact=False, steps=3, metric="wasserstein", keep_w1=True, thresh=8192,
-              pad_min=0, nsample=1024):
-    cfg, a, m, modules, (inp, dec, pos, neg) = reference_model(cfg_kw, B, seed, metric, pad_min)
+              pad_min=0, nsample=1024, cov_qk_bias=0.0):
+    cfg, a, m, modules, (inp, dec, pos, neg) = reference_model(cfg_kw, B, seed, metric, pad_min, cov_qk_bias)
     t = [torch.from_numpy(x) for x in (inp, dec, pos, neg)]
     uid = torch.zeros(B, dtype=torch.long)
     out = {"seed": seed, "input_ids": inp, "dec_ids": dec, "pos_ids": pos, "neg_ids": neg, "lambda1": np.array(lam1), "lambda2": np.array(lam2),
            "lr": lr, "cfg": np.array([cfg.item_size, cfg.maxlen, cfg.hidden_units, cfg.num_heads, cfg.num_layers, cfg.num_users]),
            "pvn_weight": cfg.pvn_weight}
+    if cov_qk_bias:
+        out["cov_qk_bias"] = cov_qk_bias
     m.eval()
     with torch.no_grad():
         mo, co, att, margins, enc_in, enc_rec, dec_out = m.finetune(t[0], t[1], uid)
@@ -227,6 +231,24 @@ def main_kl_odd():
               lam1=[0.1], lam2=[0.05], **kw)
 
 
+def main_hd128():
+    """stosa_hd128 / stosa_kl_hd128 (d 128, one head), stosa_w100_h1 / stosa_kl_w100_h1 (d 100, one head: 128 lanes) and stosa_hd128_h2.npz
+    (d 256, two heads, two layers: the head classifier at 128 lanes and the head offset): head size 128, compacted
+    like main_odd().  The weights after the first step are left out, as in main_kl(): they follow from the initial weights and the
+    gradient; stosa_hd128_h2 keeps no weights at all (main()'s l2h2 keeps none after step 3 either), which holds every file under 300 KB.
+    Under KL at d 128 the reference's own N(0.01, 0.02) initialisation makes the attention's covariances about 2.3 a lane, and its
+    kl_distance_matmul takes their PRODUCT over the 128 lanes of a head (stosa/modules.py:53-55): 2.3^128 overflows fp32 and every output is
+    NaN.  stosa_kl_hd128 therefore shifts the cov_query / cov_key biases by -0.7 (stored as cov_qk_bias), which keeps the products finite."""
+    kw = dict(compact=True, thresh=2048, nsample=STOSA_ODD_COMPACT, keep_w1=False)
+    for metric in ("wasserstein", "kl"):
+        gen_stosa("hd128", dict(item_size=42, maxlen=12, hidden_units=128, num_heads=1, num_layers=1, num_users=4, pvn_weight=0.005), B=4, seed=51,
+                  lam1=[0.3], lam2=[0.2], metric=metric, cov_qk_bias=-0.7 if metric == "kl" else 0.0, **kw)
+        gen_stosa("w100_h1", dict(item_size=42, maxlen=12, hidden_units=100, num_heads=1, num_layers=1, num_users=4, pvn_weight=0.005), B=4, seed=52,
+                  lam1=[0.3], lam2=[0.2], metric=metric, **kw)
+    gen_stosa("hd128_h2", dict(item_size=33, maxlen=20, hidden_units=256, num_heads=2, num_layers=2, num_users=3, pvn_weight=0.1), B=3, seed=53,
+              lam1=[0.25, 0.1], lam2=[0.15, 0.05], keep_w3=False, steps=1, **kw)
+
+
 def main_kl_rowwise():
     """stosa_kl_rowwise.npz: the model, seed and input_ids of stosa_kl_small.npz; rowwise_dist[b][v] = the reference's kl_distance
     (stosa/modules.py:45-50) of user b's last-position (mean, cov) from item v's (mean, ELU(cov) + 1), every row of the item tables --
@@ -252,11 +274,13 @@ if __name__ == "__main__":
     import argparse
     sys.path.insert(0, REPO)
     ap = argparse.ArgumentParser()
-    ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl", "kl_rowwise", "long", "stosa_odd", "stosa_kl_odd"])
+    ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl", "kl_rowwise", "long", "stosa_odd", "stosa_kl_odd", "stosa_hd128"])
     metric = ap.parse_args().metric
     if metric == "stosa_odd":
         main_odd()
     elif metric == "stosa_kl_odd":
         main_kl_odd()
+    elif metric == "stosa_hd128":
+        main_hd128()
     else:
         main_kl_rowwise() if metric == "kl_rowwise" else (main_long() if metric == "long" else main(metric))
