@@ -177,6 +177,8 @@ SIGNATURES = {
     "adt_kldist_pack": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
     "adt_klrow_pack": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P]),
     "adt_kldist_full_groups": (_I, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P]),
+    "adt_kldist_pack_lanes": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "adt_kldist_full_groups_lanes": (_I, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "adt_seqbatch_build": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U, _U, _P, _P, _P, _P, _P, _P]),
     "adt_seqbatch_draw": (_I, [_U, _U, _I, _I, _I, _I]),
     "adt_bertbatch_build": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _U, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

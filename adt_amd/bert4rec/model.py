@@ -83,15 +83,16 @@ def param_table(item_num, maxlen, d, H, nl, inner, type_vocab, vocab=None, block
     return t
 
 
-def padded_tables(item_num, maxlen, d, H, nl, inner, type_vocab, vocab=None):
+def padded_tables(item_num, maxlen, d, H, nl, inner, type_vocab, vocab=None, block=0):
     """(ref_table, pad_table, prefix) of a width the kernels do not tile (adt_amd/wide.py:padded_layout; pure arithmetic): the reference's
     shapes, the same names at the padded shapes -- d -> d_pad with head h at [h * hd_pad, h * hd_pad + hd), head_classifier (H, hd_pad),
     inner_units rounded up to a multiple of 4 (the dense kernels' leading dimensions) -- and the (name, axis) pairs of that zero-filled
-    inner tail for lane_index.  GELU(0) = 0, the bias pad is 0 and the pad columns of fc2 are 0, so the tail changes nothing."""
+    inner tail for lane_index.  GELU(0) = 0, the bias pad is 0 and the pad columns of fc2 are 0, so the tail changes nothing.  block > 0:
+    the supernet's tables (param_table's `block`) under the same rules."""
     _, _, dp = padded_layout(d, H)
     inner_pad = (inner + 3) // 4 * 4
-    ref = param_table(item_num, maxlen, d, H, nl, inner, type_vocab, vocab)
-    pad = param_table(item_num, maxlen, dp, H, nl, inner_pad, type_vocab, vocab)
+    ref = param_table(item_num, maxlen, d, H, nl, inner, type_vocab, vocab, block)
+    pad = param_table(item_num, maxlen, dp, H, nl, inner_pad, type_vocab, vocab, block)
     prefix = set()
     if inner_pad != inner:
         for name, _ in ref:
@@ -103,7 +104,9 @@ def padded_tables(item_num, maxlen, d, H, nl, inner, type_vocab, vocab=None):
 
 
 class BertModel(FullRankMixin, FlatModule):
-    def __init__(self, usernum, itemnum, args, vocab=None, inner_units=None, block=0):
+    def __init__(self, usernum, itemnum, args, vocab=None, inner_units=None, block=0, allow_block_lanes=False):
+        """allow_block_lanes: the supernet's layout (block > 0) at a width the kernels do not tile (SuperBertModel(allow_lanes=True);
+        DESIGN.md section 30); without it that pair raises, as it always has."""
         super().__init__()
         self.usernum, self.itemnum = usernum, itemnum
         self.maxlen, self.num_heads, self.num_layers = args.maxlen, args.num_heads, args.num_layers
@@ -119,7 +122,7 @@ class BertModel(FullRankMixin, FlatModule):
         self.prec = {"f32": ops.PREC_F32, "fp32": ops.PREC_F32, "bf16": ops.PREC_BF16}[getattr(args, "precision", "bf16")]
         d, H = self.hidden_units, self.num_heads
         tiled = d >= 64 and d % 64 == 0 and d % H == 0 and (d // H) in (16, 32, 64)      # the widths this model has always taken, as they are
-        if block and not tiled:
+        if block and not tiled and not allow_block_lanes:
             raise _lib.AdtError("SuperBertModel (adt_amd): the supernet is built for hidden_units a multiple of 64 with head size 16/32/64 only "
                                 "(padded widths and head sizes 128 / 256 run on BertModel), got d=%d H=%d" % (d, H))
         if tiled:
@@ -143,7 +146,7 @@ class BertModel(FullRankMixin, FlatModule):
                              REF_ORDER)
             ref_table = self.table
         else:
-            ref_table, table, prefix = padded_tables(itemnum, args.maxlen, d, H, args.num_layers, self.inner_units, tv, self.vocab)
+            ref_table, table, prefix = padded_tables(itemnum, args.maxlen, d, H, args.num_layers, self.inner_units, tv, self.vocab, block)
             self._build_flat(table, args.device, REF_ORDER, ref_table=ref_table, width=(d, H), prefix=prefix)
         # bert4rec/trainer.py:29-37 re-initialises every Linear/Embedding weight N(0.01, initializer_range), LayerNorm 1/0,
         # Linear bias 0; do the same here so that a freshly constructed model is usable

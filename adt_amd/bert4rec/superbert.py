@@ -33,18 +33,24 @@ def _cand_sites(sites, k):
 
 
 class SuperBertModel(BertModel):
-    def __init__(self, usernum, itemnum, rec_choice, ind_choice, args):
+    def __init__(self, usernum, itemnum, rec_choice, ind_choice, args, allow_lanes=False):
+        """allow_lanes: every (hidden_units, num_heads) BertModel takes is opt-in (bert4rec/evolution.py passes True):
+        the padded tables with `block` candidate layers per depth.  Without it a width the kernels do not tile raises, as it always has;
+        a tiled width runs the same code with or without it."""
         self.rec_choice, self.ind_choice = np.asarray(rec_choice, np.float64), np.asarray(ind_choice, np.float64)
         self.block = len(self.rec_choice) * len(self.ind_choice)
-        super().__init__(usernum, itemnum, args, vocab=itemnum + 2, inner_units=4 * args.hidden_units, block=self.block)
+        super().__init__(usernum, itemnum, args, vocab=itemnum + 2, inner_units=4 * args.hidden_units, block=self.block,
+                         allow_block_lanes=bool(allow_lanes))
         # SearcherEvolution._generate_supernet (bert4rec/evolution.py:104-112): trunc_normal_(std = initializer_range) on every tensor
         # whose name holds neither 'layer_norm' nor 'bias'; the others keep torch's constructor defaults (LayerNorm 1 / 0, mask_bias 0,
-        # Linear bias U(-1/sqrt(fan_in), 1/sqrt(fan_in)))
+        # Linear bias U(-1/sqrt(fan_in), 1/sqrt(fan_in))).  Shapes and fans are the reference's: at a padded width the live lanes only
+        # are written (R(): the reference-shaped parameters), then pushed
         g = torch.Generator(device="cpu").manual_seed(torch.initial_seed() % (1 << 31))
         std = float(getattr(args, "initializer_range", 0.02))
-        shapes = dict(self.table)
-        for name, shape in self.table:
-            v = self.P(name)
+        ref_table = [(name, (self._ref_views or self._views)[name][2]) for name, _ in self.table]
+        shapes = dict(ref_table)
+        for name, shape in ref_table:
+            v = self.R(name)
             if "layer_norm" in name:
                 v.fill_(1.0 if name.endswith("weight") else 0.0)
             elif name == "mask_bias":
@@ -56,6 +62,7 @@ class SuperBertModel(BertModel):
                 t = torch.empty(shape)
                 torch.nn.init.trunc_normal_(t, std=std, generator=g)
                 v.copy_(t)
+        self.push()
         self.shared = [((0, 0, 0, 0), (0.0, 0.0, 0.0, 0.0)) for _ in range(self.num_layers)]
 
     def set_choice(self, cand):
@@ -116,6 +123,7 @@ class SuperBertModel(BertModel):
         B, L = src.shape
         was = self.training
         self.eval()
+        self.push()      # padded widths: the reference-shaped parameters are the truth between steps (no-op otherwise)
         tp = Tape(self, self.prec, False)
         flat = src.view(-1)
         x0 = self._embed(tp, flat, SITE_EMB_SEQ)
@@ -146,7 +154,7 @@ class SuperBertModel(BertModel):
         P = len(shared_list)
         if P > 1:
             cand = cand.repeat(P, 1)
-        _, rank = ops.score_rank_bias(h, self.hidden_units, self.P("item_emb.word_emb.weight"), self.P("mask_bias"), cand, P * B, cand.shape[1], True)
+        _, rank = ops.score_rank_bias(h, self.dp, self.P("item_emb.word_emb.weight"), self.P("mask_bias"), cand, P * B, cand.shape[1], True)
         return rank.view(P, B)
 
     @torch.no_grad()

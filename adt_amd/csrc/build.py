@@ -5,7 +5,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["adt_capi.hip", "adt_sasrec.hip", "adt_wide.hip", "adt_seq.hip", "adt_lce.hip", "adt_fullrank.hip", "adt_seqbatch.hip", "adt_attn_long.hip",
-           "adt_wattn_long.hip", "adt_wattn_hd128.hip"]
+           "adt_wattn_long.hip", "adt_wattn_hd128.hip", "adt_kldist_lanes.hip"]
 OUT = os.path.join(HERE, "libadt_hip.so")
 
 HOST_SRC = "adt_hostdata.cpp"

@@ -1011,6 +1011,31 @@ def kldist_full_groups(Sm, Sc, img, lv, E, V):
     return dist
 
 
+def kldist_pack_lanes(Em, Ec, lanes):
+    """kldist_pack on padded tables (adt_kldist_pack_lanes): img (V, 2 d_pad) with +0.0 on the pad lanes of both halves, lv over the live
+    lanes; no pad lane reaches a log or a divide."""
+    H, hd, hd_pad = lanes
+    assert Em.dim() == 2 and Em.shape == Ec.shape and Em.stride(0) == Ec.stride(0), (Em.shape, Ec.shape, Em.stride(), Ec.stride())
+    V, dp = Em.shape
+    img = torch.empty(V, 2 * dp, device=Em.device, dtype=torch.float32)
+    lv = torch.empty(V, device=Em.device, dtype=torch.float32)
+    _lib.check(_lib.load().adt_kldist_pack_lanes(_p(_f32(Em)), _p(_f32(Ec)), Em.stride(0), V, dp, H, hd, hd_pad, _p(img), 2 * dp, _p(lv), _stream()),
+               "kldist_pack_lanes")
+    return img, lv
+
+
+def kldist_full_groups_lanes(Sm, Sc, img, lv, E, V, lanes):
+    """kldist_full_groups on padded state rows and the image of kldist_pack_lanes: the score over the live lanes, with the true d."""
+    H, hd, hd_pad = lanes
+    assert Sm.dim() == 2 and Sm.shape == Sc.shape and Sm.stride(0) == Sc.stride(0), (Sm.shape, Sc.shape, Sm.stride(), Sc.stride())
+    rows, dp = Sm.shape
+    assert img.shape[1] == 2 * dp and img.shape[0] >= V and lv.numel() >= V, (img.shape, lv.shape, V, dp)
+    dist = torch.empty(rows, V, device=Sm.device, dtype=torch.float32)
+    _lib.check(_lib.load().adt_kldist_full_groups_lanes(_p(_f32(Sm)), _p(_f32(Sc)), Sm.stride(0), _p(_f32(img)), img.stride(0), _p(_f32(lv)), rows,
+                                                        int(E), int(V), dp, H, hd, hd_pad, _p(dist), V, _stream()), "kldist_full_groups_lanes")
+    return dist
+
+
 # ---- STOSA-ADT batches built on the device (include/adt_hip.h: adt_seqbatch_build; adt_amd/csrc/adt_seqbatch.cuh) -----------------------
 def seqbatch_build(seq_off, seq_items, set_off, set_items, users, L, cut, item_size, seed=0, step=0, rows=None, want_neg=True,
                    want_inv_count=True, views=True):

@@ -92,7 +92,7 @@ class SearcherEvolution:
         self.rec_choice = [0, 0.0001, 0.0005, 0.001, 0.005, 0.01]
         self.ind_choice = [0, 0.0001, 0.0005, 0.001, 0.0015, 0.002]
         torch.manual_seed(args.seed)
-        self.model = SuperSASRecModel(usernum, itemnum, self.rec_choice, self.ind_choice, args)
+        self.model = SuperSASRecModel(usernum, itemnum, self.rec_choice, self.ind_choice, args, allow_lanes=True)
         self.trainer = SuperTrainer(self.model, lr=args.lr, betas=(0.9, 0.999), weight_decay=args.weight_decay, clip=args.clip, seed=args.seed)
         self.search_state = EvolutionSearch(args.num_layers, self.evaluate_candidates, "auc", args.select_num, args.population_num, args.m_prob,
                                             args.crossover_num, args.mutation_num, args.scale_factor)

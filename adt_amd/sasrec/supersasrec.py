@@ -20,7 +20,7 @@ import torch
 
 from .. import _lib, custom_ops, ops
 from ..supersearch import SupernetTrainer, candidate_features, cand_to_block, get_position, get_shared, get_weight  # noqa: F401
-from ..wide import Act, FlatModule, Tape, give, loss_norms
+from ..wide import Act, FlatModule, Tape, give, loss_norms, padded_layout
 from .model import REF_ORDER
 from .model_wide import seed_mse_nll
 
@@ -43,6 +43,20 @@ def _shapes(d, H):
     return enc, dec
 
 
+def param_table(itemnum, maxlen, width, H, nl, block):
+    """[(state_dict name, shape)] in flat order at row width `width`: the true d (the reference's shapes), or d_pad with the head
+    classifiers at (H, hd_pad) (the padded layout, wide.padded_layout).  Pure arithmetic: no GPU, no library."""
+    es, ds = _shapes(width, H)
+    t = [("item_emb.weight", (itemnum + 1, width)), ("pos_emb.weight", (maxlen, width))]
+    for i in range(nl):
+        for c in range(block):
+            t += [("encoder.encoder_layers.%d.%d.%s" % (i, c, n), s) for n, s in zip(_ENC, es)]
+    for i in range(nl):
+        for c in range(block):
+            t += [("decoder.decoder_layers.%d.%d.%s" % (i, c, n), s) for n, s in zip(_DEC, ds)]
+    return t
+
+
 def enc_sites(i, k):
     b = 16 + 8 * i + CAND_SITE * (k + 1)
     return {"attn": b, "ffn1": b + 1, "ffn2": b + 2}
@@ -54,7 +68,11 @@ def dec_sites(i, k):
 
 
 class SuperSASRecModel(FlatModule):
-    def __init__(self, usernum, itemnum, rec_choice, ind_choice, args):
+    def __init__(self, usernum, itemnum, rec_choice, ind_choice, args, allow_lanes=False):
+        """allow_lanes: every (hidden_units, num_heads) wide.padded_layout accepts and maxlen up to 1024 are opt-in (sasrec/evolution.py
+        passes True), as SASRecADTWide runs them: padded rows of d_pad columns, the streamed attention past
+        ops.attn_masked_max_len.  Without it such a shape raises, as it always has; a shape the constructor has always taken runs the same
+        code with or without it."""
         super().__init__()
         self.usernum, self.itemnum = usernum, itemnum
         self.num_heads, self.maxlen, self.num_layers = args.num_heads, args.maxlen, args.num_layers
@@ -64,26 +82,42 @@ class SuperSASRecModel(FlatModule):
         self.prec = {"f32": ops.PREC_F32, "fp32": ops.PREC_F32, "bf16": ops.PREC_BF16}[getattr(args, "precision", "bf16")]
         d, H = self.hidden_units, self.num_heads
         hd = d // H if H >= 1 and d % H == 0 else 0
-        if d not in (64, 128, 192, 256) or hd not in (16, 32, 64, 128, 256) or not 1 <= args.maxlen <= (224 if hd <= 64 else 256):
+        plain = d in (64, 128, 192, 256) and hd in (16, 32, 64, 128, 256) and 1 <= args.maxlen <= (224 if hd <= 64 else 256)
+        if not plain and not allow_lanes:
             raise _lib.AdtError("SuperSASRecModel (adt_amd): hidden_units in {64,128,192,256}, head size in {16,32,64,128,256}, maxlen <= 224 "
                                 "(head size <= 64) or <= 256 (128, 256); got d=%d H=%d L=%d" % (d, H, args.maxlen))
-        es, ds = _shapes(d, H)
-        table = [("item_emb.weight", (itemnum + 1, d)), ("pos_emb.weight", (args.maxlen, d))]
-        for i in range(self.num_layers):
-            for c in range(self.block):
-                table += [("encoder.encoder_layers.%d.%d.%s" % (i, c, n), s) for n, s in zip(_ENC, es)]
-        for i in range(self.num_layers):
-            for c in range(self.block):
-                table += [("decoder.decoder_layers.%d.%d.%s" % (i, c, n), s) for n, s in zip(_DEC, ds)]
-        self._build_flat(table, args.device, REF_ORDER)
+        if plain:
+            self.hd, self.hd_pad, self.dp = hd, hd, d
+        else:
+            try:
+                self.hd, self.hd_pad, self.dp = padded_layout(d, H)
+            except _lib.AdtError as e:
+                raise _lib.AdtError("SuperSASRecModel (adt_amd): %s" % e) from None
+            if not 1 <= args.maxlen <= 1024:
+                raise _lib.AdtError("SuperSASRecModel (adt_amd): maxlen in 1..1024; got d=%d H=%d L=%d" % (d, H, args.maxlen))
+        # dp == d: the kernels tile the width as it is.  Otherwise activations and parameters are padded to dp columns (head h at
+        # [h * hd_pad, h * hd_pad + hd), zero pad lanes; DESIGN.md sections 11 and 30) and LayerNorm, the scales and the dropout indices
+        # keep the true width.  hidden_units stays the true d; dp is the row the kernels see.
+        self.lanes = (H, self.hd, self.hd_pad) if self.dp != d else None
+        # the shapes the constructor has always taken keep their attention calls; a new one runs the general masked attention, and the
+        # streamed kernels past the length that takes at this head size (as SASRecADTWide)
+        self._general_attn = d != 64 or not plain
+        self._long_attn = not plain and args.maxlen > ops.attn_masked_max_len(self.hd_pad)
+        ref_table = param_table(itemnum, args.maxlen, d, H, self.num_layers, self.block)
+        if self.lanes is None:
+            self._build_flat(ref_table, args.device, REF_ORDER)
+        else:
+            self._build_flat(param_table(itemnum, args.maxlen, self.dp, H, self.num_layers, self.block), args.device, REF_ORDER,
+                             ref_table=ref_table, width=(d, H))
         g = torch.Generator(device="cpu").manual_seed(torch.initial_seed() % (1 << 31))
-        for name, shape in self.table:     # evolution.py:103-107: xavier_normal_ on >= 2-D tensors; 1-D keep torch defaults
-            v = self.P(name)
+        for name, shape in ref_table:      # evolution.py:103-107: xavier_normal_ on >= 2-D tensors; 1-D keep torch defaults
+            v = self.R(name)               # reference shape: the fans are the true ones, only live lanes are written
             if len(shape) >= 2:
                 fan = shape[0] + shape[1] * (shape[2] if len(shape) > 2 else 1)
                 v.copy_(torch.randn(shape, generator=g) * math.sqrt(2.0 / fan))
             elif "norm.weight" in name:
                 v.fill_(1.0)
+        self.push()
         self.shared = [((0, 0, 0, 0), (0.0, 0.0, 0.0, 0.0)) for _ in range(self.num_layers)]
 
     def set_choice(self, cand):
@@ -111,7 +145,7 @@ class SuperSASRecModel(FlatModule):
         """d = 64 only: wider supernets run every candidate layer on the width-generic stage kernels."""
         if getattr(self, "_fused", None) is None:
             import os
-            on = os.environ.get("ADT_SUPER_FUSED", "1") != "0" and self.prec == ops.PREC_BF16 and self.hidden_units == 64
+            on = os.environ.get("ADT_SUPER_FUSED", "1") != "0" and self.prec == ops.PREC_BF16 and self.hidden_units == 64 and self.lanes is None
             self._fused = bool(on and self.lib.adt_seq_layer_supported(self.prec, self.maxlen, self.hidden_units, self.hidden_units // self.num_heads))
             if self._fused:
                 self._wimg = torch.empty(3 * self.flat.numel(), device=self.dev, dtype=torch.float32)      # 6 bf16 per parameter float
@@ -253,6 +287,8 @@ class SuperSASRecModel(FlatModule):
         P, G = self.P, self.G
         L = self.maxlen
         p = tp.p_eff(self.dropout)
+        if self.lanes is not None:
+            return self._embed_lanes(tp, ids, site, p)
         x = Act(ops.embed_fwd(ids, P("item_emb.weight"), P("pos_emb.weight"), L, p, self._seed, site, tp.row_offset))
 
         def bw():
@@ -261,20 +297,40 @@ class SuperSASRecModel(FlatModule):
         tp.bw.append(bw)
         return x
 
+    def _embed_lanes(self, tp, ids, site, p):
+        """_embed on a padded width (SASRecADTWide._embed_lanes): sqrt(d) with the true d, dropout indexed at the true width
+        (adt_drop_lanes), then the row mask."""
+        P, G = self.P, self.G
+        L, scale = self.maxlen, float(self.hidden_units) ** 0.5
+        X = ops.embed_sum_fwd(ids, P("item_emb.weight"), P("pos_emb.weight"), L, None, scale)
+        x = Act(ops.drop_lanes(X, self.lanes, p, self._seed, site, tp.row_offset, mask_ids=ids, out=X))
+
+        def bw():
+            if x.g is None:
+                return
+            g = ops.drop_lanes(x.g, self.lanes, p, self._seed, site, tp.row_offset, mask_ids=ids)
+            ops.item_scatter(ids, g, None, scale, 0.0, None, 0, 0, G("item_emb.weight"), 1, 0)
+            ops.posemb_bwd(ids, g, L, 0.0, None, 0, 0, G("pos_emb.weight"))
+        tp.bw.append(bw)
+        return x
+
     def _attn(self, tp, q, kv, B, site, qkv=None):
         """Causal attention on packed projections; q: (T, d) Act, kv: (T, 2d) Act (or qkv: one (T, 3d) Act).  d = 64: the
         per-sequence causal kernels (ops.attn_fwd / attn_bwd); other widths: the general masked attention with the float causal
         mask of sasrec/modules.py (fill -inf), as SASRecADTWide._attn."""
-        d, H, L = self.hidden_units, self.num_heads, self.maxlen
+        d, H, L = self.dp, self.num_heads, self.maxlen
         p = tp.p_eff(self.dropout)
         if qkv is not None:
             Q, K, V = qkv.t[:, :d], qkv.t[:, d:2 * d], qkv.t[:, 2 * d:]
         else:
             Q, K, V = q.t, kv.t[:, :d], kv.t[:, d:]
-        general = d != 64
+        general = self._general_attn
         fill = float("-inf")
+        # padded heads: 1 / sqrt(true head size); past ops.attn_masked_max_len the streamed kernels (DESIGN.md section 30)
+        kw = {} if self.lanes is None else {"scale": 1.0 / math.sqrt(self.hd)}
+        masked_fwd, masked_bwd = (ops.attn_long_fwd, ops.attn_long_bwd) if self._long_attn else (ops.attn_masked_fwd, ops.attn_masked_bwd)
         if general:
-            O, LSE = ops.attn_masked_fwd(self.prec, Q, K, V, B, H, L, True, None, fill, p, self._seed, site, tp.b_offset)
+            O, LSE = masked_fwd(self.prec, Q, K, V, B, H, L, True, None, fill, p, self._seed, site, tp.b_offset, **kw)
         else:
             O, LSE = ops.attn_fwd(self.prec, Q, K, V, B, H, L, True, p, self._seed, site, tp.b_offset)
         o = Act(O)
@@ -289,20 +345,20 @@ class SuperSASRecModel(FlatModule):
                 q.g, kv.g = torch.empty_like(q.t), torch.empty_like(kv.t)
                 out = (q.g, kv.g[:, :d], kv.g[:, d:])
             if general:
-                ops.attn_masked_bwd(self.prec, Q, K, V, O, LSE, o.g, B, H, L, True, None, fill, p, self._seed, site, tp.b_offset, out=out)
+                masked_bwd(self.prec, Q, K, V, O, LSE, o.g, B, H, L, True, None, fill, p, self._seed, site, tp.b_offset, out=out, **kw)
             else:
                 ops.attn_bwd(self.prec, Q, K, V, O, LSE, o.g, B, H, L, True, p, self._seed, site, tp.b_offset, out=out)
         tp.bw.append(bw)
         return o
 
     def _conv(self, name, grad=False):
-        d = self.hidden_units
+        d = self.dp
         return (self.G(name) if grad else self.P(name)).view(d, d)
 
     def _enc_layer(self, tp, p, x, ids, B, st):
         """EncoderLayer.forward (sasrec/modules.py:644-655) -> (seqs, head-classifier log-probabilities)."""
         P, G = self.P, self.G
-        d = self.hidden_units
+        d = self.dp      # the in-projection slices W[:dp] / W[dp:] of the rows as laid out
         Q = tp.layernorm(x, P(p + ".attention_layernorm.weight"), P(p + ".attention_layernorm.bias"), G(p + ".attention_layernorm.weight"),
                          G(p + ".attention_layernorm.bias"), LN_EPS)
         W, b, gW, gb = P(p + ".attention_layer.in_proj_weight"), P(p + ".attention_layer.in_proj_bias"), G(p + ".attention_layer.in_proj_weight"), \
@@ -325,7 +381,7 @@ class SuperSASRecModel(FlatModule):
     def _dec_layer(self, tp, p, x, enc, ids, B, st):
         """DecoderLayer.forward (sasrec/modules.py:666-677)."""
         P, G = self.P, self.G
-        d = self.hidden_units
+        d = self.dp
         D = tp.layernorm(x, P(p + ".layer_norm.weight"), P(p + ".layer_norm.bias"), G(p + ".layer_norm.weight"), G(p + ".layer_norm.bias"), LN_EPS)
         s, e = p + ".slf_attn", p + ".enc_attn"
         qkv = tp.dense(D, P(s + ".in_proj_weight"), P(s + ".in_proj_bias"), G(s + ".in_proj_weight"), G(s + ".in_proj_bias"))
@@ -388,6 +444,10 @@ class SuperSASRecModel(FlatModule):
         Under autograd the tensors are wired into it (adt_amd::model_forward), so the reference's warm-up loop body
         (sasrec/evolution.py:296-316) runs on them unchanged; SuperTrainer.step is the fused way."""
         ids = [self.ids(a) for a in (log_seqs, dec_seqs, pos_seqs, neg_seqs)]
+        if self.lanes is not None and custom_ops.wants_grad(self):
+            raise _lib.AdtError("SuperSASRecModel (adt_amd): autograd through forward() (the reference's warm-up loop body) is not built for "
+                                "padded widths (d=%d H=%d runs as d_pad=%d); train with SuperTrainer or call forward() under torch.no_grad()"
+                                % (self.hidden_units, self.num_heads, self.dp))
         if custom_ops.wants_grad(self):
             outs = custom_ops.forward_with_grad(self, ids)
         else:
@@ -402,14 +462,21 @@ class SuperSASRecModel(FlatModule):
         d, H = self.hidden_units, self.num_heads
         if training:
             self.next_seed()
+        self.push()      # padded widths: the reference-shaped parameters are the truth between steps (no-op otherwise)
         tp = Tape(self, self.prec, training)
         feats, enc_in, recs = self._encode(tp, seq.view(-1), B)
         dec_outs = self._decode(tp, dec.view(-1), feats, B)
         pl, nl = ops.logits_fwd(feats.t, self.P("item_emb.weight"), pos.view(-1), neg.view(-1))
         dec_outs.reverse()
-        outs = [pl.view(B, L), nl.view(B, L)] + [a.t.view(B, L, d) for a in enc_in] + [a.t.view(B, L, d) for a in dec_outs] + \
+        outs = [pl.view(B, L), nl.view(B, L)] + [self._live(a.t, B, L) for a in enc_in] + [self._live(a.t, B, L) for a in dec_outs] + \
                [r.t.view(B, L, H, H) for r in recs]
         return outs, {"tp": tp, "feats": feats, "acts": list(enc_in) + list(dec_outs) + list(recs), "pos": pos, "neg": neg}
+
+    def _live(self, t, B, L):
+        """(B * L, dp) activation as the reference's (B, L, d): the live lanes of a padded width (a copy, outside the training step)."""
+        if self.lanes is None:
+            return t.view(B, L, self.dp)
+        return t.view(B, L, self.num_heads, self.hd_pad)[..., :self.hd].reshape(B, L, self.hidden_units)
 
     def _op_backward(self, st, grads):
         tp, feats, pos, neg = st["tp"], st["feats"], st["pos"].view(-1), st["neg"].view(-1)
@@ -428,10 +495,11 @@ class SuperSASRecModel(FlatModule):
         B, L = seq.shape
         was = self.training
         self.eval()
+        self.push()
         tp = Tape(self, self.prec, False)
         feats, _, _ = self._encode(tp, seq.view(-1), B)
         self.train(was)
-        d = self.hidden_units
+        d = self.dp      # the row stride of the features as laid out
         cand = None if full else self.ids(item_indices)
         C = self.itemnum + 1 if full else cand.shape[1]
         logits, rank = ops.score_rank(feats.t[L - 1:], L * d, self.P("item_emb.weight"), cand, B, C, want_rank)
@@ -446,6 +514,7 @@ class SuperSASRecModel(FlatModule):
         B, L = seq.shape
         was = self.training
         self.eval()
+        self.push()      # padded widths: the reference-shaped parameters are the truth between steps (no-op otherwise)
         tp = Tape(self, self.prec, False)
         flat = seq.view(-1)
         x0 = self._embed(tp, flat, SITE_EMB_SEQ)
@@ -475,7 +544,7 @@ class SuperSASRecModel(FlatModule):
     def predict_rank_candidates(self, log_seqs, item_indices, shared_list, stats=None):
         """Ranks of the positive (column 0) under every block choice of `shared_list` in one pass (_candidate_feature_rows): (P, B)."""
         F, B, L = self._candidate_feature_rows(log_seqs, shared_list, stats)
-        P, d = len(shared_list), self.hidden_units
+        P, d = len(shared_list), self.dp
         full = item_indices is None
         cand = None if full else self.ids(item_indices)
         C = self.itemnum + 1 if full else cand.shape[1]
@@ -490,7 +559,7 @@ class SuperSASRecModel(FlatModule):
         with rows_per_group = B, so the (B, C) device int32 `cand` is read by every group and not repeated, and the ranks are counted
         into hist (P, C) int64 (accumulated; returned) instead of being read back."""
         F, B, L = self._candidate_feature_rows(log_seqs, shared_list, stats)
-        return ops.cand_rank_hist(F[L - 1:], L * self.hidden_units, self.P("item_emb.weight"), cand, len(shared_list) * B, B, hist=hist)
+        return ops.cand_rank_hist(F[L - 1:], L * self.dp, self.P("item_emb.weight"), cand, len(shared_list) * B, B, hist=hist)
 
     def predict_rank(self, log_seqs, item_indices, want_rank=True):
         """(scores, rank of column 0) -- the interface adt_amd.sasrec.utils.evaluate_loader drives."""

@@ -88,14 +88,14 @@ def param_table(item_size, maxlen, d, H, nl, num_users, block=0, dec_layernorm=T
     return t, n_trained
 
 
-def padded_tables(item_size, maxlen, d, H, nl, num_users, dec_layernorm=True):
+def padded_tables(item_size, maxlen, d, H, nl, num_users, dec_layernorm=True, block=0):
     """(ref_table, padded table, prefix, n_trained as param_table's) of a width the kernels do not tile (wide.padded_layout): every d becomes
     d_pad (channel h * hd + j at h * hd_pad + j), the head classifiers' (H, hd) become (H, hd_pad), and the 4d of the intermediates becomes
     4 * d_pad with the 4d live channels as a zero-tailed PREFIX (element j stays at j; wide.lane_index's `prefix`): ELU(0) = 0, so the tail
     of the inner activation is zero, and (4 d_pad, d_pad) / (d_pad, 4 d_pad) are the shapes the dense arms run at width d_pad today.
-    Pure arithmetic: no GPU, no library."""
+    block > 0: the supernet's tables (param_table's `block`) under the same rules.  Pure arithmetic: no GPU, no library."""
     hd, hd_pad, dp = padded_layout(d, H)
-    ref, n_trained = param_table(item_size, maxlen, d, H, nl, num_users, 0, dec_layernorm)
+    ref, n_trained = param_table(item_size, maxlen, d, H, nl, num_users, block, dec_layernorm)
     pad, prefix = [], set()
     for name, shape in ref:
         if name.endswith("_independence_layer.weight"):
@@ -121,10 +121,11 @@ def padded_tables(item_size, maxlen, d, H, nl, num_users, dec_layernorm=True):
 
 
 class DisenDistSAModel(DistRankMixin, FlatModule):
-    def __init__(self, args, block=0, dec_layernorm=True, allow_kl_lanes=False, allow_wide_heads=False):
+    def __init__(self, args, block=0, dec_layernorm=True, allow_kl_lanes=False, allow_wide_heads=False, allow_block_lanes=False):
         """allow_kl_lanes: take distance_metric='kl' at a padded width; without it that pair raises, as it always has.
         allow_wide_heads: take a head that pads to 128 lanes (128 / 1, 256 / 2, 100 / 1, 200 / 2); without it such a
-        width raises, as it always has."""
+        width raises, as it always has.  allow_block_lanes: the supernet's layout (block > 0) at a padded width or with heads of 128 lanes
+        (DisenDistSASupernet(allow_lanes=True)); without it that pair raises, as it always has."""
         super().__init__()
         self.args = args
         self.item_size, self.maxlen, self.hidden_units = args.item_size, args.maxlen, args.hidden_units
@@ -148,7 +149,7 @@ class DisenDistSAModel(DistRankMixin, FlatModule):
                 raise _lib.AdtError("DisenDistSAModel (adt_amd): d=%d H=%d has head size %d, which pads to %d lanes; the distance attention is "
                                     "built for head sizes up to 64, and head size 128 is opt-in: pass allow_wide_heads=True to DisenDistSAModel "
                                     "(stosa/main.py does)" % (d, H, self.hd, self.hd_pad))
-            if block:
+            if block and not allow_block_lanes:
                 raise _lib.AdtError("DisenDistSASupernet (adt_amd): the supernet is built for hidden_units a multiple of 64 with head size "
                                     "16/32/64 only (padded widths run on DisenDistSAModel), got d=%d H=%d" % (d, H))
         # dp == d: the kernels tile the width as it is.  Otherwise activations and parameters are padded to dp columns (head h at
@@ -192,7 +193,7 @@ class DisenDistSAModel(DistRankMixin, FlatModule):
             dist_bpr, dist_full = (ops.kldist_bpr_lanes, ops.kldist_full_lanes) if kl else (ops.wdist_bpr_lanes, ops.wdist_full_lanes)
             self._dist_bpr = lambda *a: dist_bpr(*a, ln)
             self._dist_full = lambda *a: dist_full(*a, ln)
-            ref_table, table, prefix, n_trained = padded_tables(args.item_size, args.maxlen, d, H, args.num_layers, args.num_users, dec_layernorm)
+            ref_table, table, prefix, n_trained = padded_tables(args.item_size, args.maxlen, d, H, args.num_layers, args.num_users, dec_layernorm, block)
             self._build_flat(table, getattr(args, "device", "cuda:0"), REF_ORDER, ref_table=ref_table, width=(d, H), prefix=prefix)
         self.n_trained_floats = self._views[table[n_trained][0]][0]     # optimizer prefix (flat floats)
         # init_weights (stosa/models.py:262-272): N(0.01, initializer_range) on Linear/Embedding weights, LayerNorm 1/0, biases 0

@@ -33,7 +33,7 @@ class SearcherEvolution:
         self.rec_choice = [0, 0.0001, 0.0005, 0.001, 0.005, 0.01]
         self.ind_choice = [0, 0.0001, 0.0005, 0.001, 0.005, 0.01]
         torch.manual_seed(args.seed)
-        self.model = DisenDistSASupernet(args, self.rec_choice, self.ind_choice, allow_kl=True)      # args.distance_metric: 'wasserstein' or 'kl'
+        self.model = DisenDistSASupernet(args, self.rec_choice, self.ind_choice, allow_kl=True, allow_lanes=True)      # 'wasserstein' or 'kl', any width main.py takes
         self.trainer = SuperStosaTrainer(self.model, lr=args.lr, betas=(args.adam_beta1, args.adam_beta2), weight_decay=args.weight_decay,
                                          seed=args.seed)
         self.search_state = EvolutionSearch(args.num_layers, self._evaluate_for_search, "MRR", args.select_num, args.population_num, args.m_prob,

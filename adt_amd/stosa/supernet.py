@@ -29,16 +29,21 @@ def _cand_sites(sites, k):
 
 
 class DisenDistSASupernet(DisenDistSAModel):
-    def __init__(self, args, rec_choice, ind_choice, allow_kl=False):
+    def __init__(self, args, rec_choice, ind_choice, allow_kl=False, allow_lanes=False):
         """allow_kl: distance_metric='kl' is opt-in (SearcherEvolution passes True).  Without it the constructor refuses anything but
         'wasserstein', as it always has; with it 'kl' runs the KL attention, the KL warm-up loss and the grouped KL full sort (DESIGN.md
-        section 19), and any other string still raises in the base class."""
+        section 19), and any other string still raises in the base class.
+        allow_lanes: every (hidden_units, num_heads) DisenDistSAModel takes with allow_kl_lanes=True and allow_wide_heads=True is opt-in too
+        (SearcherEvolution passes True): padded widths (50 / 1, 100 / 2) and heads of 128 lanes (128 / 1, 100 / 1).
+        Without it such a shape raises, as it always has; a shape the kernels tile runs the same code with or without it."""
         if getattr(args, "distance_metric", "wasserstein") != "wasserstein" and not allow_kl:
             raise _lib.AdtError("DisenDistSASupernet (adt_amd): only distance_metric='wasserstein' is built for the supernet unless allow_kl=True "
                                 "is passed, got %r" % (args.distance_metric,))
         self.rec_choice, self.ind_choice = np.asarray(rec_choice, np.float64), np.asarray(ind_choice, np.float64)
         self.block = len(self.rec_choice) * len(self.ind_choice)
-        super().__init__(args, block=self.block, dec_layernorm=False)     # init_weights is the plain model's (supernet.py:101-111)
+        lanes = bool(allow_lanes)
+        super().__init__(args, block=self.block, dec_layernorm=False, allow_kl_lanes=lanes, allow_wide_heads=lanes,
+                         allow_block_lanes=lanes)                         # init_weights is the plain model's (supernet.py:101-111)
         self.shared = [((0, 0, 0, 0), (0.0, 0.0, 0.0, 0.0)) for _ in range(self.num_layers)]
 
     def set_choice(self, cand):
@@ -95,6 +100,7 @@ class DisenDistSASupernet(DisenDistSAModel):
         B, L = inp.shape
         was = self.training
         self.eval()
+        self.push()      # padded widths: the reference-shaped parameters are the truth between steps (no-op otherwise)
         tp = Tape(self, self.prec, False)
         flat = inp.view(-1)
         m0, c0 = self._embed(tp, flat, "mean", SITE_EMB["seq_mean"]), self._embed(tp, flat, "cov", SITE_EMB["seq_cov"])
@@ -115,8 +121,11 @@ class DisenDistSASupernet(DisenDistSAModel):
     def kl_item_image(self):
         """(img (item_size, 2d), lv (item_size,)) of the two item tables for the grouped KL full sort (ops.kldist_pack).  Packed on every
         call, like item_image(): no cache, it is stale after any weight update; a caller that scores many passes under the same weights
-        holds on to it and passes it as `image`."""
-        return ops.kldist_pack(self.P("item_mean_embeddings.weight"), self.P("item_cov_embeddings.weight"))
+        holds on to it and passes it as `image`.  At a padded width: ops.kldist_pack_lanes of the padded tables, (item_size, 2 d_pad) with
+        +0.0 on the pad lanes of both halves."""
+        self.push()
+        Em, Ec = self.P("item_mean_embeddings.weight"), self.P("item_cov_embeddings.weight")
+        return ops.kldist_pack(Em, Ec) if self.lanes is None else ops.kldist_pack_lanes(Em, Ec, self.lanes)
 
     @torch.no_grad()
     def predict_full_candidates(self, input_ids, shared_list, stats=None, image=None):
@@ -125,10 +134,15 @@ class DisenDistSASupernet(DisenDistSAModel):
         candidate with the B rows of this call as the eval batch (adt_kldist_full_groups with E = B: the chunking never pairs rows of two
         candidates); image: kl_item_image() of the current weights, packed here when None.  The Wasserstein path takes no image."""
         sm, sc = self._last_state_candidates(input_ids, shared_list, stats)
+        ln = self.lanes      # a padded width: the lane-aware twins, scores over the live lanes at the true d (DESIGN.md section 30)
         if self.distance_metric == "kl":
             img, lv = self.kl_item_image() if image is None else image
-            return ops.kldist_full_groups(sm, sc, img, lv, sm.shape[0] // len(shared_list), self.item_size)
-        return ops.wdist_full(sm, sc, self.P("item_mean_embeddings.weight"), self.P("item_cov_embeddings.weight"), self.item_size)
+            E = sm.shape[0] // len(shared_list)
+            if ln is not None:
+                return ops.kldist_full_groups_lanes(sm, sc, img, lv, E, self.item_size, ln)
+            return ops.kldist_full_groups(sm, sc, img, lv, E, self.item_size)
+        Em, Ec = self.P("item_mean_embeddings.weight"), self.P("item_cov_embeddings.weight")
+        return ops.wdist_full(sm, sc, Em, Ec, self.item_size) if ln is None else ops.wdist_full_lanes(sm, sc, Em, Ec, self.item_size, ln)
 
     @torch.no_grad()
     def rank_full_candidates(self, input_ids, shared_list, targets=None, seen=None, topk=0, image=None, stats=None, first_id=1, rowwise=False):

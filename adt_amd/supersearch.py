@@ -121,13 +121,18 @@ class SupernetTrainer:
         m.advance_seed()
         self.loss_slots.zero_()
         m.flat_grad.zero_()
+        ranges = self._ranges()
+        # padded widths: the reference-shaped parameters are the truth between steps; only the ranges this step
+        # trains are copied in and out (the candidate layers are contiguous in both layouts).  No-ops without padding.
+        m.push_ranges(ranges)
         m.loss_forward_backward(staged, self.rec_weights, self._ind_lambdas(), norms, self.loss_slots)
         ops.grad_sumsq(m.flat_grad, self.gn2)
-        for lo, hi in self._ranges():
+        for lo, hi in ranges:
             t = self.steps.get((lo, hi), 0) + 1
             self.steps[(lo, hi)] = t
             self._adam_range(m.flat[lo:hi], m.flat_grad[lo:hi], self.m[lo:hi], self.v[lo:hi], self.wd, self.clip, self.lr, self.betas[0],
                              self.betas[1], self.eps, t, self.gn2)
+        m.pull_ranges(ranges)
 
     def loss(self):
         return (self.loss_slots.sum(1) * torch.tensor(self._loss_w(), device=self.model.dev, dtype=torch.float32)).sum()

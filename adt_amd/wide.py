@@ -129,6 +129,7 @@ class FlatModule(torch.nn.Module):
             assert [n for n, _ in ref_table] == names
             index = lane_index(ref_table, self.table, {n: v[0] for n, v in self._views.items()}, *width, prefix=prefix)
             self.lane_idx = torch.from_numpy(index).to(self.dev)
+            self._lane_host = index      # ascending (the two tables list the same tensors in the same order): ref_range() searches it
             self.ref_flat = torch.zeros(index.size, device=self.dev, dtype=torch.float32)
             self._ref_views, o = {}, 0
             for name, shape in ref_table:
@@ -188,6 +189,27 @@ class FlatModule(torch.nn.Module):
         """Live lanes of the padded flat buffer -> reference-shaped parameters (no-op without padding)."""
         if self.ref_flat is not None:
             ops.lane_map(self.flat, self.ref_flat, self.lane_idx, False)
+
+    def ref_range(self, lo, hi):
+        """[lo, hi) of the padded flat buffer as the range of ref_flat whose elements live there.  lane_idx ascends, so a range that holds
+        whole tensors of the padded table holds a contiguous run of the reference-shaped ones.  Kept per range: a supernet has a few dozen,
+        and numpy converts the whole int32 index for every search with an int key -- milliseconds of host time per range and step."""
+        cache = self.__dict__.setdefault("_ref_ranges", {})
+        if (lo, hi) not in cache:
+            idx = self._lane_host
+            cache[(lo, hi)] = tuple(int(np.searchsorted(idx, idx.dtype.type(min(x, np.iinfo(idx.dtype).max)))) for x in (lo, hi))
+        return cache[(lo, hi)]
+
+    def push_ranges(self, ranges):
+        """push() of the flat ranges [(lo, hi)] only (a supernet step trains a few of its candidate layers)."""
+        if self.ref_flat is not None:
+            for r0, r1 in (self.ref_range(lo, hi) for lo, hi in ranges):
+                ops.lane_map(self.flat, self.ref_flat[r0:r1], self.lane_idx[r0:r1], True)
+
+    def pull_ranges(self, ranges):
+        if self.ref_flat is not None:
+            for r0, r1 in (self.ref_range(lo, hi) for lo, hi in ranges):
+                ops.lane_map(self.flat, self.ref_flat[r0:r1], self.lane_idx[r0:r1], False)
 
     def compact(self, padded):
         """The live lanes of a buffer laid out like `flat` (an Adam moment), packed like ref_flat."""

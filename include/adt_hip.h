@@ -371,6 +371,16 @@ int adt_klrow_pack(const float* M, const float* C, int ld, int rows, int d, int 
  * V + 2E + 32 >= 2^31.  rows * V may exceed 2^31: dist is indexed in size_t. */
 int adt_kldist_full_groups(const float* Sm, const float* Sc, int lds, const float* img, int ldi, const float* lv, int rows, int E, int V,
                            int d, float* dist, int ldo, void* stream);
+/* The two calls above on padded rows (adt_kldist_groups_lanes.cuh): d = H * hd_pad columns, head h at
+ * [h * hd_pad, h * hd_pad + hd), hd_pad a power of two in 16..256, d one of 64 / 128 / 192 / 256.  The score is the one above at the true
+ * width H * hd: every sum runs over the live lanes, the subtracted dimension is H * hd, and no pad lane reaches a logf or a divide.
+ * adt_kldist_pack_lanes writes +0.0 on the pad lanes of both halves of the image; adt_kldist_full_groups_lanes takes that image and state
+ * rows whose pad lanes are finite (the models keep them +0.0).  The same errors as above, and d != H * hd_pad or a (H, hd, hd_pad) that is
+ * no such layout.  hd == hd_pad is the tiled function. */
+int adt_kldist_pack_lanes(const float* Em, const float* Ec, int ld, int V, int d, int H, int hd, int hd_pad, float* img, int ldi, float* lv,
+                          void* stream);
+int adt_kldist_full_groups_lanes(const float* Sm, const float* Sc, int lds, const float* img, int ldi, const float* lv, int rows, int E, int V,
+                                 int d, int H, int hd, int hd_pad, float* dist, int ldo, void* stream);
 
 /* ---- STOSA-ADT batches built on the device (adt_seqbatch.cuh; stosa/datasets.py:202-300, utils.py:32-36 neg_sample) -----------------
  * Resident inputs: the user sequences as CSR (seq_off int64 (U + 1), seq_items int32, ids >= 1) and every user's sorted, de-duplicated

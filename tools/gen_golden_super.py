@@ -4,7 +4,7 @@ super_modules.py, base_super_modules.py) in the build container.  Fixtures are d
 SearcherEvolution._train_warmup (sasrec/evolution.py:286-316) driven with the same torch calls (evolution.py itself needs
 `jsonlines` and the dataset files, so the class cannot be constructed here); dropout is 0.
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_super.py
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_super.py [d64] [wide] [lanes]
 """
 import os
 import sys
@@ -120,3 +120,9 @@ if __name__ == "__main__":
         gen("d256h1", 40, 50, 256, 1, 2, [0, 0.001, 0.01], [0, 0.0005, 0.002], B=2, seed=33, cand=[0.7, 0.2, 0.4, 0.9], wide=True)
         gen("d256h2", 40, 200, 256, 2, 1, [0, 0.001, 0.01], [0, 0.0005, 0.002], B=2, seed=34, cand=[0.3, 0.6], wide=True)
         gen("d128h1", 40, 64, 128, 1, 1, [0, 0.001, 0.01], [0, 0.0005, 0.002], B=3, seed=35, cand=[0.8, 0.1], wide=True)
+    if "lanes" in which:
+        # widths the kernels pad (the CLI default 50 / 1; two heads of 50 in 64 lanes) and a tiled width past the
+        # resident attention's length (64 / 2 at L 272: the streamed kernels)
+        gen("w50h1", 30, 12, 50, 1, 1, [0, 0.001, 0.01], [0, 0.0005, 0.002], B=3, seed=36, cand=[0.7, 0.2], wide=True)
+        gen("w100h2", 25, 10, 100, 2, 2, [0, 0.01], [0, 0.002], B=2, seed=37, cand=[0.3, 0.9, 0.6, 0.4], wide=True)
+        gen("l272", 30, 272, 64, 2, 1, [0, 0.01], [0, 0.002], B=2, seed=38, cand=[0.4, 0.7], wide=True)

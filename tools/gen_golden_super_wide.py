@@ -6,7 +6,7 @@ super_modules.py) in the build container.  Fixtures are data only: seeded inputs
 (bert4rec/evolution.py:266-296; stosa/super_trainer.py:205-235 with bpr_optimization :30-62) driven with the same torch calls;
 dropout is 0.
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_super_wide.py [bert] [stosa] [stosa_kl]
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden_super_wide.py [bert] [stosa] [stosa_kl] [lanes]
 """
 import os
 import sys
@@ -206,3 +206,12 @@ if __name__ == "__main__":
     if "stosa_kl" in which:      # the same shapes and seeds; B divides neither item_size
         gen_stosa("c3", 42, 12, 64, 4, 1, [0, 0.001, 0.01], [0, 0.001, 0.01], B=3, seed=51, cand=[0.7, 0.2], metric="kl")
         gen_stosa("l2", 33, 10, 64, 2, 2, [0, 0.01], [0, 0.01], B=2, seed=52, cand=[0.3, 0.9, 0.6, 0.4], metric="kl")
+    if "lanes" in which:
+        # the widths the kernels pad (50 / 1, 100 / 2) and a head of 128 lanes (100 / 1: the reference's covariance
+        # product under 'kl' survives at d 100 and is NaN at d 128), every supernet, both STOSA metrics
+        gen_bert("w50h1", 30, 12, 50, 1, 1, [0, 0.001, 0.01], [0, 0.0005, 0.002], B=3, seed=43, cand=[0.7, 0.2])
+        gen_bert("w100h2", 25, 10, 100, 2, 1, [0, 0.01], [0, 0.002], B=2, seed=44, cand=[0.3, 0.9])      # one layer: under 300 KB
+        for metric in ("wasserstein", "kl"):
+            gen_stosa("w50h1", 42, 12, 50, 1, 1, [0, 0.001, 0.01], [0, 0.001, 0.01], B=3, seed=53, cand=[0.7, 0.2], metric=metric)
+            gen_stosa("w100h2", 33, 10, 100, 2, 1, [0, 0.01], [0, 0.01], B=2, seed=54, cand=[0.3, 0.9], metric=metric)      # one layer: under 300 KB
+            gen_stosa("w100h1", 33, 10, 100, 1, 1, [0, 0.01], [0, 0.01], B=2, seed=55, cand=[0.6, 0.3], metric=metric)
