@@ -173,6 +173,8 @@ SIGNATURES = {
     "adt_full_rank_ws_bytes": (_L, [_I, _I, _I, _I]),
     "adt_full_rank": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P]),
     "adt_full_rank_from": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P]),
+    "adt_full_rank_groups": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P]),
+    "adt_full_rank_stats": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "adt_wdist_pack": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _F, _P]),
     "adt_kldist_pack": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
     "adt_klrow_pack": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P]),

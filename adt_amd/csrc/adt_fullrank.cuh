@@ -14,8 +14,14 @@
 // the same fixed order (MFMA j of a 32-column block contracts columns j, 8 + j, 16 + j, 24 + j), whatever the item's place in a tile.
 // No atomics touch a result: counts are ballots, a top-K list is the K best of a SET under the total order (score descending, id
 // ascending), so neither the chunking nor S can change an output bit.
+//
+// The group-aware form (k_full_rank<true>, k_full_rank_merge<true>) ranks P stacked candidates of the same R
+// users in one launch: feature row r belongs to user row0 + r % R of a resident CSR with int64 offsets, whose target and seen list it
+// reads.  The seen bitmap and the target are per row already, so a 16-row tile may straddle a group boundary; only the three reads
+// that name the user change.  It is a template flag: the <false> instantiations compile to the code the plain kernels had.
 #pragma once
 #include "adt_common.cuh"
+#include <type_traits>
 
 namespace adt {
 
@@ -38,6 +44,10 @@ struct FullRankArgs {
   int32_t* ws_cnt; float* ws_val; int32_t* ws_idx;      // (B, S, 2) {rank count, eligible count}, (B, S, K), (B, S, K)
   int32_t* rank; int32_t* n_elig; int32_t* top_idx; float* top_val;
 };
+
+// the group-aware form's argument block: rows per group, the first CSR row, the CSR's int64 offsets (indptr is unused, indices its items)
+struct FullRankGroupArgs : FullRankArgs { int R, row0; const int64_t* off; };
+template <bool GROUPS> using FrArgs = std::conditional_t<GROUPS, FullRankGroupArgs, FullRankArgs>;
 
 static inline size_t full_rank_lds_bytes(int d) {
   const int d32 = (d + 31) & ~31;
@@ -176,7 +186,8 @@ ADT_DEVICE_INLINE void fr_run(const FullRankArgs& a, const FrCtx& x, int lo, int
   }
 }
 
-__global__ __launch_bounds__(FR_NTH) void k_full_rank(FullRankArgs a) {
+template <bool GROUPS>
+__global__ __launch_bounds__(FR_NTH) void k_full_rank(FrArgs<GROUPS> a) {
   extern __shared__ __attribute__((aligned(16))) float fr_lds[];
   FrCtx x;
   x.tid = threadIdx.x; x.lane = x.tid & 63; x.w = x.tid >> 6;
@@ -198,8 +209,13 @@ __global__ __launch_bounds__(FR_NTH) void k_full_rank(FullRankArgs a) {
     if (x.b0 + row < a.B && c4 < a.d) v = *reinterpret_cast<const float4*>(a.F + (size_t)(x.b0 + row) * a.ldf + c4);
     *reinterpret_cast<float4*>(x.Fi + row * x.frs + c4) = v;
   }
+  // the row of target / the seen CSR that feature row b reads: b itself, or user row0 + b % R
+  const auto user = [&](int b) {
+    if constexpr (GROUPS) return a.row0 + b % a.R;
+    else return b;
+  };
   if (x.tid < 16) {
-    int t = (a.target && x.b0 + x.tid < a.B) ? a.target[x.b0 + x.tid] : 0;
+    int t = (a.target && x.b0 + x.tid < a.B) ? a.target[user(x.b0 + x.tid)] : 0;
     if (t < 1 || t > a.n_items) t = 0;
     x.tgt[x.tid] = t;
     x.tsc[x.tid] = 0.f;
@@ -217,12 +233,16 @@ __global__ __launch_bounds__(FR_NTH) void k_full_rank(FullRankArgs a) {
     // seen bitmap of items [sc_lo, sc_hi): out-of-range ids and duplicates fall away, the target stays eligible
     for (int i = x.tid; i < 16 * FR_BMW; i += FR_NTH) x.bm[i] = 0u;
     __syncthreads();
-    if (a.indptr) {
+    using Off = std::conditional_t<GROUPS, int64_t, int>;      // the offsets' own type: int64 in the resident CSR
+    const Off* off;
+    if constexpr (GROUPS) off = a.off; else off = a.indptr;
+    if (off) {
       for (int row = x.w; row < 16; row += FR_NW) {
         const int b = x.b0 + row;
         if (b >= a.B) break;
-        const int t = x.tgt[row] ? x.tgt[row] : -1, j1 = a.indptr[b + 1];
-        for (int j = a.indptr[b] + x.lane; j < j1; j += 64) {
+        const int u = user(b), t = x.tgt[row] ? x.tgt[row] : -1;
+        const Off j1 = off[u + 1];
+        for (Off j = off[u] + x.lane; j < j1; j += 64) {
           const int id = a.indices[j];
           if (id >= a.first_id && id >= sc_lo && id < sc_hi && id != t) atomicOr(&x.bm[row * FR_BMW + ((id - sc_lo) >> 5)], 1u << ((id - sc_lo) & 31));
         }
@@ -244,7 +264,8 @@ __global__ __launch_bounds__(FR_NTH) void k_full_rank(FullRankArgs a) {
   });
 }
 
-__global__ __launch_bounds__(FR_NTH) void k_full_rank_merge(FullRankArgs a) {
+template <bool GROUPS>
+__global__ __launch_bounds__(FR_NTH) void k_full_rank_merge(FrArgs<GROUPS> a) {
   const int lane = threadIdx.x & 63, b = blockIdx.x * FR_NW + (threadIdx.x >> 6);
   if (b >= a.B) return;
   int cnt = 0, ne = 0;
@@ -258,7 +279,9 @@ __global__ __launch_bounds__(FR_NTH) void k_full_rank_merge(FullRankArgs a) {
     ne += __shfl_xor(ne, o, 64);
   }
   if (lane == 0) {
-    const int t = a.target ? a.target[b] : 0;
+    int u = b;
+    if constexpr (GROUPS) u = a.row0 + b % a.R;
+    const int t = a.target ? a.target[u] : 0;
     a.rank[b] = (t >= 1 && t <= a.n_items) ? cnt : -1;
     a.n_elig[b] = ne;
   }

@@ -3,6 +3,7 @@
 #include "adt_host.h"
 
 #include "adt_fullrank.cuh"
+#include "adt_fullstats.cuh"
 #include "adt_wdist_pack.cuh"
 #include "adt_kldist_groups.cuh"
 #include "adt_klrow_pack.cuh"
@@ -40,34 +41,85 @@ int64_t adt_full_rank_ws_bytes(int B, int n_items, int K, int splits) {
   return fr_ws_bytes(B, S, K);
 }
 
-int adt_full_rank_from(const float* F, int ldf, const float* E, int lde, const float* bias, int B, int d, int n_items, int first_id,
-                       const int32_t* target, const int32_t* indptr, const int32_t* indices, int K, int splits, void* ws, int64_t ws_bytes,
-                       int32_t* rank, int32_t* n_elig, int32_t* top_idx, float* top_val, void* stream) {
-  if (first_id != 0 && first_id != 1) return adt_set_error("full_rank: first_id=%d must be 0 or 1", first_id);
-  if (K < 0 || K > FR_KMAX) return adt_set_error("full_rank: K=%d outside 0..%d", K, FR_KMAX);
-  if (d < 4 || (d % 4)) return adt_set_error("full_rank: d=%d must be a positive multiple of 4", d);
-  if (lde < d || ldf < d) return adt_set_error("full_rank: lde=%d, ldf=%d must be >= d=%d", lde, ldf, d);
-  if (n_items < 1) return adt_set_error("full_rank: n_items=%d < 1", n_items);
-  if ((lde % 4) || (ldf % 4) || !adt_aligned16(F) || !adt_aligned16(E)) return adt_set_error("full_rank: F and E must be 16-byte aligned with ld %% 4 == 0");
-  if ((indptr == nullptr) != (indices == nullptr)) return adt_set_error("full_rank: indptr and indices go together");
-  if (splits < 0 || splits > 1024) return adt_set_error("full_rank: splits=%d outside 0..1024", splits);
-  if (B <= 0) return 0;
-  if (!rank || !n_elig || (K > 0 && (!top_idx || !top_val))) return adt_set_error("full_rank: missing output");
+// What every entry point asks of its arguments, then the plan and the argument block.  `what` names the entry point in the messages;
+// seen_ptr is its CSR offsets (int32 indptr or int64 seen_off).  1: nothing to do (B <= 0), 0: *a and *smem are ready, -1: an error.
+static int fr_prepare(const char* what, const float* F, int ldf, const float* E, int lde, const float* bias, int B, int d, int n_items, int first_id,
+                      const int32_t* target, const void* seen_ptr, const int32_t* indices, int K, int splits, void* ws, int64_t ws_bytes, int32_t* rank,
+                      int32_t* n_elig, int32_t* top_idx, float* top_val, FullRankArgs* out, size_t* smem_out) {
+  if (first_id != 0 && first_id != 1) return adt_set_error("%s: first_id=%d must be 0 or 1", what, first_id);
+  if (K < 0 || K > FR_KMAX) return adt_set_error("%s: K=%d outside 0..%d", what, K, FR_KMAX);
+  if (d < 4 || (d % 4)) return adt_set_error("%s: d=%d must be a positive multiple of 4", what, d);
+  if (lde < d || ldf < d) return adt_set_error("%s: lde=%d, ldf=%d must be >= d=%d", what, lde, ldf, d);
+  if (n_items < 1) return adt_set_error("%s: n_items=%d < 1", what, n_items);
+  if ((lde % 4) || (ldf % 4) || !adt_aligned16(F) || !adt_aligned16(E)) return adt_set_error("%s: F and E must be 16-byte aligned with ld %% 4 == 0", what);
+  if ((seen_ptr == nullptr) != (indices == nullptr)) return adt_set_error("%s: indptr and indices go together", what);
+  if (splits < 0 || splits > 1024) return adt_set_error("%s: splits=%d outside 0..1024", what, splits);
+  if (B <= 0) return 1;
+  if (!rank || !n_elig || (K > 0 && (!top_idx || !top_val))) return adt_set_error("%s: missing output", what);
   const size_t smem = full_rank_lds_bytes(d);
-  if (smem > ADT_LDS_MAX) return adt_set_error("full_rank: d=%d needs %zu B of LDS (> 160 KB)", d, smem);
+  if (smem > ADT_LDS_MAX) return adt_set_error("%s: d=%d needs %zu B of LDS (> 160 KB)", what, d, smem);
   FullRankArgs a{};
   fr_plan(B, n_items, splits, &a.S, &a.per);
-  if (!ws || ws_bytes < fr_ws_bytes(B, a.S, K)) return adt_set_error("full_rank: workspace of %lld B, need %lld (adt_full_rank_ws_bytes)", (long long)ws_bytes, (long long)fr_ws_bytes(B, a.S, K));
+  if (!ws || ws_bytes < fr_ws_bytes(B, a.S, K))
+    return adt_set_error("%s: workspace of %lld B, need %lld (adt_full_rank_ws_bytes)", what, (long long)ws_bytes, (long long)fr_ws_bytes(B, a.S, K));
   a.F = F; a.ldf = ldf; a.E = E; a.lde = lde; a.bias = bias; a.B = B; a.d = d; a.n_items = n_items; a.first_id = first_id;
-  a.target = target; a.indptr = indptr; a.indices = indices; a.K = K;
+  a.target = target; a.indices = indices; a.K = K;
   a.ws_cnt = static_cast<int32_t*>(ws);
   a.ws_val = reinterpret_cast<float*>(a.ws_cnt + (size_t)B * a.S * 2);
   a.ws_idx = reinterpret_cast<int32_t*>(a.ws_val + (size_t)B * a.S * K);
   a.rank = rank; a.n_elig = n_elig; a.top_idx = top_idx; a.top_val = top_val;
+  *out = a;
+  *smem_out = smem;
+  return 0;
+}
+
+int adt_full_rank_from(const float* F, int ldf, const float* E, int lde, const float* bias, int B, int d, int n_items, int first_id,
+                       const int32_t* target, const int32_t* indptr, const int32_t* indices, int K, int splits, void* ws, int64_t ws_bytes,
+                       int32_t* rank, int32_t* n_elig, int32_t* top_idx, float* top_val, void* stream) {
+  FullRankArgs a;
+  size_t smem;
+  const int st = fr_prepare("full_rank", F, ldf, E, lde, bias, B, d, n_items, first_id, target, indptr, indices, K, splits, ws, ws_bytes, rank, n_elig,
+                            top_idx, top_val, &a, &smem);
+  if (st) return st < 0 ? -1 : 0;
+  a.indptr = indptr;
   static AdtLdsOptIn optin;      // smem follows d: the high-water mark in optin follows it
-  if (adt_launch_lds1((const void*)k_full_rank, dim3((B + 15) / 16, a.S), dim3(FR_NTH), smem, a, (hipStream_t)stream, "full_rank", optin)) return -1;
-  hipLaunchKernelGGL(k_full_rank_merge, dim3((B + FR_NW - 1) / FR_NW), dim3(FR_NTH), 0, (hipStream_t)stream, a);
+  if (adt_launch_lds1((const void*)k_full_rank<false>, dim3((B + 15) / 16, a.S), dim3(FR_NTH), smem, a, (hipStream_t)stream, "full_rank", optin)) return -1;
+  hipLaunchKernelGGL(k_full_rank_merge<false>, dim3((B + FR_NW - 1) / FR_NW), dim3(FR_NTH), 0, (hipStream_t)stream, a);
   return adt_check_launch("full_rank(merge)");
+}
+
+int adt_full_rank_groups(const float* F, int ldf, const float* E, int lde, const float* bias, int n_rows, int rows_per_group, int d, int n_items,
+                         int first_id, const int32_t* target, const int64_t* seen_off, const int32_t* seen_items, int n_total, int row0, int K,
+                         int splits, void* ws, int64_t ws_bytes, int32_t* rank, int32_t* n_elig, int32_t* top_idx, float* top_val, void* stream) {
+  const int R = rows_per_group;
+  if (R < 1) return adt_set_error("full_rank_groups: rows_per_group=%d < 1", R);
+  if (n_rows < 0 || n_rows % R != 0) return adt_set_error("full_rank_groups: n_rows=%d is not a multiple of rows_per_group=%d", n_rows, R);
+  if (row0 < 0 || (int64_t)row0 + R > (int64_t)n_total)
+    return adt_set_error("full_rank_groups: rows %d .. %d + %d lie outside the %d rows of the seen lists", row0, row0, R, n_total);
+  FullRankGroupArgs a;
+  size_t smem;
+  const int st = fr_prepare("full_rank_groups", F, ldf, E, lde, bias, n_rows, d, n_items, first_id, target, seen_off, seen_items, K, splits, ws, ws_bytes,
+                            rank, n_elig, top_idx, top_val, &a, &smem);
+  if (st) return st < 0 ? -1 : 0;
+  a.R = R; a.row0 = row0; a.off = seen_off;
+  static AdtLdsOptIn optin;      // smem follows d: the high-water mark in optin follows it
+  if (adt_launch_lds1((const void*)k_full_rank<true>, dim3((n_rows + 15) / 16, a.S), dim3(FR_NTH), smem, a, (hipStream_t)stream, "full_rank_groups", optin))
+    return -1;
+  hipLaunchKernelGGL(k_full_rank_merge<true>, dim3((n_rows + FR_NW - 1) / FR_NW), dim3(FR_NTH), 0, (hipStream_t)stream, a);
+  return adt_check_launch("full_rank_groups(merge)");
+}
+
+int adt_full_rank_stats(const int32_t* rank, const int32_t* n_elig, int n_rows, int rows_per_group, int kh, int64_t* hist, double* auc,
+                        void* stream) {
+  if (kh < 1 || kh > ADT_FULLSTATS_MAX_KH) return adt_set_error("full_rank_stats: kh=%d outside 1..%d", kh, ADT_FULLSTATS_MAX_KH);
+  if (rows_per_group < 1) return adt_set_error("full_rank_stats: rows_per_group=%d < 1", rows_per_group);
+  if (n_rows < 0 || n_rows % rows_per_group != 0)
+    return adt_set_error("full_rank_stats: n_rows=%d is not a multiple of rows_per_group=%d", n_rows, rows_per_group);
+  if (!rank || !n_elig || !hist || !auc) return adt_set_error("full_rank_stats: NULL rank, n_elig, hist or auc");
+  if (n_rows == 0) return 0;
+  FullStatsArgs a{rank, n_elig, rows_per_group, kh, hist, auc};
+  hipLaunchKernelGGL(k_full_rank_stats, dim3(n_rows / rows_per_group), dim3(ADT_FULLSTATS_NTH), 0, (hipStream_t)stream, a);
+  return adt_check_launch("full_rank_stats");
 }
 
 int adt_full_rank(const float* F, int ldf, const float* E, int lde, const float* bias, int B, int d, int n_items, const int32_t* target,

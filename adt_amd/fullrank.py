@@ -36,6 +36,15 @@ class FullRankMixin:
         indptr, indices = ops.seen_csr(seen, B, E.device)
         return ops.full_rank(F, F.stride(0), E, n_items, _targets(targets, B, E.device), bias, indptr, indices, topk)
 
+    @torch.no_grad()
+    def rank_full_rows(self, log_seqs, targets, seen_off, seen_items, row0=0, topk=0):
+        """rank_full for rows row0 .. row0 + B - 1 of an evaluation set that lives on the device (DeviceEvalData.full_batch): `targets`
+        (int32) and the CSR seen_off (int64) / seen_items (int32) are the RESIDENT tensors of the whole set and are read in place by
+        adt_full_rank_groups (one group); nothing is built on the host or uploaded.  Returns what rank_full returns."""
+        F, E, n_items, bias = self._full_rank_operands(log_seqs)
+        B = F.shape[0]
+        return ops.full_rank_groups(F, F.stride(0), E, n_items, targets, seen_off, seen_items, B, B, row0=row0, bias=bias, k=topk)
+
     def recommend(self, log_seqs, k, seen=None):
         """The k best unseen items of every user: (ids (B, k) int32, scores (B, k)), best first, ties to the smaller id; -1 / -inf where
         fewer than k items are left."""

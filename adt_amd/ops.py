@@ -962,6 +962,72 @@ def full_rank(F, ldf, E, n_items, target=None, bias=None, indptr=None, indices=N
     return rank, n_elig, top_idx, top_val
 
 
+def full_rank_groups(F, ldf, E, n_items, target, seen_off, seen_items, n_rows, rows_per_group, row0=0, bias=None, k=0, splits=0, first_id=1):
+    """full_rank for P stacked candidates of the same users (adt_full_rank_groups): n_rows = P * rows_per_group feature rows (F: any view
+    whose first element is row 0, row stride ldf), group-major -- row r is user u = r % rows_per_group, whose target is target[row0 + u]
+    and whose seen list is row row0 + u of the RESIDENT CSR seen_off (int64, one entry more than the rows) / seen_items (int32), e.g.
+    DeviceEvalData's, taken as it is: a batch is named by row0.  target None ranks nothing (top-k only); seen_off and seen_items both None
+    means nothing seen.  Returns full_rank's (rank, n_elig, top_idx, top_val), each with n_rows rows."""
+    n_rows, rpg, row0 = int(n_rows), int(rows_per_group), int(row0)
+    if target is not None and (target.dtype != torch.int32 or not target.is_contiguous()):
+        raise _lib.AdtError("full_rank_groups: target must be a contiguous int32 tensor")
+    if (seen_off is None) != (seen_items is None):
+        raise _lib.AdtError("full_rank_groups: seen_off and seen_items go together")
+    if seen_off is not None and (seen_off.dtype != torch.int64 or not seen_off.is_contiguous() or seen_items.dtype != torch.int32 or not seen_items.is_contiguous()):
+        raise _lib.AdtError("full_rank_groups: seen_off must be contiguous int64 and seen_items contiguous int32")
+    # the rows the resident lists cover: what the kernel may index with row0 + u
+    n_total = seen_off.numel() - 1 if seen_off is not None else (target.numel() if target is not None else row0 + max(rpg, 0))
+    if target is not None and target.numel() < n_total:
+        raise _lib.AdtError("full_rank_groups: %d targets for the %d rows of seen_off" % (target.numel(), n_total))
+    if rpg < 1 or n_rows % rpg != 0:
+        raise _lib.AdtError("full_rank_groups: %d rows, rows_per_group=%d" % (n_rows, rpg))
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous() or bias.numel() < n_items + 1):
+        raise _lib.AdtError("full_rank_groups: bias must be contiguous fp32 with at least n_items + 1 = %d entries" % (n_items + 1))
+    if E.shape[0] < n_items + 1:
+        raise _lib.AdtError("full_rank_groups: the item table has %d rows, n_items + 1 = %d are read" % (E.shape[0], n_items + 1))
+    d, lde = E.shape[1], E.stride(0)
+    dev = E.device
+    lib = _lib.load()
+    ws = torch.empty(max(int(lib.adt_full_rank_ws_bytes(n_rows, int(n_items), int(k), int(splits))), 16), device=dev, dtype=torch.uint8)
+    rank = torch.empty(n_rows, device=dev, dtype=torch.int32)
+    n_elig = torch.empty(n_rows, device=dev, dtype=torch.int32)
+    top_idx = torch.empty(n_rows, k, device=dev, dtype=torch.int32) if k > 0 else None
+    top_val = torch.empty(n_rows, k, device=dev, dtype=torch.float32) if k > 0 else None
+    _lib.check(lib.adt_full_rank_groups(_p(_f32(F)), int(ldf), _p(_f32(E)), lde, _p(bias), n_rows, rpg, d, int(n_items), int(first_id), _p(target),
+                                        _p(seen_off), _p(seen_items), int(n_total), row0, int(k), int(splits), _p(ws), ws.numel(), _p(rank),
+                                        _p(n_elig), _p(top_idx), _p(top_val), _stream()), "full_rank_groups")
+    return rank, n_elig, top_idx, top_val
+
+
+FULLSTATS_MAX_KH = 1024
+
+
+def full_rank_stats(rank, n_elig, rows_per_group, kh, hist=None, auc=None):
+    """The additive statistics of full-catalogue ranks, counted on the device (adt_full_rank_stats): rank / n_elig (N,) int32 as
+    full_rank / full_rank_groups return them, group-major.  For every row of group g with rank >= 0: hist[g][min(rank, kh)] += 1 and
+    auc[g] += (n_elig - rank) / max(n_elig, 1).  Returns (hist (groups, kh + 1) int64, auc (groups,) float64): new zeros where an
+    output is None, otherwise the tensor given, accumulated into.  The float64 sum has a fixed order: two runs give the same bits."""
+    if rank.dtype != torch.int32 or n_elig.dtype != torch.int32 or not rank.is_contiguous() or not n_elig.is_contiguous() or rank.numel() != n_elig.numel():
+        raise _lib.AdtError("full_rank_stats: rank and n_elig must be contiguous int32 tensors of one length")
+    N, rpg, kh = rank.numel(), int(rows_per_group), int(kh)
+    if rpg < 1 or N % rpg != 0:
+        raise _lib.AdtError("full_rank_stats: %d rows, rows_per_group=%d" % (N, rpg))
+    if not 1 <= kh <= FULLSTATS_MAX_KH:
+        raise _lib.AdtError("full_rank_stats: kh=%d outside 1..%d" % (kh, FULLSTATS_MAX_KH))
+    groups = N // rpg
+    if hist is None:
+        hist = torch.zeros(groups, kh + 1, device=rank.device, dtype=torch.int64)
+    elif hist.dtype != torch.int64 or not hist.is_contiguous() or hist.numel() != groups * (kh + 1):
+        raise _lib.AdtError("full_rank_stats: hist must be contiguous int64 with %d x %d entries" % (groups, kh + 1))
+    if auc is None:
+        auc = torch.zeros(groups, device=rank.device, dtype=torch.float64)
+    elif auc.dtype != torch.float64 or not auc.is_contiguous() or auc.numel() != groups:
+        raise _lib.AdtError("full_rank_stats: auc must be contiguous float64 with %d entries" % groups)
+    if N > 0:      # an empty tensor has no address to hand over
+        _lib.check(_lib.load().adt_full_rank_stats(_p(rank), _p(n_elig), N, rpg, kh, _p(hist), _p(auc), _stream()), "full_rank_stats")
+    return hist, auc
+
+
 def wdist_pack(M, C, elu, nrm_scale):
     """Row images for Wasserstein full-catalogue ranking (adt_wdist_pack): img (rows, 2d) = [M | sqrt(max(c, 1e-24))] and
     nrm (rows,) = nrm_scale * (sum M^2 + sum c), c = ELU(C) + 1 when elu else C.  Items: (True, -0.5) -> (W, bias) of full_rank; user

@@ -119,6 +119,12 @@ class DeviceEvalData:
             raise _lib.AdtError("DeviceEvalData: no candidates yet (draw() or from_dataset())")
         return self.sequences(lo, hi), self.cand[lo:hi]
 
+    def full_batch(self, lo, hi):
+        """What the full-catalogue evaluation of rows lo:hi reads (ops.full_rank_groups): (seq (hi - lo, L), targets, seen_off, seen_items,
+        row0 = lo).  The last four name the RESIDENT tensors of the whole set -- the kernel finds the rows from row0 --, so nothing is
+        sliced or re-based, and no candidate table is needed: a set that was never drawn serves this."""
+        return self.sequences(lo, hi), self.targets, self.seen_off, self.seen_items, lo
+
     def batches(self, batch_size):
         for lo in range(0, len(self.users), batch_size):
             yield lo, min(lo + batch_size, len(self.users))

@@ -58,9 +58,18 @@ def parse_args(argv=None):
     p.add_argument("--device_negatives", default="false", choices=["true", "false"],
                    help="draw the validation candidates on the device, once (adt_evalcand_draw; implies --device_eval).  Same distribution "
                         "as the reference's sampler, but a hash stream of its own: such a search is NOT the numpy run's trajectory")
+    p.add_argument("--eval_full", default="false", choices=["true", "false"],
+                   help="score every candidate on the WHOLE catalogue instead of 1 + --sample_size sampled items: the validation set stays in "
+                        "HBM and every chunk of candidates is one adt_full_rank_groups call per batch (one histogram and one sum per "
+                        "candidate read per evaluate_candidates call)")
+    p.add_argument("--select_by", default="auc", choices=["auc", "ndcg"],
+                   help="the validation metric the search sorts by; ndcg (NDCG@10 on the whole catalogue) needs --eval_full true")
     args = p.parse_args(argv)
     args.device_negatives = args.device_negatives == "true"
     args.device_eval = args.device_eval == "true" or args.device_negatives
+    args.eval_full = args.eval_full == "true"
+    if args.select_by == "ndcg" and not args.eval_full:
+        p.error("--select_by ndcg sorts by the full-catalogue NDCG@10: pass --eval_full true")
     return args
 
 
@@ -80,6 +89,7 @@ class SearcherEvolution:
         sampler = U.PopularSampler(user_train, user_valid, user_test, usernum, itemnum, args.sample_size)
         self.warp = U.WarpDataset(user_train, usernum, itemnum, args.maxlen)
         dev_neg, dev_eval = getattr(args, "device_negatives", False), getattr(args, "device_eval", False)
+        self.eval_full = getattr(args, "eval_full", False)
         self.val_ds = U.EvalDataset(user_train, user_valid, user_test, usernum, itemnum, args.maxlen, sampler, "val", args.eval_set, not dev_neg)
         self.test_ds = U.EvalDataset(user_train, user_valid, user_test, usernum, itemnum, args.maxlen, sampler, "test", args.eval_set, not dev_neg)
         self.val_dev = None
@@ -88,13 +98,17 @@ class SearcherEvolution:
             self.val_dev = DeviceEvalData.from_dataset(self.val_ds, args.device, upload=not dev_neg)
             if dev_neg:
                 self.val_dev.draw(23, 0)
+        elif self.eval_full:         # the full-catalogue scores read no candidates: nothing to upload or draw
+            from .device_eval import DeviceEvalData
+            self.val_dev = DeviceEvalData.from_dataset(self.val_ds, args.device, upload=False)
         # search space (sasrec/evolution.py:93-98)
         self.rec_choice = [0, 0.0001, 0.0005, 0.001, 0.005, 0.01]
         self.ind_choice = [0, 0.0001, 0.0005, 0.001, 0.0015, 0.002]
         torch.manual_seed(args.seed)
         self.model = SuperSASRecModel(usernum, itemnum, self.rec_choice, self.ind_choice, args, allow_lanes=True)
         self.trainer = SuperTrainer(self.model, lr=args.lr, betas=(0.9, 0.999), weight_decay=args.weight_decay, clip=args.clip, seed=args.seed)
-        self.search_state = EvolutionSearch(args.num_layers, self.evaluate_candidates, "auc", args.select_num, args.population_num, args.m_prob,
+        score_key = "V_NDCG" if getattr(args, "select_by", "auc") == "ndcg" else "auc"
+        self.search_state = EvolutionSearch(args.num_layers, self.evaluate_candidates, score_key, args.select_num, args.population_num, args.m_prob,
                                             args.crossover_num, args.mutation_num, args.scale_factor)
         self.rng = np.random.RandomState(args.seed)
         self.eval_stats = {}
@@ -107,6 +121,8 @@ class SearcherEvolution:
         """Validation metrics of the supernet under every candidate of `cands` (get_cand_auc :173-180, for a whole chunk): each
         validation batch is scored for `group` candidates per pass."""
         shared = [get_shared(self.rec_choice, self.ind_choice, cand_to_block(self.rec_choice, self.ind_choice, c)[0]) for c in cands]
+        if dataset is None and self.eval_full:
+            return self._evaluate_candidates_full(shared, group)
         if dataset is None and self.val_dev is not None:
             return self._evaluate_candidates_device(shared, group)
         ds = self.val_ds if dataset is None else dataset
@@ -139,6 +155,24 @@ class SearcherEvolution:
         for h in hist.cpu().numpy():
             (ndcg, hr), auc = U.metrics_from_hist(h, C, [10])
             out.append({"V_NDCG": float(ndcg[10]), "V_HR": float(hr[10]), "V_AUC": float(auc), "auc": float(auc)})
+        return out
+
+    def _evaluate_candidates_full(self, shared, group, kh=10):
+        """evaluate_candidates on the WHOLE catalogue (--eval_full true): every batch of the resident validation set is built once and ranked
+        for `group` candidates per pass (SuperSASRecModel.rank_full_stats_candidates); one (candidates, kh + 1) int64 histogram and one
+        float64 sum per candidate are the only read-back.  The same keys as the sampled paths, from the full-catalogue numbers."""
+        data = self.val_dev
+        hist = torch.zeros(len(shared), kh + 1, device=data.device, dtype=torch.int64)
+        auc = torch.zeros(len(shared), device=data.device, dtype=torch.float64)
+        for lo, hi in data.batches(self.args.eval_batch_size):
+            seq, *full = data.full_batch(lo, hi)
+            for g0 in range(0, len(shared), group):
+                self.model.rank_full_stats_candidates(seq, full, shared[g0:g0 + group], hist[g0:g0 + group], auc[g0:g0 + group], kh,
+                                                      stats=self.eval_stats)
+        out = []
+        for h, a in zip(hist.cpu().numpy(), auc.cpu().numpy()):
+            (ndcg, hr), a = U.full_metrics_from_hist(h, a, [kh])
+            out.append({"V_NDCG": float(ndcg[kh]), "V_HR": float(hr[kh]), "V_AUC": float(a), "auc": float(a)})
         return out
 
     def _train_warmup(self):

@@ -72,9 +72,14 @@ def parse_args(argv=None):
                    help="draw the evaluation candidates on the device (adt_evalcand_draw; implies --device_eval): once at start-up, or at "
                         "every evaluation with --frozen_eval false.  Same distribution as the reference's sampler, but a hash stream of "
                         "its own: such a run is NOT the numpy run's trajectory")
+    p.add_argument("--device_eval_full", default=False, type=str2bool,
+                   help="run the full-catalogue evaluation on the evaluation data kept in HBM (implies --eval_full): adt_full_rank_groups on "
+                        "the resident targets and seen rows, one histogram and one float64 sum read per evaluation")
     args = p.parse_args(argv)
     if args.device_negatives:
         args.device_eval = True
+    if args.device_eval_full:
+        args.eval_full = True
     if args.device_eval and not args.device_negatives and not args.frozen_eval:
         p.error("--device_eval uploads the frozen candidate sets: pass --frozen_eval true, or --device_negatives true to redraw on the device")
     if not args.no_template:
@@ -135,6 +140,10 @@ def main(argv=None):
         if args.device_negatives and args.frozen_eval:      # one draw for the whole run; seeds 23 / 24 keep the two sets apart
             val_dev.draw(23, 0)
             test_dev.draw(24, 0)
+    elif args.device_eval_full:      # the full-catalogue evaluation reads no candidates: nothing to upload or draw
+        from .device_eval import DeviceEvalData
+        val_dev = DeviceEvalData.from_dataset(val_ds, args.device, upload=False)
+        test_dev = DeviceEvalData.from_dataset(test_ds, args.device, upload=False)
 
     # the fused executor is 64-wide and stops at maxlen 224; other widths (the d = 256 template, the default 50) and longer sequences take the general kernels
     wide = args.hidden_units != 64 or args.maxlen > 224
@@ -230,8 +239,12 @@ def main(argv=None):
                 t_test, auc_test = U.evaluate_loader(model, test_ds.batches(args.eval_batch_size), args, "test", ks, process_group=pg)
                 t_valid, auc_valid = U.evaluate_loader(model, val_ds.batches(args.eval_batch_size), args, "val", ks, process_group=pg)
             if args.eval_full:     # the held-out item against ALL unseen items (adt_full_rank), beside the sampled-negative metrics
-                f_test, _ = U.evaluate_full(model, test_ds, "test", ks, args.eval_batch_size, process_group=pg)
-                f_valid, _ = U.evaluate_full(model, val_ds, "val", ks, args.eval_batch_size, process_group=pg)
+                if args.device_eval_full:
+                    f_test, _ = U.evaluate_full_device(model, test_dev, ks, args.eval_batch_size, process_group=pg)
+                    f_valid, _ = U.evaluate_full_device(model, val_dev, ks, args.eval_batch_size, process_group=pg)
+                else:
+                    f_test, _ = U.evaluate_full(model, test_ds, "test", ks, args.eval_batch_size, process_group=pg)
+                    f_valid, _ = U.evaluate_full(model, val_ds, "val", ks, args.eval_batch_size, process_group=pg)
                 for k in ks if rank == 0 else ():
                     print("epoch: %d, full catalogue: valid (NDCG@%d: %.4f, HR@%d: %.4f), test (NDCG@%d: %.4f, HR@%d: %.4f)"
                           % (epoch + 1, k, f_valid[0][k], k, f_valid[1][k], k, f_test[0][k], k, f_test[1][k]))

@@ -561,6 +561,20 @@ class SuperSASRecModel(FlatModule):
         F, B, L = self._candidate_feature_rows(log_seqs, shared_list, stats)
         return ops.cand_rank_hist(F[L - 1:], L * self.dp, self.P("item_emb.weight"), cand, len(shared_list) * B, B, hist=hist)
 
+    @torch.no_grad()
+    def rank_full_stats_candidates(self, log_seqs, full_batch, shared_list, hist, auc, kh, stats=None, want_rank=False):
+        """rank_hist_candidates against the WHOLE catalogue: the same feature pass, then one adt_full_rank_groups call on the P * B stacked
+        last-position rows with rows_per_group = B -- full_batch = (targets, seen_off, seen_items, row0) names the batch's rows of the
+        resident evaluation set (DeviceEvalData.full_batch()[1:]), read by every group in place -- and adt_full_rank_stats into
+        hist (P, kh + 1) int64 and auc (P,) float64 (accumulated; returned).  want_rank (tests): also the (P, B) int32 ranks."""
+        F, B, L = self._candidate_feature_rows(log_seqs, shared_list, stats)
+        targets, seen_off, seen_items, row0 = full_batch
+        P = len(shared_list)
+        rank, n_elig, _, _ = ops.full_rank_groups(F[L - 1:], L * self.dp, self.P("item_emb.weight"), self.itemnum, targets, seen_off, seen_items,
+                                                  P * B, B, row0=row0)
+        out = ops.full_rank_stats(rank, n_elig, B, kh, hist=hist, auc=auc)
+        return out + (rank.view(P, B),) if want_rank else out
+
     def predict_rank(self, log_seqs, item_indices, want_rank=True):
         """(scores, rank of column 0) -- the interface adt_amd.sasrec.utils.evaluate_loader drives."""
         return self.predict(None, log_seqs, item_indices, full=item_indices is None, want_rank=True)

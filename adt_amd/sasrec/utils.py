@@ -462,3 +462,59 @@ def evaluate_full(model, dataset, mode=None, ks=(5, 10), batch_size=512, process
     ranks = np.concatenate(ranks) if ranks else np.zeros(0, np.int64)
     nel = np.concatenate(nel) if nel else np.zeros(0, np.int64)
     return metrics_from_stats(reduce_rank_stats(full_rank_stats(ranks, nel, ks), process_group), ks)
+
+
+# ---- full-catalogue evaluation kept on the device (adt_full_rank_groups + adt_full_rank_stats) --------------------
+def full_metrics_from_hist(hist_row, auc_sum, ks=(5, 10)):
+    """metrics_from_stats(full_rank_stats(...)) from what adt_full_rank_stats counts, in float64: hist_row[j] = users whose held-out item
+    has rank j (the last bin, kh, collects every rank >= kh), auc_sum = sum of (n_elig - rank) / max(n_elig, 1).  N = hist_row.sum(),
+    HR@k = sum(hist_row[:k]) / N, NDCG@k = sum(hist_row[j] / log2(j + 2), j < k) / N, AUC = auc_sum / N.  HR is equal exactly; NDCG
+    differs from the per-user sum by the order of addition only.  k > kh cannot be answered from the clipped histogram: an error."""
+    hist = np.asarray(hist_row, np.int64).reshape(-1)
+    kh = len(hist) - 1
+    if max(ks) > kh:
+        raise ValueError("full_metrics_from_hist: k=%d above kh=%d, the last rank the histogram resolves" % (max(ks), kh))
+    j = np.arange(len(hist), dtype=np.int64)
+    n = float(hist.sum())
+    ndcg, hr = {}, {}
+    for k in ks:
+        hr[k] = float(hist[:k].sum()) / n
+        ndcg[k] = float((hist[:k] / np.log2(j[:k] + 2.0)).sum()) / n
+    return (ndcg, hr), float(auc_sum) / n
+
+
+def evaluate_full_device(model, data, ks=(5, 10), batch_size=512, process_group=None, want_ranks=False):
+    """evaluate_full over a DeviceEvalData -> ((NDCG, HT), AUC): every batch is built on the device (data.full_batch), encoded by the
+    model's own evaluation pass (_full_rank_operands), ranked against the whole catalogue by adt_full_rank_groups on the resident
+    targets and seen rows, and counted by adt_full_rank_stats into one (1, max(ks) + 1) int64 histogram and one float64 sum; those
+    are the only device-to-host copies, read once at the end.  With a process group, rank r takes batches r, r + W, ... as
+    evaluate_device does and both are sum-reduced.  want_ranks (tests): also the int32 ranks of this process's rows, in row order, still
+    on the device."""
+    import torch
+    from .. import ops
+    r, W = 0, 1
+    if process_group is not None:
+        import torch.distributed as dist
+        r, W = dist.get_rank(process_group), dist.get_world_size(process_group)
+    kh = max(ks)
+    hist = torch.zeros(1, kh + 1, device=data.device, dtype=torch.int64)
+    auc = torch.zeros(1, device=data.device, dtype=torch.float64)
+    ranks = []
+    for i, (lo, hi) in enumerate(data.batches(batch_size)):
+        if i % W != r:
+            continue
+        seq, targets, seen_off, seen_items, row0 = data.full_batch(lo, hi)
+        rank, n_elig, _, _ = model.rank_full_rows(seq, targets, seen_off, seen_items, row0)
+        ops.full_rank_stats(rank, n_elig, hi - lo, kh, hist=hist, auc=auc)
+        if want_ranks:
+            ranks.append(rank)
+    if W > 1:
+        import torch.distributed as dist
+        if dist.get_backend(process_group) != "nccl":
+            hist, auc = hist.cpu(), auc.cpu()
+        dist.all_reduce(hist, group=process_group)
+        dist.all_reduce(auc, group=process_group)
+    res = full_metrics_from_hist(hist.cpu().numpy()[0], float(auc.cpu().numpy()[0]), ks)
+    if want_ranks:
+        return res, (torch.cat(ranks) if ranks else torch.zeros(0, device=data.device, dtype=torch.int32))
+    return res

@@ -342,6 +342,28 @@ int adt_full_rank(const float* F, int ldf, const float* E, int lde, const float*
 int adt_full_rank_from(const float* F, int ldf, const float* E, int lde, const float* bias, int B, int d, int n_items, int first_id,
                        const int32_t* target, const int32_t* indptr, const int32_t* indices, int K, int splits, void* ws,
                        int64_t ws_bytes, int32_t* rank, int32_t* n_elig, int32_t* top_idx, float* top_val, void* stream);
+/* adt_full_rank_from for P stacked candidates of the same users: n_rows = P * rows_per_group feature rows,
+ * group-major -- row r is user u = r % rows_per_group of group r / rows_per_group.  Its target is target[row0 + u] and its seen list is
+ * row row0 + u of a RESIDENT CSR over n_total rows with int64 offsets (seen_off, n_total + 1 entries) and int32 items (seen_items), so a
+ * batch of an evaluation set is named by row0 alone: nothing is sliced or re-based.  Everything else is adt_full_rank_from's contract
+ * (eligibility, strict rank, n_elig without the target, K = 0 .. 128 with ties to the smaller id, no output depends on splits); the rows
+ * of a 16-row tile may belong to two groups.  rows_per_group = n_rows and row0 = 0 give adt_full_rank_from's outputs bit for bit.
+ * ws: adt_full_rank_ws_bytes(n_rows, n_items, K, splits).  target may be NULL (no ranks), seen_off and seen_items both NULL (nothing seen).
+ * Errors, before any launch: those of adt_full_rank_from, rows_per_group < 1, n_rows % rows_per_group != 0, row0 < 0,
+ * row0 + rows_per_group > n_total, one of seen_off / seen_items without the other. */
+int adt_full_rank_groups(const float* F, int ldf, const float* E, int lde, const float* bias, int n_rows, int rows_per_group, int d,
+                         int n_items, int first_id, const int32_t* target, const int64_t* seen_off, const int32_t* seen_items, int n_total,
+                         int row0, int K, int splits, void* ws, int64_t ws_bytes, int32_t* rank, int32_t* n_elig, int32_t* top_idx,
+                         float* top_val, void* stream);
+/* The additive statistics of full-catalogue ranks, per group (adt_fullstats.cuh): rank / n_elig as the calls above write them, n_rows
+ * rows, group-major.  For every row r of group g with rank[r] >= 0 (a row without a target counts nowhere):
+ *   hist[g][min(rank[r], kh)] += 1                                with hist (n_rows / rows_per_group, kh + 1) contiguous int64
+ *   auc[g] += sum_r (n_elig[r] - rank[r]) / max(n_elig[r], 1)     with auc (n_rows / rows_per_group,) float64
+ * Both are ACCUMULATED into: the caller supplies the zeros.  One workgroup per group, the rows of a thread in ascending order, a fixed
+ * reduction tree and a single writer per word: the float64 sum is bit-reproducible, and no atomic touches HBM.
+ * Errors: kh outside 1..1024, rows_per_group < 1, n_rows % rows_per_group != 0, a NULL pointer. */
+int adt_full_rank_stats(const int32_t* rank, const int32_t* n_elig, int n_rows, int rows_per_group, int kh, int64_t* hist, double* auc,
+                        void* stream);
 /* Row images for Wasserstein full-catalogue ranking (adt_wdist_pack.cuh): dist[b][j] = na[b] + nb[j] - 2 A[b] . W[j] with the 2d-wide
  * rows A[b] = [sm | sqrt sc], W[j] = [em | sqrt ec], so ascending distance is descending A[b] . W[j] - nb[j] / 2 = adt_full_rank's score.
  * Per row r: img[r][0..d) = M[r], img[r][d..2d) = sqrt(max(c, 1e-24)), nrm[r] = nrm_scale * (sum M[r]^2 + sum c), with

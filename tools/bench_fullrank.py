@@ -26,7 +26,14 @@ all of them alike; 3 warm-up rounds, 5 timed ones.
 STOSA-ADT (KL) ranked by the ROW-WISE divergence at the same shape (K 40, 100 seen items per user, first_id = 0), P = 1 and 8, the same
 inputs and the same alternating scheme: (a) rowwise = the user-state pack (adt_klrow_pack, items = 0) + adt_full_rank_from on a
 pre-packed image, (b) pack = the item pack alone (items = 1), (c) matrix = adt_kldist_full_groups + adt_topk_masked, for context only:
-it ranks by kl_predict_full's batch-dependent score, a different function."""
+it ranks by kl_predict_full's batch-dependent score, a different function.
+
+  python tools/bench_fullrank.py --groups [--out profiles/r31_full_eval_device.jsonl]
+
+The group-aware call at the two dot-product shapes, R = 512 users, P = 8 and P = 32 stacked candidates, K 0 (the
+search reads ranks only): (a) groups = ONE adt_full_rank_groups call on the P * R rows and the resident int64 CSR of the R users,
+(b) loop = P adt_full_rank calls, one per candidate, on the int32 CSR.  The same alternating scheme; the two forms' ranks are compared
+bit for bit first.  One JSON line per (shape, P)."""
 import argparse
 import json
 import os
@@ -137,6 +144,38 @@ def stosa_kl_rowwise_lines(dev):
     return lines
 
 
+def groups_lines(dev):
+    R, lines = B, []
+    for name, V, d in SHAPES:
+        for P in (8, 32):
+            g = torch.Generator(device="cpu").manual_seed(V + P)
+            F = torch.randn(P * R, d, generator=g).to(dev)
+            E = torch.randn(V + 1, d, generator=g).to(dev)
+            r = np.random.RandomState(V)
+            target = torch.from_numpy(r.randint(1, V + 1, R).astype(np.int32)).to(dev)
+            indptr = torch.arange(0, (R + 1) * SEEN, SEEN, dtype=torch.int32, device=dev)
+            indices = torch.from_numpy(r.randint(1, V + 1, R * SEEN).astype(np.int32)).to(dev)
+            off = indptr.long()
+
+            def groups():
+                return ops.full_rank_groups(F, d, E, V, target, off, indices, P * R, R)
+
+            def loop():
+                return [ops.full_rank(F[p * R:(p + 1) * R], d, E, V, target, None, indptr, indices, 0) for p in range(P)]
+
+            a, b = groups(), loop()
+            same = all(torch.equal(a[i], torch.cat([x[i] for x in b])) for i in (0, 1))
+            del a, b
+            rec = {"shape": name, "V": V, "d": d, "R": R, "candidates": P, "K": 0, "seen_per_user": SEEN, "bit_equal": bool(same)}
+            rec.update(timed_alternating({"loop": loop, "groups": groups}))
+            rec["groups_over_loop"] = rec["groups"]["median_ms"] / rec["loop"]["median_ms"]
+            spread = max(rec[k]["max_ms"] - rec[k]["min_ms"] for k in ("loop", "groups"))
+            rec["accepted"] = bool(rec["groups"]["median_ms"] <= rec["loop"]["median_ms"] + spread)      # not above the loop by more than the larger spread
+            print(json.dumps(rec), flush=True)
+            lines.append(json.dumps(rec))
+    return lines
+
+
 def stosa_lines(dev):
     V, d, K = 12103, 64, 40
     lines = []
@@ -178,8 +217,11 @@ def main():
     ap.add_argument("--stosa", action="store_true", help="the STOSA-ADT (Wasserstein) Beauty shape instead of the dot-product shapes")
     ap.add_argument("--metric", default="wasserstein", choices=["wasserstein", "kl"], help="with --stosa: kl = the grouped KL full sort against P adt_kldist_full calls")
     ap.add_argument("--rowwise", action="store_true", help="with --stosa --metric kl: the ranking by the row-wise KL divergence (adt_klrow_pack + adt_full_rank_from)")
+    ap.add_argument("--groups", action="store_true", help="one adt_full_rank_groups call against P adt_full_rank calls at the dot-product shapes")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.groups and (args.stosa or args.metric == "kl" or args.rowwise):
+        ap.error("--groups runs alone")
     kl = args.stosa and args.metric == "kl"
     if args.metric == "kl" and not args.stosa:
         ap.error("--metric kl goes with --stosa")
@@ -187,10 +229,11 @@ def main():
         ap.error("--rowwise goes with --stosa --metric kl")
     if args.out is None:
         args.out = os.path.join("profiles", "r20_stosa_kl_rowwise.jsonl" if args.rowwise else "r18_stosa_kl_full.jsonl" if kl else
-                                "r08_stosa_fullrank.jsonl" if args.stosa else "r07_fullrank_bench.jsonl")
+                                "r08_stosa_fullrank.jsonl" if args.stosa else "r31_full_eval_device.jsonl" if args.groups else "r07_fullrank_bench.jsonl")
     dev = "cuda:0"
-    lines = stosa_kl_rowwise_lines(dev) if args.rowwise else stosa_kl_lines(dev) if kl else stosa_lines(dev) if args.stosa else []
-    for name, V, d in (() if args.stosa else SHAPES):
+    lines = stosa_kl_rowwise_lines(dev) if args.rowwise else stosa_kl_lines(dev) if kl else stosa_lines(dev) if args.stosa else \
+        groups_lines(dev) if args.groups else []
+    for name, V, d in (() if args.stosa or args.groups else SHAPES):
         g = torch.Generator(device="cpu").manual_seed(V)
         F = torch.randn(B, d, generator=g).to(dev)
         E = torch.randn(V + 1, d, generator=g).to(dev)
